@@ -10,6 +10,13 @@ DAC decode to a 44.1 kHz waveform, with features / weights already resident in H
 Workload (BASELINE.json configs[1]): 8 clips per GPU of 2.56 s (T=220 frames, 9 codebooks),
 top-k 250, temperature 1.0, cfg_scale 6.0 (the reference's default, configs/generate_vgg.yaml:27).
 Prints ONE JSON line on rank 0.
+
+A plain run sets up, warms up, times the K steps and prints the line (`value`, `ms_per_step`, the split of the timed steps).
+--full adds everything else the line can carry, each with runs of its own: the bf16-representable checkpoint and the exact-fp32
+engine on the same job, per-kernel figures, the plugin surface, raw frames -> waveform, the other BASELINE configs and the CPU
+baseline (the --no-* options below switch single legs of it off).
+--dump-outputs DIR writes what the LAST timed step returned, as float32 .npy files: DIR/codes.npy (tokens, clips x 9 x T) and
+DIR/waveform.npy (clips x 1 x samples); the inputs are seeded, so the same arguments give the same inputs on every run.
 """
 from __future__ import annotations
 
@@ -33,6 +40,22 @@ from vaura_amd.engine import CodecEngine, DecoderEngine  # noqa: E402
 HBM_PEAK_GBS = 8000.0           # MI355X_MICROARCH.md: 8.0 TB/s spec
 T_FRAMES, K_CB, TV = 220, 9, 32
 HOP = 512
+DUMP_CAP_BYTES = 60_000_000      # --dump-outputs: array data in all (under 64 MB with the .npy headers)
+
+
+def dump_outputs(dirname: str, arrays) -> None:
+    """name -> tensor, written as DIR/<name>.npy in float32 (token ids < 1024 are exact there).  An array that would take the total
+    past DUMP_CAP_BYTES is replaced by a fixed, seeded sample of its elements (flattened, in index order)."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    left = DUMP_CAP_BYTES
+    for name, t in arrays.items():
+        a = t.detach().to("cpu", torch.float32).numpy()
+        if a.nbytes > left:
+            idx = np.sort(np.random.default_rng(0).choice(a.size, left // a.itemsize, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(dirname, f"{name}.npy"), a)
+        left -= a.nbytes
 
 
 def algorithmic_bytes_per_launch(kind: str, cfg: synth.SamplerCfg, wbytes: int, rows: int) -> float:
@@ -364,6 +387,11 @@ def main():
     ap.add_argument("--no-extras", action="store_true")
     ap.add_argument("--no-extra-configs", action="store_true",
                     help="skip the short timed regions of the other BASELINE configs (extra_configs: c4, rows32_h2, fp8h_kv16_mx8_rows32, longform)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beyond the headline (second checkpoint, exact fp32, per-kernel figures, plugin surface, "
+                         "extractor, other BASELINE configs, CPU baseline); a plain run times the headline only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's tokens and waveform to DIR/codes.npy and DIR/waveform.npy (float32)")
     args = ap.parse_args()
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -420,6 +448,7 @@ def main():
     s_post = torch.cuda.Stream(dev) if args.overlap else s_loop
 
     marks = []      # (start, loop done, codec done) events of every step: the split of the TIMED steps themselves
+    gathered = []   # N > 1: the whole node's (codes, waveform) of the latest step, what rank 0's caller receives
 
     def step():
         with torch.cuda.stream(s_loop):
@@ -436,8 +465,7 @@ def main():
             e_c.record(s_post)
             marks.append((e_a, done, e_c))
             if world > 1:  # the single exchange of the job: final gather of tokens + waveform over RCCL
-                vdist.gather_clips(codes.to(torch.int32), counts)
-                vdist.gather_clips(wav, counts)
+                gathered[:] = [vdist.gather_clips(codes.to(torch.int32), counts), vdist.gather_clips(wav, counts)]
         return codes, wav
 
     def timed(fn):
@@ -472,6 +500,9 @@ def main():
 
     assert codes.shape == (B, K_CB, T_FRAMES) and int(codes.min()) >= 0 and int(codes.max()) < 1024
     assert wav.shape == (B, 1, T_FRAMES * HOP) and bool(torch.isfinite(wav).all())
+    if args.dump_outputs and rank == 0:
+        dump_codes, dump_wav = gathered if world > 1 else (codes, wav)
+        dump_outputs(args.dump_outputs, {"codes": dump_codes, "waveform": dump_wav})
 
     tokens = world * B * K_CB * T_FRAMES * args.steps
     rows = 2 * B if args.cfg_scale > 1 else B
@@ -529,7 +560,7 @@ def main():
 
     # ---- the same job on the bf16-representable checkpoint, where "auto" resolves to ONE fp16 plane (half the weight bytes,
     #      same real numbers).  Every rank runs it (same barriers).
-    if not args.no_extras and args.weights == "auto" and args.checkpoint == "raw" and not args.no_second:
+    if args.full and not args.no_extras and args.weights == "auto" and args.checkpoint == "raw" and not args.no_second:
         eng_main = eng
         sd_b = synth.sampler_state_dict(cfg, seed=0, round_bf16=True)
         eng = DecoderEngine(cfg, sd_b, dev, one_launch_mlp=one_launch)                    # wdtype="auto"
@@ -552,7 +583,7 @@ def main():
 
     # ---- the price of EXACT fp32: the same job, same checkpoint, on the exact-fp32-MFMA engine
     #      (`--weights f32`: fp32 tiles, v_mfma_f32_16x16x4_f32, fp32 activations between kernels) — one more timed region, driver-run
-    if not args.no_extras and args.weights == "auto" and args.checkpoint == "raw" and not args.no_second and not long_ctx:
+    if args.full and not args.no_extras and args.weights == "auto" and args.checkpoint == "raw" and not args.no_second and not long_ctx:
         eng_main = eng
         eng = DecoderEngine(cfg, sd, dev, wdtype="f32", one_launch_mlp=one_launch)
         elx, (codesx, wavx) = timed(step)
@@ -572,10 +603,7 @@ def main():
         eng = eng_main
 
     if rank == 0 and not args.no_extras:
-        # ---- split of the timed steps (HIP events recorded inside them, on the streams the work ran on) + per-kernel roofline
-        torch.cuda.synchronize(dev)
-        torch.cuda.set_stream(s_loop)    # same stream as the timed region; the per-launch events below are recorded on it
-        reps = max(2, args.steps)
+        # ---- split of the timed steps (HIP events recorded inside them, on the streams the work ran on): arithmetic only
         n_steps = T_FRAMES + K_CB - 1
         lb = decode_loop_bytes(cfg, wbytes, rows, n_steps)
         out["split_ms"] = {"decode_loop": round(t_loop, 3), "codec": round(t_codec, 3)}
@@ -590,6 +618,12 @@ def main():
                                  "frac": round(mpp * out["codec_tflops"] / cpeak, 4), "algorithmic_tflops": out["codec_tflops"],
                                  "matrix_instructions_per_product": mpp, "codec_ms": round(t_codec, 3),
                                  "counters": "profiles/r06_codec_mfma.json (tools/mfma_driver under rocprofv3 --pmc; builder: committed record, NOT measured by this run)"}
+
+    if rank == 0 and not args.no_extras and args.full:
+        # ---- per-kernel roofline and the other legs of --full, each with runs of its own
+        torch.cuda.synchronize(dev)
+        torch.cuda.set_stream(s_loop)    # same stream as the timed region; the per-launch events below are recorded on it
+        reps = max(2, args.steps)
 
         # per-kernel, live: every launch of one eager 228-step pass carries its own start/stop events on the stream it is launched on
         # (hipExtLaunchKernelGGL via vaura_profile_loop): the kernel's execution alone.  rocprofv3's kernel trace of the replayed loop

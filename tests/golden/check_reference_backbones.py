@@ -1,6 +1,9 @@
-"""Which Motionformer backbones can the REFERENCE itself run?  (build container only: imports /root/reference)
+"""Which Motionformer backbones can the REFERENCE itself run?  (needs the reference tree: see ref_harness.REFERENCE_ROOT)
 
-    python tests/golden/check_reference_backbones.py
+    python tests/golden/check_reference_backbones.py [--write]
+
+--write records the three outcomes in tests/golden/reference_backbones.json, the fixture that
+tests/test_host_logic.py::test_reference_itself_cannot_run_the_trajectory_or_joint_backbone judges.
 
 The reference picks the backbone config from the checkpoint (motionformer.py:82-114): divided_224_16x4.yaml,
 motionformer_224_16x4.yaml (ATTN_LAYER: trajectory) or joint_224_16x4.yaml.  This script builds the reference's own
@@ -16,6 +19,7 @@ because ``forward_features`` passes ``tok_mask=tok_mask`` to EVERY block (video_
 the reference at all; the divided backbone is the reference's only executable feature extractor, and the only one this build
 provides (vaura_amd/feature_extractor.py).  Exit status 0 when the finding above still holds.
 """
+import json
 import os
 import sys
 
@@ -50,13 +54,23 @@ def run_backbone(name: str) -> str:
         return f"TypeError: {e}"
 
 
+BACKBONES = ("divided_224_16x4.yaml", "motionformer_224_16x4.yaml", "joint_224_16x4.yaml")
+FIXTURE = os.path.join(HERE, "reference_backbones.json")
+
+
 def main() -> int:
-    res = {n: run_backbone(n) for n in ("divided_224_16x4.yaml", "motionformer_224_16x4.yaml", "joint_224_16x4.yaml")}
+    res = {n: run_backbone(n) for n in BACKBONES}
     for k, v in res.items():
         print(f"{k:28s} {v}")
     ok = (res["divided_224_16x4.yaml"].startswith("runs") and "tok_mask" in res["motionformer_224_16x4.yaml"]
           and "tok_mask" in res["joint_224_16x4.yaml"])
     print("finding holds: only the divided backbone is executable in the reference" if ok else "FINDING CHANGED")
+    if "--write" in sys.argv[1:]:
+        with open(FIXTURE, "w") as f:
+            json.dump({"what": "outcome of the reference's own VisionTransformer.forward_features at depth 1 for each backbone YAML "
+                               "(tests/golden/check_reference_backbones.py)", "outcomes": res}, f, indent=1)
+            f.write("\n")
+        print(f"wrote {FIXTURE}")
     return 0 if ok else 1
 
 

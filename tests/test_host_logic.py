@@ -458,18 +458,19 @@ def test_load_from_checkpoint_like_the_reference_driver(tmp_path):
         m.generate(frames=torch.zeros(1, 4, 8, 768), max_new_tokens=4, prompt_is_encoded=True)
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference"), reason="the reference tree exists in the build container only")
 def test_reference_itself_cannot_run_the_trajectory_or_joint_backbone():
     """Row f2 scope: ``VisionTransformer.forward_features`` passes ``tok_mask=`` to every block (video_model_builder.py:266-268);
     only ``DividedSpaceTimeBlock.forward`` accepts it — the trajectory / joint ``Block.forward`` (vit_helper.py:379-390) raises
     TypeError.  So the divided backbone is the only feature extractor the reference can execute, and the only one this build
-    provides (tests/golden/check_reference_backbones.py prints the three outcomes).  Run in a child process: the harness chdirs."""
-    import subprocess
-    import sys
-    script = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "check_reference_backbones.py")
-    r = subprocess.run([sys.executable, script], capture_output=True, text=True, timeout=900)
-    assert r.returncode == 0, r.stdout[-1500:] + r.stderr[-1500:]
-    assert "finding holds" in r.stdout
+    provides.  The three outcomes were recorded by running the reference itself (tests/golden/check_reference_backbones.py --write
+    -> tests/golden/reference_backbones.json); this test judges that record with the script's own rule."""
+    import json
+    with open(os.path.join(REPO, "tests", "golden", "reference_backbones.json")) as f:
+        res = json.load(f)["outcomes"]
+    assert sorted(res) == sorted(["divided_224_16x4.yaml", "motionformer_224_16x4.yaml", "joint_224_16x4.yaml"])
+    assert res["divided_224_16x4.yaml"] == "runs (1, 1569, 768)"
+    for name in ("motionformer_224_16x4.yaml", "joint_224_16x4.yaml"):
+        assert res[name].startswith("TypeError") and "unexpected keyword argument 'tok_mask'" in res[name], res[name]
 
 
 def test_parity_report_helpers_are_strict_and_locate_the_first_difference():

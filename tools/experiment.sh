@@ -25,7 +25,7 @@
 #   prefill-ab                          one later chunk of the sliding-window caller: LDS-DMA prefill GEMM (0) against the register-staged one (131072)
 #   prefill-pmc                         MFMA / LDS / HBM counters of the prefill GEMMs only (the prefill part of tools/profile_round.sh)
 #   sw-prof [flags ..]                  rocprofv3 kernel stats of one later chunk of the sliding-window caller, per debug-flag set
-#   suite                               the whole -m gpu suite, the default bench line, configs[3] / configs[4] / batch-16 bench lines and the
+#   suite                               the whole -m gpu suite, the --full bench line, configs[3] / configs[4] / batch-16 bench lines and the
 #                                       secondary timings (codec, extractor, sliding window, long form)
 set -u
 NAME=${1:-}; shift || true
@@ -181,15 +181,15 @@ sw-prof)
   done ;;
 suite)
   timeout 3000 python3 -m pytest tests -m gpu -q 2>&1 | tail -6 | tee $OUT/gpu_tests.log
-  timeout 1700 python3 bench.py > $OUT/bench_default.json 2> $OUT/bench_default.err; tail -c 300 $OUT/bench_default.err
+  timeout 1700 python3 bench.py --full > $OUT/bench_default.json 2> $OUT/bench_default.err; tail -c 300 $OUT/bench_default.err
   bench_line $OUT/bench_default.json value ms_per_step value_storage value_h1_lossless_checkpoint split_ms decode_loop_roofline \
       decode_loop_roofline_h1_lossless_checkpoint roofline kernel_us kernel_frac_of_hbm_peak codec_roofline plugin_surface end_to_end_with_extractor \
       cpu_baseline gpu_over_cpu | tee $OUT/bench_default.txt
-  timeout 900 python3 bench.py --workload c4 --no-cpu-baseline --no-plugin > $OUT/bench_c4.json 2>/dev/null
+  timeout 900 python3 bench.py --full --workload c4 --no-cpu-baseline --no-plugin > $OUT/bench_c4.json 2>/dev/null
   bench_line $OUT/bench_c4.json value ms_per_step value_h1_lossless_checkpoint decode_loop_roofline | tee $OUT/bench_c4.txt
-  timeout 900 python3 bench.py --weights fp8 --codec mx8 --batch 16 --no-cpu-baseline --no-plugin > $OUT/bench_c5.json 2>/dev/null
+  timeout 900 python3 bench.py --full --weights fp8 --codec mx8 --batch 16 --no-cpu-baseline --no-plugin > $OUT/bench_c5.json 2>/dev/null
   bench_line $OUT/bench_c5.json value ms_per_step split_ms | tee $OUT/bench_c5.txt
-  timeout 900 python3 bench.py --batch 16 --no-cpu-baseline --no-plugin --no-second > $OUT/bench_b16.json 2>/dev/null
+  timeout 900 python3 bench.py --full --batch 16 --no-cpu-baseline --no-plugin --no-second > $OUT/bench_b16.json 2>/dev/null
   bench_line $OUT/bench_b16.json value ms_per_step split_ms | tee $OUT/bench_b16.txt
   { timeout 600 python3 tools/time_codec.py; timeout 600 python3 tools/time_avclip.py; timeout 900 python3 tools/time_sliding_window.py
     timeout 900 python3 tools/bench_longform.py; } 2>&1 | tee $OUT/secondary.log ;;

@@ -26,9 +26,9 @@ MDRV=$ROOT/tools/mfma_driver
 /opt/rocm/bin/hipcc -O2 -std=c++17 --offload-arch=gfx950 $ROOT/tools/mfma_driver.cpp -o $MDRV -ldl || exit 1
 cd /tmp && export TMPDIR=/tmp
 if [ "$PART" != "mfma" ]; then
-rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -- python3 $ROOT/bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-second --no-plugin --no-extra-configs > $OUT/bench_stats.log 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -- python3 $ROOT/bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --no-second --no-plugin --no-extra-configs > $OUT/bench_stats.log 2>&1
 tail -n 1 $OUT/bench_stats.log | cut -c1-300
-rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats_c4 -- python3 $ROOT/bench.py --workload c4 --steps 2 --warmup 1 --no-cpu-baseline --no-second --no-plugin > $OUT/bench_stats_c4.log 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats_c4 -- python3 $ROOT/bench.py --full --workload c4 --steps 2 --warmup 1 --no-cpu-baseline --no-second --no-plugin > $OUT/bench_stats_c4.log 2>&1
 tail -n 1 $OUT/bench_stats_c4.log | cut -c1-200
 # round 6: the counter passes SAMPLE the whole loop — 24 cache lengths 10, 19, ..., 217 (mean 113.5 = the loop's mean) — instead of positions
 # 100..123; all 228 x 76 dispatches under rocprofv3 counters take ~15 min per pass (first attempt: killed at 45 min)

@@ -80,7 +80,7 @@ stats = newest(f"{src}/stats/**/*kernel_stats.csv")
 rows, bench_names = [], set()
 if stats:        # (absent when only the MFMA part of the round ran on this box: tools/profile_round.sh <tag> mfma)
     rows = write_stats(stats, f"{DST}/{tag}_bench_kernel_stats.csv",
-                       "rocprofv3 --kernel-trace --stats -- python3 bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-second --no-plugin --no-extra-configs   (auto -> h2 storage, un-rounded checkpoint)")
+                       "rocprofv3 --kernel-trace --stats -- python3 bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --no-second --no-plugin --no-extra-configs   (auto -> h2 storage, un-rounded checkpoint)")
     bench_names = {clean(r["Name"]) for r in rows}
     log = [l for l in open(f"{src}/bench_stats.log").read().splitlines() if l.startswith("{")]
     open(f"{DST}/{tag}_bench_under_rocprof.json", "w").write((log[-1] if log else "{}") + "\n")
@@ -132,7 +132,7 @@ for w in ("h2", "h1", "h2_rows32", "fp8h_rows32"):
 stats_c4 = newest(f"{src}/stats_c4/**/*kernel_stats.csv")
 if stats_c4:
     crow = write_stats(stats_c4, f"{DST}/{tag}_c4_kernel_stats.csv",
-                       "rocprofv3 --kernel-trace --stats -- python3 bench.py --workload c4 --steps 2 --warmup 1 --no-cpu-baseline --no-second --no-plugin")
+                       "rocprofv3 --kernel-trace --stats -- python3 bench.py --full --workload c4 --steps 2 --warmup 1 --no-cpu-baseline --no-second --no-plugin")
     c4 = {}
     for r in sorted(crow, key=lambda r: -float(r["TotalDurationNs"])):       # per stage: the kernel with the largest total time
         st_ = stage_of(clean(r["Name"]))
