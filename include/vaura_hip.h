@@ -120,7 +120,7 @@ typedef struct vaura_decoder {
   int32_t rows;            /* Bs = B, or 2B when cfg_scale > 1                     */
   int32_t max_len;         /* KV capacity in positions (>= S)                      */
   int32_t timesteps;       /* T  = max_new_tokens                                  */
-  int32_t seq_len;         /* S  = T + n_codebooks                                 */
+  int32_t seq_len;         /* S  = T + max(delay) + 1 (T + n_codebooks for the default pattern) */
   int32_t n_cond_tokens;   /* Tv                                                   */
   int32_t prefill_positions; /* > 0: every ws_* buffer holds this many positions' worth of row blocks, so a
                                 prompt is teacher-forced in chunks of that many positions per pass (bf16 path) */
@@ -184,6 +184,12 @@ typedef struct vaura_decoder {
                                 stream running ahead of its hand-off; words 512 .. 767: arrival counts of the range-split attention (the last split
                                 of a (row, head) merges the partials inside the launch; left at zero).  NULL -> every GEMV, the attention and its
                                 merge are separate launches */
+  /* codebook delay pattern (codebook_patterns.py:374-419: DelayedPatternProvider with any sorted `delays`, ParallelPatternProvider =
+   * all zeros): sequence step s >= 1 of codebook q holds timestep t = s - 1 - d_q, and seq_len = timesteps + max(d) + 1.
+   * has_pattern_delays = 0 (a zero-filled descriptor): d_q = q, the default delayed pattern.  1: pattern_delays[0 .. K-1] hold the
+   * delays — sorted, >= 0, K <= 16 (VAURA_ERR_ARG otherwise).  The sampler's valid-slot fix-up and its near-tie count follow them. */
+  int32_t has_pattern_delays;
+  int32_t pattern_delays[16];
 } vaura_decoder;
 
 /* -------------------------------------------------------------------------------------------
@@ -215,6 +221,13 @@ int vaura_pattern_build(const int32_t* codes, int32_t* seq, int B, int K, int T,
 /* a14 Pattern.revert_pattern_sequence (codebook_patterns.py:260-285) + the [..., :T] slice
  * (vaura_model.py:568-569).  seq (B,K,S) -> codes (B,K,T); positions with no source get `fill`.  */
 int vaura_pattern_revert(const int32_t* seq, int32_t* codes, int B, int K, int T, int S, int fill, vaura_stream_t s);
+/* The same two for any delay pattern (codebook_patterns.py:374-419): delays_host = K ints, sorted, >= 0, K <= 16 (VAURA_ERR_ARG
+ * otherwise).  build: S must be T + max(d) + 1 (VAURA_ERR_SHAPE otherwise); revert: any 0 < S <= T + max(d) + 1.  The two
+ * entry points above are these with d_q = q.                                                     */
+int vaura_pattern_build_delays(const int32_t* codes, int32_t* seq, int B, int K, int T, int S, int special,
+                               const int32_t* delays_host, vaura_stream_t s);
+int vaura_pattern_revert_delays(const int32_t* seq, int32_t* codes, int B, int K, int T, int S, int fill,
+                                const int32_t* delays_host, vaura_stream_t s);
 
 /* -------------------------------------------------------------------------------------------
  * a2/a13/a15  logits (rows, K*vocab) -> next tokens.  Standalone form of the sampler used inside

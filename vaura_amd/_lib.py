@@ -50,7 +50,8 @@ class Decoder(C.Structure):
                 ("ws_h", C.c_void_p), ("ws_qkv", C.c_void_p), ("ws_qkv2", C.c_void_p), ("ws_attn", C.c_void_p), ("ws_ffn", C.c_void_p),
                 ("ws_logits", C.c_void_p),
                 ("ws_h_split", C.c_void_p), ("ws_attn_split", C.c_void_p), ("ws_ffn_split", C.c_void_p),
-                ("ws_ss", C.c_void_p), ("first_norm", C.c_void_p), ("ws_attn_part", C.c_void_p), ("ws_sync", C.c_void_p)]
+                ("ws_ss", C.c_void_p), ("first_norm", C.c_void_p), ("ws_attn_part", C.c_void_p), ("ws_sync", C.c_void_p),
+                ("has_pattern_delays", C.c_int32), ("pattern_delays", C.c_int32 * 16)]
 
 
 class Conv(C.Structure):
@@ -134,6 +135,10 @@ SIGNATURES = {
                                      C.c_void_p, C.c_int64, C.c_void_p]),
     "vaura_pattern_build": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "vaura_pattern_revert": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    "vaura_pattern_build_delays": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                             C.POINTER(C.c_int32), C.c_void_p]),
+    "vaura_pattern_revert_delays": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                              C.POINTER(C.c_int32), C.c_void_p]),
     "vaura_sample": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(Sampling), C.c_void_p, C.c_int64,
                                C.c_void_p, C.c_void_p]),
     "vaura_decode_step": (C.c_int, [C.POINTER(Decoder), C.POINTER(Sampling), C.c_int, C.c_void_p]),
@@ -197,6 +202,23 @@ def check(rc: int, what: str) -> None:
         names = {-1: "VAURA_ERR_ARG", -2: "VAURA_ERR_SHAPE", -3: "VAURA_ERR_DTYPE", -4: "VAURA_ERR_STATE"}
         raise VauraHipError(f"{what}: {names.get(rc, rc)}")
     raise VauraHipError(f"{what}: hipError_t {rc}")
+
+
+def check_delays(delays, n_codebooks: int) -> tuple:
+    """A codebook delay pattern (codebook_patterns.py:374-419) as the kernels take it: K sorted, non-negative ints, K <= 16."""
+    d = tuple(int(x) for x in delays)
+    if len(d) != n_codebooks:
+        raise VauraHipError(f"pattern delays {list(d)}: {len(d)} values for {n_codebooks} codebooks")
+    if n_codebooks > 16:
+        raise VauraHipError(f"delay patterns are implemented for at most 16 codebooks, got {n_codebooks}")
+    if any(x < 0 for x in d) or list(d) != sorted(d):
+        raise VauraHipError(f"pattern delays must be sorted and non-negative, got {list(d)}")
+    return d
+
+
+def delays_host(delays) -> "C.Array":
+    """Host int32 array of the delays (the ``delays_host`` argument of vaura_pattern_*_delays)."""
+    return (C.c_int32 * len(delays))(*delays)
 
 
 def ptr(t) -> int:

@@ -26,8 +26,20 @@ static int check_decoder(const vaura_decoder* d) {
   if (d->plane_shift < 0 || d->plane_shift > 24 || (d->plane_shift && !d->ws_h_split)) return VAURA_ERR_ARG;
   if (d->kv_dtype < 0 || d->kv_dtype > 2) return VAURA_ERR_ARG;
   if (d->kv_dtype != 0 && (d->max_len > 256 || !d->ws_h_split)) return VAURA_ERR_SHAPE;      // fp16 / fp8 K / V: the pair path's single-round-trip attention only
+  // codebook delay pattern: seq_len = timesteps + max(d) + 1 (d_q = q without has_pattern_delays)
+  int span = m.n_codebooks;
+  if (d->has_pattern_delays) {
+    if (d->has_pattern_delays != 1 || m.n_codebooks <= 0 || m.n_codebooks > 16) return VAURA_ERR_ARG;
+    for (int q = 0; q < m.n_codebooks; ++q)
+      if (d->pattern_delays[q] < 0 || (q > 0 && d->pattern_delays[q] < d->pattern_delays[q - 1])) return VAURA_ERR_ARG;
+    span = d->pattern_delays[m.n_codebooks - 1] + 1;
+  }
+  if (d->seq_len != d->timesteps + span) return VAURA_ERR_SHAPE;
   return 0;
 }
+
+// the sampler's view of the pattern: host array of K delays, NULL = the default d_k = k
+static const int32_t* va_pattern_delays(const vaura_decoder* d) { return d->has_pattern_delays ? d->pattern_delays : nullptr; }
 
 // Optional per-launch timing (vaura_profile_loop): every launch of the selected kinds carries its own
 // start/stop events (see VA_LAUNCH), i.e. the interval rocprofv3's kernel trace reports.
@@ -235,7 +247,7 @@ static int enqueue_step_bf16(const vaura_decoder* d, const vaura_sampling* sp, i
   if (rc) return rc;
   PROF_B(VAURA_K_SAMPLE);
   rc = va_launch_sample(d->ws_logits, d->batch, m.n_codebooks, m.vocab, sp, d->noise, d->batch * m.n_codebooks, d->state, 0,
-                        nullptr, d->seq, d->timesteps, d->seq_len, d->state, s);
+                        nullptr, d->seq, d->timesteps, d->seq_len, d->state, va_pattern_delays(d), s);
   PROF_A(VAURA_K_SAMPLE);
   return rc;
 }
@@ -291,7 +303,7 @@ static int enqueue_step(const vaura_decoder* d, const vaura_sampling* sp, int sa
   if (rc) return rc;
   PROF_B(VAURA_K_SAMPLE);
   rc = va_launch_sample(d->ws_logits, d->batch, m.n_codebooks, m.vocab, sp, d->noise, d->batch * m.n_codebooks, d->state, 0,
-                          nullptr, d->seq, d->timesteps, d->seq_len, d->state, s);
+                          nullptr, d->seq, d->timesteps, d->seq_len, d->state, va_pattern_delays(d), s);
   PROF_A(VAURA_K_SAMPLE);
   return rc;
 }

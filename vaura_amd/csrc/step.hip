@@ -3,7 +3,7 @@
 //
 //   embed    models/modules/sampler/llama.py:455-472, 555-586  (token projection sum + video concat)
 //   sample   models/vaura_model.py:807-825, 536-544; utils/utils.py:139-196
-//   pattern  models/modules/misc/codebook_patterns.py:137-285, 390-406 (delayed pattern, closed form)
+//   pattern  models/modules/misc/codebook_patterns.py:137-285, 374-419 (delay patterns, closed form)
 #include "common.h"
 #include "gemv3_kernel.h"
 
@@ -117,6 +117,7 @@ struct SampleArgs {
   int32_t* tokens_out;   // (B, K) or null
   int32_t* seq;          // (B, K, S) or null
   int B, K, V, T, S;
+  int32_t delays[16];    // pattern delay of codebook k < 16 (seq != null): step s of codebook k holds timestep s - 1 - delays[k]
   int use_sampling, top_k, probs_in;
   float temp, top_p, cfg_scale;
   float tie_eps;         // near-tie detector (vaura_sampling.tie_eps): relative bound on a logit's error, 0 = off
@@ -489,8 +490,11 @@ __global__ __launch_bounds__(SMP_THREADS) void sample_kernel(const float* __rest
     if (a.tokens_out) a.tokens_out[b * a.K + k] = token;
     if (a.seq) {
       // vaura_model.py:536-544 — invalid pattern slots become the special token; known tokens are kept
+      int dk = k;                // this codebook's delay (static indices: k is uniform, a run-time index would go to scratch)
+#pragma unroll
+      for (int j = 0; j < 16; ++j) if (j == k) dk = a.delays[j];
       const int offset = pos + 1;
-      const int t = offset - 1 - k;
+      const int t = offset - 1 - dk;
       const int tok = (t >= 0 && t < a.T) ? token : V;
       if (offset < a.S) {   // a step past the end of the sequence (refused by vaura_generate_loop) must not write
         int32_t* slot = a.seq + ((size_t)b * a.K + k) * a.S + offset;
@@ -523,12 +527,14 @@ __global__ __launch_bounds__(SMP_THREADS) void sample_kernel(const float* __rest
 
 int va_launch_sample(const float* logits, int B, int K, int vocab, const vaura_sampling* sp, const float* noise,
                      int /*noise_rows_per_step*/, const int32_t* state, int64_t step_host, int32_t* tokens_out,
-                     int32_t* seq, int T, int S, int32_t* state_rw, hipStream_t s) {
+                     int32_t* seq, int T, int S, int32_t* state_rw, const int32_t* delays_host, hipStream_t s) {
   if (!logits || !sp || B <= 0 || K <= 0) return VAURA_ERR_ARG;
   if (vocab != 1024) return VAURA_ERR_SHAPE;
+  if (delays_host && K > 16) return VAURA_ERR_ARG;
   SampleArgs a;
   a.logits = logits; a.noise = noise; a.state = state; a.state_rw = state_rw; a.tokens_out = tokens_out; a.seq = seq;
   a.B = B; a.K = K; a.V = vocab; a.T = T; a.S = S;
+  for (int j = 0; j < 16; ++j) a.delays[j] = (delays_host && j < K) ? delays_host[j] : j;   // NULL: the default pattern, d_k = k
   a.use_sampling = sp->use_sampling; a.top_k = sp->top_k; a.temp = sp->temp; a.top_p = sp->top_p;
   a.cfg_scale = sp->input_is_probs ? 1.0f : sp->cfg_scale; a.seed = sp->seed; a.clip_base = sp->clip_base; a.step_host = step_host;
   a.probs_in = sp->input_is_probs;
@@ -549,45 +555,97 @@ int va_launch_advance(int32_t* state, int set_to, hipStream_t s) {
 }
 
 // ------------------------------------------------------------------------------------ pattern
-// delayed pattern, delays = 0..K-1: sequence step s of codebook q holds timestep t = s - 1 - q.
-__global__ void pattern_build_kernel(const int32_t* __restrict__ codes, int32_t* __restrict__ seq, int B, int K, int T,
-                                     int special) {
-  const int S = T + K;
+// delay pattern: sequence step s of codebook q holds timestep t = s - 1 - d_q; S = T + max(d) + 1 steps.  The delays travel by
+// value; codebooks q >= 16 (default pattern only) keep d_q = q.
+struct PatternDelays { int32_t d[16]; };
+
+__device__ __forceinline__ int pattern_delay(const PatternDelays& pd, int q) {
+  int dq = q;
+#pragma unroll
+  for (int j = 0; j < 16; ++j) if (j == q) dq = pd.d[j];     // static indices: a per-lane run-time index would go to scratch
+  return dq;
+}
+
+__global__ void pattern_build_kernel(const int32_t* __restrict__ codes, int32_t* __restrict__ seq, int B, int K, int T, int S,
+                                     int special, PatternDelays pd) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= (int64_t)B * K * S) return;
   const int s = (int)(i % S), q = (int)((i / S) % K), b = (int)(i / ((int64_t)S * K));
-  const int t = s - 1 - q;
+  const int t = s - 1 - pattern_delay(pd, q);
   seq[i] = (t >= 0 && t < T) ? codes[((size_t)b * K + q) * T + t] : special;
 }
 __global__ void pattern_revert_kernel(const int32_t* __restrict__ seq, int32_t* __restrict__ codes, int B, int K, int T,
-                                      int S, int fill) {
+                                      int S, int fill, PatternDelays pd) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= (int64_t)B * K * T) return;
   const int t = (int)(i % T), q = (int)((i / T) % K), b = (int)(i / ((int64_t)T * K));
-  const int s = t + 1 + q;
+  const int s = t + 1 + pattern_delay(pd, q);
   codes[i] = (s < S) ? seq[((size_t)b * K + q) * S + s] : fill;
+}
+
+// delays_host: K sorted, non-negative delays (K <= 16), or NULL for d_q = q.  Returns max(d) + 1 (K for NULL), or an error.
+static int pattern_delays_arg(const int32_t* delays_host, int K, PatternDelays* pd) {
+  for (int j = 0; j < 16; ++j) pd->d[j] = j;
+  if (!delays_host) return K;
+  if (K > 16) return VAURA_ERR_ARG;
+  for (int q = 0; q < K; ++q) {
+    if (delays_host[q] < 0 || (q > 0 && delays_host[q] < delays_host[q - 1])) return VAURA_ERR_ARG;
+    pd->d[q] = delays_host[q];
+  }
+  return delays_host[K - 1] + 1;
+}
+
+static int pattern_build(const int32_t* codes, int32_t* seq, int B, int K, int T, int S, int special, const int32_t* delays_host,
+                         hipStream_t s) {
+  if (!codes || !seq || B <= 0 || K <= 0 || T <= 0) return VAURA_ERR_ARG;
+  PatternDelays pd;
+  const int span = pattern_delays_arg(delays_host, K, &pd);
+  if (span < 0) return span;
+  if (S != T + span) return VAURA_ERR_SHAPE;
+  const int64_t n = (int64_t)B * K * S;
+  VA_LAUNCH(pattern_build_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, codes, seq, B, K, T, S, special, pd);
+  return 0;
+}
+
+static int pattern_revert(const int32_t* seq, int32_t* codes, int B, int K, int T, int S, int fill, const int32_t* delays_host,
+                          hipStream_t s) {
+  if (!codes || !seq || B <= 0 || K <= 0 || T <= 0 || S <= 0) return VAURA_ERR_ARG;
+  PatternDelays pd;
+  const int span = pattern_delays_arg(delays_host, K, &pd);
+  if (span < 0) return span;
+  if (delays_host && S > T + span) return VAURA_ERR_SHAPE;
+  const int64_t n = (int64_t)B * K * T;
+  VA_LAUNCH(pattern_revert_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, seq, codes, B, K, T, S, fill, pd);
+  return 0;
 }
 
 extern "C" {
 
 int vaura_pattern_build(const int32_t* codes, int32_t* seq, int B, int K, int T, int special, vaura_stream_t s) {
-  if (!codes || !seq || B <= 0 || K <= 0 || T <= 0) return VAURA_ERR_ARG;
-  const int64_t n = (int64_t)B * K * (T + K);
-  VA_LAUNCH(pattern_build_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, as_stream(s), codes, seq, B, K, T, special);
-  return 0;
+  return pattern_build(codes, seq, B, K, T, T + K, special, nullptr, as_stream(s));
 }
 
 int vaura_pattern_revert(const int32_t* seq, int32_t* codes, int B, int K, int T, int S, int fill, vaura_stream_t s) {
-  if (!codes || !seq || B <= 0 || K <= 0 || T <= 0 || S <= 0) return VAURA_ERR_ARG;
-  const int64_t n = (int64_t)B * K * T;
-  VA_LAUNCH(pattern_revert_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, as_stream(s), seq, codes, B, K, T, S, fill);
-  return 0;
+  return pattern_revert(seq, codes, B, K, T, S, fill, nullptr, as_stream(s));
+}
+
+int vaura_pattern_build_delays(const int32_t* codes, int32_t* seq, int B, int K, int T, int S, int special,
+                               const int32_t* delays_host, vaura_stream_t s) {
+  if (!delays_host) return VAURA_ERR_ARG;
+  return pattern_build(codes, seq, B, K, T, S, special, delays_host, as_stream(s));
+}
+
+int vaura_pattern_revert_delays(const int32_t* seq, int32_t* codes, int B, int K, int T, int S, int fill,
+                                const int32_t* delays_host, vaura_stream_t s) {
+  if (!delays_host) return VAURA_ERR_ARG;
+  return pattern_revert(seq, codes, B, K, T, S, fill, delays_host, as_stream(s));
 }
 
 int vaura_sample(const float* logits, int B, int K, int vocab, const vaura_sampling* sp, const float* noise,
                  int64_t step, int32_t* tokens_out, vaura_stream_t s) {
   if (!tokens_out) return VAURA_ERR_ARG;
-  return va_launch_sample(logits, B, K, vocab, sp, noise, B * K, nullptr, step, tokens_out, nullptr, 0, 0, nullptr, as_stream(s));
+  return va_launch_sample(logits, B, K, vocab, sp, noise, B * K, nullptr, step, tokens_out, nullptr, 0, 0, nullptr, nullptr,
+                          as_stream(s));
 }
 
 }  // extern "C"

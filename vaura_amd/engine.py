@@ -261,6 +261,7 @@ class DecoderEngine:
         self.state = None
         self._carried_status = 0             # status bits read off a state buffer that prepare() was about to replace
         self._shape = None
+        self.delays: Optional[tuple] = None  # codebook delay pattern of the prepared shape (None = 0..K-1)
         self._graph, self._graph_key = None, None
         self.weight_bytes = sum(t.numel() * t.element_size() for t in self._keep)
 
@@ -288,14 +289,24 @@ class DecoderEngine:
     # sliding-window caller's 166-token prompt in one GEMM pass (96 ms per chunk; 106 ms at 64, 120 ms at 32)
     PREFILL_POSITIONS = 192
 
+    def pattern_delays(self, delays: Optional[Sequence[int]]) -> Optional[tuple]:
+        """The codebook delay pattern as the engine keys it: None for the default (the zero-filled descriptor), otherwise the
+        checked tuple (``_lib.check_delays``; an explicit 0..K-1 goes through the descriptor's delays and gives the same bits)."""
+        return None if delays is None else L.check_delays(delays, self.cfg.num_codebooks)
+
     def prepare(self, batch: int, timesteps: int, n_cond_tokens: int, cfg_on: bool, tokens_per_frame: int = 7,
-                block_size: Optional[int] = None):
+                block_size: Optional[int] = None, delays: Optional[Sequence[int]] = None):
+        """delays: the codebook delay pattern (None = 0..K-1): S = timesteps + max(d) + 1 sequence steps."""
         c = self.cfg
         K = c.num_codebooks
-        S = timesteps + K
+        delays = self.pattern_delays(delays)
+        S = timesteps + (K if delays is None else max(delays) + 1)
+        if delays is not None and block_size and S > block_size:
+            raise L.VauraHipError(f"delay pattern {list(delays)} with {timesteps} timesteps needs {S} sequence steps; the model's "
+                                  f"block_size is {block_size}")
         rows = 2 * batch if cfg_on else batch
         max_len = (max(S, block_size or 0) + 31) // 32 * 32
-        key = (batch, timesteps, n_cond_tokens, cfg_on, tokens_per_frame, max_len)
+        key = (batch, timesteps, n_cond_tokens, cfg_on, tokens_per_frame, max_len, delays)
         self._fc = None                       # whoever prepares the engine is about to overwrite the K/V cache
         if self._shape == key:
             return
@@ -344,6 +355,10 @@ class DecoderEngine:
         d.prefill_positions = self._prefill_positions
         d.plane_shift = self.plane_shift
         d.kv_dtype = {"f32": 0, "f16": 1, "f8": 2}[self.kv_dtype]
+        if delays is not None:             # zero-filled = the default pattern (include/vaura_hip.h)
+            d.has_pattern_delays = 1
+            for q, dq in enumerate(delays):
+                d.pattern_delays[q] = dq
         d.layers_host = C.cast(self.layers, C.POINTER(L.LayerWeights))
         d.heads, d.final_norm = L.ptr(self.heads), L.ptr(self.final_norm)
         d.tok_emb, d.tok_proj_w, d.tok_proj_b = L.ptr(self.tok_emb), L.ptr(self.tok_w), L.ptr(self.tok_b)
@@ -366,6 +381,7 @@ class DecoderEngine:
         self._shape = key
         self._graph_key = None
         self.batch, self.rows, self.T, self.S, self.Tv, self.max_len = batch, rows, timesteps, S, n_cond_tokens, max_len
+        self.delays = delays
 
     def kv_bytes_per_position(self) -> int:
         c = self.cfg
@@ -418,8 +434,13 @@ class DecoderEngine:
             Tp = prompt.shape[-1]
             assert Tp < T, "gt audio prompt can not be longer than max_new_tokens"
             self.codes_i32[..., :Tp] = prompt.to(self.dev, torch.int32)
-        L.check(self.lib.vaura_pattern_build(L.ptr(self.codes_i32), L.ptr(self.seq), self.batch, K, T,
-                                             self.cfg.d_codebook, L.current_stream(self.dev)), "vaura_pattern_build")
+        if self.delays is None:
+            L.check(self.lib.vaura_pattern_build(L.ptr(self.codes_i32), L.ptr(self.seq), self.batch, K, T,
+                                                 self.cfg.d_codebook, L.current_stream(self.dev)), "vaura_pattern_build")
+        else:
+            L.check(self.lib.vaura_pattern_build_delays(L.ptr(self.codes_i32), L.ptr(self.seq), self.batch, K, T, self.S,
+                                                        self.cfg.d_codebook, L.delays_host(self.delays), L.current_stream(self.dev)),
+                    "vaura_pattern_build_delays")
         self._reset_state()
         return Tp
 
@@ -528,23 +549,30 @@ class DecoderEngine:
 
     def revert(self) -> torch.Tensor:
         K, T = self.cfg.num_codebooks, self.T
-        L.check(self.lib.vaura_pattern_revert(L.ptr(self.seq), L.ptr(self.codes_i32), self.batch, K, T, self.S, -1,
-                                              L.current_stream(self.dev)), "vaura_pattern_revert")
+        if self.delays is None:
+            L.check(self.lib.vaura_pattern_revert(L.ptr(self.seq), L.ptr(self.codes_i32), self.batch, K, T, self.S, -1,
+                                                  L.current_stream(self.dev)), "vaura_pattern_revert")
+        else:
+            L.check(self.lib.vaura_pattern_revert_delays(L.ptr(self.seq), L.ptr(self.codes_i32), self.batch, K, T, self.S, -1,
+                                                         L.delays_host(self.delays), L.current_stream(self.dev)),
+                    "vaura_pattern_revert_delays")
         return self.codes_i32
 
     @torch.no_grad()
     def generate_codes(self, feats: torch.Tensor, max_new_tokens: int, *, prompt: Optional[torch.Tensor] = None,
                        use_sampling=False, temp=1.0, top_k=0, top_p=0.0, cfg_scale=1.0, noise=None, seed=0,
-                       clip_base=0, use_graph=True, tokens_per_frame=7) -> torch.Tensor:
-        """The hot loop of generate(): (B, Tv, 768) -> codes (B, K, T) int64 (device)."""
+                       clip_base=0, use_graph=True, tokens_per_frame=7, delays=None) -> torch.Tensor:
+        """The hot loop of generate(): (B, Tv, 768) -> codes (B, K, T) int64 (device).  ``delays``: the codebook delay pattern
+        (codebook_patterns.py:374-419; None = 0..K-1, ParallelPatternProvider = all zeros): S = T + max(d) + 1 sequence steps, the
+        loop samples steps Tp + 1 + d_0 .. S - 1, and an explicit ``noise`` has S - (Tp + 1 + d_0) steps."""
         B, Tv, _ = feats.shape
         cfg_on = cfg_scale > 1.0
         self._fc = None                       # the K/V cache is about to be reused: forward_cached must start over
         with off_null_stream(self.dev) as caller:
-            self.prepare(B, max_new_tokens, Tv, cfg_on, tokens_per_frame, block_size=self.cfg.block_size)
+            self.prepare(B, max_new_tokens, Tv, cfg_on, tokens_per_frame, block_size=self.cfg.block_size, delays=delays)
             self.set_condition(feats)
             Tp = self.start_sequence(prompt)
-            start = Tp + 1  # Pattern.get_first_step_with_timesteps(Tp) for the delayed pattern
+            start = Tp + 1 + (self.delays[0] if self.delays else 0)  # Pattern.get_first_step_with_timesteps(Tp), sorted delays
             sp = self._sampling(use_sampling, temp, top_k, top_p, cfg_scale, seed, clip_base)
             if noise is not None:
                 noise = noise.to(self.dev, torch.float32).contiguous()

@@ -90,6 +90,7 @@ class VAURAModel(nn.Module):
         "models.modules.dac.model.DacModelWrapper": "vaura_amd.codec.DacModelWrapper",
         "models.modules.feature_extractors.avclip.motionformer.MotionFormer": "vaura_amd.feature_extractor.MotionFormer",
         "models.modules.misc.codebook_patterns.DelayedPatternProvider": "vaura_amd.patterns.DelayedPatternProvider",
+        "models.modules.misc.codebook_patterns.ParallelPatternProvider": "vaura_amd.patterns.ParallelPatternProvider",
     }
     # tensors of a reference checkpoint that nothing on the generation path reads: the extractor's 2-D patch embedding
     # (video_model_builder.py:246-248 builds it, forward_features uses patch_embed_3d)
@@ -194,6 +195,17 @@ class VAURAModel(nn.Module):
             vis_feats = self.visual_feature_extractor(frames)
         return self.visual_bridge(vis_feats.detach())
 
+    def _pattern_delays(self, timesteps: int) -> List[int]:
+        """The codebook delays of ``pattern_provider.get_pattern(timesteps)`` — the only layouts the decode loop implements
+        (codebook_patterns.py:374-419: DelayedPatternProvider, ParallelPatternProvider).  Anything else — a pattern object without
+        ``delays``, e.g. the reference's Unrolled / VALLE / MusicLM providers — is refused rather than decoded in another layout."""
+        pattern = self.pattern_provider.get_pattern(timesteps)
+        delays = getattr(pattern, "delays", None)
+        if delays is None:
+            raise L.VauraHipError(f"pattern provider {type(self.pattern_provider).__name__}: its pattern is not a delay pattern (no `delays`); "
+                                  "the decode loop implements DelayedPatternProvider / ParallelPatternProvider layouts only")
+        return list(L.check_delays(delays, self.num_codebooks))
+
     def _exp_noise(self, steps: int, rows: int, vocab: int) -> Optional[torch.Tensor]:
         if self.noise_mode == "philox":
             return None
@@ -219,6 +231,12 @@ class VAURAModel(nn.Module):
             # `sa_w[-1, -1, :]` (vaura_model.py:529-531) with this flag: there is no behaviour to reproduce
             raise NotImplementedError("attention-weight dumps are not produced by the fused decode path (nor by the reference's "
                                       "llama sampler, which returns None for them)")
+        K = self.num_codebooks
+        delays = self._pattern_delays(max_new_tokens)    # the layout the loop decodes: refused here, before any device work
+        block = self.sampler.block_size
+        if delays != list(range(K)) and max_new_tokens + max(delays) + 1 > block:   # (the engine refuses it too, before allocating)
+            raise L.VauraHipError(f"{max_new_tokens} timesteps under the delays {delays} need {max_new_tokens + max(delays) + 1} sequence "
+                                  f"steps; block_size is {block}")
         if audio is not None and not prompt_is_encoded:
             # vaura_model.py:463-469 encodes the prompt here.  (Its unpacking `cat([encoded[0] for encoded in audio])`
             # expects EnCodec's frame list and breaks on DacModelWrapper's (B, 9, T) tensor; the tensor is used as is.)
@@ -230,15 +248,14 @@ class VAURAModel(nn.Module):
             raise NotImplementedError("unconditional generation: the llama sampler always needs video features "
                                       "(the reference raises here too, llama.py:474-476)")
         B = vis.shape[0]
-        K = self.num_codebooks
         Tp = 0 if audio is None else int(audio.shape[-1])
         assert Tp < max_new_tokens, "gt audio prompt can not be longer than max_new_tokens"
         use_cfg = cfg_scale > 1.0 and self.sampler.__class__.__name__ == "Transformer"
         eng = self.sampler.engine()
         if self.sampler.audio_tokens_per_video_frame is None:
             raise L.VauraHipError("sampler.audio_tokens_per_video_frame must be set (scripts/generate.py:216 sets 7)")
-        S = max_new_tokens + K
-        start = Tp + 1  # Pattern.get_first_step_with_timesteps(Tp), delayed pattern
+        S = max_new_tokens + max(delays) + 1
+        start = Tp + 1 + delays[0]  # Pattern.get_first_step_with_timesteps(Tp) for sorted delays
         greedy = not (use_sampling and temp > 0.0)
         noise = None if greedy else self._exp_noise(S - start, B * K, self.sampler.d_codebook)
         # decode loop + its status word in one synchronisation (the reference's own post-conditions, :550-572, synchronise too); an
@@ -246,7 +263,8 @@ class VAURAModel(nn.Module):
         codes = eng.generate_codes_checked(
             vis.float(), max_new_tokens, prompt=audio if Tp else None, use_sampling=use_sampling, temp=temp,
             top_k=top_k, top_p=top_p, cfg_scale=cfg_scale if use_cfg else 1.0, noise=noise, seed=self.seed,
-            clip_base=self.clip_base, tokens_per_frame=self.sampler.audio_tokens_per_video_frame)
+            clip_base=self.clip_base, tokens_per_frame=self.sampler.audio_tokens_per_video_frame,
+            delays=None if delays == list(range(K)) else delays)
         bad = (codes < 0) | (codes > self.sampler.d_codebook)
         assert not bool(bad.any()), "generated sequence is incomplete or out of range"
         if check:

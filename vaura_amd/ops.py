@@ -3,7 +3,7 @@ All tensors must live on a HIP device; nothing here computes on the CPU."""
 from __future__ import annotations
 
 import ctypes as C
-from typing import Optional
+from typing import Optional, Sequence
 
 import torch
 
@@ -99,23 +99,37 @@ def sample(logits: torch.Tensor, batch: int, *, use_sampling: bool, temp: float 
     return out.to(torch.int64)[..., None]
 
 
-def pattern_build(codes: torch.Tensor, special: int) -> torch.Tensor:
+def pattern_build(codes: torch.Tensor, special: int, delays: Optional[Sequence[int]] = None) -> torch.Tensor:
+    """codes (B, K, T) -> pattern sequence (B, K, T + max(d) + 1); ``delays`` None = the default 0..K-1."""
     _cuda(codes)
     B, K, T = codes.shape
     ci = codes.to(torch.int32).contiguous()
-    seq = torch.empty(B, K, T + K, dtype=torch.int32, device=codes.device)
-    L.check(L.lib().vaura_pattern_build(L.ptr(ci), L.ptr(seq), B, K, T, special, L.current_stream()), "vaura_pattern_build")
+    if delays is None:
+        seq = torch.empty(B, K, T + K, dtype=torch.int32, device=codes.device)
+        L.check(L.lib().vaura_pattern_build(L.ptr(ci), L.ptr(seq), B, K, T, special, L.current_stream()), "vaura_pattern_build")
+    else:
+        d = L.check_delays(delays, K)
+        S = T + max(d) + 1
+        seq = torch.empty(B, K, S, dtype=torch.int32, device=codes.device)
+        L.check(L.lib().vaura_pattern_build_delays(L.ptr(ci), L.ptr(seq), B, K, T, S, special, L.delays_host(d), L.current_stream()),
+                "vaura_pattern_build_delays")
     torch.cuda.current_stream().synchronize()
     return seq.to(codes.dtype)
 
 
-def pattern_revert(seq: torch.Tensor, timesteps: int, fill: int) -> torch.Tensor:
+def pattern_revert(seq: torch.Tensor, timesteps: int, fill: int, delays: Optional[Sequence[int]] = None) -> torch.Tensor:
+    """pattern sequence (B, K, S) -> codes (B, K, timesteps); ``delays`` None = the default 0..K-1."""
     _cuda(seq)
     B, K, S = seq.shape
     si = seq.to(torch.int32).contiguous()
     codes = torch.empty(B, K, timesteps, dtype=torch.int32, device=seq.device)
-    L.check(L.lib().vaura_pattern_revert(L.ptr(si), L.ptr(codes), B, K, timesteps, S, fill, L.current_stream()),
-            "vaura_pattern_revert")
+    if delays is None:
+        L.check(L.lib().vaura_pattern_revert(L.ptr(si), L.ptr(codes), B, K, timesteps, S, fill, L.current_stream()),
+                "vaura_pattern_revert")
+    else:
+        d = L.check_delays(delays, K)
+        L.check(L.lib().vaura_pattern_revert_delays(L.ptr(si), L.ptr(codes), B, K, timesteps, S, fill, L.delays_host(d),
+                                                    L.current_stream()), "vaura_pattern_revert_delays")
     torch.cuda.current_stream().synchronize()
     return codes.to(seq.dtype)
 

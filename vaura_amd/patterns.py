@@ -4,7 +4,8 @@ Host-side mirror of /root/reference/models/modules/misc/codebook_patterns.py for
 generate configs use (Delayed / Parallel; the Unrolled/VALLE/MusicLM providers at :422-603 are not
 referenced by any config and are out of scope).  The layout bookkeeping (indexes, masks, first step
 of a timestep) is closed-form host metadata; moving token VALUES (build / revert of a sequence)
-runs on the device through ``vaura_pattern_build`` / ``vaura_pattern_revert`` and has no CPU path.
+runs on the device through ``vaura_pattern_build[_delays]`` / ``vaura_pattern_revert[_delays]`` for any
+sorted, non-negative delays of at most 16 codebooks, and has no CPU path.
 
 Delayed pattern, delays d_q (codebook_patterns.py:390-406): sequence step s (s >= 1) of codebook q
 holds timestep t = s - 1 - d_q; step 0 is the all-special start step; S = T + max(d) + 1.
@@ -27,6 +28,8 @@ class Pattern:
         self.timesteps = timesteps
         self.seq_steps = timesteps + max(self.delays) + 1
         self._unit_delays = self.delays == list(range(self.n_q))
+        # what the device kernels take: None = their default 0..K-1 (vaura_pattern_build / _revert)
+        self._device_delays = None if self._unit_delays else self.delays
 
     # ------------------------------------------------------------------ metadata (host)
     @property
@@ -91,7 +94,7 @@ class Pattern:
         if not x.is_cuda:
             raise L.VauraHipError("pattern sequences are built on the HIP device only (no CPU path)")
         if not self._unit_delays:
-            raise L.VauraHipError("the HIP kernels implement delays = 0..K-1 (DelayedPatternProvider default)")
+            L.check_delays(self.delays, self.n_q)
 
     def build_pattern_sequence(self, z: torch.Tensor, special_token: int, keep_only_valid_steps: bool = False):
         """z (B, K, T) -> (values (B, K, S), indexes (K, S), mask (K, S)) — codebook_patterns.py:180-207."""
@@ -102,7 +105,7 @@ class Pattern:
         if T != self.timesteps:
             raise L.VauraHipError("build_pattern_sequence expects T == pattern timesteps")
         idx, mask = self._build_indexes(T, z.device)
-        return ops.pattern_build(z, special_token), idx, mask
+        return ops.pattern_build(z, special_token, self._device_delays), idx, mask
 
     def revert_pattern_sequence(self, s: torch.Tensor, special_token: int, keep_only_valid_steps: bool = False):
         """s (B, K, S') -> (values (B, K, T), indexes (K, T), mask (K, T)) — codebook_patterns.py:260-285."""
@@ -111,7 +114,7 @@ class Pattern:
         assert K == self.n_q and S <= self.seq_steps
         self._check(s)
         idx, mask = self._revert_indexes(S, s.device)
-        return ops.pattern_revert(s, self.timesteps, special_token), idx, mask
+        return ops.pattern_revert(s, self.timesteps, special_token, self._device_delays), idx, mask
 
 
 class DelayedPatternProvider:
