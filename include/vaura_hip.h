@@ -273,6 +273,29 @@ int vaura_profile_loop(const vaura_decoder* dec, const vaura_sampling* sp, int n
 void vaura_profile_outliers(int64_t* per_kind);
 
 /* -------------------------------------------------------------------------------------------
+ * Teacher-forced scoring: VAURAModel.forward + _compute_loss (models/vaura_model.py:136-192, 240-280; test_step 339-347).
+ * dec->seq holds the pattern sequence of the given codes (build_pattern_sequence(codes[..., :-1]) against a pattern of
+ * dec->timesteps = Ta steps: vaura_pattern_build_delays of the codes with timestep Ta - 1 set to the special token), state zeroed,
+ * dec->rows == dec->batch (no CFG branch).  Positions [0, n_pos) are run, n_pos <= seq_len - 1 and <= max_len (VAURA_ERR_ARG);
+ * model-output position s of codebook q predicts timestep t = s - d_q, target targets[b, q, t] ((B, K, Ta) int32).
+ *   plane storages with prefill workspaces: chunks of dec->prefill_positions positions through the prefill kernels, the heads
+ *     (final RMSNorm fused) over every position of the chunk into ws_chunk_logits (prefill_positions * rows_padded * K * vocab
+ *     floats), then the NLL kernel on the chunk;
+ *   otherwise (VAURA_W_F32 / BF16): one decode step with heads per position (ws_logits), then the NLL kernel — the exact-fp32
+ *     answer; ws_chunk_logits may be NULL.  The step's sampler leaves its status bits in state[4] as in the decode loop.
+ * Outputs: nll (B, K, Ta) = logsumexp - target logit in fp32; mask_out (B, K, Ta) bytes (optional; 1 where t + d_q < n_pos, i.e.
+ * all of them when n_pos = seq_len - 1 — delay patterns leave no timestep without a logit); logits_out (optional) the reverted
+ * (B, K, Ta, vocab) logits, NaN rows where the mask is 0 (revert_pattern_logits' fill); loss_per_cb (K) = mean of the valid nll
+ * of codebook q, loss (1) = sum_q loss_per_cb[q] / K.  Summation order is fixed: two calls give the same bits.                 */
+int vaura_score(const vaura_decoder* dec, int n_pos, const int32_t* targets, float* ws_chunk_logits, float* logits_out, float* nll,
+                uint8_t* mask_out, float* loss_per_cb, float* loss, vaura_stream_t s);
+/* _compute_loss on a given reverted logits tensor (B, K, Ta, vocab) fp32, targets (B, K, Ta) int32, mask (B, K, Ta) bytes: the same
+ * NLL and reduction kernels (vocab % 256 == 0, <= 1024; K <= 16).  nll (B, K, Ta) is scratch + output (entries where mask is 0 are
+ * not meaningful).                                                                                                                */
+int vaura_score_logits(const float* logits, const int32_t* targets, const uint8_t* mask, int B, int K, int V, int Ta, float* nll,
+                       float* loss_per_cb, float* loss, vaura_stream_t s);
+
+/* -------------------------------------------------------------------------------------------
  * op-level entry points (parity tests call the same kernels the step uses)                      */
 /* out = epilogue( W x (x*gain) * rinv ):  epi 0 store, 1 +residual, 2 SwiGLU pairs, 3 gelu_tanh,
  * 4 row-major logits.  K must be one of the compiled depths (512, 768, 1024, 1536, 4096).        */

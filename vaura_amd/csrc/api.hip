@@ -118,6 +118,17 @@ static int enqueue_prefill_chunk_bf16(const vaura_decoder* d, int p0, int n, hip
   return 0;
 }
 
+// The same chunk followed by the codebook heads at ALL n positions (teacher-forced scoring, vaura_score): the last layer's w2 left
+// split(h * final_norm) and its sums of squares for every row block of the chunk, so the heads are one more GEMM over those row
+// blocks — the existing E3_LOGITS instances (the GEMM tiling from 16 row blocks up).  out: (n * rows_padded, K * vocab) row-major.
+static int enqueue_prefill_chunk_heads(const vaura_decoder* d, int p0, int n, float* out, hipStream_t s) {
+  int rc = enqueue_prefill_chunk_bf16(d, p0, n, s);
+  if (rc) return rc;
+  const vaura_dims& m = d->dims;
+  return va_launch_gemv3(g3(d->heads, d->ws_h_split, d->ws_ss, nullptr, out, nullptr, nullptr, nullptr, d, m.n_codebooks * m.vocab, n),
+                         (int64_t)m.n_codebooks * m.vocab, m.d_model, E3_LOGITS, true, s);
+}
+
 // pair path (H1 / H2 / FP8 storage): activations travel as (hi, lo) fp16 planes, products on the fp16 MFMA
 static int enqueue_step_bf16(const vaura_decoder* d, const vaura_sampling* sp, int sample, hipStream_t s) {
   const vaura_dims& m = d->dims;
@@ -487,6 +498,45 @@ int vaura_profile_loop(const vaura_decoder* dec, const vaura_sampling* sp, int n
   }
   if (rc) return rc;
   return e == hipSuccess ? 0 : (int)e;
+}
+
+int vaura_score(const vaura_decoder* dec, int n_pos, const int32_t* targets, float* ws_chunk_logits, float* logits_out, float* nll,
+                uint8_t* mask_out, float* loss_per_cb, float* loss, vaura_stream_t s) {
+  int rc = check_decoder(dec);
+  if (rc) return rc;
+  if (!targets || !nll || !loss_per_cb || !loss || n_pos <= 0) return VAURA_ERR_ARG;
+  if (dec->rows != dec->batch) return VAURA_ERR_ARG;                              // no CFG branch: the reference scores B rows
+  if (n_pos > dec->seq_len - 1 || n_pos > dec->max_len) return VAURA_ERR_ARG;
+  const vaura_dims& m = dec->dims;
+  const int B = dec->batch, K = m.n_codebooks, V = m.vocab, Ta = dec->timesteps;
+  const int32_t* delays = va_pattern_delays(dec);
+  hipStream_t st = as_stream(s);
+  if (dec->ws_h_split && dec->prefill_positions > 0) {
+    // the caller guarantees state[0] == 0 at entry (vaura_pattern_build + zeroed state), as for vaura_generate_loop's prefill
+    if (!ws_chunk_logits) return VAURA_ERR_ARG;
+    const int rp = (dec->rows + 15) / 16 * 16;
+    for (int p0 = 0; p0 < n_pos; p0 += dec->prefill_positions) {
+      const int n = (n_pos - p0 < dec->prefill_positions) ? n_pos - p0 : dec->prefill_positions;
+      rc = enqueue_prefill_chunk_heads(dec, p0, n, ws_chunk_logits, st);
+      if (rc) return rc;
+      rc = va_launch_score_nll(ws_chunk_logits, rp, p0, n, B, K, V, Ta, delays, targets, nll, logits_out, st);
+      if (rc) return rc;
+    }
+    rc = va_launch_advance(dec->state, n_pos, st);
+    if (rc) return rc;
+  } else {
+    // per position (VAURA_W_F32 / BF16, or no prefill workspaces): a decode step with heads, as logits_all_positions runs it; the
+    // greedy sampler behind it only fills -1 slots, and a fully built pattern sequence has none.  Its status bits (non-finite logits)
+    // stay in state[4] for the caller.
+    vaura_sampling sp = {};
+    for (int p = 0; p < n_pos; ++p) {
+      rc = enqueue_step(dec, &sp, 1, st);
+      if (rc) return rc;
+      rc = va_launch_score_nll(dec->ws_logits, dec->rows, p, 1, B, K, V, Ta, delays, targets, nll, logits_out, st);
+      if (rc) return rc;
+    }
+  }
+  return va_launch_score_reduce(nll, mask_out, logits_out, B, K, V, Ta, n_pos, delays, loss_per_cb, loss, st);
 }
 
 void vaura_profile_outliers(int64_t* per_kind) {

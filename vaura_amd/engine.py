@@ -706,6 +706,117 @@ class DecoderEngine:
         self.check_status()
         return out
 
+    # ------------------------------------------------------------------ teacher-forced scoring (VAURAModel.forward + _compute_loss)
+    def _score_workspace(self) -> torch.Tensor:
+        """(prefill_positions * rows_padded, K * vocab) fp32: the heads' output over one prefill chunk (vaura_score).  Allocated on
+        first use and kept while the prepared shape stays (``_shape`` keys it), so the decode loop's memory is unchanged."""
+        key = (self._shape, self._prefill_positions)
+        if getattr(self, "_score_ws_key", None) != key:
+            self._score_ws = None
+            n = self._prefill_positions * self._rows_padded(self.rows) if self._prefill_positions else 0
+            self._score_ws = (torch.empty(n, self.cfg.num_codebooks * self.cfg.d_codebook, dtype=torch.float32, device=self.dev)
+                              if n else None)
+            self._score_ws_key = key
+        return self._score_ws
+
+    @torch.no_grad()
+    def score(self, codes: torch.Tensor, feats: torch.Tensor, *, delays: Optional[Sequence[int]] = None, tokens_per_frame: int = 7,
+              return_logits: bool = False, checked: bool = True) -> Dict[str, torch.Tensor]:
+        """Teacher-forced cross-entropy of ``codes`` (B, K, Ta) under ``feats`` (B, Tv, 768): the reference's ``forward`` +
+        ``_compute_loss`` (vaura_model.py:136-192, 240-280).  The input is ``build_pattern_sequence(codes[..., :-1])`` against a pattern
+        of Ta timesteps (special token = vocab), S = Ta + max(d) + 1 (``delays`` None = 0..K-1); positions [0, S - 1) run without a CFG
+        branch (rows = B) through the prefill chunks with the heads at every position (plane storages; one decode step with heads per
+        position on "f32"), then the fused revert + log-softmax + NLL kernel and the fixed-order per-codebook mean (csrc/score.hip).
+        Returns {"loss": (), "loss_per_codebook": (K,), "nll": (B, K, Ta), "mask": (B, K, Ta) bool, and with ``return_logits`` "logits":
+        the reverted (B, K, Ta, vocab)}.  ``checked``: range safety as ``generate_codes_checked`` — a non-finite loss or a dirty status
+        word re-runs the call on the exact-fp32 twin (one warning per engine)."""
+        c = self.cfg
+        if codes.dim() != 3 or codes.shape[1] != c.num_codebooks:
+            raise L.VauraHipError(f"codes must be (B, {c.num_codebooks}, Ta), got {tuple(codes.shape)}")
+        B, K, Ta = codes.shape
+        if feats.dim() != 3 or feats.shape[0] != B or feats.shape[2] != c.cond_in:
+            raise L.VauraHipError(f"feats must be ({B}, Tv, {c.cond_in}), got {tuple(feats.shape)}")
+        if Ta < 2:
+            raise L.VauraHipError("scoring needs at least 2 timesteps (the input is codes[..., :-1])")
+        dl = self.pattern_delays(delays)
+        S = Ta + (K if dl is None else max(dl) + 1)
+        if S > c.block_size:               # before any allocation (prepare() refuses only explicit delays)
+            raise L.VauraHipError(f"{Ta} timesteps under the delays {list(dl) if dl else list(range(K))} need {S} sequence steps; the "
+                                  f"model's block_size is {c.block_size}")
+        codes_d = codes.to(self.dev)
+        if bool(((codes_d < 0) | (codes_d >= c.d_codebook)).any()):
+            raise L.VauraHipError(f"codes must lie in [0, {c.d_codebook}) (the reference's cross_entropy refuses other targets)")
+        targets = codes_d.to(torch.int32).contiguous()
+        self._fc = None                    # the K/V cache is about to be reused: forward_cached must start over
+        with off_null_stream(self.dev) as caller:
+            self.prepare(B, Ta, feats.shape[1], False, tokens_per_frame, block_size=c.block_size, delays=dl)
+            self.set_condition(feats)
+            self.codes_i32[..., :Ta - 1] = targets[..., :Ta - 1]
+            self.codes_i32[..., Ta - 1] = c.d_codebook             # build_pattern_sequence(codes[..., :-1]): no input beyond Ta - 2
+            if self.delays is None:
+                L.check(self.lib.vaura_pattern_build(L.ptr(self.codes_i32), L.ptr(self.seq), B, K, Ta, c.d_codebook,
+                                                     L.current_stream(self.dev)), "vaura_pattern_build")
+            else:
+                L.check(self.lib.vaura_pattern_build_delays(L.ptr(self.codes_i32), L.ptr(self.seq), B, K, Ta, self.S, c.d_codebook,
+                                                            L.delays_host(self.delays), L.current_stream(self.dev)),
+                        "vaura_pattern_build_delays")
+            self._reset_state()
+            f32 = dict(dtype=torch.float32, device=self.dev)
+            nll = torch.empty(B, K, Ta, **f32)
+            mask = torch.empty(B, K, Ta, dtype=torch.uint8, device=self.dev)
+            lpc = torch.empty(K, **f32)
+            loss = torch.empty((), **f32)
+            logits = torch.empty(B, K, Ta, c.d_codebook, **f32) if return_logits else None
+            L.check(self.lib.vaura_score(C.byref(self.dec), self.S - 1, L.ptr(targets), L.ptr(self._score_workspace()), L.ptr(logits),
+                                         L.ptr(nll), L.ptr(mask), L.ptr(lpc), L.ptr(loss), L.current_stream(self.dev)), "vaura_score")
+            out = {"loss": loss, "loss_per_codebook": lpc, "nll": nll, "mask": mask.bool()}
+            if return_logits:
+                out["logits"] = logits
+        if caller is not None:
+            for t in out.values():
+                t.record_stream(caller)
+        if not checked:
+            return out
+        try:
+            self.check_status()
+            if not bool(torch.isfinite(loss)):
+                err = L.VauraHipError("teacher-forced scoring: non-finite loss")
+                err.status = 1
+                raise err
+        except L.VauraHipError as e:
+            if getattr(e, "status", 0) != 1 or self.wdtype == "f32" or self._twin_sd is None:
+                raise
+            if self.range_fallbacks == 0:
+                import warnings
+                warnings.warn("vaura_amd: teacher-forced scoring gave a non-finite loss (an activation left the fp16-plane range); this "
+                              "call is re-run on the exact-fp32 twin engine (slower, ~2.7 GB more)")
+            self.range_fallbacks += 1
+            return self._twin().score(codes, feats, delays=delays, tokens_per_frame=tokens_per_frame, return_logits=return_logits)
+        return out
+
+
+@torch.no_grad()
+def score_logits(logits: torch.Tensor, targets: torch.Tensor, mask: torch.Tensor):
+    """``VAURAModel._compute_loss`` on a given reverted logits tensor (vaura_model.py:240-280): logits (B, K, T, card) fp32, targets
+    (B, K, T), mask (B, K, T) on one HIP device -> (loss (), loss_per_codebook (K,), nll (B, K, T)), through the same NLL and
+    fixed-order reduction kernels as ``DecoderEngine.score`` (vaura_score_logits)."""
+    if logits.dim() != 4 or targets.shape != logits.shape[:-1] or mask.shape != targets.shape:
+        raise L.VauraHipError(f"logits (B, K, T, card), targets and mask (B, K, T) expected, got {tuple(logits.shape)}, "
+                              f"{tuple(targets.shape)}, {tuple(mask.shape)}")
+    dev = logits.device
+    _require_cuda(dev)
+    B, K, T, V = logits.shape
+    lib = L.lib()
+    x = logits.to(torch.float32).contiguous()
+    tg = targets.to(dev, torch.int32).contiguous()
+    mk = mask.to(dev, torch.uint8).contiguous()
+    nll = torch.empty(B, K, T, dtype=torch.float32, device=dev)
+    lpc = torch.empty(K, dtype=torch.float32, device=dev)
+    loss = torch.empty((), dtype=torch.float32, device=dev)
+    L.check(lib.vaura_score_logits(L.ptr(x), L.ptr(tg), L.ptr(mk), B, K, V, T, L.ptr(nll), L.ptr(lpc), L.ptr(loss),
+                                   L.current_stream(dev)), "vaura_score_logits")
+    return loss, lpc, nll
+
 
 class CodecEngine:
     """DAC decode (codes -> waveform) on the HIP path; weights from a DAC-1.0.0-keyed state dict."""

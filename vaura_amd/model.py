@@ -5,7 +5,8 @@ Same plugin slots and constructor keywords (:28-120), same ``generate()`` keywor
 callers and ``configs/generate_*.yaml`` work once the ``target:`` strings point at ``vaura_amd``.
 It is a plain ``nn.Module`` (inference only — the Lightning training half is out of scope) and it
 does no arithmetic itself: conditioning, the 228-step decode loop, sampling, pattern bookkeeping and
-codec decode all run in libvaura_hip.so.
+codec decode all run in libvaura_hip.so.  The teacher-forced evaluation path (``forward``, ``_compute_loss``,
+``validation_step`` / ``test_step``, :136-192, 240-295, 339-347) scores given audio under given video the same way.
 
 What differs from the reference, on purpose:
   * the hot loop uses a K/V cache and runs entirely on the device (the reference re-feeds the whole
@@ -315,3 +316,89 @@ class VAURAModel(nn.Module):
         tok = sample_from_logits(last, use_sampling=use_sampling, temp=temp, top_k=top_k, top_p=top_p,
                                  cfg_scale=cfg_scale if use_cfg else 1.0)
         return tok, None, None
+
+    # ------------------------------------------------------------------ teacher-forced evaluation (vaura_model.py:136-192, 240-295, 339-347)
+    @staticmethod
+    def _auto_tokens_per_frame(seq_len: int, n_video_tokens: int, codebook_pattern: Optional[str], num_codebooks: int) -> int:
+        """llama.py:_set_audio_tokens_per_video_frame: ceil((S - K) / Tv) when the sampler's ``codebook_pattern`` names a delayed
+        pattern, ceil((S - 1) / Tv) otherwise — S the length of the pattern sequence the sampler is fed."""
+        import math
+        n = seq_len - num_codebooks if "delayed" in str(codebook_pattern).lower() else seq_len - 1
+        return int(math.ceil(n / n_video_tokens))
+
+    @torch.no_grad()
+    def forward(self, frames: torch.Tensor, audio: torch.Tensor, clip_indices: Optional[torch.Tensor] = None):
+        """Teacher-forced pass of the reference (vaura_model.py:136-192): frames (B, C, Tv, H, W) and mono audio (B, 1, N) ->
+        (logits (B, K, Ta, card), logits_mask (B, K, Ta) bool, aud_feats (B, 9, Ta)).  ``audio_encoder.encode`` (the HIP DAC encode)
+        gives the codes, the visual condition comes from ``_handle_visual_conditioning``, and ``DecoderEngine.score`` runs the
+        sampler over ``build_pattern_sequence(codes[..., :-1])`` with the heads at every position and reverts the logits on the device
+        (it does not go through ``Transformer.forward``).  Two differences from the reference, on purpose:
+          * the reference caches the first call's pattern in ``self.pattern`` and reuses it for every later ``Ta``; here the delays
+            are taken from ``pattern_provider.get_pattern(Ta)`` for each call's own ``Ta`` (``_pattern_delays``);
+          * a ``sampler.audio_tokens_per_video_frame`` of None is set from the sequence as llama.py:_set_audio_tokens_per_video_frame
+            does (and kept, as there); ``Transformer.forward`` itself still refuses None.
+        Delay patterns give every timestep a logit, so the mask is all true and no reverted row is NaN."""
+        aud_feats = self.audio_encoder.encode(audio)
+        B, _, Ta = aud_feats.shape
+        vis = self._handle_visual_conditioning(frames, clip_indices, B)
+        if vis is None:
+            raise NotImplementedError("unconditional scoring: the llama sampler always needs video features (llama.py:474-476)")
+        r = self._score(aud_feats[:, :self.num_codebooks], vis, return_logits=True)
+        return r["logits"], r["mask"], aud_feats
+
+    def _score(self, codes: torch.Tensor, vis: torch.Tensor, return_logits: bool = False) -> dict:
+        """DecoderEngine.score with this model's delays (per call) and tokens per video frame (auto-set rule when None)."""
+        K = self.num_codebooks
+        Ta = int(codes.shape[-1])
+        delays = self._pattern_delays(Ta)
+        S = Ta + max(delays) + 1
+        if S > self.sampler.block_size:
+            raise L.VauraHipError(f"{Ta} timesteps under the delays {delays} need {S} sequence steps; block_size is {self.sampler.block_size}")
+        if self.sampler.audio_tokens_per_video_frame is None:
+            self.sampler.audio_tokens_per_video_frame = self._auto_tokens_per_frame(
+                S, int(vis.shape[1]), getattr(self.sampler, "codebook_pattern", None), K)
+        eng = self.sampler.engine()
+        return eng.score(codes, vis.float(), delays=None if delays == list(range(K)) else delays,
+                         tokens_per_frame=self.sampler.audio_tokens_per_video_frame, return_logits=return_logits)
+
+    @torch.no_grad()
+    def _compute_loss(self, logits: torch.Tensor, targets: torch.Tensor, mask: torch.Tensor) -> Tuple[torch.Tensor, List[torch.Tensor]]:
+        """vaura_model.py:240-280: per-codebook cross entropy over the valid (mask) entries, averaged over the codebooks ->
+        (loss, [loss of codebook k]).  Runs the HIP NLL + fixed-order reduction kernels (``engine.score_logits``)."""
+        from .engine import score_logits
+        B, K, T = targets.shape
+        assert logits.shape[:-1] == targets.shape
+        assert mask.shape == targets.shape
+        loss, lpc, _ = score_logits(logits, targets, mask)
+        return loss, [lpc[k] for k in range(K)]
+
+    @staticmethod
+    def _stack_list_repr(list_repr, to_3dim: bool = False) -> torch.Tensor:
+        """vaura_model.py:226-238."""
+        tensor_repr = torch.stack([torch.stack(tensors) for tensors in list(list_repr)])
+        if to_3dim:
+            tensor_repr = tensor_repr.view(-1, *tensor_repr.shape[-2:])
+        return tensor_repr
+
+    def _shared_step(self, batch, batch_idx):
+        """vaura_model.py:282-295 -> (logits, target codes, loss, loss_per_codebook)."""
+        audio = batch["audio"] if self.flatten_vis_feats else self._stack_list_repr(batch["audio"], to_3dim=True)
+        frames = batch["frames"]
+        logits, logits_mask, target = self.forward(frames, audio, batch.get("meta", {}).get("clip_indices", None))
+        loss, loss_per_cb = self._compute_loss(logits, target[:, :self.num_codebooks, :], logits_mask)
+        return logits, target, loss, loss_per_cb
+
+    def _shared_log(self, stage: str, loss: torch.Tensor, loss_per_cb) -> None:
+        """There is no Lightning logger here: the values the reference logs (``{stage}_loss``, ``{stage}_loss_per_codebook``,
+        vaura_model.py:296-316) are kept in ``self.last_eval_log`` for the caller."""
+        self.last_eval_log = {f"{stage}_loss": loss, f"{stage}_loss_per_codebook": list(loss_per_cb)}
+
+    def validation_step(self, batch, batch_idx):
+        _, _, loss, loss_per_cb = self._shared_step(batch, batch_idx)
+        self._shared_log("val", loss, loss_per_cb)
+        return loss
+
+    def test_step(self, batch, batch_idx):
+        _, _, loss, loss_per_cb = self._shared_step(batch, batch_idx)
+        self._shared_log("test", loss, loss_per_cb)
+        return loss
