@@ -480,6 +480,31 @@ typedef struct vaura_vit {
 int vaura_avclip_forward(const vaura_vit* v, const float* frames, int n_seg, float* feats, vaura_stream_t s);
 size_t vaura_avclip_workspace_bytes(const vaura_vit* v, int n_seg, int which);
 
+/* -------------------------------------------------------------------------------------------
+ * Video preprocessing (csrc/preproc.hip): decoded uint8 frames -> the extractor's input.  The `video_transforms_test` list of
+ * configs/generate_*.yaml (Resize(resize, antialias) -> CenterCrop -> ToFloat32DType -> Normalize) followed by
+ * GenerateMultipleSegments (models/data/transforms/video_transforms.py:114-240) and the dataset's permute, in one launch.
+ *   video     uint8, (n_clips, T, C, H, W) or, channels_last != 0, (n_clips, T, H, W, C); C must be 3
+ *   out       fp32 (n_clips, S, C, F, crop_h, crop_w), 16-byte aligned: segment s, slot f = source frame seg_start + s * seg_stride + f
+ *   tables    built by the host once per (H, W, resize, crop) (vaura_amd/preprocess.py): for kept column x the horizontal taps
+ *             h_w[x * h_taps + k] (int16, scaled by 2^h_prec) start at source column x0 + h_rel[x]; all kept columns read inside
+ *             [x0, x0 + span).  For kept row r the vertical taps v_w[r * v_taps + k] (2^v_prec) start at source row v_start[r].
+ *             Every start + taps lies inside the source (short rows are shifted and zero-filled by the host).
+ *             lut[c * 256 + level] = ((level / 255) - mean[c]) / std[c] in fp32.
+ *   tile_rows output rows per workgroup; tile_src_rows = the most source rows any tile needs (v_start[last] + v_taps - v_start[first]).
+ * Arithmetic: acc = 2^(prec-1) + sum(tap * pixel); level = clamp(acc >> prec, 0, 255) after each pass (torch's uint8 path).
+ * VAURA_ERR_SHAPE, before any launch: C != 3; crop larger than the resized image (short side -> resize, long side ->
+ * int(resize * long / short)); crop_w % 4 != 0; T < F or a segment outside [0, T); more than VAURA_PREPROC_MAX_TAPS taps per
+ * output pixel (32: a short side of up to 15 x resize, 3840 lines at resize = 256 — 1080 x 1920 needs 11); a tile that does not
+ * fit 64 KiB of LDS (vaura_video_preprocess_lds_bytes; lower tile_rows); more than 65535 output frames per call.                 */
+#define VAURA_PREPROC_MAX_TAPS 32
+int vaura_video_preprocess(const uint8_t* video, int channels_last, int n_clips, int T, int C, int H, int W, int resize, int crop_h,
+                           int crop_w, int F, int S, int seg_start, int seg_stride, const int32_t* h_rel, const int16_t* h_w, int h_taps,
+                           int h_prec, const int32_t* v_start, const int16_t* v_w, int v_taps, int v_prec, int x0, int span,
+                           int tile_rows, int tile_src_rows, const float* lut, float* out, vaura_stream_t s);
+/* dynamic LDS bytes of one workgroup for these table sizes (0 for sizes the kernel does not take) */
+size_t vaura_video_preprocess_lds_bytes(int channels_last, int crop_w, int h_taps, int span, int tile_src_rows);
+
 /* Measurement aid (tools/pmc_driver, A/B timing): selects kernel variants for launches enqueued (or graphs captured) afterwards.
  * bit 0: wo / w2 GEMVs as one workgroup per column tile instead of the row-split pair; bit 4: prefill attention as one workgroup
  * per position instead of the MFMA kernel (tools/README.md lists every bit).

@@ -1,0 +1,115 @@
+#!/usr/bin/env python
+"""Video preprocessing at configs[1]'s batch: 8 clips x 64 frames of 360 x 640 uint8 -> (8, 4, 3, 16, 224, 224) fp32.
+  device   VideoPreprocessor on frames already on the device (the kernel alone: vaura_video_preprocess)
+  pinned   the same from pinned host memory (one uint8 copy over the link + the kernel)
+  cpu_N    the reference's route on this host with N threads: torch's antialiased uint8 interpolate + crop + /255 + normalise
+HIP events on one stream for the device rows, a host clock for the CPU rows; warm-up, then the median of `rounds` (min and max kept).
+Bytes: what the algorithm needs per frame (the source rows and columns that survive the crop, read once, plus the fp32 output) over the
+kernel time, against the 6.29 TB/s copy rate measured on this part (MI355X_MICROARCH.md).
+
+    python tools/time_preprocess.py [rounds] > profiles/preprocess_timing.txt
+"""
+import json
+import os
+import statistics
+import subprocess
+import sys
+import time
+
+import torch
+import torch.nn.functional as Fn
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from vaura_amd.preprocess import VideoPreprocessor, crop_offset, resized_size  # noqa: E402
+
+COPY_RATE = 6.29e12
+B, T, H, W = 8, 64, 360, 640
+
+
+def _events(stream, fn, rounds):
+    ts = []
+    for _ in range(rounds):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record(stream)
+        fn()
+        b.record(stream)
+        torch.cuda.synchronize()
+        ts.append(a.elapsed_time(b))
+    return statistics.median(ts), min(ts), max(ts)
+
+
+def _cpu_route(video, threads, rounds):
+    torch.set_num_threads(threads)
+    oh, ow = resized_size(H, W, 256)
+    top, left = crop_offset(oh, 224), crop_offset(ow, 224)
+
+    def run():
+        outs = []
+        for clip in video:                                               # the loader transforms one clip at a time
+            x = Fn.interpolate(clip, size=(oh, ow), mode="bilinear", antialias=True)[..., top:top + 224, left:left + 224]
+            x = (x.to(torch.float32) / 255 - 0.5) / 0.5
+            outs.append(x.view(T // 16, 16, 3, 224, 224).permute(0, 2, 1, 3, 4))
+        return torch.stack(outs)
+    run()
+    ts = []
+    for _ in range(rounds):
+        t0 = time.perf_counter()
+        run()
+        ts.append(1e3 * (time.perf_counter() - t0))
+    return statistics.median(ts), min(ts), max(ts)
+
+
+def _clocks():
+    try:
+        r = subprocess.run(["rocm-smi", "--showclocks"], capture_output=True, text=True, timeout=30)
+        return [ln.strip() for ln in r.stdout.splitlines() if "sclk" in ln or "mclk" in ln][:4]
+    except Exception as e:  # noqa: BLE001
+        return [f"not read ({type(e).__name__})"]
+
+
+def main():
+    rounds = int(sys.argv[1]) if len(sys.argv) > 1 else 20
+    dev = torch.device("cuda:0")
+    video = torch.randint(0, 256, (B, T, 3, H, W), dtype=torch.uint8, generator=torch.Generator().manual_seed(0))
+    pre = VideoPreprocessor(device=dev)
+    g = pre.geometry(H, W)
+    rows = int(g.v["start"].max()) + g.v["taps"] - int(g.v["start"].min())
+    bytes_in, bytes_out = 3 * rows * g.span, 3 * 224 * 224 * 4
+    n_frames = B * T
+    stream = torch.cuda.Stream(dev)
+    rec = {"shape": {"clips": B, "frames": T, "H": H, "W": W, "out": [B, T // 16, 3, 16, 224, 224]},
+           "bytes_per_frame": {"read": bytes_in, "written": bytes_out}, "clocks_before": _clocks(), "rows": {}}
+    with torch.cuda.stream(stream):
+        on_dev, pinned = video.to(dev), video.pin_memory()
+        for _ in range(3):
+            pre(on_dev), pre(pinned)
+        torch.cuda.synchronize()
+        for name, src in (("device", on_dev), ("pinned", pinned), ("device_again", on_dev)):
+            med, lo, hi = _events(stream, lambda: pre(src), rounds)
+            rec["rows"][name] = {"ms": med, "min_ms": lo, "max_ms": hi}
+            line = f"{name:>12}: {med:8.3f} ms per batch (min {lo:.3f}, max {hi:.3f}; {rounds} rounds)"
+            if name.startswith("device"):
+                rate = n_frames * (bytes_in + bytes_out) / (med * 1e-3)
+                rec["rows"][name].update(bytes_per_s=rate, share_of_copy_rate=rate / COPY_RATE)
+                line += f"  {rate / 1e12:.3f} TB/s needed bytes = {100 * rate / COPY_RATE:.1f} % of the 6.29 TB/s copy rate"
+            print(line, flush=True)
+        # NHWC source (what a decoder hands over)
+        nhwc = on_dev.permute(0, 1, 3, 4, 2).contiguous()
+        pre_cl = VideoPreprocessor(device=dev, channels_last=True)
+        for _ in range(3):
+            pre_cl(nhwc)
+        med, lo, hi = _events(stream, lambda: pre_cl(nhwc), rounds)
+        rec["rows"]["device_channels_last"] = {"ms": med, "min_ms": lo, "max_ms": hi}
+        print(f"{'device NHWC':>12}: {med:8.3f} ms per batch (min {lo:.3f}, max {hi:.3f})", flush=True)
+    rec["clocks_after"] = _clocks()
+    for threads in (4, 16):
+        med, lo, hi = _cpu_route(video, threads, max(3, rounds // 5))
+        rec["rows"][f"cpu_{threads}"] = {"ms": med, "min_ms": lo, "max_ms": hi}
+        print(f"{'cpu ' + str(threads) + ' thr':>12}: {med:8.1f} ms per batch (min {lo:.1f}, max {hi:.1f})  torch interpolate(antialias) uint8 + crop + "
+              f"normalise; device kernel is {med / rec['rows']['device']['ms']:.0f}x, from pinned memory {med / rec['rows']['pinned']['ms']:.0f}x faster",
+              flush=True)
+    print(json.dumps(rec))
+
+
+if __name__ == "__main__":
+    main()

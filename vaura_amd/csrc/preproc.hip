@@ -1,0 +1,189 @@
+// Video preprocessing: decoded uint8 frames -> the feature extractor's input, in one launch.
+//   torchvision.transforms.v2.Resize(256, antialias=True) -> CenterCrop([224, 224]) -> ToFloat32DType -> Normalize(0.5, 0.5)
+//                                                       configs/generate_vgg.yaml:53-65
+//   GenerateMultipleSegments(16) + permute               models/data/transforms/video_transforms.py:114-240, vggsound_dataset.py:273-275
+// The resize is torch's separable antialiased triangle filter on uint8 (horizontal pass, rounded to uint8, then vertical pass, rounded
+// to uint8), in its fixed-point form: int16 taps scaled by 2^prec, acc = 2^(prec-1) + sum(tap * pixel), clamp(acc >> prec, 0, 255).
+// The taps, their start indices and both precisions are built on the host (vaura_amd/preprocess.py: tap_table) once per geometry;
+// the kernel does no filter geometry.  Only what survives the crop is computed: the crop_w kept columns of the source rows that the
+// kept output rows need.
+//
+// One kernel, both passes; the horizontally filtered rows of a tile live in LDS as uint8 and never touch memory.
+//   grid  (ceil(crop_h / tile_rows), B * S * F): one workgroup per (tile of output rows, output frame), all three channels
+//   phase 1 (per wave, one source row of one channel [NCHW] or of all three [NHWC] at a time): the row's needed byte range
+//           [x0, x0 + span) is copied to the wave's LDS slab with aligned 4-byte loads (4 pixels per lane; the aligned words that
+//           hold the first and last byte lie in the same pages as those bytes), then each lane filters 4 adjacent kept columns from
+//           the slab and writes them as one 4-byte word of the tile
+//   phase 2: each thread filters 4 adjacent columns of one output row vertically (one 4-byte LDS word per tap), maps the four uint8
+//           levels through the 256-entry table lut[c][level] = ((level / 255) - mean[c]) / std[c] (built by the host in fp32, so the
+//           device result is the host's to the bit) and stores 16 bytes.
+// Bytes per 360 x 640 -> 224 x 224 frame: read 3 x 318 of 360 rows x 319 of 640 columns = 0.30 MB (+ the rows adjacent tiles share,
+// which come from L2), write 3 x 224 x 224 x 4 = 0.60 MB.
+#include "common.h"
+
+#define PREPROC_MAX_TAPS VAURA_PREPROC_MAX_TAPS
+#define PREPROC_WAVES 4
+#define PREPROC_LDS_LIMIT (64 * 1024)
+
+struct PreprocArgs {
+  const uint8_t* src;
+  const int32_t* h_rel;   // (crop_w) first tap of kept column x, relative to x0
+  const int16_t* h_w;     // (crop_w, h_taps)
+  const int32_t* v_start; // (crop_h) first source row of kept output row r
+  const int16_t* v_w;     // (crop_h, v_taps)
+  const float* lut;       // (3, 256)
+  float* out;             // (B, S, 3, F, crop_h, crop_w)
+  int T, H, W, S, F, seg_start, seg_stride;
+  int crop_h, crop_w, h_taps, h_prec, v_taps, v_prec, x0, span, tile_rows, tile_src_rows, slab_dwords;
+};
+
+// acc >> prec as a uint8 level.  The taps are non-negative (the host builds triangle-filter taps only), so the accumulator never is
+// negative and the clamp is the upper one alone, taken unsigned.  Written this way on purpose: from the signed form
+// clamp(acc >> prec, 0, 255) of two neighbours hipcc 7.2 selects v_ashr_pk_u8_i32 for gfx950 and ORs the third byte into a
+// register whose bits 16..23 still hold the first accumulator (seen on the device: every third column of a group of four wrong).
+__device__ __forceinline__ uint32_t level_u8(int acc, int prec) {
+  const uint32_t v = (uint32_t)acc >> prec;
+  return v > 255u ? 255u : v;
+}
+
+// dynamic LDS of one workgroup: table (768 floats), first taps, horizontal taps, one row slab per wave, the tile
+static size_t preproc_lds_bytes(int channels_last, int crop_w, int h_taps, int span, int tile_src_rows) {
+  const size_t slab = (size_t)(((channels_last ? 3 : 1) * span + 3 + 3) >> 2);
+  return 4 * ((size_t)768 + crop_w + (((size_t)crop_w * h_taps) >> 1) + (size_t)PREPROC_WAVES * slab + (size_t)3 * tile_src_rows * (crop_w >> 2));
+}
+
+template <bool NHWC>
+__global__ __launch_bounds__(64 * PREPROC_WAVES) void video_preprocess_kernel(const PreprocArgs a) {
+  extern __shared__ uint32_t smem[];
+  const int nq = a.crop_w >> 2;                                       // 4-column groups per kept row
+  float* lut = reinterpret_cast<float*>(smem);                         // 768 floats
+  int32_t* hrel = reinterpret_cast<int32_t*>(smem + 768);              // crop_w
+  int16_t* hw = reinterpret_cast<int16_t*>(smem + 768 + a.crop_w);     // crop_w * h_taps (an even count: crop_w % 4 == 0)
+  uint32_t* slabs = smem + 768 + a.crop_w + ((a.crop_w * a.h_taps) >> 1);
+  uint32_t* tile = slabs + PREPROC_WAVES * a.slab_dwords;              // [3][tile_src_rows][nq] words of 4 uint8
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+
+  const int of = blockIdx.y;                                           // output frame (b, s, f)
+  const int f = of % a.F, bs = of / a.F, s = bs % a.S, b = bs / a.S;
+  const size_t n = (size_t)b * a.T + a.seg_start + s * a.seg_stride + f;   // source frame
+  const int r0 = blockIdx.x * a.tile_rows;
+  const int nr = min(a.tile_rows, a.crop_h - r0);
+  // source rows [ylo, ylo + nrows): clamped so that no table content can index outside the frame or the tile
+  const int ylo = min(max(a.v_start[r0], 0), a.H - a.v_taps);
+  const int nrows = min(a.tile_src_rows, a.H - ylo);
+
+  for (int i = tid; i < 768; i += 64 * PREPROC_WAVES) lut[i] = a.lut[i];
+  for (int i = tid; i < a.crop_w; i += 64 * PREPROC_WAVES) hrel[i] = min(max(a.h_rel[i], 0), a.span - a.h_taps);
+  for (int i = tid; i < a.crop_w * a.h_taps; i += 64 * PREPROC_WAVES) hw[i] = a.h_w[i];
+  __syncthreads();
+
+  // ---- phase 1: horizontal pass into the tile
+  uint32_t* slab = slabs + wave * a.slab_dwords;
+  const int jobs = NHWC ? nrows : 3 * nrows;
+  const int hhalf = 1 << (a.h_prec - 1);
+  for (int j0 = 0; j0 < jobs; j0 += PREPROC_WAVES) {
+    const int j = j0 + wave;                                           // wave-uniform
+    const int yy = NHWC ? j : j / 3, cj = NHWC ? 0 : j - 3 * yy;
+    int shift = 0;
+    if (j < jobs) {
+      const size_t row = NHWC ? ((n * a.H + (ylo + yy)) * a.W + a.x0) * 3 : ((n * 3 + cj) * a.H + (ylo + yy)) * a.W + a.x0;
+      const uintptr_t p = reinterpret_cast<uintptr_t>(a.src) + row;
+      shift = (int)(p & 3);
+      const uint32_t* pa = reinterpret_cast<const uint32_t*>(p - shift);
+      const int ndw = (shift + (NHWC ? 3 : 1) * a.span + 3) >> 2;       // <= slab_dwords
+      for (int i = lane; i < ndw; i += 64) slab[i] = pa[i];
+    }
+    __syncthreads();
+    if (j < jobs) {
+      const uint8_t* sb = reinterpret_cast<const uint8_t*>(slab) + shift;
+#pragma unroll 1
+      for (int c = NHWC ? 0 : cj; c < (NHWC ? 3 : cj + 1); ++c) {
+        for (int q = lane; q < nq; q += 64) {
+          uint32_t word = 0;
+#pragma unroll
+          for (int e = 0; e < 4; ++e) {
+            const int x = 4 * q + e;
+            const uint8_t* t = NHWC ? sb + 3 * hrel[x] + c : sb + hrel[x];
+            const int16_t* w = hw + x * a.h_taps;
+            int acc = hhalf;
+            for (int k = 0; k < a.h_taps; ++k) acc += (int)t[NHWC ? 3 * k : k] * (int)w[k];
+            word |= level_u8(acc, a.h_prec) << (8 * e);
+          }
+          tile[((size_t)c * a.tile_src_rows + yy) * nq + q] = word;
+        }
+      }
+    }
+    __syncthreads();
+  }
+
+  // ---- phase 2: vertical pass, level -> fp32 table, 16-byte stores
+  const int vhalf = 1 << (a.v_prec - 1);
+  const int items = 3 * nr * nq;
+  for (int it = tid; it < items; it += 64 * PREPROC_WAVES) {
+    const int q = it % nq, rc = it / nq, rr = rc % nr, c = rc / nr;
+    const int r = r0 + rr;
+    const int ys = min(max(a.v_start[r] - ylo, 0), nrows - a.v_taps);
+    const int16_t* w = a.v_w + (size_t)r * a.v_taps;
+    const uint32_t* t = tile + ((size_t)c * a.tile_src_rows + ys) * nq + q;
+    int a0 = vhalf, a1 = vhalf, a2 = vhalf, a3 = vhalf;
+    for (int k = 0; k < a.v_taps; ++k) {
+      const uint32_t d = t[(size_t)k * nq];
+      const int wk = w[k];
+      a0 += (int)(d & 255u) * wk;
+      a1 += (int)((d >> 8) & 255u) * wk;
+      a2 += (int)((d >> 16) & 255u) * wk;
+      a3 += (int)(d >> 24) * wk;
+    }
+    const float* l = lut + 256 * c;
+    const f32x4 o = {l[level_u8(a0, a.v_prec)], l[level_u8(a1, a.v_prec)], l[level_u8(a2, a.v_prec)], l[level_u8(a3, a.v_prec)]};
+    float* dst = a.out + ((((size_t)bs * 3 + c) * a.F + f) * a.crop_h + r) * a.crop_w + 4 * q;
+    *reinterpret_cast<f32x4*>(dst) = o;
+  }
+}
+
+extern "C" {
+
+int vaura_video_preprocess(const uint8_t* video, int channels_last, int n_clips, int T, int C, int H, int W, int resize, int crop_h,
+                           int crop_w, int F, int S, int seg_start, int seg_stride, const int32_t* h_rel, const int16_t* h_w, int h_taps,
+                           int h_prec, const int32_t* v_start, const int16_t* v_w, int v_taps, int v_prec, int x0, int span,
+                           int tile_rows, int tile_src_rows, const float* lut, float* out, vaura_stream_t s) {
+  if (!video || !h_rel || !h_w || !v_start || !v_w || !lut || !out) return VAURA_ERR_ARG;
+  if (n_clips <= 0 || T <= 0 || H <= 0 || W <= 0 || resize <= 0 || crop_h <= 0 || crop_w <= 0 || F <= 0) return VAURA_ERR_ARG;
+  if (C != 3) return VAURA_ERR_SHAPE;
+  // torchvision's Resize(int): the short side to `resize`, the long side to int(resize * long / short)
+  const int lng = H > W ? H : W, sht = H > W ? W : H;
+  const int rl = (int)((double)resize * (double)lng / (double)sht);
+  const int oh = H <= W ? resize : rl, ow = H <= W ? rl : resize;
+  if (crop_h > oh || crop_w > ow || (crop_w & 3)) return VAURA_ERR_SHAPE;
+  if (T < F) return VAURA_ERR_SHAPE;
+  if (h_taps > PREPROC_MAX_TAPS || v_taps > PREPROC_MAX_TAPS) return VAURA_ERR_SHAPE;
+  if (S <= 0 || seg_start < 0 || seg_stride <= 0 || (int64_t)seg_start + (int64_t)(S - 1) * seg_stride + F > T) return VAURA_ERR_SHAPE;
+  if (h_taps <= 0 || v_taps <= 0 || h_prec <= 0 || h_prec > 22 || v_prec <= 0 || v_prec > 22) return VAURA_ERR_ARG;
+  if (x0 < 0 || span < h_taps || (int64_t)x0 + span > W || v_taps > H) return VAURA_ERR_ARG;
+  if (tile_rows <= 0 || tile_src_rows < v_taps || tile_src_rows > H) return VAURA_ERR_ARG;
+  if ((reinterpret_cast<uintptr_t>(out) & 15) || (reinterpret_cast<uintptr_t>(h_rel) & 3) || (reinterpret_cast<uintptr_t>(v_start) & 3) ||
+      (reinterpret_cast<uintptr_t>(h_w) & 1) || (reinterpret_cast<uintptr_t>(v_w) & 1) || (reinterpret_cast<uintptr_t>(lut) & 3))
+    return VAURA_ERR_ARG;
+  const int64_t frames_out = (int64_t)n_clips * S * F;
+  if (frames_out > 65535) return VAURA_ERR_SHAPE;                      // gridDim.y
+  PreprocArgs a;
+  a.src = video; a.h_rel = h_rel; a.h_w = h_w; a.v_start = v_start; a.v_w = v_w; a.lut = lut; a.out = out;
+  a.T = T; a.H = H; a.W = W; a.S = S; a.F = F; a.seg_start = seg_start; a.seg_stride = seg_stride;
+  a.crop_h = crop_h; a.crop_w = crop_w; a.h_taps = h_taps; a.h_prec = h_prec; a.v_taps = v_taps; a.v_prec = v_prec;
+  a.x0 = x0; a.span = span; a.tile_rows = tile_rows; a.tile_src_rows = tile_src_rows;
+  a.slab_dwords = ((channels_last ? 3 : 1) * span + 3 + 3) >> 2;
+  const size_t lds = preproc_lds_bytes(channels_last, crop_w, h_taps, span, tile_src_rows);
+  if (lds > PREPROC_LDS_LIMIT) return VAURA_ERR_SHAPE;
+  const dim3 grid((unsigned)((crop_h + tile_rows - 1) / tile_rows), (unsigned)frames_out);
+  hipStream_t st = as_stream(s);
+  if (channels_last) VA_LAUNCH(video_preprocess_kernel<true>, grid, dim3(64 * PREPROC_WAVES), lds, st, a);
+  else VA_LAUNCH(video_preprocess_kernel<false>, grid, dim3(64 * PREPROC_WAVES), lds, st, a);
+  return 0;
+}
+
+size_t vaura_video_preprocess_lds_bytes(int channels_last, int crop_w, int h_taps, int span, int tile_src_rows) {
+  if (crop_w <= 0 || (crop_w & 3) || h_taps <= 0 || span <= 0 || tile_src_rows <= 0) return 0;
+  return preproc_lds_bytes(channels_last, crop_w, h_taps, span, tile_src_rows);
+}
+
+}  // extern "C"

@@ -196,6 +196,24 @@ class VAURAModel(nn.Module):
             vis_feats = self.visual_feature_extractor(frames)
         return self.visual_bridge(vis_feats.detach())
 
+    def frames_from_video(self, video, video_transforms=None, channels_last: bool = False, **segment_kw) -> torch.Tensor:
+        """Decoded uint8 video -> what ``generate(frames=...)`` takes: (B, S, 3, 16, 224, 224) fp32 on the sampler's device.
+        ``video``: uint8 (B, T, C, H, W), (T, C, H, W) or a list of per-clip tensors (``channels_last``: (.., H, W, C)).
+        ``video_transforms``: the ``video_transforms_test`` list of configs/generate_*.yaml (Resize -> CenterCrop -> ToFloat32DType ->
+        Normalize); None = its values in generate_vgg.yaml:53-65.  ``segment_kw``: segment_size_vframes / n_segments / step_size_seg
+        of GenerateMultipleSegments.  The preprocessor (tap tables, device copies) is built once per distinct configuration."""
+        from .preprocess import VideoPreprocessor
+        key = (repr(_plain(video_transforms)) if video_transforms is not None else None, bool(channels_last),
+               tuple(sorted(segment_kw.items())))
+        cache = self.__dict__.setdefault("_video_preprocessors", {})
+        if key not in cache:
+            kw = dict(segment_kw, channels_last=channels_last)
+            cache[key] = (VideoPreprocessor(**kw) if video_transforms is None
+                          else VideoPreprocessor.from_transforms_config(_plain(video_transforms), **kw))
+        pre = cache[key]
+        pre.device = self.device
+        return pre(video)
+
     def _pattern_delays(self, timesteps: int) -> List[int]:
         """The codebook delays of ``pattern_provider.get_pattern(timesteps)`` — the only layouts the decode loop implements
         (codebook_patterns.py:374-419: DelayedPatternProvider, ParallelPatternProvider).  Anything else — a pattern object without

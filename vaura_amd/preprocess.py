@@ -1,0 +1,371 @@
+"""Video preprocessing on the device: decoded uint8 frames -> the feature extractor's input.
+
+What the reference's data loader does on the CPU with the ``video_transforms_test`` list of ``configs/generate_*.yaml``
+(generate_vgg.yaml:53-65) and ``GenerateMultipleSegments`` + permute (models/data/vggsound_dataset.py:233, 273-275):
+
+    Resize(256, antialias=True) -> CenterCrop([224, 224]) -> ToFloat32DType -> Normalize(0.5, 0.5) -> segments of 16 frames
+
+runs here as one launch of ``vaura_video_preprocess`` (csrc/preproc.hip) per source geometry.
+
+Arithmetic.  For tensors ``torchvision.transforms.v2.Resize`` is ``torch.nn.functional.interpolate(mode="bilinear", antialias=True)``,
+and on uint8 torch resamples in fixed point: per axis, float64 triangle-filter taps normalised to sum 1, scaled by ``2^prec`` (the
+largest ``prec`` <= 22 whose largest tap stays below 2^15) and rounded to int16; a pixel is
+``clamp((2^(prec-1) + sum(tap * src)) >> prec, 0, 255)``; the horizontal pass comes first and its result is uint8 again before the
+vertical pass.  ``tap_table`` restates that; ``reference_u8`` applies it on the CPU; the kernel applies the same tables.  On every
+geometry the tests use, ``reference_u8`` equals torch's uint8 path on every pixel.
+
+Segments (video_transforms.py:146-156, 205-236, ``is_start_random=False``, video only): ``stride = int(step_size_seg * F)``,
+``S = floor((T - F) / stride) + 1`` (or ``n_segments``), and the run of segments is CENTRED in the clip: it starts at frame
+``(T - int((S * step + 1 - step) * F)) // 2``; segment ``s`` holds frames ``start + s * stride .. + F``.  Frames outside are dropped.
+"""
+from __future__ import annotations
+
+import math
+from typing import Dict, List, Optional, Sequence, Tuple, Union
+
+import numpy as np
+import torch
+
+from . import _lib as L
+
+MAX_TAPS = 32                       # VAURA_PREPROC_MAX_TAPS (include/vaura_hip.h)
+_LDS_TARGET = 48 * 1024             # tile_rows is the largest power of two <= 32 whose workgroup stays below this
+_LDS_LIMIT = 64 * 1024
+
+_RESIZE = "torchvision.transforms.v2.Resize"
+_CROP = "torchvision.transforms.v2.CenterCrop"
+_NORM = "torchvision.transforms.v2.Normalize"
+# ToFloat32DType (video_transforms.py:68-78) is v2.ConvertDtype(float32) or, on newer torchvision, v2.ToDtype(float32, scale=True)
+_TOFLOAT = ("models.data.transforms.video_transforms.ToFloat32DType", "vaura_amd.preprocess.ToFloat32DType",
+            "torchvision.transforms.v2.ConvertDtype", "torchvision.transforms.v2.ConvertImageDtype", "torchvision.transforms.v2.ToDtype")
+
+
+class ToFloat32DType:
+    """Name holder: ``target: vaura_amd.preprocess.ToFloat32DType`` is accepted where the reference's class is named."""
+
+
+def resized_size(H: int, W: int, resize: int) -> Tuple[int, int]:
+    """torchvision's Resize(int): the short side to ``resize``, the long side to ``int(resize * long / short)``."""
+    short, long = (W, H) if W <= H else (H, W)
+    new_long = int(resize * long / short)
+    return (new_long, resize) if W <= H else (resize, new_long)
+
+
+def crop_offset(size: int, crop: int) -> int:
+    """torchvision's center_crop: ``int(round((size - crop) / 2.0))`` (Python's round: half to even)."""
+    return int(round((size - crop) / 2.0))
+
+
+def tap_table(in_size: int, out_size: int, lo: int = 0, n: Optional[int] = None) -> dict:
+    """Fixed-point taps of torch's antialiased bilinear resample of one axis, for output indices ``lo .. lo + n``.
+
+    Returns ``start`` (n,) int32, ``length`` (n,) int32, ``weights`` (n, taps) int16, ``weights_f64`` (n, taps), ``taps``, ``prec``.
+    The precision is decided by the largest tap over the WHOLE axis (as torch does), not over the kept range.  Rows near the border
+    are shifted so that ``start + taps <= in_size`` for every row (zero taps fill the front); ``start + length`` is where the last
+    non-zero tap may sit.  ``in_size == out_size`` (no resize on this axis) is the identity: one tap of 2^14.
+    """
+    n = out_size - lo if n is None else n
+    if in_size == out_size:
+        idx = np.arange(lo, lo + n, dtype=np.int32)
+        return {"start": idx, "length": np.ones(n, np.int32), "weights": np.full((n, 1), 1 << 14, np.int16),
+                "weights_f64": np.ones((n, 1)), "taps": 1, "prec": 14}
+    scale = in_size / out_size
+    support = scale if scale >= 1.0 else 1.0
+    invscale = 1.0 / scale if scale >= 1.0 else 1.0
+    K = int(math.ceil(np.float32(support))) * 2 + 1
+    w = np.zeros((out_size, K))
+    start = np.zeros(out_size, np.int64)
+    length = np.zeros(out_size, np.int64)
+    for i in range(out_size):
+        center = scale * (i + 0.5)
+        xmin = max(int(center - support + 0.5), 0)
+        xsize = min(max(min(int(center + support + 0.5), in_size) - xmin, 0), K)
+        total = 0.0
+        for j in range(xsize):
+            d = abs((j + xmin - center + 0.5) * invscale)
+            w[i, j] = 1.0 - d if d < 1.0 else 0.0
+            total += w[i, j]
+        if total != 0.0:
+            w[i, :xsize] /= total
+        start[i], length[i] = xmin, xsize
+    wmax = float(w.max())
+    prec = 0
+    while prec < 22 and int(0.5 + wmax * (1 << (prec + 1))) < (1 << 15):
+        prec += 1
+    wi = np.trunc(w * (1 << prec) + 0.5).astype(np.int64)            # bilinear taps are never negative
+    # keep the asked range, then make every row read exactly `taps` source elements inside [0, in_size)
+    w, wi, start, length = w[lo:lo + n], wi[lo:lo + n], start[lo:lo + n], length[lo:lo + n]
+    taps = min(K, in_size)
+    new_start = np.minimum(start, in_size - taps)
+    shift = start - new_start
+    wf2, wi2 = np.zeros((n, taps)), np.zeros((n, taps), np.int64)
+    for i in range(n):
+        m = min(int(length[i]), taps - int(shift[i]))
+        wf2[i, shift[i]:shift[i] + m] = w[i, :m]
+        wi2[i, shift[i]:shift[i] + m] = wi[i, :m]
+    return {"start": new_start.astype(np.int32), "length": (length + shift).astype(np.int32), "weights": wi2.astype(np.int16),
+            "weights_f64": wf2, "taps": int(taps), "prec": int(prec)}
+
+
+def segment_starts(T: int, F: int, step_size_seg: float = 1.0, n_segments: Optional[int] = None) -> Tuple[int, int, int]:
+    """(S, first frame, stride) of GenerateMultipleSegments with ``is_start_random=False`` (see the module docstring)."""
+    stride = int(step_size_seg * F)
+    if F < 1 or stride < 1:
+        raise L.VauraHipError(f"segments of {F} frames with step {step_size_seg}: the stride must be at least one frame")
+    if T < F:
+        raise L.VauraHipError(f"a clip of {T} frames is shorter than one segment of {F} frames")
+    s_max = math.floor((T - F) / stride) + 1
+    S = s_max if n_segments is None else int(n_segments)
+    if S < 1 or S > s_max:
+        raise L.VauraHipError(f"cannot make {S} segments of {F} frames (stride {stride}) from {T} frames: at most {s_max}")
+    seq = int((S * step_size_seg + (1 - step_size_seg)) * F)
+    return S, (T - seq) // 2, stride
+
+
+class _Geometry:
+    """Tables of one (H, W, resize, crop): host copies, and device copies per device."""
+
+    def __init__(self, H: int, W: int, resize: int, crop: Tuple[int, int]):
+        self.H, self.W, self.resize, self.crop = H, W, resize, crop
+        ch, cw = crop
+        oh, ow = resized_size(H, W, resize)
+        if ch > oh or cw > ow:
+            raise L.VauraHipError(f"crop {crop} is larger than the resized image {(oh, ow)} of a {H} x {W} source")
+        if cw % 4:
+            raise L.VauraHipError(f"crop width {cw}: the kernel writes 4 columns per store (multiples of 4 only)")
+        self.out_hw = (oh, ow)
+        self.top, self.left = crop_offset(oh, ch), crop_offset(ow, cw)
+        self.h = tap_table(W, ow, self.left, cw)
+        self.v = tap_table(H, oh, self.top, ch)
+        if self.h["taps"] > MAX_TAPS or self.v["taps"] > MAX_TAPS:
+            raise L.VauraHipError(f"{H} x {W} -> {oh} x {ow} needs {max(self.h['taps'], self.v['taps'])} taps per pixel; the kernel "
+                                  f"is compiled for at most {MAX_TAPS}")
+        self.x0 = int(self.h["start"].min())
+        self.span = int(self.h["start"].max()) + self.h["taps"] - self.x0
+        self.h_rel = (self.h["start"] - self.x0).astype(np.int32)
+        self._dev: Dict[str, tuple] = {}
+        self._tiles: Dict[bool, Tuple[int, int]] = {}
+
+    def tile_src_rows(self, tile_rows: int) -> int:
+        st, ch, k = self.v["start"], self.crop[0], self.v["taps"]
+        return max(int(st[min(r0 + tile_rows, ch) - 1]) + k - int(st[r0]) for r0 in range(0, ch, tile_rows))
+
+    def tiles(self, channels_last: bool) -> Tuple[int, int]:
+        """(tile_rows, tile_src_rows): the largest power of two <= 32 output rows whose workgroup stays below the LDS target."""
+        if channels_last not in self._tiles:
+            lib = L.lib()
+            pick = None
+            for tr in (32, 16, 8, 4, 2, 1):
+                rows = self.tile_src_rows(tr)
+                need = lib.vaura_video_preprocess_lds_bytes(int(channels_last), self.crop[1], self.h["taps"], self.span, rows)
+                if need <= _LDS_TARGET or (tr == 1 and need <= _LDS_LIMIT):
+                    pick = (tr, rows)
+                    break
+            if pick is None:
+                raise L.VauraHipError(f"a {self.H} x {self.W} source does not fit the kernel's {_LDS_LIMIT // 1024} KiB of LDS at one "
+                                      "output row per workgroup")
+            self._tiles[channels_last] = pick
+        return self._tiles[channels_last]
+
+    def device_tables(self, dev: torch.device):
+        key = str(dev)
+        if key not in self._dev:
+            up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)  # noqa: E731
+            self._dev[key] = (up(self.h_rel), up(self.h["weights"]), up(self.v["start"]), up(self.v["weights"]))
+        return self._dev[key]
+
+
+def _resample_axis(x: torch.Tensor, tab: dict, axis: int) -> torch.Tensor:
+    """x int32; one pass of the fixed-point resample along ``axis`` for the rows of ``tab``."""
+    x = x.movedim(axis, -1)
+    start = torch.from_numpy(tab["start"].astype(np.int64))
+    w = torch.from_numpy(tab["weights"].astype(np.int32))
+    acc = torch.full(x.shape[:-1] + (len(start),), 1 << (tab["prec"] - 1), dtype=torch.int32)
+    for k in range(tab["taps"]):
+        acc += x.index_select(-1, start + k) * w[:, k]
+    return (acc >> tab["prec"]).clamp_(0, 255).movedim(-1, axis)
+
+
+class VideoPreprocessor:
+    def __init__(self, resize: int = 256, crop: Sequence[int] = (224, 224), mean: Sequence[float] = (0.5, 0.5, 0.5),
+                 std: Sequence[float] = (0.5, 0.5, 0.5), segment_size_vframes: int = 16, n_segments: Optional[int] = None,
+                 step_size_seg: float = 1.0, channels_last: bool = False, device: Union[str, torch.device, None] = None):
+        if isinstance(crop, int):
+            crop = (crop, crop)
+        if isinstance(resize, (list, tuple)):
+            if len(resize) != 1:
+                raise L.VauraHipError(f"Resize(size={list(resize)}): only the int form (short side) is built")
+            resize = resize[0]
+        self.resize, self.crop = int(resize), (int(crop[0]), int(crop[1]))
+        mean = [float(mean)] * 3 if isinstance(mean, (int, float)) else [float(m) for m in mean]
+        std = [float(std)] * 3 if isinstance(std, (int, float)) else [float(s) for s in std]
+        if len(mean) != 3 or len(std) != 3 or any(s == 0 for s in std):
+            raise L.VauraHipError(f"Normalize(mean={mean}, std={std}): three values each, std non-zero")
+        self.mean, self.std = tuple(mean), tuple(std)
+        self.segment_size_vframes, self.n_segments, self.step_size_seg = int(segment_size_vframes), n_segments, float(step_size_seg)
+        self.channels_last = bool(channels_last)
+        self.device = None if device is None else torch.device(device)
+        self._geo: Dict[Tuple[int, int], _Geometry] = {}
+        self._lut_dev: Dict[str, torch.Tensor] = {}
+        # lut[c, level] = ((level / 255) - mean[c]) / std[c], in fp32, in that order
+        lv = torch.arange(256, dtype=torch.float32) / 255
+        self.lut = torch.stack([(lv - torch.tensor(m, dtype=torch.float32)) / torch.tensor(s, dtype=torch.float32)
+                                for m, s in zip(self.mean, self.std)]).contiguous()
+
+    # ---- configuration
+    @classmethod
+    def from_transforms_config(cls, transforms: Sequence[dict], **segment_kw) -> "VideoPreprocessor":
+        """From the reference's ``video_transforms_test`` list (configs/generate_vgg.yaml:53-65) as plain data."""
+        kw: dict = {}
+        seen: List[str] = []
+        for entry in transforms:
+            target = entry.get("target") if hasattr(entry, "get") else None
+            params = dict(entry.get("params", None) or {}) if target is not None else {}
+            if target == _RESIZE:
+                if not params.get("antialias", False):
+                    raise L.VauraHipError(f"{_RESIZE} without antialias=true is not built (the kernel is the antialiased filter)")
+                interp = str(params.get("interpolation", "bilinear")).lower()
+                if interp not in ("bilinear", "interpolationmode.bilinear", "2"):
+                    raise L.VauraHipError(f"{_RESIZE}: interpolation {params['interpolation']!r} is not built (bilinear only)")
+                if params.get("max_size") is not None:
+                    raise L.VauraHipError(f"{_RESIZE}: max_size is not built")
+                kw["resize"] = params["size"]
+            elif target == _CROP:
+                kw["crop"] = params["size"]
+            elif target in _TOFLOAT:
+                if str(params.get("dtype", "float32")).replace("torch.", "") != "float32":
+                    raise L.VauraHipError(f"{target}: dtype {params['dtype']!r} is not built (float32 only)")
+                if target.endswith(".ToDtype") and not params.get("scale", False):
+                    raise L.VauraHipError(f"{target} without scale=true leaves levels 0..255; the kernel scales by 1/255")
+            elif target == _NORM:
+                kw["mean"], kw["std"] = params["mean"], params["std"]
+            else:
+                raise L.VauraHipError(f"video transform {target!r} is not built; VideoPreprocessor takes {_RESIZE}, {_CROP}, "
+                                      f"ToFloat32DType and {_NORM}")
+            seen.append(_TOFLOAT[0] if target in _TOFLOAT else target)
+        if seen != [_RESIZE, _CROP, _TOFLOAT[0], _NORM]:
+            raise L.VauraHipError("video transforms must be Resize -> CenterCrop -> ToFloat32DType -> Normalize, in that order; got "
+                                  f"{[str(t).rsplit('.', 1)[-1] for t in seen]}")
+        return cls(**kw, **segment_kw)
+
+    def geometry(self, H: int, W: int) -> _Geometry:
+        if (H, W) not in self._geo:
+            self._geo[(H, W)] = _Geometry(H, W, self.resize, self.crop)
+        return self._geo[(H, W)]
+
+    # ---- input handling
+    def _clips(self, video) -> List[torch.Tensor]:
+        """-> list of (b, T, C, H, W) / (b, T, H, W, C) uint8 tensors, one per group of consecutive clips of one shape."""
+        items = list(video) if isinstance(video, (list, tuple)) else [video]
+        if not items:
+            raise L.VauraHipError("VideoPreprocessor: no clips")
+        out = []
+        for v in items:
+            if not torch.is_tensor(v):
+                raise L.VauraHipError(f"VideoPreprocessor takes uint8 tensors, got {type(v).__name__}")
+            if v.dtype != torch.uint8:
+                raise L.VauraHipError(f"VideoPreprocessor takes decoded uint8 frames; a {v.dtype} input has been transformed already")
+            if isinstance(video, (list, tuple)):
+                if v.dim() != 4:
+                    raise L.VauraHipError(f"clips of a list are (T, C, H, W) or (T, H, W, C); got {tuple(v.shape)}")
+                v = v[None]
+            elif v.dim() == 4:
+                v = v[None]
+            elif v.dim() != 5:
+                raise L.VauraHipError(f"video must be (B, T, C, H, W) or (T, C, H, W) (channels last: (.., H, W, C)); got {tuple(v.shape)}")
+            out.append(v)
+        return out
+
+    def _dims(self, v: torch.Tensor) -> Tuple[int, int, int, int, int]:
+        b, T = v.shape[:2]
+        C, H, W = (v.shape[4], v.shape[2], v.shape[3]) if self.channels_last else tuple(v.shape[2:])
+        if C != 3:
+            raise L.VauraHipError(f"video has {C} channels ({'last' if self.channels_last else 'first'} layout expected); 3 are needed")
+        return b, T, C, H, W
+
+    # ---- CPU restatement
+    def reference_u8(self, video) -> torch.Tensor:
+        """The kernel's integer arithmetic on the CPU with the same tap tables: uint8 levels (B, S, C, F, h, w) before the scaling."""
+        outs = []
+        for v in self._clips(video):
+            b, T, C, H, W = self._dims(v)
+            g = self.geometry(H, W)
+            S, first, stride = segment_starts(T, self.segment_size_vframes, self.step_size_seg, self.n_segments)
+            x = v.cpu()
+            if self.channels_last:
+                x = x.permute(0, 1, 4, 2, 3)
+            # rows the kept output rows need, then both passes (horizontal first, uint8 in between)
+            y0, y1 = int(g.v["start"].min()), int(g.v["start"].max()) + g.v["taps"]
+            x = x[..., y0:y1, :].to(torch.int32)
+            x = _resample_axis(x, g.h, -1)
+            vt = dict(g.v, start=g.v["start"] - y0)
+            x = _resample_axis(x, vt, -2).to(torch.uint8)                   # (b, T, C, h, w)
+            F = self.segment_size_vframes
+            seg = torch.stack([x[:, first + s * stride: first + s * stride + F] for s in range(S)], dim=1)   # (b, S, F, C, h, w)
+            outs.append(seg.permute(0, 1, 3, 2, 4, 5).contiguous())
+        return self._cat(outs)
+
+    def scale_normalize(self, u8: torch.Tensor) -> torch.Tensor:
+        """uint8 levels (B, S, C, F, h, w) -> ``((u8 / 255) - mean) / std`` in fp32, in that order (CPU)."""
+        x = u8.cpu().to(torch.float32) / 255
+        m = torch.tensor(self.mean, dtype=torch.float32).view(1, 1, 3, 1, 1, 1)
+        s = torch.tensor(self.std, dtype=torch.float32).view(1, 1, 3, 1, 1, 1)
+        return (x - m) / s
+
+    @staticmethod
+    def _cat(outs: List[torch.Tensor]) -> torch.Tensor:
+        if len({tuple(o.shape[1:]) for o in outs}) != 1:
+            raise L.VauraHipError(f"clips of one call must give the same number of segments; got shapes {[tuple(o.shape) for o in outs]}")
+        return outs[0] if len(outs) == 1 else torch.cat(outs, dim=0)
+
+    # ---- device path
+    def _launch(self, v: torch.Tensor, out: torch.Tensor, dev: torch.device) -> None:
+        b, T, C, H, W = self._dims(v)
+        g = self.geometry(H, W)
+        S, first, stride = segment_starts(T, self.segment_size_vframes, self.step_size_seg, self.n_segments)
+        if tuple(out.shape) != (b, S, 3, self.segment_size_vframes, *self.crop):
+            raise L.VauraHipError(f"clips of one call must give the same number of segments; this group gives {S}, the first {out.shape[1]}")
+        tile_rows, tile_src = g.tiles(self.channels_last)
+        h_rel, h_w, v_start, v_w = g.device_tables(dev)
+        key = str(dev)
+        if key not in self._lut_dev:
+            self._lut_dev[key] = self.lut.to(dev)
+        L.check(L.lib().vaura_video_preprocess(
+            L.ptr(v), int(self.channels_last), b, T, C, H, W, self.resize, self.crop[0], self.crop[1], self.segment_size_vframes, S,
+            first, stride, L.ptr(h_rel), L.ptr(h_w), g.h["taps"], g.h["prec"], L.ptr(v_start), L.ptr(v_w), g.v["taps"], g.v["prec"],
+            g.x0, g.span, tile_rows, tile_src, L.ptr(self._lut_dev[key]), L.ptr(out), L.current_stream(dev)), "vaura_video_preprocess")
+
+    @torch.no_grad()
+    def __call__(self, video) -> torch.Tensor:
+        """uint8 (B, T, C, H, W), (T, C, H, W) or a list of per-clip (T, C, H, W) tensors whose H, W may differ (channels last:
+        (.., H, W, C)) -> fp32 (B, S, C, F, crop_h, crop_w) on the device.  Host tensors are copied once, as uint8."""
+        clips = self._clips(video)
+        dev = self.device
+        if dev is None:
+            dev = next((v.device for v in clips if v.device.type == "cuda"), None)
+            if dev is None:
+                if not torch.cuda.is_available():
+                    raise L.VauraHipError("VideoPreprocessor runs on a HIP device only (reference_u8 is the CPU restatement)")
+                dev = torch.device("cuda", torch.cuda.current_device())
+        # one launch per run of consecutive clips of one geometry (the output keeps the clips' order)
+        groups: List[List[torch.Tensor]] = []
+        for v in clips:
+            if groups and tuple(groups[-1][0].shape[1:]) == tuple(v.shape[1:]):
+                groups[-1].append(v)
+            else:
+                groups.append([v])
+        for grp in groups:                                                   # every refusal before any device work
+            _, T, _, H, W = self._dims(grp[0])
+            self.geometry(H, W)
+            segment_starts(T, self.segment_size_vframes, self.step_size_seg, self.n_segments)
+        S = segment_starts(clips[0].shape[1], self.segment_size_vframes, self.step_size_seg, self.n_segments)[0]
+        B = sum(v.shape[0] for v in clips)
+        with torch.cuda.device(dev):
+            out = torch.empty(B, S, 3, self.segment_size_vframes, *self.crop, dtype=torch.float32, device=dev)
+            b0 = 0
+            for grp in groups:
+                grp = [v.to(dev, non_blocking=True) for v in grp]               # uint8 over the link, once
+                v = (grp[0] if len(grp) == 1 else torch.cat(grp, dim=0)).contiguous()
+                self._launch(v, out[b0:b0 + v.shape[0]], dev)                  # same stream as the copy: v may be freed after it
+                b0 += v.shape[0]
+        return out
