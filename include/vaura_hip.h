@@ -132,7 +132,8 @@ typedef struct vaura_decoder {
                               VAURA_STATUS_NONFINITE_LOGITS.  0 = the layout every parity number was taken on */
   int32_t kv_dtype;        /* 0: the K / V cache is fp32 (every parity number).  1 (round 6; the low-precision serving configuration, BASELINE
                               configs[4]): fp16 — kcache / vcache then point at (n_layer, rows, n_head, max_len, head_dim) HALVES holding
-                              fp16(rotated k) / fp16(v); caches of at most 256 positions only (VAURA_ERR_SHAPE otherwise); tolerance reported.
+                              fp16(rotated k) / fp16(v); caches of at most 256 positions only (VAURA_ERR_SHAPE otherwise, from the descriptor check and from
+                              the decode-step and prefill attention launchers alike); tolerance reported.
                               2: OCP e4m3 bytes of the same layout (unscaled, saturating at +-448): a quarter of the fp32 stream, ~1e-2 class */
 
   const vaura_layer_weights* layers_host; /* HOST array [n_layer] of device pointers */
@@ -323,6 +324,22 @@ int vaura_attention_step_split(const float* qkv, const float* rope, float* kcach
                                int rows, int n_head, int head_dim, int max_len, int pos, int n_split, vaura_stream_t s);
 /* workgroups per (row, head) the decode step uses for this shape when ws_attn_part is given (1 = no split) */
 int vaura_attention_splits(int rows, int n_head, int max_len);
+/* Op-level access for parity tests: ONE decode-step attention with every optional the step passes, through the step's own launcher.
+ * qkv2 (NULL ok): the second K-half partial of a split qkv GEMV, added to qkv on load.  out_split (NULL ok): split rows (hi, lo fp16 planes)
+ * of out * 2^-plane_shift; the fp32 `out` is never scaled.  n_split 1..8: > 1 splits the cached range like vaura_attention_step_split
+ * (`part` as there); with `arrivals` (rows * n_head zeroed words; left at zero) the last split to arrive merges inside the launch, with
+ * NULL a combine launch follows.  kv_dtype as vaura_decoder.kv_dtype: kcache / vcache hold fp32, fp16 or e4m3 elements;
+ * the narrow caches take max_len <= 256 and no split (VAURA_ERR_SHAPE otherwise, nothing is launched).                              */
+int vaura_attention_step_ex(const float* qkv, const float* qkv2, const float* rope, float* kcache, float* vcache, float* out,
+                            uint16_t* out_split, float* part, uint32_t* arrivals, int rows, int n_head, int head_dim, int max_len,
+                            int pos, int n_split, int plane_shift, int kv_dtype, vaura_stream_t s);
+/* Op-level access for parity tests: the attention of a teacher-forced chunk [p0, p0 + n_pos) of one layer — rope(q, k) + K / V append of
+ * the chunk, then its causal attention over cache positions [0, p0 + n_pos) — on a caller-filled descriptor.  Read: dims (n_layer, n_head,
+ * d_model = 96 n_head), rows, max_len, kv_dtype, plane_shift, rope, ws_qkv (packed rows: position z of the chunk is row block(s)
+ * z * rows16 .. ; q is rotated in place), kcache, vcache, ws_attn, ws_attn_split (NULL ok).  VAURA_ERR_ARG: null pointers, p0 < 0,
+ * n_pos <= 0, p0 + n_pos > max_len; VAURA_ERR_SHAPE: head_dim != 96, or a narrow cache (kv_dtype != 0) of more than 256 positions.
+ * Debug flag bit 4 selects the per-position kernel (fp32 cache).                                                                      */
+int vaura_attention_prefill(const vaura_decoder* d, int layer, int p0, int n_pos, vaura_stream_t s);
 
 /* -------------------------------------------------------------------------------------------
  * a16 DacModelWrapper.decode (models/modules/dac/model.py:41-48): quantizer.from_codes + DAC

@@ -266,11 +266,12 @@ def test_gemv_rejects_unsupported_shapes():
     assert rc == -2  # depth not compiled -> VAURA_ERR_SHAPE
 
 
-@pytest.mark.parametrize("rows,steps", [(2, 5), (16, 40), (3, 130)])
-def test_attention_step_matches_oracle(rows, steps):
+@pytest.mark.parametrize("rows,steps,max_len", [(2, 5, 160), (16, 40, 160), (3, 130, 160), (2, 256, 256)],
+                         ids=["2-5", "16-40", "3-130", "2-256-256"])
+def test_attention_step_matches_oracle(rows, steps, max_len):
+    """The last case appends all 256 positions of a 256-position cache: the NU = 4 body and the last slot on the sequential-append path."""
     from oracle.decoder_oracle import apply_rope, rope_table
     H, hd, D = 16, 96, 1536
-    max_len = 160
     g = torch.Generator().manual_seed(rows + steps)
     rope = rope_table(max_len, hd)
     kc = torch.zeros(rows, H, max_len, hd, device=DEV)
@@ -329,6 +330,9 @@ def test_range_split_attention_matches_oracle(rows, n_split):
                 assert torch.equal(kc[:, :, :pos].cpu(), k_ref[:, :, :pos])
     assert L.lib().vaura_attention_splits(4, 16, 1024) == 4 and L.lib().vaura_attention_splits(16, 16, 1024) == 1
     assert L.lib().vaura_attention_splits(4, 16, 256) == 1 and L.lib().vaura_attention_splits(1, 16, 1024) == 8
+    # boundary rows of va_attention_splits: 256 (row, head) pairs and max_len = 257 are the first shapes on the other side
+    assert L.lib().vaura_attention_splits(15, 16, 1024) == 1 and L.lib().vaura_attention_splits(16, 16, 257) == 1
+    assert L.lib().vaura_attention_splits(8, 16, 1024) == 2 and L.lib().vaura_attention_splits(4, 16, 257) == 4
 
 
 SAMPLE_CASES = [("topk1", dict(top_k=1, top_p=0.0)), ("topk128", dict(top_k=128, top_p=0.0)),

@@ -949,6 +949,7 @@ int va_launch_attention(const float* qkv, const float* qkv2, const float* rope, 
 int va_launch_rope_append(const vaura_decoder* d, int layer, int p0, int n_pos, hipStream_t s) {
   const int H = d->dims.n_head, hd = d->dims.d_model / H;
   if (hd != 96) return VAURA_ERR_SHAPE;
+  if (d->kv_dtype != 0 && d->max_len > 256) return VAURA_ERR_SHAPE;   // as va_launch_attention: the step that follows would refuse this cache
   const size_t kv_layer = (size_t)d->rows * H * (size_t)d->max_len * hd;
   if (d->kv_dtype == 1 || d->kv_dtype == 2) {      // fp16 / fp8 cache: the layer offset in elements of that type
     if (d->kv_dtype == 1)
@@ -968,6 +969,7 @@ extern unsigned va_debug_flags;   // gemv3.hip; bit 4: the per-position prefill 
 int va_launch_attention_prefill(const vaura_decoder* d, int layer, int p0, int n_pos, hipStream_t s) {
   const int H = d->dims.n_head, hd = d->dims.d_model / H;
   if (hd != 96) return VAURA_ERR_SHAPE;
+  if (d->kv_dtype != 0 && d->max_len > 256) return VAURA_ERR_SHAPE;   // as va_launch_attention (see va_launch_rope_append)
   const size_t kv_layer = (size_t)d->rows * H * (size_t)d->max_len * hd;
   if (d->kv_dtype == 1 || d->kv_dtype == 2) {
     const dim3 grid(H, d->rows, (n_pos + APF_Q - 1) / APF_Q);
@@ -1009,4 +1011,28 @@ extern "C" int vaura_attention_step_split(const float* qkv, const float* rope, f
   if (pos < 0 || pos >= max_len || !part || n_split < 2 || n_split > 8) return VAURA_ERR_ARG;
   return va_launch_attention(qkv, nullptr, rope, kcache, vcache, out, nullptr, rows, n_head, head_dim, max_len, nullptr, pos,
                              part, n_split, as_stream(s), nullptr, 1.f, 0);
+}
+
+// Op-level access for parity tests: ONE decode-step attention with every optional the step passes (api.hip: enqueue_layers), through the
+// launcher the step itself calls.
+extern "C" int vaura_attention_step_ex(const float* qkv, const float* qkv2, const float* rope, float* kcache, float* vcache, float* out,
+                                       uint16_t* out_split, float* part, uint32_t* arrivals, int rows, int n_head, int head_dim,
+                                       int max_len, int pos, int n_split, int plane_shift, int kv_dtype, vaura_stream_t s) {
+  if (pos < 0 || pos >= max_len || n_split < 1 || n_split > 8 || (n_split > 1 && !part)) return VAURA_ERR_ARG;
+  if (plane_shift < 0 || plane_shift > 24 || kv_dtype < 0 || kv_dtype > 2) return VAURA_ERR_ARG;
+  return va_launch_attention(qkv, qkv2, rope, kcache, vcache, out, out_split, rows, n_head, head_dim, max_len, nullptr, pos,
+                             n_split > 1 ? part : nullptr, n_split, as_stream(s), arrivals, ldexpf(1.f, -plane_shift), kv_dtype);
+}
+
+// Op-level access for parity tests: rope + K / V append, then the causal attention of a teacher-forced chunk [p0, p0 + n_pos) of one
+// layer, on a caller-filled descriptor (read: dims, rows, max_len, kv_dtype, plane_shift, rope, ws_qkv, kcache, vcache, ws_attn,
+// ws_attn_split) — the two launchers of api.hip's enqueue_prefill_chunk_bf16.
+extern "C" int vaura_attention_prefill(const vaura_decoder* d, int layer, int p0, int n_pos, vaura_stream_t s) {
+  if (!d || !d->rope || !d->ws_qkv || !d->kcache || !d->vcache || !d->ws_attn) return VAURA_ERR_ARG;
+  if (d->rows <= 0 || d->dims.n_head <= 0 || d->dims.n_layer <= 0 || layer < 0 || layer >= d->dims.n_layer) return VAURA_ERR_ARG;
+  if (d->kv_dtype < 0 || d->kv_dtype > 2 || d->plane_shift < 0 || d->plane_shift > 24) return VAURA_ERR_ARG;
+  if (p0 < 0 || n_pos <= 0 || p0 + n_pos > d->max_len) return VAURA_ERR_ARG;
+  int rc = va_launch_rope_append(d, layer, p0, n_pos, as_stream(s));
+  if (rc) return rc;
+  return va_launch_attention_prefill(d, layer, p0, n_pos, as_stream(s));
 }
