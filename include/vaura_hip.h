@@ -134,7 +134,12 @@ typedef struct vaura_decoder {
                               configs[4]): fp16 — kcache / vcache then point at (n_layer, rows, n_head, max_len, head_dim) HALVES holding
                               fp16(rotated k) / fp16(v); caches of at most 256 positions only (VAURA_ERR_SHAPE otherwise, from the descriptor check and from
                               the decode-step and prefill attention launchers alike); tolerance reported.
-                              2: OCP e4m3 bytes of the same layout (unscaled, saturating at +-448): a quarter of the fp32 stream, ~1e-2 class */
+                              2: OCP e4m3 bytes of the same layout (unscaled, saturating at +-448): a quarter of the fp32 stream, ~1e-2 class.
+                              3: scaled e4m3 — the bytes of 2 plus ONE E8M0 exponent byte per cached 96-channel vector in kscale / vscale
+                              (below; 97 bytes per vector).  x -> amax = max |x_c|; e = the smallest integer with amax 2^-e <= 448, clamped to
+                              [-127, 127] (amax = 0: -127); byte c = e4m3(x_c 2^-e), round to nearest even; exponent byte = e + 127; widened
+                              as float(byte) 2^e.  Nothing saturates and the grid follows each vector's own range; a vector holding an inf or
+                              NaN gets exponent byte 0xFF and widens to NaN in every channel.  Same shapes as 1 and 2 */
 
   const vaura_layer_weights* layers_host; /* HOST array [n_layer] of device pointers */
   const void*  heads;        /* (n_codebooks*vocab x d_model) MFMA tiles (VAURA_W_H1 when wdtype is FP8) llama.py:356-361 */
@@ -191,6 +196,10 @@ typedef struct vaura_decoder {
    * delays — sorted, >= 0, K <= 16 (VAURA_ERR_ARG otherwise).  The sampler's valid-slot fix-up and its near-tie count follow them. */
   int32_t has_pattern_delays;
   int32_t pattern_delays[16];
+  /* kv_dtype = 3 only (NULL otherwise): the exponent bytes of the scaled e4m3 cache, (n_layer, rows, n_head, max_len) each;
+   * VAURA_ERR_ARG when kv_dtype = 3 and either is NULL */
+  uint8_t* kscale;
+  uint8_t* vscale;
 } vaura_decoder;
 
 /* -------------------------------------------------------------------------------------------
@@ -333,10 +342,17 @@ int vaura_attention_splits(int rows, int n_head, int max_len);
 int vaura_attention_step_ex(const float* qkv, const float* qkv2, const float* rope, float* kcache, float* vcache, float* out,
                             uint16_t* out_split, float* part, uint32_t* arrivals, int rows, int n_head, int head_dim, int max_len,
                             int pos, int n_split, int plane_shift, int kv_dtype, vaura_stream_t s);
+/* vaura_attention_step_ex for every K / V storage: kv_dtype 0..3, with kscale / vscale (rows, n_head, max_len) the exponent bytes of the
+ * scaled e4m3 cache (kv_dtype = 3: VAURA_ERR_ARG when either is NULL; ignored for 0..2).  vaura_attention_step_ex itself keeps refusing
+ * kv_dtype = 3 (VAURA_ERR_ARG): it has nowhere to take them.  Storage 3 takes max_len <= 256 and no split, like 1 and 2.             */
+int vaura_attention_step_kv(const float* qkv, const float* qkv2, const float* rope, float* kcache, float* vcache, uint8_t* kscale,
+                            uint8_t* vscale, float* out, uint16_t* out_split, float* part, uint32_t* arrivals, int rows, int n_head,
+                            int head_dim, int max_len, int pos, int n_split, int plane_shift, int kv_dtype, vaura_stream_t s);
 /* Op-level access for parity tests: the attention of a teacher-forced chunk [p0, p0 + n_pos) of one layer — rope(q, k) + K / V append of
  * the chunk, then its causal attention over cache positions [0, p0 + n_pos) — on a caller-filled descriptor.  Read: dims (n_layer, n_head,
  * d_model = 96 n_head), rows, max_len, kv_dtype, plane_shift, rope, ws_qkv (packed rows: position z of the chunk is row block(s)
- * z * rows16 .. ; q is rotated in place), kcache, vcache, ws_attn, ws_attn_split (NULL ok).  VAURA_ERR_ARG: null pointers, p0 < 0,
+ * z * rows16 .. ; q is rotated in place), kcache, vcache, ws_attn, ws_attn_split (NULL ok), with kv_dtype = 3 kscale and vscale.
+ * VAURA_ERR_ARG: null pointers (kscale / vscale with kv_dtype = 3 included), p0 < 0,
  * n_pos <= 0, p0 + n_pos > max_len; VAURA_ERR_SHAPE: head_dim != 96, or a narrow cache (kv_dtype != 0) of more than 256 positions.
  * Debug flag bit 4 selects the per-position kernel (fp32 cache).                                                                      */
 int vaura_attention_prefill(const vaura_decoder* d, int layer, int p0, int n_pos, vaura_stream_t s);

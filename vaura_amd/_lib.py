@@ -51,7 +51,8 @@ class Decoder(C.Structure):
                 ("ws_logits", C.c_void_p),
                 ("ws_h_split", C.c_void_p), ("ws_attn_split", C.c_void_p), ("ws_ffn_split", C.c_void_p),
                 ("ws_ss", C.c_void_p), ("first_norm", C.c_void_p), ("ws_attn_part", C.c_void_p), ("ws_sync", C.c_void_p),
-                ("has_pattern_delays", C.c_int32), ("pattern_delays", C.c_int32 * 16)]
+                ("has_pattern_delays", C.c_int32), ("pattern_delays", C.c_int32 * 16),
+                ("kscale", C.c_void_p), ("vscale", C.c_void_p)]
 
 
 class Conv(C.Structure):
@@ -168,6 +169,9 @@ SIGNATURES = {
                                        C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "vaura_attention_step_ex": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                           C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    "vaura_attention_step_kv": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                          C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                          C.c_int, C.c_void_p]),
     "vaura_attention_prefill": (C.c_int, [C.POINTER(Decoder), C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "vaura_dac_decode": (C.c_int, [C.POINTER(Codec), C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "vaura_dac_workspace_elems": (C.c_size_t, [C.POINTER(Codec), C.c_int, C.c_int]),

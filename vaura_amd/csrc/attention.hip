@@ -214,8 +214,43 @@ __device__ __forceinline__ uint32_t kv_quad_to_f8(const f32x4 v) {
   q = __builtin_amdgcn_cvt_pk_fp8_f32(sat(v[2]), sat(v[3]), q, true);
   return (uint32_t)q;
 }
-// K / V storage of a kernel instance: KVT = vaura_decoder.kv_dtype (0 fp32, 1 fp16, 2 fp8 e4m3); Q = one quad (4 channels) as stored
+// kv_dtype = 3: scaled e4m3.  One 96-channel vector x (one k or v of one (layer, row, head, position)) is 96 e4m3 bytes in the layout of
+// kv_dtype = 2 plus ONE E8M0 exponent byte e + 127 in kscale / vscale [layer][row][head][max_len]: amax = max |x_c|, e the smallest integer
+// with amax 2^-e <= 448 (so the scaled maximum lies in (224, 448]: nothing saturates, and the e4m3 grid follows the vector's own range),
+// clamped to [-127, 127] (amax = 0: e = -127); byte c = e4m3(x_c 2^-e), an exact power-of-two multiply and ONE rounding to nearest even.
+// A vector with an inf or NaN gets the exponent byte 0xFF (and bytes 0x7F) and widens to NaN in every channel: an overflow upstream
+// still arrives at the sampler as a non-finite logit.  Widening is float(byte) * 2^e; the kernels apply 2^e once per vector, to the score
+// (k) and to the softmax weight (v): powers of two, so either is exact.  tests/kv_f8s_reference.py restates the rule on the CPU.
+__device__ __forceinline__ uint32_t kv_absmax_bits(const f32x4 v) {   // max_c |v_c| as fp32 bits: integer order = float order, NaN above inf
+  typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+  const u32x4 b = __builtin_bit_cast(u32x4, v) & 0x7fffffffu;
+  const uint32_t lo = b[0] > b[1] ? b[0] : b[1], hi = b[2] > b[3] ? b[2] : b[3];
+  return lo > hi ? lo : hi;
+}
+__device__ __forceinline__ uint32_t kv_scale_byte(const uint32_t amax_bits) {   // the exponent byte of a vector whose max |x_c| has these bits
+  if (amax_bits >= 0x7f800000u) return 255u;
+  // amax = m 2^E, m in [1, 2); 448 = 1.75 * 2^8: e = E - 8, one more where m > 1.75 (subnormal amax: far below the clamp)
+  const int e = (int)(amax_bits >> 23) - 127 - 8 + ((amax_bits & 0x7fffffu) > 0x600000u ? 1 : 0);
+  return (uint32_t)(max(e, -127) + 127);
+}
+__device__ __forceinline__ float kv_scale_to_f32(const uint32_t sb) {   // 2^(sb - 127); 2^-127 is an fp32 subnormal; 0xFF -> NaN
+  return __builtin_bit_cast(float, sb == 0u ? 0x00400000u : (sb == 255u ? 0x7fc00000u : sb << 23));
+}
+__device__ __forceinline__ uint32_t kv_quad_to_f8s(const f32x4 v, const uint32_t sb) {   // sb <= 247 for finite vectors (e <= 120)
+  if (sb == 255u) return 0x7f7f7f7fu;
+  const float inv = __builtin_bit_cast(float, (254u - sb) << 23);   // 2^-e: a normal fp32 for every e in [-127, 120]
+  int q = __builtin_amdgcn_cvt_pk_fp8_f32(v[0] * inv, v[1] * inv, 0, false);
+  q = __builtin_amdgcn_cvt_pk_fp8_f32(v[2] * inv, v[3] * inv, q, true);
+  return (uint32_t)q;
+}
+// K / V storage of a kernel instance: KVT = vaura_decoder.kv_dtype (0 fp32, 1 fp16, 2 fp8 e4m3, 3 scaled fp8 e4m3); Q = one quad (4 channels)
+// as stored.  KvT<3>::widen gives the BYTES' values; the vector's scale (narrow's second argument) travels beside it
 template <int KVT> struct KvT;
+template <> struct KvT<3> {
+  using Q = uint32_t; using E = uint8_t;
+  static __device__ __forceinline__ f32x4 widen(const Q& q) { return kv_quad8_to_f32(q); }
+  static __device__ __forceinline__ Q narrow(const f32x4& v, const uint32_t sb) { return kv_quad_to_f8s(v, sb); }
+};
 template <> struct KvT<0> {
   using Q = f32x4; using E = float;
   static __device__ __forceinline__ f32x4 widen(const Q& q) { return q; }
@@ -245,7 +280,8 @@ __device__ __forceinline__ void attention256_body(const float* __restrict__ qkv,
                                                   float* __restrict__ kc, float* __restrict__ vc, float* __restrict__ out,
                                                   uint16_t* __restrict__ outp, int n_head, int pos, f32x4* sqkv,
                                                   f32x4 (*wacc)[HD / 4], float* wm, float* wl, float pscale = 1.f,
-                                                  HOOK after_requests = HOOK()) {
+                                                  HOOK after_requests = HOOK(), uint8_t* __restrict__ ksc = nullptr,
+                                                  uint8_t* __restrict__ vsc = nullptr) {
   constexpr int QUADS = HD / 4;   // 24
   constexpr int QPL = QUADS / 8;  // 3
   constexpr int NW = ATT1_THREADS / 64;
@@ -281,22 +317,27 @@ __device__ __forceinline__ void attention256_body(const float* __restrict__ qkv,
     return reinterpret_cast<const KVQ*>(reinterpret_cast<const typename KV::E*>(base) + (size_t)p * HD);
   };
   auto widen = [&](const KVQ& x) -> f32x4 { return KV::widen(x); };
+  // KVT = 3: ksc / vsc point at this (row, head)'s exponent bytes; the 8 lanes of a position request its byte right behind its row (one
+  // more request in the same queue, no round trip of its own)
+  uint32_t ksb[NUA], vsb[NUA];
 #pragma unroll
   for (int u = 0; u < NU; ++u) {
     const int p = min(u * 64 + prow, pos - 1);
 #pragma unroll
     for (int i = 0; i < QPL; ++i) kf[u][i] = kvrow(kc, p)[sub + 8 * i];
+    if constexpr (KVT == 3) ksb[u] = ksc[p];
   }
 #pragma unroll
   for (int u = 0; u < NU; ++u) {
     const int p = min(u * 64 + prow, pos - 1);
 #pragma unroll
     for (int i = 0; i < QPL; ++i) vf[u][i] = kvrow(vc, p)[sub + 8 * i];
+    if constexpr (KVT == 3) vsb[u] = vsc[p];
   }
 
   after_requests();
   VA_STAMP(stamps, 1);                       // every request issued
-  VA_WAIT_VM(2 * NU * QPL);
+  VA_WAIT_VM(2 * NU * (QPL + (KVT == 3 ? 1 : 0)));
   VA_STAMP(stamps, 2);                       // the new q / k / v quads (written by the previous kernel) and the rope entry have landed
   // ---- 2. rotate q and k (v passes through), park them in LDS, append k and v to the cache.  Every thread
   //         rotates and writes LDS (threads past the 72 real quads hit a scratch slot): an unconditional use keeps
@@ -311,11 +352,36 @@ __device__ __forceinline__ void attention256_body(const float* __restrict__ qkv,
   y[2] = gx[2] * gcs[2] - gx[3] * gcs[3];
   y[3] = gx[3] * gcs[2] + gx[2] * gcs[3];
   if (which == 2) y = gx;   // v is not rotated
-  if constexpr (KVT != 0) {      // the new position's k / v are what later steps will read back: the stored (fp16 / fp8) values, for this step too
+  if constexpr (KVT == 1 || KVT == 2) {      // the new position's k / v are what later steps will read back: the stored (fp16 / fp8) values, for this step too
     if (which >= 1) y = KV::widen(KV::narrow(y));
   }
   sqkv[tid < 3 * QUADS ? tid : 3 * QUADS + (tid & 63)] = y;
-  if (tid >= QUADS && tid < 3 * QUADS) {
+  if constexpr (KVT == 3) {
+    // The stored bytes of a quad depend on max |x_c| over the vector's 24 quads, which sit in threads 24..47 (k) and 48..71 (v): across the
+    // wave boundary, so through LDS.  Every quad's own maximum goes to a word of wacc (idle until step 4, which lies behind the barrier
+    // below); one barrier later the 48 threads read their vector's 24 words, store bytes + exponent byte and replace their parked quad by
+    // what the cache now holds.  Like the barrier below, this one waits for LDS only: the cached rows stay in flight across both.
+    uint32_t* amx = reinterpret_cast<uint32_t*>(wacc);
+    if (tid < 3 * QUADS) amx[tid] = kv_absmax_bits(y);
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    __builtin_amdgcn_s_barrier();
+    asm volatile("" ::: "memory");
+    if (tid >= QUADS && tid < 3 * QUADS) {
+      uint32_t a = 0u;
+#pragma unroll
+      for (int i = 0; i < QUADS / 4; ++i) {
+        const uint4 t = reinterpret_cast<const uint4*>(amx + which * QUADS)[i];
+        a = max(max(a, max(t.x, t.y)), max(t.z, t.w));
+      }
+      const uint32_t sb = kv_scale_byte(a);
+      const uint32_t b = KV::narrow(y, sb);
+      va_st4(reinterpret_cast<float*>(reinterpret_cast<uint8_t*>(which == 1 ? kc : vc) + (size_t)pos * HD) + cq, __builtin_bit_cast(float, b));
+      if (cq == 0) (which == 1 ? ksc : vsc)[pos] = (uint8_t)sb;
+      // per element here, per score / softmax weight for the cached positions: the same numbers as long as no intermediate leaves fp32's
+      // normal range (fp32 denormals are preserved in this build; only vectors with |e| next to the clamp, amax ~ 1e-36 or less, could differ)
+      sqkv[tid] = KV::widen(b) * kv_scale_to_f32(sb);
+    }
+  } else if (tid >= QUADS && tid < 3 * QUADS) {
     if constexpr (KVT == 1) va_st8(reinterpret_cast<uint2*>(reinterpret_cast<_Float16*>(which == 1 ? kc : vc) + (size_t)pos * HD) + cq, kv_quad_to_f16(y));
     else if constexpr (KVT == 2) va_st4(reinterpret_cast<float*>(reinterpret_cast<uint8_t*>(which == 1 ? kc : vc) + (size_t)pos * HD) + cq, __builtin_bit_cast(float, kv_quad_to_f8(y)));
     else va_st16(reinterpret_cast<f32x4*>((which == 1 ? kc : vc) + (size_t)pos * HD) + cq, y);
@@ -359,7 +425,8 @@ __device__ __forceinline__ void attention256_body(const float* __restrict__ qkv,
     f32x4 kw[QPL];
 #pragma unroll
     for (int i = 0; i < QPL; ++i) kw[i] = widen(kf[u][i]);
-    const float d = dot8(kw) * scale;
+    float d = dot8(kw) * scale;
+    if constexpr (KVT == 3) d *= kv_scale_to_f32(ksb[u]);   // the key's 2^e, once per score
     sc[u] = (u * 64 + prow < pos) ? d : -INFINITY;
     m = fmaxf(m, sc[u]);
   }
@@ -373,8 +440,10 @@ __device__ __forceinline__ void attention256_body(const float* __restrict__ qkv,
   for (int u = 0; u < NU; ++u) {
     const float e = expf(sc[u] - m);   // exp(-inf) = 0 for the masked slots (they hold a finite, valid row)
     if (sub == 0) l += e;
+    float ev = e;
+    if constexpr (KVT == 3) ev = e * kv_scale_to_f32(vsb[u]);   // the value's 2^e, once per softmax weight
 #pragma unroll
-    for (int i = 0; i < QPL; ++i) av[i] += widen(vf[u][i]) * e;
+    for (int i = 0; i < QPL; ++i) av[i] += widen(vf[u][i]) * ev;
   }
   l = wave_sum(l);
 #pragma unroll
@@ -426,7 +495,7 @@ __global__ __launch_bounds__(ATT1_THREADS) void attention_step256_kernel(
     // argument order = what the dependent chain needs first (the leading 14 dwords are preloaded into SGPRs)
     const int32_t* __restrict__ pos_dev, float* __restrict__ kcache, float* __restrict__ vcache, const float* __restrict__ qkv,
     const float* __restrict__ qkv2, const float* __restrict__ rope, int n_head, int max_len, int pos_host,
-    float* __restrict__ out, uint16_t* __restrict__ outp, float pscale) {
+    float* __restrict__ out, uint16_t* __restrict__ outp, float pscale, uint8_t* __restrict__ kscale, uint8_t* __restrict__ vscale) {
   constexpr int QUADS = HD / 4;
   __shared__ f32x4 sqkv[3 * QUADS + 64];   // rotated q | rotated k | v of the new position | scratch
   __shared__ f32x4 wacc[ATT1_THREADS / 64][QUADS];
@@ -436,12 +505,16 @@ __global__ __launch_bounds__(ATT1_THREADS) void attention_step256_kernel(
   const size_t off = ((size_t)blockIdx.y * n_head + blockIdx.x) * (size_t)max_len * HD;
   float* kc = reinterpret_cast<float*>(reinterpret_cast<typename KvT<KVT>::E*>(kcache) + off);
   float* vc = reinterpret_cast<float*>(reinterpret_cast<typename KvT<KVT>::E*>(vcache) + off);
+  // KVT = 3: the exponent bytes of this (row, head), one per position (NULL and unused otherwise)
+  const size_t soff = KVT == 3 ? ((size_t)blockIdx.y * n_head + blockIdx.x) * (size_t)max_len : 0;
+  uint8_t* ksc = kscale + soff;
+  uint8_t* vsc = vscale + soff;
   switch ((pos + 63) >> 6) {
-    case 0: attention256_body<HD, 0, NoHook, KVT>(qkv, qkv2, rope, kc, vc, out, outp, n_head, pos, sqkv, wacc, wm, wl, pscale); break;
-    case 1: attention256_body<HD, 1, NoHook, KVT>(qkv, qkv2, rope, kc, vc, out, outp, n_head, pos, sqkv, wacc, wm, wl, pscale); break;
-    case 2: attention256_body<HD, 2, NoHook, KVT>(qkv, qkv2, rope, kc, vc, out, outp, n_head, pos, sqkv, wacc, wm, wl, pscale); break;
-    case 3: attention256_body<HD, 3, NoHook, KVT>(qkv, qkv2, rope, kc, vc, out, outp, n_head, pos, sqkv, wacc, wm, wl, pscale); break;
-    default: attention256_body<HD, 4, NoHook, KVT>(qkv, qkv2, rope, kc, vc, out, outp, n_head, pos, sqkv, wacc, wm, wl, pscale); break;
+    case 0: attention256_body<HD, 0, NoHook, KVT>(qkv, qkv2, rope, kc, vc, out, outp, n_head, pos, sqkv, wacc, wm, wl, pscale, NoHook(), ksc, vsc); break;
+    case 1: attention256_body<HD, 1, NoHook, KVT>(qkv, qkv2, rope, kc, vc, out, outp, n_head, pos, sqkv, wacc, wm, wl, pscale, NoHook(), ksc, vsc); break;
+    case 2: attention256_body<HD, 2, NoHook, KVT>(qkv, qkv2, rope, kc, vc, out, outp, n_head, pos, sqkv, wacc, wm, wl, pscale, NoHook(), ksc, vsc); break;
+    case 3: attention256_body<HD, 3, NoHook, KVT>(qkv, qkv2, rope, kc, vc, out, outp, n_head, pos, sqkv, wacc, wm, wl, pscale, NoHook(), ksc, vsc); break;
+    default: attention256_body<HD, 4, NoHook, KVT>(qkv, qkv2, rope, kc, vc, out, outp, n_head, pos, sqkv, wacc, wm, wl, pscale, NoHook(), ksc, vsc); break;
   }
 }
 
@@ -727,13 +800,17 @@ __global__ __launch_bounds__(64) void attention_combine_kernel(const float* __re
 template <int HD, int KVT = 0>
 __global__ __launch_bounds__(128) void rope_append_kernel(float* __restrict__ qkv, const float* __restrict__ rope,
                                                           float* __restrict__ kcache, float* __restrict__ vcache, int n_head,
-                                                          int max_len, int p0, int rows16) {
+                                                          int max_len, int p0, int rows16, uint8_t* __restrict__ kscale,
+                                                          uint8_t* __restrict__ vscale) {
   constexpr int QUADS = HD / 4;
   const int h = blockIdx.x, row = blockIdx.y, pos = p0 + (int)blockIdx.z, tid = threadIdx.x;
-  if (tid >= 3 * QUADS) return;
+  if constexpr (KVT != 3) {
+    if (tid >= 3 * QUADS) return;
+  }
   const int D = n_head * HD;
   const int vrow = (int)blockIdx.z * rows16 + row;
-  const int which = tid / QUADS, cq = tid % QUADS;
+  const int gt = KVT == 3 ? min(tid, 3 * QUADS - 1) : tid;      // KVT = 3: every thread reaches the barrier below (the spare ones redo the last quad, store nothing)
+  const int which = gt / QUADS, cq = gt % QUADS;
   const int col = which * D + h * HD + cq * 4;
   f32x4* src = reinterpret_cast<f32x4*>(qkv) + packed_quad(vrow, col >> 2, 3 * D);
   f32x4 x = *src;
@@ -747,8 +824,25 @@ __global__ __launch_bounds__(128) void rope_append_kernel(float* __restrict__ qk
     x = y;
   }
   const size_t cbase = (((size_t)row * n_head + h) * (size_t)max_len + pos) * HD;
+  if constexpr (KVT == 3) {      // scaled e4m3: the vector's max |x_c| over its 24 quads through LDS (as attention256_body), same bytes
+    __shared__ uint32_t amx[3 * QUADS];
+    if (tid < 3 * QUADS) amx[tid] = kv_absmax_bits(x);
+    __syncthreads();
+    if (tid >= 3 * QUADS) return;
+    if (which == 0) { *src = x; return; }
+    uint32_t a = 0u;
+#pragma unroll
+    for (int i = 0; i < QUADS / 4; ++i) {
+      const uint4 t = reinterpret_cast<const uint4*>(amx + which * QUADS)[i];
+      a = max(max(a, max(t.x, t.y)), max(t.z, t.w));
+    }
+    const uint32_t sb = kv_scale_byte(a);
+    reinterpret_cast<uint32_t*>(reinterpret_cast<uint8_t*>(which == 1 ? kcache : vcache) + cbase)[cq] = kv_quad_to_f8s(x, sb);
+    if (cq == 0) (which == 1 ? kscale : vscale)[cbase / HD] = (uint8_t)sb;
+    return;
+  }
   if (which == 0) *src = x;
-  if constexpr (KVT != 0) {
+  if constexpr (KVT == 1 || KVT == 2) {
     using KV = KvT<KVT>;
     if (which == 1) reinterpret_cast<typename KV::Q*>(reinterpret_cast<typename KV::E*>(kcache) + cbase)[cq] = KV::narrow(x);
     if (which == 2) reinterpret_cast<typename KV::Q*>(reinterpret_cast<typename KV::E*>(vcache) + cbase)[cq] = KV::narrow(x);
@@ -775,7 +869,8 @@ template <int HD, int KVT = 0>
 __global__ __launch_bounds__(256) void attention_prefill_kernel(const float* __restrict__ qkv, const float* __restrict__ kcache,
                                                                 const float* __restrict__ vcache, float* __restrict__ out,
                                                                 uint16_t* __restrict__ outp, int n_head, int max_len, int p0, int n_pos,
-                                                                int rows16, float pscale) {
+                                                                int rows16, float pscale, const uint8_t* __restrict__ kscale,
+                                                                const uint8_t* __restrict__ vscale) {
   static_assert(HD == 96, "24 k-steps of 4");
   constexpr int KS = HD / 4;        // 24 MFMA steps per S^T tile
   constexpr int DT = HD / 16;       // 6 output column tiles
@@ -813,7 +908,12 @@ __global__ __launch_bounds__(256) void attention_prefill_kernel(const float* __r
     for (int u = tid; u < 64 * (HD / 4); u += 256) {
       const int j = u / (HD / 4), c = u % (HD / 4);
       const int kp = min(kb + j, last_q);
-      if constexpr (KVT != 0) {      // fp16 / fp8 cache: widened on the way into the fp32 staging (the products stay exact-fp32 MFMAs on the stored values)
+      if constexpr (KVT == 3) {      // scaled e4m3: bytes x the vector's 2^e (exact) on the way into the fp32 staging
+        using KV = KvT<3>;
+        const size_t sp = kvoff / HD + kp;
+        *reinterpret_cast<f32x4*>(Ks + j * APF_STRIDE + 4 * c) = KV::widen(reinterpret_cast<const uint32_t*>(reinterpret_cast<const uint8_t*>(kc) + (size_t)kp * HD)[c]) * kv_scale_to_f32(kscale[sp]);
+        *reinterpret_cast<f32x4*>(Vs + j * APF_STRIDE + 4 * c) = KV::widen(reinterpret_cast<const uint32_t*>(reinterpret_cast<const uint8_t*>(vc) + (size_t)kp * HD)[c]) * kv_scale_to_f32(vscale[sp]);
+      } else if constexpr (KVT != 0) {      // fp16 / fp8 cache: widened on the way into the fp32 staging (the products stay exact-fp32 MFMAs on the stored values)
         using KV = KvT<KVT>;
         *reinterpret_cast<f32x4*>(Ks + j * APF_STRIDE + 4 * c) = KV::widen(reinterpret_cast<const typename KV::Q*>(reinterpret_cast<const typename KV::E*>(kc) + (size_t)kp * HD)[c]);
         *reinterpret_cast<f32x4*>(Vs + j * APF_STRIDE + 4 * c) = KV::widen(reinterpret_cast<const typename KV::Q*>(reinterpret_cast<const typename KV::E*>(vc) + (size_t)kp * HD)[c]);
@@ -909,10 +1009,12 @@ int va_attention_splits(int rows, int n_head, int max_len) {
 
 int va_launch_attention(const float* qkv, const float* qkv2, const float* rope, float* kc, float* vc, float* out,
                         uint16_t* outp, int rows, int n_head, int head_dim, int max_len, const int32_t* pos_dev, int pos_host,
-                        float* part, int n_split, hipStream_t s, uint32_t* arrivals, float pscale, int kv_half) {
+                        float* part, int n_split, hipStream_t s, uint32_t* arrivals, float pscale, int kv_half, uint8_t* kscale,
+                        uint8_t* vscale) {
   if (!qkv || !rope || !kc || !vc || !out || rows <= 0 || n_head <= 0) return VAURA_ERR_ARG;
+  if (kv_half == 3 && (!kscale || !vscale)) return VAURA_ERR_ARG;      // scaled e4m3: one exponent byte per cached vector
   if (head_dim != 96) return VAURA_ERR_SHAPE;
-  // fp16 K / V cache: the single-round-trip kernel only (every 2.56 s configuration); long caches / range splits keep fp32
+  // fp16 / fp8 / scaled fp8 K / V cache: the single-round-trip kernel only (every 2.56 s configuration); long caches / range splits keep fp32
   if (kv_half && (max_len > 256 || (part && n_split > 1))) return VAURA_ERR_SHAPE;
   if (part && n_split > 1) {   // few (row, head) pairs over a long cache: split the range, then combine
     if (n_split > 8) return VAURA_ERR_ARG;
@@ -926,13 +1028,16 @@ int va_launch_attention(const float* qkv, const float* qkv2, const float* rope, 
   if (max_len <= 256) {   // static per descriptor (the step graph is captured once): single-round-trip kernel
     if (kv_half == 1)
       VA_LAUNCH((attention_step256_kernel<96, 1>), dim3(n_head, rows), dim3(ATT1_THREADS), 0, s, pos_dev, kc, vc, qkv, qkv2, rope,
-                n_head, max_len, pos_host, out, outp, pscale);
+                n_head, max_len, pos_host, out, outp, pscale, (uint8_t*)nullptr, (uint8_t*)nullptr);
     else if (kv_half == 2)
       VA_LAUNCH((attention_step256_kernel<96, 2>), dim3(n_head, rows), dim3(ATT1_THREADS), 0, s, pos_dev, kc, vc, qkv, qkv2, rope,
-                n_head, max_len, pos_host, out, outp, pscale);
+                n_head, max_len, pos_host, out, outp, pscale, (uint8_t*)nullptr, (uint8_t*)nullptr);
+    else if (kv_half == 3)
+      VA_LAUNCH((attention_step256_kernel<96, 3>), dim3(n_head, rows), dim3(ATT1_THREADS), 0, s, pos_dev, kc, vc, qkv, qkv2, rope,
+                n_head, max_len, pos_host, out, outp, pscale, kscale, vscale);
     else
       VA_LAUNCH(attention_step256_kernel<96>, dim3(n_head, rows), dim3(ATT1_THREADS), 0, s, pos_dev, kc, vc, qkv, qkv2, rope,
-                n_head, max_len, pos_host, out, outp, pscale);
+                n_head, max_len, pos_host, out, outp, pscale, (uint8_t*)nullptr, (uint8_t*)nullptr);
     return 0;
   }
   const size_t smem = sizeof(float) * (size_t)(3 * 96 + 4 * 96 + 8 + max_len + 4);
@@ -951,17 +1056,22 @@ int va_launch_rope_append(const vaura_decoder* d, int layer, int p0, int n_pos, 
   if (hd != 96) return VAURA_ERR_SHAPE;
   if (d->kv_dtype != 0 && d->max_len > 256) return VAURA_ERR_SHAPE;   // as va_launch_attention: the step that follows would refuse this cache
   const size_t kv_layer = (size_t)d->rows * H * (size_t)d->max_len * hd;
-  if (d->kv_dtype == 1 || d->kv_dtype == 2) {      // fp16 / fp8 cache: the layer offset in elements of that type
+  if (d->kv_dtype == 3 && (!d->kscale || !d->vscale)) return VAURA_ERR_ARG;
+  if (d->kv_dtype >= 1 && d->kv_dtype <= 3) {      // fp16 / fp8 / scaled fp8 cache: the layer offset in elements of that type
     if (d->kv_dtype == 1)
       VA_LAUNCH((rope_append_kernel<96, 1>), dim3(H, d->rows, n_pos), dim3(128), 0, s, d->ws_qkv, d->rope, va_kv_layer(d, d->kcache, layer),
-                va_kv_layer(d, d->vcache, layer), H, d->max_len, p0, (d->rows + 15) / 16 * 16);
-    else
+                va_kv_layer(d, d->vcache, layer), H, d->max_len, p0, (d->rows + 15) / 16 * 16, (uint8_t*)nullptr, (uint8_t*)nullptr);
+    else if (d->kv_dtype == 2)
       VA_LAUNCH((rope_append_kernel<96, 2>), dim3(H, d->rows, n_pos), dim3(128), 0, s, d->ws_qkv, d->rope, va_kv_layer(d, d->kcache, layer),
-                va_kv_layer(d, d->vcache, layer), H, d->max_len, p0, (d->rows + 15) / 16 * 16);
+                va_kv_layer(d, d->vcache, layer), H, d->max_len, p0, (d->rows + 15) / 16 * 16, (uint8_t*)nullptr, (uint8_t*)nullptr);
+    else
+      VA_LAUNCH((rope_append_kernel<96, 3>), dim3(H, d->rows, n_pos), dim3(128), 0, s, d->ws_qkv, d->rope, va_kv_layer(d, d->kcache, layer),
+                va_kv_layer(d, d->vcache, layer), H, d->max_len, p0, (d->rows + 15) / 16 * 16, va_kv_scale_layer(d, d->kscale, layer),
+                va_kv_scale_layer(d, d->vscale, layer));
     return 0;
   }
   VA_LAUNCH(rope_append_kernel<96>, dim3(H, d->rows, n_pos), dim3(128), 0, s, d->ws_qkv, d->rope, d->kcache + layer * kv_layer,
-            d->vcache + layer * kv_layer, H, d->max_len, p0, (d->rows + 15) / 16 * 16);
+            d->vcache + layer * kv_layer, H, d->max_len, p0, (d->rows + 15) / 16 * 16, (uint8_t*)nullptr, (uint8_t*)nullptr);
   return 0;
 }
 
@@ -971,22 +1081,28 @@ int va_launch_attention_prefill(const vaura_decoder* d, int layer, int p0, int n
   if (hd != 96) return VAURA_ERR_SHAPE;
   if (d->kv_dtype != 0 && d->max_len > 256) return VAURA_ERR_SHAPE;   // as va_launch_attention (see va_launch_rope_append)
   const size_t kv_layer = (size_t)d->rows * H * (size_t)d->max_len * hd;
-  if (d->kv_dtype == 1 || d->kv_dtype == 2) {
+  if (d->kv_dtype == 3 && (!d->kscale || !d->vscale)) return VAURA_ERR_ARG;
+  if (d->kv_dtype >= 1 && d->kv_dtype <= 3) {
     const dim3 grid(H, d->rows, (n_pos + APF_Q - 1) / APF_Q);
     if (d->kv_dtype == 1)
       VA_LAUNCH((attention_prefill_kernel<96, 1>), grid, dim3(256), 0, s, (const float*)d->ws_qkv, (const float*)va_kv_layer(d, d->kcache, layer),
                 (const float*)va_kv_layer(d, d->vcache, layer), d->ws_attn, d->ws_attn_split, H, d->max_len, p0, n_pos, (d->rows + 15) / 16 * 16,
-                ldexpf(1.f, -d->plane_shift));
-    else
+                ldexpf(1.f, -d->plane_shift), (const uint8_t*)nullptr, (const uint8_t*)nullptr);
+    else if (d->kv_dtype == 2)
       VA_LAUNCH((attention_prefill_kernel<96, 2>), grid, dim3(256), 0, s, (const float*)d->ws_qkv, (const float*)va_kv_layer(d, d->kcache, layer),
                 (const float*)va_kv_layer(d, d->vcache, layer), d->ws_attn, d->ws_attn_split, H, d->max_len, p0, n_pos, (d->rows + 15) / 16 * 16,
-                ldexpf(1.f, -d->plane_shift));
+                ldexpf(1.f, -d->plane_shift), (const uint8_t*)nullptr, (const uint8_t*)nullptr);
+    else
+      VA_LAUNCH((attention_prefill_kernel<96, 3>), grid, dim3(256), 0, s, (const float*)d->ws_qkv, (const float*)va_kv_layer(d, d->kcache, layer),
+                (const float*)va_kv_layer(d, d->vcache, layer), d->ws_attn, d->ws_attn_split, H, d->max_len, p0, n_pos, (d->rows + 15) / 16 * 16,
+                ldexpf(1.f, -d->plane_shift), (const uint8_t*)va_kv_scale_layer(d, d->kscale, layer),
+                (const uint8_t*)va_kv_scale_layer(d, d->vscale, layer));
     return 0;
   }
   if (!(va_debug_flags & 16u)) {
     VA_LAUNCH(attention_prefill_kernel<96>, dim3(H, d->rows, (n_pos + APF_Q - 1) / APF_Q), dim3(256), 0, s, (const float*)d->ws_qkv,
               (const float*)(d->kcache + layer * kv_layer), (const float*)(d->vcache + layer * kv_layer), d->ws_attn, d->ws_attn_split, H,
-              d->max_len, p0, n_pos, (d->rows + 15) / 16 * 16, ldexpf(1.f, -d->plane_shift));
+              d->max_len, p0, n_pos, (d->rows + 15) / 16 * 16, ldexpf(1.f, -d->plane_shift), (const uint8_t*)nullptr, (const uint8_t*)nullptr);
     return 0;
   }
   const size_t smem = sizeof(float) * (size_t)(3 * 96 + 4 * 96 + 8 + d->max_len + 4);
@@ -1024,13 +1140,26 @@ extern "C" int vaura_attention_step_ex(const float* qkv, const float* qkv2, cons
                              n_split > 1 ? part : nullptr, n_split, as_stream(s), arrivals, ldexpf(1.f, -plane_shift), kv_dtype);
 }
 
+// ... and the same with the exponent bytes of the scaled e4m3 cache (kv_dtype = 3; NULL ok for 0 .. 2): kscale / vscale (rows, n_head, max_len)
+extern "C" int vaura_attention_step_kv(const float* qkv, const float* qkv2, const float* rope, float* kcache, float* vcache, uint8_t* kscale,
+                                       uint8_t* vscale, float* out, uint16_t* out_split, float* part, uint32_t* arrivals, int rows,
+                                       int n_head, int head_dim, int max_len, int pos, int n_split, int plane_shift, int kv_dtype,
+                                       vaura_stream_t s) {
+  if (pos < 0 || pos >= max_len || n_split < 1 || n_split > 8 || (n_split > 1 && !part)) return VAURA_ERR_ARG;
+  if (plane_shift < 0 || plane_shift > 24 || kv_dtype < 0 || kv_dtype > 3) return VAURA_ERR_ARG;
+  return va_launch_attention(qkv, qkv2, rope, kcache, vcache, out, out_split, rows, n_head, head_dim, max_len, nullptr, pos,
+                             n_split > 1 ? part : nullptr, n_split, as_stream(s), arrivals, ldexpf(1.f, -plane_shift), kv_dtype, kscale,
+                             vscale);
+}
+
 // Op-level access for parity tests: rope + K / V append, then the causal attention of a teacher-forced chunk [p0, p0 + n_pos) of one
 // layer, on a caller-filled descriptor (read: dims, rows, max_len, kv_dtype, plane_shift, rope, ws_qkv, kcache, vcache, ws_attn,
 // ws_attn_split) — the two launchers of api.hip's enqueue_prefill_chunk_bf16.
 extern "C" int vaura_attention_prefill(const vaura_decoder* d, int layer, int p0, int n_pos, vaura_stream_t s) {
   if (!d || !d->rope || !d->ws_qkv || !d->kcache || !d->vcache || !d->ws_attn) return VAURA_ERR_ARG;
   if (d->rows <= 0 || d->dims.n_head <= 0 || d->dims.n_layer <= 0 || layer < 0 || layer >= d->dims.n_layer) return VAURA_ERR_ARG;
-  if (d->kv_dtype < 0 || d->kv_dtype > 2 || d->plane_shift < 0 || d->plane_shift > 24) return VAURA_ERR_ARG;
+  if (d->kv_dtype < 0 || d->kv_dtype > 3 || d->plane_shift < 0 || d->plane_shift > 24) return VAURA_ERR_ARG;
+  if (d->kv_dtype == 3 && (!d->kscale || !d->vscale)) return VAURA_ERR_ARG;
   if (p0 < 0 || n_pos <= 0 || p0 + n_pos > d->max_len) return VAURA_ERR_ARG;
   int rc = va_launch_rope_append(d, layer, p0, n_pos, as_stream(s));
   if (rc) return rc;

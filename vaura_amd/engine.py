@@ -102,6 +102,7 @@ def streamed_matrices(sd: Dict[str, torch.Tensor]):
 
 
 WEIGHT_DTYPES = ("h1", "h2", "fp8", "fp8h", "f32")
+KV_DTYPES = ("f32", "f16", "f8", "f8s")      # K / V cache storages, in the order of vaura_decoder.kv_dtype
 
 
 def resolve_weight_dtype(sd: Dict[str, torch.Tensor], wdtype: str) -> str:
@@ -180,8 +181,11 @@ class DecoderEngine:
         # with weight_dtype="fp8h": fp16(rotated k) / fp16(v), half the attention's stream; caches of at most 256 positions, plane storages)
         # "f8": OCP e4m3 bytes, unscaled and saturating — a quarter of the fp32 stream, a ~1e-2-class approximation of the attention (still an
         # order of magnitude below the fp8 weights' own error); an OPTION of that configuration, reported beside "f16"
-        if kv_dtype not in ("f32", "f16", "f8"):
-            raise L.VauraHipError(f"kv_dtype must be f32 | f16 | f8, got {kv_dtype!r}")
+        # "f8s": the same e4m3 bytes scaled per cached vector — one E8M0 exponent byte per 96-channel k or v (97 bytes against 96), chosen
+        # so that the vector's largest |value| lands in (224, 448]: nothing saturates or drops to zero whatever the checkpoint's range,
+        # and a non-finite k / v stays non-finite (include/vaura_hip.h, vaura_decoder.kv_dtype = 3): the range-safe fp8 option
+        if kv_dtype not in KV_DTYPES:
+            raise L.VauraHipError(f"kv_dtype must be {' | '.join(KV_DTYPES)}, got {kv_dtype!r}")
         self.kv_dtype = kv_dtype
         self.plane_shift = int(plane_shift)
         if not 0 <= self.plane_shift <= 24:
@@ -326,6 +330,10 @@ class DecoderEngine:
             else:
                 self.kcache = torch.zeros(c.num_layers, rows, c.nhead, max_len, c.head_dim, **f32)
             self.vcache = torch.zeros_like(self.kcache)
+            self.kscale = self.vscale = None      # "f8s": the exponent byte of every cached vector
+            if self.kv_dtype == "f8s":
+                self.kscale = torch.zeros(c.num_layers, rows, c.nhead, max_len, device=self.dev, dtype=torch.uint8)
+                self.vscale = torch.zeros_like(self.kscale)
             self.seq = torch.zeros(batch, K, S, dtype=torch.int32, device=self.dev)
             self.state = torch.zeros(8, dtype=torch.int32, device=self.dev)   # include/vaura_hip.h: position, arrivals, step, id, STATUS, spare
             self.ws_h = torch.zeros(rp * c.d_model, **f32)
@@ -354,7 +362,8 @@ class DecoderEngine:
         d.timesteps, d.seq_len, d.n_cond_tokens = timesteps, S, n_cond_tokens
         d.prefill_positions = self._prefill_positions
         d.plane_shift = self.plane_shift
-        d.kv_dtype = {"f32": 0, "f16": 1, "f8": 2}[self.kv_dtype]
+        d.kv_dtype = KV_DTYPES.index(self.kv_dtype)
+        d.kscale, d.vscale = L.ptr(self.kscale), L.ptr(self.vscale)
         if delays is not None:             # zero-filled = the default pattern (include/vaura_hip.h)
             d.has_pattern_delays = 1
             for q, dq in enumerate(delays):

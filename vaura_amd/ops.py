@@ -104,18 +104,45 @@ def attention_step_ex(qkv_p: torch.Tensor, rope: torch.Tensor, kcache: torch.Ten
     return out, out_split
 
 
+def attention_step_kv(qkv_p: torch.Tensor, rope: torch.Tensor, kcache: torch.Tensor, vcache: torch.Tensor, rows: int, n_head: int,
+                      head_dim: int, pos: int, *, kv_dtype: int = 0, kscale: Optional[torch.Tensor] = None,
+                      vscale: Optional[torch.Tensor] = None, qkv2_p: Optional[torch.Tensor] = None, n_split: int = 1,
+                      part: Optional[torch.Tensor] = None, arrivals: Optional[torch.Tensor] = None, want_split: bool = False,
+                      plane_shift: int = 0, out: Optional[torch.Tensor] = None, out_split: Optional[torch.Tensor] = None):
+    """vaura_attention_step_kv: ``attention_step_ex`` for every storage, 0..3.  kv_dtype = 3 (scaled e4m3): kcache / vcache hold the
+    bytes (uint8 or float8_e4m3fn), kscale / vscale (rows, n_head, max_len) uint8 the exponent byte of every cached vector."""
+    _cuda(qkv_p, qkv2_p, rope, kcache, vcache, kscale, vscale, part, arrivals, out, out_split)
+    max_len = kcache.shape[-2]
+    rp = (rows + 15) // 16 * 16
+    dev = qkv_p.device
+    if out is None:
+        out = torch.zeros(rp * n_head * head_dim, dtype=torch.float32, device=dev)
+    if want_split and out_split is None:
+        out_split = torch.zeros(rp * 2 * n_head * head_dim, dtype=torch.int16, device=dev)
+    if n_split > 1 and part is None:
+        part = torch.empty(rows * n_head * n_split * (head_dim + 8), dtype=torch.float32, device=dev)
+    L.check(L.lib().vaura_attention_step_kv(L.ptr(qkv_p), L.ptr(qkv2_p), L.ptr(rope), L.ptr(kcache), L.ptr(vcache), L.ptr(kscale),
+                                            L.ptr(vscale), L.ptr(out), L.ptr(out_split), L.ptr(part), L.ptr(arrivals), rows, n_head,
+                                            head_dim, max_len, pos, n_split, plane_shift, kv_dtype, L.current_stream()),
+            "vaura_attention_step_kv")
+    return out, out_split
+
+
 def attention_prefill(qkv_p: torch.Tensor, rope: torch.Tensor, kcache: torch.Tensor, vcache: torch.Tensor, attn: torch.Tensor,
                       attn_split: Optional[torch.Tensor], rows: int, n_head: int, head_dim: int, p0: int, n_pos: int, *,
-                      kv_dtype: int = 0, plane_shift: int = 0) -> None:
+                      kv_dtype: int = 0, plane_shift: int = 0, kscale: Optional[torch.Tensor] = None,
+                      vscale: Optional[torch.Tensor] = None) -> None:
     """vaura_attention_prefill on a one-layer descriptor: rope + K / V append of the chunk [p0, p0 + n_pos), then its causal attention.
     qkv_p: packed rows of (n_pos * rows16, 3 D), position z of the chunk in rows z * rows16 ..; its q columns are rotated in place.
-    attn (packed rows of (n_pos * rows16, D)) and attn_split (its split rows, or None) receive the output."""
-    _cuda(qkv_p, rope, kcache, vcache, attn, attn_split)
+    attn (packed rows of (n_pos * rows16, D)) and attn_split (its split rows, or None) receive the output.  kscale / vscale (rows, n_head,
+    max_len) uint8: the exponent bytes of the scaled e4m3 cache (kv_dtype = 3)."""
+    _cuda(qkv_p, rope, kcache, vcache, attn, attn_split, kscale, vscale)
     d = L.Decoder()
     d.dims.n_layer, d.dims.n_head, d.dims.d_model = 1, n_head, n_head * head_dim
     d.rows, d.max_len, d.kv_dtype, d.plane_shift = rows, kcache.shape[-2], kv_dtype, plane_shift
     d.rope, d.ws_qkv, d.kcache, d.vcache = L.ptr(rope), L.ptr(qkv_p), L.ptr(kcache), L.ptr(vcache)
     d.ws_attn, d.ws_attn_split = L.ptr(attn), L.ptr(attn_split)
+    d.kscale, d.vscale = L.ptr(kscale), L.ptr(vscale)
     L.check(L.lib().vaura_attention_prefill(C.byref(d), 0, p0, n_pos, L.current_stream()), "vaura_attention_prefill")
 
 
