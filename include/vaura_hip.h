@@ -108,6 +108,19 @@ typedef struct vaura_sampling {
                              step + 1) and raises VAURA_STATUS_NEAR_TIE.  The token chosen is never changed by the detector           */
 } vaura_sampling;
 
+/* ---- the same five parameters for ONE clip of a batched call: vaura_decoder.clip_sampling / vaura_sample_clips take B of these in
+ * DEVICE memory, record b for clip b.  32 bytes, 16-byte aligned, plain 4-byte fields (the sampler's workgroup of clip b fetches its
+ * record with two vector loads, 16 + 4 bytes).  Every field means what its namesake in vaura_sampling means. */
+typedef struct vaura_clip_sampling {
+  int32_t use_sampling;
+  float   temp;
+  int32_t top_k;
+  float   top_p;
+  float   cfg_scale;      /* > 1: this clip mixes in its null-condition row.  <= 1 inside a call that carries those rows: no mix at all —
+                             the row is not read, no lu + (x - lu) * 1, near-tie factor 1: the bits of a cfg_scale <= 1 call */
+  int32_t reserved[3];    /* 0 */
+} vaura_clip_sampling;
+
 /* ---- everything one decode step touches.  All buffers are owned by the caller (torch tensors). */
 #define VAURA_STATUS_NONFINITE_LOGITS 1
 #define VAURA_STATUS_HANDOFF_TIMEOUT 2    /* a consumer of the one-launch MLP (csrc/mlp_engine.h) gave up waiting for its producers */
@@ -200,6 +213,17 @@ typedef struct vaura_decoder {
    * VAURA_ERR_ARG when kv_dtype = 3 and either is NULL */
   uint8_t* kscale;
   uint8_t* vscale;
+  /* Per-clip sampling parameters (NULL: the scalars of the call's vaura_sampling hold for every clip): `batch` records in device
+   * memory.  With it, use_sampling / temp / top_k / top_p / cfg_scale of vaura_sampling are not read, except that the scalar
+   * cfg_scale > 1 together with rows == 2 batch still states that the null-condition rows exist (set both when any clip's scale is
+   * above 1); seed, clip_base, tie_eps keep their meaning.  It lives here, next to `noise`, and not in vaura_sampling: that struct
+   * keeps its 48 bytes for callers compiled against it.  The sampler reads the records at every step, and a captured step graph
+   * holds the POINTER: rewrite the records between calls and replay the same graph.  vaura_decode_step, vaura_generate_loop and
+   * vaura_step_graph_build return VAURA_ERR_ARG for records together with input_is_probs = 1, and for a record with cfg_scale > 1
+   * when rows != 2 batch or the scalar cfg_scale <= 1 (they read the records back: one small copy and a wait on the stream, per
+   * call — vaura_generate_loop only when it launches eagerly, graph == NULL: replays of a built graph stay asynchronous; not while
+   * the stream is being captured either.  Where nothing is read back the kernel clamps such a record to 1).  vaura_score ignores it. */
+  const vaura_clip_sampling* clip_sampling;
 } vaura_decoder;
 
 /* -------------------------------------------------------------------------------------------
@@ -245,6 +269,17 @@ int vaura_pattern_revert_delays(const int32_t* seq, int32_t* codes, int B, int K
  * `step`).  tokens_out (B,K) int32.                                                              */
 int vaura_sample(const float* logits, int B, int K, int vocab, const vaura_sampling* sp, const float* noise,
                  int64_t step, int32_t* tokens_out, vaura_stream_t s);
+
+/* vaura_sample with per-clip records (B of them, device memory; see vaura_decoder.clip_sampling): clip b is sampled with record b, and
+ * the result equals, clip by clip, vaura_sample with that clip's parameters.  sp->cfg_scale > 1 states that logits has 2B rows.
+ * seq == NULL: tokens_out (B,K) as vaura_sample.  seq != NULL: the sampler as the decode step runs it, on the caller's logits — seq
+ * (B,K,S) pattern sequence (default delays) and `state` (8 words, vaura_decoder.state) are required, position and step index come
+ * from state[0] / state[2] (`step` is not read), the slot state[0] + 1 is filled where it holds -1, the status bits and near-tie
+ * counters are raised and the state advances; tokens_out may be NULL.
+ * VAURA_ERR_ARG: clips == NULL, input_is_probs = 1, a record with cfg_scale > 1 while sp->cfg_scale <= 1.                        */
+int vaura_sample_clips(const float* logits, int B, int K, int vocab, const vaura_sampling* sp, const vaura_clip_sampling* clips,
+                       const float* noise, int64_t step, int32_t* tokens_out, int32_t* seq, int T, int S, int32_t* state,
+                       vaura_stream_t s);
 
 /* -------------------------------------------------------------------------------------------
  * a3..a12 + a2/a13/a15 for ONE position: Transformer.inference (llama.py:445-504) restricted to the

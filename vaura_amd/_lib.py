@@ -37,6 +37,12 @@ class Sampling(C.Structure):
                 ("tie_eps", C.c_float)]
 
 
+class ClipSampling(C.Structure):
+    """vaura_clip_sampling: one clip's parameters of a batched call (32 bytes; engine.DecoderEngine keeps B of them on the device)."""
+    _fields_ = [("use_sampling", C.c_int32), ("temp", C.c_float), ("top_k", C.c_int32), ("top_p", C.c_float),
+                ("cfg_scale", C.c_float), ("reserved", C.c_int32 * 3)]
+
+
 class Decoder(C.Structure):
     _fields_ = [("dims", Dims), ("wdtype", C.c_int32), ("batch", C.c_int32), ("rows", C.c_int32),
                 ("max_len", C.c_int32), ("timesteps", C.c_int32), ("seq_len", C.c_int32),
@@ -52,7 +58,7 @@ class Decoder(C.Structure):
                 ("ws_h_split", C.c_void_p), ("ws_attn_split", C.c_void_p), ("ws_ffn_split", C.c_void_p),
                 ("ws_ss", C.c_void_p), ("first_norm", C.c_void_p), ("ws_attn_part", C.c_void_p), ("ws_sync", C.c_void_p),
                 ("has_pattern_delays", C.c_int32), ("pattern_delays", C.c_int32 * 16),
-                ("kscale", C.c_void_p), ("vscale", C.c_void_p)]
+                ("kscale", C.c_void_p), ("vscale", C.c_void_p), ("clip_sampling", C.c_void_p)]
 
 
 class Conv(C.Structure):
@@ -146,6 +152,8 @@ SIGNATURES = {
                                               C.POINTER(C.c_int32), C.c_void_p]),
     "vaura_sample": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(Sampling), C.c_void_p, C.c_int64,
                                C.c_void_p, C.c_void_p]),
+    "vaura_sample_clips": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(Sampling), C.c_void_p, C.c_void_p, C.c_int64,
+                                     C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "vaura_decode_step": (C.c_int, [C.POINTER(Decoder), C.POINTER(Sampling), C.c_int, C.c_void_p]),
     "vaura_generate_loop": (C.c_int, [C.POINTER(Decoder), C.POINTER(Sampling), C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "vaura_step_graph_build": (C.c_int, [C.POINTER(Decoder), C.POINTER(Sampling), C.c_void_p, C.POINTER(C.c_void_p)]),
@@ -202,7 +210,7 @@ def lib() -> C.CDLL:
             fn = getattr(handle, name)  # AttributeError if the symbol is not exported
             fn.restype = res
             fn.argtypes = args
-        for which, cls in enumerate([Dims, LayerWeights, Sampling, Decoder, Conv, Codec, CodecEncoder, Vit, VitBlock]):
+        for which, cls in enumerate([Dims, LayerWeights, Sampling, Decoder, Conv, Codec, CodecEncoder, Vit, VitBlock, ClipSampling]):
             if C.sizeof(cls) != handle.vaura_struct_size(which):
                 raise VauraHipError(f"{LIB_PATH} was built from a different include/vaura_hip.h: sizeof({cls.__name__}) is "
                                     f"{handle.vaura_struct_size(which)} there, {C.sizeof(cls)} here (rebuild the library)")

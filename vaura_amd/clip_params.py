@@ -1,0 +1,99 @@
+"""Per-clip sampling parameters of one batched generate() call — host-side bookkeeping only (no device work, no HIP library).
+
+``use_sampling``, ``temp``, ``top_k``, ``top_p`` and ``cfg_scale`` may each be a scalar (every clip) or a length-B sequence / 1-D
+tensor (clip b gets element b).  Any non-scalar argument selects the per-clip path of the sampler (csrc/step.hip
+``sample_kernel<true>``, include/vaura_hip.h ``vaura_clip_sampling``); scalars next to it are broadcast.  An all-scalar call stays
+the scalar call it always was.
+"""
+from __future__ import annotations
+
+import struct
+from typing import Dict, List, Optional
+
+NAMES = ("use_sampling", "temp", "top_k", "top_p", "cfg_scale")
+_CAST = {"use_sampling": lambda v: int(bool(v)), "temp": float, "top_k": int, "top_p": float, "cfg_scale": float}
+RECORD_BYTES = 32            # sizeof(vaura_clip_sampling)
+
+
+def _error(msg: str):
+    from ._lib import VauraHipError
+    return VauraHipError(msg)
+
+
+def is_per_clip(v) -> bool:
+    """A list / tuple / array / tensor with a clip dimension; Python and 0-d scalars are not."""
+    if isinstance(v, (list, tuple, range)):
+        return True
+    return bool(getattr(v, "ndim", 0)) and hasattr(v, "tolist")
+
+
+def _scalar(v):
+    return v.item() if hasattr(v, "item") and not isinstance(v, (bool, int, float)) else v
+
+
+def per_clip_length(**params) -> Optional[int]:
+    """The common length of the non-scalar arguments (None: all scalars); sequences of different lengths are refused."""
+    n = None
+    for name, v in params.items():
+        if not is_per_clip(v):
+            continue
+        if getattr(v, "ndim", 1) != 1:
+            raise _error(f"per-clip {name} must be one-dimensional (one value per clip), got shape {tuple(v.shape)}")
+        if n is not None and len(v) != n[1]:
+            raise _error(f"per-clip {name} has {len(v)} values but {n[0]} has {n[1]}: one value per clip")
+        n = n or (name, len(v))
+    return None if n is None else n[1]
+
+
+def resolve(batch: int, use_sampling, temp, top_k, top_p, cfg_scale) -> Optional[Dict[str, List]]:
+    """None for an all-scalar call; otherwise every parameter as a list of ``batch`` plain Python values (scalars broadcast).
+    A sequence whose length is not ``batch`` raises ``VauraHipError``."""
+    given = dict(zip(NAMES, (use_sampling, temp, top_k, top_p, cfg_scale)))
+    if per_clip_length(**given) is None:
+        return None
+    out = {}
+    for name, v in given.items():
+        if is_per_clip(v):
+            vals = v.tolist() if hasattr(v, "tolist") else list(v)
+            if len(vals) != batch:
+                raise _error(f"per-clip {name} has {len(vals)} values for a batch of {batch} clips")
+        else:
+            vals = [_scalar(v)] * batch
+        out[name] = [_CAST[name](x) for x in vals]
+    return out
+
+
+def check_lengths(batch: Optional[int], **params) -> None:
+    """Refuse per-clip sequences that disagree with each other or with ``batch`` (when it is known) — cheap, before any device work."""
+    n = per_clip_length(**params)
+    if n is not None and batch is not None and n != batch:
+        name = next(k for k, v in params.items() if is_per_clip(v))
+        raise _error(f"per-clip {name} has {n} values for a batch of {batch} clips")
+
+
+def any_cfg(cfg_scale) -> bool:
+    """``use_cfg`` of a call: some clip's scale is above 1 (the null-condition rows are then carried for the whole batch)."""
+    if is_per_clip(cfg_scale):
+        return any(float(x) > 1.0 for x in (cfg_scale.tolist() if hasattr(cfg_scale, "tolist") else cfg_scale))
+    return bool(_scalar(cfg_scale) > 1.0)
+
+
+def any_sampled(use_sampling, temp) -> bool:
+    """Does any clip draw (use_sampling and temp > 0)?  Noise is needed then; the rows of greedy clips stay unused."""
+    n = per_clip_length(use_sampling=use_sampling, temp=temp)
+    if n is None:
+        return bool(_scalar(use_sampling) and _scalar(temp) > 0.0)
+    us = use_sampling.tolist() if hasattr(use_sampling, "tolist") else (list(use_sampling) if is_per_clip(use_sampling) else [use_sampling] * n)
+    tp = temp.tolist() if hasattr(temp, "tolist") else (list(temp) if is_per_clip(temp) else [temp] * n)
+    return any(bool(u) and float(t) > 0.0 for u, t in zip(us, tp))
+
+
+def take(v, first: int, count: int):
+    """Clips [first, first + count) of one argument: a slice of a per-clip sequence, a scalar as it is."""
+    return v[first:first + count] if is_per_clip(v) else v
+
+
+def pack_records(p: Dict[str, List]) -> bytes:
+    """``vaura_clip_sampling`` records, one per clip, as the device buffer holds them."""
+    return b"".join(struct.pack("<ififf3i", p["use_sampling"][b], p["temp"][b], p["top_k"][b], p["top_p"][b], p["cfg_scale"][b], 0, 0, 0)
+                    for b in range(len(p["temp"])))

@@ -130,6 +130,12 @@ static int enqueue_prefill_chunk_heads(const vaura_decoder* d, int p0, int n, fl
                          (int64_t)m.n_codebooks * m.vocab, m.d_model, E3_LOGITS, true, s);
 }
 
+// per-clip sampling records of a decoder call (vaura_decoder.clip_sampling): refused with probability rows, and with a clip scale > 1
+// when the descriptor carries no null-condition rows (step.hip va_check_clip_sampling)
+static int check_clips(const vaura_decoder* d, const vaura_sampling* sp, hipStream_t s) {
+  return va_check_clip_sampling(sp, d->clip_sampling, d->batch, d->rows == 2 * d->batch, s);
+}
+
 // pair path (H1 / H2 / FP8 storage): activations travel as (hi, lo) fp16 planes, products on the fp16 MFMA
 static int enqueue_step_bf16(const vaura_decoder* d, const vaura_sampling* sp, int sample, hipStream_t s) {
   const vaura_dims& m = d->dims;
@@ -259,7 +265,7 @@ static int enqueue_step_bf16(const vaura_decoder* d, const vaura_sampling* sp, i
   PROF_A(VAURA_K_HEADS);
   if (rc) return rc;
   PROF_B(VAURA_K_SAMPLE);
-  rc = va_launch_sample(d->ws_logits, d->batch, m.n_codebooks, m.vocab, sp, d->noise, d->batch * m.n_codebooks, d->state, 0,
+  rc = va_launch_sample(d->ws_logits, d->batch, m.n_codebooks, m.vocab, sp, d->clip_sampling, d->noise, d->batch * m.n_codebooks, d->state, 0,
                         nullptr, d->seq, d->timesteps, d->seq_len, d->state, va_pattern_delays(d), s);
   PROF_A(VAURA_K_SAMPLE);
   return rc;
@@ -315,7 +321,7 @@ static int enqueue_step(const vaura_decoder* d, const vaura_sampling* sp, int sa
   PROF_A(VAURA_K_HEADS);
   if (rc) return rc;
   PROF_B(VAURA_K_SAMPLE);
-  rc = va_launch_sample(d->ws_logits, d->batch, m.n_codebooks, m.vocab, sp, d->noise, d->batch * m.n_codebooks, d->state, 0,
+  rc = va_launch_sample(d->ws_logits, d->batch, m.n_codebooks, m.vocab, sp, d->clip_sampling, d->noise, d->batch * m.n_codebooks, d->state, 0,
                           nullptr, d->seq, d->timesteps, d->seq_len, d->state, va_pattern_delays(d), s);
   PROF_A(VAURA_K_SAMPLE);
   return rc;
@@ -368,6 +374,7 @@ size_t vaura_struct_size(int which) {
     case 6: return sizeof(vaura_codec_encoder);
     case 7: return sizeof(vaura_vit);
     case 8: return sizeof(vaura_vit_block);
+    case 9: return sizeof(vaura_clip_sampling);
     default: return 0;
   }
 }
@@ -376,6 +383,7 @@ int vaura_decode_step(const vaura_decoder* dec, const vaura_sampling* sp, int sa
   int rc = check_decoder(dec);
   if (rc) return rc;
   if (sample && !sp) return VAURA_ERR_ARG;
+  if (sample && (rc = check_clips(dec, sp, as_stream(s)))) return rc;
   return enqueue_step(dec, sp, sample, as_stream(s));
 }
 
@@ -394,6 +402,7 @@ int vaura_step_graph_build(const vaura_decoder* dec, const vaura_sampling* sp, v
   if (rc) return rc;
   if (!sp || !out) return VAURA_ERR_ARG;
   *out = nullptr;
+  if ((rc = check_clips(dec, sp, as_stream(s)))) return rc;
   StepGraph* g = new StepGraph();
   hipStream_t st = as_stream(s);
   hipError_t e = hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal);
@@ -422,6 +431,9 @@ int vaura_generate_loop(const vaura_decoder* dec, const vaura_sampling* sp, int 
   // the loop feeds positions [0, n_prefill + n_steps) and the sampler writes seq[..., position + 1]: the last written
   // slot must exist (the reference's loop is range(start, S), vaura_model.py:502), and so must its K/V rows
   if (n_prefill + n_steps > dec->seq_len - 1 || n_prefill + n_steps > dec->max_len) return VAURA_ERR_ARG;
+  // records are read back (a copy + a wait) only where this call launches eagerly: a graph was checked when it was built, its replays
+  // stay asynchronous, and records rewritten since then are held inside their rows by the kernel's clamp
+  if (n_steps > 0 && !graph && (rc = check_clips(dec, sp, as_stream(s)))) return rc;
   hipStream_t st = as_stream(s);
   if (n_prefill > 0 && dec->ws_h_split && dec->prefill_positions > 0) {
     // the caller guarantees state[0] == 0 at entry (vaura_pattern_build + zeroed state)
@@ -531,8 +543,10 @@ int vaura_score(const vaura_decoder* dec, int n_pos, const int32_t* targets, flo
     // greedy sampler behind it only fills -1 slots, and a fully built pattern sequence has none.  Its status bits (non-finite logits)
     // stay in state[4] for the caller.
     vaura_sampling sp = {};
+    vaura_decoder plain = *dec;
+    plain.clip_sampling = nullptr;        // scoring has no sampling parameters, per clip or otherwise
     for (int p = 0; p < n_pos; ++p) {
-      rc = enqueue_step(dec, &sp, 1, st);
+      rc = enqueue_step(&plain, &sp, 1, st);
       if (rc) return rc;
       rc = va_launch_score_nll(dec->ws_logits, dec->rows, p, 1, B, K, V, Ta, delays, targets, nll, logits_out, st);
       if (rc) return rc;

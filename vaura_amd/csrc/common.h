@@ -221,9 +221,11 @@ int va_launch_attn_wo(const float* qkv, const float* qkv2, const float* rope, fl
 int va_launch_tail_engine(const Gemv3Args& awo, const Gemv3Args& a13, const Gemv3Args& a2, uint32_t* flags, int32_t* state, int layer,
                           hipStream_t s);
 int va_launch_embed(const vaura_decoder* d, int pos_host, int n_pos, hipStream_t s);
-int va_launch_sample(const float* logits, int B, int K, int vocab, const vaura_sampling* sp, const float* noise,
-                     int noise_rows_per_step, const int32_t* state, int64_t step_host, int32_t* tokens_out,
+// clips: per-clip records (vaura_decoder.clip_sampling) or NULL for the scalars of `sp`
+int va_launch_sample(const float* logits, int B, int K, int vocab, const vaura_sampling* sp, const vaura_clip_sampling* clips,
+                     const float* noise, int noise_rows_per_step, const int32_t* state, int64_t step_host, int32_t* tokens_out,
                      int32_t* seq, int T, int S, int32_t* state_rw, const int32_t* delays_host, hipStream_t s);
+int va_check_clip_sampling(const vaura_sampling* sp, const vaura_clip_sampling* clips, int B, bool doubled, hipStream_t s);
 int va_launch_advance(int32_t* state, int set_to, hipStream_t s);
 int va_launch_linear_pair(const uint16_t* in, const uint16_t* w, const float* bias, const float* res, float* out_raw,
                           uint16_t* out_act, int act, int B, int Lin, int Lout, int oshift, int Cin, int Cout, hipStream_t s);

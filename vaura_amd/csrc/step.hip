@@ -4,6 +4,7 @@
 //   embed    models/modules/sampler/llama.py:455-472, 555-586  (token projection sum + video concat)
 //   sample   models/vaura_model.py:807-825, 536-544; utils/utils.py:139-196
 //   pattern  models/modules/misc/codebook_patterns.py:137-285, 374-419 (delay patterns, closed form)
+#include <vector>
 #include "common.h"
 #include "gemv3_kernel.h"
 
@@ -195,8 +196,13 @@ __device__ __forceinline__ int block_count(int v, int* si) {
 }
 
 // V == 1024 == 4 * SMP_THREADS: thread t owns candidates 4t .. 4t+3
+// PC (per-clip parameters, vaura_decoder.clip_sampling): the workgroup of clip b = blockIdx.y takes use_sampling / temp / top_k / top_p /
+// cfg_scale from record b of `clips` instead of the launch's scalars; everything below reads them through `a` either way.  PC = false
+// is the scalar launch as it always was: the fetch is compiled out and `clips` (NULL) is never read.
+typedef int32_t i32x4 __attribute__((ext_vector_type(4)));
+template <bool PC>
 __global__ __launch_bounds__(SMP_THREADS) void sample_kernel(const float* __restrict__ logits_q, const int32_t* __restrict__ state_q,
-                                                             SampleArgs a) {
+                                                             SampleArgs a, const int32_t* __restrict__ clips) {
   a.logits = logits_q;   // explicit scalar copies: preloaded into SGPRs at wave launch (the struct is not)
   a.state = state_q;
   __shared__ float sv[8];
@@ -212,6 +218,26 @@ __global__ __launch_bounds__(SMP_THREADS) void sample_kernel(const float* __rest
   const int V = a.V;
 
   const f32x4 lc = *reinterpret_cast<const f32x4*>(a.logits + ((size_t)b * a.K + k) * V + 4 * tid);
+  if constexpr (PC) {
+    // This clip's record, requested right behind its logits so that it waits under the same latency.  Two VECTOR loads, 16 + 4 bytes (five fields)
+    // (the opaque lane offset keeps the address out of the scalar unit: the host rewrites the records between replays of one
+    // captured graph, and the vector path is the one that is coherent with those copies); the fields are wave-uniform, so they go
+    // back to SGPRs and every branch on them stays a scalar branch, as in the scalar instance.
+    int lane0 = 0;
+    asm volatile("" : "+v"(lane0));
+    const int32_t* rec = clips + (size_t)b * (sizeof(vaura_clip_sampling) / 4) + lane0;
+    const i32x4 r0 = *reinterpret_cast<const i32x4*>(rec);
+    const int32_t r1 = rec[4];
+    a.use_sampling = __builtin_amdgcn_readfirstlane(r0[0]);
+    a.temp = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(r0[1]));
+    a.top_k = __builtin_amdgcn_readfirstlane(r0[2]);
+    a.top_p = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(r0[3]));
+    const float cfg = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(r1));
+    // the launch's scalar cfg_scale > 1 says that the null-condition rows [B, 2B) exist; a clip whose own scale is <= 1 skips the mix
+    // (no lu + (x - lu) * 1: not the same bits), never reads them, and screens near-ties with factor 1 — the scalar path at
+    // cfg_scale <= 1.  Without those rows no record can switch the mix on (refused on the host; clamped here: never out of bounds).
+    a.cfg_scale = a.cfg_scale > 1.0f ? cfg : fminf(cfg, 1.0f);
+  }
   float x[4] = {lc[0], lc[1], lc[2], lc[3]};
   // near-tie detector: magnitude of the rows this decision is made from (both branches, before the mix)
   float amax = fmaxf(fmaxf(fabsf(lc[0]), fabsf(lc[1])), fmaxf(fabsf(lc[2]), fabsf(lc[3])));
@@ -525,10 +551,33 @@ __global__ __launch_bounds__(SMP_THREADS) void sample_kernel(const float* __rest
   }
 }
 
-int va_launch_sample(const float* logits, int B, int K, int vocab, const vaura_sampling* sp, const float* noise,
-                     int /*noise_rows_per_step*/, const int32_t* state, int64_t step_host, int32_t* tokens_out,
+// Host side of the per-clip records' contract (the public entry points call it, never a captured launch): no records with probability
+// rows, and no record may ask for the CFG mix unless the call carries the null-condition rows (`doubled`, and the scalar cfg_scale > 1
+// that says so to the kernel).  Reads the B records back (one small copy + a wait on `s`); skipped while `s` is being captured, where
+// nothing may wait — the kernel's own clamp keeps such a launch inside its rows.
+int va_check_clip_sampling(const vaura_sampling* sp, const vaura_clip_sampling* clips, int B, bool doubled, hipStream_t s) {
+  if (!clips) return 0;
+  if (!sp || B <= 0 || sp->input_is_probs) return VAURA_ERR_ARG;
+  if (((uintptr_t)clips & 15u) != 0) return VAURA_ERR_ARG;
+  hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+  const hipError_t ce = hipStreamIsCapturing(s, &cs);
+  if (ce != hipSuccess) { (void)hipGetLastError(); return (int)ce; }      // no answer: refuse, never skip silently
+  if (cs != hipStreamCaptureStatusNone) return 0;
+  std::vector<vaura_clip_sampling> host((size_t)B);
+  hipError_t e = hipMemcpyAsync(host.data(), clips, host.size() * sizeof(vaura_clip_sampling), hipMemcpyDeviceToHost, s);
+  if (e == hipSuccess) e = hipStreamSynchronize(s);
+  if (e != hipSuccess) return (int)e;
+  const bool rows = doubled && sp->cfg_scale > 1.0f;
+  for (const vaura_clip_sampling& r : host)
+    if (r.cfg_scale > 1.0f && !rows) return VAURA_ERR_ARG;
+  return 0;
+}
+
+int va_launch_sample(const float* logits, int B, int K, int vocab, const vaura_sampling* sp, const vaura_clip_sampling* clips,
+                     const float* noise, int /*noise_rows_per_step*/, const int32_t* state, int64_t step_host, int32_t* tokens_out,
                      int32_t* seq, int T, int S, int32_t* state_rw, const int32_t* delays_host, hipStream_t s) {
   if (!logits || !sp || B <= 0 || K <= 0) return VAURA_ERR_ARG;
+  if (clips && sp->input_is_probs) return VAURA_ERR_ARG;
   if (vocab != 1024) return VAURA_ERR_SHAPE;
   if (delays_host && K > 16) return VAURA_ERR_ARG;
   SampleArgs a;
@@ -539,7 +588,11 @@ int va_launch_sample(const float* logits, int B, int K, int vocab, const vaura_s
   a.cfg_scale = sp->input_is_probs ? 1.0f : sp->cfg_scale; a.seed = sp->seed; a.clip_base = sp->clip_base; a.step_host = step_host;
   a.probs_in = sp->input_is_probs;
   a.tie_eps = sp->tie_eps > 0.f ? sp->tie_eps : 0.f;
-  VA_LAUNCH(sample_kernel, dim3(K, B), dim3(SMP_THREADS), 0, s, a.logits, a.state, a);
+  if (clips) {
+    VA_LAUNCH(sample_kernel<true>, dim3(K, B), dim3(SMP_THREADS), 0, s, a.logits, a.state, a, reinterpret_cast<const int32_t*>(clips));
+    return 0;
+  }
+  VA_LAUNCH(sample_kernel<false>, dim3(K, B), dim3(SMP_THREADS), 0, s, a.logits, a.state, a, (const int32_t*)nullptr);
   return 0;
 }
 
@@ -644,8 +697,20 @@ int vaura_pattern_revert_delays(const int32_t* seq, int32_t* codes, int B, int K
 int vaura_sample(const float* logits, int B, int K, int vocab, const vaura_sampling* sp, const float* noise,
                  int64_t step, int32_t* tokens_out, vaura_stream_t s) {
   if (!tokens_out) return VAURA_ERR_ARG;
-  return va_launch_sample(logits, B, K, vocab, sp, noise, B * K, nullptr, step, tokens_out, nullptr, 0, 0, nullptr, nullptr,
+  return va_launch_sample(logits, B, K, vocab, sp, nullptr, noise, B * K, nullptr, step, tokens_out, nullptr, 0, 0, nullptr, nullptr,
                           as_stream(s));
+}
+
+int vaura_sample_clips(const float* logits, int B, int K, int vocab, const vaura_sampling* sp, const vaura_clip_sampling* clips,
+                       const float* noise, int64_t step, int32_t* tokens_out, int32_t* seq, int T, int S, int32_t* state,
+                       vaura_stream_t s) {
+  if (!clips || (!tokens_out && !seq)) return VAURA_ERR_ARG;
+  if (seq && (!state || T <= 0 || S <= 0)) return VAURA_ERR_ARG;
+  if (!logits || !sp || B <= 0 || K <= 0) return VAURA_ERR_ARG;
+  const int rc = va_check_clip_sampling(sp, clips, B, sp->cfg_scale > 1.0f, as_stream(s));
+  if (rc) return rc;
+  int32_t* st = seq ? state : nullptr;      // the standalone form keeps no state, like vaura_sample
+  return va_launch_sample(logits, B, K, vocab, sp, clips, noise, B * K, st, step, tokens_out, seq, T, S, st, nullptr, as_stream(s));
 }
 
 }  // extern "C"

@@ -124,6 +124,16 @@ def shard(total: int, rank: int, world: int) -> Tuple[int, int]:
     return first, count
 
 
+def shard_params(params: dict, total: int, rank: int, world: int) -> dict:
+    """The sampling arguments (``use_sampling``, ``temp``, ``top_k``, ``top_p``, ``cfg_scale``; other keys pass through) of the clips
+    ``shard(total, rank, world)`` gives this rank: per-clip sequences are cut by the same contiguous split, scalars are kept.  With
+    ``clip_base`` = the rank's first clip, a per-clip call then gives the same tokens for every world size, as scalar calls do."""
+    from . import clip_params
+    clip_params.check_lengths(total, **{k: v for k, v in params.items() if k in clip_params.NAMES})
+    first, count = shard(total, rank, world)
+    return {k: (clip_params.take(v, first, count) if k in clip_params.NAMES else v) for k, v in params.items()}
+
+
 def gather_clips(local: torch.Tensor, counts: List[int]) -> torch.Tensor:
     """All-gather per-rank results (clip dim 0, possibly ragged) into global clip order."""
     if _single():

@@ -19,6 +19,7 @@ from typing import Dict, Optional, Sequence
 import torch
 
 from . import _lib as L
+from . import clip_params
 from .synth import CodecCfg, SamplerCfg, fold_weight_norm
 
 
@@ -355,6 +356,7 @@ class DecoderEngine:
             self.cond_tmp = torch.zeros(crp * c.cond_dim, **f32)
             self.cond_proj = torch.zeros(crp * c.cond_dim, **f32)
             self.codes_i32 = torch.zeros(batch, K, timesteps, dtype=torch.int32, device=self.dev)
+            self.clip_params = torch.zeros(batch, 8, dtype=torch.int32, device=self.dev)   # vaura_clip_sampling records (per-clip calls)
         d = L.Decoder()
         d.dims = self.dims
         d.dims.tokens_per_frame = tokens_per_frame
@@ -364,6 +366,7 @@ class DecoderEngine:
         d.plane_shift = self.plane_shift
         d.kv_dtype = KV_DTYPES.index(self.kv_dtype)
         d.kscale, d.vscale = L.ptr(self.kscale), L.ptr(self.vscale)
+        d.clip_sampling = 0                # set per call by _sampling(): NULL = the scalars of the call's vaura_sampling
         if delays is not None:             # zero-filled = the default pattern (include/vaura_hip.h)
             d.has_pattern_delays = 1
             for q, dq in enumerate(delays):
@@ -427,10 +430,34 @@ class DecoderEngine:
 
     # ------------------------------------------------------------------ generation
     def _sampling(self, use_sampling, temp, top_k, top_p, cfg_scale, seed, clip_base) -> L.Sampling:
+        """The call's ``vaura_sampling``.  Each of the five parameters is a scalar or a length-B sequence / tensor (clip_params.py):
+        any sequence selects the per-clip path — the records go into the engine-owned device buffer the descriptor (and a captured
+        step graph) points at, and the struct then only says whether the rows are doubled; an all-scalar call leaves the descriptor's
+        pointer NULL and is the call it always was."""
+        tie = self.near_tie_eps if (self.near_tie != "off" and self.planes) else 0.0      # the exact-fp32 engine IS the reference's arithmetic
+        per_clip = clip_params.resolve(self.batch, use_sampling, temp, top_k, top_p, cfg_scale)
+        if per_clip is not None:
+            doubled = self.rows == 2 * self.batch
+            for b in range(self.batch):
+                us, tp, tk, pp, cs = (per_clip[n][b] for n in clip_params.NAMES)
+                if us and tp > 0.0 and not pp > 0.0 and tk > self.cfg.d_codebook:
+                    raise L.VauraHipError(f"top_k = {tk} of clip {b} exceeds the codebook size {self.cfg.d_codebook} (the reference's "
+                                          "torch.topk raises as well)")
+                if cs > 1.0 and not doubled:
+                    raise L.VauraHipError(f"cfg_scale = {cs} of clip {b} needs the null-condition rows: prepare the engine with cfg_on "
+                                          f"(rows = {self.rows}, batch = {self.batch})")
+            host = torch.frombuffer(bytearray(clip_params.pack_records(per_clip)), dtype=torch.int32).view(self.batch, 8)
+            self.clip_params.copy_(host)          # on the current stream, ahead of the loop that reads it
+            self.dec.clip_sampling = L.ptr(self.clip_params)
+            # scalars: unread by the per-clip sampler, except that cfg_scale > 1 states "rows [B, 2B) exist" (include/vaura_hip.h).
+            # Nothing here depends on the values, so the bytes of this struct key ONE graph for every per-clip call of a shape.
+            return L.Sampling(0, 1.0, 0, 0.0, 2.0 if doubled else 1.0, int(seed), int(clip_base), 0, float(tie))
+        if self.dec is not None:
+            self.dec.clip_sampling = 0
+        use_sampling, temp, top_k, top_p, cfg_scale = (clip_params._scalar(v) for v in (use_sampling, temp, top_k, top_p, cfg_scale))
         if use_sampling and temp > 0.0 and not top_p > 0.0 and int(top_k) > self.cfg.d_codebook:
             # the reference's sample_top_k is torch.topk(probs, k) (utils/utils.py:172): k beyond the codebook raises there too
             raise L.VauraHipError(f"top_k = {top_k} exceeds the codebook size {self.cfg.d_codebook} (the reference's torch.topk raises as well)")
-        tie = self.near_tie_eps if (self.near_tie != "off" and self.planes) else 0.0      # the exact-fp32 engine IS the reference's arithmetic
         return L.Sampling(int(bool(use_sampling)), float(temp), int(top_k), float(top_p),
                           float(cfg_scale if self.rows == 2 * self.batch else 1.0), int(seed), int(clip_base), 0, float(tie))
 
@@ -465,7 +492,8 @@ class DecoderEngine:
         with (off_null_stream(self.dev) if use_graph else contextlib.nullcontext()):
             st = L.current_stream(self.dev)
             if use_graph:
-                key = (self._shape, L.ptr(noise), bytes(sp))
+                # per-clip calls: the record POINTER and the canonical struct of _sampling() — "per-clip + row doubling", never the values
+                key = (self._shape, L.ptr(noise), bytes(sp), int(self.dec.clip_sampling or 0))
                 if self._graph_key != key:       # the captured step is tied to these buffers / parameters
                     self._free_graph()
                     handle = C.c_void_p()
@@ -573,9 +601,12 @@ class DecoderEngine:
                        clip_base=0, use_graph=True, tokens_per_frame=7, delays=None) -> torch.Tensor:
         """The hot loop of generate(): (B, Tv, 768) -> codes (B, K, T) int64 (device).  ``delays``: the codebook delay pattern
         (codebook_patterns.py:374-419; None = 0..K-1, ParallelPatternProvider = all zeros): S = T + max(d) + 1 sequence steps, the
-        loop samples steps Tp + 1 + d_0 .. S - 1, and an explicit ``noise`` has S - (Tp + 1 + d_0) steps."""
+        loop samples steps Tp + 1 + d_0 .. S - 1, and an explicit ``noise`` has S - (Tp + 1 + d_0) steps.
+        ``use_sampling``, ``temp``, ``top_k``, ``top_p``, ``cfg_scale``: a scalar, or one value per clip (list / tuple / 1-D tensor of
+        length B) — clip b is then decoded exactly as the scalar call with its values would decode it (``_sampling``)."""
         B, Tv, _ = feats.shape
-        cfg_on = cfg_scale > 1.0
+        clip_params.check_lengths(B, use_sampling=use_sampling, temp=temp, top_k=top_k, top_p=top_p, cfg_scale=cfg_scale)
+        cfg_on = clip_params.any_cfg(cfg_scale)     # some clip mixes: the whole batch carries the null-condition rows
         self._fc = None                       # the K/V cache is about to be reused: forward_cached must start over
         with off_null_stream(self.dev) as caller:
             self.prepare(B, max_new_tokens, Tv, cfg_on, tokens_per_frame, block_size=self.cfg.block_size, delays=delays)

@@ -46,7 +46,11 @@ def generate_long(model, frames: torch.Tensor, duration: float, *, stride: float
                   vfps: float = 25, frame_step: int = 1, clip_indices=None, use_sampling: bool = True, temp: float = 1.0,
                   top_k: int = 128, top_p: float = 0.0, cfg_scale: float = 1.0) -> dict:
     """frames: whatever the feature-extractor plugin accepts, segments on dim 1 — raw (B, S, C, T, H, W) or, with the
-    pass-through ``MotionFormer``, features (B, S, t, 768).  Returns {"generated_audio", "sampled_indices"}."""
+    pass-through ``MotionFormer``, features (B, S, t, 768).  Returns {"generated_audio", "sampled_indices"}.
+    ``use_sampling``, ``temp``, ``top_k``, ``top_p``, ``cfg_scale``: scalars, or one value per clip (length-B list / tuple / 1-D
+    tensor) — every chunk of clip b is sampled with clip b's values (``VAURAModel.generate_tokens``)."""
+    from .clip_params import check_lengths
+    check_lengths(frames.shape[0], use_sampling=use_sampling, temp=temp, top_k=top_k, top_p=top_p, cfg_scale=cfg_scale)
     if model_max_duration is None:   # scripts/generate.py:221-226
         model_max_duration = 2.56 if model.sampler.config.block_size > 64 else 0.64
     sched = chunk_schedule(duration, model_max_duration, stride, vfps)

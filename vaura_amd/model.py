@@ -24,6 +24,7 @@ import torch
 import torch.nn as nn
 
 from . import _lib as L
+from . import clip_params
 from .engine import off_null_stream
 from .patterns import DelayedPatternProvider
 from .utils import instantiate_from_config, sample_from_logits
@@ -243,8 +244,14 @@ class VAURAModel(nn.Module):
                         prompt_is_encoded: bool = False, cfg_scale: float = 1.0) -> torch.Tensor:
         """generate() up to and including revert_pattern_sequence (vaura_model.py:410-572): (B, K, T') int64 tokens on
         the device, no codec decode.  The sliding-window caller (vaura_amd.longform) uses this for every chunk and
-        decodes the concatenated tokens once, as the reference's script does (scripts/generate.py:366-369)."""
+        decodes the concatenated tokens once, as the reference's script does (scripts/generate.py:366-369).
+        ``use_sampling``, ``temp``, ``top_k``, ``top_p`` and ``cfg_scale`` each take a scalar or one value per clip (a length-B list /
+        tuple / 1-D tensor): clip b is decoded as the scalar call with its values would decode it, in the same batch
+        (``DecoderEngine.generate_codes``)."""
         assert not self.training, "do not use generation in training mode"
+        # per-clip parameter sequences of the wrong length: refused here, before any device work (frames carry the batch on dim 0)
+        clip_params.check_lengths(frames.shape[0] if hasattr(frames, "shape") else None, use_sampling=use_sampling, temp=temp,
+                                  top_k=top_k, top_p=top_p, cfg_scale=cfg_scale)
         if return_attention_weights:
             # the reference's own llama sampler returns (logits, None, None) (llama.py:520-539), so its generate() fails on
             # `sa_w[-1, -1, :]` (vaura_model.py:529-531) with this flag: there is no behaviour to reproduce
@@ -269,13 +276,13 @@ class VAURAModel(nn.Module):
         B = vis.shape[0]
         Tp = 0 if audio is None else int(audio.shape[-1])
         assert Tp < max_new_tokens, "gt audio prompt can not be longer than max_new_tokens"
-        use_cfg = cfg_scale > 1.0 and self.sampler.__class__.__name__ == "Transformer"
+        use_cfg = clip_params.any_cfg(cfg_scale) and self.sampler.__class__.__name__ == "Transformer"   # any clip's scale > 1
         eng = self.sampler.engine()
         if self.sampler.audio_tokens_per_video_frame is None:
             raise L.VauraHipError("sampler.audio_tokens_per_video_frame must be set (scripts/generate.py:216 sets 7)")
         S = max_new_tokens + max(delays) + 1
         start = Tp + 1 + delays[0]  # Pattern.get_first_step_with_timesteps(Tp) for sorted delays
-        greedy = not (use_sampling and temp > 0.0)
+        greedy = not clip_params.any_sampled(use_sampling, temp)     # per-clip: noise for the batch as soon as one clip draws
         noise = None if greedy else self._exp_noise(S - start, B * K, self.sampler.d_codebook)
         # decode loop + its status word in one synchronisation (the reference's own post-conditions, :550-572, synchronise too); an
         # activation beyond the fp16-plane range is re-run on the exact-fp32 engine instead of raising (engine.generate_codes_checked)
