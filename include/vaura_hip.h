@@ -224,6 +224,17 @@ typedef struct vaura_decoder {
    * call — vaura_generate_loop only when it launches eagerly, graph == NULL: replays of a built graph stay asynchronous; not while
    * the stream is being captured either.  Where nothing is read back the kernel clamps such a record to 1).  vaura_score ignores it. */
   const vaura_clip_sampling* clip_sampling;
+  /* Token log-probabilities (NULL: none — the sampler instances every earlier caller runs, unchanged): fp32 (batch, K, seq_len), the
+   * layout of `seq`.  Where the sampler's fix-up writes a SAMPLED token (a valid pattern slot that held -1) it writes, at the same
+   * index, the log-probability of that token under the distribution the decision was made from:
+   *     lp = log softmax(x / tau)[token] = (x[token] / tau - mx) - logf(den),  mx = max x / tau,  den = sum expf(x / tau - mx)
+   * with x the CFG-mixed, sanitised logits of (clip, codebook) and tau = temp where the clip samples (use_sampling && temp > 0), 1
+   * where it is greedy.  The softmax runs over the FULL vocabulary — the probability before any top-k / top-p truncation — so the
+   * values compare across candidates, across sampling settings and with vaura_score.  In the sampled branch mx and den are the very
+   * values the draw used.  Prompt, known and special slots are not written: the caller zeroes the buffer first.  On a (clip, codebook)
+   * row that raised VAURA_STATUS_NONFINITE_LOGITS the value is NaN.  The token drawn never depends on this pointer.  A captured step
+   * graph holds it like every other buffer.  VAURA_ERR_ARG together with input_is_probs = 1.  vaura_score ignores it. */
+  float* logprobs;
 } vaura_decoder;
 
 /* -------------------------------------------------------------------------------------------
@@ -280,6 +291,31 @@ int vaura_sample(const float* logits, int B, int K, int vocab, const vaura_sampl
 int vaura_sample_clips(const float* logits, int B, int K, int vocab, const vaura_sampling* sp, const vaura_clip_sampling* clips,
                        const float* noise, int64_t step, int32_t* tokens_out, int32_t* seq, int T, int S, int32_t* state,
                        vaura_stream_t s);
+
+/* vaura_sample_clips (clips == NULL: the scalars of sp, i.e. vaura_sample; seq / T / S / state as there, NULL seq = the standalone
+ * form) that also reports the log-probability of every token drawn: logprobs_out (B, K) fp32, defined at vaura_decoder.logprobs
+ * (written for every (clip, codebook), whatever the slot held).  The tokens equal what vaura_sample / vaura_sample_clips return for
+ * the same inputs.  VAURA_ERR_ARG: input_is_probs = 1 (rows that already are probabilities have no log-probability to report), a
+ * NULL logprobs_out, and what vaura_sample_clips refuses.                                                                          */
+int vaura_sample_logprobs(const float* logits, int B, int K, int vocab, const vaura_sampling* sp, const vaura_clip_sampling* clips,
+                          const float* noise, int64_t step, int32_t* tokens_out, int32_t* seq, int T, int S, int32_t* state,
+                          float* logprobs_out, vaura_stream_t s);
+/* float twin of vaura_pattern_revert_delays: seq (B,K,S) fp32 -> out (B,K,T), frame t of codebook q from step t + 1 + d_q, `fill`
+ * where S ends before it.  delays_host == NULL: d_q = q.                                                                           */
+int vaura_pattern_revert_delays_f32(const float* seq, float* out, int B, int K, int T, int S, float fill, const int32_t* delays_host,
+                                    vaura_stream_t s);
+/* Sequence scores from token log-probabilities in the layout of seq (vaura_decoder.logprobs): logprobs (B, K, seq_len), seq_len =
+ * T + max(d) + 1 (VAURA_ERR_SHAPE otherwise; delays_host NULL: d_q = q), K <= 16.  per_codebook (B, K) = mean over frames t0 .. T - 1
+ * (t0 = prompt frames, excluded) of codebook q, per_clip (B) = mean of those K means.  Fixed summation order (one wave per codebook:
+ * lane l adds frames t0 + l, t0 + l + 64, ..; lanes are added pairwise at distance 1, 2, 4, .. 32; the K means in codebook order):
+ * two runs give the same bits.  A NaN anywhere in a clip makes per_clip AND all K per_codebook values of that clip NaN.            */
+int vaura_sequence_logprob(const float* logprobs, int seq_len, const int32_t* delays_host, int B, int K, int T, int t0,
+                           float* per_codebook, float* per_clip, vaura_stream_t s);
+/* Best-of-N selection: scores (B * N), candidate j of clip b at b * N + j; codes (B * N, K, T) -> codes_out (B, K, T) = the codes of
+ * the candidate with the largest score, winner (B) its index j.  The first index wins a tie; a NaN never beats a number; when every
+ * score of a clip is NaN, candidate 0 wins.                                                                                        */
+int vaura_select_candidates(const float* scores, const int32_t* codes, int B, int N, int K, int T, int32_t* codes_out, int32_t* winner,
+                            vaura_stream_t s);
 
 /* -------------------------------------------------------------------------------------------
  * a3..a12 + a2/a13/a15 for ONE position: Transformer.inference (llama.py:445-504) restricted to the

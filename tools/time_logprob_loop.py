@@ -1,0 +1,52 @@
+"""The 228-step decode loop of BASELINE configs[1] (8 clips x 2.56 s, T = 220, top-k 250, temperature 1, cfg 6, un-rounded checkpoint,
+storage "auto") through DecoderEngine.generate_codes, timed with HIP events around 5 batches enqueued back to back (median of
+--repeat such regions):    python tools/time_logprob_loop.py [--package-root D] [--repeat R]
+
+  plain            return_logprobs=False: the sampler instances without log-probabilities
+  logprobs         return_logprobs=True: sample_kernel<PC, LP = true> + the float revert + vaura_sequence_logprob
+  candidates 2x4   num_candidates=4 at B = 2 (the same 8 sequences, 16 decoder rows; the condition MLP on 2 clips) with log-probabilities
+
+--package-root D imports vaura_amd from D (another build of the library, e.g. the parent commit): modes that tree does not have are
+skipped, so the plain line of two trees can be taken in one session on one card."""
+import argparse
+import inspect
+import os
+import sys
+
+ap = argparse.ArgumentParser()
+ap.add_argument("--package-root", default=os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+ap.add_argument("--repeat", type=int, default=5)
+args = ap.parse_args()
+import torch  # noqa: E402
+sys.path.insert(0, os.path.abspath(args.package_root))
+from vaura_amd import synth  # noqa: E402
+from vaura_amd.engine import DecoderEngine  # noqa: E402
+
+dev = torch.device("cuda:0")
+cfg = synth.FULL_SAMPLER
+eng = DecoderEngine(cfg, synth.sampler_state_dict(cfg, seed=0, round_bf16=False), dev)
+kw = dict(use_sampling=True, temp=1.0, top_k=250, cfg_scale=6.0, seed=1)
+has_lp = "return_logprobs" in inspect.signature(eng.generate_codes).parameters
+modes = [("plain", 8, {})]
+if has_lp:
+    modes += [("logprobs", 8, dict(return_logprobs=True)), ("candidates 2x4", 2, dict(return_logprobs=True, num_candidates=4))]
+print(f"tree {os.path.abspath(args.package_root)}: storage {eng.wdtype}, 228 steps per batch, 5 batches per region, {args.repeat} regions")
+s = torch.cuda.Stream(dev)
+with torch.cuda.stream(s):
+    for name, clips, extra in modes:
+        feats = synth.video_features(clips, seed=0).to(dev)
+        for _ in range(2):
+            eng.generate_codes(feats, 220, **kw, **extra)
+        torch.cuda.synchronize()
+        ms = []
+        for _ in range(args.repeat):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for _ in range(5):
+                eng.generate_codes(feats, 220, **kw, **extra)
+            e1.record()
+            torch.cuda.synchronize()
+            ms.append(e0.elapsed_time(e1) / 5)
+        eng.check_status()        # a broken hand-off / non-finite logits would make these times meaningless: fail instead
+        ms.sort()
+        print(f"{name:16s} {ms[len(ms) // 2]:8.3f} ms per batch (median; min {ms[0]:.3f}, max {ms[-1]:.3f}) = {ms[len(ms) // 2] / 228 * 1e3:7.2f} us per step")

@@ -3,12 +3,15 @@
 --clips B        clips per launch (default 8; the CFG modes carry 2 B rows: 8 -> 16 rows, 16 -> 32 rows)
 --per-clip       time the per-clip instance (vaura_sample_clips, B records holding the same parameters) next to the scalar one,
                  both as 200 launches of one captured graph
+--logprobs       add the LP column: the same launch through vaura_sample_logprobs (sample_kernel<PC, LP = true>: the token's log-probability
+                 kept and stored), eager and, with --per-clip, inside the captured graph
 --repeat R       print R lines per mode (run-to-run spread)
 --package-root D import vaura_amd from D instead of this tree (A/B against another build of the library)"""
 import argparse, os, sys
 ap = argparse.ArgumentParser()
 ap.add_argument("--clips", type=int, default=8)
 ap.add_argument("--per-clip", action="store_true")
+ap.add_argument("--logprobs", action="store_true")
 ap.add_argument("--repeat", type=int, default=1)
 ap.add_argument("--package-root", default=os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 args = ap.parse_args()
@@ -21,16 +24,20 @@ dev = "cuda:0"
 B, K, V = args.clips, 9, 1024
 logits = torch.randn(2 * B, K * V, device=dev) * 3
 tokens = torch.zeros(B * K, dtype=torch.int32, device=dev)
-def run(use_sampling, top_k, top_p, cfg, tie_eps=0.0, per_clip=False, graph=False):
+logprobs = torch.zeros(B * K, dtype=torch.float32, device=dev)
+def run(use_sampling, top_k, top_p, cfg, tie_eps=0.0, per_clip=False, graph=False, lp=False):
     sp = L.Sampling()
     sp.use_sampling, sp.top_k, sp.temp, sp.top_p, sp.cfg_scale, sp.seed, sp.clip_base, sp.input_is_probs = use_sampling, top_k, 1.0, top_p, cfg, 1, 0, 0
     sp.tie_eps = tie_eps          # near-tie screen (round 6): 0 = off
+    rec = None
     if per_clip:                  # the same parameters, from B device records (include/vaura_hip.h vaura_clip_sampling)
         from vaura_amd import clip_params
         rec = clip_params.pack_records(clip_params.resolve(B, [use_sampling] * B, 1.0, top_k, top_p, cfg))
         rec = torch.frombuffer(bytearray(rec), dtype=torch.int32).to(dev)
         launch = lambda i: lib.vaura_sample_clips(L.ptr(logits), B, K, V, C.byref(sp), L.ptr(rec), None, i, L.ptr(tokens), None, 0, 0, None, L.current_stream(torch.device(dev)))
-    else:
+    if lp:                        # LP = true instances (records or scalars)
+        launch = lambda i: lib.vaura_sample_logprobs(L.ptr(logits), B, K, V, C.byref(sp), L.ptr(rec), None, i, L.ptr(tokens), None, 0, 0, None, L.ptr(logprobs), L.current_stream(torch.device(dev)))
+    elif not per_clip:
         launch = lambda i: lib.vaura_sample(L.ptr(logits), B, K, V, C.byref(sp), None, i, L.ptr(tokens), L.current_stream(torch.device(dev)))
     s = torch.cuda.Stream()
     if graph:
@@ -69,4 +76,8 @@ for _ in range(args.repeat):
         if args.per_clip:
             line += (f"; 200 launches in one captured graph: scalar {run(*a, graph=True):.2f}, per-clip records {run(*a, per_clip=True, graph=True):.2f}"
                      f"; with the screen: scalar {run(*a, 1.5e-6, graph=True):.2f}, per-clip records {run(*a, 1.5e-6, True, True):.2f}")
+        if args.logprobs:
+            line += f"; LP (vaura_sample_logprobs): {run(*a, lp=True):.2f}"
+            if args.per_clip:
+                line += f", in the graph: scalar {run(*a, graph=True, lp=True):.2f}, per-clip records {run(*a, per_clip=True, graph=True, lp=True):.2f}"
         print(f"[{B} clips] {line}" if (args.clips != 8 or args.per_clip or args.repeat > 1) else line)

@@ -58,7 +58,7 @@ class Decoder(C.Structure):
                 ("ws_h_split", C.c_void_p), ("ws_attn_split", C.c_void_p), ("ws_ffn_split", C.c_void_p),
                 ("ws_ss", C.c_void_p), ("first_norm", C.c_void_p), ("ws_attn_part", C.c_void_p), ("ws_sync", C.c_void_p),
                 ("has_pattern_delays", C.c_int32), ("pattern_delays", C.c_int32 * 16),
-                ("kscale", C.c_void_p), ("vscale", C.c_void_p), ("clip_sampling", C.c_void_p)]
+                ("kscale", C.c_void_p), ("vscale", C.c_void_p), ("clip_sampling", C.c_void_p), ("logprobs", C.c_void_p)]
 
 
 class Conv(C.Structure):
@@ -154,6 +154,14 @@ SIGNATURES = {
                                C.c_void_p, C.c_void_p]),
     "vaura_sample_clips": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(Sampling), C.c_void_p, C.c_void_p, C.c_int64,
                                      C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "vaura_sample_logprobs": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(Sampling), C.c_void_p, C.c_void_p, C.c_int64,
+                                        C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "vaura_pattern_revert_delays_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float,
+                                                  C.POINTER(C.c_int32), C.c_void_p]),
+    "vaura_sequence_logprob": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int32), C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p,
+                                         C.c_void_p, C.c_void_p]),
+    "vaura_select_candidates": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                          C.c_void_p]),
     "vaura_decode_step": (C.c_int, [C.POINTER(Decoder), C.POINTER(Sampling), C.c_int, C.c_void_p]),
     "vaura_generate_loop": (C.c_int, [C.POINTER(Decoder), C.POINTER(Sampling), C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "vaura_step_graph_build": (C.c_int, [C.POINTER(Decoder), C.POINTER(Sampling), C.c_void_p, C.POINTER(C.c_void_p)]),

@@ -93,6 +93,14 @@ def take(v, first: int, count: int):
     return v[first:first + count] if is_per_clip(v) else v
 
 
+def repeat(v, n: int):
+    """One argument of a best-of-N call: every clip's value ``n`` times in a row (candidate j of clip b is row b * n + j); a scalar as it is."""
+    if not is_per_clip(v):
+        return v
+    vals = v.tolist() if hasattr(v, "tolist") else list(v)
+    return [x for x in vals for _ in range(n)]
+
+
 def pack_records(p: Dict[str, List]) -> bytes:
     """``vaura_clip_sampling`` records, one per clip, as the device buffer holds them."""
     return b"".join(struct.pack("<ififf3i", p["use_sampling"][b], p["temp"][b], p["top_k"][b], p["top_p"][b], p["cfg_scale"][b], 0, 0, 0)

@@ -133,6 +133,7 @@ static int enqueue_prefill_chunk_heads(const vaura_decoder* d, int p0, int n, fl
 // per-clip sampling records of a decoder call (vaura_decoder.clip_sampling): refused with probability rows, and with a clip scale > 1
 // when the descriptor carries no null-condition rows (step.hip va_check_clip_sampling)
 static int check_clips(const vaura_decoder* d, const vaura_sampling* sp, hipStream_t s) {
+  if (d->logprobs && sp && sp->input_is_probs) return VAURA_ERR_ARG;      // probability rows have no log-probability to report (step.hip LP)
   return va_check_clip_sampling(sp, d->clip_sampling, d->batch, d->rows == 2 * d->batch, s);
 }
 
@@ -266,7 +267,7 @@ static int enqueue_step_bf16(const vaura_decoder* d, const vaura_sampling* sp, i
   if (rc) return rc;
   PROF_B(VAURA_K_SAMPLE);
   rc = va_launch_sample(d->ws_logits, d->batch, m.n_codebooks, m.vocab, sp, d->clip_sampling, d->noise, d->batch * m.n_codebooks, d->state, 0,
-                        nullptr, d->seq, d->timesteps, d->seq_len, d->state, va_pattern_delays(d), s);
+                        nullptr, d->seq, d->timesteps, d->seq_len, d->state, va_pattern_delays(d), s, nullptr, d->logprobs);
   PROF_A(VAURA_K_SAMPLE);
   return rc;
 }
@@ -322,7 +323,7 @@ static int enqueue_step(const vaura_decoder* d, const vaura_sampling* sp, int sa
   if (rc) return rc;
   PROF_B(VAURA_K_SAMPLE);
   rc = va_launch_sample(d->ws_logits, d->batch, m.n_codebooks, m.vocab, sp, d->clip_sampling, d->noise, d->batch * m.n_codebooks, d->state, 0,
-                          nullptr, d->seq, d->timesteps, d->seq_len, d->state, va_pattern_delays(d), s);
+                          nullptr, d->seq, d->timesteps, d->seq_len, d->state, va_pattern_delays(d), s, nullptr, d->logprobs);
   PROF_A(VAURA_K_SAMPLE);
   return rc;
 }
@@ -544,6 +545,7 @@ int vaura_score(const vaura_decoder* dec, int n_pos, const int32_t* targets, flo
     // stay in state[4] for the caller.
     vaura_sampling sp = {};
     vaura_decoder plain = *dec;
+    plain.logprobs = nullptr;             // ... and reports no token log-probabilities
     plain.clip_sampling = nullptr;        // scoring has no sampling parameters, per clip or otherwise
     for (int p = 0; p < n_pos; ++p) {
       rc = enqueue_step(&plain, &sp, 1, st);

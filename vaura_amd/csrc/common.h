@@ -224,7 +224,8 @@ int va_launch_embed(const vaura_decoder* d, int pos_host, int n_pos, hipStream_t
 // clips: per-clip records (vaura_decoder.clip_sampling) or NULL for the scalars of `sp`
 int va_launch_sample(const float* logits, int B, int K, int vocab, const vaura_sampling* sp, const vaura_clip_sampling* clips,
                      const float* noise, int noise_rows_per_step, const int32_t* state, int64_t step_host, int32_t* tokens_out,
-                     int32_t* seq, int T, int S, int32_t* state_rw, const int32_t* delays_host, hipStream_t s);
+                     int32_t* seq, int T, int S, int32_t* state_rw, const int32_t* delays_host, hipStream_t s,
+                     float* lp_out /* (B, K) */, float* lp_seq /* (B, K, S); either non-NULL selects the LP instances */);
 int va_check_clip_sampling(const vaura_sampling* sp, const vaura_clip_sampling* clips, int B, bool doubled, hipStream_t s);
 int va_launch_advance(int32_t* state, int set_to, hipStream_t s);
 int va_launch_linear_pair(const uint16_t* in, const uint16_t* w, const float* bias, const float* res, float* out_raw,

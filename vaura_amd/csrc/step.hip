@@ -199,10 +199,27 @@ __device__ __forceinline__ int block_count(int v, int* si) {
 // PC (per-clip parameters, vaura_decoder.clip_sampling): the workgroup of clip b = blockIdx.y takes use_sampling / temp / top_k / top_p /
 // cfg_scale from record b of `clips` instead of the launch's scalars; everything below reads them through `a` either way.  PC = false
 // is the scalar launch as it always was: the fetch is compiled out and `clips` (NULL) is never read.
+// LP (token log-probabilities, vaura_decoder.logprobs / vaura_sample_logprobs): the kernel also reports log softmax(x / tau)[token] of the
+// decision it made — x the CFG-mixed, sanitised logits, tau = temp where the clip samples and 1 where it is greedy, over the FULL
+// vocabulary (before any top-k / top-p cut).  The sampled branch keeps the maximum and the denominator its draw used; the greedy branch
+// pays one block_max and one block_sum more, same order.  The thread that owns the token's column does the epilogue (tid 0 otherwise) and
+// stores the value next to the token.  LP = false compiles all of it out: those two instances are the kernels they were.
+// The two output pointers travel as a trailing parameter PACK that is empty when LP = false: those instances keep the argument list, and
+// with it the kernel-argument offsets, of the kernels they were (an extra pointer would move the hidden arguments behind it).
 typedef int32_t i32x4 __attribute__((ext_vector_type(4)));
-template <bool PC>
+struct SampleLogprobs {
+  float* out;   // (B, K) next to tokens_out, or null
+  float* seq;   // (B, K, S) in the layout of seq, or null
+};
+template <typename T, typename... R>
+__device__ __forceinline__ T va_first(T t, R...) { return t; }
+template <bool PC, bool LP, typename... LpArgs>
 __global__ __launch_bounds__(SMP_THREADS) void sample_kernel(const float* __restrict__ logits_q, const int32_t* __restrict__ state_q,
-                                                             SampleArgs a, const int32_t* __restrict__ clips) {
+                                                             SampleArgs a, const int32_t* __restrict__ clips, LpArgs... lp_args) {
+  static_assert(sizeof...(LpArgs) == (LP ? 1 : 0), "LP instances take one SampleLogprobs, the others nothing");
+  [[maybe_unused]] float* lp_out = nullptr;
+  [[maybe_unused]] float* lp_seq = nullptr;
+  if constexpr (LP) { lp_out = va_first(lp_args...).out; lp_seq = va_first(lp_args...).seq; }
   a.logits = logits_q;   // explicit scalar copies: preloaded into SGPRs at wave launch (the struct is not)
   a.state = state_q;
   __shared__ float sv[8];
@@ -255,6 +272,8 @@ __global__ __launch_bounds__(SMP_THREADS) void sample_kernel(const float* __rest
   // is never changed here.  What the host does with it is policy (engine.py near_tie: report | rerun on the exact-fp32 twin).
   bool near_tie = false;
   float tie_delta = 0.f;       // absolute bound on a mixed logit's error
+  [[maybe_unused]] int lp_bad = 0;                         // LP only
+  [[maybe_unused]] float lp_mx = 0.f, lp_den = 1.f;        // LP only: maximum and denominator of softmax(x / tau)
   const bool tie_on = a.tie_eps > 0.f && !a.probs_in;
   const float tie_mix = a.tie_eps * (a.cfg_scale > 1.0f ? 2.f * a.cfg_scale - 1.f : 1.f);
   if (tie_on && !(a.use_sampling && a.temp > 0.0f)) tie_delta = tie_mix * block_max(amax, sv);      // greedy: its own reduction; sampled: with the softmax's maximum
@@ -270,7 +289,9 @@ __global__ __launch_bounds__(SMP_THREADS) void sample_kernel(const float* __rest
     // top-k sampling).  The token drawn from the sanitised row is meaningless — the status bit says so — but it is a valid id.
 #pragma unroll
     for (int j = 0; j < 4; ++j) x[j] = fabsf(x[j]) < INFINITY ? x[j] : 0.f;
+    if constexpr (LP) lp_bad = 1;
   }
+  if constexpr (LP) lp_bad = __syncthreads_or(lp_bad);     // the row held an inf / NaN somewhere: its score is NaN, like its status bit
 
   int token;
   if (!(a.use_sampling && a.temp > 0.0f)) {
@@ -286,6 +307,13 @@ __global__ __launch_bounds__(SMP_THREADS) void sample_kernel(const float* __rest
       for (int j = 0; j < 4; ++j) if (4 * tid + j != ri) second = fmaxf(second, x[j]);
       second = block_max(second, sv);
       near_tie = (rv - second) < 2.f * tie_delta;
+    }
+    if constexpr (LP) {        // tau = 1: the reductions of the sampled branch, in its order
+      lp_mx = block_max(fmaxf(fmaxf(x[0], x[1]), fmaxf(x[2], x[3])), sv);
+      float e[4];
+#pragma unroll
+      for (int j = 0; j < 4; ++j) e[j] = expf(x[j] - lp_mx);
+      lp_den = block_sum((e[0] + e[1]) + (e[2] + e[3]), sv);
     }
   } else {
     // softmax(logits / temp) — or the input rows themselves when they already are probabilities (utils/utils.py:139-196)
@@ -308,6 +336,7 @@ __global__ __launch_bounds__(SMP_THREADS) void sample_kernel(const float* __rest
       const float den = block_sum((p[0] + p[1]) + (p[2] + p[3]), sv);
 #pragma unroll
       for (int j = 0; j < 4; ++j) p[j] = p[j] / den;
+      if constexpr (LP) { lp_mx = mx; lp_den = den; }      // the values the draw uses
     }
 
     // Exp(1) draws for this (clip, codebook, step)
@@ -512,8 +541,17 @@ __global__ __launch_bounds__(SMP_THREADS) void sample_kernel(const float* __rest
     }
   }
 
-  if (tid == 0) {
+  [[maybe_unused]] float lp = 0.f;
+  if constexpr (LP) {          // (x holds x / tau here; static register indices)
+    float xt = x[0];
+#pragma unroll
+    for (int j = 1; j < 4; ++j) if ((token & 3) == j) xt = x[j];
+    lp = lp_bad ? __builtin_nanf("") : (xt - lp_mx) - logf(lp_den);
+  }
+  const int writer = LP ? (token >> 2) : 0;      // LP: the thread that holds the token's logit
+  if (tid == writer) {
     if (a.tokens_out) a.tokens_out[b * a.K + k] = token;
+    if constexpr (LP) if (lp_out) lp_out[b * a.K + k] = lp;
     if (a.seq) {
       // vaura_model.py:536-544 — invalid pattern slots become the special token; known tokens are kept
       int dk = k;                // this codebook's delay (static indices: k is uniform, a run-time index would go to scratch)
@@ -526,6 +564,7 @@ __global__ __launch_bounds__(SMP_THREADS) void sample_kernel(const float* __rest
         int32_t* slot = a.seq + ((size_t)b * a.K + k) * a.S + offset;
         if (*slot == -1) {
           *slot = tok;
+          if constexpr (LP) if (lp_seq && t >= 0 && t < a.T) lp_seq[((size_t)b * a.K + k) * a.S + offset] = lp;   // a sampled token only
           // near-tie detector: only decisions that are USED count (a valid pattern slot that was still unknown)
           if (near_tie && t >= 0 && t < a.T && a.state_rw) {
             __hip_atomic_fetch_or(&a.state_rw[4], VAURA_STATUS_NEAR_TIE, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -575,9 +614,12 @@ int va_check_clip_sampling(const vaura_sampling* sp, const vaura_clip_sampling* 
 
 int va_launch_sample(const float* logits, int B, int K, int vocab, const vaura_sampling* sp, const vaura_clip_sampling* clips,
                      const float* noise, int /*noise_rows_per_step*/, const int32_t* state, int64_t step_host, int32_t* tokens_out,
-                     int32_t* seq, int T, int S, int32_t* state_rw, const int32_t* delays_host, hipStream_t s) {
+                     int32_t* seq, int T, int S, int32_t* state_rw, const int32_t* delays_host, hipStream_t s, float* lp_out,
+                     float* lp_seq) {
   if (!logits || !sp || B <= 0 || K <= 0) return VAURA_ERR_ARG;
   if (clips && sp->input_is_probs) return VAURA_ERR_ARG;
+  const bool lp = lp_out || lp_seq;
+  if (lp && sp->input_is_probs) return VAURA_ERR_ARG;        // rows that already are probabilities: no log-probability to report
   if (vocab != 1024) return VAURA_ERR_SHAPE;
   if (delays_host && K > 16) return VAURA_ERR_ARG;
   SampleArgs a;
@@ -588,11 +630,17 @@ int va_launch_sample(const float* logits, int B, int K, int vocab, const vaura_s
   a.cfg_scale = sp->input_is_probs ? 1.0f : sp->cfg_scale; a.seed = sp->seed; a.clip_base = sp->clip_base; a.step_host = step_host;
   a.probs_in = sp->input_is_probs;
   a.tie_eps = sp->tie_eps > 0.f ? sp->tie_eps : 0.f;
-  if (clips) {
-    VA_LAUNCH(sample_kernel<true>, dim3(K, B), dim3(SMP_THREADS), 0, s, a.logits, a.state, a, reinterpret_cast<const int32_t*>(clips));
+  const int32_t* rec = reinterpret_cast<const int32_t*>(clips);
+  // (named outside the macro: the commas of the template arguments would split its argument list)
+  const auto k_plain = sample_kernel<false, false>, k_pc = sample_kernel<true, false>;
+  const auto k_lp = sample_kernel<false, true, SampleLogprobs>, k_pc_lp = sample_kernel<true, true, SampleLogprobs>;
+  if (lp) {
+    if (clips) VA_LAUNCH(k_pc_lp, dim3(K, B), dim3(SMP_THREADS), 0, s, a.logits, a.state, a, rec, SampleLogprobs{lp_out, lp_seq});
+    else VA_LAUNCH(k_lp, dim3(K, B), dim3(SMP_THREADS), 0, s, a.logits, a.state, a, rec, SampleLogprobs{lp_out, lp_seq});
     return 0;
   }
-  VA_LAUNCH(sample_kernel<false>, dim3(K, B), dim3(SMP_THREADS), 0, s, a.logits, a.state, a, (const int32_t*)nullptr);
+  if (clips) VA_LAUNCH(k_pc, dim3(K, B), dim3(SMP_THREADS), 0, s, a.logits, a.state, a, rec);
+  else VA_LAUNCH(k_plain, dim3(K, B), dim3(SMP_THREADS), 0, s, a.logits, a.state, a, rec);
   return 0;
 }
 
@@ -672,6 +720,58 @@ static int pattern_revert(const int32_t* seq, int32_t* codes, int B, int K, int 
   return 0;
 }
 
+// float twin of pattern_revert_kernel (token log-probabilities live in the layout of seq): the same index map
+__global__ void pattern_revert_f32_kernel(const float* __restrict__ seq, float* __restrict__ out, int B, int K, int T, int S, float fill,
+                                          PatternDelays pd) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= (int64_t)B * K * T) return;
+  const int t = (int)(i % T), q = (int)((i / T) % K);
+  const int64_t b = i / ((int64_t)T * K);
+  const int s = t + 1 + pattern_delay(pd, q);
+  out[i] = (s < S) ? seq[((size_t)b * K + q) * S + s] : fill;
+}
+
+// Sequence scores of token log-probabilities kept in the layout of seq.  One workgroup per clip, one wave per codebook (K <= 16), in a
+// fixed order (the scheme of csrc/score.hip): lane l adds frames t0 + l, t0 + l + 64, .. of its codebook one after the other, the wave's
+// fixed butterfly (wave_sum: neighbours at distance 1, 2, 4, .., 32) adds the lanes, the mean is sum / (T - t0); thread 0 then adds the K
+// means in codebook order and divides by K.  Two runs give the same bits; a NaN anywhere in the clip reaches the clip's score through
+// the sums (and every codebook's mean is then reported NaN as well: the clip's scores are not to be used).
+__global__ __launch_bounds__(1024) void sequence_logprob_kernel(const float* __restrict__ lp, int B, int K, int T, int S, int t0,
+                                                                PatternDelays pd, float* __restrict__ per_codebook,
+                                                                float* __restrict__ per_clip) {
+  __shared__ float means[16];
+  const int lane = threadIdx.x & 63, q = threadIdx.x >> 6, b = blockIdx.x;
+  const int dq = pattern_delay(pd, q);
+  const float* row = lp + ((size_t)b * K + q) * S + 1 + dq;
+  float acc = 0.f;
+  for (int t = t0 + lane; t < T; t += 64) acc += (t + 1 + dq < S) ? row[t] : 0.f;
+  acc = wave_sum(acc);
+  if (lane == 0) means[q] = acc / (float)(T - t0);
+  __syncthreads();
+  float tot = 0.f;
+  for (int j = 0; j < K; ++j) tot += means[j];
+  tot = tot / (float)K;
+  if (lane == 0) per_codebook[(size_t)b * K + q] = (tot != tot) ? tot : means[q];
+  if (threadIdx.x == 0) per_clip[b] = tot;
+}
+
+// Best-of-N: one workgroup per clip picks the candidate with the largest score — the first index wins a tie, a NaN never beats a
+// number, candidate 0 when every score is NaN — and copies its (K, T) codes.
+__global__ __launch_bounds__(256) void select_candidates_kernel(const float* __restrict__ scores, const int32_t* __restrict__ codes, int N,
+                                                                int KT, int32_t* __restrict__ codes_out, int32_t* __restrict__ winner) {
+  const int b = blockIdx.x;
+  int best = 0;
+  float sb = scores[(size_t)b * N];
+  for (int j = 1; j < N; ++j) {
+    const float sj = scores[(size_t)b * N + j];
+    if (sj > sb || (sb != sb && sj == sj)) { best = j; sb = sj; }
+  }
+  const int32_t* src = codes + ((size_t)b * N + best) * KT;
+  int32_t* dst = codes_out + (size_t)b * KT;
+  for (int i = threadIdx.x; i < KT; i += blockDim.x) dst[i] = src[i];
+  if (threadIdx.x == 0) winner[b] = best;
+}
+
 extern "C" {
 
 int vaura_pattern_build(const int32_t* codes, int32_t* seq, int B, int K, int T, int special, vaura_stream_t s) {
@@ -698,7 +798,7 @@ int vaura_sample(const float* logits, int B, int K, int vocab, const vaura_sampl
                  int64_t step, int32_t* tokens_out, vaura_stream_t s) {
   if (!tokens_out) return VAURA_ERR_ARG;
   return va_launch_sample(logits, B, K, vocab, sp, nullptr, noise, B * K, nullptr, step, tokens_out, nullptr, 0, 0, nullptr, nullptr,
-                          as_stream(s));
+                          as_stream(s), nullptr, nullptr);
 }
 
 int vaura_sample_clips(const float* logits, int B, int K, int vocab, const vaura_sampling* sp, const vaura_clip_sampling* clips,
@@ -710,7 +810,53 @@ int vaura_sample_clips(const float* logits, int B, int K, int vocab, const vaura
   const int rc = va_check_clip_sampling(sp, clips, B, sp->cfg_scale > 1.0f, as_stream(s));
   if (rc) return rc;
   int32_t* st = seq ? state : nullptr;      // the standalone form keeps no state, like vaura_sample
-  return va_launch_sample(logits, B, K, vocab, sp, clips, noise, B * K, st, step, tokens_out, seq, T, S, st, nullptr, as_stream(s));
+  return va_launch_sample(logits, B, K, vocab, sp, clips, noise, B * K, st, step, tokens_out, seq, T, S, st, nullptr, as_stream(s), nullptr, nullptr);
+}
+
+int vaura_sample_logprobs(const float* logits, int B, int K, int vocab, const vaura_sampling* sp, const vaura_clip_sampling* clips,
+                          const float* noise, int64_t step, int32_t* tokens_out, int32_t* seq, int T, int S, int32_t* state,
+                          float* logprobs_out, vaura_stream_t s) {
+  if (!logits || !sp || !logprobs_out || (!tokens_out && !seq) || B <= 0 || K <= 0) return VAURA_ERR_ARG;
+  if (seq && (!state || T <= 0 || S <= 0)) return VAURA_ERR_ARG;
+  if (sp->input_is_probs) return VAURA_ERR_ARG;
+  const int rc = va_check_clip_sampling(sp, clips, B, sp->cfg_scale > 1.0f, as_stream(s));
+  if (rc) return rc;
+  int32_t* st = seq ? state : nullptr;
+  return va_launch_sample(logits, B, K, vocab, sp, clips, noise, B * K, st, step, tokens_out, seq, T, S, st, nullptr, as_stream(s),
+                          logprobs_out, nullptr);
+}
+
+int vaura_pattern_revert_delays_f32(const float* seq, float* out, int B, int K, int T, int S, float fill, const int32_t* delays_host,
+                                    vaura_stream_t s) {
+  if (!seq || !out || B <= 0 || K <= 0 || T <= 0 || S <= 0) return VAURA_ERR_ARG;
+  PatternDelays pd;
+  const int span = pattern_delays_arg(delays_host, K, &pd);
+  if (span < 0) return span;
+  if (delays_host && S > T + span) return VAURA_ERR_SHAPE;
+  const int64_t n = (int64_t)B * K * T;
+  VA_LAUNCH(pattern_revert_f32_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, as_stream(s), seq, out, B, K, T, S, fill, pd);
+  return 0;
+}
+
+int vaura_sequence_logprob(const float* logprobs, int seq_len, const int32_t* delays_host, int B, int K, int T, int t0,
+                           float* per_codebook, float* per_clip, vaura_stream_t s) {
+  if (!logprobs || !per_codebook || !per_clip || B <= 0 || K <= 0 || T <= 0 || seq_len <= 0 || t0 < 0 || t0 >= T) return VAURA_ERR_ARG;
+  if (K > 16) return VAURA_ERR_SHAPE;
+  PatternDelays pd;
+  const int span = pattern_delays_arg(delays_host, K, &pd);
+  if (span < 0) return span;
+  if (seq_len != T + span) return VAURA_ERR_SHAPE;      // every frame of every codebook has its slot
+  VA_LAUNCH(sequence_logprob_kernel, dim3((unsigned)B), dim3(64 * K), 0, as_stream(s), logprobs, B, K, T, seq_len, t0, pd, per_codebook,
+            per_clip);
+  return 0;
+}
+
+int vaura_select_candidates(const float* scores, const int32_t* codes, int B, int N, int K, int T, int32_t* codes_out, int32_t* winner,
+                            vaura_stream_t s) {
+  if (!scores || !codes || !codes_out || !winner || B <= 0 || N <= 0 || K <= 0 || T <= 0) return VAURA_ERR_ARG;
+  if ((int64_t)K * T > 0x7fffffff) return VAURA_ERR_SHAPE;
+  VA_LAUNCH(select_candidates_kernel, dim3((unsigned)B), dim3(256), 0, as_stream(s), scores, codes, N, K * T, codes_out, winner);
+  return 0;
 }
 
 }  // extern "C"

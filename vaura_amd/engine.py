@@ -357,6 +357,7 @@ class DecoderEngine:
             self.cond_proj = torch.zeros(crp * c.cond_dim, **f32)
             self.codes_i32 = torch.zeros(batch, K, timesteps, dtype=torch.int32, device=self.dev)
             self.clip_params = torch.zeros(batch, 8, dtype=torch.int32, device=self.dev)   # vaura_clip_sampling records (per-clip calls)
+            self.logprobs = torch.zeros(batch, K, S, **f32)     # token log-probabilities in the layout of seq (return_logprobs calls)
         d = L.Decoder()
         d.dims = self.dims
         d.dims.tokens_per_frame = tokens_per_frame
@@ -367,6 +368,7 @@ class DecoderEngine:
         d.kv_dtype = KV_DTYPES.index(self.kv_dtype)
         d.kscale, d.vscale = L.ptr(self.kscale), L.ptr(self.vscale)
         d.clip_sampling = 0                # set per call by _sampling(): NULL = the scalars of the call's vaura_sampling
+        d.logprobs = 0                     # set per call by generate_codes(return_logprobs=True): NULL = the sampler without them
         if delays is not None:             # zero-filled = the default pattern (include/vaura_hip.h)
             d.has_pattern_delays = 1
             for q, dq in enumerate(delays):
@@ -399,26 +401,39 @@ class DecoderEngine:
         c = self.cfg
         return 2 * c.num_layers * self.rows * c.d_model * 4
 
-    def set_condition(self, feats: torch.Tensor):
+    def set_condition(self, feats: torch.Tensor, replicate: int = 1):
         """feats (B, Tv, 768) fp32 on device.  Rows [B, 2B) get the CFG null embedding
-        (models/vaura_model.py:790-793) when the engine was prepared with cfg_on."""
+        (models/vaura_model.py:790-793) when the engine was prepared with cfg_on.
+        ``replicate`` = N > 1 (best-of-N): the engine is prepared for B * N clips, feats holds the B distinct ones.  The MLP runs on
+        those B (+ B null) rows once; the projected rows are then copied N times each on the device (unpack, gather, pack), clip b
+        to rows b * N .. b * N + N - 1 of its half.  A projected row depends on nothing but its own input row, so the copies are the
+        bits that projecting the repeated features would give."""
         assert self.dec is not None
         self._fc = None
         B, Tv, Cin = feats.shape
-        assert B == self.batch and Tv == self.Tv and Cin == self.cfg.cond_in
+        N = int(replicate)
+        assert B * N == self.batch and Tv == self.Tv and Cin == self.cfg.cond_in
+        doubled = self.rows == 2 * self.batch
         x = feats.to(self.dev, torch.float32)
-        if self.rows == 2 * B:
+        if doubled:
             if Tv != self.uncond.shape[0]:
                 raise L.VauraHipError(f"CFG null embedding has {self.uncond.shape[0]} tokens, condition has {Tv}")
             x = torch.cat([x, torch.zeros_like(x) + self.uncond], dim=0)
-        x = x.reshape(self.rows * Tv, Cin).contiguous()
+        n = x.shape[0] * Tv                   # rows the MLP runs on: self.rows * Tv / N
+        x = x.reshape(n, Cin).contiguous()
         st = L.current_stream(self.dev)
-        n = self.rows * Tv
         L.check(self.lib.vaura_pack_rows(L.ptr(x), L.ptr(self.cond_in), n, Cin, st), "vaura_pack_rows")
         L.check(self.lib.vaura_prefill_cond(C.byref(self.dims), L.ptr(self.cond_in), L.ptr(self.fc1), L.ptr(self.fc2),
                                             L.W_F32, L.ptr(self.cond_tmp), L.ptr(self.cond_proj), n, st),
                 "vaura_prefill_cond")
         self._cond_keepalive = x
+        if N > 1:
+            cd = self.cfg.cond_dim
+            once = torch.empty(n, cd, dtype=torch.float32, device=self.dev)
+            L.check(self.lib.vaura_unpack_rows(L.ptr(self.cond_proj), L.ptr(once), n, cd, st), "vaura_unpack_rows")
+            rep = once.view(-1, Tv * cd).repeat_interleave(N, dim=0).reshape(self.rows * Tv, cd).contiguous()
+            L.check(self.lib.vaura_pack_rows(L.ptr(rep), L.ptr(self.cond_proj), self.rows * Tv, cd, st), "vaura_pack_rows")
+            self._cond_keepalive = (x, once, rep)
 
     def cond_projection(self) -> torch.Tensor:
         """(rows, Tv, cond_dim) row-major view of the hoisted video MLP output (tests)."""
@@ -493,7 +508,7 @@ class DecoderEngine:
             st = L.current_stream(self.dev)
             if use_graph:
                 # per-clip calls: the record POINTER and the canonical struct of _sampling() — "per-clip + row doubling", never the values
-                key = (self._shape, L.ptr(noise), bytes(sp), int(self.dec.clip_sampling or 0))
+                key = (self._shape, L.ptr(noise), bytes(sp), int(self.dec.clip_sampling or 0), int(self.dec.logprobs or 0))
                 if self._graph_key != key:       # the captured step is tied to these buffers / parameters
                     self._free_graph()
                     handle = C.c_void_p()
@@ -598,33 +613,69 @@ class DecoderEngine:
     @torch.no_grad()
     def generate_codes(self, feats: torch.Tensor, max_new_tokens: int, *, prompt: Optional[torch.Tensor] = None,
                        use_sampling=False, temp=1.0, top_k=0, top_p=0.0, cfg_scale=1.0, noise=None, seed=0,
-                       clip_base=0, use_graph=True, tokens_per_frame=7, delays=None) -> torch.Tensor:
+                       clip_base=0, use_graph=True, tokens_per_frame=7, delays=None, return_logprobs=False, num_candidates=1):
         """The hot loop of generate(): (B, Tv, 768) -> codes (B, K, T) int64 (device).  ``delays``: the codebook delay pattern
         (codebook_patterns.py:374-419; None = 0..K-1, ParallelPatternProvider = all zeros): S = T + max(d) + 1 sequence steps, the
         loop samples steps Tp + 1 + d_0 .. S - 1, and an explicit ``noise`` has S - (Tp + 1 + d_0) steps.
         ``use_sampling``, ``temp``, ``top_k``, ``top_p``, ``cfg_scale``: a scalar, or one value per clip (list / tuple / 1-D tensor of
-        length B) — clip b is then decoded exactly as the scalar call with its values would decode it (``_sampling``)."""
+        length B) — clip b is then decoded exactly as the scalar call with its values would decode it (``_sampling``).
+        ``num_candidates`` = N > 1: N candidates per clip in one call, exactly the batch ``feats.repeat_interleave(N, 0)`` (candidate j
+        of clip b is row b * N + j; per-clip values and the prompt are repeated per candidate; Philox noise is keyed by clip_base + row;
+        an explicit ``noise`` has B * N * K rows) — but the condition MLP runs on the B distinct clips (``set_condition``).  Returns
+        codes (B * N, K, T).
+        ``return_logprobs``: returns ``(codes, {"logprobs": (B * N, K, T) fp32, "per_codebook": (B * N, K), "score": (B * N,)})`` — the
+        log-probability of every sampled token under the distribution its decision was made from (include/vaura_hip.h
+        ``vaura_decoder.logprobs``; prompt frames hold 0), its mean over the generated frames per codebook, and the mean of those over
+        the codebooks (``vaura_sequence_logprob``: fixed order, a NaN anywhere makes the clip's scores NaN).  The tokens are the ones
+        the call returns without it."""
         B, Tv, _ = feats.shape
+        N = num_candidates
+        if isinstance(N, bool) or not isinstance(N, int) or N < 1:
+            raise L.VauraHipError(f"num_candidates must be an int >= 1, got {N!r}")
         clip_params.check_lengths(B, use_sampling=use_sampling, temp=temp, top_k=top_k, top_p=top_p, cfg_scale=cfg_scale)
         cfg_on = clip_params.any_cfg(cfg_scale)     # some clip mixes: the whole batch carries the null-condition rows
+        if N > 1:
+            use_sampling, temp, top_k, top_p, cfg_scale = (clip_params.repeat(v, N) for v in (use_sampling, temp, top_k, top_p, cfg_scale))
+            if prompt is not None:
+                prompt = prompt.repeat_interleave(N, dim=0)
+        K = self.cfg.num_codebooks
         self._fc = None                       # the K/V cache is about to be reused: forward_cached must start over
         with off_null_stream(self.dev) as caller:
-            self.prepare(B, max_new_tokens, Tv, cfg_on, tokens_per_frame, block_size=self.cfg.block_size, delays=delays)
-            self.set_condition(feats)
+            self.prepare(B * N, max_new_tokens, Tv, cfg_on, tokens_per_frame, block_size=self.cfg.block_size, delays=delays)
+            self.set_condition(feats, replicate=N)
             Tp = self.start_sequence(prompt)
             start = Tp + 1 + (self.delays[0] if self.delays else 0)  # Pattern.get_first_step_with_timesteps(Tp), sorted delays
             sp = self._sampling(use_sampling, temp, top_k, top_p, cfg_scale, seed, clip_base)
             if noise is not None:
                 noise = noise.to(self.dev, torch.float32).contiguous()
-                assert noise.shape == (self.S - start, B * self.cfg.num_codebooks, self.cfg.d_codebook), noise.shape
+                assert noise.shape == (self.S - start, B * N * K, self.cfg.d_codebook), noise.shape
+            if return_logprobs:
+                self.logprobs.zero_()         # slots the sampler does not fill (prompt, special) read 0
+            self.dec.logprobs = L.ptr(self.logprobs) if return_logprobs else 0
             self.run(start - 1, self.S - start, sp, noise, use_graph)
             out = self.revert().to(torch.int64)
+            extra = self._sequence_logprobs(Tp) if return_logprobs else None
         if caller is not None:
             out.record_stream(caller)
-        return out
+            for t in (extra or {}).values():
+                t.record_stream(caller)
+        return (out, extra) if return_logprobs else out
+
+    def _sequence_logprobs(self, Tp: int) -> Dict[str, torch.Tensor]:
+        """The finished call's log-probabilities, reverted to (batch, K, T), and their fixed-order means over frames Tp .. T - 1."""
+        K, T, Bn = self.cfg.num_codebooks, self.T, self.batch
+        f32 = dict(dtype=torch.float32, device=self.dev)
+        lp, pcb, score = torch.empty(Bn, K, T, **f32), torch.empty(Bn, K, **f32), torch.empty(Bn, **f32)
+        dl = L.delays_host(self.delays) if self.delays is not None else None
+        st = L.current_stream(self.dev)
+        L.check(self.lib.vaura_pattern_revert_delays_f32(L.ptr(self.logprobs), L.ptr(lp), Bn, K, T, self.S, 0.0, dl, st),
+                "vaura_pattern_revert_delays_f32")
+        L.check(self.lib.vaura_sequence_logprob(L.ptr(self.logprobs), self.S, dl, Bn, K, T, Tp, L.ptr(pcb), L.ptr(score), st),
+                "vaura_sequence_logprob")
+        return {"logprobs": lp, "per_codebook": pcb, "score": score}
 
     @torch.no_grad()
-    def generate_codes_checked(self, feats: torch.Tensor, max_new_tokens: int, **kw) -> torch.Tensor:
+    def generate_codes_checked(self, feats: torch.Tensor, max_new_tokens: int, **kw):
         """``generate_codes`` + ``check_status`` (ONE host-device synchronisation) with range safety BY CONSTRUCTION: when — and only
         when — the status word reports non-finite logits (an activation left the fp16-plane range somewhere in the loop: every such
         overflow arrives at the sampler as NaN), the whole call is run again on the exact-fp32 twin engine

@@ -236,19 +236,47 @@ class VAURAModel(nn.Module):
         return torch.stack([torch.empty(rows, vocab).exponential_(1) for _ in range(steps)])
 
     # ------------------------------------------------------------------ generate
+    @staticmethod
+    def _check_candidates(num_candidates, return_all_candidates, use_sampling, temp) -> int:
+        """The best-of-N arguments of generate() / generate_tokens(), checked on the host alone."""
+        N = num_candidates
+        if isinstance(N, bool) or not isinstance(N, int):
+            raise L.VauraHipError(f"num_candidates must be an int, got {N!r}")
+        if N < 1:
+            raise L.VauraHipError(f"num_candidates must be at least 1, got {N}")
+        if return_all_candidates and N == 1:
+            raise L.VauraHipError("return_all_candidates needs num_candidates > 1")
+        if N > 1 and not clip_params.any_sampled(use_sampling, temp):
+            raise L.VauraHipError(f"num_candidates = {N} with greedy decoding for every clip: the candidates would be identical "
+                                  "(use_sampling with temp > 0 for at least one clip)")
+        return N
+
     @torch.no_grad()
     def generate_tokens(self, frames=None, audio: Union[torch.Tensor, None] = None, clip_indices=None,
                         max_new_tokens: int = 512, return_attention_weights: bool = False,
                         return_sampled_indices: bool = True, check: bool = False, use_sampling: bool = True,
                         temp: float = 1.0, top_k: int = 256, top_p: float = 0.0, remove_prompts: bool = False,
-                        prompt_is_encoded: bool = False, cfg_scale: float = 1.0) -> torch.Tensor:
+                        prompt_is_encoded: bool = False, cfg_scale: float = 1.0, return_logprobs: bool = False,
+                        num_candidates: int = 1, return_all_candidates: bool = False):
         """generate() up to and including revert_pattern_sequence (vaura_model.py:410-572): (B, K, T') int64 tokens on
         the device, no codec decode.  The sliding-window caller (vaura_amd.longform) uses this for every chunk and
         decodes the concatenated tokens once, as the reference's script does (scripts/generate.py:366-369).
         ``use_sampling``, ``temp``, ``top_k``, ``top_p`` and ``cfg_scale`` each take a scalar or one value per clip (a length-B list /
         tuple / 1-D tensor): clip b is decoded as the scalar call with its values would decode it, in the same batch
-        (``DecoderEngine.generate_codes``)."""
+        (``DecoderEngine.generate_codes``).
+        With ``return_logprobs`` or ``num_candidates`` > 1 the result is a dict instead of the tensor: "tokens" (B, K, T') plus
+          * ``return_logprobs``: "logprobs" (B, K, T') — log-probability of every generated token under the distribution its decision
+            was made from (CFG-mixed logits over the temperature where the clip samples, full vocabulary: before top-k / top-p),
+            0 in prompt frames —, "logprob_per_codebook" (B, K) and "sequence_logprob" (B,): its mean over the generated frames, and
+            the mean of that over the codebooks (prompt frames are not counted).  ``remove_prompts`` slices "logprobs" like the tokens;
+          * ``num_candidates`` = N > 1: N takes per clip in one call — the extractor and the condition MLP run on the B clips — ranked on
+            the device by "sequence_logprob": "tokens" holds each clip's winner, "selected_candidate" (B,) its index,
+            "candidate_scores" (B, N) every take's score, "candidate_indices" (B * N, K, T') every take's tokens (candidate j of clip
+            b is row b * N + j — the rows of a call on ``frames.repeat_interleave(N, 0)``);
+          * ``return_all_candidates``: nothing is selected (for a caller with its own scorer): "tokens" and the log-probabilities are
+            those of all B * N takes, in candidate order."""
         assert not self.training, "do not use generation in training mode"
+        N = self._check_candidates(num_candidates, return_all_candidates, use_sampling, temp)   # refused before any device work
         # per-clip parameter sequences of the wrong length: refused here, before any device work (frames carry the batch on dim 0)
         clip_params.check_lengths(frames.shape[0] if hasattr(frames, "shape") else None, use_sampling=use_sampling, temp=temp,
                                   top_k=top_k, top_p=top_p, cfg_scale=cfg_scale)
@@ -283,45 +311,83 @@ class VAURAModel(nn.Module):
         S = max_new_tokens + max(delays) + 1
         start = Tp + 1 + delays[0]  # Pattern.get_first_step_with_timesteps(Tp) for sorted delays
         greedy = not clip_params.any_sampled(use_sampling, temp)     # per-clip: noise for the batch as soon as one clip draws
-        noise = None if greedy else self._exp_noise(S - start, B * K, self.sampler.d_codebook)
+        noise = None if greedy else self._exp_noise(S - start, B * N * K, self.sampler.d_codebook)
         # decode loop + its status word in one synchronisation (the reference's own post-conditions, :550-572, synchronise too); an
         # activation beyond the fp16-plane range is re-run on the exact-fp32 engine instead of raising (engine.generate_codes_checked)
+        want_lp = bool(return_logprobs) or N > 1            # candidates are ranked by their sequence log-probability
         codes = eng.generate_codes_checked(
             vis.float(), max_new_tokens, prompt=audio if Tp else None, use_sampling=use_sampling, temp=temp,
             top_k=top_k, top_p=top_p, cfg_scale=cfg_scale if use_cfg else 1.0, noise=noise, seed=self.seed,
             clip_base=self.clip_base, tokens_per_frame=self.sampler.audio_tokens_per_video_frame,
-            delays=None if delays == list(range(K)) else delays)
+            delays=None if delays == list(range(K)) else delays, **(dict(return_logprobs=True, num_candidates=N) if want_lp else {}))
+        lp = None
+        if want_lp:
+            codes, lp = codes
         bad = (codes < 0) | (codes > self.sampler.d_codebook)
         assert not bool(bad.any()), "generated sequence is incomplete or out of range"
         if check:
             # vaura_model.py:508-515 checks, every step, that the prefix is coherent with the pattern mask and holds no unknown
             # token; the device loop fills the sequence in place, so the same two properties are checked on the finished one
             # (they are monotone: a violation at any step is still there at the end).  :550-558 are these asserts, always on.
-            seq = eng.seq[:B].to(torch.int64)
+            seq = eng.seq[:B * N].to(torch.int64)
             _, mask = self.pattern_provider.get_pattern(max_new_tokens)._build_indexes(max_new_tokens, seq.device)
             special = torch.full_like(seq, self.special_token_id)
             assert not bool((seq == -1).any()), "unknown tokens left in the generated sequence"
             assert bool((seq == torch.where(mask[None].expand_as(seq), seq, special)).all()), "sequence and pattern mask disagree"
-        return codes[..., (Tp if remove_prompts else 0):max_new_tokens]
+        lo = Tp if remove_prompts else 0
+        if not want_lp:
+            return codes[..., lo:max_new_tokens]
+        out = {}
+        if N > 1:
+            out["candidate_indices"] = codes[..., lo:max_new_tokens]
+            out["candidate_scores"] = lp["score"].view(B, N)
+            if not return_all_candidates:
+                c32 = codes.to(torch.int32).contiguous()
+                won = torch.empty(B, K, max_new_tokens, dtype=torch.int32, device=codes.device)
+                winner = torch.empty(B, dtype=torch.int32, device=codes.device)
+                L.check(eng.lib.vaura_select_candidates(L.ptr(lp["score"]), L.ptr(c32), B, N, K, max_new_tokens, L.ptr(won), L.ptr(winner),
+                                                        L.current_stream(eng.dev)), "vaura_select_candidates")
+                rows = torch.arange(B, device=codes.device) * N + winner.to(torch.int64)
+                codes = won.to(torch.int64)
+                lp = {k: v[rows] for k, v in lp.items()}
+                out["selected_candidate"] = winner.to(torch.int64)
+        out["tokens"] = codes[..., lo:max_new_tokens]
+        if return_logprobs:
+            out["logprobs"] = lp["logprobs"][..., lo:max_new_tokens]
+            out["logprob_per_codebook"] = lp["per_codebook"]
+            out["sequence_logprob"] = lp["score"]
+        return out
 
     @torch.no_grad()
     def generate(self, frames=None, audio: Union[torch.Tensor, None] = None, clip_indices=None, max_new_tokens: int = 512,
                  return_attention_weights: bool = False, return_sampled_indices: bool = False, check: bool = False,
                  use_sampling: bool = True, temp: float = 1.0, top_k: int = 256, top_p: float = 0.0,
-                 remove_prompts: bool = False, prompt_is_encoded: bool = False, cfg_scale: float = 1.0) -> dict:
+                 remove_prompts: bool = False, prompt_is_encoded: bool = False, cfg_scale: float = 1.0,
+                 return_logprobs: bool = False, num_candidates: int = 1, return_all_candidates: bool = False) -> dict:
+        """``return_logprobs`` / ``num_candidates`` / ``return_all_candidates``: see ``generate_tokens`` — its extra entries are added
+        to the result ("sampled_indices" takes "tokens"); the codec decodes the winners (B clips), or with ``return_all_candidates``
+        all B * N takes.  With the defaults the result is the dict it always was."""
         K = self.num_codebooks
+        self._check_candidates(num_candidates, return_all_candidates, use_sampling, temp)    # before the engine is touched
+        extra = {}
         with off_null_stream(self.sampler.engine().dev) as caller:   # decode loop + codec leave HIP's null stream together
             out_codes = self.generate_tokens(
                 frames=frames, audio=audio, clip_indices=clip_indices, max_new_tokens=max_new_tokens,
                 return_attention_weights=return_attention_weights, check=check, use_sampling=use_sampling, temp=temp,
                 top_k=top_k, top_p=top_p, remove_prompts=remove_prompts, prompt_is_encoded=prompt_is_encoded,
-                cfg_scale=cfg_scale)
+                cfg_scale=cfg_scale, return_logprobs=return_logprobs, num_candidates=num_candidates,
+                return_all_candidates=return_all_candidates)
+            if isinstance(out_codes, dict):
+                extra = out_codes
+                out_codes = extra.pop("tokens")
             generated_audio = self.audio_encoder.decode([(out_codes[..., :K, :], None)])
         if caller is not None:
             out_codes.record_stream(caller)
             generated_audio.record_stream(caller)
+            for t in extra.values():
+                t.record_stream(caller)
         return {"generated_audio": generated_audio, "s_attn_weights": None, "mha_attn_weights": None,
-                "sampled_indices": out_codes if return_sampled_indices else None}
+                "sampled_indices": out_codes if return_sampled_indices else None, **extra}
 
     # ------------------------------------------------------------------ one step, reference signature
     @torch.no_grad()
