@@ -487,3 +487,75 @@ def test_step_and_prefill_leave_the_same_cache(name, kv):
         e_ref = max(e_ref, A.rel_err(ref["out32"], ref["out64"]))
     d = A.rel_err(out_s, out_p)
     assert d <= (3e-6 if name == "flat" else A.bar(e_ref)), f"last position: step and prefill outputs differ by {d:.3e}"
+
+
+# ------------------------------------------------------------------- the two op-level step entry points are one launcher
+def _c_step_ex(qp, rope, kc, vc, out, out_split, rows, n_head, head_dim, pos, kv):
+    """vaura_attention_step_ex itself (ops.attention_step_ex goes through attention_step_kv); returns the C return code."""
+    return L.lib().vaura_attention_step_ex(L.ptr(qp), 0, L.ptr(rope), L.ptr(kc), L.ptr(vc), L.ptr(out), L.ptr(out_split), 0, 0,
+                                           rows, n_head, head_dim, kc.shape[-2], pos, 1, 0, kv, L.current_stream())
+
+
+@pytest.mark.parametrize("kv", [0, 1, 2])
+def test_step_ex_and_step_kv_are_bit_identical(kv):
+    """ops.attention_step_ex, ops.attention_step_kv and the C entry point vaura_attention_step_ex: the same bits in out, out_split and
+    both caches, on an empty cache and on both sides of a 64-position pass boundary."""
+    rows, nh, T = 2, 2, 128
+    g = torch.Generator().manual_seed(77 + kv)
+    rope = rope_table(T, HD).to(DEV)
+    K0, V0 = (A.narrow(torch.randn(rows, nh, T, HD, generator=g), kv).to(DEV) for _ in range(2))
+    for pos in (0, 63, 64):
+        qp = ops.pack_rows(torch.randn(rows, 3 * nh * HD, generator=g).to(DEV))
+        got = []
+        for fn in (ops.attention_step_ex, ops.attention_step_kv, None):
+            kc, vc = K0.clone(), V0.clone()
+            if fn is not None:
+                o, osp = fn(qp, rope, kc, vc, rows, nh, HD, pos, kv_dtype=kv, want_split=True)
+            else:
+                o, osp = torch.zeros(16 * nh * HD, device=DEV), torch.zeros(16 * 2 * nh * HD, dtype=torch.int16, device=DEV)
+                assert _c_step_ex(qp, rope, kc, vc, o, osp, rows, nh, HD, pos, kv) == 0
+            got.append((o, osp, bits(kc), bits(vc)))
+        assert bool(torch.isfinite(got[0][0]).all()) and bool(got[0][0].ne(0).any())
+        for other in got[1:]:
+            for a, b, what in zip(got[0], other, ("out", "out_split", "k cache", "v cache")):
+                assert torch.equal(a, b), f"storage {A.STORAGE[kv]} pos {pos}: {what} differs between the entry points"
+
+
+def test_op_level_refusals():
+    """What the cache check refuses, through the op-level entry points: the documented code, and nothing launched (out stays NaN, the
+    caches stay zero)."""
+    rows, T = 2, 128
+    rope = rope_table(512, HD).to(DEV)
+    qp = ops.pack_rows(torch.randn(rows, 3 * D, device=DEV))
+    qkv = ops.pack_rows(torch.randn(4 * 16, 3 * D, device=DEV))
+    out = torch.full((16 * D,), float("nan"), device=DEV)
+    attn = torch.full((4 * 16 * D,), float("nan"), device=DEV)
+    cache = lambda dt, max_len=T, hd=HD: torch.zeros(rows, H, max_len, hd, device=DEV).to(dt)
+    u8, before = cache(torch.uint8), qkv.clone()
+    f32_64, f16_288 = cache(torch.float32, hd=64), cache(torch.float16, 288)
+    ks = torch.zeros(rows, H, T, dtype=torch.uint8, device=DEV)
+    step, prefill = ops.attention_step_kv, lambda kc, hd, **kw: ops.attention_prefill(qkv, rope, kc, kc.clone(), attn, None, rows, H, hd, 0, 4, **kw)
+    table = [
+        ("VAURA_ERR_SHAPE", lambda: step(qp, rope, f32_64, f32_64.clone(), rows, H, 64, 5, out=out)),
+        ("VAURA_ERR_SHAPE", lambda: ops.attention_step_ex(qp, rope, f32_64, f32_64.clone(), rows, H, 64, 5, out=out)),
+        ("VAURA_ERR_SHAPE", lambda: prefill(f32_64, 64)),
+        ("VAURA_ERR_SHAPE", lambda: step(qp, rope, f16_288, f16_288.clone(), rows, H, HD, 5, kv_dtype=1, out=out)),
+        ("VAURA_ERR_SHAPE", lambda: prefill(f16_288, HD, kv_dtype=1)),
+        ("VAURA_ERR_ARG", lambda: step(qp, rope, u8, u8.clone(), rows, H, HD, 5, kv_dtype=3, out=out)),
+        ("VAURA_ERR_ARG", lambda: step(qp, rope, u8, u8.clone(), rows, H, HD, 5, kv_dtype=3, kscale=ks, out=out)),
+        ("VAURA_ERR_ARG", lambda: prefill(u8, HD, kv_dtype=3)),
+        ("VAURA_ERR_ARG", lambda: ops.attention_step_ex(qp, rope, u8, u8.clone(), rows, H, HD, 5, kv_dtype=3, out=out)),
+        ("VAURA_ERR_ARG", lambda: step(qp, rope, u8, u8.clone(), rows, H, HD, 5, kv_dtype=4, kscale=ks, vscale=ks.clone(), out=out)),
+        ("VAURA_ERR_ARG", lambda: prefill(u8, HD, kv_dtype=4, kscale=ks, vscale=ks.clone())),
+        # missing exponent bytes AND a wrong head_dim: the step's launcher reports the bytes, the prefill's entry point checks them first too
+        ("VAURA_ERR_ARG", lambda: step(qp, rope, u8, u8.clone(), rows, H, 64, 5, kv_dtype=3, out=out)),
+        ("VAURA_ERR_ARG", lambda: prefill(u8, 64, kv_dtype=3)),
+    ]
+    for i, (code, call) in enumerate(table):
+        with pytest.raises(L.VauraHipError, match=code):
+            call()
+        print(f"refusal {i}: {code}")
+    assert _c_step_ex(qp, rope, u8, u8.clone(), out, None, rows, H, HD, 5, 3) == -1      # VAURA_ERR_ARG from the C entry point itself
+    torch.cuda.synchronize()
+    assert bool(torch.isnan(out).all()) and bool(torch.isnan(attn).all())
+    assert not any(bool(t.ne(0).any()) for t in (u8, f32_64, f16_288, ks)) and torch.equal(qkv, before)

@@ -1,0 +1,43 @@
+"""Compare the device code of one translation unit before and after a host-only change.
+
+    hipcc <build.py FLAGS> [-D...] --cuda-device-only -S vaura_amd/csrc/UNIT.hip -o UNIT.s     (once per tree)
+    python tools/compare_device_asm.py OLD.s NEW.s
+
+identical: equal bytes once the compile-unit id (__hip_cuid_<hash of the source path and options>) is masked.
+same-set : not identical, but equal after splitting at the function symbols and at the kernels' metadata records, masking the index of
+           the function in its local labels (.LBB<i>_<j>, .Lfunc_end<i>) and sorting: host code instantiated the templates in another
+           order; the set of symbols and every instruction stream are equal.  Anything else exits 1."""
+import hashlib
+import re
+import sys
+
+
+def load(p):
+    return re.sub(r"__hip_cuid_[0-9a-f]+", "__hip_cuid", open(p).read())
+
+
+def pieces(t):
+    head, meta = t.split("\t.amdgpu_metadata\n")
+    head, trailer = head.split("\t.section\t.AMDGPU.gpr_maximums")      # what follows the last function
+    funcs = re.split(r"(?m)^(?=(?:\t\.section\t\.text\.\S+\n|\t\.text\n)?\t\.(?:protected|globl|weak)\t\S+ *; -- Begin function)", head)
+    funcs = [re.sub(r"BB\d+_", "BB_", re.sub(r"(Lfunc_end|Lfunc_begin|LJTI|Ltmp|LCPI)\d+", r"\1", f)) for f in funcs]
+    meta, tail = meta.split("amdhsa.target:")
+    recs = re.split(r"(?m)^(?=  - \.(?:agpr_count|args):)", meta)
+    return sorted(funcs) + [trailer, "<metadata>"] + sorted(recs) + [tail]
+
+
+def sha(s):
+    return hashlib.sha256(s.encode()).hexdigest()
+
+
+if __name__ == "__main__":
+    a, b = load(sys.argv[1]), load(sys.argv[2])
+    if a == b:
+        print("identical", sha(a))
+        sys.exit(0)
+    pa, pb = pieces(a), pieces(b)
+    if pa == pb:
+        print("same-set ", sha("".join(pa)), f"({len(pa)} pieces; order differs)")
+        sys.exit(0)
+    print("DIFFERENT", sha(a), sha(b), f"{len(set(pa) ^ set(pb))} pieces differ")
+    sys.exit(1)

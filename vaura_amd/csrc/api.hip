@@ -137,17 +137,37 @@ static int check_clips(const vaura_decoder* d, const vaura_sampling* sp, hipStre
   return va_check_clip_sampling(sp, d->clip_sampling, d->batch, d->rows == 2 * d->batch, s);
 }
 
+// what both step paths pass to the attention of layer l (the pair path adds qkv2, the planes for wo and the arrival words) ...
+static VaAttentionStep attention_step(const vaura_decoder* d, int l) {
+  VaAttentionStep a;
+  a.qkv = d->ws_qkv; a.rope = d->rope; a.kv = va_kv_cache(d, l); a.out = d->ws_attn;
+  a.rows = d->rows; a.n_head = d->dims.n_head; a.head_dim = d->dims.d_model / d->dims.n_head;
+  a.pos_dev = d->state;
+  a.part = d->ws_attn_part;
+  a.n_split = d->ws_attn_part ? va_attention_splits(d->rows, d->dims.n_head, d->max_len) : 1;
+  return a;
+}
+// ... and to the sampler that ends a step
+static VaSampleLaunch sample_launch(const vaura_decoder* d, const vaura_sampling* sp) {
+  VaSampleLaunch a;
+  a.logits = d->ws_logits; a.B = d->batch; a.K = d->dims.n_codebooks; a.vocab = d->dims.vocab;
+  a.sp = sp; a.clips = d->clip_sampling; a.noise = d->noise; a.state = d->state;
+  a.seq = d->seq; a.T = d->timesteps; a.S = d->seq_len;
+  a.delays_host = va_pattern_delays(d);
+  a.lp_seq = d->logprobs;
+  return a;
+}
+
 // pair path (H1 / H2 / FP8 storage): activations travel as (hi, lo) fp16 planes, products on the fp16 MFMA
 static int enqueue_step_bf16(const vaura_decoder* d, const vaura_sampling* sp, int sample, hipStream_t s) {
   const vaura_dims& m = d->dims;
-  const int D = m.d_model, F = m.ffn_dim, H = m.n_head, hd = D / H;
+  const int D = m.d_model, F = m.ffn_dim, H = m.n_head;
   const int rows = d->rows;
   if (!d->ws_h_split || !d->ws_attn_split || !d->ws_ffn_split || !d->ws_ss) return VAURA_ERR_ARG;
   PROF_B(VAURA_K_EMBED);
   int rc = va_launch_embed(d, -1, 1, s);   // h, split(h * attn_norm[0]), ss partials
   PROF_A(VAURA_K_EMBED);
   if (rc) return rc;
-  const size_t kv_layer = (size_t)rows * H * (size_t)d->max_len * hd;
   // K-split qkv (consumer-reduced): fewer than 16 row blocks (otherwise the GEMM tiling takes over)
   float* qkv2 = (d->ws_qkv2 && (rows + 15) / 16 < 16) ? d->ws_qkv2 : nullptr;
   // the MLP half of every layer as ONE launch (mlp_engine.h) where the shape is eligible and the caller provided the hand-off
@@ -162,7 +182,7 @@ static int enqueue_step_bf16(const vaura_decoder* d, const vaura_sampling* sp, i
 #ifdef VAURA_EXPERIMENT_ENGINES
   const bool attn_wo = mlp_engine && rows <= 16 && H == 16 && d->max_len <= 256 && (va_debug_flags_get() & 0x1000u) && !(va_debug_flags_get() & 8u) &&
                        d->plane_shift == 0;   // the experiments' own attention epilogues store unscaled planes
-  const bool fuse_attn = fuse_qkv && rows <= 16 && H == 16 && hd == 96 && d->max_len <= 256 && d->ws_attn_split && !attn_wo && d->plane_shift == 0 &&
+  const bool fuse_attn = fuse_qkv && rows <= 16 && H == 16 && D / H == 96 && d->max_len <= 256 && d->ws_attn_split && !attn_wo && d->plane_shift == 0 &&
                          !(va_debug_flags_get() & 8u) && (va_debug_flags2_get() & 4u);
   const bool tail_engine = mlp_engine && rows <= 16 && (va_debug_flags_get() & 8u);
 #else
@@ -189,18 +209,20 @@ static int enqueue_step_bf16(const vaura_decoder* d, const vaura_sampling* sp, i
 #ifdef VAURA_EXPERIMENT_ENGINES
     } else if (attn_wo) {
       PROF_B(VAURA_K_ATTN);
-      rc = va_launch_attn_wo(d->ws_qkv, qkv2, d->rope, d->kcache + l * kv_layer, d->vcache + l * kv_layer, d->ws_attn, d->ws_attn_split,
-                             rows, H, d->max_len, d->state, awo0, d->ws_sync + 512, l, s);
+      rc = va_launch_attn_wo(d->ws_qkv, qkv2, d->rope, va_kv_cache(d, l), d->ws_attn, d->ws_attn_split, rows, H, d->state, awo0,
+                             d->ws_sync + 512, l, s);
       PROF_A(VAURA_K_ATTN);
       if (rc) return rc;
 #endif
     } else {
     PROF_B(VAURA_K_ATTN);  // rope + cache append + softmax(qK^T)V                     llama.py:234-257
-    rc = va_launch_attention(d->ws_qkv, qkv2, d->rope, va_kv_layer(d, d->kcache, l), va_kv_layer(d, d->vcache, l), d->ws_attn,
-                             d->ws_attn_split, rows, H, hd, d->max_len, d->state, 0, d->ws_attn_part,
-                             d->ws_attn_part ? va_attention_splits(rows, H, d->max_len) : 1, s,
-                             d->ws_sync ? d->ws_sync + 512 : nullptr, ldexpf(1.f, -d->plane_shift), d->kv_dtype,
-                             va_kv_scale_layer(d, d->kscale, l), va_kv_scale_layer(d, d->vscale, l));      // words 512 .. 767: arrival counts of the range-split attention (the MLP / tail engines use 0 .. 511; the attention + wo experiment uses 512 .. only with caches <= 256, where nothing is split)
+    VaAttentionStep at = attention_step(d, l);
+    at.qkv2 = qkv2; at.out_split = d->ws_attn_split;
+    // words 512 .. 767: arrival counts of the range-split attention (the MLP / tail engines use 0 .. 511; the attention + wo experiment
+    // uses 512 .. only with caches <= 256, where nothing is split)
+    at.arrivals = d->ws_sync ? d->ws_sync + 512 : nullptr;
+    at.pscale = ldexpf(1.f, -d->plane_shift);
+    rc = va_launch_attention(at, s);
     PROF_A(VAURA_K_ATTN);
     if (rc) return rc;
     }
@@ -236,8 +258,7 @@ static int enqueue_step_bf16(const vaura_decoder* d, const vaura_sampling* sp, i
       VaEngineAttention att;
       const bool with_attn = with_qkv && fuse_attn;
       if (with_attn)
-        att = VaEngineAttention{d->rope, d->kcache + (size_t)(l + 1) * kv_layer, d->vcache + (size_t)(l + 1) * kv_layer, d->ws_attn,
-                                d->ws_attn_split, H, d->max_len};
+        att = VaEngineAttention{d->rope, va_kv_cache(d, l + 1), d->ws_attn, d->ws_attn_split, H};
       PROF_B(VAURA_K_W13);
       // what the idle workgroups of this launch may warm in the Infinity Cache: the NEXT layer's w1||w3 (its first consumer)
       const void* warm = l + 1 < m.n_layer ? d->layers_host[l + 1].w13 : nullptr;
@@ -266,8 +287,7 @@ static int enqueue_step_bf16(const vaura_decoder* d, const vaura_sampling* sp, i
   PROF_A(VAURA_K_HEADS);
   if (rc) return rc;
   PROF_B(VAURA_K_SAMPLE);
-  rc = va_launch_sample(d->ws_logits, d->batch, m.n_codebooks, m.vocab, sp, d->clip_sampling, d->noise, d->batch * m.n_codebooks, d->state, 0,
-                        nullptr, d->seq, d->timesteps, d->seq_len, d->state, va_pattern_delays(d), s, nullptr, d->logprobs);
+  rc = va_launch_sample(sample_launch(d, sp), s);
   PROF_A(VAURA_K_SAMPLE);
   return rc;
 }
@@ -277,13 +297,12 @@ static int enqueue_step(const vaura_decoder* d, const vaura_sampling* sp, int sa
   if (d->wdtype == VAURA_W_H1 || d->wdtype == VAURA_W_H2 || va_is_fp8(d->wdtype)) return enqueue_step_bf16(d, sp, sample, s);
   if (d->wdtype != VAURA_W_F32 && d->wdtype != VAURA_W_BF16) return VAURA_ERR_DTYPE;
   const vaura_dims& m = d->dims;
-  const int D = m.d_model, F = m.ffn_dim, H = m.n_head, hd = D / H;
+  const int D = m.d_model, F = m.ffn_dim;
   const int rows = d->rows;
   PROF_B(VAURA_K_EMBED);
   int rc = va_launch_embed(d, -1, 1, s);
   PROF_A(VAURA_K_EMBED);
   if (rc) return rc;
-  const size_t kv_layer = (size_t)rows * H * (size_t)d->max_len * hd;
   for (int l = 0; l < m.n_layer; ++l) {
     const vaura_layer_weights& L = d->layers_host[l];
     // h -> qkv  (attention_norm fused)                                   llama.py:280, 228
@@ -293,9 +312,7 @@ static int enqueue_step(const vaura_decoder* d, const vaura_sampling* sp, int sa
     if (rc) return rc;
     // rope + cache append + softmax(qK^T)V                               llama.py:234-257
     PROF_B(VAURA_K_ATTN);
-    rc = va_launch_attention(d->ws_qkv, nullptr, d->rope, d->kcache + l * kv_layer, d->vcache + l * kv_layer, d->ws_attn, nullptr, rows,
-                             H, hd, d->max_len, d->state, 0, d->ws_attn_part,
-                             d->ws_attn_part ? va_attention_splits(rows, H, d->max_len) : 1, s);
+    rc = va_launch_attention(attention_step(d, l), s);
     PROF_A(VAURA_K_ATTN);
     if (rc) return rc;
     // h += wo . attn                                                      llama.py:259, 279
@@ -322,8 +339,7 @@ static int enqueue_step(const vaura_decoder* d, const vaura_sampling* sp, int sa
   PROF_A(VAURA_K_HEADS);
   if (rc) return rc;
   PROF_B(VAURA_K_SAMPLE);
-  rc = va_launch_sample(d->ws_logits, d->batch, m.n_codebooks, m.vocab, sp, d->clip_sampling, d->noise, d->batch * m.n_codebooks, d->state, 0,
-                          nullptr, d->seq, d->timesteps, d->seq_len, d->state, va_pattern_delays(d), s, nullptr, d->logprobs);
+  rc = va_launch_sample(sample_launch(d, sp), s);
   PROF_A(VAURA_K_SAMPLE);
   return rc;
 }

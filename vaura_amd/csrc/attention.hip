@@ -1007,42 +1007,31 @@ int va_attention_splits(int rows, int n_head, int max_len) {
   return pairs >= 256 ? 1 : max(1, min(8, 256 / pairs));
 }
 
-int va_launch_attention(const float* qkv, const float* qkv2, const float* rope, float* kc, float* vc, float* out,
-                        uint16_t* outp, int rows, int n_head, int head_dim, int max_len, const int32_t* pos_dev, int pos_host,
-                        float* part, int n_split, hipStream_t s, uint32_t* arrivals, float pscale, int kv_half, uint8_t* kscale,
-                        uint8_t* vscale) {
-  if (!qkv || !rope || !kc || !vc || !out || rows <= 0 || n_head <= 0) return VAURA_ERR_ARG;
-  if (kv_half == 3 && (!kscale || !vscale)) return VAURA_ERR_ARG;      // scaled e4m3: one exponent byte per cached vector
-  if (head_dim != 96) return VAURA_ERR_SHAPE;
-  // fp16 / fp8 / scaled fp8 K / V cache: the single-round-trip kernel only (every 2.56 s configuration); long caches / range splits keep fp32
-  if (kv_half && (max_len > 256 || (part && n_split > 1))) return VAURA_ERR_SHAPE;
-  if (part && n_split > 1) {   // few (row, head) pairs over a long cache: split the range, then combine
-    if (n_split > 8) return VAURA_ERR_ARG;
+int va_launch_attention(const VaAttentionStep& a, hipStream_t s) {
+  const VaKvCache& kv = a.kv;
+  const bool split = a.part && a.n_split > 1;
+  if (!a.qkv || !a.rope || !kv.k || !kv.v || !a.out || a.rows <= 0 || a.n_head <= 0) return VAURA_ERR_ARG;
+  if (int rc = va_kv_check(kv, a.head_dim, split, true)) return rc;
+  if (split) {   // few (row, head) pairs over a long cache: split the range, then combine
+    if (a.n_split > 8) return VAURA_ERR_ARG;
     // arrivals (rows * n_head zeroed words, e.g. the decoder's ws_sync + 512): the last split to arrive merges; debug flag bit 19: own launch
-    if (va_debug_flags_get() & 0x80000u) arrivals = nullptr;
-    VA_LAUNCH(attention_split_kernel<96>, dim3(n_head, rows, n_split), dim3(ATT1_THREADS), 0, s, pos_dev, kc, vc, qkv, qkv2,
-              rope, n_head, max_len, pos_host, part, arrivals, out, outp, pscale);
-    if (!arrivals) VA_LAUNCH(attention_combine_kernel<96>, dim3(n_head, rows), dim3(64), 0, s, (const float*)part, out, outp, n_head, n_split, pscale);
+    uint32_t* arrivals = (va_debug_flags_get() & 0x80000u) ? nullptr : a.arrivals;
+    VA_LAUNCH(attention_split_kernel<96>, dim3(a.n_head, a.rows, a.n_split), dim3(ATT1_THREADS), 0, s, a.pos_dev, kv.k, kv.v, a.qkv, a.qkv2,
+              a.rope, a.n_head, kv.max_len, a.pos_host, a.part, arrivals, a.out, a.out_split, a.pscale);
+    if (!arrivals)
+      VA_LAUNCH(attention_combine_kernel<96>, dim3(a.n_head, a.rows), dim3(64), 0, s, (const float*)a.part, a.out, a.out_split, a.n_head,
+                a.n_split, a.pscale);
     return 0;
   }
-  if (max_len <= 256) {   // static per descriptor (the step graph is captured once): single-round-trip kernel
-    if (kv_half == 1)
-      VA_LAUNCH((attention_step256_kernel<96, 1>), dim3(n_head, rows), dim3(ATT1_THREADS), 0, s, pos_dev, kc, vc, qkv, qkv2, rope,
-                n_head, max_len, pos_host, out, outp, pscale, (uint8_t*)nullptr, (uint8_t*)nullptr);
-    else if (kv_half == 2)
-      VA_LAUNCH((attention_step256_kernel<96, 2>), dim3(n_head, rows), dim3(ATT1_THREADS), 0, s, pos_dev, kc, vc, qkv, qkv2, rope,
-                n_head, max_len, pos_host, out, outp, pscale, (uint8_t*)nullptr, (uint8_t*)nullptr);
-    else if (kv_half == 3)
-      VA_LAUNCH((attention_step256_kernel<96, 3>), dim3(n_head, rows), dim3(ATT1_THREADS), 0, s, pos_dev, kc, vc, qkv, qkv2, rope,
-                n_head, max_len, pos_host, out, outp, pscale, kscale, vscale);
-    else
-      VA_LAUNCH(attention_step256_kernel<96>, dim3(n_head, rows), dim3(ATT1_THREADS), 0, s, pos_dev, kc, vc, qkv, qkv2, rope,
-                n_head, max_len, pos_host, out, outp, pscale, (uint8_t*)nullptr, (uint8_t*)nullptr);
-    return 0;
-  }
-  const size_t smem = sizeof(float) * (size_t)(3 * 96 + 4 * 96 + 8 + max_len + 4);
-  VA_LAUNCH(attention_step_kernel<96>, dim3(n_head, rows), dim3(ATT_THREADS), smem, s, qkv, qkv2, rope, kc, vc, out, outp,
-            n_head, max_len, pos_dev, pos_host, 0, pscale);
+  if (kv.max_len <= 256)   // static per descriptor (the step graph is captured once): single-round-trip kernel
+    return va_kv_dispatch(kv.dtype, [&](auto kvt) -> int {
+      VA_LAUNCH((attention_step256_kernel<96, decltype(kvt)::value>), dim3(a.n_head, a.rows), dim3(ATT1_THREADS), 0, s, a.pos_dev, kv.k, kv.v, a.qkv, a.qkv2,
+                a.rope, a.n_head, kv.max_len, a.pos_host, a.out, a.out_split, a.pscale, kv.kscale, kv.vscale);
+      return 0;
+    });
+  const size_t smem = sizeof(float) * (size_t)(3 * 96 + 4 * 96 + 8 + kv.max_len + 4);
+  VA_LAUNCH(attention_step_kernel<96>, dim3(a.n_head, a.rows), dim3(ATT_THREADS), smem, s, a.qkv, a.qkv2, a.rope, kv.k, kv.v, a.out,
+            a.out_split, a.n_head, kv.max_len, a.pos_dev, a.pos_host, 0, a.pscale);
   return 0;
 }
 
@@ -1052,71 +1041,71 @@ int va_launch_attention(const float* qkv, const float* qkv2, const float* rope, 
 #endif
 
 int va_launch_rope_append(const vaura_decoder* d, int layer, int p0, int n_pos, hipStream_t s) {
-  const int H = d->dims.n_head, hd = d->dims.d_model / H;
-  if (hd != 96) return VAURA_ERR_SHAPE;
-  if (d->kv_dtype != 0 && d->max_len > 256) return VAURA_ERR_SHAPE;   // as va_launch_attention: the step that follows would refuse this cache
-  const size_t kv_layer = (size_t)d->rows * H * (size_t)d->max_len * hd;
-  if (d->kv_dtype == 3 && (!d->kscale || !d->vscale)) return VAURA_ERR_ARG;
-  if (d->kv_dtype >= 1 && d->kv_dtype <= 3) {      // fp16 / fp8 / scaled fp8 cache: the layer offset in elements of that type
-    if (d->kv_dtype == 1)
-      VA_LAUNCH((rope_append_kernel<96, 1>), dim3(H, d->rows, n_pos), dim3(128), 0, s, d->ws_qkv, d->rope, va_kv_layer(d, d->kcache, layer),
-                va_kv_layer(d, d->vcache, layer), H, d->max_len, p0, (d->rows + 15) / 16 * 16, (uint8_t*)nullptr, (uint8_t*)nullptr);
-    else if (d->kv_dtype == 2)
-      VA_LAUNCH((rope_append_kernel<96, 2>), dim3(H, d->rows, n_pos), dim3(128), 0, s, d->ws_qkv, d->rope, va_kv_layer(d, d->kcache, layer),
-                va_kv_layer(d, d->vcache, layer), H, d->max_len, p0, (d->rows + 15) / 16 * 16, (uint8_t*)nullptr, (uint8_t*)nullptr);
-    else
-      VA_LAUNCH((rope_append_kernel<96, 3>), dim3(H, d->rows, n_pos), dim3(128), 0, s, d->ws_qkv, d->rope, va_kv_layer(d, d->kcache, layer),
-                va_kv_layer(d, d->vcache, layer), H, d->max_len, p0, (d->rows + 15) / 16 * 16, va_kv_scale_layer(d, d->kscale, layer),
-                va_kv_scale_layer(d, d->vscale, layer));
+  const int H = d->dims.n_head;
+  const VaKvCache kv = va_kv_cache(d, layer);
+  if (int rc = va_kv_check(kv, d->dims.d_model / H, false, false)) return rc;   // a cache the step that follows would refuse
+  return va_kv_dispatch(kv.dtype, [&](auto kvt) -> int {
+    VA_LAUNCH((rope_append_kernel<96, decltype(kvt)::value>), dim3(H, d->rows, n_pos), dim3(128), 0, s, d->ws_qkv, d->rope, kv.k, kv.v, H, kv.max_len, p0,
+              (d->rows + 15) / 16 * 16, kv.kscale, kv.vscale);
     return 0;
-  }
-  VA_LAUNCH(rope_append_kernel<96>, dim3(H, d->rows, n_pos), dim3(128), 0, s, d->ws_qkv, d->rope, d->kcache + layer * kv_layer,
-            d->vcache + layer * kv_layer, H, d->max_len, p0, (d->rows + 15) / 16 * 16, (uint8_t*)nullptr, (uint8_t*)nullptr);
-  return 0;
+  });
 }
 
 extern unsigned va_debug_flags;   // gemv3.hip; bit 4: the per-position prefill attention (A/B of the MFMA kernel)
 int va_launch_attention_prefill(const vaura_decoder* d, int layer, int p0, int n_pos, hipStream_t s) {
-  const int H = d->dims.n_head, hd = d->dims.d_model / H;
-  if (hd != 96) return VAURA_ERR_SHAPE;
-  if (d->kv_dtype != 0 && d->max_len > 256) return VAURA_ERR_SHAPE;   // as va_launch_attention (see va_launch_rope_append)
-  const size_t kv_layer = (size_t)d->rows * H * (size_t)d->max_len * hd;
-  if (d->kv_dtype == 3 && (!d->kscale || !d->vscale)) return VAURA_ERR_ARG;
-  if (d->kv_dtype >= 1 && d->kv_dtype <= 3) {
-    const dim3 grid(H, d->rows, (n_pos + APF_Q - 1) / APF_Q);
-    if (d->kv_dtype == 1)
-      VA_LAUNCH((attention_prefill_kernel<96, 1>), grid, dim3(256), 0, s, (const float*)d->ws_qkv, (const float*)va_kv_layer(d, d->kcache, layer),
-                (const float*)va_kv_layer(d, d->vcache, layer), d->ws_attn, d->ws_attn_split, H, d->max_len, p0, n_pos, (d->rows + 15) / 16 * 16,
-                ldexpf(1.f, -d->plane_shift), (const uint8_t*)nullptr, (const uint8_t*)nullptr);
-    else if (d->kv_dtype == 2)
-      VA_LAUNCH((attention_prefill_kernel<96, 2>), grid, dim3(256), 0, s, (const float*)d->ws_qkv, (const float*)va_kv_layer(d, d->kcache, layer),
-                (const float*)va_kv_layer(d, d->vcache, layer), d->ws_attn, d->ws_attn_split, H, d->max_len, p0, n_pos, (d->rows + 15) / 16 * 16,
-                ldexpf(1.f, -d->plane_shift), (const uint8_t*)nullptr, (const uint8_t*)nullptr);
-    else
-      VA_LAUNCH((attention_prefill_kernel<96, 3>), grid, dim3(256), 0, s, (const float*)d->ws_qkv, (const float*)va_kv_layer(d, d->kcache, layer),
-                (const float*)va_kv_layer(d, d->vcache, layer), d->ws_attn, d->ws_attn_split, H, d->max_len, p0, n_pos, (d->rows + 15) / 16 * 16,
-                ldexpf(1.f, -d->plane_shift), (const uint8_t*)va_kv_scale_layer(d, d->kscale, layer),
-                (const uint8_t*)va_kv_scale_layer(d, d->vscale, layer));
+  const int H = d->dims.n_head, rows16 = (d->rows + 15) / 16 * 16;
+  const float pscale = ldexpf(1.f, -d->plane_shift);
+  const VaKvCache kv = va_kv_cache(d, layer);
+  if (int rc = va_kv_check(kv, d->dims.d_model / H, false, false)) return rc;
+  if (kv.dtype == 0 && (va_debug_flags & 16u)) {      // fp32 only: one workgroup per (row, head, position)
+    const size_t smem = sizeof(float) * (size_t)(3 * 96 + 4 * 96 + 8 + kv.max_len + 4);
+    VA_LAUNCH(attention_step_kernel<96>, dim3(H, d->rows, n_pos), dim3(ATT_THREADS), smem, s, d->ws_qkv, (const float*)nullptr, d->rope, kv.k,
+              kv.v, d->ws_attn, d->ws_attn_split, H, kv.max_len, nullptr, p0, rows16, pscale);
     return 0;
   }
-  if (!(va_debug_flags & 16u)) {
-    VA_LAUNCH(attention_prefill_kernel<96>, dim3(H, d->rows, (n_pos + APF_Q - 1) / APF_Q), dim3(256), 0, s, (const float*)d->ws_qkv,
-              (const float*)(d->kcache + layer * kv_layer), (const float*)(d->vcache + layer * kv_layer), d->ws_attn, d->ws_attn_split, H,
-              d->max_len, p0, n_pos, (d->rows + 15) / 16 * 16, ldexpf(1.f, -d->plane_shift), (const uint8_t*)nullptr, (const uint8_t*)nullptr);
+  return va_kv_dispatch(kv.dtype, [&](auto kvt) -> int {
+    VA_LAUNCH((attention_prefill_kernel<96, decltype(kvt)::value>), dim3(H, d->rows, (n_pos + APF_Q - 1) / APF_Q), dim3(256), 0, s, (const float*)d->ws_qkv,
+              (const float*)kv.k, (const float*)kv.v, d->ws_attn, d->ws_attn_split, H, kv.max_len, p0, n_pos, rows16, pscale,
+              (const uint8_t*)kv.kscale, (const uint8_t*)kv.vscale);
     return 0;
-  }
-  const size_t smem = sizeof(float) * (size_t)(3 * 96 + 4 * 96 + 8 + d->max_len + 4);
-  VA_LAUNCH(attention_step_kernel<96>, dim3(H, d->rows, n_pos), dim3(ATT_THREADS), smem, s, d->ws_qkv, (const float*)nullptr, d->rope,
-            d->kcache + layer * kv_layer, d->vcache + layer * kv_layer, d->ws_attn, d->ws_attn_split, H, d->max_len, nullptr,
-            p0, (d->rows + 15) / 16 * 16, ldexpf(1.f, -d->plane_shift));
-  return 0;
+  });
 }
 
+// Op-level access for parity tests: ONE decode-step attention with every optional the step passes (api.hip: enqueue_layers), through the
+// launcher the step itself calls, for every K / V storage: kv_dtype 0..3, kscale / vscale (rows, n_head, max_len) the exponent bytes of the
+// scaled e4m3 cache (kv_dtype = 3; ignored for 0 .. 2)
+extern "C" int vaura_attention_step_kv(const float* qkv, const float* qkv2, const float* rope, float* kcache, float* vcache, uint8_t* kscale,
+                                       uint8_t* vscale, float* out, uint16_t* out_split, float* part, uint32_t* arrivals, int rows,
+                                       int n_head, int head_dim, int max_len, int pos, int n_split, int plane_shift, int kv_dtype,
+                                       vaura_stream_t s) {
+  if (pos < 0 || pos >= max_len || n_split < 1 || n_split > 8 || (n_split > 1 && !part)) return VAURA_ERR_ARG;
+  if (plane_shift < 0 || plane_shift > 24 || kv_dtype < 0 || kv_dtype > 3) return VAURA_ERR_ARG;
+  VaAttentionStep a;
+  a.qkv = qkv; a.qkv2 = qkv2; a.rope = rope;
+  a.kv.k = kcache; a.kv.v = vcache; a.kv.dtype = kv_dtype; a.kv.max_len = max_len;
+  if (kv_dtype == 3) { a.kv.kscale = kscale; a.kv.vscale = vscale; }
+  a.out = out; a.out_split = out_split;
+  a.rows = rows; a.n_head = n_head; a.head_dim = head_dim;
+  a.pos_host = pos;
+  a.part = n_split > 1 ? part : nullptr; a.n_split = n_split; a.arrivals = arrivals;
+  a.pscale = ldexpf(1.f, -plane_shift);
+  return va_launch_attention(a, as_stream(s));
+}
+
+// ... without the scaled storage: it has nowhere to take the exponent bytes
+extern "C" int vaura_attention_step_ex(const float* qkv, const float* qkv2, const float* rope, float* kcache, float* vcache, float* out,
+                                       uint16_t* out_split, float* part, uint32_t* arrivals, int rows, int n_head, int head_dim,
+                                       int max_len, int pos, int n_split, int plane_shift, int kv_dtype, vaura_stream_t s) {
+  if (kv_dtype > 2) return VAURA_ERR_ARG;
+  return vaura_attention_step_kv(qkv, qkv2, rope, kcache, vcache, nullptr, nullptr, out, out_split, part, arrivals, rows, n_head, head_dim,
+                                 max_len, pos, n_split, plane_shift, kv_dtype, s);
+}
+
+// ... and the two plain forms: fp32 cache, no optionals
 extern "C" int vaura_attention_step(const float* qkv, const float* rope, float* kcache, float* vcache, float* out,
                                     int rows, int n_head, int head_dim, int max_len, int pos, vaura_stream_t s) {
-  if (pos < 0 || pos >= max_len) return VAURA_ERR_ARG;
-  return va_launch_attention(qkv, nullptr, rope, kcache, vcache, out, nullptr, rows, n_head, head_dim, max_len, nullptr, pos,
-                             nullptr, 1, as_stream(s), nullptr, 1.f, 0);
+  return vaura_attention_step_kv(qkv, nullptr, rope, kcache, vcache, nullptr, nullptr, out, nullptr, nullptr, nullptr, rows, n_head, head_dim,
+                                 max_len, pos, 1, 0, 0, s);
 }
 
 extern "C" int vaura_attention_splits(int rows, int n_head, int max_len) { return va_attention_splits(rows, n_head, max_len); }
@@ -1124,32 +1113,9 @@ extern "C" int vaura_attention_splits(int rows, int n_head, int max_len) { retur
 extern "C" int vaura_attention_step_split(const float* qkv, const float* rope, float* kcache, float* vcache, float* out,
                                           float* part, int rows, int n_head, int head_dim, int max_len, int pos, int n_split,
                                           vaura_stream_t s) {
-  if (pos < 0 || pos >= max_len || !part || n_split < 2 || n_split > 8) return VAURA_ERR_ARG;
-  return va_launch_attention(qkv, nullptr, rope, kcache, vcache, out, nullptr, rows, n_head, head_dim, max_len, nullptr, pos,
-                             part, n_split, as_stream(s), nullptr, 1.f, 0);
-}
-
-// Op-level access for parity tests: ONE decode-step attention with every optional the step passes (api.hip: enqueue_layers), through the
-// launcher the step itself calls.
-extern "C" int vaura_attention_step_ex(const float* qkv, const float* qkv2, const float* rope, float* kcache, float* vcache, float* out,
-                                       uint16_t* out_split, float* part, uint32_t* arrivals, int rows, int n_head, int head_dim,
-                                       int max_len, int pos, int n_split, int plane_shift, int kv_dtype, vaura_stream_t s) {
-  if (pos < 0 || pos >= max_len || n_split < 1 || n_split > 8 || (n_split > 1 && !part)) return VAURA_ERR_ARG;
-  if (plane_shift < 0 || plane_shift > 24 || kv_dtype < 0 || kv_dtype > 2) return VAURA_ERR_ARG;
-  return va_launch_attention(qkv, qkv2, rope, kcache, vcache, out, out_split, rows, n_head, head_dim, max_len, nullptr, pos,
-                             n_split > 1 ? part : nullptr, n_split, as_stream(s), arrivals, ldexpf(1.f, -plane_shift), kv_dtype);
-}
-
-// ... and the same with the exponent bytes of the scaled e4m3 cache (kv_dtype = 3; NULL ok for 0 .. 2): kscale / vscale (rows, n_head, max_len)
-extern "C" int vaura_attention_step_kv(const float* qkv, const float* qkv2, const float* rope, float* kcache, float* vcache, uint8_t* kscale,
-                                       uint8_t* vscale, float* out, uint16_t* out_split, float* part, uint32_t* arrivals, int rows,
-                                       int n_head, int head_dim, int max_len, int pos, int n_split, int plane_shift, int kv_dtype,
-                                       vaura_stream_t s) {
-  if (pos < 0 || pos >= max_len || n_split < 1 || n_split > 8 || (n_split > 1 && !part)) return VAURA_ERR_ARG;
-  if (plane_shift < 0 || plane_shift > 24 || kv_dtype < 0 || kv_dtype > 3) return VAURA_ERR_ARG;
-  return va_launch_attention(qkv, qkv2, rope, kcache, vcache, out, out_split, rows, n_head, head_dim, max_len, nullptr, pos,
-                             n_split > 1 ? part : nullptr, n_split, as_stream(s), arrivals, ldexpf(1.f, -plane_shift), kv_dtype, kscale,
-                             vscale);
+  if (!part || n_split < 2) return VAURA_ERR_ARG;
+  return vaura_attention_step_kv(qkv, nullptr, rope, kcache, vcache, nullptr, nullptr, out, nullptr, part, nullptr, rows, n_head, head_dim,
+                                 max_len, pos, n_split, 0, 0, s);
 }
 
 // Op-level access for parity tests: rope + K / V append, then the causal attention of a teacher-forced chunk [p0, p0 + n_pos) of one

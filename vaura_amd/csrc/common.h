@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
 #include <stdint.h>
+#include <type_traits>
 #include "../../include/vaura_hip.h"
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
@@ -181,21 +182,61 @@ __device__ __forceinline__ void va_stamp_flush(const VaStamps& st, int kind) {
 int va_launch_gemv(const void* w, int wdtype, const float* x, const float* gain, const float* residual, float* out,
                    int64_t rows, int64_t N, int64_t K, int epilogue, float eps, hipStream_t s);
 int va_attention_splits(int rows, int n_head, int max_len);   // workgroups per (row, head) for this shape
-int va_launch_attention(const float* qkv, const float* qkv2, const float* rope, float* kc, float* vc, float* out,
-                        uint16_t* outp, int rows, int n_head, int head_dim, int max_len, const int32_t* pos_dev, int pos_host,
-                        float* part, int n_split, hipStream_t s, uint32_t* arrivals = nullptr, float pscale = 1.f, int kv_half = 0,
-                        uint8_t* kscale = nullptr, uint8_t* vscale = nullptr);   // kv_half = vaura_decoder.kv_dtype; 3 needs the exponent bytes
-// K / V cache of one layer: the layer stride in ELEMENTS, the elements fp32 or (vaura_decoder.kv_dtype = 1 / 2 / 3) fp16 / fp8 e4m3 / scaled e4m3
-static inline float* va_kv_layer(const vaura_decoder* d, float* base, int layer) {
-  const size_t kv_layer = (size_t)d->rows * d->dims.n_head * (size_t)d->max_len * (size_t)(d->dims.d_model / d->dims.n_head);
-  if (d->kv_dtype == 1) return reinterpret_cast<float*>(reinterpret_cast<uint16_t*>(base) + layer * kv_layer);
-  if (d->kv_dtype == 2 || d->kv_dtype == 3) return reinterpret_cast<float*>(reinterpret_cast<uint8_t*>(base) + layer * kv_layer);
-  return base + layer * kv_layer;
+// One layer's K / V cache as the attention launchers see it.  k / v are typed as the kernels take them (float* whatever the storage: same
+// kernarg layout); the elements are fp32 or (dtype = vaura_decoder.kv_dtype = 1 / 2 / 3) fp16 / fp8 e4m3 / scaled e4m3.
+struct VaKvCache {
+  float *k = nullptr, *v = nullptr;             // (rows, n_head, max_len, 96) elements of the storage
+  uint8_t *kscale = nullptr, *vscale = nullptr; // dtype = 3 only (NULL otherwise): one exponent byte per cached vector, (rows, n_head, max_len)
+  int dtype = 0, max_len = 0;
+};
+// layer `layer` of a descriptor's cache: the layer stride in ELEMENTS of the storage (an out-of-range dtype is refused by va_kv_dispatch)
+static inline VaKvCache va_kv_cache(const vaura_decoder* d, int layer) {
+  const size_t vectors = (size_t)layer * d->rows * d->dims.n_head * (size_t)d->max_len;
+  const size_t bytes = vectors * (size_t)(d->dims.d_model / d->dims.n_head) * (d->kv_dtype == 1 ? 2 : (d->kv_dtype == 2 || d->kv_dtype == 3) ? 1 : 4);
+  VaKvCache c;
+  c.k = reinterpret_cast<float*>(reinterpret_cast<char*>(d->kcache) + bytes);
+  c.v = reinterpret_cast<float*>(reinterpret_cast<char*>(d->vcache) + bytes);
+  if (d->kv_dtype == 3 && d->kscale && d->vscale) { c.kscale = d->kscale + vectors; c.vscale = d->vscale + vectors; }
+  c.dtype = d->kv_dtype; c.max_len = d->max_len;
+  return c;
 }
-// exponent bytes of one layer (kv_dtype = 3): one per cached vector, (n_layer, rows, n_head, max_len)
-static inline uint8_t* va_kv_scale_layer(const vaura_decoder* d, uint8_t* base, int layer) {
-  return base ? base + (size_t)layer * d->rows * d->dims.n_head * (size_t)d->max_len : nullptr;
+// What every attention launcher refuses about a cache: head_dim != 96 and a narrow cache (dtype != 0) of more than 256 positions or under
+// a range split are VAURA_ERR_SHAPE (fp16 / fp8 / scaled fp8 have the single-round-trip step kernel only: every 2.56 s configuration),
+// scaled e4m3 without its exponent bytes is VAURA_ERR_ARG.  When two apply, the decode step's launcher has always reported the missing
+// bytes (arg_first), the two prefill launchers the shape: each keeps its order.
+static inline int va_kv_check(const VaKvCache& c, int head_dim, bool range_split, bool arg_first) {
+  const bool no_scales = c.dtype == 3 && (!c.kscale || !c.vscale);
+  if (arg_first && no_scales) return VAURA_ERR_ARG;
+  if (head_dim != 96 || (c.dtype != 0 && (c.max_len > 256 || range_split))) return VAURA_ERR_SHAPE;
+  return no_scales ? VAURA_ERR_ARG : 0;
 }
+// f(std::integral_constant<int, KVT>{}) for the storage `dtype`: the one place that maps vaura_decoder.kv_dtype to a KvT<> instance.
+// f returns int: VA_LAUNCH inside a lambda returns the launch error from the lambda, and the launcher passes that on.
+template <class F>
+static inline int va_kv_dispatch(int dtype, F&& f) {
+  switch (dtype) {
+    case 0: return f(std::integral_constant<int, 0>{});
+    case 1: return f(std::integral_constant<int, 1>{});
+    case 2: return f(std::integral_constant<int, 2>{});
+    case 3: return f(std::integral_constant<int, 3>{});
+  }
+  return VAURA_ERR_ARG;
+}
+struct VaAttentionStep {             // one decode-step attention: rope + cache append + softmax(qK^T)V of `rows` rows at one position
+  const float *qkv = nullptr, *qkv2 = nullptr;   // qkv2: second K-half partial of qkv (added on load), or NULL
+  const float* rope = nullptr;
+  VaKvCache kv;
+  float* out = nullptr;              // fp32 packed rows (rows x d_model)
+  uint16_t* out_split = nullptr;     // planes for wo, or NULL
+  int rows = 0, n_head = 0, head_dim = 0;
+  const int32_t* pos_dev = nullptr;  // position on the device (state[0]), or NULL for pos_host
+  int pos_host = 0;
+  float* part = nullptr;             // partials of the range split (with n_split > 1), or NULL
+  int n_split = 1;
+  uint32_t* arrivals = nullptr;      // rows * n_head zeroed words: the last split to arrive merges; NULL: a combine launch follows
+  float pscale = 1.f;                // scale of the out_split planes (2^-plane_shift)
+};
+int va_launch_attention(const VaAttentionStep& a, hipStream_t s);
 struct Gemv3Args;
 static inline bool va_is_fp8(int wdtype) { return wdtype == VAURA_W_FP8 || wdtype == VAURA_W_FP8H; }   // e4m3 tile pairs (both activation arithmetics)
 unsigned va_debug_flags2_get();  // vaura_set_debug_flags2: the second word
@@ -206,26 +247,34 @@ int va_launch_gemv3(const Gemv3Args& a, int64_t n_weight_rows, int64_t K, int ep
 bool va_mlp_engine_eligible(const vaura_decoder* d);
 struct VaEngineAttention {     // the next layer's attention as a fourth phase of the one-launch MLP (mlp_engine.h, ATT instances)
   const float* rope;
-  float* kc;                   // K / V cache of THAT layer: (rows, n_head, max_len, 96)
-  float* vc;
+  VaKvCache kv;                // K / V cache of THAT layer (fp32 only)
   float* out;                  // fp32 packed rows (rows x d_model)
   uint16_t* outp;              // planes for wo
-  int n_head, max_len;
+  int n_head;
 };
 int va_launch_mlp_engine(const Gemv3Args& a13, const Gemv3Args& a2, const Gemv3Args* aq_next, uint32_t* flags, int32_t* state, int layer,
                          hipStream_t s, const VaEngineAttention* att = nullptr, const void* warm_ptr = nullptr, size_t warm_bytes = 0,
                          const void* warm0_ptr = nullptr, size_t warm0_bytes = 0);
 // experiment builds only (-DVAURA_EXPERIMENT_ENGINES: csrc/experiments/)
-int va_launch_attn_wo(const float* qkv, const float* qkv2, const float* rope, float* kc, float* vc, float* out, uint16_t* outp,
-                      int rows, int n_head, int max_len, const int32_t* state, const Gemv3Args& awo, uint32_t* flags, int layer, hipStream_t s);
+int va_launch_attn_wo(const float* qkv, const float* qkv2, const float* rope, const VaKvCache& kv, float* out, uint16_t* outp,
+                      int rows, int n_head, const int32_t* state, const Gemv3Args& awo, uint32_t* flags, int layer, hipStream_t s);
 int va_launch_tail_engine(const Gemv3Args& awo, const Gemv3Args& a13, const Gemv3Args& a2, uint32_t* flags, int32_t* state, int layer,
                           hipStream_t s);
 int va_launch_embed(const vaura_decoder* d, int pos_host, int n_pos, hipStream_t s);
-// clips: per-clip records (vaura_decoder.clip_sampling) or NULL for the scalars of `sp`
-int va_launch_sample(const float* logits, int B, int K, int vocab, const vaura_sampling* sp, const vaura_clip_sampling* clips,
-                     const float* noise, int noise_rows_per_step, const int32_t* state, int64_t step_host, int32_t* tokens_out,
-                     int32_t* seq, int T, int S, int32_t* state_rw, const int32_t* delays_host, hipStream_t s,
-                     float* lp_out /* (B, K) */, float* lp_seq /* (B, K, S); either non-NULL selects the LP instances */);
+struct VaSampleLaunch {              // one sampler launch over (B, K) rows of logits
+  const float* logits = nullptr;
+  int B = 0, K = 0, vocab = 0;
+  const vaura_sampling* sp = nullptr;
+  const vaura_clip_sampling* clips = nullptr;   // per-clip records (vaura_decoder.clip_sampling) or NULL for the scalars of `sp`
+  const float* noise = nullptr;
+  int32_t* state = nullptr;          // decoder state, or NULL (standalone: step_host).  Feeds the kernel's preloaded `state` argument,
+  int64_t step_host = 0;             // SampleArgs.state (position, step: read) and SampleArgs.state_rw (arrivals, advance, status: written)
+  int32_t *tokens_out = nullptr, *seq = nullptr;   // (B, K) tokens and / or the pattern sequence (B, K, S) of T timesteps
+  int T = 0, S = 0;
+  const int32_t* delays_host = nullptr;   // K delays, NULL = the default d_k = k
+  float *lp_out = nullptr, *lp_seq = nullptr;     // (B, K) / (B, K, S); either non-NULL selects the LP instances
+};
+int va_launch_sample(const VaSampleLaunch& a, hipStream_t s);
 int va_check_clip_sampling(const vaura_sampling* sp, const vaura_clip_sampling* clips, int B, bool doubled, hipStream_t s);
 int va_launch_advance(int32_t* state, int set_to, hipStream_t s);
 int va_launch_linear_pair(const uint16_t* in, const uint16_t* w, const float* bias, const float* res, float* out_raw,

@@ -139,11 +139,11 @@ __global__ __launch_bounds__(ATT1_THREADS) void attn_wo_kernel(
 
 // attention (single-round-trip kernel) + wo of one layer as one launch; the caller checked va_mlp_engine_eligible, rows in 1..16,
 // n_head == 16, max_len <= 256.  flags: 256 words.  awo.wscale is filled in here (the scales follow the packed tiles).
-int va_launch_attn_wo(const float* qkv, const float* qkv2, const float* rope, float* kc, float* vc, float* out, uint16_t* outp,
-                      int rows, int n_head, int max_len, const int32_t* state, const Gemv3Args& awo, uint32_t* flags, int layer, hipStream_t s) {
-  if (!qkv || !rope || !kc || !vc || !out || !outp || !state || !flags || !awo.W || awo.XP != outp || !awo.res || !awo.out || !awo.outp ||
+int va_launch_attn_wo(const float* qkv, const float* qkv2, const float* rope, const VaKvCache& kv, float* out, uint16_t* outp,
+                      int rows, int n_head, const int32_t* state, const Gemv3Args& awo, uint32_t* flags, int layer, hipStream_t s) {
+  if (!qkv || !rope || !kv.k || !kv.v || !out || !outp || !state || !flags || !awo.W || awo.XP != outp || !awo.res || !awo.out || !awo.outp ||
       !awo.gain_out || !awo.ss_out || awo.R != 1) return VAURA_ERR_ARG;
-  if (n_head != 16 || max_len > 256 || rows < 1 || rows > 16 || awo.N != 1536 || (awo.wq != 0 && awo.wq != 2)) return VAURA_ERR_SHAPE;
+  if (kv.dtype != 0 || n_head != 16 || kv.max_len > 256 || rows < 1 || rows > 16 || awo.N != 1536 || (awo.wq != 0 && awo.wq != 2)) return VAURA_ERR_SHAPE;
   AttnWoArgs e;
   e.rows = rows;
   e.wo = awo;
@@ -151,9 +151,9 @@ int va_launch_attn_wo(const float* qkv, const float* qkv2, const float* rope, fl
   e.flags = flags; e.state = state; e.state_rw = const_cast<int32_t*>(state); e.layer = layer;
   e.abl = (int)((va_debug_flags_get() >> 28) & 15u);
   if (awo.wq == 2)
-    VA_LAUNCH(attn_wo_kernel<2>, dim3(n_head, 16), dim3(ATT1_THREADS), 0, s, state, kc, vc, qkv, qkv2, rope, n_head, max_len, out, outp, e);
+    VA_LAUNCH(attn_wo_kernel<2>, dim3(n_head, 16), dim3(ATT1_THREADS), 0, s, state, kv.k, kv.v, qkv, qkv2, rope, n_head, kv.max_len, out, outp, e);
   else
-    VA_LAUNCH(attn_wo_kernel<0>, dim3(n_head, 16), dim3(ATT1_THREADS), 0, s, state, kc, vc, qkv, qkv2, rope, n_head, max_len, out, outp, e);
+    VA_LAUNCH(attn_wo_kernel<0>, dim3(n_head, 16), dim3(ATT1_THREADS), 0, s, state, kv.k, kv.v, qkv, qkv2, rope, n_head, kv.max_len, out, outp, e);
   return 0;
 }
 

@@ -274,9 +274,10 @@ int va_launch_mlp_engine(const Gemv3Args& a13, const Gemv3Args& a2, const Gemv3A
   e.pf_lines0 = (warm0_ptr && (va_debug_flags2 & 0x400000u)) ? (int)(warm0_bytes / 128) : 0;
   e.att_rope = nullptr; e.att_kc = e.att_vc = e.att_out = nullptr; e.att_outp = nullptr; e.att_max_len = 0;
   if (att) {
-    if (!aq || a13.R != 1 || !att->rope || !att->kc || !att->vc || !att->out || att->n_head != 16 || att->max_len > 256 || att->max_len < 1)
+    if (!aq || a13.R != 1 || !att->rope || !att->kv.k || !att->kv.v || att->kv.dtype != 0 || !att->out || att->n_head != 16 || att->kv.max_len > 256 ||
+        att->kv.max_len < 1)
       return VAURA_ERR_ARG;
-    e.att_rope = att->rope; e.att_kc = att->kc; e.att_vc = att->vc; e.att_out = att->out; e.att_outp = att->outp; e.att_max_len = att->max_len;
+    e.att_rope = att->rope; e.att_kc = att->kv.k; e.att_vc = att->kv.v; e.att_out = att->out; e.att_outp = att->outp; e.att_max_len = att->kv.max_len;
   }
   e.p1 = a13;
   e.p2 = a2;

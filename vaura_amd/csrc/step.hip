@@ -612,34 +612,33 @@ int va_check_clip_sampling(const vaura_sampling* sp, const vaura_clip_sampling* 
   return 0;
 }
 
-int va_launch_sample(const float* logits, int B, int K, int vocab, const vaura_sampling* sp, const vaura_clip_sampling* clips,
-                     const float* noise, int /*noise_rows_per_step*/, const int32_t* state, int64_t step_host, int32_t* tokens_out,
-                     int32_t* seq, int T, int S, int32_t* state_rw, const int32_t* delays_host, hipStream_t s, float* lp_out,
-                     float* lp_seq) {
-  if (!logits || !sp || B <= 0 || K <= 0) return VAURA_ERR_ARG;
-  if (clips && sp->input_is_probs) return VAURA_ERR_ARG;
-  const bool lp = lp_out || lp_seq;
+int va_launch_sample(const VaSampleLaunch& l, hipStream_t s) {
+  const vaura_sampling* sp = l.sp;
+  const int B = l.B, K = l.K;
+  if (!l.logits || !sp || B <= 0 || K <= 0) return VAURA_ERR_ARG;
+  if (l.clips && sp->input_is_probs) return VAURA_ERR_ARG;
+  const bool lp = l.lp_out || l.lp_seq;
   if (lp && sp->input_is_probs) return VAURA_ERR_ARG;        // rows that already are probabilities: no log-probability to report
-  if (vocab != 1024) return VAURA_ERR_SHAPE;
-  if (delays_host && K > 16) return VAURA_ERR_ARG;
+  if (l.vocab != 1024) return VAURA_ERR_SHAPE;
+  if (l.delays_host && K > 16) return VAURA_ERR_ARG;
   SampleArgs a;
-  a.logits = logits; a.noise = noise; a.state = state; a.state_rw = state_rw; a.tokens_out = tokens_out; a.seq = seq;
-  a.B = B; a.K = K; a.V = vocab; a.T = T; a.S = S;
-  for (int j = 0; j < 16; ++j) a.delays[j] = (delays_host && j < K) ? delays_host[j] : j;   // NULL: the default pattern, d_k = k
+  a.logits = l.logits; a.noise = l.noise; a.state = l.state; a.state_rw = l.state; a.tokens_out = l.tokens_out; a.seq = l.seq;
+  a.B = B; a.K = K; a.V = l.vocab; a.T = l.T; a.S = l.S;
+  for (int j = 0; j < 16; ++j) a.delays[j] = (l.delays_host && j < K) ? l.delays_host[j] : j;   // NULL: the default pattern, d_k = k
   a.use_sampling = sp->use_sampling; a.top_k = sp->top_k; a.temp = sp->temp; a.top_p = sp->top_p;
-  a.cfg_scale = sp->input_is_probs ? 1.0f : sp->cfg_scale; a.seed = sp->seed; a.clip_base = sp->clip_base; a.step_host = step_host;
+  a.cfg_scale = sp->input_is_probs ? 1.0f : sp->cfg_scale; a.seed = sp->seed; a.clip_base = sp->clip_base; a.step_host = l.step_host;
   a.probs_in = sp->input_is_probs;
   a.tie_eps = sp->tie_eps > 0.f ? sp->tie_eps : 0.f;
-  const int32_t* rec = reinterpret_cast<const int32_t*>(clips);
+  const int32_t* rec = reinterpret_cast<const int32_t*>(l.clips);
   // (named outside the macro: the commas of the template arguments would split its argument list)
   const auto k_plain = sample_kernel<false, false>, k_pc = sample_kernel<true, false>;
   const auto k_lp = sample_kernel<false, true, SampleLogprobs>, k_pc_lp = sample_kernel<true, true, SampleLogprobs>;
   if (lp) {
-    if (clips) VA_LAUNCH(k_pc_lp, dim3(K, B), dim3(SMP_THREADS), 0, s, a.logits, a.state, a, rec, SampleLogprobs{lp_out, lp_seq});
-    else VA_LAUNCH(k_lp, dim3(K, B), dim3(SMP_THREADS), 0, s, a.logits, a.state, a, rec, SampleLogprobs{lp_out, lp_seq});
+    if (l.clips) VA_LAUNCH(k_pc_lp, dim3(K, B), dim3(SMP_THREADS), 0, s, a.logits, a.state, a, rec, SampleLogprobs{l.lp_out, l.lp_seq});
+    else VA_LAUNCH(k_lp, dim3(K, B), dim3(SMP_THREADS), 0, s, a.logits, a.state, a, rec, SampleLogprobs{l.lp_out, l.lp_seq});
     return 0;
   }
-  if (clips) VA_LAUNCH(k_pc, dim3(K, B), dim3(SMP_THREADS), 0, s, a.logits, a.state, a, rec);
+  if (l.clips) VA_LAUNCH(k_pc, dim3(K, B), dim3(SMP_THREADS), 0, s, a.logits, a.state, a, rec);
   else VA_LAUNCH(k_plain, dim3(K, B), dim3(SMP_THREADS), 0, s, a.logits, a.state, a, rec);
   return 0;
 }
@@ -708,18 +707,6 @@ static int pattern_build(const int32_t* codes, int32_t* seq, int B, int K, int T
   return 0;
 }
 
-static int pattern_revert(const int32_t* seq, int32_t* codes, int B, int K, int T, int S, int fill, const int32_t* delays_host,
-                          hipStream_t s) {
-  if (!codes || !seq || B <= 0 || K <= 0 || T <= 0 || S <= 0) return VAURA_ERR_ARG;
-  PatternDelays pd;
-  const int span = pattern_delays_arg(delays_host, K, &pd);
-  if (span < 0) return span;
-  if (delays_host && S > T + span) return VAURA_ERR_SHAPE;
-  const int64_t n = (int64_t)B * K * T;
-  VA_LAUNCH(pattern_revert_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, seq, codes, B, K, T, S, fill, pd);
-  return 0;
-}
-
 // float twin of pattern_revert_kernel (token log-probabilities live in the layout of seq): the same index map
 __global__ void pattern_revert_f32_kernel(const float* __restrict__ seq, float* __restrict__ out, int B, int K, int T, int S, float fill,
                                           PatternDelays pd) {
@@ -729,6 +716,21 @@ __global__ void pattern_revert_f32_kernel(const float* __restrict__ seq, float* 
   const int64_t b = i / ((int64_t)T * K);
   const int s = t + 1 + pattern_delay(pd, q);
   out[i] = (s < S) ? seq[((size_t)b * K + q) * S + s] : fill;
+}
+
+// tokens (int32_t) or their log-probabilities (float): the two kernels above
+template <typename E>
+static int pattern_revert(const E* seq, E* out, int B, int K, int T, int S, E fill, const int32_t* delays_host, hipStream_t s) {
+  if (!out || !seq || B <= 0 || K <= 0 || T <= 0 || S <= 0) return VAURA_ERR_ARG;
+  PatternDelays pd;
+  const int span = pattern_delays_arg(delays_host, K, &pd);
+  if (span < 0) return span;
+  if (delays_host && S > T + span) return VAURA_ERR_SHAPE;
+  const int64_t n = (int64_t)B * K * T;
+  const dim3 grid((unsigned)((n + 255) / 256));
+  if constexpr (std::is_same<E, float>::value) VA_LAUNCH(pattern_revert_f32_kernel, grid, dim3(256), 0, s, seq, out, B, K, T, S, fill, pd);
+  else VA_LAUNCH(pattern_revert_kernel, grid, dim3(256), 0, s, seq, out, B, K, T, S, fill, pd);
+  return 0;
 }
 
 // Sequence scores of token log-probabilities kept in the layout of seq.  One workgroup per clip, one wave per codebook (K <= 16), in a
@@ -797,8 +799,9 @@ int vaura_pattern_revert_delays(const int32_t* seq, int32_t* codes, int B, int K
 int vaura_sample(const float* logits, int B, int K, int vocab, const vaura_sampling* sp, const float* noise,
                  int64_t step, int32_t* tokens_out, vaura_stream_t s) {
   if (!tokens_out) return VAURA_ERR_ARG;
-  return va_launch_sample(logits, B, K, vocab, sp, nullptr, noise, B * K, nullptr, step, tokens_out, nullptr, 0, 0, nullptr, nullptr,
-                          as_stream(s), nullptr, nullptr);
+  VaSampleLaunch a;      // no state: the step comes from the host
+  a.logits = logits; a.B = B; a.K = K; a.vocab = vocab; a.sp = sp; a.noise = noise; a.step_host = step; a.tokens_out = tokens_out;
+  return va_launch_sample(a, as_stream(s));
 }
 
 int vaura_sample_clips(const float* logits, int B, int K, int vocab, const vaura_sampling* sp, const vaura_clip_sampling* clips,
@@ -809,8 +812,11 @@ int vaura_sample_clips(const float* logits, int B, int K, int vocab, const vaura
   if (!logits || !sp || B <= 0 || K <= 0) return VAURA_ERR_ARG;
   const int rc = va_check_clip_sampling(sp, clips, B, sp->cfg_scale > 1.0f, as_stream(s));
   if (rc) return rc;
-  int32_t* st = seq ? state : nullptr;      // the standalone form keeps no state, like vaura_sample
-  return va_launch_sample(logits, B, K, vocab, sp, clips, noise, B * K, st, step, tokens_out, seq, T, S, st, nullptr, as_stream(s), nullptr, nullptr);
+  VaSampleLaunch a;
+  a.logits = logits; a.B = B; a.K = K; a.vocab = vocab; a.sp = sp; a.clips = clips; a.noise = noise; a.step_host = step;
+  a.tokens_out = tokens_out; a.seq = seq; a.T = T; a.S = S;
+  a.state = seq ? state : nullptr;      // the standalone form keeps no state, like vaura_sample
+  return va_launch_sample(a, as_stream(s));
 }
 
 int vaura_sample_logprobs(const float* logits, int B, int K, int vocab, const vaura_sampling* sp, const vaura_clip_sampling* clips,
@@ -821,21 +827,17 @@ int vaura_sample_logprobs(const float* logits, int B, int K, int vocab, const va
   if (sp->input_is_probs) return VAURA_ERR_ARG;
   const int rc = va_check_clip_sampling(sp, clips, B, sp->cfg_scale > 1.0f, as_stream(s));
   if (rc) return rc;
-  int32_t* st = seq ? state : nullptr;
-  return va_launch_sample(logits, B, K, vocab, sp, clips, noise, B * K, st, step, tokens_out, seq, T, S, st, nullptr, as_stream(s),
-                          logprobs_out, nullptr);
+  VaSampleLaunch a;
+  a.logits = logits; a.B = B; a.K = K; a.vocab = vocab; a.sp = sp; a.clips = clips; a.noise = noise; a.step_host = step;
+  a.tokens_out = tokens_out; a.seq = seq; a.T = T; a.S = S;
+  a.state = seq ? state : nullptr;      // the standalone form keeps no state, like vaura_sample
+  a.lp_out = logprobs_out;
+  return va_launch_sample(a, as_stream(s));
 }
 
 int vaura_pattern_revert_delays_f32(const float* seq, float* out, int B, int K, int T, int S, float fill, const int32_t* delays_host,
                                     vaura_stream_t s) {
-  if (!seq || !out || B <= 0 || K <= 0 || T <= 0 || S <= 0) return VAURA_ERR_ARG;
-  PatternDelays pd;
-  const int span = pattern_delays_arg(delays_host, K, &pd);
-  if (span < 0) return span;
-  if (delays_host && S > T + span) return VAURA_ERR_SHAPE;
-  const int64_t n = (int64_t)B * K * T;
-  VA_LAUNCH(pattern_revert_f32_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, as_stream(s), seq, out, B, K, T, S, fill, pd);
-  return 0;
+  return pattern_revert(seq, out, B, K, T, S, fill, delays_host, as_stream(s));
 }
 
 int vaura_sequence_logprob(const float* logprobs, int seq_len, const int32_t* delays_host, int B, int K, int T, int t0,

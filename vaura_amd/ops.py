@@ -85,23 +85,12 @@ def attention_step_ex(qkv_p: torch.Tensor, rope: torch.Tensor, kcache: torch.Ten
                       head_dim: int, pos: int, *, kv_dtype: int = 0, qkv2_p: Optional[torch.Tensor] = None, n_split: int = 1,
                       part: Optional[torch.Tensor] = None, arrivals: Optional[torch.Tensor] = None, want_split: bool = False,
                       plane_shift: int = 0, out: Optional[torch.Tensor] = None, out_split: Optional[torch.Tensor] = None):
-    """vaura_attention_step_ex: one decode-step attention with every optional of the step.  kcache / vcache (rows, n_head, max_len,
-    head_dim) in the storage of ``kv_dtype`` (fp32, fp16, e4m3).  Returns (out packed rows, out_split or None); ``out`` / ``out_split`` /
-    ``part`` may be passed in (pre-filled) instead of allocated here."""
-    _cuda(qkv_p, qkv2_p, rope, kcache, vcache, part, arrivals, out, out_split)
-    max_len = kcache.shape[-2]
-    rp = (rows + 15) // 16 * 16
-    dev = qkv_p.device
-    if out is None:
-        out = torch.zeros(rp * n_head * head_dim, dtype=torch.float32, device=dev)
-    if want_split and out_split is None:
-        out_split = torch.zeros(rp * 2 * n_head * head_dim, dtype=torch.int16, device=dev)
-    if n_split > 1 and part is None:
-        part = torch.empty(rows * n_head * n_split * (head_dim + 8), dtype=torch.float32, device=dev)
-    L.check(L.lib().vaura_attention_step_ex(L.ptr(qkv_p), L.ptr(qkv2_p), L.ptr(rope), L.ptr(kcache), L.ptr(vcache), L.ptr(out),
-                                            L.ptr(out_split), L.ptr(part), L.ptr(arrivals), rows, n_head, head_dim, max_len, pos,
-                                            n_split, plane_shift, kv_dtype, L.current_stream()), "vaura_attention_step_ex")
-    return out, out_split
+    """vaura_attention_step_ex: ``attention_step_kv`` without the scaled storage (kv_dtype 0..2: fp32, fp16, e4m3), refused here as the C
+    entry point refuses it."""
+    if kv_dtype == 3:
+        L.check(-1, "vaura_attention_step_ex")      # VAURA_ERR_ARG: it has nowhere to take the exponent bytes
+    return attention_step_kv(qkv_p, rope, kcache, vcache, rows, n_head, head_dim, pos, kv_dtype=kv_dtype, qkv2_p=qkv2_p, n_split=n_split,
+                             part=part, arrivals=arrivals, want_split=want_split, plane_shift=plane_shift, out=out, out_split=out_split)
 
 
 def attention_step_kv(qkv_p: torch.Tensor, rope: torch.Tensor, kcache: torch.Tensor, vcache: torch.Tensor, rows: int, n_head: int,
@@ -109,8 +98,10 @@ def attention_step_kv(qkv_p: torch.Tensor, rope: torch.Tensor, kcache: torch.Ten
                       vscale: Optional[torch.Tensor] = None, qkv2_p: Optional[torch.Tensor] = None, n_split: int = 1,
                       part: Optional[torch.Tensor] = None, arrivals: Optional[torch.Tensor] = None, want_split: bool = False,
                       plane_shift: int = 0, out: Optional[torch.Tensor] = None, out_split: Optional[torch.Tensor] = None):
-    """vaura_attention_step_kv: ``attention_step_ex`` for every storage, 0..3.  kv_dtype = 3 (scaled e4m3): kcache / vcache hold the
-    bytes (uint8 or float8_e4m3fn), kscale / vscale (rows, n_head, max_len) uint8 the exponent byte of every cached vector."""
+    """vaura_attention_step_kv: one decode-step attention with every optional of the step.  kcache / vcache (rows, n_head, max_len,
+    head_dim) in the storage of ``kv_dtype`` (fp32, fp16, e4m3, scaled e4m3).  kv_dtype = 3: kcache / vcache hold the bytes (uint8 or
+    float8_e4m3fn), kscale / vscale (rows, n_head, max_len) uint8 the exponent byte of every cached vector.  Returns (out packed rows,
+    out_split or None); ``out`` / ``out_split`` / ``part`` may be passed in (pre-filled) instead of allocated here."""
     _cuda(qkv_p, qkv2_p, rope, kcache, vcache, kscale, vscale, part, arrivals, out, out_split)
     max_len = kcache.shape[-2]
     rp = (rows + 15) // 16 * 16
