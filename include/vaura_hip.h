@@ -209,6 +209,11 @@ typedef struct vaura_decoder {
    * delays — sorted, >= 0, K <= 16 (VAURA_ERR_ARG otherwise).  The sampler's valid-slot fix-up and its near-tie count follow them. */
   int32_t has_pattern_delays;
   int32_t pattern_delays[16];
+  /* Bytes of extension that FOLLOW this struct in the caller's memory: 0 (a zero-filled descriptor: none), or
+   * sizeof(vaura_decoder_ext) - sizeof(vaura_decoder) when `dec` is the first member of a vaura_decoder_ext (below); anything else is
+   * VAURA_ERR_ARG.  It occupies what was alignment padding in front of `kscale`: no field moved and the struct keeps its size, so a
+   * caller compiled against the descriptor without it (and zero-filling it, as every field's default asks) runs unchanged. */
+  int32_t ext_bytes;
   /* kv_dtype = 3 only (NULL otherwise): the exponent bytes of the scaled e4m3 cache, (n_layer, rows, n_head, max_len) each;
    * VAURA_ERR_ARG when kv_dtype = 3 and either is NULL */
   uint8_t* kscale;
@@ -236,6 +241,26 @@ typedef struct vaura_decoder {
    * graph holds it like every other buffer.  VAURA_ERR_ARG together with input_is_probs = 1.  vaura_score ignores it. */
   float* logprobs;
 } vaura_decoder;
+
+/* vaura_decoder with the video-relevance pointers appended behind its last field.  Every entry point takes `&ext.dec`; the library
+ * reads the two pointers only when ext.dec.ext_bytes says that they are there.
+ * Video relevance of the sampled tokens (both NULL: none — the sampler instances above, unchanged; exactly one NULL: VAURA_ERR_ARG):
+ * two fp32 buffers (batch, K, seq_len) in the layout of `seq`, written where `logprobs` is written (a sampled token in a valid slot
+ * that held -1; the caller zeroes them first).  For the token chosen, its log-probability under the model's two distributions,
+ *     logprobs_cond = (x_c[tok] - max x_c) - logf(sum expf(x_c - max x_c))     x_c = the conditional row of (clip, codebook)
+ *     logprobs_null = (x_u[tok] - max x_u) - logf(sum expf(x_u - max x_u))     x_u = the null-condition row of the same prefix
+ * full vocabulary, NO temperature and no CFG mix: relevance = logprobs_cond - logprobs_null, the pointwise mutual information of
+ * token and video, does not depend on the sampling settings.  Reduction order per row: block maximum, then block sum (csrc/step.hip).
+ * Needs the null-condition rows: rows == 2 batch and the scalar cfg_scale > 1 (VAURA_ERR_ARG otherwise, before any launch).  A clip
+ * whose own scale is <= 1 is still drawn un-mixed; its null row is read for logprobs_null only.  NaN in both on a row that raised
+ * VAURA_STATUS_NONFINITE_LOGITS — which these pointers also raise for a non-finite value in either of the two rows.  The token drawn
+ * never depends on them.  A captured step graph holds them like `logprobs`.  VAURA_ERR_ARG with input_is_probs = 1.  vaura_score
+ * ignores them. */
+typedef struct vaura_decoder_ext {
+  vaura_decoder dec;        /* dec.ext_bytes = sizeof(vaura_decoder_ext) - sizeof(vaura_decoder) */
+  float* logprobs_cond;
+  float* logprobs_null;
+} vaura_decoder_ext;
 
 /* -------------------------------------------------------------------------------------------
  * Weight ingress (once, at load).  Replaces nn.Module.load_state_dict for the streamed matrices.
@@ -300,6 +325,15 @@ int vaura_sample_clips(const float* logits, int B, int K, int vocab, const vaura
 int vaura_sample_logprobs(const float* logits, int B, int K, int vocab, const vaura_sampling* sp, const vaura_clip_sampling* clips,
                           const float* noise, int64_t step, int32_t* tokens_out, int32_t* seq, int T, int S, int32_t* state,
                           float* logprobs_out, vaura_stream_t s);
+/* vaura_sample_logprobs that also reports the video relevance of every token drawn (vaura_decoder_ext.logprobs_cond / logprobs_null):
+ * cond_out, null_out (B, K) fp32 = the token's log-probability under the conditional row and under the null row, tau = 1, full
+ * vocabulary.  logits has 2B rows and sp->cfg_scale > 1 says so (scalar form: the clips are mixed with that scale; per-clip form: a
+ * record with cfg_scale <= 1 draws un-mixed and its null row is read for null_out only).  logprobs_out may be NULL.  Tokens and
+ * logprobs_out equal what vaura_sample_logprobs returns for the same inputs.  VAURA_ERR_ARG: sp->cfg_scale <= 1 (no null rows), a NULL
+ * cond_out or null_out, and what vaura_sample_logprobs refuses.                                                                    */
+int vaura_sample_relevance(const float* logits, int B, int K, int vocab, const vaura_sampling* sp, const vaura_clip_sampling* clips,
+                           const float* noise, int64_t step, int32_t* tokens_out, int32_t* seq, int T, int S, int32_t* state,
+                           float* logprobs_out, float* cond_out, float* null_out, vaura_stream_t s);
 /* float twin of vaura_pattern_revert_delays: seq (B,K,S) fp32 -> out (B,K,T), frame t of codebook q from step t + 1 + d_q, `fill`
  * where S ends before it.  delays_host == NULL: d_q = q.                                                                           */
 int vaura_pattern_revert_delays_f32(const float* seq, float* out, int B, int K, int T, int S, float fill, const int32_t* delays_host,
@@ -370,6 +404,14 @@ void vaura_profile_outliers(int64_t* per_kind);
  * of codebook q, loss (1) = sum_q loss_per_cb[q] / K.  Summation order is fixed: two calls give the same bits.                 */
 int vaura_score(const vaura_decoder* dec, int n_pos, const int32_t* targets, float* ws_chunk_logits, float* logits_out, float* nll,
                 uint8_t* mask_out, float* loss_per_cb, float* loss, vaura_stream_t s);
+/* vaura_score on a descriptor with the null-condition rows (dec->rows == 2 dec->batch; VAURA_ERR_ARG otherwise): the given codes are
+ * prefilled under the video (rows [0, B)) and under the null condition (rows [B, 2B)) in one pass, the NLL kernel runs on both row sets
+ * and the reduction on both nll tensors.  nll / loss_per_cb / loss as vaura_score; nll_null (B, K, Ta), loss_per_cb_null (K),
+ * loss_null (1) the same quantities of the null rows (same mask, same fixed order).  nll_null - nll is how much the video explains
+ * of every given token.                                                                                                            */
+int vaura_score_relevance(const vaura_decoder* dec, int n_pos, const int32_t* targets, float* ws_chunk_logits, float* logits_out, float* nll,
+                          uint8_t* mask_out, float* loss_per_cb, float* loss, float* nll_null, float* loss_per_cb_null, float* loss_null,
+                          vaura_stream_t s);
 /* _compute_loss on a given reverted logits tensor (B, K, Ta, vocab) fp32, targets (B, K, Ta) int32, mask (B, K, Ta) bytes: the same
  * NLL and reduction kernels (vocab % 256 == 0, <= 1024; K <= 16).  nll (B, K, Ta) is scratch + output (entries where mask is 0 are
  * not meaningful).                                                                                                                */

@@ -6,7 +6,13 @@
 identical: equal bytes once the compile-unit id (__hip_cuid_<hash of the source path and options>) is masked.
 same-set : not identical, but equal after splitting at the function symbols and at the kernels' metadata records, masking the index of
            the function in its local labels (.LBB<i>_<j>, .Lfunc_end<i>) and sorting: host code instantiated the templates in another
-           order; the set of symbols and every instruction stream are equal.  Anything else exits 1."""
+           order; the set of symbols and every instruction stream are equal.  Anything else exits 1.
+
+    python tools/compare_device_asm.py --subset OLD.s NEW.s
+subset   : for a change that ADDS kernels to the unit: every function of OLD and every metadata record of OLD's kernels is in NEW,
+           equal byte for byte under the same masking; the functions NEW adds are listed.  The padding the assembler puts behind the
+           LAST function of the unit (.p2alignl / .fill of s_code_end words) is taken off first: it follows whichever function the
+           unit ends with, not that function's code.  Anything else exits 1."""
 import hashlib
 import re
 import sys
@@ -26,11 +32,33 @@ def pieces(t):
     return sorted(funcs) + [trailer, "<metadata>"] + sorted(recs) + [tail]
 
 
+PAD = re.compile(r"\t\.text\n\t\.p2alignl \d+, \d+\n\t\.fill \d+, \d+, \d+\n\Z")
+
+
+def subset(a, b):
+    pa, pb = ([PAD.sub("", x) for x in pieces(t)] for t in (a, b))
+    ia, ib = pa.index("<metadata>"), pb.index("<metadata>")
+    fa, fb = pa[:ia - 1], set(pb[:ib - 1])                  # functions (without the trailer)
+    ra, rb = pa[ia + 1:-1], set(pb[ib + 1:-1])              # metadata records (without the tail)
+    missing = [f for f in fa if f not in fb] + [r for r in ra if r not in rb]
+    added = sorted(m.group(1) for f in fb - set(fa) for m in [re.search(r"\t\.(?:protected|globl|weak)\t(\S+)", f)] if m)
+    return missing, added, sha("".join(fa + ra))
+
+
 def sha(s):
     return hashlib.sha256(s.encode()).hexdigest()
 
 
 if __name__ == "__main__":
+    if sys.argv[1] == "--subset":
+        missing, added, h = subset(load(sys.argv[2]), load(sys.argv[3]))
+        if missing:
+            print("DIFFERENT", f"{len(missing)} pieces of the old unit are not in the new one")
+            sys.exit(1)
+        print("subset   ", h, f"(every old function and metadata record is in the new unit; {len(added)} functions added)")
+        for name in added:
+            print("  added:", name)
+        sys.exit(0)
     a, b = load(sys.argv[1]), load(sys.argv[2])
     if a == b:
         print("identical", sha(a))

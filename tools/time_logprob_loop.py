@@ -1,10 +1,14 @@
 """The 228-step decode loop of BASELINE configs[1] (8 clips x 2.56 s, T = 220, top-k 250, temperature 1, cfg 6, un-rounded checkpoint,
 storage "auto") through DecoderEngine.generate_codes, timed with HIP events around 5 batches enqueued back to back (median of
---repeat such regions):    python tools/time_logprob_loop.py [--package-root D] [--repeat R]
+--repeat such regions):    python tools/time_logprob_loop.py [--package-root D] [--repeat R] [--relevance]
 
   plain            return_logprobs=False: the sampler instances without log-probabilities
   logprobs         return_logprobs=True: sample_kernel<PC, LP = true> + the float revert + vaura_sequence_logprob
   candidates 2x4   num_candidates=4 at B = 2 (the same 8 sequences, 16 decoder rows; the condition MLP on 2 clips) with log-probabilities
+  --relevance adds (where the tree has it):
+  relevance        return_relevance=True at cfg 6: the mode-2 sampler + three float reverts, one subtraction, vaura_sequence_logprob
+  both             return_logprobs and return_relevance
+  relevance cfg1   return_relevance=True at cfg 1 next to "plain cfg1": the null rows are carried for the flag alone (twice the rows)
 
 --package-root D imports vaura_amd from D (another build of the library, e.g. the parent commit): modes that tree does not have are
 skipped, so the plain line of two trees can be taken in one session on one card."""
@@ -16,6 +20,7 @@ import sys
 ap = argparse.ArgumentParser()
 ap.add_argument("--package-root", default=os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 ap.add_argument("--repeat", type=int, default=5)
+ap.add_argument("--relevance", action="store_true")
 args = ap.parse_args()
 import torch  # noqa: E402
 sys.path.insert(0, os.path.abspath(args.package_root))
@@ -30,20 +35,23 @@ has_lp = "return_logprobs" in inspect.signature(eng.generate_codes).parameters
 modes = [("plain", 8, {})]
 if has_lp:
     modes += [("logprobs", 8, dict(return_logprobs=True)), ("candidates 2x4", 2, dict(return_logprobs=True, num_candidates=4))]
+if args.relevance and "return_relevance" in inspect.signature(eng.generate_codes).parameters:
+    modes += [("relevance", 8, dict(return_relevance=True)), ("both", 8, dict(return_logprobs=True, return_relevance=True)),
+              ("plain cfg1", 8, dict(cfg_scale=1.0)), ("relevance cfg1", 8, dict(cfg_scale=1.0, return_relevance=True))]
 print(f"tree {os.path.abspath(args.package_root)}: storage {eng.wdtype}, 228 steps per batch, 5 batches per region, {args.repeat} regions")
 s = torch.cuda.Stream(dev)
 with torch.cuda.stream(s):
     for name, clips, extra in modes:
         feats = synth.video_features(clips, seed=0).to(dev)
         for _ in range(2):
-            eng.generate_codes(feats, 220, **kw, **extra)
+            eng.generate_codes(feats, 220, **dict(kw, **extra))
         torch.cuda.synchronize()
         ms = []
         for _ in range(args.repeat):
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             e0.record()
             for _ in range(5):
-                eng.generate_codes(feats, 220, **kw, **extra)
+                eng.generate_codes(feats, 220, **dict(kw, **extra))
             e1.record()
             torch.cuda.synchronize()
             ms.append(e0.elapsed_time(e1) / 5)

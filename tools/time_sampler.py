@@ -5,6 +5,9 @@
                  both as 200 launches of one captured graph
 --logprobs       add the LP column: the same launch through vaura_sample_logprobs (sample_kernel<PC, LP = true>: the token's log-probability
                  kept and stored), eager and, with --per-clip, inside the captured graph
+--relevance      add the mode-2 column: the same launch through vaura_sample_relevance (sample_kernel<PC, true, SampleRelevance>: lp plus the
+                 token's log-probability under the conditional and the null row); the cfg1 line has no null rows and shows none.  With
+                 --package-root of a build without the entry point the column is left out (modes 0 and 1 of that build are the A/B)
 --repeat R       print R lines per mode (run-to-run spread)
 --package-root D import vaura_amd from D instead of this tree (A/B against another build of the library)"""
 import argparse, os, sys
@@ -12,6 +15,7 @@ ap = argparse.ArgumentParser()
 ap.add_argument("--clips", type=int, default=8)
 ap.add_argument("--per-clip", action="store_true")
 ap.add_argument("--logprobs", action="store_true")
+ap.add_argument("--relevance", action="store_true")
 ap.add_argument("--repeat", type=int, default=1)
 ap.add_argument("--package-root", default=os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 args = ap.parse_args()
@@ -25,7 +29,9 @@ B, K, V = args.clips, 9, 1024
 logits = torch.randn(2 * B, K * V, device=dev) * 3
 tokens = torch.zeros(B * K, dtype=torch.int32, device=dev)
 logprobs = torch.zeros(B * K, dtype=torch.float32, device=dev)
-def run(use_sampling, top_k, top_p, cfg, tie_eps=0.0, per_clip=False, graph=False, lp=False):
+lcond, lnull = torch.zeros_like(logprobs), torch.zeros_like(logprobs)
+has_rel = "vaura_sample_relevance" in L.SIGNATURES
+def run(use_sampling, top_k, top_p, cfg, tie_eps=0.0, per_clip=False, graph=False, lp=False, rel=False):
     sp = L.Sampling()
     sp.use_sampling, sp.top_k, sp.temp, sp.top_p, sp.cfg_scale, sp.seed, sp.clip_base, sp.input_is_probs = use_sampling, top_k, 1.0, top_p, cfg, 1, 0, 0
     sp.tie_eps = tie_eps          # near-tie screen (round 6): 0 = off
@@ -37,7 +43,9 @@ def run(use_sampling, top_k, top_p, cfg, tie_eps=0.0, per_clip=False, graph=Fals
         launch = lambda i: lib.vaura_sample_clips(L.ptr(logits), B, K, V, C.byref(sp), L.ptr(rec), None, i, L.ptr(tokens), None, 0, 0, None, L.current_stream(torch.device(dev)))
     if lp:                        # LP = true instances (records or scalars)
         launch = lambda i: lib.vaura_sample_logprobs(L.ptr(logits), B, K, V, C.byref(sp), L.ptr(rec), None, i, L.ptr(tokens), None, 0, 0, None, L.ptr(logprobs), L.current_stream(torch.device(dev)))
-    elif not per_clip:
+    if rel:                       # mode 2 (records or scalars): lp, lc, lu
+        launch = lambda i: lib.vaura_sample_relevance(L.ptr(logits), B, K, V, C.byref(sp), L.ptr(rec), None, i, L.ptr(tokens), None, 0, 0, None, L.ptr(logprobs), L.ptr(lcond), L.ptr(lnull), L.current_stream(torch.device(dev)))
+    elif not lp and not per_clip:
         launch = lambda i: lib.vaura_sample(L.ptr(logits), B, K, V, C.byref(sp), None, i, L.ptr(tokens), L.current_stream(torch.device(dev)))
     s = torch.cuda.Stream()
     if graph:
@@ -80,4 +88,8 @@ for _ in range(args.repeat):
             line += f"; LP (vaura_sample_logprobs): {run(*a, lp=True):.2f}"
             if args.per_clip:
                 line += f", in the graph: scalar {run(*a, graph=True, lp=True):.2f}, per-clip records {run(*a, per_clip=True, graph=True, lp=True):.2f}"
+        if args.relevance and has_rel and a[3] > 1.0:
+            line += f"; relevance (vaura_sample_relevance): {run(*a, rel=True):.2f}"
+            if args.per_clip:
+                line += f", in the graph: scalar {run(*a, graph=True, rel=True):.2f}, per-clip records {run(*a, per_clip=True, graph=True, rel=True):.2f}"
         print(f"[{B} clips] {line}" if (args.clips != 8 or args.per_clip or args.repeat > 1) else line)

@@ -57,8 +57,14 @@ class Decoder(C.Structure):
                 ("ws_logits", C.c_void_p),
                 ("ws_h_split", C.c_void_p), ("ws_attn_split", C.c_void_p), ("ws_ffn_split", C.c_void_p),
                 ("ws_ss", C.c_void_p), ("first_norm", C.c_void_p), ("ws_attn_part", C.c_void_p), ("ws_sync", C.c_void_p),
-                ("has_pattern_delays", C.c_int32), ("pattern_delays", C.c_int32 * 16),
+                ("has_pattern_delays", C.c_int32), ("pattern_delays", C.c_int32 * 16), ("ext_bytes", C.c_int32),
                 ("kscale", C.c_void_p), ("vscale", C.c_void_p), ("clip_sampling", C.c_void_p), ("logprobs", C.c_void_p)]
+
+
+class DecoderExt(C.Structure):
+    """vaura_decoder_ext: the descriptor with the video-relevance pointers behind its last field.  Entry points take ``byref(ext.dec)``
+    (``ext.dec`` is a view of this object's memory); ``dec.ext_bytes`` = 16 tells the library that the two pointers follow."""
+    _fields_ = [("dec", Decoder), ("logprobs_cond", C.c_void_p), ("logprobs_null", C.c_void_p)]
 
 
 class Conv(C.Structure):
@@ -156,6 +162,9 @@ SIGNATURES = {
                                      C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "vaura_sample_logprobs": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(Sampling), C.c_void_p, C.c_void_p, C.c_int64,
                                         C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "vaura_sample_relevance": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(Sampling), C.c_void_p, C.c_void_p, C.c_int64,
+                                         C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                         C.c_void_p]),
     "vaura_pattern_revert_delays_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float,
                                                   C.POINTER(C.c_int32), C.c_void_p]),
     "vaura_sequence_logprob": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int32), C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p,
@@ -171,6 +180,8 @@ SIGNATURES = {
     "vaura_profile_outliers": (None, [C.POINTER(C.c_int64)]),
     "vaura_score": (C.c_int, [C.POINTER(Decoder), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                               C.c_void_p, C.c_void_p]),
+    "vaura_score_relevance": (C.c_int, [C.POINTER(Decoder), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "vaura_score_logits": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
                                      C.c_void_p, C.c_void_p]),
     "vaura_gemv": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
@@ -218,7 +229,7 @@ def lib() -> C.CDLL:
             fn = getattr(handle, name)  # AttributeError if the symbol is not exported
             fn.restype = res
             fn.argtypes = args
-        for which, cls in enumerate([Dims, LayerWeights, Sampling, Decoder, Conv, Codec, CodecEncoder, Vit, VitBlock, ClipSampling]):
+        for which, cls in enumerate([Dims, LayerWeights, Sampling, Decoder, Conv, Codec, CodecEncoder, Vit, VitBlock, ClipSampling, DecoderExt]):
             if C.sizeof(cls) != handle.vaura_struct_size(which):
                 raise VauraHipError(f"{LIB_PATH} was built from a different include/vaura_hip.h: sizeof({cls.__name__}) is "
                                     f"{handle.vaura_struct_size(which)} there, {C.sizeof(cls)} here (rebuild the library)")

@@ -36,6 +36,7 @@ static int check_decoder(const vaura_decoder* d) {
     span = d->pattern_delays[m.n_codebooks - 1] + 1;
   }
   if (d->seq_len != d->timesteps + span) return VAURA_ERR_SHAPE;
+  if (d->ext_bytes != 0 && !va_decoder_ext(d)) return VAURA_ERR_ARG;      // an extension of another size than vaura_decoder_ext's
   return 0;
 }
 
@@ -133,7 +134,13 @@ static int enqueue_prefill_chunk_heads(const vaura_decoder* d, int p0, int n, fl
 // per-clip sampling records of a decoder call (vaura_decoder.clip_sampling): refused with probability rows, and with a clip scale > 1
 // when the descriptor carries no null-condition rows (step.hip va_check_clip_sampling)
 static int check_clips(const vaura_decoder* d, const vaura_sampling* sp, hipStream_t s) {
-  if (d->logprobs && sp && sp->input_is_probs) return VAURA_ERR_ARG;      // probability rows have no log-probability to report (step.hip LP)
+  const vaura_decoder_ext* x = va_decoder_ext(d);
+  float* const lc = x ? x->logprobs_cond : nullptr;
+  float* const lu = x ? x->logprobs_null : nullptr;
+  if ((d->logprobs || lc || lu) && sp && sp->input_is_probs) return VAURA_ERR_ARG;      // probability rows have no log-probability to report (step.hip LP)
+  // video relevance (step.hip mode 2): both buffers or neither, and only with the null-condition rows it reads
+  if (!lc != !lu) return VAURA_ERR_ARG;
+  if (lc && (d->rows != 2 * d->batch || !sp || !(sp->cfg_scale > 1.0f))) return VAURA_ERR_ARG;
   return va_check_clip_sampling(sp, d->clip_sampling, d->batch, d->rows == 2 * d->batch, s);
 }
 
@@ -155,6 +162,8 @@ static VaSampleLaunch sample_launch(const vaura_decoder* d, const vaura_sampling
   a.seq = d->seq; a.T = d->timesteps; a.S = d->seq_len;
   a.delays_host = va_pattern_delays(d);
   a.lp_seq = d->logprobs;
+  if (const vaura_decoder_ext* x = va_decoder_ext(d)) { a.cond_seq = x->logprobs_cond; a.null_seq = x->logprobs_null; }
+  a.null_rows = d->rows == 2 * d->batch;
   return a;
 }
 
@@ -392,6 +401,7 @@ size_t vaura_struct_size(int which) {
     case 7: return sizeof(vaura_vit);
     case 8: return sizeof(vaura_vit_block);
     case 9: return sizeof(vaura_clip_sampling);
+    case 10: return sizeof(vaura_decoder_ext);
     default: return 0;
   }
 }
@@ -531,12 +541,18 @@ int vaura_profile_loop(const vaura_decoder* dec, const vaura_sampling* sp, int n
   return e == hipSuccess ? 0 : (int)e;
 }
 
-int vaura_score(const vaura_decoder* dec, int n_pos, const int32_t* targets, float* ws_chunk_logits, float* logits_out, float* nll,
-                uint8_t* mask_out, float* loss_per_cb, float* loss, vaura_stream_t s) {
+}  // extern "C"
+
+// vaura_score, and with nll_null its twin over the null-condition rows [B, 2B) of a doubled descriptor (vaura_score_relevance): the same
+// prefill, the NLL kernel launched once more per chunk on the logits of those rows, the reduction once more on their nll.
+static int score_rows(const vaura_decoder* dec, int n_pos, const int32_t* targets, float* ws_chunk_logits, float* logits_out, float* nll,
+                      uint8_t* mask_out, float* loss_per_cb, float* loss, float* nll_null, float* loss_per_cb_null, float* loss_null,
+                      vaura_stream_t s) {
   int rc = check_decoder(dec);
   if (rc) return rc;
   if (!targets || !nll || !loss_per_cb || !loss || n_pos <= 0) return VAURA_ERR_ARG;
-  if (dec->rows != dec->batch) return VAURA_ERR_ARG;                              // no CFG branch: the reference scores B rows
+  if (nll_null && (!loss_per_cb_null || !loss_null)) return VAURA_ERR_ARG;
+  if (dec->rows != (nll_null ? 2 : 1) * dec->batch) return VAURA_ERR_ARG;         // no CFG branch: the reference scores B rows
   if (n_pos > dec->seq_len - 1 || n_pos > dec->max_len) return VAURA_ERR_ARG;
   const vaura_dims& m = dec->dims;
   const int B = dec->batch, K = m.n_codebooks, V = m.vocab, Ta = dec->timesteps;
@@ -552,6 +568,8 @@ int vaura_score(const vaura_decoder* dec, int n_pos, const int32_t* targets, flo
       if (rc) return rc;
       rc = va_launch_score_nll(ws_chunk_logits, rp, p0, n, B, K, V, Ta, delays, targets, nll, logits_out, st);
       if (rc) return rc;
+      if (nll_null) rc = va_launch_score_nll(ws_chunk_logits + (size_t)B * K * V, rp, p0, n, B, K, V, Ta, delays, targets, nll_null, nullptr, st);
+      if (rc) return rc;
     }
     rc = va_launch_advance(dec->state, n_pos, st);
     if (rc) return rc;
@@ -562,15 +580,35 @@ int vaura_score(const vaura_decoder* dec, int n_pos, const int32_t* targets, flo
     vaura_sampling sp = {};
     vaura_decoder plain = *dec;
     plain.logprobs = nullptr;             // ... and reports no token log-probabilities
+    plain.ext_bytes = 0;                  // (a copy of the descriptor alone: nothing follows it)
     plain.clip_sampling = nullptr;        // scoring has no sampling parameters, per clip or otherwise
     for (int p = 0; p < n_pos; ++p) {
       rc = enqueue_step(&plain, &sp, 1, st);
       if (rc) return rc;
       rc = va_launch_score_nll(dec->ws_logits, dec->rows, p, 1, B, K, V, Ta, delays, targets, nll, logits_out, st);
       if (rc) return rc;
+      if (nll_null) rc = va_launch_score_nll(dec->ws_logits + (size_t)B * K * V, dec->rows, p, 1, B, K, V, Ta, delays, targets, nll_null, nullptr, st);
+      if (rc) return rc;
     }
   }
-  return va_launch_score_reduce(nll, mask_out, logits_out, B, K, V, Ta, n_pos, delays, loss_per_cb, loss, st);
+  rc = va_launch_score_reduce(nll, mask_out, logits_out, B, K, V, Ta, n_pos, delays, loss_per_cb, loss, st);
+  if (rc || !nll_null) return rc;
+  return va_launch_score_reduce(nll_null, nullptr, nullptr, B, K, V, Ta, n_pos, delays, loss_per_cb_null, loss_null, st);
+}
+
+extern "C" {
+
+int vaura_score(const vaura_decoder* dec, int n_pos, const int32_t* targets, float* ws_chunk_logits, float* logits_out, float* nll,
+                uint8_t* mask_out, float* loss_per_cb, float* loss, vaura_stream_t s) {
+  return score_rows(dec, n_pos, targets, ws_chunk_logits, logits_out, nll, mask_out, loss_per_cb, loss, nullptr, nullptr, nullptr, s);
+}
+
+int vaura_score_relevance(const vaura_decoder* dec, int n_pos, const int32_t* targets, float* ws_chunk_logits, float* logits_out, float* nll,
+                          uint8_t* mask_out, float* loss_per_cb, float* loss, float* nll_null, float* loss_per_cb_null, float* loss_null,
+                          vaura_stream_t s) {
+  if (!nll_null) return VAURA_ERR_ARG;
+  return score_rows(dec, n_pos, targets, ws_chunk_logits, logits_out, nll, mask_out, loss_per_cb, loss, nll_null, loss_per_cb_null,
+                    loss_null, s);
 }
 
 void vaura_profile_outliers(int64_t* per_kind) {

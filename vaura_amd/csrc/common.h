@@ -261,6 +261,10 @@ int va_launch_attn_wo(const float* qkv, const float* qkv2, const float* rope, co
 int va_launch_tail_engine(const Gemv3Args& awo, const Gemv3Args& a13, const Gemv3Args& a2, uint32_t* flags, int32_t* state, int layer,
                           hipStream_t s);
 int va_launch_embed(const vaura_decoder* d, int pos_host, int n_pos, hipStream_t s);
+// the relevance pointers behind a descriptor (vaura_decoder_ext), or NULL when the caller passed a plain vaura_decoder
+inline const vaura_decoder_ext* va_decoder_ext(const vaura_decoder* d) {
+  return d->ext_bytes == (int32_t)(sizeof(vaura_decoder_ext) - sizeof(vaura_decoder)) ? reinterpret_cast<const vaura_decoder_ext*>(d) : nullptr;
+}
 struct VaSampleLaunch {              // one sampler launch over (B, K) rows of logits
   const float* logits = nullptr;
   int B = 0, K = 0, vocab = 0;
@@ -273,6 +277,10 @@ struct VaSampleLaunch {              // one sampler launch over (B, K) rows of l
   int T = 0, S = 0;
   const int32_t* delays_host = nullptr;   // K delays, NULL = the default d_k = k
   float *lp_out = nullptr, *lp_seq = nullptr;     // (B, K) / (B, K, S); either non-NULL selects the LP instances
+  // video relevance (mode 2 of step.hip's sampler): lc / lu of the chosen token, (B, K) and / or (B, K, S).  Any of them selects the
+  // mode-2 instances; both values are needed, and null_rows = "logits has rows [B, 2B)" (VAURA_ERR_ARG otherwise, before the launch)
+  float *cond_out = nullptr, *cond_seq = nullptr, *null_out = nullptr, *null_seq = nullptr;
+  bool null_rows = false;
 };
 int va_launch_sample(const VaSampleLaunch& a, hipStream_t s);
 int va_check_clip_sampling(const vaura_sampling* sp, const vaura_clip_sampling* clips, int B, bool doubled, hipStream_t s);

@@ -206,17 +206,51 @@ __device__ __forceinline__ int block_count(int v, int* si) {
 // stores the value next to the token.  LP = false compiles all of it out: those two instances are the kernels they were.
 // The two output pointers travel as a trailing parameter PACK that is empty when LP = false: those instances keep the argument list, and
 // with it the kernel-argument offsets, of the kernels they were (an extra pointer would move the hidden arguments behind it).
+// The reporting MODE of an instance: 0 = none (LP = false, empty pack), 1 = the log-probability (LP = true, pack = SampleLogprobs), 2 = that
+// plus the video relevance of the token (LP = true, pack = SampleRelevance; vaura_decoder_ext.logprobs_cond / logprobs_null,
+// vaura_sample_relevance).  Mode 2 is told by the TYPE of the pack, not by a third template value: the four instances of modes 0 and 1
+// keep their symbols, argument lists and instruction streams.  Mode 2 needs the null-condition rows [B, 2B) (refused on the host
+// otherwise) and reports, for the token the workgroup chose, its log-probability under the model's two distributions, tau = 1:
+//     lc = (x_c[tok] - max x_c) - logf(sum expf(x_c - max x_c))      x_c: the conditional row of (clip, codebook), as the mix reads it
+//     lu = (x_u[tok] - max x_u) - logf(sum expf(x_u - max x_u))      x_u: the null row of the same prefix
+// over the FULL vocabulary, no temperature, no top-k / top-p cut: a property of the model, not of the sampling settings.  Reduction
+// order, per row, that of the mode-1 greedy branch: thread t takes the maximum of its candidates 4t .. 4t+3, block max (wave_max, then
+// the four waves fmaxf(fmaxf(w0, w1), fmaxf(w2, w3))); thread t adds (e0 + e1) + (e2 + e3) of e_j = expf(x_j - max), block sum (wave_sum,
+// then ((w0 + w1) + w2) + w3).  The two rows share each barrier pair (block_max2 / block_sum2: the same arithmetic).  A clip whose own
+// scale is <= 1 still skips the mix for its token; its null row is read for lu only.  The thread that owns the token's column stores
+// both values with ordinary vector stores, where — and only where — lp is stored.  NaN in both when either row (or their mix) holds a
+// non-finite value; the status bit is raised for that as well (a null row the un-mixed draw never read is no draw error, but the
+// values are not to be used).  The token never depends on the mode: everything of mode 2 happens after the draw.
 typedef int32_t i32x4 __attribute__((ext_vector_type(4)));
 struct SampleLogprobs {
   float* out;   // (B, K) next to tokens_out, or null
   float* seq;   // (B, K, S) in the layout of seq, or null
 };
+struct SampleRelevance {
+  float* out;   // as SampleLogprobs
+  float* seq;
+  float* cond_out;   // lc: (B, K) or null
+  float* cond_seq;   // lc: (B, K, S) in the layout of seq, or null
+  float* null_out;   // lu: (B, K) or null
+  float* null_seq;   // lu: (B, K, S) or null
+};
 template <typename T, typename... R>
 __device__ __forceinline__ T va_first(T t, R...) { return t; }
+// two sums with ONE barrier pair (block_sum's order for each)
+__device__ __forceinline__ void block_sum2(float& a, float& b, float* sv) {
+  a = wave_sum(a);
+  b = wave_sum(b);
+  __syncthreads();
+  if ((threadIdx.x & 63) == 0) { sv[threadIdx.x >> 6] = a; sv[4 + (threadIdx.x >> 6)] = b; }
+  __syncthreads();
+  a = ((sv[0] + sv[1]) + sv[2]) + sv[3];
+  b = ((sv[4] + sv[5]) + sv[6]) + sv[7];
+}
 template <bool PC, bool LP, typename... LpArgs>
 __global__ __launch_bounds__(SMP_THREADS) void sample_kernel(const float* __restrict__ logits_q, const int32_t* __restrict__ state_q,
                                                              SampleArgs a, const int32_t* __restrict__ clips, LpArgs... lp_args) {
-  static_assert(sizeof...(LpArgs) == (LP ? 1 : 0), "LP instances take one SampleLogprobs, the others nothing");
+  static_assert(sizeof...(LpArgs) == (LP ? 1 : 0), "LP instances take one SampleLogprobs / SampleRelevance, the others nothing");
+  constexpr bool REL = (std::is_same<LpArgs, SampleRelevance>::value || ...);      // mode 2
   [[maybe_unused]] float* lp_out = nullptr;
   [[maybe_unused]] float* lp_seq = nullptr;
   if constexpr (LP) { lp_out = va_first(lp_args...).out; lp_seq = va_first(lp_args...).seq; }
@@ -548,6 +582,47 @@ __global__ __launch_bounds__(SMP_THREADS) void sample_kernel(const float* __rest
     for (int j = 1; j < 4; ++j) if ((token & 3) == j) xt = x[j];
     lp = lp_bad ? __builtin_nanf("") : (xt - lp_mx) - logf(lp_den);
   }
+  if constexpr (REL) {
+    // Mode 2, whole and apart (the instances of modes 0 and 1 see none of it): after the draw, before the fix-up below writes the slot.
+    // The null row is read here whatever this clip's scale (the host guarantees rows [B, 2B)).
+    const SampleRelevance r = va_first(lp_args...);
+    const f32x4 un = *reinterpret_cast<const f32x4*>(a.logits + ((size_t)(a.B + b) * a.K + k) * V + 4 * tid);
+    const float c[4] = {lc[0], lc[1], lc[2], lc[3]}, u[4] = {un[0], un[1], un[2], un[3]};
+    bool mine = false;               // a non-finite value among this thread's eight: it poisons both sums below (no reduction of its own)
+#pragma unroll
+    for (int j = 0; j < 4; ++j) if (!(fabsf(c[j]) < INFINITY && fabsf(u[j]) < INFINITY)) mine = true;
+    float mc = fmaxf(fmaxf(c[0], c[1]), fmaxf(c[2], c[3])), mu = fmaxf(fmaxf(u[0], u[1]), fmaxf(u[2], u[3]));
+    block_max2(mc, mu, sv);
+    float ec[4], eu[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) { ec[j] = expf(c[j] - mc); eu[j] = expf(u[j] - mu); }
+    float dc = (ec[0] + ec[1]) + (ec[2] + ec[3]), du = (eu[0] + eu[1]) + (eu[2] + eu[3]);
+    if (mine) dc = du = __builtin_nanf("");
+    block_sum2(dc, du, sv);
+    const bool bad = lp_bad || dc != dc;      // block-uniform: the row's own status (mixed logits), or a NaN that reached the sums
+    if (tid == (token >> 2)) {       // the thread that holds the token's two logits
+      float ct = c[0], ut = u[0];
+#pragma unroll
+      for (int j = 1; j < 4; ++j) if ((token & 3) == j) { ct = c[j]; ut = u[j]; }
+      const float rel_c = bad ? __builtin_nanf("") : (ct - mc) - logf(dc);
+      const float rel_n = bad ? __builtin_nanf("") : (ut - mu) - logf(du);
+      if (r.cond_out) r.cond_out[b * a.K + k] = rel_c;
+      if (r.null_out) r.null_out[b * a.K + k] = rel_n;
+      if (bad && a.state_rw) __hip_atomic_fetch_or(&a.state_rw[4], VAURA_STATUS_NONFINITE_LOGITS, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      if (a.seq && (r.cond_seq || r.null_seq)) {
+        // the fix-up's own rule, evaluated by the thread that applies it next: a sampled token only (a valid slot that still holds -1)
+        int dk = k;
+#pragma unroll
+        for (int j = 0; j < 16; ++j) if (j == k) dk = a.delays[j];
+        const int offset = pos + 1, t = offset - 1 - dk;
+        const size_t slot = ((size_t)b * a.K + k) * a.S + offset;
+        if (offset < a.S && t >= 0 && t < a.T && a.seq[slot] == -1) {
+          if (r.cond_seq) r.cond_seq[slot] = rel_c;
+          if (r.null_seq) r.null_seq[slot] = rel_n;
+        }
+      }
+    }
+  }
   const int writer = LP ? (token >> 2) : 0;      // LP: the thread that holds the token's logit
   if (tid == writer) {
     if (a.tokens_out) a.tokens_out[b * a.K + k] = token;
@@ -617,8 +692,11 @@ int va_launch_sample(const VaSampleLaunch& l, hipStream_t s) {
   const int B = l.B, K = l.K;
   if (!l.logits || !sp || B <= 0 || K <= 0) return VAURA_ERR_ARG;
   if (l.clips && sp->input_is_probs) return VAURA_ERR_ARG;
-  const bool lp = l.lp_out || l.lp_seq;
+  const bool rel = l.cond_out || l.cond_seq || l.null_out || l.null_seq;
+  const bool lp = l.lp_out || l.lp_seq || rel;
   if (lp && sp->input_is_probs) return VAURA_ERR_ARG;        // rows that already are probabilities: no log-probability to report
+  // mode 2 reads rows [B, 2B) for every clip: both values or neither, and only when the call states that those rows exist
+  if (rel && (!(l.cond_out || l.cond_seq) || !(l.null_out || l.null_seq) || !l.null_rows || !(sp->cfg_scale > 1.0f))) return VAURA_ERR_ARG;
   if (l.vocab != 1024) return VAURA_ERR_SHAPE;
   if (l.delays_host && K > 16) return VAURA_ERR_ARG;
   SampleArgs a;
@@ -633,6 +711,13 @@ int va_launch_sample(const VaSampleLaunch& l, hipStream_t s) {
   // (named outside the macro: the commas of the template arguments would split its argument list)
   const auto k_plain = sample_kernel<false, false>, k_pc = sample_kernel<true, false>;
   const auto k_lp = sample_kernel<false, true, SampleLogprobs>, k_pc_lp = sample_kernel<true, true, SampleLogprobs>;
+  if (rel) {
+    const auto k_rel = sample_kernel<false, true, SampleRelevance>, k_pc_rel = sample_kernel<true, true, SampleRelevance>;
+    const SampleRelevance r{l.lp_out, l.lp_seq, l.cond_out, l.cond_seq, l.null_out, l.null_seq};
+    if (l.clips) VA_LAUNCH(k_pc_rel, dim3(K, B), dim3(SMP_THREADS), 0, s, a.logits, a.state, a, rec, r);
+    else VA_LAUNCH(k_rel, dim3(K, B), dim3(SMP_THREADS), 0, s, a.logits, a.state, a, rec, r);
+    return 0;
+  }
   if (lp) {
     if (l.clips) VA_LAUNCH(k_pc_lp, dim3(K, B), dim3(SMP_THREADS), 0, s, a.logits, a.state, a, rec, SampleLogprobs{l.lp_out, l.lp_seq});
     else VA_LAUNCH(k_lp, dim3(K, B), dim3(SMP_THREADS), 0, s, a.logits, a.state, a, rec, SampleLogprobs{l.lp_out, l.lp_seq});
@@ -832,6 +917,24 @@ int vaura_sample_logprobs(const float* logits, int B, int K, int vocab, const va
   a.tokens_out = tokens_out; a.seq = seq; a.T = T; a.S = S;
   a.state = seq ? state : nullptr;      // the standalone form keeps no state, like vaura_sample
   a.lp_out = logprobs_out;
+  return va_launch_sample(a, as_stream(s));
+}
+
+int vaura_sample_relevance(const float* logits, int B, int K, int vocab, const vaura_sampling* sp, const vaura_clip_sampling* clips,
+                           const float* noise, int64_t step, int32_t* tokens_out, int32_t* seq, int T, int S, int32_t* state,
+                           float* logprobs_out, float* cond_out, float* null_out, vaura_stream_t s) {
+  if (!logits || !sp || !cond_out || !null_out || (!tokens_out && !seq) || B <= 0 || K <= 0) return VAURA_ERR_ARG;
+  if (seq && (!state || T <= 0 || S <= 0)) return VAURA_ERR_ARG;
+  if (sp->input_is_probs) return VAURA_ERR_ARG;
+  if (!(sp->cfg_scale > 1.0f)) return VAURA_ERR_ARG;      // no null-condition rows: nothing to compare the conditional row with
+  const int rc = va_check_clip_sampling(sp, clips, B, true, as_stream(s));
+  if (rc) return rc;
+  VaSampleLaunch a;
+  a.logits = logits; a.B = B; a.K = K; a.vocab = vocab; a.sp = sp; a.clips = clips; a.noise = noise; a.step_host = step;
+  a.tokens_out = tokens_out; a.seq = seq; a.T = T; a.S = S;
+  a.state = seq ? state : nullptr;      // the standalone form keeps no state, like vaura_sample
+  a.lp_out = logprobs_out;              // optional here: NULL = lc and lu only
+  a.cond_out = cond_out; a.null_out = null_out; a.null_rows = true;
   return va_launch_sample(a, as_stream(s));
 }
 

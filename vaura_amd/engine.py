@@ -358,7 +358,10 @@ class DecoderEngine:
             self.codes_i32 = torch.zeros(batch, K, timesteps, dtype=torch.int32, device=self.dev)
             self.clip_params = torch.zeros(batch, 8, dtype=torch.int32, device=self.dev)   # vaura_clip_sampling records (per-clip calls)
             self.logprobs = torch.zeros(batch, K, S, **f32)     # token log-probabilities in the layout of seq (return_logprobs calls)
-        d = L.Decoder()
+            self.logprobs_cond = self.logprobs_null = None      # video relevance (return_relevance calls): allocated by the first such call
+        self.dec_ext = L.DecoderExt()      # the descriptor + the relevance pointers behind it (both NULL: the descriptor alone)
+        d = self.dec_ext.dec               # a view: byref(self.dec) points into dec_ext
+        d.ext_bytes = C.sizeof(L.DecoderExt) - C.sizeof(L.Decoder)
         d.dims = self.dims
         d.dims.tokens_per_frame = tokens_per_frame
         d.wdtype, d.batch, d.rows, d.max_len = self.wd, batch, rows, max_len
@@ -508,7 +511,8 @@ class DecoderEngine:
             st = L.current_stream(self.dev)
             if use_graph:
                 # per-clip calls: the record POINTER and the canonical struct of _sampling() — "per-clip + row doubling", never the values
-                key = (self._shape, L.ptr(noise), bytes(sp), int(self.dec.clip_sampling or 0), int(self.dec.logprobs or 0))
+                key = (self._shape, L.ptr(noise), bytes(sp), int(self.dec.clip_sampling or 0), int(self.dec.logprobs or 0),
+                       int(self.dec_ext.logprobs_cond or 0), int(self.dec_ext.logprobs_null or 0))
                 if self._graph_key != key:       # the captured step is tied to these buffers / parameters
                     self._free_graph()
                     handle = C.c_void_p()
@@ -613,7 +617,8 @@ class DecoderEngine:
     @torch.no_grad()
     def generate_codes(self, feats: torch.Tensor, max_new_tokens: int, *, prompt: Optional[torch.Tensor] = None,
                        use_sampling=False, temp=1.0, top_k=0, top_p=0.0, cfg_scale=1.0, noise=None, seed=0,
-                       clip_base=0, use_graph=True, tokens_per_frame=7, delays=None, return_logprobs=False, num_candidates=1):
+                       clip_base=0, use_graph=True, tokens_per_frame=7, delays=None, return_logprobs=False, num_candidates=1,
+                       return_relevance=False):
         """The hot loop of generate(): (B, Tv, 768) -> codes (B, K, T) int64 (device).  ``delays``: the codebook delay pattern
         (codebook_patterns.py:374-419; None = 0..K-1, ParallelPatternProvider = all zeros): S = T + max(d) + 1 sequence steps, the
         loop samples steps Tp + 1 + d_0 .. S - 1, and an explicit ``noise`` has S - (Tp + 1 + d_0) steps.
@@ -627,7 +632,14 @@ class DecoderEngine:
         log-probability of every sampled token under the distribution its decision was made from (include/vaura_hip.h
         ``vaura_decoder.logprobs``; prompt frames hold 0), its mean over the generated frames per codebook, and the mean of those over
         the codebooks (``vaura_sequence_logprob``: fixed order, a NaN anywhere makes the clip's scores NaN).  The tokens are the ones
-        the call returns without it."""
+        the call returns without it.
+        ``return_relevance``: the dict (returned as with ``return_logprobs``; both flags give one dict) gains the video relevance of
+        every sampled token, r = log p(token | prefix, video) - log p(token | prefix, null video), both at temperature 1 over the full
+        vocabulary (include/vaura_hip.h ``vaura_decoder_ext.logprobs_cond``): "logprob_cond", "logprob_null", "relevance" (B * N, K, T)
+        (0 in prompt frames), "relevance_per_codebook" (B * N, K) and "sequence_relevance" (B * N,), the fixed-order means of
+        ``vaura_sequence_logprob`` applied to r.  It needs the null-condition rows: when no clip's ``cfg_scale`` exceeds 1 the engine
+        prepares the doubled batch anyway and draws every clip un-mixed through the per-clip records (its own scale, <= 1) — the tokens
+        are those of the call without the flag, but such a call streams TWICE the rows through the decode step."""
         B, Tv, _ = feats.shape
         N = num_candidates
         if isinstance(N, bool) or not isinstance(N, int) or N < 1:
@@ -638,6 +650,12 @@ class DecoderEngine:
             use_sampling, temp, top_k, top_p, cfg_scale = (clip_params.repeat(v, N) for v in (use_sampling, temp, top_k, top_p, cfg_scale))
             if prompt is not None:
                 prompt = prompt.repeat_interleave(N, dim=0)
+        if return_relevance and not cfg_on:
+            # relevance reads the null rows: carry them, and keep every clip un-mixed through its record (the scalar cfg_scale of the
+            # call's vaura_sampling then only says that the rows exist)
+            cfg_on = True
+            if not clip_params.is_per_clip(cfg_scale):
+                cfg_scale = [float(clip_params._scalar(cfg_scale))] * (B * N)
         K = self.cfg.num_codebooks
         self._fc = None                       # the K/V cache is about to be reused: forward_cached must start over
         with off_null_stream(self.dev) as caller:
@@ -652,27 +670,56 @@ class DecoderEngine:
             if return_logprobs:
                 self.logprobs.zero_()         # slots the sampler does not fill (prompt, special) read 0
             self.dec.logprobs = L.ptr(self.logprobs) if return_logprobs else 0
+            if return_relevance:
+                if self.logprobs_cond is None:
+                    self.logprobs_cond, self.logprobs_null = torch.zeros_like(self.logprobs), torch.zeros_like(self.logprobs)
+                else:
+                    self.logprobs_cond.zero_()
+                    self.logprobs_null.zero_()
+            self.dec_ext.logprobs_cond = L.ptr(self.logprobs_cond) if return_relevance else 0
+            self.dec_ext.logprobs_null = L.ptr(self.logprobs_null) if return_relevance else 0
             self.run(start - 1, self.S - start, sp, noise, use_graph)
             out = self.revert().to(torch.int64)
             extra = self._sequence_logprobs(Tp) if return_logprobs else None
+            if return_relevance:
+                extra = dict(extra or {}, **self._sequence_relevance(Tp))
         if caller is not None:
             out.record_stream(caller)
             for t in (extra or {}).values():
                 t.record_stream(caller)
-        return (out, extra) if return_logprobs else out
+        return (out, extra) if (return_logprobs or return_relevance) else out
+
+    def _revert_f32(self, buf: torch.Tensor) -> torch.Tensor:
+        """fp32 values in the layout of seq -> (batch, K, T), 0 where the sequence holds no frame."""
+        K, T, Bn = self.cfg.num_codebooks, self.T, self.batch
+        out = torch.empty(Bn, K, T, dtype=torch.float32, device=self.dev)
+        dl = L.delays_host(self.delays) if self.delays is not None else None
+        L.check(self.lib.vaura_pattern_revert_delays_f32(L.ptr(buf), L.ptr(out), Bn, K, T, self.S, 0.0, dl, L.current_stream(self.dev)),
+                "vaura_pattern_revert_delays_f32")
+        return out
+
+    def _sequence_means(self, buf: torch.Tensor, Tp: int):
+        """Fixed-order means of values in the layout of seq over frames Tp .. T - 1 -> (per codebook (batch, K), per clip (batch,))."""
+        K, T, Bn = self.cfg.num_codebooks, self.T, self.batch
+        f32 = dict(dtype=torch.float32, device=self.dev)
+        pcb, score = torch.empty(Bn, K, **f32), torch.empty(Bn, **f32)
+        dl = L.delays_host(self.delays) if self.delays is not None else None
+        L.check(self.lib.vaura_sequence_logprob(L.ptr(buf), self.S, dl, Bn, K, T, Tp, L.ptr(pcb), L.ptr(score), L.current_stream(self.dev)),
+                "vaura_sequence_logprob")
+        return pcb, score
 
     def _sequence_logprobs(self, Tp: int) -> Dict[str, torch.Tensor]:
         """The finished call's log-probabilities, reverted to (batch, K, T), and their fixed-order means over frames Tp .. T - 1."""
-        K, T, Bn = self.cfg.num_codebooks, self.T, self.batch
-        f32 = dict(dtype=torch.float32, device=self.dev)
-        lp, pcb, score = torch.empty(Bn, K, T, **f32), torch.empty(Bn, K, **f32), torch.empty(Bn, **f32)
-        dl = L.delays_host(self.delays) if self.delays is not None else None
-        st = L.current_stream(self.dev)
-        L.check(self.lib.vaura_pattern_revert_delays_f32(L.ptr(self.logprobs), L.ptr(lp), Bn, K, T, self.S, 0.0, dl, st),
-                "vaura_pattern_revert_delays_f32")
-        L.check(self.lib.vaura_sequence_logprob(L.ptr(self.logprobs), self.S, dl, Bn, K, T, Tp, L.ptr(pcb), L.ptr(score), st),
-                "vaura_sequence_logprob")
-        return {"logprobs": lp, "per_codebook": pcb, "score": score}
+        pcb, score = self._sequence_means(self.logprobs, Tp)
+        return {"logprobs": self._revert_f32(self.logprobs), "per_codebook": pcb, "score": score}
+
+    def _sequence_relevance(self, Tp: int) -> Dict[str, torch.Tensor]:
+        """The finished call's relevance r = lc - lu (one fp32 subtraction per slot, in the layout of seq: 0 - 0 where nothing was
+        sampled), the three reverted to (batch, K, T), and the fixed-order means of r (the log-probability's reduction kernel)."""
+        r = self.logprobs_cond - self.logprobs_null
+        pcb, score = self._sequence_means(r, Tp)
+        return {"relevance": self._revert_f32(r), "logprob_cond": self._revert_f32(self.logprobs_cond),
+                "logprob_null": self._revert_f32(self.logprobs_null), "relevance_per_codebook": pcb, "sequence_relevance": score}
 
     @torch.no_grad()
     def generate_codes_checked(self, feats: torch.Tensor, max_new_tokens: int, **kw):
@@ -812,7 +859,7 @@ class DecoderEngine:
 
     @torch.no_grad()
     def score(self, codes: torch.Tensor, feats: torch.Tensor, *, delays: Optional[Sequence[int]] = None, tokens_per_frame: int = 7,
-              return_logits: bool = False, checked: bool = True) -> Dict[str, torch.Tensor]:
+              return_logits: bool = False, checked: bool = True, relevance: bool = False) -> Dict[str, torch.Tensor]:
         """Teacher-forced cross-entropy of ``codes`` (B, K, Ta) under ``feats`` (B, Tv, 768): the reference's ``forward`` +
         ``_compute_loss`` (vaura_model.py:136-192, 240-280).  The input is ``build_pattern_sequence(codes[..., :-1])`` against a pattern
         of Ta timesteps (special token = vocab), S = Ta + max(d) + 1 (``delays`` None = 0..K-1); positions [0, S - 1) run without a CFG
@@ -820,7 +867,13 @@ class DecoderEngine:
         position on "f32"), then the fused revert + log-softmax + NLL kernel and the fixed-order per-codebook mean (csrc/score.hip).
         Returns {"loss": (), "loss_per_codebook": (K,), "nll": (B, K, Ta), "mask": (B, K, Ta) bool, and with ``return_logits`` "logits":
         the reverted (B, K, Ta, vocab)}.  ``checked``: range safety as ``generate_codes_checked`` — a non-finite loss or a dirty status
-        word re-runs the call on the exact-fp32 twin (one warning per engine)."""
+        word re-runs the call on the exact-fp32 twin (one warning per engine).
+        ``relevance``: the codes are prefilled under the video AND under the null condition (rows [B, 2B), the layout CFG uses: twice
+        the rows in one pass), the NLL kernel and the reduction run on both row sets (``vaura_score_relevance``), and the result gains
+        "nll_null" (B, K, Ta), "loss_null" / "loss_null_per_codebook", "nll_per_codebook" and "nll_null_per_codebook" (B, K) — the mean
+        over the timesteps per clip and codebook, in the fixed order of ``vaura_sequence_logprob`` —, "relevance_per_codebook" (B, K)
+        = nll_null_per_codebook - nll_per_codebook (how many nats per token the video explains) and "relevance" (B,), its mean over
+        the codebooks.  Today's entries are the bits of the call without the flag."""
         c = self.cfg
         if codes.dim() != 3 or codes.shape[1] != c.num_codebooks:
             raise L.VauraHipError(f"codes must be (B, {c.num_codebooks}, Ta), got {tuple(codes.shape)}")
@@ -840,7 +893,7 @@ class DecoderEngine:
         targets = codes_d.to(torch.int32).contiguous()
         self._fc = None                    # the K/V cache is about to be reused: forward_cached must start over
         with off_null_stream(self.dev) as caller:
-            self.prepare(B, Ta, feats.shape[1], False, tokens_per_frame, block_size=c.block_size, delays=dl)
+            self.prepare(B, Ta, feats.shape[1], bool(relevance), tokens_per_frame, block_size=c.block_size, delays=dl)
             self.set_condition(feats)
             self.codes_i32[..., :Ta - 1] = targets[..., :Ta - 1]
             self.codes_i32[..., Ta - 1] = c.d_codebook             # build_pattern_sequence(codes[..., :-1]): no input beyond Ta - 2
@@ -858,11 +911,22 @@ class DecoderEngine:
             lpc = torch.empty(K, **f32)
             loss = torch.empty((), **f32)
             logits = torch.empty(B, K, Ta, c.d_codebook, **f32) if return_logits else None
-            L.check(self.lib.vaura_score(C.byref(self.dec), self.S - 1, L.ptr(targets), L.ptr(self._score_workspace()), L.ptr(logits),
-                                         L.ptr(nll), L.ptr(mask), L.ptr(lpc), L.ptr(loss), L.current_stream(self.dev)), "vaura_score")
+            if relevance:
+                nll0, lpc0, loss0 = torch.empty(B, K, Ta, **f32), torch.empty(K, **f32), torch.empty((), **f32)
+                L.check(self.lib.vaura_score_relevance(C.byref(self.dec), self.S - 1, L.ptr(targets), L.ptr(self._score_workspace()),
+                                                       L.ptr(logits), L.ptr(nll), L.ptr(mask), L.ptr(lpc), L.ptr(loss), L.ptr(nll0),
+                                                       L.ptr(lpc0), L.ptr(loss0), L.current_stream(self.dev)), "vaura_score_relevance")
+            else:
+                L.check(self.lib.vaura_score(C.byref(self.dec), self.S - 1, L.ptr(targets), L.ptr(self._score_workspace()), L.ptr(logits),
+                                             L.ptr(nll), L.ptr(mask), L.ptr(lpc), L.ptr(loss), L.current_stream(self.dev)), "vaura_score")
             out = {"loss": loss, "loss_per_codebook": lpc, "nll": nll, "mask": mask.bool()}
             if return_logits:
                 out["logits"] = logits
+            if relevance:
+                pcb, pcb0 = self._clip_codebook_means(nll), self._clip_codebook_means(nll0)
+                rpc = pcb0 - pcb
+                out.update({"nll_null": nll0, "loss_null": loss0, "loss_null_per_codebook": lpc0, "nll_per_codebook": pcb,
+                            "nll_null_per_codebook": pcb0, "relevance_per_codebook": rpc, "relevance": rpc.sum(-1) / K})
         if caller is not None:
             for t in out.values():
                 t.record_stream(caller)
@@ -882,8 +946,20 @@ class DecoderEngine:
                 warnings.warn("vaura_amd: teacher-forced scoring gave a non-finite loss (an activation left the fp16-plane range); this "
                               "call is re-run on the exact-fp32 twin engine (slower, ~2.7 GB more)")
             self.range_fallbacks += 1
-            return self._twin().score(codes, feats, delays=delays, tokens_per_frame=tokens_per_frame, return_logits=return_logits)
+            return self._twin().score(codes, feats, delays=delays, tokens_per_frame=tokens_per_frame, return_logits=return_logits,
+                                      relevance=relevance)
         return out
+
+    def _clip_codebook_means(self, nll: torch.Tensor) -> torch.Tensor:
+        """(B, K, Ta) -> (B, K): the mean over the timesteps of every (clip, codebook), by the fixed-order reduction of the token
+        log-probabilities (``vaura_sequence_logprob``) — the tensor read as a pattern layout of zero delays, one unused leading step."""
+        B, K, Ta = nll.shape
+        lay = torch.zeros(B, K, Ta + 1, dtype=torch.float32, device=self.dev)
+        lay[..., 1:] = nll
+        pcb, clip = torch.empty(B, K, dtype=torch.float32, device=self.dev), torch.empty(B, dtype=torch.float32, device=self.dev)
+        L.check(self.lib.vaura_sequence_logprob(L.ptr(lay), Ta + 1, L.delays_host([0] * K), B, K, Ta, 0, L.ptr(pcb), L.ptr(clip),
+                                                L.current_stream(self.dev)), "vaura_sequence_logprob")
+        return pcb
 
 
 @torch.no_grad()

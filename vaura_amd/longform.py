@@ -44,11 +44,16 @@ def chunk_schedule(duration: float, model_max_duration: float = 2.56, stride: fl
 @torch.no_grad()
 def generate_long(model, frames: torch.Tensor, duration: float, *, stride: float = 0.64, model_max_duration: Optional[float] = None,
                   vfps: float = 25, frame_step: int = 1, clip_indices=None, use_sampling: bool = True, temp: float = 1.0,
-                  top_k: int = 128, top_p: float = 0.0, cfg_scale: float = 1.0) -> dict:
+                  top_k: int = 128, top_p: float = 0.0, cfg_scale: float = 1.0, return_relevance: bool = False) -> dict:
     """frames: whatever the feature-extractor plugin accepts, segments on dim 1 — raw (B, S, C, T, H, W) or, with the
     pass-through ``MotionFormer``, features (B, S, t, 768).  Returns {"generated_audio", "sampled_indices"}.
     ``use_sampling``, ``temp``, ``top_k``, ``top_p``, ``cfg_scale``: scalars, or one value per clip (length-B list / tuple / 1-D
-    tensor) — every chunk of clip b is sampled with clip b's values (``VAURAModel.generate_tokens``)."""
+    tensor) — every chunk of clip b is sampled with clip b's values (``VAURAModel.generate_tokens``).
+    ``return_relevance``: passed to every chunk; the result gains "relevance", "logprob_cond" and "logprob_null" (B, K, T), the chunks'
+    values concatenated with the prompt overlap removed the way the tokens are (every frame carries the values of the chunk that
+    GENERATED it).  No sequence means are returned here: chunks overlap, and a mean per chunk is not a mean of the clip — reduce the
+    (B, K, T) values as needed."""
+    REL = ("relevance", "logprob_cond", "logprob_null")
     from .clip_params import check_lengths
     check_lengths(frames.shape[0], use_sampling=use_sampling, temp=temp, top_k=top_k, top_p=top_p, cfg_scale=cfg_scale)
     if model_max_duration is None:   # scripts/generate.py:221-226
@@ -58,10 +63,13 @@ def generate_long(model, frames: torch.Tensor, duration: float, *, stride: float
               top_p=top_p, remove_prompts=False, prompt_is_encoded=True, cfg_scale=cfg_scale)
     if len(sched) == 1 and sched[0]["positions"] is None:     # single chunk (:309-324)
         selected = frames[:, :, ::frame_step, ...] if frame_step != 1 else frames
-        item = model.generate(frames=selected, audio=None, max_new_tokens=sched[0]["max_gen_len"], **kw)
-        return {"generated_audio": item["generated_audio"], "sampled_indices": item["sampled_indices"]}
+        item = model.generate(frames=selected, audio=None, max_new_tokens=sched[0]["max_gen_len"],
+                              **(dict(kw, return_relevance=True) if return_relevance else kw))
+        return {"generated_audio": item["generated_audio"], "sampled_indices": item["sampled_indices"],
+                **({k: item[k] for k in REL} if return_relevance else {})}
     stride_tokens = int(COMPRESSION_MODEL_FRAME_RATE * stride)
     all_tokens, prompt_tokens = [], None
+    all_rel = {k: [] for k in REL}
     for ch in sched:                                            # chunked generation (:327-365)
         lo, hi = ch["positions"]
         positions = torch.arange(lo, hi, device=frames.device)
@@ -69,9 +77,15 @@ def generate_long(model, frames: torch.Tensor, duration: float, *, stride: float
         if frame_step != 1:
             selected = selected[:, :, :, ::frame_step, ...]
         # tokens only: the reference decodes every chunk inside generate() and throws the audio away (:344-357)
-        gen_tokens = model.generate_tokens(frames=selected, audio=prompt_tokens, max_new_tokens=ch["max_gen_len"], **kw)
+        gen_tokens = model.generate_tokens(frames=selected, audio=prompt_tokens, max_new_tokens=ch["max_gen_len"],
+                                           **(dict(kw, return_relevance=True) if return_relevance else kw))
+        if return_relevance:
+            rel, gen_tokens = gen_tokens, gen_tokens["tokens"]
+            for k in REL:
+                all_rel[k].append(rel[k] if prompt_tokens is None else rel[k][:, :, prompt_tokens.shape[-1]:])
         all_tokens.append(gen_tokens if prompt_tokens is None else gen_tokens[:, :, prompt_tokens.shape[-1]:])
         prompt_tokens = gen_tokens[:, :, stride_tokens:]
     gen_tokens = torch.cat(all_tokens, dim=-1)
     audio = model.audio_encoder.decode([(gen_tokens[..., : model.num_codebooks, :], None)])   # :366-369
-    return {"generated_audio": audio, "sampled_indices": gen_tokens}
+    return {"generated_audio": audio, "sampled_indices": gen_tokens,
+            **({k: torch.cat(v, dim=-1) for k, v in all_rel.items()} if return_relevance else {})}

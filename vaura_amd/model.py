@@ -237,9 +237,11 @@ class VAURAModel(nn.Module):
 
     # ------------------------------------------------------------------ generate
     @staticmethod
-    def _check_candidates(num_candidates, return_all_candidates, use_sampling, temp) -> int:
+    def _check_candidates(num_candidates, return_all_candidates, use_sampling, temp, rank_by="logprob", return_relevance=False) -> int:
         """The best-of-N arguments of generate() / generate_tokens(), checked on the host alone."""
         N = num_candidates
+        if rank_by not in ("logprob", "relevance"):
+            raise L.VauraHipError(f'rank_by must be "logprob" or "relevance", got {rank_by!r}')
         if isinstance(N, bool) or not isinstance(N, int):
             raise L.VauraHipError(f"num_candidates must be an int, got {N!r}")
         if N < 1:
@@ -249,6 +251,9 @@ class VAURAModel(nn.Module):
         if N > 1 and not clip_params.any_sampled(use_sampling, temp):
             raise L.VauraHipError(f"num_candidates = {N} with greedy decoding for every clip: the candidates would be identical "
                                   "(use_sampling with temp > 0 for at least one clip)")
+        if rank_by == "relevance" and N == 1 and not return_relevance:
+            raise L.VauraHipError('rank_by="relevance" with num_candidates = 1 and no return_relevance: nothing is ranked and nothing '
+                                  "is returned (pointless: it would stream the null-condition rows for no result)")
         return N
 
     @torch.no_grad()
@@ -257,7 +262,8 @@ class VAURAModel(nn.Module):
                         return_sampled_indices: bool = True, check: bool = False, use_sampling: bool = True,
                         temp: float = 1.0, top_k: int = 256, top_p: float = 0.0, remove_prompts: bool = False,
                         prompt_is_encoded: bool = False, cfg_scale: float = 1.0, return_logprobs: bool = False,
-                        num_candidates: int = 1, return_all_candidates: bool = False):
+                        num_candidates: int = 1, return_all_candidates: bool = False, return_relevance: bool = False,
+                        rank_by: str = "logprob"):
         """generate() up to and including revert_pattern_sequence (vaura_model.py:410-572): (B, K, T') int64 tokens on
         the device, no codec decode.  The sliding-window caller (vaura_amd.longform) uses this for every chunk and
         decodes the concatenated tokens once, as the reference's script does (scripts/generate.py:366-369).
@@ -274,9 +280,18 @@ class VAURAModel(nn.Module):
             "candidate_scores" (B, N) every take's score, "candidate_indices" (B * N, K, T') every take's tokens (candidate j of clip
             b is row b * N + j — the rows of a call on ``frames.repeat_interleave(N, 0)``);
           * ``return_all_candidates``: nothing is selected (for a caller with its own scorer): "tokens" and the log-probabilities are
-            those of all B * N takes, in candidate order."""
+            those of all B * N takes, in candidate order;
+          * ``return_relevance`` (a dict as well): the video relevance of every generated token, "relevance" (B, K, T') = "logprob_cond"
+            - "logprob_null", the token's log-probability given the video minus the one given the null video, both at temperature 1
+            over the full vocabulary — a property of the model's two distributions, not of the sampling settings; 0 in prompt frames,
+            sliced by ``remove_prompts`` like "logprobs" —, "relevance_per_codebook" (B, K) and "sequence_relevance" (B,), its
+            fixed-order means over the generated frames and then the codebooks.  It reads the null-condition rows: a call in which no
+            clip's ``cfg_scale`` exceeds 1 carries them anyway (twice the rows through the decode step; the tokens are unchanged);
+          * ``rank_by`` = "logprob" (default: today's ranking) | "relevance": the score the N takes are ranked by — "sequence_logprob"
+            or "sequence_relevance", same tie and NaN rules (``vaura_select_candidates``); "candidate_scores" holds the score that
+            ranked.  "relevance" without candidates and without ``return_relevance`` is refused."""
         assert not self.training, "do not use generation in training mode"
-        N = self._check_candidates(num_candidates, return_all_candidates, use_sampling, temp)   # refused before any device work
+        N = self._check_candidates(num_candidates, return_all_candidates, use_sampling, temp, rank_by, return_relevance)   # refused before any device work
         # per-clip parameter sequences of the wrong length: refused here, before any device work (frames carry the batch on dim 0)
         clip_params.check_lengths(frames.shape[0] if hasattr(frames, "shape") else None, use_sampling=use_sampling, temp=temp,
                                   top_k=top_k, top_p=top_p, cfg_scale=cfg_scale)
@@ -314,14 +329,21 @@ class VAURAModel(nn.Module):
         noise = None if greedy else self._exp_noise(S - start, B * N * K, self.sampler.d_codebook)
         # decode loop + its status word in one synchronisation (the reference's own post-conditions, :550-572, synchronise too); an
         # activation beyond the fp16-plane range is re-run on the exact-fp32 engine instead of raising (engine.generate_codes_checked)
-        want_lp = bool(return_logprobs) or N > 1            # candidates are ranked by their sequence log-probability
+        by_rel = rank_by == "relevance"
+        want_rel = bool(return_relevance) or (N > 1 and by_rel)
+        want_lp = bool(return_logprobs) or (N > 1 and not by_rel)      # candidates are ranked by their sequence log-probability by default
+        extra_kw = dict(num_candidates=N) if N > 1 else {}
+        if want_lp:
+            extra_kw.update(return_logprobs=True, num_candidates=N)
+        if want_rel:
+            extra_kw.update(return_relevance=True)
         codes = eng.generate_codes_checked(
             vis.float(), max_new_tokens, prompt=audio if Tp else None, use_sampling=use_sampling, temp=temp,
             top_k=top_k, top_p=top_p, cfg_scale=cfg_scale if use_cfg else 1.0, noise=noise, seed=self.seed,
             clip_base=self.clip_base, tokens_per_frame=self.sampler.audio_tokens_per_video_frame,
-            delays=None if delays == list(range(K)) else delays, **(dict(return_logprobs=True, num_candidates=N) if want_lp else {}))
+            delays=None if delays == list(range(K)) else delays, **extra_kw)
         lp = None
-        if want_lp:
+        if want_lp or want_rel:
             codes, lp = codes
         bad = (codes < 0) | (codes > self.sampler.d_codebook)
         assert not bool(bad.any()), "generated sequence is incomplete or out of range"
@@ -335,17 +357,18 @@ class VAURAModel(nn.Module):
             assert not bool((seq == -1).any()), "unknown tokens left in the generated sequence"
             assert bool((seq == torch.where(mask[None].expand_as(seq), seq, special)).all()), "sequence and pattern mask disagree"
         lo = Tp if remove_prompts else 0
-        if not want_lp:
+        if not (want_lp or want_rel):
             return codes[..., lo:max_new_tokens]
         out = {}
         if N > 1:
+            rank = lp["sequence_relevance" if by_rel else "score"]
             out["candidate_indices"] = codes[..., lo:max_new_tokens]
-            out["candidate_scores"] = lp["score"].view(B, N)
+            out["candidate_scores"] = rank.view(B, N)
             if not return_all_candidates:
                 c32 = codes.to(torch.int32).contiguous()
                 won = torch.empty(B, K, max_new_tokens, dtype=torch.int32, device=codes.device)
                 winner = torch.empty(B, dtype=torch.int32, device=codes.device)
-                L.check(eng.lib.vaura_select_candidates(L.ptr(lp["score"]), L.ptr(c32), B, N, K, max_new_tokens, L.ptr(won), L.ptr(winner),
+                L.check(eng.lib.vaura_select_candidates(L.ptr(rank), L.ptr(c32), B, N, K, max_new_tokens, L.ptr(won), L.ptr(winner),
                                                         L.current_stream(eng.dev)), "vaura_select_candidates")
                 rows = torch.arange(B, device=codes.device) * N + winner.to(torch.int64)
                 codes = won.to(torch.int64)
@@ -356,6 +379,11 @@ class VAURAModel(nn.Module):
             out["logprobs"] = lp["logprobs"][..., lo:max_new_tokens]
             out["logprob_per_codebook"] = lp["per_codebook"]
             out["sequence_logprob"] = lp["score"]
+        if return_relevance:
+            for k in ("relevance", "logprob_cond", "logprob_null"):
+                out[k] = lp[k][..., lo:max_new_tokens]
+            out["relevance_per_codebook"] = lp["relevance_per_codebook"]
+            out["sequence_relevance"] = lp["sequence_relevance"]
         return out
 
     @torch.no_grad()
@@ -363,12 +391,13 @@ class VAURAModel(nn.Module):
                  return_attention_weights: bool = False, return_sampled_indices: bool = False, check: bool = False,
                  use_sampling: bool = True, temp: float = 1.0, top_k: int = 256, top_p: float = 0.0,
                  remove_prompts: bool = False, prompt_is_encoded: bool = False, cfg_scale: float = 1.0,
-                 return_logprobs: bool = False, num_candidates: int = 1, return_all_candidates: bool = False) -> dict:
-        """``return_logprobs`` / ``num_candidates`` / ``return_all_candidates``: see ``generate_tokens`` — its extra entries are added
+                 return_logprobs: bool = False, num_candidates: int = 1, return_all_candidates: bool = False,
+                 return_relevance: bool = False, rank_by: str = "logprob") -> dict:
+        """``return_logprobs`` / ``num_candidates`` / ``return_all_candidates`` / ``return_relevance`` / ``rank_by``: see ``generate_tokens`` — its extra entries are added
         to the result ("sampled_indices" takes "tokens"); the codec decodes the winners (B clips), or with ``return_all_candidates``
         all B * N takes.  With the defaults the result is the dict it always was."""
         K = self.num_codebooks
-        self._check_candidates(num_candidates, return_all_candidates, use_sampling, temp)    # before the engine is touched
+        self._check_candidates(num_candidates, return_all_candidates, use_sampling, temp, rank_by, return_relevance)    # before the engine is touched
         extra = {}
         with off_null_stream(self.sampler.engine().dev) as caller:   # decode loop + codec leave HIP's null stream together
             out_codes = self.generate_tokens(
@@ -376,7 +405,7 @@ class VAURAModel(nn.Module):
                 return_attention_weights=return_attention_weights, check=check, use_sampling=use_sampling, temp=temp,
                 top_k=top_k, top_p=top_p, remove_prompts=remove_prompts, prompt_is_encoded=prompt_is_encoded,
                 cfg_scale=cfg_scale, return_logprobs=return_logprobs, num_candidates=num_candidates,
-                return_all_candidates=return_all_candidates)
+                return_all_candidates=return_all_candidates, return_relevance=return_relevance, rank_by=rank_by)
             if isinstance(out_codes, dict):
                 extra = out_codes
                 out_codes = extra.pop("tokens")
@@ -437,7 +466,21 @@ class VAURAModel(nn.Module):
         r = self._score(aud_feats[:, :self.num_codebooks], vis, return_logits=True)
         return r["logits"], r["mask"], aud_feats
 
-    def _score(self, codes: torch.Tensor, vis: torch.Tensor, return_logits: bool = False) -> dict:
+    @torch.no_grad()
+    def score_relevance(self, frames: torch.Tensor, audio: torch.Tensor, clip_indices: Optional[torch.Tensor] = None) -> dict:
+        """How much of GIVEN audio the video explains: ``forward``'s inputs (frames, mono audio (B, 1, N)) -> ``DecoderEngine.score(...,
+        relevance=True)`` of the audio's codes: the teacher-forced cross-entropy under the video ("nll", "nll_per_codebook", "loss",
+        "loss_per_codebook") and under the null condition ("nll_null", "nll_null_per_codebook", ...), "relevance_per_codebook" (B, K) =
+        nll_null_per_codebook - nll_per_codebook and "relevance" (B,), its mean over the codebooks — nats per token; plus "codes"
+        (B, K, Ta), the audio's codes.  ``forward`` / ``test_step`` do not go through here."""
+        aud_feats = self.audio_encoder.encode(audio)
+        vis = self._handle_visual_conditioning(frames, clip_indices, aud_feats.shape[0])
+        if vis is None:
+            raise NotImplementedError("unconditional scoring: the llama sampler always needs video features (llama.py:474-476)")
+        codes = aud_feats[:, :self.num_codebooks]
+        return dict(self._score(codes, vis, relevance=True), codes=codes)
+
+    def _score(self, codes: torch.Tensor, vis: torch.Tensor, return_logits: bool = False, relevance: bool = False) -> dict:
         """DecoderEngine.score with this model's delays (per call) and tokens per video frame (auto-set rule when None)."""
         K = self.num_codebooks
         Ta = int(codes.shape[-1])
@@ -450,7 +493,8 @@ class VAURAModel(nn.Module):
                 S, int(vis.shape[1]), getattr(self.sampler, "codebook_pattern", None), K)
         eng = self.sampler.engine()
         return eng.score(codes, vis.float(), delays=None if delays == list(range(K)) else delays,
-                         tokens_per_frame=self.sampler.audio_tokens_per_video_frame, return_logits=return_logits)
+                         tokens_per_frame=self.sampler.audio_tokens_per_video_frame, return_logits=return_logits,
+                         **(dict(relevance=True) if relevance else {}))
 
     @torch.no_grad()
     def _compute_loss(self, logits: torch.Tensor, targets: torch.Tensor, mask: torch.Tensor) -> Tuple[torch.Tensor, List[torch.Tensor]]:
