@@ -210,7 +210,8 @@ typedef struct vaura_decoder {
   int32_t has_pattern_delays;
   int32_t pattern_delays[16];
   /* Bytes of extension that FOLLOW this struct in the caller's memory: 0 (a zero-filled descriptor: none), or
-   * sizeof(vaura_decoder_ext) - sizeof(vaura_decoder) when `dec` is the first member of a vaura_decoder_ext (below); anything else is
+   * sizeof(vaura_decoder_ext) - sizeof(vaura_decoder) when `dec` is the first member of a vaura_decoder_ext (below), or
+   * sizeof(vaura_decoder_ext2) - sizeof(vaura_decoder) when that in turn is the first member of a vaura_decoder_ext2; anything else is
    * VAURA_ERR_ARG.  It occupies what was alignment padding in front of `kscale`: no field moved and the struct keeps its size, so a
    * caller compiled against the descriptor without it (and zero-filling it, as every field's default asks) runs unchanged. */
   int32_t ext_bytes;
@@ -261,6 +262,28 @@ typedef struct vaura_decoder_ext {
   float* logprobs_cond;
   float* logprobs_null;
 } vaura_decoder_ext;
+
+/* vaura_decoder_ext with the per-clip lengths of a ragged batch appended behind it.  Every entry point takes `&ext2.ext.dec`; the
+ * library reads the two pointers only when ext.dec.ext_bytes = sizeof(vaura_decoder_ext2) - sizeof(vaura_decoder).  Both are `batch`
+ * int32 in device memory, and either may be NULL (every clip then has dec.timesteps / dec.n_cond_tokens, as without this struct):
+ *   clip_timesteps    T_b, 1 <= T_b <= dec.timesteps.  Clip b ends after T_b frames: the sampler's fix-up, its log-probability /
+ *                     relevance writes and its near-tie count treat a slot whose timestep is >= T_b as invalid (the special token,
+ *                     nothing reported, nothing counted), exactly as the call with timesteps = T_b treats it.  dec.timesteps and
+ *                     dec.seq_len stay those of the longest clip; a finished clip rides along to the end of the loop.
+ *   clip_cond_tokens  Tv_b, 1 <= Tv_b <= dec.n_cond_tokens.  Only the first Tv_b video tokens of clip b are real: a position whose
+ *                     frame pos / tokens_per_frame is >= Tv_b takes empty_video, in the decode step and in the prefill pass, for the
+ *                     clip's conditional row b and its null-condition row batch + b.  The row stride of cond_proj stays
+ *                     dec.n_cond_tokens; what it holds behind token Tv_b - 1 of a clip is never read.
+ * The kernels read the arrays at every step, and a captured step graph holds the POINTERS: rewrite the values between calls and
+ * replay the same graph.  vaura_decode_step, vaura_generate_loop, vaura_step_graph_build and vaura_embed return VAURA_ERR_ARG for a
+ * value outside its range (they read the arrays back: one small copy and a wait on the stream — under the rules of
+ * vaura_decoder.clip_sampling: not for replays of a built graph, not while the stream is being captured; where nothing is read back
+ * the kernels clamp a value to its upper bound, so nothing is read out of bounds).  vaura_score ignores clip_timesteps. */
+typedef struct vaura_decoder_ext2 {
+  vaura_decoder_ext ext;    /* ext.dec.ext_bytes = sizeof(vaura_decoder_ext2) - sizeof(vaura_decoder) */
+  const int32_t* clip_timesteps;
+  const int32_t* clip_cond_tokens;
+} vaura_decoder_ext2;
 
 /* -------------------------------------------------------------------------------------------
  * Weight ingress (once, at load).  Replaces nn.Module.load_state_dict for the streamed matrices.
@@ -350,6 +373,36 @@ int vaura_sequence_logprob(const float* logprobs, int seq_len, const int32_t* de
  * score of a clip is NaN, candidate 0 wins.                                                                                        */
 int vaura_select_candidates(const float* scores, const int32_t* codes, int B, int N, int K, int T, int32_t* codes_out, int32_t* winner,
                             vaura_stream_t s);
+
+/* ---- per-clip lengths (vaura_decoder_ext2): the kernels above with T_b = clip_timesteps[b] (B int32, device memory) in place of T.
+ * T stays the longest length (the row stride of codes / out, and S = T + max(d) + 1); delays_host NULL: d_q = q.  Each result equals,
+ * clip by clip and over frames [0, T_b), what the entry point above gives for T = T_b.  VAURA_ERR_ARG: a NULL clip_timesteps, a value
+ * outside 1 .. T (the values are read back: one small copy and a wait on the stream), and what the scalar form refuses.
+ * build:  seq[b, q, s] = codes[b, q, t] for 0 <= t = s - 1 - d_q < T_b, else `special`.
+ * revert: out[b, q, t] = seq[b, q, t + 1 + d_q] for t < T_b (`fill` where S ends before it), `pad` for t >= T_b.
+ * sequence_logprob: the means run over frames t0 .. T_b - 1 of each clip (t0 < T_b for every clip), same order, same NaN rule.      */
+int vaura_pattern_build_clips(const int32_t* codes, int32_t* seq, int B, int K, int T, int S, int special, const int32_t* delays_host,
+                              const int32_t* clip_timesteps, vaura_stream_t s);
+int vaura_pattern_revert_clips(const int32_t* seq, int32_t* codes, int B, int K, int T, int S, int fill, int pad,
+                               const int32_t* delays_host, const int32_t* clip_timesteps, vaura_stream_t s);
+int vaura_pattern_revert_clips_f32(const float* seq, float* out, int B, int K, int T, int S, float fill, float pad,
+                                   const int32_t* delays_host, const int32_t* clip_timesteps, vaura_stream_t s);
+int vaura_sequence_logprob_clips(const float* logprobs, int seq_len, const int32_t* delays_host, int B, int K, int T, int t0,
+                                 const int32_t* clip_timesteps, float* per_codebook, float* per_clip, vaura_stream_t s);
+/* The sampler exactly as the decode step runs it, on the caller's logits, with every option of the loop: seq (B, K, S) and `state` are
+ * required (position state[0], step state[2]; the slot state[0] + 1 is filled where it holds -1; status bits and near-tie counters are
+ * raised; the state advances).  clips: per-clip records or NULL; delays_host: K delays or NULL (d_q = q); clip_timesteps: B lengths
+ * or NULL (every clip has T); lp_seq / cond_seq / null_seq: (B, K, S) fp32 in the layout of seq or NULL (vaura_decoder.logprobs,
+ * vaura_decoder_ext.logprobs_cond / logprobs_null: cond_seq and null_seq together, with 2B rows of logits and sp->cfg_scale > 1).   */
+int vaura_sample_seq(const float* logits, int B, int K, int vocab, const vaura_sampling* sp, const vaura_clip_sampling* clips,
+                     const float* noise, int32_t* seq, int T, int S, int32_t* state, const int32_t* delays_host,
+                     const int32_t* clip_timesteps, float* lp_seq, float* cond_seq, float* null_seq, vaura_stream_t s);
+/* The input embedding of the decode step (pos_host < 0, n_pos = 1: the position is state[0]) or of n_pos prefill positions from
+ * pos_host on, alone: dec->ws_h (packed rows; prefill: one block of rows_padded rows per position) and, on the plane storages, the
+ * planes and sums of squares behind it.  Obeys vaura_decoder_ext2.clip_cond_tokens.  Nothing advances.  Every token of dec->seq at the
+ * embedded positions must be known (0 .. vocab): the kernel gathers table rows by token, as in the loop, where the sampler has filled
+ * a slot before the step that embeds it — a slot that still holds -1 is the caller's error and is not checked.                              */
+int vaura_embed(const vaura_decoder* dec, int pos_host, int n_pos, vaura_stream_t s);
 
 /* -------------------------------------------------------------------------------------------
  * a3..a12 + a2/a13/a15 for ONE position: Transformer.inference (llama.py:445-504) restricted to the
@@ -669,7 +722,7 @@ long long vaura_debug_counter(int which);
 
 const char* vaura_version(void);
 /* sizeof() of the descriptor structs as compiled into the library (0 dims, 1 layer_weights, 2 sampling, 3 decoder,
- * 4 conv, 5 codec, 6 codec_encoder, 7 vit, 8 vit_block): a binding checks its mirrored struct layouts against these before the first call.            */
+ * 4 conv, 5 codec, 6 codec_encoder, 7 vit, 8 vit_block, 9 clip_sampling, 10 decoder_ext, 11 decoder_ext2): a binding checks its mirrored struct layouts against these before the first call.            */
 size_t vaura_struct_size(int which);
 
 #ifdef __cplusplus

@@ -3,7 +3,8 @@
     hipcc <build.py FLAGS> [-D...] --cuda-device-only -S vaura_amd/csrc/UNIT.hip -o UNIT.s     (once per tree)
     python tools/compare_device_asm.py OLD.s NEW.s
 
-identical: equal bytes once the compile-unit id (__hip_cuid_<hash of the source path and options>) is masked.
+identical: equal bytes once the compile-unit id (__hip_cuid_<hash of the source path and options>) and the blanks that align the comment
+           behind a local label (their count follows the digits of the function's index in the unit) are masked.
 same-set : not identical, but equal after splitting at the function symbols and at the kernels' metadata records, masking the index of
            the function in its local labels (.LBB<i>_<j>, .Lfunc_end<i>) and sorting: host code instantiated the templates in another
            order; the set of symbols and every instruction stream are equal.  Anything else exits 1.
@@ -19,7 +20,9 @@ import sys
 
 
 def load(p):
-    return re.sub(r"__hip_cuid_[0-9a-f]+", "__hip_cuid", open(p).read())
+    # the compile-unit id, and the run of blanks that aligns a trailing "; comment" behind a local label: its width follows the number of
+    # digits of the function's index in the unit (.LBB99_3: -> .LBB100_3:), which a unit that gains functions changes for the old ones
+    return re.sub(r"(?m)^(\.L\w+:) +;", r"\1 ;", re.sub(r"__hip_cuid_[0-9a-f]+", "__hip_cuid", open(p).read()))
 
 
 def pieces(t):

@@ -10,6 +10,13 @@ storage "auto") through DecoderEngine.generate_codes, timed with HIP events arou
   both             return_logprobs and return_relevance
   relevance cfg1   return_relevance=True at cfg 1 next to "plain cfg1": the null rows are carried for the flag alone (twice the rows)
 
+  --lengths adds (where the tree has them):
+  lengths = T      max_new_tokens=[220] * 8, video_lengths=[32] * 8: the per-clip-length instances (sample_kernel<.., SampleLengths>,
+                   embed_clips_kernel, the _clips pattern kernels) on the shape of "plain" — what the two integer loads per workgroup cost
+  lengths ragged   max_new_tokens=[220, 110, 55, 220, 165, 28, 110, 220]: the same loop (a finished clip rides along to S)
+  codec 1 / 2 / 4  CodecEngine.decode of 8 clips x 220 frames in one pass, and grouped as generate() groups a ragged batch: two lengths
+                   (4 x 220 + 4 x 110) and four (2 x 220 + 2 x 165 + 2 x 110 + 2 x 55), median of 20 after 3 warm-ups
+
 --package-root D imports vaura_amd from D (another build of the library, e.g. the parent commit): modes that tree does not have are
 skipped, so the plain line of two trees can be taken in one session on one card."""
 import argparse
@@ -21,6 +28,7 @@ ap = argparse.ArgumentParser()
 ap.add_argument("--package-root", default=os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 ap.add_argument("--repeat", type=int, default=5)
 ap.add_argument("--relevance", action="store_true")
+ap.add_argument("--lengths", action="store_true")
 args = ap.parse_args()
 import torch  # noqa: E402
 sys.path.insert(0, os.path.abspath(args.package_root))
@@ -38,23 +46,49 @@ if has_lp:
 if args.relevance and "return_relevance" in inspect.signature(eng.generate_codes).parameters:
     modes += [("relevance", 8, dict(return_relevance=True)), ("both", 8, dict(return_logprobs=True, return_relevance=True)),
               ("plain cfg1", 8, dict(cfg_scale=1.0)), ("relevance cfg1", 8, dict(cfg_scale=1.0, return_relevance=True))]
+has_len = args.lengths and "video_lengths" in inspect.signature(eng.generate_codes).parameters
+if has_len:
+    modes += [("lengths = T", 8, dict(T=[220] * 8, video_lengths=[32] * 8)), ("lengths ragged", 8, dict(T=[220, 110, 55, 220, 165, 28, 110, 220]))]
 print(f"tree {os.path.abspath(args.package_root)}: storage {eng.wdtype}, 228 steps per batch, 5 batches per region, {args.repeat} regions")
 s = torch.cuda.Stream(dev)
 with torch.cuda.stream(s):
     for name, clips, extra in modes:
         feats = synth.video_features(clips, seed=0).to(dev)
+        extra = dict(extra)
+        T = extra.pop("T", 220)
         for _ in range(2):
-            eng.generate_codes(feats, 220, **dict(kw, **extra))
+            eng.generate_codes(feats, T, **dict(kw, **extra))
         torch.cuda.synchronize()
         ms = []
         for _ in range(args.repeat):
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             e0.record()
             for _ in range(5):
-                eng.generate_codes(feats, 220, **dict(kw, **extra))
+                eng.generate_codes(feats, T, **dict(kw, **extra))
             e1.record()
             torch.cuda.synchronize()
             ms.append(e0.elapsed_time(e1) / 5)
         eng.check_status()        # a broken hand-off / non-finite logits would make these times meaningless: fail instead
         ms.sort()
         print(f"{name:16s} {ms[len(ms) // 2]:8.3f} ms per batch (median; min {ms[0]:.3f}, max {ms[-1]:.3f}) = {ms[len(ms) // 2] / 228 * 1e3:7.2f} us per step")
+
+if has_len:
+    from vaura_amd.engine import CodecEngine  # noqa: E402
+    ccfg = synth.FULL_CODEC
+    codec = CodecEngine(ccfg, synth.codec_state_dict(ccfg, seed=0), dev)
+    codes = torch.randint(0, 1024, (8, 9, 220), generator=torch.Generator().manual_seed(0)).to(dev)
+    for name, groups in (("codec 1 length", [(8, 220)]), ("codec 2 lengths", [(4, 220), (4, 110)]),
+                         ("codec 4 lengths", [(2, 220), (2, 165), (2, 110), (2, 55)])):
+        ms = []
+        with torch.cuda.stream(s):
+            for i in range(23):
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                for n, Tg in groups:
+                    codec.decode(codes[:n, :, :Tg])
+                e1.record()
+                torch.cuda.synchronize()
+                if i >= 3:
+                    ms.append(e0.elapsed_time(e1))
+        ms.sort()
+        print(f"{name:16s} {ms[len(ms) // 2]:8.3f} ms (median of 20; min {ms[0]:.3f}, max {ms[-1]:.3f})")

@@ -67,6 +67,12 @@ class DecoderExt(C.Structure):
     _fields_ = [("dec", Decoder), ("logprobs_cond", C.c_void_p), ("logprobs_null", C.c_void_p)]
 
 
+class DecoderExt2(C.Structure):
+    """vaura_decoder_ext2: the extended descriptor with the per-clip lengths of a ragged batch behind it (two device pointers to B int32,
+    either may be NULL).  Entry points take ``byref(ext2.ext.dec)``; ``dec.ext_bytes`` = 32 tells the library that all four pointers follow."""
+    _fields_ = [("ext", DecoderExt), ("clip_timesteps", C.c_void_p), ("clip_cond_tokens", C.c_void_p)]
+
+
 class Conv(C.Structure):
     _fields_ = [("w", C.c_void_p), ("bias", C.c_void_p), ("wscale", C.c_void_p), ("cin", C.c_int32), ("cout", C.c_int32),
                 ("taps", C.c_int32), ("dilation", C.c_int32), ("stride", C.c_int32), ("_pad", C.c_int32)]
@@ -171,6 +177,17 @@ SIGNATURES = {
                                          C.c_void_p, C.c_void_p]),
     "vaura_select_candidates": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
                                           C.c_void_p]),
+    "vaura_pattern_build_clips": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int32),
+                                            C.c_void_p, C.c_void_p]),
+    "vaura_pattern_revert_clips": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                             C.POINTER(C.c_int32), C.c_void_p, C.c_void_p]),
+    "vaura_pattern_revert_clips_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float,
+                                                 C.POINTER(C.c_int32), C.c_void_p, C.c_void_p]),
+    "vaura_sequence_logprob_clips": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int32), C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p,
+                                               C.c_void_p, C.c_void_p, C.c_void_p]),
+    "vaura_sample_seq": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(Sampling), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
+                                   C.c_int, C.c_void_p, C.POINTER(C.c_int32), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "vaura_embed": (C.c_int, [C.POINTER(Decoder), C.c_int, C.c_int, C.c_void_p]),
     "vaura_decode_step": (C.c_int, [C.POINTER(Decoder), C.POINTER(Sampling), C.c_int, C.c_void_p]),
     "vaura_generate_loop": (C.c_int, [C.POINTER(Decoder), C.POINTER(Sampling), C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "vaura_step_graph_build": (C.c_int, [C.POINTER(Decoder), C.POINTER(Sampling), C.c_void_p, C.POINTER(C.c_void_p)]),
@@ -229,7 +246,7 @@ def lib() -> C.CDLL:
             fn = getattr(handle, name)  # AttributeError if the symbol is not exported
             fn.restype = res
             fn.argtypes = args
-        for which, cls in enumerate([Dims, LayerWeights, Sampling, Decoder, Conv, Codec, CodecEncoder, Vit, VitBlock, ClipSampling, DecoderExt]):
+        for which, cls in enumerate([Dims, LayerWeights, Sampling, Decoder, Conv, Codec, CodecEncoder, Vit, VitBlock, ClipSampling, DecoderExt, DecoderExt2]):
             if C.sizeof(cls) != handle.vaura_struct_size(which):
                 raise VauraHipError(f"{LIB_PATH} was built from a different include/vaura_hip.h: sizeof({cls.__name__}) is "
                                     f"{handle.vaura_struct_size(which)} there, {C.sizeof(cls)} here (rebuild the library)")

@@ -105,3 +105,57 @@ def pack_records(p: Dict[str, List]) -> bytes:
     """``vaura_clip_sampling`` records, one per clip, as the device buffer holds them."""
     return b"".join(struct.pack("<ififf3i", p["use_sampling"][b], p["temp"][b], p["top_k"][b], p["top_p"][b], p["cfg_scale"][b], 0, 0, 0)
                     for b in range(len(p["temp"])))
+
+
+# ---- per-clip lengths of one batched call: max_new_tokens as one int per clip (T_b) and video_lengths (Tv_b, the leading video tokens
+# of clip b's features that are real).  Resolved and checked here, before any device work (include/vaura_hip.h vaura_decoder_ext2).
+def _int_list(name: str, v) -> List[int]:
+    if getattr(v, "ndim", 1) != 1:
+        raise _error(f"per-clip {name} must be one-dimensional (one value per clip), got shape {tuple(v.shape)}")
+    vals = v.tolist() if hasattr(v, "tolist") else list(v)
+    for x in vals:
+        if isinstance(x, bool) or not isinstance(x, int):
+            raise _error(f"per-clip {name} must hold integers, got {x!r}")
+    return vals
+
+
+def max_tokens(max_new_tokens) -> int:
+    """T_max of a call: the int itself, or the largest of a per-clip sequence (integers >= 1, checked)."""
+    if not is_per_clip(max_new_tokens):
+        return int(_scalar(max_new_tokens))
+    vals = _int_list("max_new_tokens", max_new_tokens)
+    if not vals or min(vals) < 1:
+        raise _error(f"per-clip max_new_tokens must be at least 1 for every clip, got {vals}")
+    return max(vals)
+
+
+def resolve_lengths(batch: Optional[int], max_new_tokens, video_lengths=None, n_video_tokens: Optional[int] = None, prompt_len: int = 0):
+    """(T_max, [T_b] or None, [Tv_b] or None) of a call.  ``max_new_tokens``: an int (None in the second place: every clip has it) or one
+    int >= 1 per clip; ``video_lengths``: None or one int per clip, 1 <= Tv_b <= ``n_video_tokens`` (where that is known).  ``batch``
+    and ``n_video_tokens`` None: not known yet, checked by a later call.  A common prompt must be shorter than every clip of a per-clip sequence."""
+    t_max = max_tokens(max_new_tokens)
+    lens = _int_list("max_new_tokens", max_new_tokens) if is_per_clip(max_new_tokens) else None
+    if lens is not None and batch is not None and len(lens) != batch:
+        raise _error(f"per-clip max_new_tokens has {len(lens)} values for a batch of {batch} clips")
+    if lens is not None and prompt_len >= min(lens):     # (an int max_new_tokens keeps the callers' own check)
+        raise _error(f"the audio prompt ({prompt_len} frames) must be shorter than every clip's max_new_tokens ({lens})")
+    tv = None
+    if video_lengths is not None:
+        if not is_per_clip(video_lengths):
+            raise _error(f"video_lengths must be one integer per clip (a list, tuple or 1-D tensor), got {video_lengths!r}")
+        tv = _int_list("video_lengths", video_lengths)
+        if batch is not None and len(tv) != batch:
+            raise _error(f"video_lengths has {len(tv)} values for a batch of {batch} clips")
+        if lens is not None and len(tv) != len(lens):
+            raise _error(f"video_lengths has {len(tv)} values but max_new_tokens has {len(lens)}: one value per clip")
+        if not tv or min(tv) < 1 or (n_video_tokens is not None and max(tv) > n_video_tokens):
+            raise _error(f"video_lengths must lie in 1 .. {n_video_tokens if n_video_tokens is not None else 'Tv'} (the video tokens of the "
+                         f"features), got {tv}")
+    return t_max, lens, tv
+
+
+def refuse_lengths(where: str, max_new_tokens=None, video_lengths=None) -> None:
+    """Callers that keep one length per call (the sliding window, teacher-forced scoring) refuse a per-clip sequence with a message."""
+    if is_per_clip(max_new_tokens) or video_lengths is not None:
+        raise _error(f"{where} takes one length for the whole call: per-clip lengths (a max_new_tokens / duration sequence, video_lengths) "
+                     "are served by generate() / generate_tokens() only")

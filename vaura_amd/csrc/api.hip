@@ -36,7 +36,7 @@ static int check_decoder(const vaura_decoder* d) {
     span = d->pattern_delays[m.n_codebooks - 1] + 1;
   }
   if (d->seq_len != d->timesteps + span) return VAURA_ERR_SHAPE;
-  if (d->ext_bytes != 0 && !va_decoder_ext(d)) return VAURA_ERR_ARG;      // an extension of another size than vaura_decoder_ext's
+  if (d->ext_bytes != 0 && !va_decoder_ext(d)) return VAURA_ERR_ARG;      // an extension of another size than vaura_decoder_ext's / _ext2's
   return 0;
 }
 
@@ -131,6 +131,12 @@ static int enqueue_prefill_chunk_heads(const vaura_decoder* d, int p0, int n, fl
                          (int64_t)m.n_codebooks * m.vocab, m.d_model, E3_LOGITS, true, s);
 }
 
+// per-clip lengths of a decoder call (vaura_decoder_ext2): 1 <= T_b <= timesteps, 1 <= Tv_b <= n_cond_tokens (step.hip va_check_clip_lengths)
+static int check_clip_lengths(const vaura_decoder* d, hipStream_t s) {
+  const int rc = va_check_clip_lengths(va_clip_timesteps(d), d->batch, 1, d->timesteps, s);
+  return rc ? rc : va_check_clip_lengths(va_clip_cond_tokens(d), d->batch, 1, d->n_cond_tokens, s);
+}
+
 // per-clip sampling records of a decoder call (vaura_decoder.clip_sampling): refused with probability rows, and with a clip scale > 1
 // when the descriptor carries no null-condition rows (step.hip va_check_clip_sampling)
 static int check_clips(const vaura_decoder* d, const vaura_sampling* sp, hipStream_t s) {
@@ -141,7 +147,8 @@ static int check_clips(const vaura_decoder* d, const vaura_sampling* sp, hipStre
   // video relevance (step.hip mode 2): both buffers or neither, and only with the null-condition rows it reads
   if (!lc != !lu) return VAURA_ERR_ARG;
   if (lc && (d->rows != 2 * d->batch || !sp || !(sp->cfg_scale > 1.0f))) return VAURA_ERR_ARG;
-  return va_check_clip_sampling(sp, d->clip_sampling, d->batch, d->rows == 2 * d->batch, s);
+  const int rc = va_check_clip_sampling(sp, d->clip_sampling, d->batch, d->rows == 2 * d->batch, s);
+  return rc ? rc : check_clip_lengths(d, s);
 }
 
 // what both step paths pass to the attention of layer l (the pair path adds qkv2, the planes for wo and the arrival words) ...
@@ -164,6 +171,7 @@ static VaSampleLaunch sample_launch(const vaura_decoder* d, const vaura_sampling
   a.lp_seq = d->logprobs;
   if (const vaura_decoder_ext* x = va_decoder_ext(d)) { a.cond_seq = x->logprobs_cond; a.null_seq = x->logprobs_null; }
   a.null_rows = d->rows == 2 * d->batch;
+  a.clip_T = va_clip_timesteps(d);
   return a;
 }
 
@@ -402,6 +410,7 @@ size_t vaura_struct_size(int which) {
     case 8: return sizeof(vaura_vit_block);
     case 9: return sizeof(vaura_clip_sampling);
     case 10: return sizeof(vaura_decoder_ext);
+    case 11: return sizeof(vaura_decoder_ext2);
     default: return 0;
   }
 }
@@ -412,6 +421,15 @@ int vaura_decode_step(const vaura_decoder* dec, const vaura_sampling* sp, int sa
   if (sample && !sp) return VAURA_ERR_ARG;
   if (sample && (rc = check_clips(dec, sp, as_stream(s)))) return rc;
   return enqueue_step(dec, sp, sample, as_stream(s));
+}
+
+int vaura_embed(const vaura_decoder* dec, int pos_host, int n_pos, vaura_stream_t s) {
+  int rc = check_decoder(dec);
+  if (rc) return rc;
+  if (n_pos < 1 || (pos_host < 0 && n_pos != 1) || (pos_host >= 0 && pos_host + n_pos > dec->seq_len)) return VAURA_ERR_ARG;
+  if (n_pos > 1 && n_pos > dec->prefill_positions) return VAURA_ERR_ARG;      // the workspaces hold that many positions' row blocks
+  if ((rc = check_clip_lengths(dec, as_stream(s)))) return rc;
+  return va_launch_embed(dec, pos_host, n_pos, as_stream(s));
 }
 
 void vaura_step_graph_free(vaura_step_graph_t g_) {

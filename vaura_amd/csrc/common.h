@@ -263,8 +263,16 @@ int va_launch_tail_engine(const Gemv3Args& awo, const Gemv3Args& a13, const Gemv
 int va_launch_embed(const vaura_decoder* d, int pos_host, int n_pos, hipStream_t s);
 // the relevance pointers behind a descriptor (vaura_decoder_ext), or NULL when the caller passed a plain vaura_decoder
 inline const vaura_decoder_ext* va_decoder_ext(const vaura_decoder* d) {
-  return d->ext_bytes == (int32_t)(sizeof(vaura_decoder_ext) - sizeof(vaura_decoder)) ? reinterpret_cast<const vaura_decoder_ext*>(d) : nullptr;
+  return (d->ext_bytes == (int32_t)(sizeof(vaura_decoder_ext) - sizeof(vaura_decoder)) ||
+          d->ext_bytes == (int32_t)(sizeof(vaura_decoder_ext2) - sizeof(vaura_decoder)))
+             ? reinterpret_cast<const vaura_decoder_ext*>(d) : nullptr;
 }
+// the per-clip lengths behind those (vaura_decoder_ext2), or NULL
+inline const vaura_decoder_ext2* va_decoder_ext2(const vaura_decoder* d) {
+  return d->ext_bytes == (int32_t)(sizeof(vaura_decoder_ext2) - sizeof(vaura_decoder)) ? reinterpret_cast<const vaura_decoder_ext2*>(d) : nullptr;
+}
+inline const int32_t* va_clip_timesteps(const vaura_decoder* d) { const vaura_decoder_ext2* x = va_decoder_ext2(d); return x ? x->clip_timesteps : nullptr; }
+inline const int32_t* va_clip_cond_tokens(const vaura_decoder* d) { const vaura_decoder_ext2* x = va_decoder_ext2(d); return x ? x->clip_cond_tokens : nullptr; }
 struct VaSampleLaunch {              // one sampler launch over (B, K) rows of logits
   const float* logits = nullptr;
   int B = 0, K = 0, vocab = 0;
@@ -281,9 +289,12 @@ struct VaSampleLaunch {              // one sampler launch over (B, K) rows of l
   // mode-2 instances; both values are needed, and null_rows = "logits has rows [B, 2B)" (VAURA_ERR_ARG otherwise, before the launch)
   float *cond_out = nullptr, *cond_seq = nullptr, *null_out = nullptr, *null_seq = nullptr;
   bool null_rows = false;
+  const int32_t* clip_T = nullptr;        // per-clip timesteps T_b (vaura_decoder_ext2.clip_timesteps) or NULL: every clip has T
 };
 int va_launch_sample(const VaSampleLaunch& a, hipStream_t s);
 int va_check_clip_sampling(const vaura_sampling* sp, const vaura_clip_sampling* clips, int B, bool doubled, hipStream_t s);
+// host side of the per-clip lengths' contract: B values of `lengths` (device; NULL passes) read back and held to lo .. hi
+int va_check_clip_lengths(const int32_t* lengths, int B, int lo, int hi, hipStream_t s);
 int va_launch_advance(int32_t* state, int set_to, hipStream_t s);
 int va_launch_linear_pair(const uint16_t* in, const uint16_t* w, const float* bias, const float* res, float* out_raw,
                           uint16_t* out_act, int act, int B, int Lin, int Lout, int oshift, int Cin, int Cout, hipStream_t s);

@@ -74,12 +74,73 @@ __global__ __launch_bounds__(64) void embed_kernel(
   }
 }
 
+// embed_kernel with per-clip video lengths (vaura_decoder_ext2.clip_cond_tokens): only the first Tv_b = clip_tv[b] video tokens of clip
+// b = row % B are real — the null-condition row of a clip follows its clip —, frames from Tv_b on take empty_video; the row stride of
+// cond_proj stays Tv.  One vector load per workgroup (the host rewrites the array between replays of one captured graph: the vector
+// path is the one that is coherent with those copies), clamped to Tv so that no value can send the gather out of its rows.  A copy
+// of the kernel above and not a shared inlined body: that changed the operand order of embed_kernel's address arithmetic, and the
+// kernel every existing call runs stays the instruction stream it was.
+__global__ __launch_bounds__(64) void embed_clips_kernel(
+    const int32_t* __restrict__ seq, const int32_t* __restrict__ state, const float* __restrict__ cond_proj,
+    const float* __restrict__ empty_video, const float* __restrict__ table, float* __restrict__ h,
+    uint16_t* __restrict__ hsplit, const float* __restrict__ gain, float* __restrict__ ss, int B, int K, int S, int Tv,
+    int tpf, int vocab1, int cond_dim, int tok_dim, int pos_host, int rows16, const int32_t* __restrict__ clip_tv) {
+  const int row = blockIdx.x;
+  const int cq = blockIdx.y * 64 + threadIdx.x;   // 4-column quad
+  const int b = row % B;
+  int lane0 = 0;
+  asm volatile("" : "+v"(lane0));
+  const int tv_b = min(__builtin_amdgcn_readfirstlane(clip_tv[b + lane0]), Tv);
+  // decode: the position lives on the device; prefill: positions pos_host + blockIdx.z, one row block
+  // (rows16 = padded row count) per position
+  const int pos = pos_host >= 0 ? pos_host + (int)blockIdx.z : state[0];
+  const int vrow = (int)blockIdx.z * rows16 + row;
+  const int D = cond_dim + tok_dim;
+  const int frame = pos / tpf;
+  f32x4 o;
+  if (cq < cond_dim / 4) {
+    if (frame < tv_b)
+      o = reinterpret_cast<const f32x4*>(cond_proj)[packed_quad(row * Tv + frame, cq, cond_dim)];
+    else
+      o = reinterpret_cast<const f32x4*>(empty_video)[cq];
+  } else {
+    const int c0 = (cq - cond_dim / 4) * 4;
+    o = f32x4{0.f, 0.f, 0.f, 0.f};
+    int tok[16];
+#pragma unroll
+    for (int k = 0; k < 16; ++k) tok[k] = (k < K) ? seq[((size_t)b * K + k) * S + pos] : 0;
+    f32x4 e[16];
+#pragma unroll
+    for (int k = 0; k < 16; ++k)
+      if (k < K) e[k] = *reinterpret_cast<const f32x4*>(table + ((size_t)k * vocab1 + tok[k]) * tok_dim + c0);
+#pragma unroll
+    for (int k = 0; k < 16; ++k)    // same left-to-right order as the reference's sum([...]) (llama.py:455-460)
+      if (k < K) o += e[k];
+  }
+  va_st16(reinterpret_cast<f32x4*>(h) + packed_quad(vrow, cq, D), o);
+  if (hsplit) {
+    float s = ((o[0] * o[0] + o[1] * o[1]) + o[2] * o[2]) + o[3] * o[3];
+    s += __shfl_xor(s, 1, 64);
+    s += __shfl_xor(s, 2, 64);
+    if ((threadIdx.x & 3) == 0) va_st4(ss + ((size_t)(vrow >> 4) * (D / 16) + (cq >> 2)) * 16 + (vrow & 15), s);
+    const f32x4 u = o * *reinterpret_cast<const f32x4*>(gain + cq * 4);
+    store_split4(hsplit, vrow, cq * 4, D, u);
+  }
+}
+
 int va_launch_embed(const vaura_decoder* d, int pos_host, int n_pos, hipStream_t s) {
   const vaura_dims& m = d->dims;
   const int D = m.cond_dim + m.tok_dim;
   if (!d->tok_table || (D % 256)) return VAURA_ERR_SHAPE;
   const bool split = d->wdtype == VAURA_W_H1 || d->wdtype == VAURA_W_H2 || va_is_fp8(d->wdtype);   // pair path (api.hip enqueue_step)
   if (split && (!d->ws_h_split || !d->ws_ss || !d->first_norm)) return VAURA_ERR_ARG;
+  if (const int32_t* clip_tv = va_clip_cond_tokens(d)) {
+    VA_LAUNCH(embed_clips_kernel, dim3(d->rows, D / 256, n_pos), dim3(64), 0, s, d->seq, d->state, d->cond_proj, d->empty_video,
+              d->tok_table, d->ws_h, split ? d->ws_h_split : nullptr, d->first_norm, d->ws_ss, d->batch, m.n_codebooks,
+              d->seq_len, d->n_cond_tokens, m.tokens_per_frame, m.vocab + 1, m.cond_dim, m.tok_dim, pos_host,
+              (d->rows + 15) / 16 * 16, clip_tv);
+    return 0;
+  }
   VA_LAUNCH(embed_kernel, dim3(d->rows, D / 256, n_pos), dim3(64), 0, s, d->seq, d->state, d->cond_proj, d->empty_video,
             d->tok_table, d->ws_h, split ? d->ws_h_split : nullptr, d->first_norm, d->ws_ss, d->batch, m.n_codebooks,
             d->seq_len, d->n_cond_tokens, m.tokens_per_frame, m.vocab + 1, m.cond_dim, m.tok_dim, pos_host,
@@ -234,8 +295,20 @@ struct SampleRelevance {
   float* null_out;   // lu: (B, K) or null
   float* null_seq;   // lu: (B, K, S) or null
 };
+// The per-clip LENGTHS of an instance (vaura_decoder_ext2.clip_timesteps): one more member of the pack, behind the reporting one where
+// there is one — told by its type, like mode 2: the six instances without it keep their symbols, argument lists and instruction
+// streams.  With it the workgroup of clip b takes T_b = T[b] for a.T, i.e. wherever a slot's validity is decided (the fix-up, the
+// lp / lc / lu writes into the sequence layout, the near-tie count): a slot whose timestep is >= T_b gets the special token, and nothing
+// of the clip is reported or counted there — the launch with a.T = T_b.  One vector load per workgroup, for the reason given at PC.
+struct SampleLengths {
+  const int32_t* T;   // (B) timesteps of every clip, 1 .. a.T (checked on the host; a larger value only keeps slots valid that a.S bounds anyway)
+};
 template <typename T, typename... R>
 __device__ __forceinline__ T va_first(T t, R...) { return t; }
+template <typename T>
+__device__ __forceinline__ T va_last(T t) { return t; }
+template <typename T, typename... R>
+__device__ __forceinline__ auto va_last(T, R... r) { return va_last(r...); }
 // two sums with ONE barrier pair (block_sum's order for each)
 __device__ __forceinline__ void block_sum2(float& a, float& b, float* sv) {
   a = wave_sum(a);
@@ -249,8 +322,10 @@ __device__ __forceinline__ void block_sum2(float& a, float& b, float* sv) {
 template <bool PC, bool LP, typename... LpArgs>
 __global__ __launch_bounds__(SMP_THREADS) void sample_kernel(const float* __restrict__ logits_q, const int32_t* __restrict__ state_q,
                                                              SampleArgs a, const int32_t* __restrict__ clips, LpArgs... lp_args) {
-  static_assert(sizeof...(LpArgs) == (LP ? 1 : 0), "LP instances take one SampleLogprobs / SampleRelevance, the others nothing");
   constexpr bool REL = (std::is_same<LpArgs, SampleRelevance>::value || ...);      // mode 2
+  constexpr bool CL = (std::is_same<LpArgs, SampleLengths>::value || ...);         // per-clip lengths
+  static_assert(sizeof...(LpArgs) == (LP ? 1 : 0) + (CL ? 1 : 0),
+                "LP instances take one SampleLogprobs / SampleRelevance, the others nothing; SampleLengths follows where the clips have lengths");
   [[maybe_unused]] float* lp_out = nullptr;
   [[maybe_unused]] float* lp_seq = nullptr;
   if constexpr (LP) { lp_out = va_first(lp_args...).out; lp_seq = va_first(lp_args...).seq; }
@@ -288,6 +363,11 @@ __global__ __launch_bounds__(SMP_THREADS) void sample_kernel(const float* __rest
     // (no lu + (x - lu) * 1: not the same bits), never reads them, and screens near-ties with factor 1 — the scalar path at
     // cfg_scale <= 1.  Without those rows no record can switch the mix on (refused on the host; clamped here: never out of bounds).
     a.cfg_scale = a.cfg_scale > 1.0f ? cfg : fminf(cfg, 1.0f);
+  }
+  if constexpr (CL) {      // this clip's timesteps: everything below reads them through `a`, like the per-clip parameters
+    int lane0 = 0;
+    asm volatile("" : "+v"(lane0));
+    a.T = __builtin_amdgcn_readfirstlane(va_last(lp_args...).T[b + lane0]);
   }
   float x[4] = {lc[0], lc[1], lc[2], lc[3]};
   // near-tie detector: magnitude of the rows this decision is made from (both branches, before the mix)
@@ -687,6 +767,24 @@ int va_check_clip_sampling(const vaura_sampling* sp, const vaura_clip_sampling* 
   return 0;
 }
 
+// Host side of the per-clip lengths' contract, under the rules of va_check_clip_sampling: the B values are read back (one small copy + a
+// wait on `s`) and held to lo .. hi; skipped while `s` is being captured — the kernels' own clamps keep such a launch inside its rows.
+int va_check_clip_lengths(const int32_t* lengths, int B, int lo, int hi, hipStream_t s) {
+  if (!lengths) return 0;
+  if (B <= 0 || ((uintptr_t)lengths & 3u) != 0) return VAURA_ERR_ARG;
+  hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+  const hipError_t ce = hipStreamIsCapturing(s, &cs);
+  if (ce != hipSuccess) { (void)hipGetLastError(); return (int)ce; }
+  if (cs != hipStreamCaptureStatusNone) return 0;
+  std::vector<int32_t> host((size_t)B);
+  hipError_t e = hipMemcpyAsync(host.data(), lengths, host.size() * sizeof(int32_t), hipMemcpyDeviceToHost, s);
+  if (e == hipSuccess) e = hipStreamSynchronize(s);
+  if (e != hipSuccess) return (int)e;
+  for (const int32_t v : host)
+    if (v < lo || v > hi) return VAURA_ERR_ARG;
+  return 0;
+}
+
 int va_launch_sample(const VaSampleLaunch& l, hipStream_t s) {
   const vaura_sampling* sp = l.sp;
   const int B = l.B, K = l.K;
@@ -708,6 +806,26 @@ int va_launch_sample(const VaSampleLaunch& l, hipStream_t s) {
   a.probs_in = sp->input_is_probs;
   a.tie_eps = sp->tie_eps > 0.f ? sp->tie_eps : 0.f;
   const int32_t* rec = reinterpret_cast<const int32_t*>(l.clips);
+  if (l.clip_T) {      // per-clip lengths: the same six instances with SampleLengths behind their pack
+    if (!l.seq) return VAURA_ERR_ARG;               // lengths decide the validity of sequence slots: nothing to decide without a sequence
+    const SampleLengths cl{l.clip_T};
+    const dim3 grid(K, B), block(SMP_THREADS);
+    if (rel) {
+      const auto k_rel = sample_kernel<false, true, SampleRelevance, SampleLengths>, k_pc_rel = sample_kernel<true, true, SampleRelevance, SampleLengths>;
+      const SampleRelevance r{l.lp_out, l.lp_seq, l.cond_out, l.cond_seq, l.null_out, l.null_seq};
+      if (l.clips) VA_LAUNCH(k_pc_rel, grid, block, 0, s, a.logits, a.state, a, rec, r, cl);
+      else VA_LAUNCH(k_rel, grid, block, 0, s, a.logits, a.state, a, rec, r, cl);
+    } else if (lp) {
+      const auto k_lp = sample_kernel<false, true, SampleLogprobs, SampleLengths>, k_pc_lp = sample_kernel<true, true, SampleLogprobs, SampleLengths>;
+      if (l.clips) VA_LAUNCH(k_pc_lp, grid, block, 0, s, a.logits, a.state, a, rec, SampleLogprobs{l.lp_out, l.lp_seq}, cl);
+      else VA_LAUNCH(k_lp, grid, block, 0, s, a.logits, a.state, a, rec, SampleLogprobs{l.lp_out, l.lp_seq}, cl);
+    } else {
+      const auto k_plain = sample_kernel<false, false, SampleLengths>, k_pc = sample_kernel<true, false, SampleLengths>;
+      if (l.clips) VA_LAUNCH(k_pc, grid, block, 0, s, a.logits, a.state, a, rec, cl);
+      else VA_LAUNCH(k_plain, grid, block, 0, s, a.logits, a.state, a, rec, cl);
+    }
+    return 0;
+  }
   // (named outside the macro: the commas of the template arguments would split its argument list)
   const auto k_plain = sample_kernel<false, false>, k_pc = sample_kernel<true, false>;
   const auto k_lp = sample_kernel<false, true, SampleLogprobs>, k_pc_lp = sample_kernel<true, true, SampleLogprobs>;
@@ -768,6 +886,28 @@ __global__ void pattern_revert_kernel(const int32_t* __restrict__ seq, int32_t* 
   codes[i] = (s < S) ? seq[((size_t)b * K + q) * S + s] : fill;
 }
 
+// Per-clip lengths (vaura_pattern_*_clips): clip b holds T_b = clip_T[b] <= T frames.  build: a slot whose timestep is >= T_b holds the
+// special token, as in the sequence built for T = T_b; revert (tokens or fp32 values): frames from T_b on get `pad`.  T_b is clamped
+// to T: no value can send a read out of the clip's rows.
+__global__ void pattern_build_clips_kernel(const int32_t* __restrict__ codes, int32_t* __restrict__ seq, int B, int K, int T, int S,
+                                           int special, PatternDelays pd, const int32_t* __restrict__ clip_T) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= (int64_t)B * K * S) return;
+  const int s = (int)(i % S), q = (int)((i / S) % K), b = (int)(i / ((int64_t)S * K));
+  const int t = s - 1 - pattern_delay(pd, q);
+  seq[i] = (t >= 0 && t < min(clip_T[b], T)) ? codes[((size_t)b * K + q) * T + t] : special;
+}
+template <typename E>
+__global__ void pattern_revert_clips_kernel(const E* __restrict__ seq, E* __restrict__ out, int B, int K, int T, int S, E fill, E pad,
+                                            PatternDelays pd, const int32_t* __restrict__ clip_T) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= (int64_t)B * K * T) return;
+  const int t = (int)(i % T), q = (int)((i / T) % K);
+  const int64_t b = i / ((int64_t)T * K);
+  const int s = t + 1 + pattern_delay(pd, q);
+  out[i] = t < clip_T[b] ? ((s < S) ? seq[((size_t)b * K + q) * S + s] : fill) : pad;
+}
+
 // delays_host: K sorted, non-negative delays (K <= 16), or NULL for d_q = q.  Returns max(d) + 1 (K for NULL), or an error.
 static int pattern_delays_arg(const int32_t* delays_host, int K, PatternDelays* pd) {
   for (int j = 0; j < 16; ++j) pd->d[j] = j;
@@ -789,6 +929,20 @@ static int pattern_build(const int32_t* codes, int32_t* seq, int B, int K, int T
   if (S != T + span) return VAURA_ERR_SHAPE;
   const int64_t n = (int64_t)B * K * S;
   VA_LAUNCH(pattern_build_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, codes, seq, B, K, T, S, special, pd);
+  return 0;
+}
+
+static int pattern_build_clips(const int32_t* codes, int32_t* seq, int B, int K, int T, int S, int special, const int32_t* delays_host,
+                               const int32_t* clip_T, hipStream_t s) {
+  if (!codes || !seq || !clip_T || B <= 0 || K <= 0 || T <= 0) return VAURA_ERR_ARG;
+  PatternDelays pd;
+  const int span = pattern_delays_arg(delays_host, K, &pd);
+  if (span < 0) return span;
+  if (S != T + span) return VAURA_ERR_SHAPE;
+  const int rc = va_check_clip_lengths(clip_T, B, 1, T, s);
+  if (rc) return rc;
+  const int64_t n = (int64_t)B * K * S;
+  VA_LAUNCH(pattern_build_clips_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, codes, seq, B, K, T, S, special, pd, clip_T);
   return 0;
 }
 
@@ -818,6 +972,22 @@ static int pattern_revert(const E* seq, E* out, int B, int K, int T, int S, E fi
   return 0;
 }
 
+template <typename E>
+static int pattern_revert_clips(const E* seq, E* out, int B, int K, int T, int S, E fill, E pad, const int32_t* delays_host,
+                                const int32_t* clip_T, hipStream_t s) {
+  if (!out || !seq || !clip_T || B <= 0 || K <= 0 || T <= 0 || S <= 0) return VAURA_ERR_ARG;
+  PatternDelays pd;
+  const int span = pattern_delays_arg(delays_host, K, &pd);
+  if (span < 0) return span;
+  if (delays_host && S > T + span) return VAURA_ERR_SHAPE;
+  const int rc = va_check_clip_lengths(clip_T, B, 1, T, s);
+  if (rc) return rc;
+  const int64_t n = (int64_t)B * K * T;
+  const auto kern = pattern_revert_clips_kernel<E>;
+  VA_LAUNCH(kern, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, seq, out, B, K, T, S, fill, pad, pd, clip_T);
+  return 0;
+}
+
 // Sequence scores of token log-probabilities kept in the layout of seq.  One workgroup per clip, one wave per codebook (K <= 16), in a
 // fixed order (the scheme of csrc/score.hip): lane l adds frames t0 + l, t0 + l + 64, .. of its codebook one after the other, the wave's
 // fixed butterfly (wave_sum: neighbours at distance 1, 2, 4, .., 32) adds the lanes, the mean is sum / (T - t0); thread 0 then adds the K
@@ -828,6 +998,27 @@ __global__ __launch_bounds__(1024) void sequence_logprob_kernel(const float* __r
                                                                 float* __restrict__ per_clip) {
   __shared__ float means[16];
   const int lane = threadIdx.x & 63, q = threadIdx.x >> 6, b = blockIdx.x;
+  const int dq = pattern_delay(pd, q);
+  const float* row = lp + ((size_t)b * K + q) * S + 1 + dq;
+  float acc = 0.f;
+  for (int t = t0 + lane; t < T; t += 64) acc += (t + 1 + dq < S) ? row[t] : 0.f;
+  acc = wave_sum(acc);
+  if (lane == 0) means[q] = acc / (float)(T - t0);
+  __syncthreads();
+  float tot = 0.f;
+  for (int j = 0; j < K; ++j) tot += means[j];
+  tot = tot / (float)K;
+  if (lane == 0) per_codebook[(size_t)b * K + q] = (tot != tot) ? tot : means[q];
+  if (threadIdx.x == 0) per_clip[b] = tot;
+}
+// The same with per-clip lengths (vaura_sequence_logprob_clips): the means of clip b run over frames [t0, T_b), T_b = clip_T[b] — the
+// launch with T = T_b (a copy for the reason given at embed_clips_kernel).
+__global__ __launch_bounds__(1024) void sequence_logprob_clips_kernel(const float* __restrict__ lp, int B, int K, int T, int S, int t0,
+                                                                PatternDelays pd, float* __restrict__ per_codebook,
+                                                                float* __restrict__ per_clip, const int32_t* __restrict__ clip_T) {
+  __shared__ float means[16];
+  const int lane = threadIdx.x & 63, q = threadIdx.x >> 6, b = blockIdx.x;
+  T = clip_T[b];
   const int dq = pattern_delay(pd, q);
   const float* row = lp + ((size_t)b * K + q) * S + 1 + dq;
   float acc = 0.f;
@@ -954,6 +1145,58 @@ int vaura_sequence_logprob(const float* logprobs, int seq_len, const int32_t* de
   VA_LAUNCH(sequence_logprob_kernel, dim3((unsigned)B), dim3(64 * K), 0, as_stream(s), logprobs, B, K, T, seq_len, t0, pd, per_codebook,
             per_clip);
   return 0;
+}
+
+int vaura_pattern_build_clips(const int32_t* codes, int32_t* seq, int B, int K, int T, int S, int special, const int32_t* delays_host,
+                              const int32_t* clip_timesteps, vaura_stream_t s) {
+  return pattern_build_clips(codes, seq, B, K, T, S, special, delays_host, clip_timesteps, as_stream(s));
+}
+
+int vaura_pattern_revert_clips(const int32_t* seq, int32_t* codes, int B, int K, int T, int S, int fill, int pad,
+                               const int32_t* delays_host, const int32_t* clip_timesteps, vaura_stream_t s) {
+  return pattern_revert_clips<int32_t>(seq, codes, B, K, T, S, fill, pad, delays_host, clip_timesteps, as_stream(s));
+}
+
+int vaura_pattern_revert_clips_f32(const float* seq, float* out, int B, int K, int T, int S, float fill, float pad,
+                                   const int32_t* delays_host, const int32_t* clip_timesteps, vaura_stream_t s) {
+  return pattern_revert_clips<float>(seq, out, B, K, T, S, fill, pad, delays_host, clip_timesteps, as_stream(s));
+}
+
+int vaura_sequence_logprob_clips(const float* logprobs, int seq_len, const int32_t* delays_host, int B, int K, int T, int t0,
+                                 const int32_t* clip_timesteps, float* per_codebook, float* per_clip, vaura_stream_t s) {
+  if (!logprobs || !clip_timesteps || !per_codebook || !per_clip || B <= 0 || K <= 0 || T <= 0 || seq_len <= 0 || t0 < 0 || t0 >= T)
+    return VAURA_ERR_ARG;
+  if (K > 16) return VAURA_ERR_SHAPE;
+  PatternDelays pd;
+  const int span = pattern_delays_arg(delays_host, K, &pd);
+  if (span < 0) return span;
+  if (seq_len != T + span) return VAURA_ERR_SHAPE;
+  const int rc = va_check_clip_lengths(clip_timesteps, B, t0 + 1, T, as_stream(s));      // every clip has a frame behind the prompt
+  if (rc) return rc;
+  VA_LAUNCH(sequence_logprob_clips_kernel, dim3((unsigned)B), dim3(64 * K), 0, as_stream(s), logprobs, B, K, T, seq_len, t0, pd,
+            per_codebook, per_clip, clip_timesteps);
+  return 0;
+}
+
+int vaura_sample_seq(const float* logits, int B, int K, int vocab, const vaura_sampling* sp, const vaura_clip_sampling* clips,
+                     const float* noise, int32_t* seq, int T, int S, int32_t* state, const int32_t* delays_host,
+                     const int32_t* clip_timesteps, float* lp_seq, float* cond_seq, float* null_seq, vaura_stream_t s) {
+  if (!logits || !sp || !seq || !state || B <= 0 || K <= 0 || T <= 0 || S <= 0) return VAURA_ERR_ARG;
+  if (sp->input_is_probs && (clips || lp_seq || cond_seq || null_seq)) return VAURA_ERR_ARG;
+  if (!cond_seq != !null_seq) return VAURA_ERR_ARG;
+  if (delays_host) {
+    PatternDelays pd;
+    const int span = pattern_delays_arg(delays_host, K, &pd);
+    if (span < 0) return span;
+  }
+  int rc = va_check_clip_sampling(sp, clips, B, sp->cfg_scale > 1.0f, as_stream(s));
+  if (!rc) rc = va_check_clip_lengths(clip_timesteps, B, 1, T, as_stream(s));
+  if (rc) return rc;
+  VaSampleLaunch a;
+  a.logits = logits; a.B = B; a.K = K; a.vocab = vocab; a.sp = sp; a.clips = clips; a.noise = noise;
+  a.seq = seq; a.T = T; a.S = S; a.state = state; a.delays_host = delays_host; a.clip_T = clip_timesteps;
+  a.lp_seq = lp_seq; a.cond_seq = cond_seq; a.null_seq = null_seq; a.null_rows = sp->cfg_scale > 1.0f;
+  return va_launch_sample(a, as_stream(s));
 }
 
 int vaura_select_candidates(const float* scores, const int32_t* codes, int B, int N, int K, int T, int32_t* codes_out, int32_t* winner,

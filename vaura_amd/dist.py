@@ -125,13 +125,19 @@ def shard(total: int, rank: int, world: int) -> Tuple[int, int]:
 
 
 def shard_params(params: dict, total: int, rank: int, world: int) -> dict:
-    """The sampling arguments (``use_sampling``, ``temp``, ``top_k``, ``top_p``, ``cfg_scale``; other keys pass through) of the clips
+    """The per-clip arguments (``use_sampling``, ``temp``, ``top_k``, ``top_p``, ``cfg_scale``, and the lengths ``max_new_tokens`` /
+    ``video_lengths``; other keys pass through) of the clips
     ``shard(total, rank, world)`` gives this rank: per-clip sequences are cut by the same contiguous split, scalars are kept.  With
     ``clip_base`` = the rank's first clip, a per-clip call then gives the same tokens for every world size, as scalar calls do."""
     from . import clip_params
     clip_params.check_lengths(total, **{k: v for k, v in params.items() if k in clip_params.NAMES})
+    if "max_new_tokens" in params:      # the per-clip lengths travel with their clips (an int max_new_tokens is kept)
+        clip_params.resolve_lengths(total, params["max_new_tokens"], params.get("video_lengths"))
+    elif params.get("video_lengths") is not None:
+        clip_params.resolve_lengths(total, 1, params["video_lengths"])
     first, count = shard(total, rank, world)
-    return {k: (clip_params.take(v, first, count) if k in clip_params.NAMES else v) for k, v in params.items()}
+    cut = clip_params.NAMES + ("max_new_tokens", "video_lengths")
+    return {k: (clip_params.take(v, first, count) if k in cut else v) for k, v in params.items()}
 
 
 def gather_clips(local: torch.Tensor, counts: List[int]) -> torch.Tensor:

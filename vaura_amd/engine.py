@@ -359,9 +359,15 @@ class DecoderEngine:
             self.clip_params = torch.zeros(batch, 8, dtype=torch.int32, device=self.dev)   # vaura_clip_sampling records (per-clip calls)
             self.logprobs = torch.zeros(batch, K, S, **f32)     # token log-probabilities in the layout of seq (return_logprobs calls)
             self.logprobs_cond = self.logprobs_null = None      # video relevance (return_relevance calls): allocated by the first such call
-        self.dec_ext = L.DecoderExt()      # the descriptor + the relevance pointers behind it (both NULL: the descriptor alone)
-        d = self.dec_ext.dec               # a view: byref(self.dec) points into dec_ext
-        d.ext_bytes = C.sizeof(L.DecoderExt) - C.sizeof(L.Decoder)
+            # per-clip lengths of a ragged call (vaura_decoder_ext2): T_b and Tv_b.  Engine-owned like clip_params: the descriptor and a
+            # captured step graph hold the POINTERS, _set_lengths() rewrites the values
+            self.clip_T = torch.zeros(batch, dtype=torch.int32, device=self.dev)
+            self.clip_Tv = torch.zeros(batch, dtype=torch.int32, device=self.dev)
+        self.lengths = self.video_lengths = None      # the host lists of the call being run (None: every clip has T / Tv)
+        self.dec_ext2 = L.DecoderExt2()    # the descriptor + the relevance pointers + the per-clip lengths behind it (all NULL: the descriptor alone)
+        self.dec_ext = self.dec_ext2.ext   # views: byref(self.dec) points into dec_ext2
+        d = self.dec_ext.dec
+        d.ext_bytes = C.sizeof(L.DecoderExt2) - C.sizeof(L.Decoder)
         d.dims = self.dims
         d.dims.tokens_per_frame = tokens_per_frame
         d.wdtype, d.batch, d.rows, d.max_len = self.wd, batch, rows, max_len
@@ -479,6 +485,21 @@ class DecoderEngine:
         return L.Sampling(int(bool(use_sampling)), float(temp), int(top_k), float(top_p),
                           float(cfg_scale if self.rows == 2 * self.batch else 1.0), int(seed), int(clip_base), 0, float(tie))
 
+    def _set_lengths(self, lengths: Optional[Sequence[int]], video_lengths: Optional[Sequence[int]]):
+        """The per-clip lengths of the call about to run (lists of ``batch`` ints, already checked by ``clip_params.resolve_lengths``;
+        None: every clip has T / Tv): written into the engine-owned device arrays on the current stream, and the descriptor points
+        at them or holds NULL."""
+        for vals, buf, name in ((lengths, self.clip_T, "clip_timesteps"), (video_lengths, self.clip_Tv, "clip_cond_tokens")):
+            if vals is not None:
+                assert len(vals) == self.batch
+                buf.copy_(torch.tensor(vals, dtype=torch.int32))
+            setattr(self.dec_ext2, name, L.ptr(buf) if vals is not None else 0)
+        self.lengths = None if lengths is None else list(lengths)
+        self.video_lengths = None if video_lengths is None else list(video_lengths)
+
+    def _delays_arg(self):
+        return L.delays_host(self.delays) if self.delays is not None else None
+
     def start_sequence(self, prompt: Optional[torch.Tensor]):
         """codes = -1 everywhere but the prompt -> pattern sequence on device; returns Tp."""
         K, T = self.cfg.num_codebooks, self.T
@@ -486,9 +507,13 @@ class DecoderEngine:
         Tp = 0
         if prompt is not None and prompt.shape[-1] > 0:
             Tp = prompt.shape[-1]
-            assert Tp < T, "gt audio prompt can not be longer than max_new_tokens"
+            assert Tp < (min(self.lengths) if self.lengths else T), "gt audio prompt can not be longer than max_new_tokens"
             self.codes_i32[..., :Tp] = prompt.to(self.dev, torch.int32)
-        if self.delays is None:
+        if self.lengths is not None:       # a slot past a clip's own end holds the special token, as in the sequence built for T_b
+            L.check(self.lib.vaura_pattern_build_clips(L.ptr(self.codes_i32), L.ptr(self.seq), self.batch, K, T, self.S, self.cfg.d_codebook,
+                                                       self._delays_arg(), L.ptr(self.clip_T), L.current_stream(self.dev)),
+                    "vaura_pattern_build_clips")
+        elif self.delays is None:
             L.check(self.lib.vaura_pattern_build(L.ptr(self.codes_i32), L.ptr(self.seq), self.batch, K, T,
                                                  self.cfg.d_codebook, L.current_stream(self.dev)), "vaura_pattern_build")
         else:
@@ -512,7 +537,9 @@ class DecoderEngine:
             if use_graph:
                 # per-clip calls: the record POINTER and the canonical struct of _sampling() — "per-clip + row doubling", never the values
                 key = (self._shape, L.ptr(noise), bytes(sp), int(self.dec.clip_sampling or 0), int(self.dec.logprobs or 0),
-                       int(self.dec_ext.logprobs_cond or 0), int(self.dec_ext.logprobs_null or 0))
+                       int(self.dec_ext.logprobs_cond or 0), int(self.dec_ext.logprobs_null or 0),
+                       # per-clip lengths: the POINTERS (engine-owned arrays, rewritten per call) — other lengths replay the same graph
+                       int(self.dec_ext2.clip_timesteps or 0), int(self.dec_ext2.clip_cond_tokens or 0))
                 if self._graph_key != key:       # the captured step is tied to these buffers / parameters
                     self._free_graph()
                     handle = C.c_void_p()
@@ -605,7 +632,11 @@ class DecoderEngine:
 
     def revert(self) -> torch.Tensor:
         K, T = self.cfg.num_codebooks, self.T
-        if self.delays is None:
+        if self.lengths is not None:       # frames past a clip's own end: the special id
+            L.check(self.lib.vaura_pattern_revert_clips(L.ptr(self.seq), L.ptr(self.codes_i32), self.batch, K, T, self.S, -1,
+                                                        self.cfg.d_codebook, self._delays_arg(), L.ptr(self.clip_T),
+                                                        L.current_stream(self.dev)), "vaura_pattern_revert_clips")
+        elif self.delays is None:
             L.check(self.lib.vaura_pattern_revert(L.ptr(self.seq), L.ptr(self.codes_i32), self.batch, K, T, self.S, -1,
                                                   L.current_stream(self.dev)), "vaura_pattern_revert")
         else:
@@ -615,10 +646,10 @@ class DecoderEngine:
         return self.codes_i32
 
     @torch.no_grad()
-    def generate_codes(self, feats: torch.Tensor, max_new_tokens: int, *, prompt: Optional[torch.Tensor] = None,
+    def generate_codes(self, feats: torch.Tensor, max_new_tokens, *, prompt: Optional[torch.Tensor] = None,
                        use_sampling=False, temp=1.0, top_k=0, top_p=0.0, cfg_scale=1.0, noise=None, seed=0,
                        clip_base=0, use_graph=True, tokens_per_frame=7, delays=None, return_logprobs=False, num_candidates=1,
-                       return_relevance=False):
+                       return_relevance=False, video_lengths=None):
         """The hot loop of generate(): (B, Tv, 768) -> codes (B, K, T) int64 (device).  ``delays``: the codebook delay pattern
         (codebook_patterns.py:374-419; None = 0..K-1, ParallelPatternProvider = all zeros): S = T + max(d) + 1 sequence steps, the
         loop samples steps Tp + 1 + d_0 .. S - 1, and an explicit ``noise`` has S - (Tp + 1 + d_0) steps.
@@ -639,12 +670,23 @@ class DecoderEngine:
         (0 in prompt frames), "relevance_per_codebook" (B * N, K) and "sequence_relevance" (B * N,), the fixed-order means of
         ``vaura_sequence_logprob`` applied to r.  It needs the null-condition rows: when no clip's ``cfg_scale`` exceeds 1 the engine
         prepares the doubled batch anyway and draws every clip un-mixed through the per-clip records (its own scale, <= 1) — the tokens
-        are those of the call without the flag, but such a call streams TWICE the rows through the decode step."""
+        are those of the call without the flag, but such a call streams TWICE the rows through the decode step.
+        ``max_new_tokens``: an int, or one int per clip (list / tuple / 1-D integer tensor of length B) T_b >= 1 — the call runs to T_max =
+        max T_b and returns codes (B * N, K, T_max), clip b padded with the special id from frame T_b on; ``video_lengths``: None, or
+        one int per clip, 1 <= Tv_b <= Tv, the leading video tokens of clip b's features that are real (later positions take
+        ``empty_video_emb``; what lies in ``feats[b, Tv_b:]`` does not matter).  With Philox noise or greedy decoding clip b's frames
+        [0, T_b) — tokens, log-probabilities, relevance, and their means — are the bits of the scalar call at the same batch with
+        ``max_new_tokens=T_b`` (and ``feats[:, :Tv_b]``).  A common prompt must be shorter than every T_b.  An explicit ``noise`` is
+        consumed per step of the call, so such a call works but is not comparable with a stand-alone one."""
         B, Tv, _ = feats.shape
         N = num_candidates
         if isinstance(N, bool) or not isinstance(N, int) or N < 1:
             raise L.VauraHipError(f"num_candidates must be an int >= 1, got {N!r}")
         clip_params.check_lengths(B, use_sampling=use_sampling, temp=temp, top_k=top_k, top_p=top_p, cfg_scale=cfg_scale)
+        t_max, lengths, tv_lengths = clip_params.resolve_lengths(B, max_new_tokens, video_lengths, Tv,
+                                                                 0 if prompt is None else int(prompt.shape[-1]))
+        if N > 1:                          # candidate j of clip b is row b * N + j: it has clip b's lengths
+            lengths, tv_lengths = (clip_params.repeat(v, N) if v is not None else None for v in (lengths, tv_lengths))
         cfg_on = clip_params.any_cfg(cfg_scale)     # some clip mixes: the whole batch carries the null-condition rows
         if N > 1:
             use_sampling, temp, top_k, top_p, cfg_scale = (clip_params.repeat(v, N) for v in (use_sampling, temp, top_k, top_p, cfg_scale))
@@ -659,7 +701,8 @@ class DecoderEngine:
         K = self.cfg.num_codebooks
         self._fc = None                       # the K/V cache is about to be reused: forward_cached must start over
         with off_null_stream(self.dev) as caller:
-            self.prepare(B * N, max_new_tokens, Tv, cfg_on, tokens_per_frame, block_size=self.cfg.block_size, delays=delays)
+            self.prepare(B * N, t_max, Tv, cfg_on, tokens_per_frame, block_size=self.cfg.block_size, delays=delays)
+            self._set_lengths(lengths, tv_lengths)
             self.set_condition(feats, replicate=N)
             Tp = self.start_sequence(prompt)
             start = Tp + 1 + (self.delays[0] if self.delays else 0)  # Pattern.get_first_step_with_timesteps(Tp), sorted delays
@@ -694,6 +737,10 @@ class DecoderEngine:
         K, T, Bn = self.cfg.num_codebooks, self.T, self.batch
         out = torch.empty(Bn, K, T, dtype=torch.float32, device=self.dev)
         dl = L.delays_host(self.delays) if self.delays is not None else None
+        if self.lengths is not None:
+            L.check(self.lib.vaura_pattern_revert_clips_f32(L.ptr(buf), L.ptr(out), Bn, K, T, self.S, 0.0, 0.0, dl, L.ptr(self.clip_T),
+                                                            L.current_stream(self.dev)), "vaura_pattern_revert_clips_f32")
+            return out
         L.check(self.lib.vaura_pattern_revert_delays_f32(L.ptr(buf), L.ptr(out), Bn, K, T, self.S, 0.0, dl, L.current_stream(self.dev)),
                 "vaura_pattern_revert_delays_f32")
         return out
@@ -704,6 +751,10 @@ class DecoderEngine:
         f32 = dict(dtype=torch.float32, device=self.dev)
         pcb, score = torch.empty(Bn, K, **f32), torch.empty(Bn, **f32)
         dl = L.delays_host(self.delays) if self.delays is not None else None
+        if self.lengths is not None:       # every clip's means over its own frames Tp .. T_b - 1
+            L.check(self.lib.vaura_sequence_logprob_clips(L.ptr(buf), self.S, dl, Bn, K, T, Tp, L.ptr(self.clip_T), L.ptr(pcb), L.ptr(score),
+                                                          L.current_stream(self.dev)), "vaura_sequence_logprob_clips")
+            return pcb, score
         L.check(self.lib.vaura_sequence_logprob(L.ptr(buf), self.S, dl, Bn, K, T, Tp, L.ptr(pcb), L.ptr(score), L.current_stream(self.dev)),
                 "vaura_sequence_logprob")
         return pcb, score
@@ -793,6 +844,7 @@ class DecoderEngine:
             n0 = st["n"]
         else:
             self.prepare(Bs, cap - K, feats.shape[1], False, tokens_per_frame, block_size=cap)    # S = cap positions, K/V capacity = cap
+            self._set_lengths(None, None)
             self.set_condition(feats)
             self.seq.zero_()
             self._reset_state()
@@ -829,6 +881,7 @@ class DecoderEngine:
         Bs, K, Lq = idx.shape
         self._fc = None
         self.prepare(Bs, Lq, feats.shape[1], False, tokens_per_frame, block_size=self.cfg.block_size)
+        self._set_lengths(None, None)
         self.set_condition(feats)
         self.seq.zero_()
         self.seq[:, :, :Lq] = idx.to(self.dev, torch.int32)
@@ -859,7 +912,7 @@ class DecoderEngine:
 
     @torch.no_grad()
     def score(self, codes: torch.Tensor, feats: torch.Tensor, *, delays: Optional[Sequence[int]] = None, tokens_per_frame: int = 7,
-              return_logits: bool = False, checked: bool = True, relevance: bool = False) -> Dict[str, torch.Tensor]:
+              return_logits: bool = False, checked: bool = True, relevance: bool = False, video_lengths=None) -> Dict[str, torch.Tensor]:
         """Teacher-forced cross-entropy of ``codes`` (B, K, Ta) under ``feats`` (B, Tv, 768): the reference's ``forward`` +
         ``_compute_loss`` (vaura_model.py:136-192, 240-280).  The input is ``build_pattern_sequence(codes[..., :-1])`` against a pattern
         of Ta timesteps (special token = vocab), S = Ta + max(d) + 1 (``delays`` None = 0..K-1); positions [0, S - 1) run without a CFG
@@ -873,8 +926,12 @@ class DecoderEngine:
         "nll_null" (B, K, Ta), "loss_null" / "loss_null_per_codebook", "nll_per_codebook" and "nll_null_per_codebook" (B, K) — the mean
         over the timesteps per clip and codebook, in the fixed order of ``vaura_sequence_logprob`` —, "relevance_per_codebook" (B, K)
         = nll_null_per_codebook - nll_per_codebook (how many nats per token the video explains) and "relevance" (B,), its mean over
-        the codebooks.  Today's entries are the bits of the call without the flag."""
+        the codebooks.  Today's entries are the bits of the call without the flag.
+        One length per call: a list of code tensors, or ``video_lengths``, is refused."""
         c = self.cfg
+        if not torch.is_tensor(codes) or video_lengths is not None:      # one length per call here (a projected video row depends on its own input row only: pad the features)
+            raise L.VauraHipError("score() takes one length for the whole call — one (B, K, Ta) tensor of codes, no video_lengths: per-clip "
+                                  "lengths are served by generate() / generate_tokens() only")
         if codes.dim() != 3 or codes.shape[1] != c.num_codebooks:
             raise L.VauraHipError(f"codes must be (B, {c.num_codebooks}, Ta), got {tuple(codes.shape)}")
         B, K, Ta = codes.shape
@@ -894,6 +951,7 @@ class DecoderEngine:
         self._fc = None                    # the K/V cache is about to be reused: forward_cached must start over
         with off_null_stream(self.dev) as caller:
             self.prepare(B, Ta, feats.shape[1], bool(relevance), tokens_per_frame, block_size=c.block_size, delays=dl)
+            self._set_lengths(None, None)      # scoring keeps one length per call
             self.set_condition(feats)
             self.codes_i32[..., :Ta - 1] = targets[..., :Ta - 1]
             self.codes_i32[..., Ta - 1] = c.d_codebook             # build_pattern_sequence(codes[..., :-1]): no input beyond Ta - 2

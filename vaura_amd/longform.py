@@ -44,7 +44,7 @@ def chunk_schedule(duration: float, model_max_duration: float = 2.56, stride: fl
 @torch.no_grad()
 def generate_long(model, frames: torch.Tensor, duration: float, *, stride: float = 0.64, model_max_duration: Optional[float] = None,
                   vfps: float = 25, frame_step: int = 1, clip_indices=None, use_sampling: bool = True, temp: float = 1.0,
-                  top_k: int = 128, top_p: float = 0.0, cfg_scale: float = 1.0, return_relevance: bool = False) -> dict:
+                  top_k: int = 128, top_p: float = 0.0, cfg_scale: float = 1.0, return_relevance: bool = False, video_lengths=None) -> dict:
     """frames: whatever the feature-extractor plugin accepts, segments on dim 1 — raw (B, S, C, T, H, W) or, with the
     pass-through ``MotionFormer``, features (B, S, t, 768).  Returns {"generated_audio", "sampled_indices"}.
     ``use_sampling``, ``temp``, ``top_k``, ``top_p``, ``cfg_scale``: scalars, or one value per clip (length-B list / tuple / 1-D
@@ -52,9 +52,12 @@ def generate_long(model, frames: torch.Tensor, duration: float, *, stride: float
     ``return_relevance``: passed to every chunk; the result gains "relevance", "logprob_cond" and "logprob_null" (B, K, T), the chunks'
     values concatenated with the prompt overlap removed the way the tokens are (every frame carries the values of the chunk that
     GENERATED it).  No sequence means are returned here: chunks overlap, and a mean per chunk is not a mean of the clip — reduce the
-    (B, K, T) values as needed."""
+    (B, K, T) values as needed.
+    One ``duration`` for the whole call: a per-clip sequence of durations, or ``video_lengths``, is refused (per-clip lengths are a
+    feature of one ``generate()`` call; the chunk schedule here is shared by the batch)."""
     REL = ("relevance", "logprob_cond", "logprob_null")
-    from .clip_params import check_lengths
+    from .clip_params import check_lengths, refuse_lengths
+    refuse_lengths("generate_long", duration, video_lengths)
     check_lengths(frames.shape[0], use_sampling=use_sampling, temp=temp, top_k=top_k, top_p=top_p, cfg_scale=cfg_scale)
     if model_max_duration is None:   # scripts/generate.py:221-226
         model_max_duration = 2.56 if model.sampler.config.block_size > 64 else 0.64

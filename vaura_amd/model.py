@@ -263,7 +263,7 @@ class VAURAModel(nn.Module):
                         temp: float = 1.0, top_k: int = 256, top_p: float = 0.0, remove_prompts: bool = False,
                         prompt_is_encoded: bool = False, cfg_scale: float = 1.0, return_logprobs: bool = False,
                         num_candidates: int = 1, return_all_candidates: bool = False, return_relevance: bool = False,
-                        rank_by: str = "logprob"):
+                        rank_by: str = "logprob", video_lengths=None):
         """generate() up to and including revert_pattern_sequence (vaura_model.py:410-572): (B, K, T') int64 tokens on
         the device, no codec decode.  The sliding-window caller (vaura_amd.longform) uses this for every chunk and
         decodes the concatenated tokens once, as the reference's script does (scripts/generate.py:366-369).
@@ -289,12 +289,27 @@ class VAURAModel(nn.Module):
             clip's ``cfg_scale`` exceeds 1 carries them anyway (twice the rows through the decode step; the tokens are unchanged);
           * ``rank_by`` = "logprob" (default: today's ranking) | "relevance": the score the N takes are ranked by — "sequence_logprob"
             or "sequence_relevance", same tie and NaN rules (``vaura_select_candidates``); "candidate_scores" holds the score that
-            ranked.  "relevance" without candidates and without ``return_relevance`` is refused."""
+            ranked.  "relevance" without candidates and without ``return_relevance`` is refused.
+        Per-clip lengths: ``max_new_tokens`` also takes one int per clip (a length-B list / tuple / 1-D integer tensor) T_b >= 1, and
+        ``video_lengths`` one int per clip, 1 <= Tv_b <= Tv: the leading video tokens of clip b that are real (positions behind them take
+        ``empty_video_emb``, as a stand-alone call given only Tv_b tokens pads them; what the features hold behind them does not matter).
+        The call runs to T_max = max T_b and the result is then always a dict: "tokens" (B, K, T_max) with the special id from frame
+        T_b on, "lengths" (B,) = T_b (minus the prompt with ``remove_prompts``), and the entries above, zero past a clip's end, their
+        means taken over the clip's own frames.  With ``noise_mode="philox"`` or greedy decoding, clip b's frames [0, T_b) — tokens and
+        every reported value — are the bits of the same call with ``max_new_tokens=T_b`` (and the features cut to Tv_b): one batched
+        call serves clips of different lengths.  ``noise_mode="torch_cpu"`` works but is not comparable (its draws are consumed per step
+        of the call).  A common prompt must be shorter than every T_b."""
         assert not self.training, "do not use generation in training mode"
         N = self._check_candidates(num_candidates, return_all_candidates, use_sampling, temp, rank_by, return_relevance)   # refused before any device work
         # per-clip parameter sequences of the wrong length: refused here, before any device work (frames carry the batch on dim 0)
         clip_params.check_lengths(frames.shape[0] if hasattr(frames, "shape") else None, use_sampling=use_sampling, temp=temp,
                                   top_k=top_k, top_p=top_p, cfg_scale=cfg_scale)
+        # per-clip lengths: resolved and checked here with what is known before any device work (the batch from the frames, an encoded prompt)
+        t_max, lengths, tv_lengths = clip_params.resolve_lengths(
+            frames.shape[0] if hasattr(frames, "shape") else None, max_new_tokens, video_lengths, None,
+            int(audio.shape[-1]) if (audio is not None and prompt_is_encoded) else 0)
+        ragged = lengths is not None or tv_lengths is not None
+        max_new_tokens = t_max               # the call runs to the longest clip
         if return_attention_weights:
             # the reference's own llama sampler returns (logits, None, None) (llama.py:520-539), so its generate() fails on
             # `sa_w[-1, -1, :]` (vaura_model.py:529-531) with this flag: there is no behaviour to reproduce
@@ -318,7 +333,9 @@ class VAURAModel(nn.Module):
                                       "(the reference raises here too, llama.py:474-476)")
         B = vis.shape[0]
         Tp = 0 if audio is None else int(audio.shape[-1])
-        assert Tp < max_new_tokens, "gt audio prompt can not be longer than max_new_tokens"
+        assert lengths is not None or Tp < max_new_tokens, "gt audio prompt can not be longer than max_new_tokens"
+        if ragged:                           # again with the batch, the video tokens and the prompt known: still before the engine is touched
+            _, lengths, tv_lengths = clip_params.resolve_lengths(B, lengths if lengths is not None else t_max, tv_lengths, int(vis.shape[1]), Tp)
         use_cfg = clip_params.any_cfg(cfg_scale) and self.sampler.__class__.__name__ == "Transformer"   # any clip's scale > 1
         eng = self.sampler.engine()
         if self.sampler.audio_tokens_per_video_frame is None:
@@ -338,28 +355,43 @@ class VAURAModel(nn.Module):
         if want_rel:
             extra_kw.update(return_relevance=True)
         codes = eng.generate_codes_checked(
-            vis.float(), max_new_tokens, prompt=audio if Tp else None, use_sampling=use_sampling, temp=temp,
+            vis.float(), lengths if lengths is not None else max_new_tokens, prompt=audio if Tp else None, use_sampling=use_sampling, temp=temp,
             top_k=top_k, top_p=top_p, cfg_scale=cfg_scale if use_cfg else 1.0, noise=noise, seed=self.seed,
             clip_base=self.clip_base, tokens_per_frame=self.sampler.audio_tokens_per_video_frame,
-            delays=None if delays == list(range(K)) else delays, **extra_kw)
+            delays=None if delays == list(range(K)) else delays, **extra_kw,
+            **(dict(video_lengths=tv_lengths) if tv_lengths is not None else {}))
         lp = None
         if want_lp or want_rel:
             codes, lp = codes
         bad = (codes < 0) | (codes > self.sampler.d_codebook)
+        row_len = None
+        if lengths is not None:              # the special id past a clip's own end, and only there
+            row_len = torch.tensor(clip_params.repeat(lengths, N), device=codes.device)
+            past = torch.arange(max_new_tokens, device=codes.device)[None, None, :] >= row_len[:, None, None]
+            bad = torch.where(past, codes != self.special_token_id, bad | (codes == self.special_token_id))
         assert not bool(bad.any()), "generated sequence is incomplete or out of range"
         if check:
             # vaura_model.py:508-515 checks, every step, that the prefix is coherent with the pattern mask and holds no unknown
             # token; the device loop fills the sequence in place, so the same two properties are checked on the finished one
             # (they are monotone: a violation at any step is still there at the end).  :550-558 are these asserts, always on.
             seq = eng.seq[:B * N].to(torch.int64)
-            _, mask = self.pattern_provider.get_pattern(max_new_tokens)._build_indexes(max_new_tokens, seq.device)
+            if lengths is None:
+                _, mask = self.pattern_provider.get_pattern(max_new_tokens)._build_indexes(max_new_tokens, seq.device)
+                mask = mask[None].expand_as(seq)
+            else:                            # every clip against its OWN pattern mask: steps behind its sequence hold the special token
+                mask = torch.zeros_like(seq, dtype=torch.bool)
+                for T_b in sorted(set(row_len.tolist())):
+                    _, m = self.pattern_provider.get_pattern(T_b)._build_indexes(T_b, seq.device)
+                    mask[row_len == T_b, :, :m.shape[-1]] = m
             special = torch.full_like(seq, self.special_token_id)
             assert not bool((seq == -1).any()), "unknown tokens left in the generated sequence"
-            assert bool((seq == torch.where(mask[None].expand_as(seq), seq, special)).all()), "sequence and pattern mask disagree"
+            assert bool((seq == torch.where(mask, seq, special)).all()), "sequence and pattern mask disagree"
         lo = Tp if remove_prompts else 0
-        if not (want_lp or want_rel):
+        if not (want_lp or want_rel or ragged):
             return codes[..., lo:max_new_tokens]
         out = {}
+        if ragged:
+            out["lengths"] = torch.tensor(lengths if lengths is not None else [max_new_tokens] * B, device=codes.device) - lo
         if N > 1:
             rank = lp["sequence_relevance" if by_rel else "score"]
             out["candidate_indices"] = codes[..., lo:max_new_tokens]
@@ -392,12 +424,17 @@ class VAURAModel(nn.Module):
                  use_sampling: bool = True, temp: float = 1.0, top_k: int = 256, top_p: float = 0.0,
                  remove_prompts: bool = False, prompt_is_encoded: bool = False, cfg_scale: float = 1.0,
                  return_logprobs: bool = False, num_candidates: int = 1, return_all_candidates: bool = False,
-                 return_relevance: bool = False, rank_by: str = "logprob") -> dict:
+                 return_relevance: bool = False, rank_by: str = "logprob", video_lengths=None) -> dict:
         """``return_logprobs`` / ``num_candidates`` / ``return_all_candidates`` / ``return_relevance`` / ``rank_by``: see ``generate_tokens`` — its extra entries are added
         to the result ("sampled_indices" takes "tokens"); the codec decodes the winners (B clips), or with ``return_all_candidates``
-        all B * N takes.  With the defaults the result is the dict it always was."""
+        all B * N takes.  With the defaults the result is the dict it always was.
+        ``max_new_tokens`` as one int per clip and / or ``video_lengths`` (see ``generate_tokens``): the codec decodes once per distinct
+        length (the clips grouped), "generated_audio" is (B, 1, T_max * hop) with zeros past each clip's end, and the result gains
+        "lengths" (B,) in frames and "audio_lengths" (B,) in samples.  With an int and no ``video_lengths`` nothing is added."""
         K = self.num_codebooks
         self._check_candidates(num_candidates, return_all_candidates, use_sampling, temp, rank_by, return_relevance)    # before the engine is touched
+        clip_params.resolve_lengths(frames.shape[0] if hasattr(frames, "shape") else None, max_new_tokens, video_lengths, None,
+                                    int(audio.shape[-1]) if (audio is not None and prompt_is_encoded) else 0)           # likewise
         extra = {}
         with off_null_stream(self.sampler.engine().dev) as caller:   # decode loop + codec leave HIP's null stream together
             out_codes = self.generate_tokens(
@@ -405,11 +442,26 @@ class VAURAModel(nn.Module):
                 return_attention_weights=return_attention_weights, check=check, use_sampling=use_sampling, temp=temp,
                 top_k=top_k, top_p=top_p, remove_prompts=remove_prompts, prompt_is_encoded=prompt_is_encoded,
                 cfg_scale=cfg_scale, return_logprobs=return_logprobs, num_candidates=num_candidates,
-                return_all_candidates=return_all_candidates, return_relevance=return_relevance, rank_by=rank_by)
+                return_all_candidates=return_all_candidates, return_relevance=return_relevance, rank_by=rank_by,
+                **(dict(video_lengths=video_lengths) if video_lengths is not None else {}))
             if isinstance(out_codes, dict):
                 extra = out_codes
                 out_codes = extra.pop("tokens")
-            generated_audio = self.audio_encoder.decode([(out_codes[..., :K, :], None)])
+            if "lengths" not in extra:
+                generated_audio = self.audio_encoder.decode([(out_codes[..., :K, :], None)])
+            else:
+                # one codec pass per distinct length: a clip's waveform is what decoding its own T_b frames gives, zeros behind it
+                rows = out_codes.shape[0]
+                row_len = extra["lengths"].repeat_interleave(rows // extra["lengths"].shape[0])      # (every take of a clip has its length)
+                generated_audio = None
+                for T_b in sorted(set(row_len.tolist())):
+                    idx = torch.nonzero(row_len == T_b)[:, 0]
+                    wav = self.audio_encoder.decode([(out_codes[idx][..., :K, :T_b], None)])
+                    if generated_audio is None:
+                        hop = wav.shape[-1] // T_b
+                        generated_audio = wav.new_zeros(rows, wav.shape[1], out_codes.shape[-1] * hop)
+                    generated_audio[idx, :, :wav.shape[-1]] = wav
+                extra["audio_lengths"] = extra["lengths"] * hop
         if caller is not None:
             out_codes.record_stream(caller)
             generated_audio.record_stream(caller)
