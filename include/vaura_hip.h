@@ -640,6 +640,18 @@ size_t vaura_audio_scratch_elems(int n_clips);
 int vaura_audio_loudness(const float* wav, float* out, int n_clips, int64_t n_samples, int sample_rate, float loudness_headroom_db,
                          int compressor, float energy_floor, float* scratch, vaura_stream_t s);
 size_t vaura_audio_loudness_scratch_elems(int n_clips);
+/* The two entry points above for the zero-padded waveform of a ragged batch (generate(max_new_tokens=[..]) -> "audio_lengths"): clip b
+ * occupies wav[b * n_stride, b * n_stride + n_b), n_b = lengths[b] (device, n_clips int32, 4-byte aligned).  Its statistics and its
+ * output samples [0, n_b) are the bits of a one-clip call of the entry point above with n_samples = n_b on those samples (everything
+ * derived from the length — the partition of the sums, the rms divisor, the gating blocks, "shorter than one block" — is derived
+ * from n_b); out[b, n_b:] is written as 0.0f; wav[b, n_b:] is never read (it may hold anything, NaN included).  Scratch: the same
+ * *_scratch_elems(n_clips); the loudness gains are per clip as above.  VAURA_ERR_ARG before any launch: lengths NULL or misaligned, a
+ * value outside 1 .. n_stride (the n_clips values are read back once; skipped while the stream is capturing).  VAURA_ERR_SHAPE for
+ * 'loudness' as above, from n_stride.                                                                                              */
+int vaura_audio_normalize_clips(const float* wav, float* out, int n_clips, int64_t n_stride, const int32_t* lengths, int strategy,
+                                int normalize, float peak_clip_headroom_db, float rms_headroom_db, float* scratch, vaura_stream_t s);
+int vaura_audio_loudness_clips(const float* wav, float* out, int n_clips, int64_t n_stride, const int32_t* lengths, int sample_rate,
+                               float loudness_headroom_db, int compressor, float energy_floor, float* scratch, vaura_stream_t s);
 
 /* -------------------------------------------------------------------------------------------
  * f2 (the step before the path) Segment-AVCLIP visual features: MotionFormer.forward

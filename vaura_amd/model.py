@@ -430,7 +430,9 @@ class VAURAModel(nn.Module):
         all B * N takes.  With the defaults the result is the dict it always was.
         ``max_new_tokens`` as one int per clip and / or ``video_lengths`` (see ``generate_tokens``): the codec decodes once per distinct
         length (the clips grouped), "generated_audio" is (B, 1, T_max * hop) with zeros past each clip's end, and the result gains
-        "lengths" (B,) in frames and "audio_lengths" (B,) in samples.  With an int and no ``video_lengths`` nothing is added."""
+        "lengths" (B,) in frames and "audio_lengths" (B,) in samples.  With an int and no ``video_lengths`` nothing is added.
+        The post stage takes that batch in one call: ``post.normalize_audio(r["generated_audio"], ..., lengths=r["audio_lengths"])``,
+        or ``post.scale_batch`` / ``post.save_wavs`` for the per-clip tensors and files."""
         K = self.num_codebooks
         self._check_candidates(num_candidates, return_all_candidates, use_sampling, temp, rank_by, return_relevance)    # before the engine is touched
         clip_params.resolve_lengths(frames.shape[0] if hasattr(frames, "shape") else None, max_new_tokens, video_lengths, None,
