@@ -278,7 +278,8 @@ typedef struct vaura_decoder_ext {
  * replay the same graph.  vaura_decode_step, vaura_generate_loop, vaura_step_graph_build and vaura_embed return VAURA_ERR_ARG for a
  * value outside its range (they read the arrays back: one small copy and a wait on the stream — under the rules of
  * vaura_decoder.clip_sampling: not for replays of a built graph, not while the stream is being captured; where nothing is read back
- * the kernels clamp a value to its upper bound, so nothing is read out of bounds).  vaura_score ignores clip_timesteps. */
+ * the kernels clamp a value to its upper bound, so nothing is read out of bounds).  vaura_score / vaura_score_relevance obey both
+ * arrays (see there: 2 <= T_b, scoring needs two timesteps). */
 typedef struct vaura_decoder_ext2 {
   vaura_decoder_ext ext;    /* ext.dec.ext_bytes = sizeof(vaura_decoder_ext2) - sizeof(vaura_decoder) */
   const int32_t* clip_timesteps;
@@ -454,7 +455,21 @@ void vaura_profile_outliers(int64_t* per_kind);
  * Outputs: nll (B, K, Ta) = logsumexp - target logit in fp32; mask_out (B, K, Ta) bytes (optional; 1 where t + d_q < n_pos, i.e.
  * all of them when n_pos = seq_len - 1 — delay patterns leave no timestep without a logit); logits_out (optional) the reverted
  * (B, K, Ta, vocab) logits, NaN rows where the mask is 0 (revert_pattern_logits' fill); loss_per_cb (K) = mean of the valid nll
- * of codebook q, loss (1) = sum_q loss_per_cb[q] / K.  Summation order is fixed: two calls give the same bits.                 */
+ * of codebook q, loss (1) = sum_q loss_per_cb[q] / K.  Summation order is fixed: two calls give the same bits.
+ * Per-clip lengths (the design chosen: this entry point and vaura_score_relevance are length-aware; there is no separate per-clip entry
+ * point, and the per-clip means are one more call, below).  With vaura_decoder_ext2.clip_timesteps clip b holds Ta_b = clip_timesteps[b]
+ * timesteps, 2 <= Ta_b <= dec->timesteps; dec->seq is vaura_pattern_build_clips of the codes with the special token from timestep
+ * Ta_b - 1 on (build_pattern_sequence(codes_b[..., :Ta_b - 1]) against a pattern of Ta_b steps), n_pos the positions of the longest
+ * clip.  An entry is valid iff t < Ta_b and t + d_q < n_pos: invalid entries get nll NaN, mask 0 and a NaN row of logits_out;
+ * loss_per_cb[q] is the mean over all valid (b, t) in the same fixed order (_compute_loss under the mask t < Ta_b), loss the mean of
+ * those.  targets behind Ta_b are not read.  Attention is causal, so clip b's valid entries are what the call on the clip alone gives;
+ * the rows of a finished clip are computed and ignored.  With clip_cond_tokens the embed of either path takes Tv_b as in the decode
+ * loop.  Both arrays are read back and range-checked once (one small copy and a wait on the stream; not while the stream is being
+ * captured), before any launch: VAURA_ERR_ARG for a value outside its range.  Both NULL: the launches and the bits of the call
+ * without the extension.
+ * Per-clip means: vaura_sequence_logprob_clips(lay, Ta + 1, zero delays, B, K, Ta, 0, clip_timesteps, per_codebook, per_clip) on
+ * lay (B, K, Ta + 1) = one unused leading step followed by nll — per_codebook (B, K) the mean of clip b's codebook q over t < Ta_b,
+ * per_clip (B) the mean of those over the codebooks, the loss clip b gets scored alone; fixed order, the entries behind Ta_b unread. */
 int vaura_score(const vaura_decoder* dec, int n_pos, const int32_t* targets, float* ws_chunk_logits, float* logits_out, float* nll,
                 uint8_t* mask_out, float* loss_per_cb, float* loss, vaura_stream_t s);
 /* vaura_score on a descriptor with the null-condition rows (dec->rows == 2 dec->batch; VAURA_ERR_ARG otherwise): the given codes are

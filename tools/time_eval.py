@@ -8,6 +8,17 @@ storage h2), B = 8 and 16 clips, no CFG branch.  Reports ms per batch and scored
 HIP events on one stream, median of `rounds`.
 
     python tools/time_eval.py [rounds] > profiles/eval_score_timing.txt
+
+Per-clip mode (``--clips``): 16 clips, Ta = 220, h2, the four routes taken in turn within every round (alternating: whatever else
+shares the machine hits all of them alike), median / min / max over the rounds of
+  a  score()                                          one length
+  b  score_clips, every length 220                    the per-clip kernels on the same schedule: expected = a within a's spread
+  c  score_clips, lengths 220 / 165 / 110 / 55 (four clips each) in one call
+  d  the same clips as one score() call per distinct length (4 clips each): the only route without score_clips.  Two figures: on
+     ONE engine, which re-prepares its workspaces for every new shape (d_one_engine), and on four engines that each keep their shape
+     (d_prepared: the weights four times in memory, nothing re-prepared — the floor of this route)
+
+    python tools/time_eval.py --clips [rounds] > profiles/eval_score_clips_timing.txt
 """
 import ctypes as C
 import json
@@ -35,7 +46,56 @@ def _time(stream, fn, rounds):
     return statistics.median(ts), min(ts), max(ts)
 
 
+def _stats(ts):
+    return {"median_ms": statistics.median(ts), "min_ms": min(ts), "max_ms": max(ts)}
+
+
+def clips_mode(rounds):
+    dev = torch.device("cuda:0")
+    cfg = synth.FULL_SAMPLER
+    sd = synth.sampler_state_dict(cfg, seed=0, round_bf16=False)
+    B, Ta, K = 16, 220, cfg.num_codebooks
+    distinct = [220, 165, 110, 55]
+    lengths = [t for t in distinct for _ in range(B // len(distinct))]
+    eng = DecoderEngine(cfg, sd, dev, wdtype="h2")
+    per_len = [DecoderEngine(cfg, sd, dev, wdtype="h2") for _ in distinct]
+    stream = torch.cuda.Stream(dev)
+    with torch.cuda.stream(stream):
+        feats = synth.video_features(B, seed=0).to(dev)
+        codes = torch.randint(0, 1024, (B, K, Ta), generator=torch.Generator().manual_seed(7)).to(dev)
+        groups = [(codes[i * 4:i * 4 + 4, :, :t].contiguous(), feats[i * 4:i * 4 + 4].contiguous()) for i, t in enumerate(distinct)]
+        routes = {
+            "a_score": lambda: eng.score(codes, feats, checked=False),
+            "b_score_clips_equal": lambda: eng.score_clips(codes, feats, [Ta] * B, checked=False),
+            "c_score_clips_mixed": lambda: eng.score_clips(codes, feats, lengths, checked=False),
+            "d_one_engine": lambda: [eng.score(c, f, checked=False) for c, f in groups],
+            "d_prepared": lambda: [e.score(c, f, checked=False) for e, (c, f) in zip(per_len, groups)],
+        }
+        for fn in routes.values():                                            # warm-up (workspaces of every shape)
+            fn()
+        torch.cuda.synchronize()
+        ts = {k: [] for k in routes}
+        for _ in range(rounds):
+            for k, fn in routes.items():
+                a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                a.record(stream)
+                fn()
+                b.record(stream)
+                torch.cuda.synchronize()
+                ts[k].append(a.elapsed_time(b))
+    rec = {"shape": {"B": B, "Ta": Ta, "storage": eng.wdtype, "lengths": lengths, "rounds": rounds}, "routes": {k: _stats(v) for k, v in ts.items()}}
+    for k, v in rec["routes"].items():
+        print(f"{k:22s} median {v['median_ms']:8.2f} ms   min {v['min_ms']:8.2f}   max {v['max_ms']:8.2f}", flush=True)
+    m = {k: v["median_ms"] for k, v in rec["routes"].items()}
+    print(f"b / a = {m['b_score_clips_equal'] / m['a_score']:.4f}   d_one_engine / c = {m['d_one_engine'] / m['c_score_clips_mixed']:.3f}   "
+          f"d_prepared / c = {m['d_prepared'] / m['c_score_clips_mixed']:.3f}")
+    print(json.dumps(rec))
+
+
 def main():
+    if "--clips" in sys.argv[1:]:
+        rest = [a for a in sys.argv[1:] if a != "--clips"]
+        return clips_mode(int(rest[0]) if rest else 9)
     rounds = int(sys.argv[1]) if len(sys.argv) > 1 else 5
     dev = torch.device("cuda:0")
     cfg = synth.FULL_SAMPLER

@@ -159,3 +159,37 @@ def refuse_lengths(where: str, max_new_tokens=None, video_lengths=None) -> None:
     if is_per_clip(max_new_tokens) or video_lengths is not None:
         raise _error(f"{where} takes one length for the whole call: per-clip lengths (a max_new_tokens / duration sequence, video_lengths) "
                      "are served by generate() / generate_tokens() only")
+
+
+# ---- per-clip lengths of one teacher-forced scoring call (DecoderEngine.score_clips): Ta_b timesteps of clip b's codes and Tv_b video
+# tokens.  Scoring feeds codes[..., :Ta_b - 1], so a clip needs two timesteps.
+def resolve_score_lengths(batch: int, timesteps: int, lengths=None, video_lengths=None, n_video_tokens: Optional[int] = None):
+    """([Ta_b] or None, [Tv_b] or None) of a scoring call over ``batch`` clips padded to ``timesteps``.  ``lengths``: None (every clip
+    has ``timesteps``) or one int per clip, 2 <= Ta_b <= ``timesteps``; ``video_lengths`` as in ``resolve_lengths``."""
+    lens = None
+    if lengths is not None:
+        if not is_per_clip(lengths):
+            raise _error(f"lengths must be one integer per clip (a list, tuple or 1-D tensor), got {lengths!r}")
+        lens = _int_list("lengths", lengths)
+        if len(lens) != batch:
+            raise _error(f"per-clip lengths has {len(lens)} values for a batch of {batch} clips")
+        if min(lens) < 2 or max(lens) > timesteps:
+            raise _error(f"per-clip lengths must lie in 2 .. {timesteps} (scoring needs at least 2 timesteps: the input is "
+                         f"codes[..., :-1]; the codes hold {timesteps}), got {lens}")
+    _, _, tv = resolve_lengths(batch, timesteps, video_lengths, n_video_tokens)
+    return lens, tv
+
+
+def score_list_lengths(codes, num_codebooks: int) -> List[int]:
+    """The lengths of a list of per-clip code tensors (K, Ta_b) / (1, K, Ta_b), from their shapes alone; another layout is refused."""
+    if not isinstance(codes, (list, tuple)) or not codes:
+        raise _error("codes must be one (B, K, Ta) tensor or a non-empty list of per-clip (K, Ta_b) tensors")
+    lens = []
+    for b, c in enumerate(codes):
+        shape = tuple(getattr(c, "shape", ()))
+        if len(shape) == 3 and shape[0] == 1:
+            shape = shape[1:]
+        if len(shape) != 2 or shape[0] != num_codebooks:
+            raise _error(f"codes of clip {b} must be ({num_codebooks}, Ta_b) or (1, {num_codebooks}, Ta_b), got {tuple(getattr(c, 'shape', ()))}")
+        lens.append(int(shape[1]))
+    return lens

@@ -563,6 +563,9 @@ int vaura_profile_loop(const vaura_decoder* dec, const vaura_sampling* sp, int n
 
 // vaura_score, and with nll_null its twin over the null-condition rows [B, 2B) of a doubled descriptor (vaura_score_relevance): the same
 // prefill, the NLL kernel launched once more per chunk on the logits of those rows, the reduction once more on their nll.
+// Per-clip lengths (vaura_decoder_ext2): with clip_timesteps the NLL kernel and the reduction take Ta_b for clip b (2 <= Ta_b <= timesteps:
+// scoring needs two timesteps), with clip_cond_tokens the embed of either path takes Tv_b; both are read back and checked once, here,
+// before any launch.  Both NULL: the launches every call ran before.
 static int score_rows(const vaura_decoder* dec, int n_pos, const int32_t* targets, float* ws_chunk_logits, float* logits_out, float* nll,
                       uint8_t* mask_out, float* loss_per_cb, float* loss, float* nll_null, float* loss_per_cb_null, float* loss_null,
                       vaura_stream_t s) {
@@ -576,6 +579,9 @@ static int score_rows(const vaura_decoder* dec, int n_pos, const int32_t* target
   const int B = dec->batch, K = m.n_codebooks, V = m.vocab, Ta = dec->timesteps;
   const int32_t* delays = va_pattern_delays(dec);
   hipStream_t st = as_stream(s);
+  const int32_t* clip_T = va_clip_timesteps(dec);
+  if ((rc = va_check_clip_lengths(clip_T, B, 2, Ta, st))) return rc;
+  if ((rc = va_check_clip_lengths(va_clip_cond_tokens(dec), B, 1, dec->n_cond_tokens, st))) return rc;
   if (dec->ws_h_split && dec->prefill_positions > 0) {
     // the caller guarantees state[0] == 0 at entry (vaura_pattern_build + zeroed state), as for vaura_generate_loop's prefill
     if (!ws_chunk_logits) return VAURA_ERR_ARG;
@@ -584,9 +590,9 @@ static int score_rows(const vaura_decoder* dec, int n_pos, const int32_t* target
       const int n = (n_pos - p0 < dec->prefill_positions) ? n_pos - p0 : dec->prefill_positions;
       rc = enqueue_prefill_chunk_heads(dec, p0, n, ws_chunk_logits, st);
       if (rc) return rc;
-      rc = va_launch_score_nll(ws_chunk_logits, rp, p0, n, B, K, V, Ta, delays, targets, nll, logits_out, st);
+      rc = va_launch_score_nll(ws_chunk_logits, rp, p0, n, B, K, V, Ta, delays, targets, nll, logits_out, clip_T, st);
       if (rc) return rc;
-      if (nll_null) rc = va_launch_score_nll(ws_chunk_logits + (size_t)B * K * V, rp, p0, n, B, K, V, Ta, delays, targets, nll_null, nullptr, st);
+      if (nll_null) rc = va_launch_score_nll(ws_chunk_logits + (size_t)B * K * V, rp, p0, n, B, K, V, Ta, delays, targets, nll_null, nullptr, clip_T, st);
       if (rc) return rc;
     }
     rc = va_launch_advance(dec->state, n_pos, st);
@@ -596,22 +602,28 @@ static int score_rows(const vaura_decoder* dec, int n_pos, const int32_t* target
     // greedy sampler behind it only fills -1 slots, and a fully built pattern sequence has none.  Its status bits (non-finite logits)
     // stay in state[4] for the caller.
     vaura_sampling sp = {};
-    vaura_decoder plain = *dec;
+    vaura_decoder_ext2 copy = {};         // a copy of the descriptor with a zeroed extension behind it: no relevance buffers, and no
+    vaura_decoder& plain = copy.ext.dec;  // clip_timesteps — the step's sampler stays the instance it was, the lengths act in the NLL kernel
+    plain = *dec;
     plain.logprobs = nullptr;             // ... and reports no token log-probabilities
-    plain.ext_bytes = 0;                  // (a copy of the descriptor alone: nothing follows it)
+    plain.ext_bytes = 0;                  // (nothing follows the copy ...
     plain.clip_sampling = nullptr;        // scoring has no sampling parameters, per clip or otherwise
+    if (const int32_t* clip_tv = va_clip_cond_tokens(dec)) {      // ... but Tv_b, which the step's embed obeys as the prefill chunks' does)
+      plain.ext_bytes = (int32_t)(sizeof(vaura_decoder_ext2) - sizeof(vaura_decoder));
+      copy.clip_cond_tokens = clip_tv;
+    }
     for (int p = 0; p < n_pos; ++p) {
       rc = enqueue_step(&plain, &sp, 1, st);
       if (rc) return rc;
-      rc = va_launch_score_nll(dec->ws_logits, dec->rows, p, 1, B, K, V, Ta, delays, targets, nll, logits_out, st);
+      rc = va_launch_score_nll(dec->ws_logits, dec->rows, p, 1, B, K, V, Ta, delays, targets, nll, logits_out, clip_T, st);
       if (rc) return rc;
-      if (nll_null) rc = va_launch_score_nll(dec->ws_logits + (size_t)B * K * V, dec->rows, p, 1, B, K, V, Ta, delays, targets, nll_null, nullptr, st);
+      if (nll_null) rc = va_launch_score_nll(dec->ws_logits + (size_t)B * K * V, dec->rows, p, 1, B, K, V, Ta, delays, targets, nll_null, nullptr, clip_T, st);
       if (rc) return rc;
     }
   }
-  rc = va_launch_score_reduce(nll, mask_out, logits_out, B, K, V, Ta, n_pos, delays, loss_per_cb, loss, st);
+  rc = va_launch_score_reduce(nll, mask_out, logits_out, B, K, V, Ta, n_pos, delays, loss_per_cb, loss, clip_T, st);
   if (rc || !nll_null) return rc;
-  return va_launch_score_reduce(nll_null, nullptr, nullptr, B, K, V, Ta, n_pos, delays, loss_per_cb_null, loss_null, st);
+  return va_launch_score_reduce(nll_null, nullptr, nullptr, B, K, V, Ta, n_pos, delays, loss_per_cb_null, loss_null, clip_T, st);
 }
 
 extern "C" {

@@ -300,11 +300,11 @@ int va_launch_linear_pair(const uint16_t* in, const uint16_t* w, const float* bi
                           uint16_t* out_act, int act, int B, int Lin, int Lout, int oshift, int Cin, int Cout, hipStream_t s);
 int va_launch_rope_append(const vaura_decoder* d, int layer, int p0, int n_pos, hipStream_t s);
 int va_launch_attention_prefill(const vaura_decoder* d, int layer, int p0, int n_pos, hipStream_t s);
-// teacher-forced scoring (score.hip)
+// teacher-forced scoring (score.hip); clip_T: per-clip timesteps (vaura_decoder_ext2.clip_timesteps) or NULL: every clip has Ta
 int va_launch_score_nll(const float* logits, int rows_per_pos, int p0, int n_pos, int B, int K, int V, int Ta, const int32_t* delays_host,
-                        const int32_t* targets, float* nll, float* logits_out, hipStream_t s);
+                        const int32_t* targets, float* nll, float* logits_out, const int32_t* clip_T, hipStream_t s);
 int va_launch_score_reduce(float* nll, uint8_t* mask, float* logits_out, int B, int K, int V, int Ta, int n_scored, const int32_t* delays_host,
-                           float* loss_per_cb, float* loss, hipStream_t s);
+                           float* loss_per_cb, float* loss, const int32_t* clip_T, hipStream_t s);
 
 // Epoch of an in-launch hand-off (mlp_engine.h, the attention + wo experiment): neither the flag words in global memory nor the arrival
 // words in LDS are ever reset — a hand-off passes when every producer's word holds THIS launch's epoch — so no two launches that can

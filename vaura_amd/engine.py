@@ -927,11 +927,58 @@ class DecoderEngine:
         over the timesteps per clip and codebook, in the fixed order of ``vaura_sequence_logprob`` —, "relevance_per_codebook" (B, K)
         = nll_null_per_codebook - nll_per_codebook (how many nats per token the video explains) and "relevance" (B,), its mean over
         the codebooks.  Today's entries are the bits of the call without the flag.
-        One length per call: a list of code tensors, or ``video_lengths``, is refused."""
+        One length per call: a list of code tensors, or ``video_lengths``, is refused (``score_clips`` serves them)."""
         c = self.cfg
         if not torch.is_tensor(codes) or video_lengths is not None:      # one length per call here (a projected video row depends on its own input row only: pad the features)
             raise L.VauraHipError("score() takes one length for the whole call — one (B, K, Ta) tensor of codes, no video_lengths: per-clip "
-                                  "lengths are served by generate() / generate_tokens() only")
+                                  "lengths are served by score_clips() (and by generate() / generate_tokens())")
+        return self._score(codes, feats, None, None, delays, tokens_per_frame, return_logits, checked, relevance, False)
+
+    @torch.no_grad()
+    def score_clips(self, codes, feats: torch.Tensor, lengths=None, *, video_lengths=None, delays: Optional[Sequence[int]] = None,
+                    tokens_per_frame: int = 7, return_logits: bool = False, checked: bool = True,
+                    relevance: bool = False) -> Dict[str, torch.Tensor]:
+        """``score`` for clips of different lengths in ONE call: clip b is scored over its own ``Ta_b`` timesteps and its own ``Tv_b``
+        video tokens, as ``score(codes[b:b + 1, :, :Ta_b], feats[b:b + 1, :Tv_b])`` scores it — attention is causal, so nothing behind a
+        clip's end reaches a position before it: exact, not an approximation.
+        ``codes``: a (B, K, Ta) tensor with ``lengths`` one int per clip, 2 <= Ta_b <= Ta (None: every clip has Ta), or a list of B
+        tensors (K, Ta_b) / (1, K, Ta_b), padded here (``lengths`` then comes from the shapes).  What ``codes`` holds from timestep Ta_b
+        on never matters (it is not range-checked either).  ``video_lengths``: as in ``generate_codes`` — positions whose frame is >=
+        Tv_b take ``empty_video_emb``; ``feats[b, Tv_b:]`` does not matter.
+        Clip b's input is ``build_pattern_sequence(codes_b[..., :Ta_b - 1])`` against a pattern of Ta_b timesteps
+        (``vaura_pattern_build_clips``), the call runs the S_max - 1 positions of the longest clip, and the scoring kernels take Ta_b
+        (csrc/score.hip ``score_nll_clips_kernel`` / ``score_reduce_clips_kernel``; a finished clip's rows are computed and ignored).
+        Returns what ``score`` returns — "loss_per_codebook"[q] the mean over ALL valid (b, t), the reference's ``_compute_loss`` under
+        the mask t < Ta_b, "loss" the mean of those; "nll" / "logits" NaN and "mask" False behind each clip's end — plus "lengths" (B,)
+        int32, "nll_per_codebook" (B, K): the mean of clip b's codebook q over t < Ta_b, and "loss_per_clip" (B,): its mean over the
+        codebooks, the loss clip b gets scored alone (``vaura_sequence_logprob_clips``: fixed order, two calls give the same bits).
+        ``relevance``: the null-condition twins of ``score`` and "relevance_per_codebook" / "relevance", all over clip b's own frames.
+        Everything wrong with the lengths is refused before any device work (``clip_params.resolve_score_lengths``)."""
+        c = self.cfg
+        K = c.num_codebooks
+        if torch.is_tensor(codes):
+            if codes.dim() != 3 or codes.shape[1] != K:
+                raise L.VauraHipError(f"codes must be (B, {K}, Ta), got {tuple(codes.shape)}")
+            B, Ta = int(codes.shape[0]), int(codes.shape[2])
+        else:
+            shapes = clip_params.score_list_lengths(codes, K)
+            if lengths is not None and clip_params._int_list("lengths", lengths) != shapes:
+                raise L.VauraHipError(f"lengths {list(lengths)} given next to a list of codes whose shapes say {shapes}")
+            lengths, B, Ta = shapes, len(shapes), max(shapes)
+        if feats.dim() != 3 or feats.shape[0] != B or feats.shape[2] != c.cond_in:
+            raise L.VauraHipError(f"feats must be ({B}, Tv, {c.cond_in}), got {tuple(feats.shape)}")
+        lens, tv = clip_params.resolve_score_lengths(B, Ta, lengths, video_lengths, int(feats.shape[1]))
+        if not torch.is_tensor(codes):         # pad with a valid id: never read as a target, never fed (the special token stands there)
+            padded = torch.zeros(B, K, Ta, dtype=torch.int64, device=self.dev)
+            for b, cb in enumerate(codes):
+                padded[b, :, :lens[b]] = cb.reshape(K, -1).to(self.dev)
+            codes = padded
+        return self._score(codes, feats, lens, tv, delays, tokens_per_frame, return_logits, checked, relevance, True)
+
+    def _score(self, codes, feats, lengths, video_lengths, delays, tokens_per_frame, return_logits, checked, relevance, per_clip):
+        """``score`` (lengths and video_lengths None, per_clip False: the launches and the bits it always had) and ``score_clips``
+        (checked lists of per-clip lengths or None; per_clip: the per-clip entries of the result)."""
+        c = self.cfg
         if codes.dim() != 3 or codes.shape[1] != c.num_codebooks:
             raise L.VauraHipError(f"codes must be (B, {c.num_codebooks}, Ta), got {tuple(codes.shape)}")
         B, K, Ta = codes.shape
@@ -945,17 +992,30 @@ class DecoderEngine:
             raise L.VauraHipError(f"{Ta} timesteps under the delays {list(dl) if dl else list(range(K))} need {S} sequence steps; the "
                                   f"model's block_size is {c.block_size}")
         codes_d = codes.to(self.dev)
-        if bool(((codes_d < 0) | (codes_d >= c.d_codebook)).any()):
+        bad = (codes_d < 0) | (codes_d >= c.d_codebook)
+        last = None                        # (B, 1, 1): the last timestep of every clip, Ta_b - 1
+        if lengths is not None:            # only a clip's own Ta_b columns are its codes
+            last = torch.tensor(lengths, device=self.dev).view(B, 1, 1) - 1
+            bad &= torch.arange(Ta, device=self.dev).view(1, 1, Ta) <= last
+        if bool(bad.any()):
             raise L.VauraHipError(f"codes must lie in [0, {c.d_codebook}) (the reference's cross_entropy refuses other targets)")
         targets = codes_d.to(torch.int32).contiguous()
         self._fc = None                    # the K/V cache is about to be reused: forward_cached must start over
         with off_null_stream(self.dev) as caller:
             self.prepare(B, Ta, feats.shape[1], bool(relevance), tokens_per_frame, block_size=c.block_size, delays=dl)
-            self._set_lengths(None, None)      # scoring keeps one length per call
+            self._set_lengths(lengths, video_lengths)      # score(): (None, None), one length per call
             self.set_condition(feats)
-            self.codes_i32[..., :Ta - 1] = targets[..., :Ta - 1]
-            self.codes_i32[..., Ta - 1] = c.d_codebook             # build_pattern_sequence(codes[..., :-1]): no input beyond Ta - 2
-            if self.delays is None:
+            if lengths is None:
+                self.codes_i32[..., :Ta - 1] = targets[..., :Ta - 1]
+                self.codes_i32[..., Ta - 1] = c.d_codebook             # build_pattern_sequence(codes[..., :-1]): no input beyond Ta - 2
+            else:                          # clip b: build_pattern_sequence(codes_b[..., :Ta_b - 1]) — the special id from Ta_b - 1 on
+                self.codes_i32.copy_(torch.where(torch.arange(Ta, device=self.dev).view(1, 1, Ta) < last, targets,
+                                                 torch.full_like(targets, c.d_codebook)))
+            if lengths is not None:
+                L.check(self.lib.vaura_pattern_build_clips(L.ptr(self.codes_i32), L.ptr(self.seq), B, K, Ta, self.S, c.d_codebook,
+                                                           self._delays_arg(), L.ptr(self.clip_T), L.current_stream(self.dev)),
+                        "vaura_pattern_build_clips")
+            elif self.delays is None:
                 L.check(self.lib.vaura_pattern_build(L.ptr(self.codes_i32), L.ptr(self.seq), B, K, Ta, c.d_codebook,
                                                      L.current_stream(self.dev)), "vaura_pattern_build")
             else:
@@ -980,8 +1040,12 @@ class DecoderEngine:
             out = {"loss": loss, "loss_per_codebook": lpc, "nll": nll, "mask": mask.bool()}
             if return_logits:
                 out["logits"] = logits
+            if per_clip:
+                pcb, clip = self._clip_means(nll)
+                out.update({"lengths": torch.tensor(lengths if lengths is not None else [Ta] * B, dtype=torch.int32, device=self.dev),
+                            "nll_per_codebook": pcb, "loss_per_clip": clip})
             if relevance:
-                pcb, pcb0 = self._clip_codebook_means(nll), self._clip_codebook_means(nll0)
+                pcb, pcb0 = out["nll_per_codebook"] if per_clip else self._clip_codebook_means(nll), self._clip_codebook_means(nll0)
                 rpc = pcb0 - pcb
                 out.update({"nll_null": nll0, "loss_null": loss0, "loss_null_per_codebook": lpc0, "nll_per_codebook": pcb,
                             "nll_null_per_codebook": pcb0, "relevance_per_codebook": rpc, "relevance": rpc.sum(-1) / K})
@@ -1004,20 +1068,33 @@ class DecoderEngine:
                 warnings.warn("vaura_amd: teacher-forced scoring gave a non-finite loss (an activation left the fp16-plane range); this "
                               "call is re-run on the exact-fp32 twin engine (slower, ~2.7 GB more)")
             self.range_fallbacks += 1
+            if per_clip:                   # the twin scores the same clips: their lengths go with them
+                return self._twin().score_clips(codes, feats, lengths, video_lengths=video_lengths, delays=delays,
+                                                tokens_per_frame=tokens_per_frame, return_logits=return_logits, relevance=relevance)
             return self._twin().score(codes, feats, delays=delays, tokens_per_frame=tokens_per_frame, return_logits=return_logits,
                                       relevance=relevance)
         return out
 
     def _clip_codebook_means(self, nll: torch.Tensor) -> torch.Tensor:
-        """(B, K, Ta) -> (B, K): the mean over the timesteps of every (clip, codebook), by the fixed-order reduction of the token
-        log-probabilities (``vaura_sequence_logprob``) — the tensor read as a pattern layout of zero delays, one unused leading step."""
+        """(B, K, Ta) -> (B, K): the mean over the timesteps of every (clip, codebook) — ``_clip_means`` without the clip's own mean."""
+        return self._clip_means(nll)[0]
+
+    def _clip_means(self, nll: torch.Tensor):
+        """(B, K, Ta) -> ((B, K), (B,)): the mean over the timesteps of every (clip, codebook) and the mean of those over the codebooks,
+        by the fixed-order reduction of the token log-probabilities (``vaura_sequence_logprob``) — the tensor read as a pattern layout
+        of zero delays, one unused leading step.  With per-clip lengths set (``score_clips``) the means of clip b run over its own
+        t < Ta_b (``vaura_sequence_logprob_clips``), the NaN entries behind its end unread."""
         B, K, Ta = nll.shape
         lay = torch.zeros(B, K, Ta + 1, dtype=torch.float32, device=self.dev)
         lay[..., 1:] = nll
         pcb, clip = torch.empty(B, K, dtype=torch.float32, device=self.dev), torch.empty(B, dtype=torch.float32, device=self.dev)
+        if self.lengths is not None:
+            L.check(self.lib.vaura_sequence_logprob_clips(L.ptr(lay), Ta + 1, L.delays_host([0] * K), B, K, Ta, 0, L.ptr(self.clip_T),
+                                                          L.ptr(pcb), L.ptr(clip), L.current_stream(self.dev)), "vaura_sequence_logprob_clips")
+            return pcb, clip
         L.check(self.lib.vaura_sequence_logprob(L.ptr(lay), Ta + 1, L.delays_host([0] * K), B, K, Ta, 0, L.ptr(pcb), L.ptr(clip),
                                                 L.current_stream(self.dev)), "vaura_sequence_logprob")
-        return pcb
+        return pcb, clip
 
 
 @torch.no_grad()

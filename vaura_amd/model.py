@@ -501,7 +501,8 @@ class VAURAModel(nn.Module):
         return int(math.ceil(n / n_video_tokens))
 
     @torch.no_grad()
-    def forward(self, frames: torch.Tensor, audio: torch.Tensor, clip_indices: Optional[torch.Tensor] = None):
+    def forward(self, frames: torch.Tensor, audio: torch.Tensor, clip_indices: Optional[torch.Tensor] = None, *, audio_lengths=None,
+                video_lengths=None):
         """Teacher-forced pass of the reference (vaura_model.py:136-192): frames (B, C, Tv, H, W) and mono audio (B, 1, N) ->
         (logits (B, K, Ta, card), logits_mask (B, K, Ta) bool, aud_feats (B, 9, Ta)).  ``audio_encoder.encode`` (the HIP DAC encode)
         gives the codes, the visual condition comes from ``_handle_visual_conditioning``, and ``DecoderEngine.score`` runs the
@@ -511,31 +512,68 @@ class VAURAModel(nn.Module):
             are taken from ``pattern_provider.get_pattern(Ta)`` for each call's own ``Ta`` (``_pattern_delays``);
           * a ``sampler.audio_tokens_per_video_frame`` of None is set from the sequence as llama.py:_set_audio_tokens_per_video_frame
             does (and kept, as there); ``Transformer.forward`` itself still refuses None.
-        Delay patterns give every timestep a logit, so the mask is all true and no reverted row is NaN."""
-        aud_feats = self.audio_encoder.encode(audio)
+        Delay patterns give every timestep a logit, so the mask is all true and no reverted row is NaN.
+        A padded batch of clips of different durations: ``audio_lengths`` — one int per clip, the samples of ``audio[b]`` that are real —
+        and / or ``video_lengths`` (one int per clip, the leading video tokens that are real, as in ``generate``).  The audio is then
+        encoded once per distinct length, each group cut to its own samples, so clip b's codes are those of the clip encoded alone
+        (``Ta_b`` = what the encoder returns for its samples; ``aud_feats`` is padded with 0 to the longest), the clips are scored in
+        one ``DecoderEngine.score_clips`` call, and ``logits_mask[b, :, t]`` = t < Ta_b (the logits rows behind it are NaN):
+        ``_compute_loss`` under that mask is the loss of the real frames.  With neither keyword every path is the one it was."""
+        aud_feats, lengths = self._encode_clips(audio, audio_lengths)
         B, _, Ta = aud_feats.shape
         vis = self._handle_visual_conditioning(frames, clip_indices, B)
         if vis is None:
             raise NotImplementedError("unconditional scoring: the llama sampler always needs video features (llama.py:474-476)")
-        r = self._score(aud_feats[:, :self.num_codebooks], vis, return_logits=True)
+        r = self._score(aud_feats[:, :self.num_codebooks], vis, return_logits=True, lengths=lengths, video_lengths=video_lengths)
         return r["logits"], r["mask"], aud_feats
 
+    def _encode_clips(self, audio: torch.Tensor, audio_lengths=None):
+        """``audio_encoder.encode`` of a padded batch -> (codes (B, Kc, Ta_max), [Ta_b] or None).  ``audio_lengths`` None: one encode of
+        the whole batch, as ever.  Otherwise one encode per distinct length, each group cut to its own samples — a clip encoded with
+        zero padding behind it is not the clip — as ``generate`` decodes once per distinct length; frames behind Ta_b hold 0."""
+        if audio_lengths is None:
+            return self.audio_encoder.encode(audio), None
+        if not clip_params.is_per_clip(audio_lengths):
+            raise L.VauraHipError(f"audio_lengths must be one integer per clip (a list, tuple or 1-D tensor), got {audio_lengths!r}")
+        n = clip_params._int_list("audio_lengths", audio_lengths)
+        if len(n) != audio.shape[0]:
+            raise L.VauraHipError(f"audio_lengths has {len(n)} values for a batch of {audio.shape[0]} clips")
+        if min(n) < 1 or max(n) > audio.shape[-1]:
+            raise L.VauraHipError(f"audio_lengths must lie in 1 .. {audio.shape[-1]} (the samples of the padded batch), got {n}")
+        groups = []
+        for n_b in sorted(set(n)):
+            idx = torch.tensor([b for b, v in enumerate(n) if v == n_b], device=audio.device)
+            groups.append((idx, self.audio_encoder.encode(audio[idx][..., :n_b])))
+        ta_max = max(int(c.shape[-1]) for _, c in groups)
+        codes = groups[0][1].new_zeros(len(n), groups[0][1].shape[1], ta_max)
+        lengths = [0] * len(n)
+        for idx, c in groups:
+            codes[idx.to(codes.device), :, :c.shape[-1]] = c
+            for b in idx.tolist():
+                lengths[b] = int(c.shape[-1])
+        return codes, lengths
+
     @torch.no_grad()
-    def score_relevance(self, frames: torch.Tensor, audio: torch.Tensor, clip_indices: Optional[torch.Tensor] = None) -> dict:
+    def score_relevance(self, frames: torch.Tensor, audio: torch.Tensor, clip_indices: Optional[torch.Tensor] = None, *,
+                        audio_lengths=None, video_lengths=None) -> dict:
         """How much of GIVEN audio the video explains: ``forward``'s inputs (frames, mono audio (B, 1, N)) -> ``DecoderEngine.score(...,
         relevance=True)`` of the audio's codes: the teacher-forced cross-entropy under the video ("nll", "nll_per_codebook", "loss",
         "loss_per_codebook") and under the null condition ("nll_null", "nll_null_per_codebook", ...), "relevance_per_codebook" (B, K) =
         nll_null_per_codebook - nll_per_codebook and "relevance" (B,), its mean over the codebooks — nats per token; plus "codes"
-        (B, K, Ta), the audio's codes.  ``forward`` / ``test_step`` do not go through here."""
-        aud_feats = self.audio_encoder.encode(audio)
+        (B, K, Ta), the audio's codes.  ``forward`` / ``test_step`` do not go through here.
+        ``audio_lengths`` / ``video_lengths``: a padded batch, as in ``forward`` — every per-clip entry then runs over clip b's own
+        frames (``DecoderEngine.score_clips``), "codes" is padded with 0 and the result holds "lengths" (B,)."""
+        aud_feats, lengths = self._encode_clips(audio, audio_lengths)
         vis = self._handle_visual_conditioning(frames, clip_indices, aud_feats.shape[0])
         if vis is None:
             raise NotImplementedError("unconditional scoring: the llama sampler always needs video features (llama.py:474-476)")
         codes = aud_feats[:, :self.num_codebooks]
-        return dict(self._score(codes, vis, relevance=True), codes=codes)
+        return dict(self._score(codes, vis, relevance=True, lengths=lengths, video_lengths=video_lengths), codes=codes)
 
-    def _score(self, codes: torch.Tensor, vis: torch.Tensor, return_logits: bool = False, relevance: bool = False) -> dict:
-        """DecoderEngine.score with this model's delays (per call) and tokens per video frame (auto-set rule when None)."""
+    def _score(self, codes: torch.Tensor, vis: torch.Tensor, return_logits: bool = False, relevance: bool = False, lengths=None,
+               video_lengths=None) -> dict:
+        """DecoderEngine.score — with per-clip lengths ``score_clips`` — with this model's delays (per call) and tokens per video frame
+        (auto-set rule when None)."""
         K = self.num_codebooks
         Ta = int(codes.shape[-1])
         delays = self._pattern_delays(Ta)
@@ -546,9 +584,11 @@ class VAURAModel(nn.Module):
             self.sampler.audio_tokens_per_video_frame = self._auto_tokens_per_frame(
                 S, int(vis.shape[1]), getattr(self.sampler, "codebook_pattern", None), K)
         eng = self.sampler.engine()
-        return eng.score(codes, vis.float(), delays=None if delays == list(range(K)) else delays,
-                         tokens_per_frame=self.sampler.audio_tokens_per_video_frame, return_logits=return_logits,
-                         **(dict(relevance=True) if relevance else {}))
+        kw = dict(delays=None if delays == list(range(K)) else delays, tokens_per_frame=self.sampler.audio_tokens_per_video_frame,
+                  return_logits=return_logits, **(dict(relevance=True) if relevance else {}))
+        if lengths is not None or video_lengths is not None:
+            return eng.score_clips(codes, vis.float(), lengths, video_lengths=video_lengths, **kw)
+        return eng.score(codes, vis.float(), **kw)
 
     @torch.no_grad()
     def _compute_loss(self, logits: torch.Tensor, targets: torch.Tensor, mask: torch.Tensor) -> Tuple[torch.Tensor, List[torch.Tensor]]:
@@ -573,7 +613,9 @@ class VAURAModel(nn.Module):
         """vaura_model.py:282-295 -> (logits, target codes, loss, loss_per_codebook)."""
         audio = batch["audio"] if self.flatten_vis_feats else self._stack_list_repr(batch["audio"], to_3dim=True)
         frames = batch["frames"]
-        logits, logits_mask, target = self.forward(frames, audio, batch.get("meta", {}).get("clip_indices", None))
+        # a padded batch of clips of different durations says so: "audio_lengths" (samples) / "video_lengths" (video tokens) per clip
+        ragged = {k: batch[k] for k in ("audio_lengths", "video_lengths") if batch.get(k) is not None}
+        logits, logits_mask, target = self.forward(frames, audio, batch.get("meta", {}).get("clip_indices", None), **ragged)
         loss, loss_per_cb = self._compute_loss(logits, target[:, :self.num_codebooks, :], logits_mask)
         return logits, target, loss, loss_per_cb
 
