@@ -597,6 +597,37 @@ size_t vaura_dac_workspace_elems(const vaura_codec* c, int B, int T);
  * Lout = Lin * stride.  `scratch` (>= B*Lin*Cin floats) receives the input in the precision's activation format.   */
 int vaura_dac_conv(const vaura_conv* cv, int precision, const float* in, float* out, float* scratch, int B, int Lin,
                    vaura_stream_t s);
+/* Op-level access for parity tests: vaura_dac_conv with the epilogue of the decode path — exactly the launch vaura_dac_decode /
+ * vaura_dac_encode make for one convolution.  in (B, Lin, Cin) fp32, already activated (converted into `scratch` as above; for
+ * precision 0 scratch may be NULL).  res (B, Lout, Cout) fp32 or NULL: added to conv(in) + bias.  out_raw (B, Lout, Cout) fp32 or NULL:
+ * that sum.  out_act or NULL (then alpha may be NULL): Snake(alpha) of it in the precision's own activation format: fp32 (B, Lout, Cout)
+ * for precision 0; pair planes [row][Cout/8][hi|lo][8] halves for 1, 2 and 4; for 3 e4m3 bytes (B, Lout, Cout) followed, at byte
+ * ((B*Lout*Cout + 15) & ~15), by (B * Lout, ceil(Cout/128)) words of four E8M0 bytes, one per 32 channels (4 * B*Lout*Cout bytes hold
+ * both).  At least one of out_raw / out_act.  VAURA_ERR_ARG / VAURA_ERR_SHAPE as vaura_dac_conv; out_act without alpha: VAURA_ERR_ARG. */
+int vaura_dac_conv_ex(const vaura_conv* cv, int precision, const float* in, const float* res, const float* alpha, float* out_raw,
+                      void* out_act, float* scratch, int B, int Lin, vaura_stream_t s);
+/* Returned by vaura_dac_unit when the unit is not eligible for the one-launch kernel (shape, precision, fewer than 384 workgroups, or
+ * debug flag bit 20 / 21): not an error.                                                                                               */
+#define VAURA_DAC_UNIT_TWO_LAUNCHES (-100)
+/* Op-level access for parity tests: ONE residual unit of the decoder, out = res + c1(Snake(alpha_mid)(c7(in))), as vaura_dac_decode runs
+ * it.  in (B, L, C) fp32 = Snake of the unit's input, already applied; res (B, L, C) fp32 the unit's input; out_raw (NULL ok) and out_act
+ * (required; Snake(alpha_next) of out) as for vaura_dac_conv_ex.  Returns 0 when the unit ran as ONE launch (vaura_debug_counter(1)
+ * counts those).  Otherwise VAURA_DAC_UNIT_TWO_LAUNCHES: with `mid` (4 * B*L*C bytes; receives c7's activated output in the precision's
+ * format) the two convolutions were launched one after the other and the outputs are valid, with mid = NULL nothing was launched.
+ * out_act must not alias in / scratch.                                                                                                  */
+int vaura_dac_unit(const vaura_conv* c7, const vaura_conv* c1, int precision, const float* in, const float* res,
+                   const float* alpha_mid, const float* alpha_next, float* out_raw, void* out_act, float* scratch, float* mid, int B,
+                   int L, vaura_stream_t s);
+/* Op-level access for parity tests: quantizer.from_codes as vaura_dac_decode launches it.  codes (B, K, T) int32, codebooks (K, size,
+ * dim), out_proj_w (K, latent, dim), out_proj_b (K, latent) -> z (B, T, latent): fp32 for pairs = 0, pair planes otherwise.
+ * K <= 16, dim <= 8, latent % 8 == 0 (VAURA_ERR_SHAPE).  Codes are not range-checked.                                                  */
+int vaura_dac_from_codes(const int32_t* codes, const float* codebooks, const float* out_proj_w, const float* out_proj_b, void* z,
+                         int B, int K, int T, int size, int dim, int latent, int pairs, vaura_stream_t s);
+/* Op-level access for parity tests: the decoder's last convolution (C -> 1, k = 7, tanh; cv->w fp32 [7][C]) with the dispatch of
+ * vaura_dac_decode (debug flag bit 13: the untiled kernel).  in (B, L, C) fp32, converted into `scratch` (>= B*L*C floats) in the
+ * activation format of `precision` (0: read as is; 1, 2, 4: pair planes; 3: mx8) -> wav (B, L) fp32.                                   */
+int vaura_dac_conv_out(const vaura_conv* cv, int precision, const float* in, float* wav, float* scratch, int B, int L,
+                       vaura_stream_t s);
 /* Op-level access for parity tests: the codec's activation, Snake1d of descript-audio-codec 1.0.0 (dac/nn/layers.py: x + (alpha + 1e-9)^-1 *
  * sin(alpha x)^2), exactly as every conv epilogue of the decoder / encoder applies it.  x, y (rows, C) fp32 channels-last, alpha (C).
  * The sine is an own restatement (period-pi reduction of sin^2 + a degree-9 odd polynomial, csrc/dac.hip::snake_sin2): max abs error
@@ -635,6 +666,16 @@ typedef struct vaura_codec_encoder {
 /* wav (B, n_samples) fp32, n_samples a multiple of prod(rates) (DAC.preprocess zero-pads on the right; the caller does)
  * -> codes (B, K, n_samples / prod(rates)) int32 */
 int vaura_dac_encode(const vaura_codec_encoder* c, const float* wav, int B, int64_t n_samples, int32_t* codes, vaura_stream_t s);
+/* Op-level access for parity tests: the encoder's first convolution (1 -> C, k = 7, pad 3) as vaura_dac_encode launches it.  wav (B, L)
+ * fp32, w (7, C), bias (C), alpha (C) -> out_raw (B, L, C) fp32 and out_act = Snake(alpha) of it in pair planes.  C % 32 == 0.           */
+int vaura_dac_enc_conv_in(const float* wav, const float* w, const float* bias, const float* alpha, float* out_raw, void* out_act,
+                          int B, int64_t L, int C, vaura_stream_t s);
+/* Op-level access for parity tests: ONE stage of the residual vector quantiser as vaura_dac_encode launches it.  residual (B * T,
+ * latent) fp32 is updated in place; in_w (dim, latent), in_b (dim), codebook (size, dim), out_w (latent, dim), out_b (latent) are the
+ * stage's own; its codes go to codes[(b * K + k) * T + t] of a (B, K, T) int32 tensor.  dim <= 8, size <= 1024, latent <= 2048.       */
+int vaura_dac_rvq_stage(float* residual, const float* in_w, const float* in_b, const float* codebook, const float* out_w,
+                        const float* out_b, int32_t* codes, int B, int T, int latent, int dim, int size, int K, int k,
+                        vaura_stream_t s);
 size_t vaura_dac_encode_workspace_elems(const vaura_codec_encoder* c, int B, int64_t n_samples);
 
 /* -------------------------------------------------------------------------------------------

@@ -101,3 +101,49 @@ def assert_tokens_or_recorded_near_tie(report, golden, storage, what, tok, ref, 
         before = (_steps(K, T) < e["first_diff_step"])[None].expand_as(ref)
         assert torch.equal(tok[before], ref[before])
     return e
+
+
+# ------------------------------------------------------------------------------------------------------------------
+# Activation formats of the codec kernels (csrc/dac.hip store_act_octet / store_pair4), decoded on the CPU for the op-level
+# parity tests of tests/test_gpu_codec_stages.py.  tests/test_codec_stage_host.py checks these decoders themselves.
+
+def pair_planes_to_f64(buf: torch.Tensor, rows: int, Cc: int):
+    """(hi, lo) fp16 pair planes of a (rows, C) tensor -> (value = hi + lo, hi, lo), fp64 (rows, C) each.  Layout: per row C/8 octets
+    of [plane hi | plane lo][8] halves — the half of channel c of row r sits at ((r * C/8 + c/8) * 2 + plane) * 8 + c % 8.  `buf`: any
+    contiguous CPU tensor whose first rows * C * 4 bytes are the planes."""
+    h = buf.contiguous().view(torch.uint8).reshape(-1)[: rows * Cc * 4].view(torch.float16).reshape(rows, Cc // 8, 2, 8).double()
+    hi, lo = h[:, :, 0].reshape(rows, Cc), h[:, :, 1].reshape(rows, Cc)
+    return hi + lo, hi, lo
+
+
+def mx8_scale_offset(elems: int) -> int:
+    return (elems + 15) & ~15
+
+
+def mx8_to_f64(buf: torch.Tensor, rows: int, Cc: int):
+    """Block-scaled e4m3 of a (rows, C) tensor -> (dequantised values fp64 (rows, C), scale bytes uint8 (rows, C/32)).  Layout: rows * C
+    e4m3 bytes, row-major; at byte mx8_scale_offset(rows * C) one word of four E8M0 bytes per 128 channels of a row: the scale byte of
+    the 32-channel block j of row r is byte (r * ceil(C/128) + j/4) * 4 + j % 4 there; value = e4m3 * 2^(byte - 127)."""
+    raw = buf.contiguous().view(torch.uint8).reshape(-1)
+    nsc = (Cc + 127) // 128
+    off = mx8_scale_offset(rows * Cc)
+    q = raw[: rows * Cc].view(torch.float8_e4m3fn).float().double().reshape(rows, Cc)
+    sb = raw[off: off + rows * nsc * 4].reshape(rows, nsc * 4)[:, : Cc // 32].contiguous()
+    scale = torch.ldexp(torch.ones(rows, Cc // 32, dtype=torch.float64), sb.to(torch.int32) - 127)
+    return q * scale.repeat_interleave(32, dim=1), sb
+
+
+def mx8_scale_bytes(x: torch.Tensor) -> torch.Tensor:
+    """The E8M0 byte vaura_amd.quant's rule gives every 32-channel block of x (rows, C) fp32: the smallest power of two s = 2^(byte - 127)
+    with amax <= 448 s, the byte clamped to [1, 253] -> uint8 (rows, C/32).  An all-zero block has no such smallest power: the kernel's
+    integer form of the rule (mx8_scale_byte) lands on the clamp, byte 1, and so does this; every value of the block is 0 either way."""
+    amax = x.detach().float().reshape(x.shape[0], -1, 32).abs().amax(dim=2)
+    m, e = torch.frexp(amax)
+    exp = torch.where(m <= 0.875, e - 9, e - 8).clamp(min=-126, max=126)
+    return torch.where(amax > 0, exp + 127, torch.ones_like(exp)).to(torch.uint8)
+
+
+def e4m3_step(q: torch.Tensor) -> torch.Tensor:
+    """Spacing of the e4m3 grid at |q| (in units of the block scale): 2^-9 below 2^-6 (subnormals), else 2^(floor(log2 |q|) - 3)."""
+    _, e = torch.frexp(q.abs().double().clamp(min=2.0 ** -6))        # |q| = m 2^e, m in [0.5, 1): floor(log2 |q|) = e - 1
+    return torch.ldexp(torch.ones_like(q, dtype=torch.float64), e - 4)

@@ -1885,6 +1885,21 @@ __global__ __launch_bounds__(256) void snake_kernel(const float* __restrict__ x,
   if (i < n) y[i] = snake_f(x[i], alpha[i % C]);
 }
 
+// the last conv of vaura_dac_decode: its dispatch and launches, on the activation buffer A of length L
+static int launch_conv_out(const vaura_conv& co, const float* A, float* wav, int B, int L, int pr, hipStream_t s) {
+  const int C = co.cin;
+  if (co.cout != 1 || co.taps != 7 || (C % 4)) return VAURA_ERR_SHAPE;
+  if (C <= 128 && C % 8 == 0 && !(va_debug_flags_get() & 8192)) {     // debug flag bit 13: the untiled kernel
+    const size_t sm = sizeof(float) * ((size_t)(CO_TL + 6) * (C + 4) + CO_TL);
+    static unsigned long long big = 0;
+    if (va_big_lds_once(reinterpret_cast<const void*>(conv_out_tiled_kernel), 80 * 1024, &big)) return VAURA_ERR_STATE;
+    VA_LAUNCH(conv_out_tiled_kernel, dim3((L + CO_TL - 1) / CO_TL, B), dim3(256), sm, s, A, co.w, co.bias, wav, L, C, pr);
+  } else {
+    VA_LAUNCH(conv_out_kernel, dim3((L + 31) / 32, B), dim3(256), 0, s, A, co.w, co.bias, wav, L, C, pr);
+  }
+  return 0;
+}
+
 extern "C" {
 
 long long vaura_debug_counter(int which) {
@@ -1949,17 +1964,7 @@ int vaura_dac_decode(const vaura_codec* c, const int32_t* codes, int B, int T, f
       if (rc) return rc;
     }
   }
-  const int C = c->conv_out.cin;
-  if (c->conv_out.cout != 1 || c->conv_out.taps != 7 || (C % 4)) return VAURA_ERR_SHAPE;
-  if (C <= 128 && C % 8 == 0 && !(va_debug_flags_get() & 8192)) {     // debug flag bit 13: the untiled kernel
-    const size_t sm = sizeof(float) * ((size_t)(CO_TL + 6) * (C + 4) + CO_TL);
-    static unsigned long long big = 0;
-    if (va_big_lds_once(reinterpret_cast<const void*>(conv_out_tiled_kernel), 80 * 1024, &big)) return VAURA_ERR_STATE;
-    VA_LAUNCH(conv_out_tiled_kernel, dim3((L + CO_TL - 1) / CO_TL, B), dim3(256), sm, s, A, c->conv_out.w, c->conv_out.bias, wav, L, C, pr);
-  } else {
-    VA_LAUNCH(conv_out_kernel, dim3((L + 31) / 32, B), dim3(256), 0, s, A, c->conv_out.w, c->conv_out.bias, wav, L, C, pr);
-  }
-  return 0;
+  return launch_conv_out(c->conv_out, A, wav, B, L, pr, s);
 }
 
 int vaura_snake(const float* x, const float* alpha, float* y, int64_t rows, int C, vaura_stream_t s_) {
@@ -1969,20 +1974,87 @@ int vaura_snake(const float* x, const float* alpha, float* y, int64_t rows, int 
   return 0;
 }
 
+// fp32 rows (B * L, C) -> the input format of `cv` at `precision` in `scratch` (act_convert_kernel); fp32 itself for precision 0
+static int va_conv_input(const vaura_conv& cv, int precision, const float* in, float* scratch, int B, int L, hipStream_t s,
+                         const float** x) {
+  *x = in;
+  if (!precision) return 0;
+  if (!scratch) return VAURA_ERR_ARG;
+  const bool mx = precision == 3 && cv.wscale;
+  const size_t rows = (size_t)B * L, n = rows * (cv.cin / 8);
+  uint8_t* sc = reinterpret_cast<uint8_t*>(scratch) + mx8_scale_offset(rows * cv.cin);
+  VA_LAUNCH(act_convert_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, in, scratch, sc, rows, cv.cin, mx ? 1 : 0);
+  *x = scratch;
+  return 0;
+}
+
 int vaura_dac_conv(const vaura_conv* cv, int precision, const float* in, float* out, float* scratch, int B, int Lin,
                    vaura_stream_t s_) {
   if (!cv || !in || !out || !scratch || B <= 0 || Lin <= 0 || precision < 0 || precision > 4) return VAURA_ERR_ARG;
   if (cv->cin % 32) return VAURA_ERR_SHAPE;
   hipStream_t s = as_stream(s_);
   const float* x = in;
-  if (precision) {
-    const bool mx = precision == 3 && cv->wscale;
-    const size_t rows = (size_t)B * Lin, n = rows * (cv->cin / 8);
+  const int rc = va_conv_input(*cv, precision, in, scratch, B, Lin, s, &x);
+  if (rc) return rc;
+  return launch_conv(*cv, x, nullptr, nullptr, out, nullptr, B, Lin, precision, s);
+}
+
+int vaura_dac_conv_ex(const vaura_conv* cv, int precision, const float* in, const float* res, const float* alpha, float* out_raw,
+                      void* out_act, float* scratch, int B, int Lin, vaura_stream_t s_) {
+  if (!cv || !in || (!out_raw && !out_act) || (precision && !scratch) || B <= 0 || Lin <= 0 || precision < 0 || precision > 4)
+    return VAURA_ERR_ARG;
+  if (cv->cin % 32) return VAURA_ERR_SHAPE;
+  hipStream_t s = as_stream(s_);
+  const float* x = in;
+  const int rc = va_conv_input(*cv, precision, in, scratch, B, Lin, s, &x);
+  if (rc) return rc;
+  return launch_conv(*cv, x, res, alpha, out_raw, reinterpret_cast<float*>(out_act), B, Lin, precision, s);
+}
+
+int vaura_dac_unit(const vaura_conv* c7, const vaura_conv* c1, int precision, const float* in, const float* res,
+                   const float* alpha_mid, const float* alpha_next, float* out_raw, void* out_act, float* scratch, float* mid, int B,
+                   int L, vaura_stream_t s_) {
+  if (!c7 || !c1 || !in || !res || !alpha_mid || !alpha_next || !out_act || (precision && !scratch) || B <= 0 || L <= 0 ||
+      precision < 0 || precision > 4)
+    return VAURA_ERR_ARG;
+  if (c7->cin % 32) return VAURA_ERR_SHAPE;
+  hipStream_t s = as_stream(s_);
+  const float* x = in;
+  int rc = va_conv_input(*c7, precision, in, scratch, B, L, s, &x);
+  if (rc) return rc;
+  rc = launch_conv_unit(*c7, *c1, x, res, alpha_mid, alpha_next, out_raw, reinterpret_cast<float*>(out_act), B, L, precision, s);
+  if (rc != VA_UNIT_NOT_ELIGIBLE) return rc;
+  if (!mid) return VAURA_DAC_UNIT_TWO_LAUNCHES;
+  // the two launches of vaura_dac_decode for a unit that is not eligible
+  rc = launch_conv(*c7, x, nullptr, alpha_mid, nullptr, mid, B, L, precision, s);
+  if (rc) return rc;
+  rc = launch_conv(*c1, mid, res, alpha_next, out_raw, reinterpret_cast<float*>(out_act), B, L, precision, s);
+  return rc ? rc : VAURA_DAC_UNIT_TWO_LAUNCHES;
+}
+
+int vaura_dac_from_codes(const int32_t* codes, const float* codebooks, const float* out_proj_w, const float* out_proj_b, void* z,
+                         int B, int K, int T, int size, int dim, int latent, int pairs, vaura_stream_t s_) {
+  if (!codes || !codebooks || !out_proj_w || !out_proj_b || !z || B <= 0 || T <= 0) return VAURA_ERR_ARG;
+  if (K < 1 || K > 16 || dim < 1 || dim > 8 || size < 1 || latent < 8 || (latent % 8)) return VAURA_ERR_SHAPE;
+  VA_LAUNCH(from_codes_kernel, dim3((T + FC_NT - 1) / FC_NT, B), dim3(256), 0, as_stream(s_), codes, codebooks, out_proj_w, out_proj_b,
+            reinterpret_cast<float*>(z), K, T, size, dim, latent, pairs ? 1 : 0);
+  return 0;
+}
+
+int vaura_dac_conv_out(const vaura_conv* cv, int precision, const float* in, float* wav, float* scratch, int B, int L,
+                       vaura_stream_t s_) {
+  if (!cv || !cv->w || !cv->bias || !in || !wav || (precision && !scratch) || B <= 0 || L <= 0 || precision < 0 || precision > 4)
+    return VAURA_ERR_ARG;
+  if (precision && (cv->cin % 32)) return VAURA_ERR_SHAPE;
+  hipStream_t s = as_stream(s_);
+  const float* x = in;
+  if (precision) {          // the producer of the last activation writes the precision's own format, mx8 included
+    const size_t rows = (size_t)B * L, n = rows * (cv->cin / 8);
     uint8_t* sc = reinterpret_cast<uint8_t*>(scratch) + mx8_scale_offset(rows * cv->cin);
-    VA_LAUNCH(act_convert_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, in, scratch, sc, rows, cv->cin, mx ? 1 : 0);
+    VA_LAUNCH(act_convert_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, in, scratch, sc, rows, cv->cin, precision == 3 ? 1 : 0);
     x = scratch;
   }
-  return launch_conv(*cv, x, nullptr, nullptr, out, nullptr, B, Lin, precision, s);
+  return launch_conv_out(*cv, x, wav, B, L, precision, s);
 }
 
 size_t vaura_dac_encode_workspace_elems(const vaura_codec_encoder* c, int B, int64_t n_samples) {
@@ -2049,6 +2121,27 @@ int vaura_dac_encode(const vaura_codec_encoder* c, const float* wav, int B, int6
               c->out_proj_w + (size_t)k * c->latent_dim * c->codebook_dim, c->out_proj_b + (size_t)k * c->latent_dim, codes,
               c->latent_dim, c->codebook_dim, c->codebook_size, T, c->n_codebooks, k);
   }
+  return 0;
+}
+
+int vaura_dac_enc_conv_in(const float* wav, const float* w, const float* bias, const float* alpha, float* out_raw, void* out_act,
+                          int B, int64_t L, int C, vaura_stream_t s_) {
+  if (!wav || !w || !bias || !alpha || !out_raw || !out_act || B <= 0 || L <= 0) return VAURA_ERR_ARG;
+  if (C <= 0 || (C % 32)) return VAURA_ERR_SHAPE;
+  const int64_t total = L * (C / 4);
+  VA_LAUNCH(enc_conv_in_kernel, dim3((unsigned)((total + 255) / 256), B), dim3(256), 0, as_stream(s_), wav, w, bias, alpha, out_raw,
+            reinterpret_cast<uint16_t*>(out_act), L, C);
+  return 0;
+}
+
+int vaura_dac_rvq_stage(float* residual, const float* in_w, const float* in_b, const float* codebook, const float* out_w,
+                        const float* out_b, int32_t* codes, int B, int T, int latent, int dim, int size, int K, int k,
+                        vaura_stream_t s_) {
+  if (!residual || !in_w || !in_b || !codebook || !out_w || !out_b || !codes || B <= 0 || T <= 0 || K <= 0 || k < 0 || k >= K)
+    return VAURA_ERR_ARG;
+  if (K > 16 || dim < 1 || dim > 8 || size < 1 || size > 1024 || latent < 1 || latent > 2048) return VAURA_ERR_SHAPE;
+  VA_LAUNCH(rvq_stage_kernel, dim3((unsigned)(B * T)), dim3(256), 0, as_stream(s_), residual, in_w, in_b, codebook, out_w, out_b, codes,
+            latent, dim, size, T, K, k);
   return 0;
 }
 

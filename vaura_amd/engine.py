@@ -1264,6 +1264,137 @@ class CodecConvOp:
         return out
 
 
+    @torch.no_grad()
+    def ex(self, x: torch.Tensor, res: Optional[torch.Tensor] = None, alpha: Optional[torch.Tensor] = None,
+           out_raw: Optional[torch.Tensor] = None, out_act: Optional[torch.Tensor] = None) -> None:
+        """The convolution with the epilogue of the decode path, through ``vaura_dac_conv_ex``: x (B, L, Cin) fp32, res (B, L * stride, Cout)
+        fp32 or None, alpha (Cout) for out_act.  out_raw (fp32) / out_act (``codec_act_bytes`` bytes of any dtype, in the precision's own
+        activation format) are contiguous device tensors the CALLER allocates — a view into a larger buffer with guard rows, in the
+        parity tests — and the launch writes into."""
+        B, Lin, cin = x.shape
+        assert cin == self.cv.cin and (out_raw is not None or out_act is not None)
+        _cuda_contiguous(res, alpha, out_raw, out_act)
+        with off_null_stream(self.dev):
+            xi = x.to(self.dev, torch.float32).contiguous()
+            scratch = torch.empty(B * Lin * cin + 64, dtype=torch.float32, device=self.dev)
+            L.check(self.lib.vaura_dac_conv_ex(C.byref(self.cv), self.pairs, L.ptr(xi), L.ptr(res), L.ptr(alpha), L.ptr(out_raw),
+                                               L.ptr(out_act), L.ptr(scratch), B, Lin, L.current_stream(self.dev)), "vaura_dac_conv_ex")
+            self._keepalive = (xi, scratch)
+
+
+def _cuda_contiguous(*ts):
+    for t in ts:
+        if t is not None and not (t.is_cuda and t.is_contiguous()):
+            raise L.VauraHipError("op-level codec entry: contiguous tensors on a HIP device expected")
+
+
+def codec_act_bytes(precision: str, rows: int, Cc: int) -> int:
+    """Bytes of an activated (rows, C) tensor in the activation format of a codec precision (include/vaura_hip.h, vaura_dac_conv_ex):
+    fp32 or pair planes: 4 per element; "mx8": the e4m3 bytes, padded to 16, then one word of four E8M0 bytes per 128 channels of a row."""
+    if precision != "mx8":
+        return 4 * rows * Cc
+    return ((rows * Cc + 15) & ~15) + rows * ((Cc + 127) // 128) * 4
+
+
+class CodecUnitOp:
+    """ONE residual unit of the decoder through ``vaura_dac_unit`` (op-level parity tests): 7-tap dilated conv (C, C, 7) -> Snake ->
+    1 x 1 conv (C, C, 1) -> + residual, in the arithmetic of a codec ``precision``."""
+
+    def __init__(self, w7: torch.Tensor, b7: torch.Tensor, dilation: int, w1: torch.Tensor, b1: torch.Tensor,
+                 precision: str = "f16pair", device="cuda:0"):
+        _require_cuda(device)
+        self.dev, self.lib, self._keep = torch.device(device), L.lib(), []
+        self.pairs = {"f32": 0, "f16pair": 1, "f16pair_w8": 2, "mx8": 3, "f16": 4}[precision]
+        self.c7, self.c1 = L.Conv(), L.Conv()
+        CodecEngine._pack_conv(self, self.c7, w7.float(), b7.float(), dilation, 1)
+        CodecEngine._pack_conv(self, self.c1, w1.float(), b1.float(), 1, 1)
+
+    _dev = CodecEngine._dev
+
+    @torch.no_grad()
+    def __call__(self, x: torch.Tensor, res: torch.Tensor, alpha_mid: torch.Tensor, alpha_next: torch.Tensor,
+                 out_raw: Optional[torch.Tensor], out_act: torch.Tensor, mid: Optional[torch.Tensor] = None) -> bool:
+        """x (B, L, C) fp32 = Snake of the unit's input, res (B, L, C) the input itself; out_raw / out_act / mid: device tensors of the
+        caller as in ``CodecConvOp.ex`` (mid: ``codec_act_bytes`` bytes, the activated output of the first conv when two launches ran).
+        True: the unit ran as ONE launch.  False: as two (mid given) or not at all (mid None)."""
+        B, Ln, cin = x.shape
+        assert cin == self.c7.cin and res.shape == x.shape
+        _cuda_contiguous(res, alpha_mid, alpha_next, out_raw, out_act, mid)
+        with off_null_stream(self.dev):
+            xi = x.to(self.dev, torch.float32).contiguous()
+            scratch = torch.empty(B * Ln * cin + 64, dtype=torch.float32, device=self.dev)
+            rc = self.lib.vaura_dac_unit(C.byref(self.c7), C.byref(self.c1), self.pairs, L.ptr(xi), L.ptr(res), L.ptr(alpha_mid),
+                                         L.ptr(alpha_next), L.ptr(out_raw), L.ptr(out_act), L.ptr(scratch), L.ptr(mid), B, Ln,
+                                         L.current_stream(self.dev))
+            self._keepalive = (xi, scratch)
+        if rc == L.DAC_UNIT_TWO_LAUNCHES:
+            return False
+        L.check(rc, "vaura_dac_unit")
+        return True
+
+
+@torch.no_grad()
+def codec_from_codes(codes: torch.Tensor, codebooks: torch.Tensor, out_proj_w: torch.Tensor, out_proj_b: torch.Tensor,
+                     out: torch.Tensor, pairs: bool) -> None:
+    """``quantizer.from_codes`` through ``vaura_dac_from_codes``: codes (B, K, T) int32, codebooks (K, size, dim), out_proj_w (K, latent,
+    dim), out_proj_b (K, latent) fp32 -> out (B, T, latent), fp32 or (pairs) pair planes; every tensor the caller's, on one HIP device."""
+    _cuda_contiguous(codes, codebooks, out_proj_w, out_proj_b, out)
+    assert codes.dtype == torch.int32
+    B, K, T = codes.shape
+    _, size, dim = codebooks.shape
+    latent = out_proj_w.shape[1]
+    with off_null_stream(out.device):
+        L.check(L.lib().vaura_dac_from_codes(L.ptr(codes), L.ptr(codebooks), L.ptr(out_proj_w), L.ptr(out_proj_b), L.ptr(out), B, K, T,
+                                             size, dim, latent, 1 if pairs else 0, L.current_stream(out.device)), "vaura_dac_from_codes")
+
+
+@torch.no_grad()
+def codec_conv_out(w: torch.Tensor, bias: torch.Tensor, x: torch.Tensor, out: torch.Tensor, precision: str = "f16pair") -> None:
+    """The decoder's last convolution through ``vaura_dac_conv_out``: w (1, C, 7) Conv1d weight, bias (1), x (B, L, C) fp32 (stored in the
+    activation format of ``precision`` by the entry) -> out (B, L) fp32 = tanh(conv), the caller's tensor."""
+    _cuda_contiguous(x, out)
+    dev = x.device
+    pairs = {"f32": 0, "f16pair": 1, "f16pair_w8": 2, "mx8": 3, "f16": 4}[precision]
+    B, Ln, Cc = x.shape
+    cv = L.Conv()
+    wl = w.float()[0].t().contiguous().to(dev)          # [7][C]
+    bl = bias.float().contiguous().to(dev)
+    cv.w, cv.bias, cv.cin, cv.cout, cv.taps, cv.dilation, cv.stride = L.ptr(wl), L.ptr(bl), Cc, 1, 7, 1, 1
+    with off_null_stream(dev):
+        xi = x.float().contiguous()
+        scratch = torch.empty(B * Ln * Cc + 64, dtype=torch.float32, device=dev)
+        L.check(L.lib().vaura_dac_conv_out(C.byref(cv), pairs, L.ptr(xi), L.ptr(out), L.ptr(scratch), B, Ln, L.current_stream(dev)),
+                "vaura_dac_conv_out")
+        torch.cuda.current_stream(dev).synchronize()    # wl, bl, xi, scratch die with this frame
+
+
+@torch.no_grad()
+def codec_enc_conv_in(wav: torch.Tensor, w: torch.Tensor, bias: torch.Tensor, alpha: torch.Tensor, out_raw: torch.Tensor,
+                      out_act: torch.Tensor) -> None:
+    """The encoder's first convolution through ``vaura_dac_enc_conv_in``: wav (B, L), w (7, C), bias (C), alpha (C) fp32 -> out_raw (B, L,
+    C) fp32 and out_act, Snake(alpha) of it in pair planes; every tensor the caller's, on one HIP device."""
+    _cuda_contiguous(wav, w, bias, alpha, out_raw, out_act)
+    B, Ln = wav.shape
+    with off_null_stream(wav.device):
+        L.check(L.lib().vaura_dac_enc_conv_in(L.ptr(wav), L.ptr(w), L.ptr(bias), L.ptr(alpha), L.ptr(out_raw), L.ptr(out_act), B, Ln,
+                                              w.shape[1], L.current_stream(wav.device)), "vaura_dac_enc_conv_in")
+
+
+@torch.no_grad()
+def codec_rvq_stage(residual: torch.Tensor, in_w: torch.Tensor, in_b: torch.Tensor, codebook: torch.Tensor, out_w: torch.Tensor,
+                    out_b: torch.Tensor, codes: torch.Tensor, k: int) -> None:
+    """ONE residual-VQ stage through ``vaura_dac_rvq_stage``: residual (B, T, latent) fp32 updated IN PLACE, the stage's in_w (dim, latent),
+    in_b (dim), codebook (size, dim), out_w (latent, dim), out_b (latent); codes (B, K, T) int32 receives plane k."""
+    _cuda_contiguous(residual, in_w, in_b, codebook, out_w, out_b, codes)
+    assert codes.dtype == torch.int32
+    B, T, latent = residual.shape
+    size, dim = codebook.shape
+    with off_null_stream(residual.device):
+        L.check(L.lib().vaura_dac_rvq_stage(L.ptr(residual), L.ptr(in_w), L.ptr(in_b), L.ptr(codebook), L.ptr(out_w), L.ptr(out_b),
+                                            L.ptr(codes), B, T, latent, dim, size, codes.shape[1], k,
+                                            L.current_stream(residual.device)), "vaura_dac_rvq_stage")
+
+
 def snake(x: torch.Tensor, alpha: torch.Tensor, device="cuda:0") -> torch.Tensor:
     """The codec's activation through ``vaura_snake`` (op-level parity tests): x (..., C) fp32 channels-last, alpha (C)."""
     _require_cuda(device)
