@@ -591,6 +591,28 @@ typedef struct vaura_codec {
 int vaura_dac_decode(const vaura_codec* c, const int32_t* codes, int B, int T, float* wav, vaura_stream_t s);
 /* floats each of the 4 workspaces must hold for (B, T) */
 size_t vaura_dac_workspace_elems(const vaura_codec* c, int B, int T);
+/* Clips of different lengths in ONE decode pass.  codes (B, K, T_max) int32, padded; lengths: B ints ON THE HOST, clip b has
+ * lengths[b] frames, 1 .. T_max (codes behind them are not read) -> wav (B, 1, T_max*hop): wav[b, 0, :lengths[b]*hop] is bit for bit
+ * what vaura_dac_decode gives for codes[b, :, :lengths[b]] alone, every sample behind it is 0.
+ * How: the clips are laid out behind one another as ONE sequence with a gap of vaura_dac_clips_gap(c) latent frames of zeros
+ * between neighbours — clip b at latent row o_b, at row o_b * rate on a level with `rate` rows per frame, at sample o_b * hop — and
+ * every convolution runs on that sequence as a batch of one, through the kernels and the instance choice of vaura_dac_decode (the
+ * grid is that of the whole batch, so short clips reach the 256-row and one-launch instances too).  A tap that leaves a clip reads a
+ * gap row (zeros: what the row mask gives the clip alone); the gap rows of an activated buffer are cleared again behind the launch
+ * that wrote it.  The gap is the smallest number of frames that covers, on every level, the one-sided reach ((taps - 1) / 2 *
+ * dilation rows; 1 for a transposed conv) of the convs that run there: 4 for the 44.1 kHz geometry (27 rows at 8 rows per frame).
+ * Nothing in the call waits for the device or copies from it; the lengths are read before it returns.
+ * The 4 workspaces must hold vaura_dac_decode_clips_workspace_elems(c, B, lengths) floats each (0: c / lengths NULL, B <= 0, a
+ * length < 1, or a sequence beyond the int range).
+ * VAURA_ERR_ARG: NULL c / codes / wav / lengths (not dereferenced), B or T_max <= 0, a length outside 1 .. T_max, workspaces NULL or
+ * too small; VAURA_ERR_SHAPE: as vaura_dac_decode, or the packed sequence's largest level (rows x channels) does not fit an int;
+ * VAURA_ERR_DTYPE: precision.  All before any launch.                                                                               */
+int vaura_dac_decode_clips(const vaura_codec* c, const int32_t* codes, int B, int T_max, const int32_t* lengths, float* wav,
+                           vaura_stream_t s);
+size_t vaura_dac_decode_clips_workspace_elems(const vaura_codec* c, int B, const int32_t* lengths);
+/* gap (latent frames) of vaura_dac_decode_clips for this geometry, from the convs' taps, dilations and the rates; -1: c NULL or not a
+ * geometry the decode pass takes.  Reads no device pointer.                                                                          */
+int vaura_dac_clips_gap(const vaura_codec* c);
 /* Op-level access for parity tests: ONE convolution of the decoder (WNConv1d / WNConvTranspose1d of descript-audio-codec's
  * DecoderBlock / ResidualUnit) in the arithmetic of `precision` (vaura_codec.precision; weights laid out for it).
  * in (B, Lin, Cin) fp32 channels-last, already activated -> out (B, Lout, Cout) fp32 = conv(in) + bias,
@@ -677,6 +699,21 @@ int vaura_dac_rvq_stage(float* residual, const float* in_w, const float* in_b, c
                         const float* out_b, int32_t* codes, int B, int T, int latent, int dim, int size, int K, int k,
                         vaura_stream_t s);
 size_t vaura_dac_encode_workspace_elems(const vaura_codec_encoder* c, int B, int64_t n_samples);
+/* Clips of different lengths in ONE encode pass.  wav (B, n_max) fp32, padded (n_max need not be a multiple of the hop);
+ * sample_lengths: B int64 ON THE HOST, clip b has sample_lengths[b] samples, 1 .. n_max (samples behind them are not read)
+ * -> codes (B, K, T_max) int32, T_max = ceil(n_max / hop): codes[b, :, :ceil(n_b / hop)] is bit for bit what vaura_dac_encode gives for
+ * clip b's own samples (zero-padded to a multiple of the hop, DAC.preprocess) alone, every frame behind them holds 0.
+ * The packed sequence of vaura_dac_decode_clips, from the other side: clip b's samples at sample o_b * hop, zeros up to the end of
+ * its last frame, then vaura_dac_encode_clips_gap(c) frames of zeros; the strided convs keep their view of r rows as one (every
+ * offset is a multiple of the hop).  The gap covers the encoder's reaches per level: 4 for the 44.1 kHz geometry (27 rows in the
+ * last block, at 8 rows per frame).  No wait for the device, no copy from it.
+ * Workspaces: vaura_dac_encode_clips_workspace_elems(c, B, sample_lengths) floats each (0 as above).
+ * VAURA_ERR_ARG: NULL c / wav / codes / sample_lengths (not dereferenced), B or n_max <= 0, a length outside 1 .. n_max, workspaces
+ * NULL or too small; VAURA_ERR_SHAPE: as vaura_dac_encode, or the packed sequence does not fit an int.  All before any launch.       */
+int vaura_dac_encode_clips(const vaura_codec_encoder* c, const float* wav, int B, int64_t n_max, const int64_t* sample_lengths,
+                           int32_t* codes, vaura_stream_t s);
+size_t vaura_dac_encode_clips_workspace_elems(const vaura_codec_encoder* c, int B, const int64_t* sample_lengths);
+int vaura_dac_encode_clips_gap(const vaura_codec_encoder* c);
 
 /* -------------------------------------------------------------------------------------------
  * f3 (the step after the path) post-codec scaling: normalize_audio (utils/data_utils.py:407-466) as called by

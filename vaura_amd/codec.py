@@ -161,6 +161,19 @@ class DacModelWrapper(nn.Module):
             codes = codes[0][0]
         return self.engine().decode(codes)
 
+    @torch.no_grad()
+    def decode_clips(self, codes: torch.Tensor, lengths):
+        """A padded batch in ONE codec pass: codes (B, 9, T_max), ``lengths`` one int per clip -> wav (B, 1, 512*T_max) with
+        ``wav[b, :, :512*T_b]`` the bits of ``decode(codes[b:b+1, :, :T_b])`` and zeros behind it (``CodecEngine.decode_clips``)."""
+        return self.engine().decode_clips(codes, lengths)
+
+    @torch.no_grad()
+    def encode_clips(self, wav: torch.Tensor, sample_lengths):
+        """A padded batch in ONE encoder pass: wav (B, 1, N) | (B, N), ``sample_lengths`` one int per clip -> codes (B, 9, ceil(N / 512))
+        with ``codes[b, :, :ceil(n_b / 512)]`` the bits of ``encode(wav[b:b+1, :, :n_b])`` and 0 behind them
+        (``CodecEncoderEngine.encode_clips``)."""
+        return self.encoder_engine().encode_clips(wav, sample_lengths)
+
     @property
     def sample_rate(self):
         return self.model.sample_rate

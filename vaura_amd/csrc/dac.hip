@@ -13,6 +13,8 @@
 // epilogue is float4: + bias, + residual, raw store, and Snake with the NEXT layer's alpha — the
 // activation is evaluated once per element by its producer, never per tap by the consumer.
 #include "common.h"
+#include <algorithm>
+#include <vector>
 
 #define BM 128   // positions per workgroup tile
 #define BN 96    // output channels per workgroup tile (divides 1536, 768, 384, 192, 96)
@@ -1900,6 +1902,139 @@ static int launch_conv_out(const vaura_conv& co, const float* A, float* wav, int
   return 0;
 }
 
+// ---------------------------------------------------------------------------------------------
+// Clips of different lengths in ONE pass (vaura_dac_decode_clips / vaura_dac_encode_clips).  The B clips lie behind one another
+// on the time axis of a single sequence (B = 1 for every conv launch), `gap` latent frames of zeros between neighbours: clip b
+// starts at latent row off[b], at row off[b] * rate on a level with `rate` rows per latent frame, at sample off[b] * hop.  No conv
+// kernel knows about it.  A tap of a row of clip b lands inside the clip, in a gap — zeros, what the `jr >= 0 && jr < Lin` mask
+// gives the clip decoded alone — or past an end of the sequence, where that mask applies.  Residual and raw rows are read at their own
+// position only, a 1 x 1 conv is pointwise, and a transposed conv writes a row from one (j, phase).  A launch writes gap rows like
+// any other (from the neighbours' edges), so the gap rows of every ACTIVATED buffer that a conv with more than one tap reads are
+// cleared again behind the launch that wrote it (clips_zero_gaps_kernel).  The gap is the smallest number of latent frames that, on
+// every level, covers the largest one-sided reach of the convs that run there (va_clips_gap_*).
+#define VA_CLIP_CHUNK 64
+struct ClipChunk {                    // up to VA_CLIP_CHUNK clips by value: a launch per chunk, no table on the device
+  int n, b0;                          // clips in this chunk, index of the first
+  int off[VA_CLIP_CHUNK];             // first latent row of the clip in the packed sequence
+  int len[VA_CLIP_CHUNK];             // its latent frames
+  int64_t aux[VA_CLIP_CHUNK];         // its samples (encode)
+};
+struct ClipLayout {
+  int B, gap;
+  int64_t total;                      // latent rows of the packed sequence: off[B - 1] + len[B - 1]
+  const int* off;
+  const int* len;
+  const int64_t* aux;
+};
+static ClipChunk va_clip_chunk(const ClipLayout& l, int b0, int bend) {
+  ClipChunk k;
+  k.b0 = b0; k.n = bend - b0 < VA_CLIP_CHUNK ? bend - b0 : VA_CLIP_CHUNK;
+  for (int i = 0; i < k.n; ++i) { k.off[i] = l.off[b0 + i]; k.len[i] = l.len[b0 + i]; k.aux[i] = l.aux ? l.aux[b0 + i] : 0; }
+  return k;
+}
+
+// the `gap` frames behind each clip of the chunk: unit = bytes of one latent frame of this buffer (rows per frame x bytes per row, a
+// multiple of 16).  0 is all-zero bytes in fp32, in both fp16 planes and in e4m3; an mx8 buffer keeps the scale bytes its producer wrote
+// (1 .. 253, mx8_scale_byte): 0 x 2^s is 0.
+__global__ __launch_bounds__(256) void clips_zero_gaps_kernel(unsigned char* __restrict__ buf, ClipChunk k, size_t unit, int gap) {
+  const int i = blockIdx.y;
+  u32x4* p = reinterpret_cast<u32x4*>(buf + (size_t)(k.off[i] + k.len[i]) * unit);
+  const size_t n16 = (size_t)gap * unit / 16;
+  for (size_t u = (size_t)blockIdx.x * 256 + threadIdx.x; u < n16; u += (size_t)gridDim.x * 256) p[u] = u32x4{0u, 0u, 0u, 0u};
+}
+// codes (B, K, Tmax) -> packed (K, total): a clip's own frames, code 0 on the `tail` frames behind it (the gap; 0 behind the last clip)
+__global__ __launch_bounds__(256) void clips_pack_codes_kernel(const int32_t* __restrict__ codes, int32_t* __restrict__ packed, ClipChunk k,
+                                                               int K, int Tmax, int64_t total, int gap, int B) {
+  const int i = blockIdx.y, kk = blockIdx.z, b = k.b0 + i;
+  const int n = k.len[i] + (b + 1 < B ? gap : 0);
+  for (int t = blockIdx.x * 256 + threadIdx.x; t < n; t += gridDim.x * 256)
+    packed[(size_t)kk * total + k.off[i] + t] = t < k.len[i] ? codes[((size_t)b * K + kk) * Tmax + t] : 0;
+}
+// packed (K, total) -> codes (B, K, Tmax): 0 behind a clip's frames
+__global__ __launch_bounds__(256) void clips_unpack_codes_kernel(const int32_t* __restrict__ packed, int32_t* __restrict__ codes, ClipChunk k,
+                                                                 int K, int Tmax, int64_t total) {
+  const int i = blockIdx.y, kk = blockIdx.z, b = k.b0 + i;
+  for (int t = blockIdx.x * 256 + threadIdx.x; t < Tmax; t += gridDim.x * 256)
+    codes[((size_t)b * K + kk) * Tmax + t] = t < k.len[i] ? packed[(size_t)kk * total + k.off[i] + t] : 0;
+}
+// wav (B, n_max) -> packed samples: aux[i] samples of the clip, zeros up to the end of its last frame (DAC.preprocess) and through the gap
+__global__ __launch_bounds__(256) void clips_pack_wav_kernel(const float* __restrict__ wav, float* __restrict__ packed, ClipChunk k,
+                                                             int64_t n_max, int hop, int gap, int B) {
+  const int i = blockIdx.y, b = k.b0 + i;
+  const int64_t n = (int64_t)(k.len[i] + (b + 1 < B ? gap : 0)) * hop;
+  float* dst = packed + (size_t)k.off[i] * hop;
+  for (int64_t u = (int64_t)blockIdx.x * 256 + threadIdx.x; u < n; u += (int64_t)gridDim.x * 256)
+    dst[u] = u < k.aux[i] ? wav[(size_t)b * n_max + u] : 0.f;
+}
+// packed samples -> wav (B, n_out): len[i] * hop samples of the clip, 0 behind them
+__global__ __launch_bounds__(256) void clips_unpack_wav_kernel(const float* __restrict__ packed, float* __restrict__ wav, ClipChunk k,
+                                                               int64_t n_out, int hop) {
+  const int i = blockIdx.y, b = k.b0 + i;
+  const int64_t n = (int64_t)k.len[i] * hop;
+  const float* src = packed + (size_t)k.off[i] * hop;
+  for (int64_t u = (int64_t)blockIdx.x * 256 + threadIdx.x; u < n_out; u += (int64_t)gridDim.x * 256)
+    wav[(size_t)b * n_out + u] = u < n ? src[u] : 0.f;
+}
+
+static unsigned va_clip_gx(int64_t items) {                     // workgroups along x for `items` per clip: grid-stride beyond 256
+  const int64_t g = (items + 255) / 256;
+  return (unsigned)(g < 1 ? 1 : (g > 256 ? 256 : g));
+}
+// clear the gaps of one buffer: `rate` rows per latent frame, `row_bytes` per row
+static int va_clips_zero(const ClipLayout& l, void* buf, int64_t rate, size_t row_bytes, hipStream_t s) {
+  const size_t unit = (size_t)rate * row_bytes;
+  if (unit % 16) return VAURA_ERR_SHAPE;
+  for (int b0 = 0; b0 < l.B - 1; b0 += VA_CLIP_CHUNK) {         // the last clip has no gap behind it
+    const ClipChunk k = va_clip_chunk(l, b0, l.B - 1);
+    VA_LAUNCH(clips_zero_gaps_kernel, dim3(va_clip_gx((int64_t)((size_t)l.gap * unit / 16)), k.n), dim3(256), 0, s,
+              reinterpret_cast<unsigned char*>(buf), k, unit, l.gap);
+  }
+  return 0;
+}
+static inline int va_ceil_div(int a, int b) { return (a + b - 1) / b; }
+static inline int va_conv_reach(const vaura_conv& cv) { return cv.stride > 1 ? 1 : ((cv.taps - 1) / 2) * cv.dilation; }
+// smallest gap (latent frames) with gap * rate(level) >= the one-sided reach of every conv on that level; -1: not a geometry of the pass
+static int va_clips_gap_decode(const vaura_codec* c) {
+  if (c->n_blocks < 1 || c->n_blocks > 4 || c->n_units != 3) return -1;
+  int g = va_conv_reach(c->conv_in), rate = 1;
+  for (int b = 0; b < c->n_blocks; ++b) {
+    if (c->rates[b] < 1) return -1;
+    g = std::max(g, va_ceil_div(va_conv_reach(c->up[b]), rate));     // reads rows j, j - 1 of its input level
+    rate *= c->rates[b];
+    for (int u = 0; u < 3; ++u)
+      for (int i = 0; i < 2; ++i) g = std::max(g, va_ceil_div(va_conv_reach(c->res[b][u][i]), rate));
+  }
+  g = std::max(g, va_ceil_div(va_conv_reach(c->conv_out), rate));
+  return g < 1 ? 1 : g;
+}
+static int va_clips_gap_encode(const vaura_codec_encoder* c, int64_t* hop_out) {
+  if (c->n_blocks < 1 || c->n_blocks > 4 || c->n_units != 3) return -1;
+  int64_t hop = 1;
+  for (int b = 0; b < c->n_blocks; ++b) { if (c->rates[b] < 1) return -1; hop *= c->rates[b]; }
+  if (hop_out) *hop_out = hop;
+  int rate = (int)hop;
+  int g = va_ceil_div(3, rate);                                  // the first conv: k = 7 on the samples
+  for (int b = 0; b < c->n_blocks; ++b) {
+    for (int u = 0; u < 3; ++u)
+      for (int i = 0; i < 2; ++i) g = std::max(g, va_ceil_div(va_conv_reach(c->res[b][u][i]), rate));
+    rate /= c->rates[b];
+    g = std::max(g, va_ceil_div(va_conv_reach(c->down[b]), rate));   // 3 taps over rows of r * C channels = rows of its OUTPUT level
+  }
+  g = std::max(g, va_ceil_div(va_conv_reach(c->conv_out), rate));
+  return g < 1 ? 1 : g;
+}
+// offsets of `B` clips of `frames[b]` latent frames; false when the packed sequence leaves the int range of the launch arithmetic
+static bool va_clips_offsets(const int* frames, int B, int gap, int* off, int64_t* total) {
+  int64_t o = 0;
+  for (int b = 0; b < B; ++b) {
+    if (o > 0x7fffffff) return false;
+    off[b] = (int)o;
+    o += frames[b] + (b + 1 < B ? gap : 0);
+  }
+  *total = o;
+  return o <= 0x7fffffff;
+}
+
 extern "C" {
 
 long long vaura_debug_counter(int which) {
@@ -1927,44 +2062,126 @@ size_t vaura_dac_workspace_elems(const vaura_codec* c, int B, int T) {
   return best * (size_t)B;
 }
 
-int vaura_dac_decode(const vaura_codec* c, const int32_t* codes, int B, int T, float* wav, vaura_stream_t s_) {
-  if (!c || !codes || !wav || B <= 0 || T <= 0) return VAURA_ERR_ARG;
-  if (c->n_blocks < 1 || c->n_blocks > 4 || c->n_units != 3 || c->n_codebooks > 16 || c->codebook_dim > 8)
-    return VAURA_ERR_SHAPE;
-  if (c->ws_elems < vaura_dac_workspace_elems(c, B, T)) return VAURA_ERR_ARG;
-  for (int i = 0; i < 4; ++i) if (!c->ws[i]) return VAURA_ERR_ARG;
-  hipStream_t s = as_stream(s_);
+// the decode pass on checked arguments.  lay = NULL: (B, K, T) codes -> (B, 1, T * hop) samples, the launches vaura_dac_decode has always
+// made.  With a layout, B and T are those of the padded tensors: the codes are packed into one sequence of lay->total frames, every
+// conv runs on it as ONE clip, the gaps of each activated buffer are cleared behind its producer, and the samples are unpacked.
+static int va_dac_decode_pass(const vaura_codec* c, const int32_t* codes, int B, int T, float* wav, const ClipLayout* lay, hipStream_t s) {
   const int pr = c->precision;
-  if (pr < 0 || pr > 4) return VAURA_ERR_DTYPE;
   float* R = c->ws[0]; float* A = c->ws[1]; float* Y = c->ws[2]; float* Z = c->ws[3];
+  const int Bc = B, Tc = T;           // the caller's batch and padded length
+  int rc = 0;
+  if (lay) {
+    int32_t* packed = reinterpret_cast<int32_t*>(Z);              // Z is first written by the first transposed conv
+    for (int b0 = 0; b0 < Bc; b0 += VA_CLIP_CHUNK) {
+      const ClipChunk k = va_clip_chunk(*lay, b0, Bc);
+      VA_LAUNCH(clips_pack_codes_kernel, dim3(va_clip_gx(Tc + lay->gap), k.n, c->n_codebooks), dim3(256), 0, s, codes, packed, k,
+                c->n_codebooks, Tc, lay->total, lay->gap, Bc);
+    }
+    codes = packed; B = 1; T = (int)lay->total;
+  }
+  // a row of an activated buffer: fp32 or (hi, lo) fp16 planes 4 bytes per channel, mx8 one (its scales lie behind the whole tensor)
+  const size_t act_b = pr == 3 ? 1 : 4;
 
   VA_LAUNCH(from_codes_kernel, dim3((T + FC_NT - 1) / FC_NT, B), dim3(256), 0, s, codes, c->codebooks, c->out_proj_w, c->out_proj_b, Y,
                      c->n_codebooks, T, c->codebook_size, c->codebook_dim, c->latent_dim, pr ? 1 : 0);
+  if (lay && (rc = va_clips_zero(*lay, Y, 1, (size_t)c->latent_dim * 4, s))) return rc;       // code 0 is not latent 0
   // conv_in: only the activated output is consumed (by the first transposed conv)
-  int rc = launch_conv(c->conv_in, Y, nullptr, c->alpha_up[0], nullptr, A, B, T, pr, s);
+  rc = launch_conv(c->conv_in, Y, nullptr, c->alpha_up[0], nullptr, A, B, T, pr, s);
   if (rc) return rc;
+  if (lay && (rc = va_clips_zero(*lay, A, 1, c->conv_in.cout * act_b, s))) return rc;
   int L = T;
   for (int b = 0; b < c->n_blocks; ++b) {
     // Snake (already applied by the producer) -> transposed conv; raw kept for the first residual
     rc = launch_conv(c->up[b], A, nullptr, c->alpha_res[b][0][0], Y, Z, B, L, pr, s);
     if (rc) return rc;
     L *= c->rates[b];
+    if (lay && (rc = va_clips_zero(*lay, Z, L / T, c->up[b].cout * act_b, s))) return rc;
     { float* t = R; R = Y; Y = t; t = A; A = Z; Z = t; }
     for (int u = 0; u < 3; ++u) {
       const float* next_alpha = (u < 2) ? c->alpha_res[b][u + 1][0] : (b + 1 < c->n_blocks ? c->alpha_up[b + 1] : c->alpha_out);
       // the whole unit in one launch where one workgroup holds every channel (the activated result goes to Y: neighbours still read A's halo rows)
       rc = launch_conv_unit(c->res[b][u][0], c->res[b][u][1], A, R, c->alpha_res[b][u][1], next_alpha, (u < 2) ? R : nullptr, Y, B, L, pr, s);
-      if (rc == 0) { float* t = A; A = Y; Y = t; continue; }
+      if (rc == 0) {
+        float* t = A; A = Y; Y = t;
+        if (lay && (rc = va_clips_zero(*lay, A, L / T, c->up[b].cout * act_b, s))) return rc;
+        continue;
+      }
       if (rc != VA_UNIT_NOT_ELIGIBLE) return rc;          // a real failure of the one-launch unit (argument error or hipError_t): not a fallback
       // y = Snake2(conv7(Snake1(x)))  (Snake1 applied by the producer)
       rc = launch_conv(c->res[b][u][0], A, nullptr, c->alpha_res[b][u][1], nullptr, Y, B, L, pr, s);
       if (rc) return rc;
-      // x = x + conv1(y); emit Snake_next(x)
+      // x = x + conv1(y); emit Snake_next(x)   (packed: y's gap rows stay as they are, the 1 x 1 conv reads a row for that row only)
       rc = launch_conv(c->res[b][u][1], Y, R, next_alpha, (u < 2) ? R : nullptr, A, B, L, pr, s);
       if (rc) return rc;
+      if (lay && (rc = va_clips_zero(*lay, A, L / T, c->up[b].cout * act_b, s))) return rc;
     }
   }
-  return launch_conv_out(c->conv_out, A, wav, B, L, pr, s);
+  if (!lay) return launch_conv_out(c->conv_out, A, wav, B, L, pr, s);
+  const int hop = L / T;
+  rc = launch_conv_out(c->conv_out, A, R, B, L, pr, s);            // the last residual stream has been consumed: R takes the packed samples
+  if (rc) return rc;
+  for (int b0 = 0; b0 < Bc; b0 += VA_CLIP_CHUNK) {
+    const ClipChunk k = va_clip_chunk(*lay, b0, Bc);
+    VA_LAUNCH(clips_unpack_wav_kernel, dim3(va_clip_gx((int64_t)Tc * hop), k.n), dim3(256), 0, s, R, wav, k, (int64_t)Tc * hop, hop);
+  }
+  return 0;
+}
+
+int vaura_dac_decode(const vaura_codec* c, const int32_t* codes, int B, int T, float* wav, vaura_stream_t s_) {
+  if (!c || !codes || !wav || B <= 0 || T <= 0) return VAURA_ERR_ARG;
+  if (c->n_blocks < 1 || c->n_blocks > 4 || c->n_units != 3 || c->n_codebooks > 16 || c->codebook_dim > 8)
+    return VAURA_ERR_SHAPE;
+  if (c->ws_elems < vaura_dac_workspace_elems(c, B, T)) return VAURA_ERR_ARG;
+  for (int i = 0; i < 4; ++i) if (!c->ws[i]) return VAURA_ERR_ARG;
+  const int pr = c->precision;
+  if (pr < 0 || pr > 4) return VAURA_ERR_DTYPE;
+  return va_dac_decode_pass(c, codes, B, T, wav, nullptr, as_stream(s_));
+}
+
+int vaura_dac_clips_gap(const vaura_codec* c) { return c ? va_clips_gap_decode(c) : -1; }
+
+// frames of the packed sequence for `lengths`, 0 for anything vaura_dac_decode_clips refuses (T_max <= 0: lengths are checked against >= 1 only)
+static int64_t va_decode_clips_total(const vaura_codec* c, int B, int T_max, const int32_t* lengths, int* off, int* gap_out) {
+  const int gap = va_clips_gap_decode(c);
+  if (gap < 0) return 0;
+  for (int b = 0; b < B; ++b)
+    if (lengths[b] < 1 || (T_max > 0 && lengths[b] > T_max)) return 0;
+  int64_t total = 0;
+  if (!va_clips_offsets(lengths, B, gap, off, &total)) return -1;
+  if (gap_out) *gap_out = gap;
+  return total;
+}
+// floats per workspace for the packed sequence: its activations as ONE clip, the packed codes, the packed samples
+static size_t va_decode_clips_elems(const vaura_codec* c, int64_t total) {
+  size_t need = vaura_dac_workspace_elems(c, 1, (int)total);
+  const size_t kc = (size_t)c->n_codebooks * (size_t)total;
+  return need > kc ? need : kc;                 // total * hop samples <= total * hop * C_last
+}
+
+size_t vaura_dac_decode_clips_workspace_elems(const vaura_codec* c, int B, const int32_t* lengths) {
+  if (!c || !lengths || B <= 0) return 0;
+  std::vector<int> off((size_t)B);
+  const int64_t total = va_decode_clips_total(c, B, 0, lengths, off.data(), nullptr);
+  return total > 0 ? va_decode_clips_elems(c, total) : 0;
+}
+
+int vaura_dac_decode_clips(const vaura_codec* c, const int32_t* codes, int B, int T_max, const int32_t* lengths, float* wav,
+                           vaura_stream_t s_) {
+  if (!c || !codes || !wav || !lengths || B <= 0 || T_max <= 0) return VAURA_ERR_ARG;
+  if (c->n_blocks < 1 || c->n_blocks > 4 || c->n_units != 3 || c->n_codebooks > 16 || c->codebook_dim > 8)
+    return VAURA_ERR_SHAPE;
+  std::vector<int> off((size_t)B), len(lengths, lengths + B);
+  ClipLayout lay;
+  lay.B = B; lay.off = off.data(); lay.len = len.data(); lay.aux = nullptr;
+  lay.total = va_decode_clips_total(c, B, T_max, lengths, off.data(), &lay.gap);
+  if (lay.total == 0) return VAURA_ERR_ARG;              // a length outside 1 .. T_max
+  // every launch indexes rows and rows * stride in int (ConvPArgs, the grids): the largest level of the packed sequence must fit
+  if (lay.total < 0 || va_decode_clips_elems(c, lay.total) > (size_t)0x7fffffff || (int64_t)B * T_max > 0x7fffffff) return VAURA_ERR_SHAPE;
+  if (c->ws_elems < va_decode_clips_elems(c, lay.total)) return VAURA_ERR_ARG;
+  for (int i = 0; i < 4; ++i) if (!c->ws[i]) return VAURA_ERR_ARG;
+  const int pr = c->precision;
+  if (pr < 0 || pr > 4) return VAURA_ERR_DTYPE;
+  return va_dac_decode_pass(c, codes, B, T_max, wav, &lay, as_stream(s_));
 }
 
 int vaura_snake(const float* x, const float* alpha, float* y, int64_t rows, int C, vaura_stream_t s_) {
@@ -2070,18 +2287,22 @@ size_t vaura_dac_encode_workspace_elems(const vaura_codec_encoder* c, int B, int
   return best * (size_t)B;
 }
 
-int vaura_dac_encode(const vaura_codec_encoder* c, const float* wav, int B, int64_t n_samples, int32_t* codes, vaura_stream_t s_) {
-  if (!c || !wav || !codes || B <= 0 || n_samples <= 0) return VAURA_ERR_ARG;
-  if (c->n_blocks < 1 || c->n_blocks > 4 || c->n_units != 3 || c->n_codebooks > 16 || c->codebook_dim > 8 ||
-      c->codebook_size > 1024 || c->latent_dim > 2048 || (c->enc_dim % 32))
-    return VAURA_ERR_SHAPE;
-  int64_t hop = 1;
-  for (int b = 0; b < c->n_blocks; ++b) hop *= c->rates[b];
-  if (n_samples % hop) return VAURA_ERR_SHAPE;                 // DAC.preprocess pads; the caller hands in the padded clip
-  if (c->ws_elems < vaura_dac_encode_workspace_elems(c, B, n_samples)) return VAURA_ERR_ARG;
-  for (int i = 0; i < 4; ++i) if (!c->ws[i]) return VAURA_ERR_ARG;
-  hipStream_t s = as_stream(s_);
+// the encode pass on checked arguments.  lay = NULL: (B, n_samples) -> (B, K, n_samples / hop), the launches vaura_dac_encode has always
+// made.  With a layout: wav (B, n_samples) padded, clip b's lay->aux[b] samples packed into one sequence (see ClipLayout), codes
+// (B, K, T_max) with T_max = ceil(n_samples / hop).
+static int va_dac_encode_pass(const vaura_codec_encoder* c, const float* wav, int B, int64_t n_samples, int32_t* codes, const ClipLayout* lay,
+                              int64_t hop, hipStream_t s) {
   float* R = c->ws[0]; float* A = c->ws[1]; float* Y = c->ws[2]; float* Z = c->ws[3];
+  const int Bc = B;
+  const int64_t n_in = n_samples;
+  int rc = 0;
+  if (lay) {
+    for (int b0 = 0; b0 < Bc; b0 += VA_CLIP_CHUNK) {               // Z is first written by the first strided conv
+      const ClipChunk k = va_clip_chunk(*lay, b0, Bc);
+      VA_LAUNCH(clips_pack_wav_kernel, dim3(va_clip_gx(n_in + lay->gap * hop), k.n), dim3(256), 0, s, wav, Z, k, n_in, (int)hop, lay->gap, Bc);
+    }
+    wav = Z; B = 1; n_samples = lay->total * hop;
+  }
 
   int64_t L = n_samples;
   int C = c->enc_dim;
@@ -2090,16 +2311,17 @@ int vaura_dac_encode(const vaura_codec_encoder* c, const float* wav, int B, int6
     VA_LAUNCH(enc_conv_in_kernel, dim3((unsigned)((total + 255) / 256), B), dim3(256), 0, s, wav, c->conv_in_w, c->conv_in_b,
               c->alpha_res[0][0][0], R, reinterpret_cast<uint16_t*>(A), L, C);
   }
-  int rc = 0;
+  if (lay && (rc = va_clips_zero(*lay, A, L / lay->total, (size_t)C * 4, s))) return rc;
   for (int b = 0; b < c->n_blocks; ++b) {
     for (int u = 0; u < 3; ++u) {
       // y = Snake2(conv7(Snake1(x)))   (Snake1 applied by the producer)
       rc = launch_conv(c->res[b][u][0], A, nullptr, c->alpha_res[b][u][1], nullptr, Y, B, (int)L, 1, s);
       if (rc) return rc;
-      // x = x + conv1(y); emit Snake_next(x)
+      // x = x + conv1(y); emit Snake_next(x)   (packed: y's gap rows stay as they are, the 1 x 1 conv reads a row for that row only)
       const float* next_alpha = (u < 2) ? c->alpha_res[b][u + 1][0] : c->alpha_down[b];
       rc = launch_conv(c->res[b][u][1], Y, R, next_alpha, (u < 2) ? R : nullptr, A, B, (int)L, 1, s);
       if (rc) return rc;
+      if (lay && (rc = va_clips_zero(*lay, A, L / lay->total, (size_t)C * 4, s))) return rc;
     }
     // strided conv (k = 2r, stride r, pad r/2) == 3-tap conv over rows of r*C channels (see vaura_codec_encoder.down)
     const int r = c->rates[b];
@@ -2108,20 +2330,100 @@ int vaura_dac_encode(const vaura_codec_encoder* c, const float* wav, int B, int6
     if (rc) return rc;
     L /= r;
     C *= 2;
+    if (lay && (rc = va_clips_zero(*lay, Z, L / lay->total, (size_t)C * 4, s))) return rc;
     { float* t = R; R = Y; Y = t; t = A; A = Z; Z = t; }
   }
   // Snake (applied by the producer) -> conv k3 -> latent z, fp32 rows (B*T, latent)
   rc = launch_conv(c->conv_out, A, nullptr, nullptr, Y, nullptr, B, (int)L, 1, s);
   if (rc) return rc;
   const int T = (int)L;
+  int32_t* codes_out = lay ? reinterpret_cast<int32_t*>(Z) : codes;      // packed: (K, total) in a buffer nothing reads any more
   for (int k = 0; k < c->n_codebooks; ++k) {
     VA_LAUNCH(rvq_stage_kernel, dim3((unsigned)(B * T)), dim3(256), 0, s, Y,
               c->in_proj_w + (size_t)k * c->codebook_dim * c->latent_dim, c->in_proj_b + (size_t)k * c->codebook_dim,
               c->codebooks + (size_t)k * c->codebook_size * c->codebook_dim,
-              c->out_proj_w + (size_t)k * c->latent_dim * c->codebook_dim, c->out_proj_b + (size_t)k * c->latent_dim, codes,
+              c->out_proj_w + (size_t)k * c->latent_dim * c->codebook_dim, c->out_proj_b + (size_t)k * c->latent_dim, codes_out,
               c->latent_dim, c->codebook_dim, c->codebook_size, T, c->n_codebooks, k);
   }
+  if (!lay) return 0;
+  const int T_max = (int)((n_in + hop - 1) / hop);
+  for (int b0 = 0; b0 < Bc; b0 += VA_CLIP_CHUNK) {
+    const ClipChunk k = va_clip_chunk(*lay, b0, Bc);
+    VA_LAUNCH(clips_unpack_codes_kernel, dim3(va_clip_gx(T_max), k.n, c->n_codebooks), dim3(256), 0, s, codes_out, codes, k, c->n_codebooks,
+              T_max, lay->total);
+  }
   return 0;
+}
+
+static bool va_encoder_shape_ok(const vaura_codec_encoder* c) {
+  return !(c->n_blocks < 1 || c->n_blocks > 4 || c->n_units != 3 || c->n_codebooks > 16 || c->codebook_dim > 8 ||
+           c->codebook_size > 1024 || c->latent_dim > 2048 || (c->enc_dim % 32));
+}
+
+int vaura_dac_encode(const vaura_codec_encoder* c, const float* wav, int B, int64_t n_samples, int32_t* codes, vaura_stream_t s_) {
+  if (!c || !wav || !codes || B <= 0 || n_samples <= 0) return VAURA_ERR_ARG;
+  if (!va_encoder_shape_ok(c)) return VAURA_ERR_SHAPE;
+  int64_t hop = 1;
+  for (int b = 0; b < c->n_blocks; ++b) hop *= c->rates[b];
+  if (n_samples % hop) return VAURA_ERR_SHAPE;                 // DAC.preprocess pads; the caller hands in the padded clip
+  if (c->ws_elems < vaura_dac_encode_workspace_elems(c, B, n_samples)) return VAURA_ERR_ARG;
+  for (int i = 0; i < 4; ++i) if (!c->ws[i]) return VAURA_ERR_ARG;
+  return va_dac_encode_pass(c, wav, B, n_samples, codes, nullptr, hop, as_stream(s_));
+}
+
+int vaura_dac_encode_clips_gap(const vaura_codec_encoder* c) { return c ? va_clips_gap_encode(c, nullptr) : -1; }
+
+// frames of the packed sequence (0: a length outside 1 .. n_max, n_max <= 0 = no upper bound; -1: beyond the int range); frames[b] = ceil(n_b / hop)
+static int64_t va_encode_clips_total(const vaura_codec_encoder* c, int B, int64_t n_max, const int64_t* n, int* frames, int* off, int* gap_out,
+                                     int64_t* hop_out) {
+  int64_t hop = 1;
+  const int gap = va_clips_gap_encode(c, &hop);
+  if (gap < 0) return 0;
+  for (int b = 0; b < B; ++b) {
+    if (n[b] < 1 || (n_max > 0 && n[b] > n_max)) return 0;
+    const int64_t f = (n[b] + hop - 1) / hop;
+    if (f > 0x7fffffff) return -1;
+    frames[b] = (int)f;
+  }
+  int64_t total = 0;
+  if (!va_clips_offsets(frames, B, gap, off, &total)) return -1;
+  if (gap_out) *gap_out = gap;
+  if (hop_out) *hop_out = hop;
+  return total;
+}
+static size_t va_encode_clips_elems(const vaura_codec_encoder* c, int64_t total, int64_t hop) {
+  const size_t need = vaura_dac_encode_workspace_elems(c, 1, total * hop);      // >= total * hop packed samples
+  const size_t kc = (size_t)c->n_codebooks * (size_t)total;
+  return need > kc ? need : kc;
+}
+
+size_t vaura_dac_encode_clips_workspace_elems(const vaura_codec_encoder* c, int B, const int64_t* sample_lengths) {
+  if (!c || !sample_lengths || B <= 0) return 0;
+  std::vector<int> off((size_t)B), frames((size_t)B);
+  int64_t hop = 1;
+  const int64_t total = va_encode_clips_total(c, B, 0, sample_lengths, frames.data(), off.data(), nullptr, &hop);
+  if (total <= 0 || total > 0x7fffffff / hop) return 0;
+  return va_encode_clips_elems(c, total, hop);
+}
+
+int vaura_dac_encode_clips(const vaura_codec_encoder* c, const float* wav, int B, int64_t n_max, const int64_t* sample_lengths,
+                           int32_t* codes, vaura_stream_t s_) {
+  if (!c || !wav || !codes || !sample_lengths || B <= 0 || n_max <= 0) return VAURA_ERR_ARG;
+  if (!va_encoder_shape_ok(c)) return VAURA_ERR_SHAPE;
+  std::vector<int> off((size_t)B), frames((size_t)B);
+  std::vector<int64_t> n(sample_lengths, sample_lengths + B);
+  ClipLayout lay;
+  int64_t hop = 1;
+  lay.B = B; lay.off = off.data(); lay.len = frames.data(); lay.aux = n.data();
+  lay.total = va_encode_clips_total(c, B, n_max, sample_lengths, frames.data(), off.data(), &lay.gap, &hop);
+  if (lay.total == 0) return VAURA_ERR_ARG;              // a length outside 1 .. n_max
+  // rows (samples at the first level) and rows * channels are ints in every conv launch
+  if (lay.total < 0 || lay.total > 0x7fffffff / hop || va_encode_clips_elems(c, lay.total, hop) > (size_t)0x7fffffff ||
+      n_max > 0x7fffffff || (int64_t)B * ((n_max + hop - 1) / hop) > 0x7fffffff)
+    return VAURA_ERR_SHAPE;
+  if (c->ws_elems < va_encode_clips_elems(c, lay.total, hop)) return VAURA_ERR_ARG;
+  for (int i = 0; i < 4; ++i) if (!c->ws[i]) return VAURA_ERR_ARG;
+  return va_dac_encode_pass(c, wav, B, n_max, codes, &lay, hop, as_stream(s_));
 }
 
 int vaura_dac_enc_conv_in(const float* wav, const float* w, const float* bias, const float* alpha, float* out_raw, void* out_act,

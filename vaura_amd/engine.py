@@ -1120,6 +1120,19 @@ def score_logits(logits: torch.Tensor, targets: torch.Tensor, mask: torch.Tensor
     return loss, lpc, nll
 
 
+def _clip_lengths(name: str, lengths, batch: int, hi: int) -> list:
+    """One int per clip in 1 .. ``hi`` as a list of Python ints; anything else is refused before any device work."""
+    from . import clip_params
+    if not clip_params.is_per_clip(lengths):
+        raise L.VauraHipError(f"{name} must be one integer per clip (a list, tuple or 1-D tensor), got {lengths!r}")
+    n = clip_params._int_list(name, lengths)
+    if len(n) != batch:
+        raise L.VauraHipError(f"{name} has {len(n)} values for a batch of {batch} clips")
+    if min(n) < 1 or max(n) > hi:
+        raise L.VauraHipError(f"{name} must lie in 1 .. {hi}, got {n}")
+    return n
+
+
 class CodecEngine:
     """DAC decode (codes -> waveform) on the HIP path; weights from a DAC-1.0.0-keyed state dict."""
 
@@ -1225,6 +1238,35 @@ class CodecEngine:
             wav = torch.empty(B, 1, T * self.cfg.hop, dtype=torch.float32, device=self.dev)
             L.check(self.lib.vaura_dac_decode(C.byref(self.c), L.ptr(ci), B, T, L.ptr(wav), L.current_stream(self.dev)),
                     "vaura_dac_decode")
+            self._codes_keepalive = ci
+        if caller is not None:
+            wav.record_stream(caller)
+        return wav
+
+    @torch.no_grad()
+    def decode_clips(self, codes: torch.Tensor, lengths) -> torch.Tensor:
+        """codes (B, K, T_max) on device, padded; ``lengths`` one int per clip (host values), 1 <= T_b <= T_max -> wav (B, 1, T_max*hop):
+        ``wav[b, :, :T_b*hop]`` is bit for bit ``decode(codes[b:b+1, :, :T_b])``, zeros behind it.  ONE codec pass over the clips packed
+        into a single sequence (``codec_clips.clip_layout``; vaura_dac_decode_clips), whatever the lengths."""
+        from .codec_clips import clip_layout
+        B, K, T = codes.shape
+        n = _clip_lengths("lengths", lengths, B, T)
+        lay = clip_layout(n, self.cfg, "decode")
+        host = (C.c_int32 * B)(*n)
+        with off_null_stream(self.dev) as caller:
+            ci = codes.to(self.dev, torch.int32).contiguous()
+            need = self.lib.vaura_dac_decode_clips_workspace_elems(C.byref(self.c), B, host)
+            if need == 0:
+                raise L.VauraHipError(f"decode_clips: a packed sequence of {lay.total} frames is beyond what one pass can index")
+            if self._ws_key is None or self._ws_key < need:
+                self._ws = [torch.empty(need, dtype=torch.float32, device=self.dev) for _ in range(4)]
+                for i in range(4):
+                    self.c.ws[i] = L.ptr(self._ws[i])
+                self.c.ws_elems = need
+                self._ws_key = need
+            wav = torch.empty(B, 1, T * self.cfg.hop, dtype=torch.float32, device=self.dev)
+            L.check(self.lib.vaura_dac_decode_clips(C.byref(self.c), L.ptr(ci), B, T, host, L.ptr(wav), L.current_stream(self.dev)),
+                    "vaura_dac_decode_clips")
             self._codes_keepalive = ci
         if caller is not None:
             wav.record_stream(caller)
@@ -1512,6 +1554,41 @@ class CodecEncoderEngine:
             codes = torch.empty(B, self.cfg.n_codebooks, T, dtype=torch.int32, device=self.dev)
             L.check(self.lib.vaura_dac_encode(C.byref(self.c), L.ptr(x), B, T * hop, L.ptr(codes), L.current_stream(self.dev)),
                     "vaura_dac_encode")
+            out = codes.to(torch.int64)
+        if caller is not None:
+            out.record_stream(caller)
+        return out
+
+    @torch.no_grad()
+    def encode_clips(self, wav: torch.Tensor, sample_lengths) -> torch.Tensor:
+        """wav (B, 1, N) / (B, N) on the device, padded; ``sample_lengths`` one int per clip (host values), 1 <= n_b <= N -> codes
+        (B, K, ceil(N / hop)) int64: ``codes[b, :, :ceil(n_b / hop)]`` is bit for bit ``encode(wav[b:b+1, ..., :n_b])``, 0 behind it.
+        ONE encoder pass over the clips packed into a single sequence (``codec_clips.clip_layout``; vaura_dac_encode_clips)."""
+        from .codec_clips import clip_layout
+        if wav.dim() == 3:
+            wav = wav[:, 0]
+        if wav.dim() != 2:
+            raise L.VauraHipError(f"encode_clips takes a (B, 1, N) or (B, N) batch, got shape {tuple(wav.shape)}")
+        B, N = wav.shape
+        n = _clip_lengths("sample_lengths", sample_lengths, B, N)
+        lay = clip_layout(n, self.cfg, "encode")
+        host = (C.c_int64 * B)(*n)
+        T = (N + lay.hop - 1) // lay.hop
+        with off_null_stream(self.dev) as caller:
+            x = wav.to(self.dev, torch.float32).contiguous()
+            need = self.lib.vaura_dac_encode_clips_workspace_elems(C.byref(self.c), B, host)
+            if need == 0:
+                raise L.VauraHipError(f"encode_clips: a packed sequence of {lay.total} frames is beyond what one pass can index")
+            if self._ws_key is None or self._ws_key < need:
+                self._ws = [torch.empty(need, dtype=torch.float32, device=self.dev) for _ in range(4)]
+                for i in range(4):
+                    self.c.ws[i] = L.ptr(self._ws[i])
+                self.c.ws_elems = need
+                self._ws_key = need
+            codes = torch.empty(B, self.cfg.n_codebooks, T, dtype=torch.int32, device=self.dev)
+            L.check(self.lib.vaura_dac_encode_clips(C.byref(self.c), L.ptr(x), B, N, host, L.ptr(codes), L.current_stream(self.dev)),
+                    "vaura_dac_encode_clips")
+            self._wav_keepalive = x
             out = codes.to(torch.int64)
         if caller is not None:
             out.record_stream(caller)

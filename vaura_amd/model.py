@@ -428,8 +428,8 @@ class VAURAModel(nn.Module):
         """``return_logprobs`` / ``num_candidates`` / ``return_all_candidates`` / ``return_relevance`` / ``rank_by``: see ``generate_tokens`` — its extra entries are added
         to the result ("sampled_indices" takes "tokens"); the codec decodes the winners (B clips), or with ``return_all_candidates``
         all B * N takes.  With the defaults the result is the dict it always was.
-        ``max_new_tokens`` as one int per clip and / or ``video_lengths`` (see ``generate_tokens``): the codec decodes once per distinct
-        length (the clips grouped), "generated_audio" is (B, 1, T_max * hop) with zeros past each clip's end, and the result gains
+        ``max_new_tokens`` as one int per clip and / or ``video_lengths`` (see ``generate_tokens``): the codec decodes the padded batch in
+        one pass (``decode_clips``: the clips packed into one sequence; clips that all have one length: the plain ``decode``), "generated_audio" is (B, 1, T_max * hop) with zeros past each clip's end, and the result gains
         "lengths" (B,) in frames and "audio_lengths" (B,) in samples.  With an int and no ``video_lengths`` nothing is added.
         The post stage takes that batch in one call: ``post.normalize_audio(r["generated_audio"], ..., lengths=r["audio_lengths"])``,
         or ``post.scale_batch`` / ``post.save_wavs`` for the per-clip tensors and files."""
@@ -452,17 +452,20 @@ class VAURAModel(nn.Module):
             if "lengths" not in extra:
                 generated_audio = self.audio_encoder.decode([(out_codes[..., :K, :], None)])
             else:
-                # one codec pass per distinct length: a clip's waveform is what decoding its own T_b frames gives, zeros behind it
+                # ONE codec pass over the clips packed into a single sequence: a clip's waveform is, bit for bit, what decoding its own
+                # T_b frames alone gives, zeros behind it (every take of a clip has the clip's length)
                 rows = out_codes.shape[0]
-                row_len = extra["lengths"].repeat_interleave(rows // extra["lengths"].shape[0])      # (every take of a clip has its length)
-                generated_audio = None
-                for T_b in sorted(set(row_len.tolist())):
-                    idx = torch.nonzero(row_len == T_b)[:, 0]
-                    wav = self.audio_encoder.decode([(out_codes[idx][..., :K, :T_b], None)])
-                    if generated_audio is None:
-                        hop = wav.shape[-1] // T_b
-                        generated_audio = wav.new_zeros(rows, wav.shape[1], out_codes.shape[-1] * hop)
-                    generated_audio[idx, :, :wav.shape[-1]] = wav
+                row_len = extra["lengths"].repeat_interleave(rows // extra["lengths"].shape[0])
+                lens = row_len.tolist()
+                if len(set(lens)) == 1:
+                    # every clip has the same length: the plain batched pass gives the same bits without the gaps and the pack / clear /
+                    # unpack launches, which cost 2.4 % at 8 clips of 220 frames
+                    generated_audio = self.audio_encoder.decode([(out_codes[..., :K, :lens[0]], None)])
+                    if lens[0] < out_codes.shape[-1]:
+                        generated_audio = torch.nn.functional.pad(generated_audio, (0, generated_audio.shape[-1] // lens[0] * (out_codes.shape[-1] - lens[0])))
+                else:
+                    generated_audio = self.audio_encoder.decode_clips(out_codes[..., :K, :], lens)
+                hop = generated_audio.shape[-1] // out_codes.shape[-1]
                 extra["audio_lengths"] = extra["lengths"] * hop
         if caller is not None:
             out_codes.record_stream(caller)
@@ -515,7 +518,7 @@ class VAURAModel(nn.Module):
         Delay patterns give every timestep a logit, so the mask is all true and no reverted row is NaN.
         A padded batch of clips of different durations: ``audio_lengths`` — one int per clip, the samples of ``audio[b]`` that are real —
         and / or ``video_lengths`` (one int per clip, the leading video tokens that are real, as in ``generate``).  The audio is then
-        encoded once per distinct length, each group cut to its own samples, so clip b's codes are those of the clip encoded alone
+        encoded in one pass (``encode_clips``: every clip cut to its own samples, packed into one sequence), so clip b's codes are those of the clip encoded alone
         (``Ta_b`` = what the encoder returns for its samples; ``aud_feats`` is padded with 0 to the longest), the clips are scored in
         one ``DecoderEngine.score_clips`` call, and ``logits_mask[b, :, t]`` = t < Ta_b (the logits rows behind it are NaN):
         ``_compute_loss`` under that mask is the loss of the real frames.  With neither keyword every path is the one it was."""
@@ -529,8 +532,8 @@ class VAURAModel(nn.Module):
 
     def _encode_clips(self, audio: torch.Tensor, audio_lengths=None):
         """``audio_encoder.encode`` of a padded batch -> (codes (B, Kc, Ta_max), [Ta_b] or None).  ``audio_lengths`` None: one encode of
-        the whole batch, as ever.  Otherwise one encode per distinct length, each group cut to its own samples — a clip encoded with
-        zero padding behind it is not the clip — as ``generate`` decodes once per distinct length; frames behind Ta_b hold 0."""
+        the whole batch, as ever.  Otherwise ``audio_encoder.encode_clips``: one pass over the clips, each cut to its own samples — a clip encoded
+        with zero padding behind it is not the clip — packed into one sequence, as ``generate`` decodes them; frames behind Ta_b hold 0."""
         if audio_lengths is None:
             return self.audio_encoder.encode(audio), None
         if not clip_params.is_per_clip(audio_lengths):
@@ -540,17 +543,12 @@ class VAURAModel(nn.Module):
             raise L.VauraHipError(f"audio_lengths has {len(n)} values for a batch of {audio.shape[0]} clips")
         if min(n) < 1 or max(n) > audio.shape[-1]:
             raise L.VauraHipError(f"audio_lengths must lie in 1 .. {audio.shape[-1]} (the samples of the padded batch), got {n}")
-        groups = []
-        for n_b in sorted(set(n)):
-            idx = torch.tensor([b for b, v in enumerate(n) if v == n_b], device=audio.device)
-            groups.append((idx, self.audio_encoder.encode(audio[idx][..., :n_b])))
-        ta_max = max(int(c.shape[-1]) for _, c in groups)
-        codes = groups[0][1].new_zeros(len(n), groups[0][1].shape[1], ta_max)
-        lengths = [0] * len(n)
-        for idx, c in groups:
-            codes[idx.to(codes.device), :, :c.shape[-1]] = c
-            for b in idx.tolist():
-                lengths[b] = int(c.shape[-1])
+        from .codec_clips import clip_layout
+        lengths = list(clip_layout(n, self.audio_encoder.cfg, "encode").frames)
+        if len(set(n)) == 1:      # one length: the plain batched pass, the same bits for 2.3 % less
+            codes = self.audio_encoder.encode(audio[..., :n[0]])
+        else:
+            codes = self.audio_encoder.encode_clips(audio[..., :max(n)], n)
         return codes, lengths
 
     @torch.no_grad()
