@@ -784,6 +784,43 @@ typedef struct vaura_vit {
 int vaura_avclip_forward(const vaura_vit* v, const float* frames, int n_seg, float* feats, vaura_stream_t s);
 size_t vaura_avclip_workspace_bytes(const vaura_vit* v, int n_seg, int which);
 
+/* Op-level entry points of the extractor: each runs ONE launcher of vaura_avclip_forward (the same static function the forward
+ * calls) on caller-owned buffers, so the op-level parity tests (tests/test_gpu_avclip_ops.py) test the product path.  Those that
+ * take a vaura_vit read only its dims, eps and the pointers named below (no workspace, no blocks) and apply the forward's own
+ * shape gate first: dim == 768, heads * 64 == dim, n_frames == 8, 1 <= n_patches <= 255, hidden % 96 == 0, patch_k % 32 == 0
+ * (VAURA_ERR_SHAPE otherwise; NULL pointers / counts <= 0: VAURA_ERR_ARG; nothing is launched in either case).
+ * "pair" = the (hi, lo) fp16 pair layout [row][C/8][hi|lo][8] halves, 4 bytes per element.
+ *   patchify       frames (n_seg, in_chans, frames_per_seg, img, img) fp32, 16-byte aligned -> patches (n_seg * T/pt * (img/patch)^2,
+ *                  in_chans * pt * patch^2) pair, columns in the Conv3d weight's flattening order.  patch % 8, img % patch,
+ *                  frames_per_seg % patch_t and columns % 32 must be 0 (VAURA_ERR_SHAPE).
+ *   embed          x (n_seg, 1 + 8 n_patches, 768) fp32 in place: row 0 = cls_token + pos_embed[0]; row 1 + f n_patches + i +=
+ *                  pos_embed[1 + i] + temp_embed[f] (v->cls_token, v->pos_embed, v->temp_embed).
+ *   layernorm      `rows` rows of x (v->eps, biased variance) -> out_f32 and / or out_pair (either may be NULL, not both).  map 0: row r
+ *                  -> row r.  map 1 (rows a multiple of 8 n_patches): source rows are the patch rows of sequences of 1 + 8 n_patches
+ *                  rows (row 0 of each is never read), destination row (seg * 8 + f) * (n_patches + 1) + 1 + i (slot 0 not written).
+ *   fill_rows      dst[i * stride] (768 floats each) = vec for i < n.
+ *   cls_attention  qkv (n_seq * Lseq, 3 * 768) fp32 rows [q | k | v]: the query of row 0 of every sequence over its Lseq rows ->
+ *                  out_pair row seq * out_stride.  part != NULL and Lseq > 512: 8 key splits and a combine launch, part >= n_seq *
+ *                  heads * 8 * 66 floats.  Lseq <= 2041 (VAURA_ERR_SHAPE).
+ *   time / space   qkv (n_seg * (1 + 8 n_patches), 3 * 768): every patch row over the CLS row and the 8 rows at its location / the
+ *                  n_patches rows of its frame -> out_pair, same row; CLS rows of out_pair are not written.  n_patches > 207 takes
+ *                  the generic fp32 kernel.
+ *   linear_pair    out[b][row + oshift] = act(in[b][row] . w^T + bias (+ res[b][row + oshift])), in (B, Lin, Cin) pair, w (Cout, Cin)
+ *                  pair, out_raw fp32 and / or out_act pair in sequences of Lout rows; res may be out_raw.  act 1: exact GELU
+ *                  into out_act, 2: identity.  Cin % 32, Cout % 96 (VAURA_ERR_SHAPE); Lin + oshift <= Lout, act in {1, 2} (VAURA_ERR_ARG). */
+int vaura_vit_patchify(const float* frames, void* patches, int n_seg, int in_chans, int frames_per_seg, int img, int patch_t, int patch,
+                       vaura_stream_t s);
+int vaura_vit_embed(const vaura_vit* v, float* x, int n_seg, vaura_stream_t s);
+int vaura_vit_layernorm(const vaura_vit* v, const float* x, const float* w, const float* b, float* out_f32, void* out_pair, int64_t rows,
+                        int map, vaura_stream_t s);
+int vaura_vit_fill_rows(const vaura_vit* v, float* dst, const float* vec, int64_t n, int64_t stride, vaura_stream_t s);
+int vaura_vit_cls_attention(const vaura_vit* v, const float* qkv, void* out_pair, float* part, int n_seq, int Lseq, int64_t out_stride,
+                            vaura_stream_t s);
+int vaura_vit_time_attention(const vaura_vit* v, const float* qkv, void* out_pair, int n_seg, vaura_stream_t s);
+int vaura_vit_space_attention(const vaura_vit* v, const float* qkv, void* out_pair, int n_seg, vaura_stream_t s);
+int vaura_linear_pair(const void* in, const void* w, const float* bias, const float* res, float* out_raw, void* out_act, int act, int B,
+                      int Lin, int Lout, int oshift, int Cin, int Cout, vaura_stream_t s);
+
 /* -------------------------------------------------------------------------------------------
  * Video preprocessing (csrc/preproc.hip): decoded uint8 frames -> the extractor's input.  The `video_transforms_test` list of
  * configs/generate_*.yaml (Resize(resize, antialias) -> CenterCrop -> ToFloat32DType -> Normalize) followed by

@@ -144,6 +144,16 @@ SIGNATURES = {
     "vaura_dac_encode_workspace_elems": (C.c_size_t, [C.POINTER(CodecEncoder), C.c_int, C.c_int64]),
     "vaura_avclip_forward": (C.c_int, [C.POINTER(Vit), C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     "vaura_avclip_workspace_bytes": (C.c_size_t, [C.POINTER(Vit), C.c_int, C.c_int]),
+    "vaura_vit_patchify": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    "vaura_vit_embed": (C.c_int, [C.POINTER(Vit), C.c_void_p, C.c_int, C.c_void_p]),
+    "vaura_vit_layernorm": (C.c_int, [C.POINTER(Vit), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int,
+                                      C.c_void_p]),
+    "vaura_vit_fill_rows": (C.c_int, [C.POINTER(Vit), C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p]),
+    "vaura_vit_cls_attention": (C.c_int, [C.POINTER(Vit), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int64, C.c_void_p]),
+    "vaura_vit_time_attention": (C.c_int, [C.POINTER(Vit), C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
+    "vaura_vit_space_attention": (C.c_int, [C.POINTER(Vit), C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
+    "vaura_linear_pair": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int,
+                                    C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "vaura_video_preprocess": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                          C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
                                          C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),

@@ -19,6 +19,11 @@
 
 typedef _Float16 vf16x8 __attribute__((ext_vector_type(8)));
 
+// The (hi, lo) split of this file, hi = fp16(x), lo = fp16(x - hi), needs ONE hi: the value stored and the value lo is taken against.
+// Where x is a product formed at the call site (acc * inv), the compiler may fuse it into the conversion (v_fma_mixlo_f16: fp16 of the
+// exact product) at one use and not at the other; on an fp16 rounding tie of the fp32 product the two differ by one fp16 step.  This
+// compiler takes both from one conversion in put_pair8 / put_pair4 and the CLS kernels (checked in the device code; guarded by
+// tests/test_gpu_avclip_ops.py); vit_space_attn_mfma_kernel, where it did not, pins the product in a register first.
 __device__ __forceinline__ void put_pair8(uint16_t* base, size_t row, int oct, int C, const float* v) {
   vf16x8 hi, lo;
 #pragma unroll
@@ -577,7 +582,11 @@ __global__ __launch_bounds__(512) void vit_space_attn_mfma_kernel(const float* _
         vf16x4 hi, lo;
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
-          const float o = acc[r] * inv;
+          // One fp32 product, then split.  Left to the compiler, the conversion behind `hi` was emitted twice: the stored one as
+          // fp16(fp32(acc inv)), the one `lo` is taken against as fp16 of the EXACT product (v_fma_mixlo_f16).  Where the fp32 product is
+          // an fp16 rounding tie the two differ by one fp16 step, and hi + lo was off by that step (found by tests/test_gpu_avclip_ops.py).
+          float o = acc[r] * inv;
+          asm volatile("" : "+v"(o));
           hi[r] = (_Float16)o;
           lo[r] = (_Float16)(o - (float)hi[r]);
         }
@@ -759,6 +768,33 @@ __global__ __launch_bounds__(512) void vit_space_attn_pair_kernel(const float* _
 }
 
 // ---------------------------------------------------------------------------------------------- driver
+// The shape gate of vaura_avclip_forward, shared with the op-level entry points below: what the kernels of this file were written for.
+static int vit_gate(const vaura_vit* v) {
+  if (v->dim != 768 || v->heads * VHD != v->dim || (v->hidden % 96) || (v->patch_k % 32) || v->n_frames != 8 || v->heads * v->n_frames > 128 ||
+      v->n_patches > 255)
+    return VAURA_ERR_SHAPE;
+  return 0;
+}
+
+static int patchify(const float* frames, uint16_t* P, int n_seg, int C, int T, int HW, int pt, int ps, hipStream_t s) {
+  const int gh = HW / ps;
+  const int64_t total = (int64_t)n_seg * (T / pt) * gh * gh * (C * pt * ps * ps / 8);
+  VA_LAUNCH(vit_patchify_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, frames, P, n_seg, C, T, HW, pt, ps);
+  return 0;
+}
+
+static int embed(const vaura_vit* v, float* X, int n_seg, hipStream_t s) {
+  const int64_t q4 = (int64_t)n_seg * (1 + v->n_frames * v->n_patches) * (v->dim / 4);
+  VA_LAUNCH(vit_embed_kernel, dim3((unsigned)((q4 + 255) / 256)), dim3(256), 0, s, X, v->cls_token, v->pos_embed, v->temp_embed, n_seg,
+            v->n_frames, v->n_patches, v->dim);
+  return 0;
+}
+
+static int fill_rows(float* dst, const float* vec, int64_t n, int64_t stride, int D, hipStream_t s) {
+  VA_LAUNCH(vit_fill_rows_kernel, dim3((unsigned)((n * (D / 4) + 255) / 256)), dim3(256), 0, s, dst, vec, n, stride, D);
+  return 0;
+}
+
 static int ln(const vaura_vit* v, const float* X, const float* w, const float* b, float* of, uint16_t* op, int64_t rows, int map, hipStream_t s) {
   VA_LAUNCH(vit_ln_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, s, X, w, b, of, op, rows, v->dim, v->eps, map, v->n_frames, v->n_patches);
   return 0;
@@ -781,6 +817,45 @@ static int cls_attention(const vaura_vit* v, const float* qkv, uint16_t* out, fl
   return 0;
 }
 
+// time pattern launcher
+static int time_attention(const vaura_vit* v, const float* qkv, uint16_t* out, int n_seg, hipStream_t s) {
+  const int D = v->dim;
+  if ((va_debug_flags_get() & 1024) || (v->heads & 1))      // debug flag bit 10: one thread per (head, frame)
+    VA_LAUNCH(vit_time_attn_kernel<8>, dim3(v->n_patches, n_seg), dim3(128), 0, s, qkv, out, v->n_patches,
+              v->heads, D);
+  else
+    VA_LAUNCH(vit_time_attn16_kernel<8>, dim3(v->heads / 2, v->n_patches, n_seg), dim3(256), 0, s, qkv, out,
+              v->n_patches, D);
+  return 0;
+}
+
+// space pattern launcher: the fp16-pair MFMA kernel for n_patches + 1 <= 208 keys, else (or under debug flags) the fp32 kernels
+static int space_attention(const vaura_vit* v, const float* qkv, uint16_t* out, int n_seg, hipStream_t s) {
+  const int D = v->dim;
+  if (v->n_patches + 1 <= VS_NKT * 16 && !(va_debug_flags_get() & (128 | 2048))) {   // the fp16-pair MFMA kernel
+    const size_t sm = (size_t)2 * (VP_KEYS + VP_VROWS) * VP_ROWH * 2;               // 135 KB of the CU's 160 KB
+    static unsigned long long big_lds_p = 0;
+    if (va_big_lds_once(reinterpret_cast<const void*>(vit_space_attn_pair_kernel), sm, &big_lds_p)) return VAURA_ERR_STATE;
+    VA_LAUNCH(vit_space_attn_pair_kernel, dim3(v->heads, v->n_frames, n_seg), dim3(512), sm, s, qkv, out, v->n_frames,
+              v->n_patches, D);
+  } else if (v->n_patches + 1 <= VS_NKT * 16 && !(va_debug_flags_get() & 128)) {   // debug flag bit 11: exact-fp32 MFMA; bit 7: one thread per query
+    const size_t sm = sizeof(float) * (size_t)(VS_NKT * 16) * (VSK + VSV);       // 108 KB of the CU's 160 KB
+    static unsigned long long big_lds_m = 0;
+    if (va_big_lds_once(reinterpret_cast<const void*>(vit_space_attn_mfma_kernel), sm, &big_lds_m)) return VAURA_ERR_STATE;
+    VA_LAUNCH(vit_space_attn_mfma_kernel, dim3(v->heads, v->n_frames, n_seg), dim3(512), sm, s, qkv, out, v->n_frames,
+              v->n_patches, D);
+  } else {
+    const size_t sm = sizeof(float) * 2 * (size_t)(v->n_patches + 1) * VHD;      // 100.9 KB of the CU's 160 KB
+    // the attribute is set once per device: ask for the most this kernel can need (n_patches <= 255: 128 KB), not this call's size
+    const size_t sm_max = sizeof(float) * 2 * (size_t)256 * VHD;
+    static unsigned long long big_lds = 0;
+    if (va_big_lds_once(reinterpret_cast<const void*>(vit_space_attn_kernel), sm_max, &big_lds)) return VAURA_ERR_STATE;
+    VA_LAUNCH(vit_space_attn_kernel, dim3(v->heads, v->n_frames, n_seg), dim3(256), sm, s, qkv, out, v->n_frames,
+              v->n_patches, D);
+  }
+  return 0;
+}
+
 static int divided_attention(const vaura_vit* v, const vaura_vit_attn& at, const float* ln_w, const float* ln_b, bool time, int n_seg,
                              hipStream_t s) {
   const int D = v->dim, L = 1 + v->n_frames * v->n_patches;
@@ -791,34 +866,8 @@ static int divided_attention(const vaura_vit* v, const vaura_vit_attn& at, const
   if (rc) return rc;
   rc = cls_attention(v, (const float*)v->ws_qkv, v->ws_a, v->ws_s /* free until the aggregation layer */, n_seg, L, (int64_t)L, s);
   if (rc) return rc;
-  if (time) {
-    if ((va_debug_flags_get() & 1024) || (v->heads & 1))      // debug flag bit 10: one thread per (head, frame)
-      VA_LAUNCH(vit_time_attn_kernel<8>, dim3(v->n_patches, n_seg), dim3(128), 0, s, (const float*)v->ws_qkv, v->ws_a, v->n_patches,
-                v->heads, D);
-    else
-      VA_LAUNCH(vit_time_attn16_kernel<8>, dim3(v->heads / 2, v->n_patches, n_seg), dim3(256), 0, s, (const float*)v->ws_qkv, v->ws_a,
-                v->n_patches, D);
-  } else {
-    if (v->n_patches + 1 <= VS_NKT * 16 && !(va_debug_flags_get() & (128 | 2048))) {   // the fp16-pair MFMA kernel
-      const size_t sm = (size_t)2 * (VP_KEYS + VP_VROWS) * VP_ROWH * 2;               // 135 KB of the CU's 160 KB
-      static unsigned long long big_lds_p = 0;
-      if (va_big_lds_once(reinterpret_cast<const void*>(vit_space_attn_pair_kernel), sm, &big_lds_p)) return VAURA_ERR_STATE;
-      VA_LAUNCH(vit_space_attn_pair_kernel, dim3(v->heads, v->n_frames, n_seg), dim3(512), sm, s, (const float*)v->ws_qkv, v->ws_a, v->n_frames,
-                v->n_patches, D);
-    } else if (v->n_patches + 1 <= VS_NKT * 16 && !(va_debug_flags_get() & 128)) {   // debug flag bit 11: exact-fp32 MFMA; bit 7: one thread per query
-      const size_t sm = sizeof(float) * (size_t)(VS_NKT * 16) * (VSK + VSV);       // 108 KB of the CU's 160 KB
-      static unsigned long long big_lds_m = 0;
-      if (va_big_lds_once(reinterpret_cast<const void*>(vit_space_attn_mfma_kernel), sm, &big_lds_m)) return VAURA_ERR_STATE;
-      VA_LAUNCH(vit_space_attn_mfma_kernel, dim3(v->heads, v->n_frames, n_seg), dim3(512), sm, s, (const float*)v->ws_qkv, v->ws_a, v->n_frames,
-                v->n_patches, D);
-    } else {
-      const size_t sm = sizeof(float) * 2 * (size_t)(v->n_patches + 1) * VHD;      // 100.9 KB of the CU's 160 KB
-      static unsigned long long big_lds = 0;
-      if (va_big_lds_once(reinterpret_cast<const void*>(vit_space_attn_kernel), sm, &big_lds)) return VAURA_ERR_STATE;
-      VA_LAUNCH(vit_space_attn_kernel, dim3(v->heads, v->n_frames, n_seg), dim3(256), sm, s, (const float*)v->ws_qkv, v->ws_a, v->n_frames,
-                v->n_patches, D);
-    }
-  }
+  rc = time ? time_attention(v, (const float*)v->ws_qkv, v->ws_a, n_seg, s) : space_attention(v, (const float*)v->ws_qkv, v->ws_a, n_seg, s);
+  if (rc) return rc;
   // x = x + proj(attention)      vit_helper.py:452-468
   return va_launch_linear_pair(v->ws_a, (const uint16_t*)at.proj_w, at.proj_b, v->ws_x, v->ws_x, nullptr, 2, 1, (int)N, (int)N, 0, D, D, s);
 }
@@ -843,9 +892,7 @@ size_t vaura_avclip_workspace_bytes(const vaura_vit* v, int n_seg, int which) {
 
 int vaura_avclip_forward(const vaura_vit* v, const float* frames, int n_seg, float* feats, vaura_stream_t s_) {
   if (!v || !frames || !feats || n_seg <= 0 || !v->blocks_host) return VAURA_ERR_ARG;
-  if (v->dim != 768 || v->heads * VHD != v->dim || (v->hidden % 96) || (v->patch_k % 32) || v->n_frames != 8 || v->heads * v->n_frames > 128 ||
-      v->n_patches > 255)
-    return VAURA_ERR_SHAPE;
+  if (vit_gate(v)) return VAURA_ERR_SHAPE;
   if (!v->ws_x || !v->ws_qkv || !v->ws_a || !v->ws_h || !v->ws_p || !v->ws_z || !v->ws_s) return VAURA_ERR_ARG;
   hipStream_t s = as_stream(s_);
   const int D = v->dim, nf = v->n_frames, np = v->n_patches, L = 1 + nf * np;
@@ -853,14 +900,12 @@ int vaura_avclip_forward(const vaura_vit* v, const float* frames, int n_seg, flo
   int rc;
   // ---- tokens: 3-D patch embedding as a GEMM into rows 1.. of every sequence, then CLS + positional embeddings
   {
-    const int64_t total = (int64_t)n_seg * nf * np * (v->patch_k / 8);
-    VA_LAUNCH(vit_patchify_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, frames, v->ws_p, n_seg, v->in_chans, v->frames,
-              v->img, v->patch_t, v->patch);
+    rc = patchify(frames, v->ws_p, n_seg, v->in_chans, v->frames, v->img, v->patch_t, v->patch, s);
+    if (rc) return rc;
     rc = va_launch_linear_pair(v->ws_p, (const uint16_t*)v->pe_w, v->pe_b, nullptr, v->ws_x, nullptr, 2, n_seg, nf * np, L, 1, v->patch_k, D, s);
     if (rc) return rc;
-    const int64_t q4 = N * (D / 4);
-    VA_LAUNCH(vit_embed_kernel, dim3((unsigned)((q4 + 255) / 256)), dim3(256), 0, s, v->ws_x, v->cls_token, v->pos_embed, v->temp_embed, n_seg,
-              nf, np, D);
+    rc = embed(v, v->ws_x, n_seg, s);
+    if (rc) return rc;
   }
   // ---- 12 divided space-time blocks                                  vit_helper.py:443-472
   for (int i = 0; i < v->depth; ++i) {
@@ -880,7 +925,8 @@ int vaura_avclip_forward(const vaura_vit* v, const float* frames, int n_seg, flo
   const int64_t nq = (int64_t)n_seg * nf, NA = nq * (np + 1);
   rc = ln(v, v->ws_x, v->norm_w, v->norm_b, v->ws_z, nullptr, (int64_t)n_seg * nf * np, 1, s);
   if (rc) return rc;
-  VA_LAUNCH(vit_fill_rows_kernel, dim3((unsigned)((nq * (D / 4) + 255) / 256)), dim3(256), 0, s, v->ws_z, v->agg_cls, nq, (int64_t)(np + 1), D);
+  rc = fill_rows(v->ws_z, v->agg_cls, nq, (int64_t)(np + 1), D, s);
+  if (rc) return rc;
   // ---- spatial aggregation: one pre-norm encoder layer; only its CLS row is used                   motionformer.py:399-448
   float* r0 = v->ws_s;                                  // residual rows (the CLS token) -> x0 after the attention
   float* x0 = r0 + nq * D;
@@ -892,7 +938,8 @@ int vaura_avclip_forward(const vaura_vit* v, const float* frames, int n_seg, flo
   if (rc) return rc;
   rc = cls_attention(v, (const float*)v->ws_qkv, a0, nullptr, (int)nq, np + 1, (int64_t)1, s);     // 197 keys: one workgroup each
   if (rc) return rc;
-  VA_LAUNCH(vit_fill_rows_kernel, dim3((unsigned)((nq * (D / 4) + 255) / 256)), dim3(256), 0, s, r0, v->agg_cls, nq, (int64_t)1, D);
+  rc = fill_rows(r0, v->agg_cls, nq, (int64_t)1, D, s);
+  if (rc) return rc;
   rc = va_launch_linear_pair(a0, (const uint16_t*)v->agg_out_w, v->agg_out_b, r0, x0, nullptr, 2, 1, (int)nq, (int)nq, 0, D, D, s);
   if (rc) return rc;
   rc = ln(v, x0, v->agg_ln2_w, v->agg_ln2_b, nullptr, a0, nq, 0, s);
@@ -900,6 +947,80 @@ int vaura_avclip_forward(const vaura_vit* v, const float* frames, int n_seg, flo
   rc = va_launch_linear_pair(a0, (const uint16_t*)v->agg_l1_w, v->agg_l1_b, nullptr, nullptr, h0, 1, 1, (int)nq, (int)nq, 0, D, v->hidden, s);
   if (rc) return rc;
   return va_launch_linear_pair(h0, (const uint16_t*)v->agg_l2_w, v->agg_l2_b, x0, feats, nullptr, 2, 1, (int)nq, (int)nq, 0, v->hidden, D, s);
+}
+
+// ---------------------------------------------------------------------------------------------- op-level entry points
+// One launcher of the forward above each (the SAME static function the forward calls), for the op-level parity tests of
+// tests/test_gpu_avclip_ops.py.  Every one applies the forward's shape gate before it launches anything.
+static int vit_op_gate(const vaura_vit* v) {
+  if (!v) return VAURA_ERR_ARG;
+  if (vit_gate(v) || v->n_patches <= 0) return VAURA_ERR_SHAPE;
+  return 0;
+}
+
+int vaura_vit_patchify(const float* frames, void* patches, int n_seg, int in_chans, int frames_per_seg, int img, int patch_t, int patch,
+                       vaura_stream_t s_) {
+  if (!frames || !patches || n_seg <= 0) return VAURA_ERR_ARG;
+  // the kernel moves 8 consecutive pixels of one patch row as two aligned float4
+  if (in_chans <= 0 || frames_per_seg <= 0 || img <= 0 || patch_t <= 0 || patch <= 0 || (patch % 8) || (img % patch) || (frames_per_seg % patch_t) ||
+      ((int64_t)in_chans * patch_t * patch * patch) % 32 || ((uintptr_t)frames & 15))
+    return VAURA_ERR_SHAPE;
+  return patchify(frames, reinterpret_cast<uint16_t*>(patches), n_seg, in_chans, frames_per_seg, img, patch_t, patch, as_stream(s_));
+}
+
+int vaura_vit_embed(const vaura_vit* v, float* x, int n_seg, vaura_stream_t s_) {
+  const int rc = vit_op_gate(v);
+  if (rc) return rc;
+  if (!x || n_seg <= 0 || !v->cls_token || !v->pos_embed || !v->temp_embed) return VAURA_ERR_ARG;
+  return embed(v, x, n_seg, as_stream(s_));
+}
+
+int vaura_vit_layernorm(const vaura_vit* v, const float* x, const float* w, const float* b, float* out_f32, void* out_pair, int64_t rows,
+                        int map, vaura_stream_t s_) {
+  const int rc = vit_op_gate(v);
+  if (rc) return rc;
+  if (!x || !w || !b || (!out_f32 && !out_pair) || rows <= 0 || (map != 0 && map != 1)) return VAURA_ERR_ARG;
+  if (map == 1 && rows % ((int64_t)v->n_frames * v->n_patches)) return VAURA_ERR_SHAPE;      // whole segments only
+  return ln(v, x, w, b, out_f32, reinterpret_cast<uint16_t*>(out_pair), rows, map, as_stream(s_));
+}
+
+int vaura_vit_fill_rows(const vaura_vit* v, float* dst, const float* vec, int64_t n, int64_t stride, vaura_stream_t s_) {
+  const int rc = vit_op_gate(v);
+  if (rc) return rc;
+  if (!dst || !vec || n <= 0 || stride <= 0) return VAURA_ERR_ARG;
+  return fill_rows(dst, vec, n, stride, v->dim, as_stream(s_));
+}
+
+int vaura_vit_cls_attention(const vaura_vit* v, const float* qkv, void* out_pair, float* part, int n_seq, int Lseq, int64_t out_stride,
+                            vaura_stream_t s_) {
+  const int rc = vit_op_gate(v);
+  if (rc) return rc;
+  if (!qkv || !out_pair || n_seq <= 0 || out_stride <= 0) return VAURA_ERR_ARG;
+  if (Lseq <= 0 || Lseq > 1 + 8 * 255) return VAURA_ERR_SHAPE;          // the longest sequence the forward's gate lets through
+  return cls_attention(v, qkv, reinterpret_cast<uint16_t*>(out_pair), part, n_seq, Lseq, out_stride, as_stream(s_));
+}
+
+int vaura_vit_time_attention(const vaura_vit* v, const float* qkv, void* out_pair, int n_seg, vaura_stream_t s_) {
+  const int rc = vit_op_gate(v);
+  if (rc) return rc;
+  if (!qkv || !out_pair || n_seg <= 0) return VAURA_ERR_ARG;
+  return time_attention(v, qkv, reinterpret_cast<uint16_t*>(out_pair), n_seg, as_stream(s_));
+}
+
+int vaura_vit_space_attention(const vaura_vit* v, const float* qkv, void* out_pair, int n_seg, vaura_stream_t s_) {
+  const int rc = vit_op_gate(v);
+  if (rc) return rc;
+  if (!qkv || !out_pair || n_seg <= 0) return VAURA_ERR_ARG;
+  return space_attention(v, qkv, reinterpret_cast<uint16_t*>(out_pair), n_seg, as_stream(s_));
+}
+
+int vaura_linear_pair(const void* in, const void* w, const float* bias, const float* res, float* out_raw, void* out_act, int act, int B,
+                      int Lin, int Lout, int oshift, int Cin, int Cout, vaura_stream_t s_) {
+  if (!in || !w || !bias || (!out_raw && !out_act) || B <= 0 || Lin <= 0 || oshift < 0 || (int64_t)Lin + oshift > Lout || (act != 1 && act != 2))
+    return VAURA_ERR_ARG;
+  if (Cin <= 0 || Cout <= 0 || (Cin % 32) || (Cout % 96)) return VAURA_ERR_SHAPE;
+  return va_launch_linear_pair(reinterpret_cast<const uint16_t*>(in), reinterpret_cast<const uint16_t*>(w), bias, res, out_raw,
+                               reinterpret_cast<uint16_t*>(out_act), act, B, Lin, Lout, oshift, Cin, Cout, as_stream(s_));
 }
 
 }  // extern "C"
