@@ -154,6 +154,28 @@ def resolve_lengths(batch: Optional[int], max_new_tokens, video_lengths=None, n_
     return t_max, lens, tv
 
 
+def resolve_segments(batch: Optional[int], video_segments, video_lengths=None, n_segments: Optional[int] = None, flattened: bool = True,
+                     lens: Optional[List[int]] = None) -> List[int]:
+    """``video_segments`` of a call — the leading real segments of every clip, one int per clip in 1 .. ``n_segments`` (dim 1 of the
+    frames) — as a list.  It stands in for ``video_lengths`` (both at once are refused) and counts in units that only the flattened
+    AVCLIP layout has."""
+    if video_lengths is not None:
+        raise _error("video_segments and video_lengths both say how much of a clip's video is real: pass one of them")
+    if not flattened:
+        raise _error("video_segments needs the flattened AVCLIP layout (a MotionFormer extractor with flatten_vis_feats): only there "
+                     "is a video token part of one segment")
+    if not is_per_clip(video_segments):
+        raise _error(f"video_segments must be one integer per clip (a list, tuple or 1-D tensor), got {video_segments!r}")
+    seg = _int_list("video_segments", video_segments)
+    if batch is not None and len(seg) != batch:
+        raise _error(f"video_segments has {len(seg)} values for a batch of {batch} clips")
+    if lens is not None and len(seg) != len(lens):
+        raise _error(f"video_segments has {len(seg)} values but max_new_tokens has {len(lens)}: one value per clip")
+    if not seg or min(seg) < 1 or (n_segments is not None and max(seg) > n_segments):
+        raise _error(f"video_segments must lie in 1 .. {n_segments if n_segments is not None else 'S'} (the segments of the frames), got {seg}")
+    return seg
+
+
 def refuse_lengths(where: str, max_new_tokens=None, video_lengths=None) -> None:
     """Callers that keep one length per call (the sliding window, teacher-forced scoring) refuse a per-clip sequence with a message."""
     if is_per_clip(max_new_tokens) or video_lengths is not None:

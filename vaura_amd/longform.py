@@ -6,6 +6,10 @@ every later chunk is prompted with the tail of the previous one (``max_gen_len -
 produces ``stride_tokens`` new ones; the video segments of a chunk are ``positions % n_segments`` (:336-341).  The
 prompt of a chunk is teacher-forced by the batched prefill pass of the engine (32 positions per weight stream),
 the rest by the captured decode-step graph; the waveform of the whole clip is decoded once at the end (:366-369).
+
+``generate_long`` keeps one duration per call.  ``generate_long_clips`` takes one duration per clip: clip b follows its own
+``chunk_schedule``, and the schedules are merged into ONE ``generate_tokens`` call per chunk index (``clip_chunk_plan``) over the
+per-clip lengths that call already serves; a clip whose schedule has ended stays in the batch, parked, until the longest is done.
 """
 from __future__ import annotations
 
@@ -92,3 +96,220 @@ def generate_long(model, frames: torch.Tensor, duration: float, *, stride: float
     audio = model.audio_encoder.decode([(gen_tokens[..., : model.num_codebooks, :], None)])   # :366-369
     return {"generated_audio": audio, "sampled_indices": gen_tokens,
             **({k: torch.cat(v, dim=-1) for k, v in all_rel.items()} if return_relevance else {})}
+
+
+# ---- one duration per clip: the schedules of the clips merged into one call per chunk index
+def _error(msg: str):
+    from ._lib import VauraHipError
+    return VauraHipError(msg)
+
+
+def _clip_durations(durations, batch: Optional[int] = None) -> List[float]:
+    """``durations`` as a list of ``batch`` finite floats > 0 that each give at least one frame; anything else is refused."""
+    from .clip_params import is_per_clip
+    if not is_per_clip(durations) or getattr(durations, "ndim", 1) != 1:
+        raise _error(f"durations must be one duration per clip (a list, tuple or 1-D tensor), got {durations!r}")
+    vals = durations.tolist() if hasattr(durations, "tolist") else list(durations)
+    if batch is not None and len(vals) != batch:
+        raise _error(f"durations has {len(vals)} values for a batch of {batch} clips")
+    out = []
+    for b, d in enumerate(vals):
+        if isinstance(d, bool) or not isinstance(d, (int, float)):
+            raise _error(f"the duration of clip {b} must be a number of seconds, got {d!r}")
+        d = float(d)
+        if d != d or d in (float("inf"), float("-inf")) or d <= 0.0:
+            raise _error(f"the duration of clip {b} must be finite and positive, got {d!r}")
+        if int(d * COMPRESSION_MODEL_FRAME_RATE) < 1:
+            raise _error(f"the duration of clip {b} ({d!r} s) gives no frame at {COMPRESSION_MODEL_FRAME_RATE} frames per second")
+        out.append(d)
+    if not out:
+        raise _error("durations is empty")
+    return out
+
+
+def _clip_segments(segments, batch: int, S: int) -> List[int]:
+    """``segments`` as a list of ``batch`` ints in 1 .. S (None: every clip has all S)."""
+    from .clip_params import _int_list, is_per_clip
+    if segments is None:
+        return [int(S)] * batch
+    if not is_per_clip(segments):
+        raise _error(f"segments must be one integer per clip (a list, tuple or 1-D tensor), got {segments!r}")
+    vals = _int_list("segments", segments)
+    if len(vals) != batch:
+        raise _error(f"segments has {len(vals)} values for a batch of {batch} clips")
+    if min(vals) < 1 or max(vals) > S:
+        raise _error(f"segments must lie in 1 .. {S} (the segments of the padded batch), got {vals}")
+    return vals
+
+
+def clip_chunk_plan(durations, segments=None, S: Optional[int] = None, *, model_max_duration: float = 2.56, stride: float = 0.64,
+                    vfps: float = 25) -> dict:
+    """The ``chunk_schedule`` of every clip, merged by chunk index — pure bookkeeping, no tensors.  ``durations``: one per clip;
+    ``segments``: the leading real segments S_b of every clip (None: all ``S``); ``S``: the segments of the padded batch.
+    Returns {"stride_tokens", "clips": [per clip: "duration", "segments", "schedule" (its ``chunk_schedule``), "single" (the branch
+    without positions, d_b <= model_max_duration), "length" L_b = offset + max_gen_len of its last chunk], "chunks": [per chunk index
+    c: "prompt_len" (common), "lo" (common; None when no clip of the chunk has positions), and per clip "T" (max_gen_len), "hi",
+    "indices" (the segments of frames[b] the call reads: arange(lo, hi_b) % S_b, or range(S_b) for a single-chunk clip),
+    "n_segments" and "parked", and "width": the segments the call's video tensor holds per clip — the longest selection, and at least
+    the window's (a full chunk's at offset 0), so that the last chunks, where every selection is shorter, still give the call the
+    video tokens of a full window (guidance needs as many as the null embedding holds)]}.  A parked clip — its schedule ended before
+    chunk c — has T = prompt_len + 1, hi None and the one segment [0]: it keeps its row, and what the call gives for it is thrown away.
+    The merge rests on four facts of ``chunk_schedule`` (every chunk of a clip but its last has the full length; chunk c >= 1 starts
+    at c * stride_tokens, has the prompt length full - stride_tokens, and generates at least one frame); they are checked here, and
+    a set of schedules that breaks one is refused rather than merged."""
+    from .clip_params import _int_list
+    d = _clip_durations(durations)
+    B = len(d)
+    if S is None:                      # the batch is as wide as its longest clip
+        if segments is None:
+            raise _error("clip_chunk_plan needs S, the segments of the padded batch, or per-clip segments")
+        S = max(_int_list("segments", segments), default=0)
+    seg = _clip_segments(segments, B, int(S))
+    stride_tokens = int(COMPRESSION_MODEL_FRAME_RATE * stride)
+    full = ceil(model_max_duration * COMPRESSION_MODEL_FRAME_RATE)
+    window = ceil(model_max_duration * vfps) // 16      # the segments of a full chunk at offset 0
+    clips = []
+    for b in range(B):
+        sched = chunk_schedule(d[b], model_max_duration, stride, vfps)
+        last = sched[-1]
+        clips.append(dict(duration=d[b], segments=seg[b], schedule=sched, single=last["positions"] is None,
+                          length=last["offset"] + last["max_gen_len"]))
+    chunks = []
+    for c in range(max(len(cl["schedule"]) for cl in clips)):
+        live = [cl["schedule"][c] for cl in clips if c < len(cl["schedule"])]
+        prompt_len = live[0]["prompt_len"]
+        los = {ch["positions"][0] for ch in live if ch["positions"] is not None}
+        if len({ch["prompt_len"] for ch in live}) != 1 or len(los) > 1 or any(ch["offset"] != c * stride_tokens for ch in live) \
+                or any(ch["new_tokens"] < 1 for ch in live):
+            raise _error(f"the chunk schedules of durations {d} cannot be merged at chunk {c}: the clips disagree on the prompt length, "
+                         "the offset or the first video position, or a chunk generates no frame")
+        lo = los.pop() if los else None
+        T, hi, indices, parked = [], [], [], []
+        for cl in clips:
+            n = len(cl["schedule"])
+            if c >= n:
+                T.append(prompt_len + 1); hi.append(None); indices.append([0]); parked.append(True)
+                continue
+            ch = cl["schedule"][c]
+            if c < n - 1 and ch["max_gen_len"] != full:
+                raise _error(f"the chunk schedules of durations {d} cannot be merged at chunk {c}: a chunk that is not a clip's last "
+                             f"has {ch['max_gen_len']} frames, the window has {full}")
+            T.append(ch["max_gen_len"]); parked.append(False)
+            if ch["positions"] is None:
+                hi.append(None); indices.append(list(range(cl["segments"])))
+            else:
+                hi.append(ch["positions"][1])
+                indices.append([p % cl["segments"] for p in range(ch["positions"][0], ch["positions"][1])])
+                if not indices[-1]:
+                    raise _error(f"chunk {c} of the clip of {cl['duration']} s covers no video segment (positions {ch['positions']})")
+        chunks.append(dict(index=c, prompt_len=prompt_len, lo=lo, T=T, hi=hi, indices=indices, n_segments=[len(i) for i in indices],
+                           width=max(window, max(len(i) for i in indices)), parked=parked))
+    return dict(stride_tokens=stride_tokens, clips=clips, chunks=chunks)
+
+
+REL = ("relevance", "logprob_cond", "logprob_null")
+
+
+@torch.no_grad()
+def generate_long_clips(model, frames: torch.Tensor, durations, *, segments=None, stride: float = 0.64,
+                        model_max_duration: Optional[float] = None, vfps: float = 25, frame_step: int = 1, clip_indices=None,
+                        use_sampling: bool = True, temp: float = 1.0, top_k: int = 128, top_p: float = 0.0, cfg_scale: float = 1.0,
+                        return_relevance: bool = False, video_lengths=None, num_candidates=None) -> dict:
+    """``generate_long`` for a batch whose clips differ in duration, in one call: ``durations`` holds one positive float per clip
+    (list / tuple / 1-D tensor of length B), and clip b's tokens, relevance values and waveform are, bit for bit (``noise_mode=
+    "philox"`` or greedy decoding), those of ``generate_long(model, frames, durations[b], ...)`` on the same batch.
+    ``segments``: one int per clip, 1 <= S_b <= frames.shape[1] — the leading segments of ``frames[b]`` that are real (the batch is
+    padded on dim 1; a shorter video has fewer segments).  Clip b's positions wrap at S_b, and what lies behind is never read: the
+    reference for clip b is then ``generate_long(model, frames[:, :S_b], durations[b], ...)``.
+    The other keywords are ``generate_long``'s.  Clip b follows ``chunk_schedule(durations[b])``; chunk index c of every clip runs in
+    ONE ``model.generate_tokens`` call on the full batch (``clip_chunk_plan``): per-clip ``max_new_tokens``, the clip's own video
+    selection (shorter selections padded by repeating their last segment, hidden by ``video_segments``) and the common prompt.  A
+    clip whose schedule has ended stays in the batch PARKED — one new frame after the prompt, one segment, result thrown away — so
+    the batch, the captured step graph, the kernel instances chosen by row count and the Philox key ``clip_base + row`` stay what
+    they are in the scalar call.  A parked row still goes through the prompt prefill.
+    Returns "sampled_indices" (B, K, L_max) with the special id from frame L_b on, "lengths" (B,) = L_b = the offset plus the length
+    of clip b's last chunk (``ceil`` in the schedule: it can exceed int(d_b * 86) by one, as in ``generate_long``), "generated_audio"
+    (B, 1, L_max * hop) — ONE ``decode_clips`` pass, zeros past a clip's end; the plain ``decode`` when every L_b is the same — and
+    "audio_lengths" (B,) = L_b * hop: ``post.normalize_audio(r["generated_audio"], ..., lengths=r["audio_lengths"])`` and
+    ``post.save_wavs`` take it as it is.  ``return_relevance`` adds "relevance", "logprob_cond", "logprob_null" (B, K, L_max), zero past
+    L_b (no sequence means, as in ``generate_long``).  Equal durations without ``segments``: ``generate_long`` itself (what it
+    refuses included) plus the two lengths.
+    Refused before any device work: durations that are no per-clip sequence of length B, not finite, <= 0 or without a frame;
+    ``segments`` out of range; ``video_lengths`` (a chunk's video length follows from the clip's duration) and ``num_candidates``;
+    and ``frame_step`` != 1 for a batch that mixes single-chunk clips (d_b <= model_max_duration) with chunked ones — the two
+    branches of ``generate_long`` stride different dimensions, which one tensor cannot hold.
+    With ``cfg_scale`` > 1 or ``return_relevance`` the engine needs as many video tokens in a call as the null embedding holds, so
+    ``generate_long`` refuses a duration whose last chunk selects fewer segments than a full window.  Here every call is as wide as
+    a full window (``clip_chunk_plan``: "width"), and such a clip is served the way ``generate_tokens(video_lengths=...)`` serves a
+    clip with fewer video tokens than the batch: it has no scalar ``generate_long`` to be compared with under guidance; its scalar
+    counterpart is the one-duration loop over calls of the same width."""
+    from .clip_params import check_lengths
+    if video_lengths is not None:
+        raise _error("generate_long_clips takes no video_lengths: the video length of a chunk follows from the clip's duration "
+                     "(pass `segments` for videos of different lengths)")
+    if num_candidates is not None:
+        raise _error("generate_long_clips takes no num_candidates: best-of-N is a feature of one generate() call")
+    if not hasattr(frames, "shape") or len(frames.shape) < 2:
+        raise _error("frames must carry the clips on dim 0 and the segments on dim 1")
+    B, S = int(frames.shape[0]), int(frames.shape[1])
+    d = _clip_durations(durations, B)
+    seg = _clip_segments(segments, B, S)
+    check_lengths(B, use_sampling=use_sampling, temp=temp, top_k=top_k, top_p=top_p, cfg_scale=cfg_scale)
+    if model_max_duration is None:   # scripts/generate.py:221-226
+        model_max_duration = 2.56 if model.sampler.config.block_size > 64 else 0.64
+    single = [x <= model_max_duration for x in d]
+    if frame_step != 1 and any(single) and not all(single):
+        raise _error(f"frame_step = {frame_step} with a batch that mixes single-chunk clips (durations <= {model_max_duration} s) and "
+                     "chunked ones: generate_long strides another dimension in each branch, and one tensor cannot hold both — call "
+                     "the two groups separately")
+    kw = dict(stride=stride, model_max_duration=model_max_duration, vfps=vfps)
+    sample_kw = dict(clip_indices=clip_indices, use_sampling=use_sampling, temp=temp, top_k=top_k, top_p=top_p, cfg_scale=cfg_scale)
+    if segments is None and len(set(d)) == 1:          # one duration after all: the scalar call, plus the lengths
+        r = generate_long(model, frames, d[0], frame_step=frame_step, return_relevance=return_relevance, **kw, **sample_kw)
+        L_b = int(r["sampled_indices"].shape[-1])
+        r["lengths"] = torch.full((B,), L_b, dtype=torch.int64, device=r["sampled_indices"].device)
+        r["audio_lengths"] = r["lengths"] * (int(r["generated_audio"].shape[-1]) // L_b)
+        return r
+    plan = clip_chunk_plan(d, seg, S, **kw)
+    dev = frames.device
+    K, special, stride_tokens = model.num_codebooks, model.special_token_id, plan["stride_tokens"]
+    lengths = [cl["length"] for cl in plan["clips"]]
+    L_max = max(lengths)
+    tokens = None
+    rel = {}
+    rows = torch.arange(B, device=dev)[:, None]
+    gen_kw = dict(sample_kw, return_sampled_indices=True, remove_prompts=False, prompt_is_encoded=True,
+                  **(dict(return_relevance=True) if return_relevance else {}))
+    prompt = None
+    for c, ch in enumerate(plan["chunks"]):
+        idx = torch.tensor([i + [i[-1]] * (ch["width"] - len(i)) for i in ch["indices"]], device=dev)
+        selected = frames[rows, idx]                        # (B, width, ...): clip b's own segments, its last one repeated behind them
+        if frame_step != 1:                                 # in the branch the clips' schedules take (:309-324 / :336-341)
+            selected = selected[:, :, ::frame_step, ...] if all(single) else selected[:, :, :, ::frame_step, ...]
+        out = model.generate_tokens(frames=selected, audio=prompt, max_new_tokens=ch["T"], video_segments=ch["n_segments"], **gen_kw)
+        tok, P = out["tokens"], ch["prompt_len"]
+        if tokens is None:
+            tokens = torch.full((B, tok.shape[1], L_max), special, dtype=tok.dtype, device=tok.device)
+            rel = {k: torch.zeros(B, tok.shape[1], L_max, dtype=out[k].dtype, device=tok.device) for k in REL} if return_relevance else {}
+        for b in range(B):                                  # every frame from the chunk that GENERATED it
+            if not ch["parked"][b]:
+                off, T_b = c * stride_tokens, ch["T"][b]
+                tokens[b, :, off + P:off + T_b] = tok[b, :, P:T_b]
+                for k in rel:
+                    rel[k][b, :, off + P:off + T_b] = out[k][b, :, P:T_b]
+        if c + 1 < len(plan["chunks"]):
+            # the next prompt: a continuing clip's tokens from stride_tokens on (its chunk was full); a clip that is — or will be — parked
+            # carries the last frames it holds (zeros in front of a track shorter than the prompt): valid ids, and nothing reads the result
+            P_next = plan["chunks"][c + 1]["prompt_len"]
+            prompt = torch.zeros(B, tok.shape[1], P_next, dtype=tok.dtype, device=tok.device)
+            for b in range(B):
+                T_b = ch["T"][b]
+                n = min(T_b, P_next)
+                prompt[b, :, P_next - n:] = tok[b, :, T_b - n:T_b]
+    if len(set(lengths)) == 1:
+        audio = model.audio_encoder.decode([(tokens[..., :K, :], None)])
+    else:
+        audio = model.audio_encoder.decode_clips(tokens[..., :K, :], lengths)
+    lens = torch.tensor(lengths, dtype=torch.int64, device=tokens.device)
+    return {"generated_audio": audio, "sampled_indices": tokens, "lengths": lens,
+            "audio_lengths": lens * (int(audio.shape[-1]) // L_max), **rel}

@@ -263,7 +263,7 @@ class VAURAModel(nn.Module):
                         temp: float = 1.0, top_k: int = 256, top_p: float = 0.0, remove_prompts: bool = False,
                         prompt_is_encoded: bool = False, cfg_scale: float = 1.0, return_logprobs: bool = False,
                         num_candidates: int = 1, return_all_candidates: bool = False, return_relevance: bool = False,
-                        rank_by: str = "logprob", video_lengths=None):
+                        rank_by: str = "logprob", video_lengths=None, video_segments=None):
         """generate() up to and including revert_pattern_sequence (vaura_model.py:410-572): (B, K, T') int64 tokens on
         the device, no codec decode.  The sliding-window caller (vaura_amd.longform) uses this for every chunk and
         decodes the concatenated tokens once, as the reference's script does (scripts/generate.py:366-369).
@@ -298,7 +298,11 @@ class VAURAModel(nn.Module):
         means taken over the clip's own frames.  With ``noise_mode="philox"`` or greedy decoding, clip b's frames [0, T_b) — tokens and
         every reported value — are the bits of the same call with ``max_new_tokens=T_b`` (and the features cut to Tv_b): one batched
         call serves clips of different lengths.  ``noise_mode="torch_cpu"`` works but is not comparable (its draws are consumed per step
-        of the call).  A common prompt must be shorter than every T_b."""
+        of the call).  A common prompt must be shorter than every T_b.
+        ``video_segments``: ``video_lengths`` counted in segments of ``frames`` (dim 1) instead of video tokens — one int per clip,
+        1 <= n_b <= S, the leading segments of clip b that are real.  How many tokens a segment gives is known only once the extractor
+        has run, so it is turned into ``video_lengths`` = n_b * (Tv // S) from the features' own shape.  It needs the flattened AVCLIP
+        layout (``flatten_vis_feats``) and excludes ``video_lengths``; a call without it takes the path it always took."""
         assert not self.training, "do not use generation in training mode"
         N = self._check_candidates(num_candidates, return_all_candidates, use_sampling, temp, rank_by, return_relevance)   # refused before any device work
         # per-clip parameter sequences of the wrong length: refused here, before any device work (frames carry the batch on dim 0)
@@ -308,7 +312,12 @@ class VAURAModel(nn.Module):
         t_max, lengths, tv_lengths = clip_params.resolve_lengths(
             frames.shape[0] if hasattr(frames, "shape") else None, max_new_tokens, video_lengths, None,
             int(audio.shape[-1]) if (audio is not None and prompt_is_encoded) else 0)
-        ragged = lengths is not None or tv_lengths is not None
+        n_segments = None
+        if video_segments is not None:       # refused here, before any device work
+            n_segments = clip_params.resolve_segments(frames.shape[0] if hasattr(frames, "shape") else None, video_segments, video_lengths,
+                                                      frames.shape[1] if hasattr(frames, "shape") and len(frames.shape) > 1 else None,
+                                                      self.flatten_vis_feats, lengths)
+        ragged = lengths is not None or tv_lengths is not None or n_segments is not None
         max_new_tokens = t_max               # the call runs to the longest clip
         if return_attention_weights:
             # the reference's own llama sampler returns (logits, None, None) (llama.py:520-539), so its generate() fails on
@@ -334,6 +343,10 @@ class VAURAModel(nn.Module):
         B = vis.shape[0]
         Tp = 0 if audio is None else int(audio.shape[-1])
         assert lengths is not None or Tp < max_new_tokens, "gt audio prompt can not be longer than max_new_tokens"
+        if n_segments is not None:           # segments -> video tokens, from the features' own shape
+            if int(vis.shape[1]) % int(frames.shape[1]):
+                raise L.VauraHipError(f"video_segments: {int(vis.shape[1])} video tokens are no multiple of the {int(frames.shape[1])} segments")
+            tv_lengths = [n * (int(vis.shape[1]) // int(frames.shape[1])) for n in n_segments]
         if ragged:                           # again with the batch, the video tokens and the prompt known: still before the engine is touched
             _, lengths, tv_lengths = clip_params.resolve_lengths(B, lengths if lengths is not None else t_max, tv_lengths, int(vis.shape[1]), Tp)
         use_cfg = clip_params.any_cfg(cfg_scale) and self.sampler.__class__.__name__ == "Transformer"   # any clip's scale > 1
