@@ -846,6 +846,37 @@ int vaura_video_preprocess(const uint8_t* video, int channels_last, int n_clips,
 /* dynamic LDS bytes of one workgroup for these table sizes (0 for sizes the kernel does not take) */
 size_t vaura_video_preprocess_lds_bytes(int channels_last, int crop_w, int h_taps, int span, int tile_src_rows);
 
+/* -------------------------------------------------------------------------------------------
+ * Audio preprocessing (csrc/audio_pre.hip): decoded PCM -> the codec's padded mono input.  The `audio_transforms_test` list of
+ * configs/generate_vas.yaml:43-54 (AudioStereoToMono -> AudioResample(44100) -> AudioTrim; models/data/transforms/
+ * audio_transforms.py:162-192, the resampler being torchaudio.transforms.Resample at its defaults) in one launch.  One source rate,
+ * one channel count and one sample format per call; per-clip sample counts.
+ *   pcm       B clips of C channels: planar (B, C, in_stride) or, interleaved != 0, (B, in_stride, C) as a decoder hands it over;
+ *             format VAURA_PCM_S16 (x / 32768), VAURA_PCM_S32 (x / 2147483648) or VAURA_PCM_F32 (as is); aligned to its element
+ *   n_in      device, (B) int32: the real samples of clip b (held to 0 .. in_stride); nothing at or behind them is read
+ *   o, n, w   orig / gcd, new / gcd and the half width ceil(6 o / (0.99 min(o, n))) of the full form's 2 w + o taps per phase
+ *   table     built by the host once per rate pair (vaura_amd/audio_preprocess.py: resample_table): for phase p the taps
+ *             taps[j * phases + p], j < taps_per_phase (fp32, tap-major), are taps first[p] .. of the full form, the run outside of
+ *             which every fp32 tap is exactly 0; phases == n.  o == n is the identity (the mono signal): the table is not read
+ *             and may be NULL.
+ *   out       fp32 (B, out_stride): clip b's n_out[b] samples (device int32, held to 0 .. out_stride; the host has applied the
+ *             trim), 0 from there to the row's end.  Nothing outside the B rows is written.
+ * Arithmetic, all fp32: channels added in channel order, divided by C; output m = q n + p is the sum over the taps, in tap order,
+ * of tap * x[q o + first[p] + j - w], x = 0 outside [0, n_in[b]).
+ * VAURA_ERR_ARG: a NULL or misaligned pointer, a size below 1, phases != n.  VAURA_ERR_DTYPE: an unknown format.  VAURA_ERR_SHAPE, before any
+ * launch: C > 8; more than VAURA_AUDIO_PRE_MAX_TAPS (64) taps per phase; more than 2^20 table entries; a row of more than
+ * 2^31 - 1 samples; more than 65535 clips; a tile whose input span does not fit 64 KiB of LDS (vaura_audio_preprocess_lds_bytes).   */
+#define VAURA_AUDIO_PRE_TILE 1024
+#define VAURA_AUDIO_PRE_MAX_TAPS 64
+enum { VAURA_PCM_S16 = 0, VAURA_PCM_S32 = 1, VAURA_PCM_F32 = 2 };
+int vaura_audio_preprocess(const void* pcm, int format, int interleaved, int B, int C, int64_t in_stride, const int32_t* n_in, int o, int n,
+                           int w, const int32_t* first, const float* taps, int phases, int taps_per_phase, float* out, int64_t out_stride,
+                           const int32_t* n_out, vaura_stream_t s);
+/* dynamic LDS bytes of one workgroup: the mono input span of one tile (0 for sizes the kernel does not take) */
+size_t vaura_audio_preprocess_lds_bytes(int o, int n, int w, int taps_per_phase);
+/* output samples per workgroup (VAURA_AUDIO_PRE_TILE as the library was compiled) */
+int vaura_audio_preprocess_tile(void);
+
 /* Measurement aid (tools/pmc_driver, A/B timing): selects kernel variants for launches enqueued (or graphs captured) afterwards.
  * bit 0: wo / w2 GEMVs as one workgroup per column tile instead of the row-split pair; bit 4: prefill attention as one workgroup
  * per position instead of the MFMA kernel (tools/README.md lists every bit).

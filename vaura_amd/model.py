@@ -215,6 +215,29 @@ class VAURAModel(nn.Module):
         pre.device = self.device
         return pre(video)
 
+    def audio_from_pcm(self, pcm, sample_rate: int, *, lengths=None, audio_transforms=None, duration: Optional[float] = None,
+                       interleaved: bool = False):
+        """Decoded PCM -> what ``forward`` / ``score_relevance`` / ``test_step`` batches / ``generate(audio=...)`` take: ``(audio (B, 1,
+        N) fp32 mono at the codec's rate on the sampler's device, audio_lengths)``.  ``pcm``: int16, int32 or float32, (B, C, N) or
+        (C, N) (``interleaved``: (B, N, C) / (N, C)) at ``sample_rate``; ``lengths``: the real samples of each row (None: whole rows —
+        ``audio_lengths`` is then None too, every clip has N samples).  ``audio_transforms``: the ``audio_transforms_test`` list of
+        configs/generate_vas.yaml:43-54 (AudioStereoToMono -> AudioResample -> AudioTrim); None = resample to the codec's rate, trim
+        to ``duration`` seconds when given.  The preprocessor (tap tables, device copies) is built once per distinct configuration."""
+        from .audio_preprocess import AudioPreprocessor
+        key = (repr(_plain(audio_transforms)) if audio_transforms is not None else None, duration)
+        cache = self.__dict__.setdefault("_audio_preprocessors", {})
+        if key not in cache:
+            if audio_transforms is None:
+                cache[key] = AudioPreprocessor(target_sr=int(getattr(self.audio_encoder, "model_sr", 44100)), duration=duration)
+            else:
+                cache[key] = AudioPreprocessor.from_transforms_config(_plain(audio_transforms))
+                if duration is not None:                                 # the call's own duration wins over the list's AudioTrim
+                    cache[key].duration = float(duration)
+        pre = cache[key]
+        pre.device = self.device
+        audio, out_lengths = pre(pcm, sample_rate=sample_rate, lengths=lengths, interleaved=interleaved)
+        return audio, (None if lengths is None else out_lengths)
+
     def _pattern_delays(self, timesteps: int) -> List[int]:
         """The codebook delays of ``pattern_provider.get_pattern(timesteps)`` — the only layouts the decode loop implements
         (codebook_patterns.py:374-419: DelayedPatternProvider, ParallelPatternProvider).  Anything else — a pattern object without
