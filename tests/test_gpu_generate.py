@@ -1282,15 +1282,14 @@ def test_heavy_tailed_checkpoint_rows_against_live_oracle(wdtype):
 @pytest.mark.parametrize("wdtype", ["h2", "h1", "fp8", "fp8h"])
 def test_one_launch_mlp_is_bit_identical_to_two_launches(wdtype, clips):
     """csrc/mlp_engine.h, the default where eligible: the MLP of a layer (w1||w3 + SwiGLU -> w2 + residual) as ONE launch with an
-    in-launch hand-off, w2's weights requested ahead of it (debug flag bit 2: every GEMV its own launch; bit 3: the experimental
-    three-phase launch that takes wo in as well).  Same products in the same order as the separate launches: teacher-forced
+    in-launch hand-off, w2's weights requested ahead of it (debug flag bit 2: every GEMV its own launch; bit 1: the next layer's
+    qkv stays its own launch).  Same products in the same order as the separate launches: teacher-forced
     logits must be BIT-identical, tokens (greedy + CFG, and Philox-sampled) identical, through the eager path and through the
     captured step graph, and no consumer may have given up waiting (status word clean).  6 clips x cfg = 12 decoder rows (both row
     halves live) and 3 clips = 6 rows (configs[3]'s regime: one live half; the separate launches then use one workgroup per tile, the
     one-launch form keeps its (tile, row half) workgroups and the second half multiplies zeros).  Round 5: 16 clips x cfg = 32 rows (the
     reference's default batch, configs/generate_vgg.yaml:41) and 10 clips = 20 rows (second row block ragged): the two-row-block
-    instances (mlp_engine_kernel<.., RBK = 2>) against the separate two-row-block launches; the attention + wo and tail experiments
-    do not exist there (the flags then select the default).  fp8 tile pairs (configs[4]) take the one-launch form with 17..32 rows only
+    instances (mlp_engine_kernel<.., RBK = 2>) against the separate two-row-block launches.  fp8 tile pairs (configs[4]) take the one-launch form with 17..32 rows only
     (its qkv phase on four waves of six k-groups, like the separate fp8 K-split kernel): 16 and 10 clips test it, 6 and 3 are the
     separate launches either way."""
     from vaura_amd import _lib as L
@@ -1303,8 +1302,8 @@ def test_one_launch_mlp_is_bit_identical_to_two_launches(wdtype, clips):
     out = {}
     try:
         # the default (w1||w3 -> w2 -> next layer's qkv in one launch) | qkv separate | every GEMV and the attention their own launches.
-        # (The three measured-negative engines — attention + wo, the layer tail, the attention as a fourth phase — left the product
-        # library in round 6: experiment builds only, `tools/experiment.sh engines`; their bit-identity records are in DESIGN_HISTORY.md.)
+        # (The three measured-negative engines — attention + wo, the layer tail, the attention as a fourth phase — are no longer
+        # in the tree; their bit-identity records are in DESIGN_HISTORY.md.)
         for flags in (0, 0x2, 4):
             f1, f2 = flags if isinstance(flags, tuple) else (flags, 0)
             L.lib().vaura_set_debug_flags(f1)

@@ -1,25 +1,23 @@
 #!/usr/bin/env python
-"""Timeline of the one-launch MLP / layer-tail kernels (csrc/mlp_engine.h) from the diagnostic build's in-kernel stamps
+"""Timeline of the one-launch MLP (mlp_engine_kernel, csrc/mlp_engine.h) from the diagnostic build's in-kernel stamps
 (tools/pmc_driver <libvaura_hip_stamps.so> --stamps out.bin with PMC_STAMP_ALL_WAVES=1): per stamp, when the first / median /
 last WAVE of the launch reached it, relative to the launch's first wave start (us; medians over launches), wave 0 and waves 1..7
 separately.
 
-    python tools/engine_stamps.py gpurun_out/r04/stamps_mlp_h2.bin [kind]      kind 11 = mlp_engine_kernel, 12 = tail_engine_kernel
+    python tools/engine_stamps.py stamps_mlp_h2.bin [kind]      kind 11 = mlp_engine_kernel
 """
 import sys
 
 import numpy as np
 
 NAMES = {11: ["start", "p1 requested", "p1 products done", "w0: published | w1-7: w2 requested", "hand-off passed", "weights+planes landed",
-              "done", "flushed"],
-         12: ["start", "p0 products done", "w0: p0 published", "hand-off 0 passed", "p1 products done", "w0: p1 published",
-              "hand-off 1 passed", "done"]}
+              "done", "flushed"]}
 
 
 def main():
     rec = np.fromfile(sys.argv[1], dtype=np.uint64).reshape(-1, 16)
     kind = (rec[:, 0] & np.uint64(0xFF)).astype(np.int64)
-    want = int(sys.argv[2]) if len(sys.argv) > 2 else (11 if (kind == 11).any() else 12)
+    want = int(sys.argv[2]) if len(sys.argv) > 2 else 11
     blk = ((rec[:, 0] >> np.uint64(8)) & np.uint64(0xFFFFFFFF)).astype(np.int64)
     wave = ((rec[:, 0] >> np.uint64(48)) & np.uint64(0xFF)).astype(np.int64)
     t = rec[:, 1:9].astype(np.int64)

@@ -48,7 +48,7 @@ def stage_of(name):
             return "w13"
         if epi == 4:
             return "heads"
-    m = re.match(r"mlp_engine_kernel<(\d+), (true|false)", name)   # <WT, QKV, RBK, ATT>: w1||w3 -> w2 (-> next layer's qkv) in one launch
+    m = re.match(r"mlp_engine_kernel<(\d+), (true|false)", name)   # <WT, QKV, RBK, false>: w1||w3 -> w2 (-> next layer's qkv) in one launch
     if m:
         return "mlp" if m.group(2) == "true" else "mlp_last"
     m = re.match(r"gemv3h_kernel<(\d+), ", name)      # row-split pair kernels: G2 = k-group pairs per wave

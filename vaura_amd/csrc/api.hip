@@ -178,7 +178,7 @@ static VaSampleLaunch sample_launch(const vaura_decoder* d, const vaura_sampling
 // pair path (H1 / H2 / FP8 storage): activations travel as (hi, lo) fp16 planes, products on the fp16 MFMA
 static int enqueue_step_bf16(const vaura_decoder* d, const vaura_sampling* sp, int sample, hipStream_t s) {
   const vaura_dims& m = d->dims;
-  const int D = m.d_model, F = m.ffn_dim, H = m.n_head;
+  const int D = m.d_model, F = m.ffn_dim;
   const int rows = d->rows;
   if (!d->ws_h_split || !d->ws_attn_split || !d->ws_ffn_split || !d->ws_ss) return VAURA_ERR_ARG;
   PROF_B(VAURA_K_EMBED);
@@ -193,19 +193,6 @@ static int enqueue_step_bf16(const vaura_decoder* d, const vaura_sampling* sp, i
   // ... and the NEXT layer's qkv GEMV as a third phase of that launch
   const bool fuse_qkv = mlp_engine && qkv2 && !(va_debug_flags_get() & 0x2u);   // debug flag bit 1: qkv stays its own launch
   bool qkv_done = false;                     // layer l's qkv partials were written by layer l - 1's engine launch
-  // EXPERIMENT builds only (-DVAURA_EXPERIMENT_ENGINES; DESIGN_HISTORY.md rounds 4-5, all bit-identical and measured slower or no
-  // faster): debug flag bit 12 = attention + wo as one launch, bit 3 = the whole layer tail as one launch, second flag word bit 2 = the
-  // next layer's attention as a fourth phase of the one-launch MLP.  The product library compiles none of them.
-#ifdef VAURA_EXPERIMENT_ENGINES
-  const bool attn_wo = mlp_engine && rows <= 16 && H == 16 && d->max_len <= 256 && (va_debug_flags_get() & 0x1000u) && !(va_debug_flags_get() & 8u) &&
-                       d->plane_shift == 0;   // the experiments' own attention epilogues store unscaled planes
-  const bool fuse_attn = fuse_qkv && rows <= 16 && H == 16 && D / H == 96 && d->max_len <= 256 && d->ws_attn_split && !attn_wo && d->plane_shift == 0 &&
-                         !(va_debug_flags_get() & 8u) && (va_debug_flags2_get() & 4u);
-  const bool tail_engine = mlp_engine && rows <= 16 && (va_debug_flags_get() & 8u);
-#else
-  constexpr bool attn_wo = false, fuse_attn = false;
-#endif
-  bool attn_done = false;                    // layer l's attention was computed by layer l - 1's engine launch
   for (int l = 0; l < m.n_layer; ++l) {
     const vaura_layer_weights& L = d->layers_host[l];
     const float* next_attn_gain = (l + 1 < m.n_layer) ? d->layers_host[l + 1].attn_norm : d->final_norm;
@@ -218,49 +205,20 @@ static int enqueue_step_bf16(const vaura_decoder* d, const vaura_sampling* sp, i
       if (rc) return rc;
     }
     qkv_done = false;
-#ifdef VAURA_EXPERIMENT_ENGINES
-    const Gemv3Args awo0 = g3(L.wo, d->ws_attn_split, nullptr, d->ws_h, d->ws_h, d->ws_h_split, L.ffn_norm, d->ws_ss, d, D);
-#endif
-    if (attn_done) {
-      attn_done = false;                     // (computed by the previous layer's one-launch MLP)
-#ifdef VAURA_EXPERIMENT_ENGINES
-    } else if (attn_wo) {
-      PROF_B(VAURA_K_ATTN);
-      rc = va_launch_attn_wo(d->ws_qkv, qkv2, d->rope, va_kv_cache(d, l), d->ws_attn, d->ws_attn_split, rows, H, d->state, awo0,
-                             d->ws_sync + 512, l, s);
-      PROF_A(VAURA_K_ATTN);
-      if (rc) return rc;
-#endif
-    } else {
     PROF_B(VAURA_K_ATTN);  // rope + cache append + softmax(qK^T)V                     llama.py:234-257
     VaAttentionStep at = attention_step(d, l);
     at.qkv2 = qkv2; at.out_split = d->ws_attn_split;
-    // words 512 .. 767: arrival counts of the range-split attention (the MLP / tail engines use 0 .. 511; the attention + wo experiment
-    // uses 512 .. only with caches <= 256, where nothing is split)
+    // words 512 .. 767: arrival counts of the range-split attention (the one-launch MLP uses 0 .. 511)
     at.arrivals = d->ws_sync ? d->ws_sync + 512 : nullptr;
     at.pscale = ldexpf(1.f, -d->plane_shift);
     rc = va_launch_attention(at, s);
     PROF_A(VAURA_K_ATTN);
     if (rc) return rc;
-    }
     const Gemv3Args awo = g3(L.wo, d->ws_attn_split, nullptr, d->ws_h, d->ws_h, d->ws_h_split, L.ffn_norm, d->ws_ss, d, D);
-#ifdef VAURA_EXPERIMENT_ENGINES
-    if (tail_engine) {
-      PROF_B(VAURA_K_W13);
-      rc = va_launch_tail_engine(awo, g3(L.w13, d->ws_h_split, d->ws_ss, nullptr, nullptr, d->ws_ffn_split, nullptr, nullptr, d, F),
-                                 g3(L.w2, d->ws_ffn_split, nullptr, d->ws_h, d->ws_h, d->ws_h_split, next_attn_gain, d->ws_ss, d, D),
-                                 d->ws_sync, d->state, l, s);
-      PROF_A(VAURA_K_W13);
-      if (rc) return rc;
-      continue;
-    }
-#endif
-    if (!attn_wo) {
-      PROF_B(VAURA_K_WO);    // h += Wo.attn ; emit split(h * ffn_norm) + ss               llama.py:259, 279
-      rc = va_launch_gemv3(awo, D, D, E3_RESID, false, s);
-      PROF_A(VAURA_K_WO);
-      if (rc) return rc;
-    }
+    PROF_B(VAURA_K_WO);    // h += Wo.attn ; emit split(h * ffn_norm) + ss               llama.py:259, 279
+    rc = va_launch_gemv3(awo, D, D, E3_RESID, false, s);
+    PROF_A(VAURA_K_WO);
+    if (rc) return rc;
     const Gemv3Args a13 = g3(L.w13, d->ws_h_split, d->ws_ss, nullptr, nullptr, d->ws_ffn_split, nullptr, nullptr, d, F);
     const Gemv3Args a2 = g3(L.w2, d->ws_ffn_split, nullptr, d->ws_h, d->ws_h, d->ws_h_split, next_attn_gain, d->ws_ss, d, D);
     if (mlp_engine) {
@@ -272,20 +230,11 @@ static int enqueue_step_bf16(const vaura_decoder* d, const vaura_sampling* sp, i
         aqn = g3(d->layers_host[l + 1].wqkv, d->ws_h_split, d->ws_ss, nullptr, d->ws_qkv, nullptr, nullptr, nullptr, d, 3 * D);
         aqn.out2 = qkv2;
       }
-      VaEngineAttention att;
-      const bool with_attn = with_qkv && fuse_attn;
-      if (with_attn)
-        att = VaEngineAttention{d->rope, va_kv_cache(d, l + 1), d->ws_attn, d->ws_attn_split, H};
       PROF_B(VAURA_K_W13);
-      // what the idle workgroups of this launch may warm in the Infinity Cache: the NEXT layer's w1||w3 (its first consumer)
-      const void* warm = l + 1 < m.n_layer ? d->layers_host[l + 1].w13 : nullptr;
-      const size_t warm_bytes = (size_t)2 * F * D * (d->wdtype == VAURA_W_H2 ? 4 : (va_is_fp8(d->wdtype) ? 1 : 2));
-      rc = va_launch_mlp_engine(a13, a2, with_qkv ? &aqn : nullptr, d->ws_sync, d->state, l, s, with_attn ? &att : nullptr, warm, warm_bytes,
-                                l + 1 < m.n_layer ? d->layers_host[l + 1].wo : nullptr, warm_bytes * D / (2 * F));
+      rc = va_launch_mlp_engine(a13, a2, with_qkv ? &aqn : nullptr, d->ws_sync, d->state, l, s);
       PROF_A(VAURA_K_W13);
       if (rc) return rc;
       qkv_done = with_qkv;
-      attn_done = with_attn;
       continue;
     }
     PROF_B(VAURA_K_W13);   // ffn = silu(W1 x) * (W3 x), x = rmsnorm(h)                  llama.py:282, 177

@@ -1035,11 +1035,6 @@ int va_launch_attention(const VaAttentionStep& a, hipStream_t s) {
   return 0;
 }
 
-#ifdef VAURA_EXPERIMENT_ENGINES
-// measured-negative engine (attention + wo as one launch; DESIGN_HISTORY.md round 4): experiment builds only
-#include "experiments/attn_wo.h"
-#endif
-
 int va_launch_rope_append(const vaura_decoder* d, int layer, int p0, int n_pos, hipStream_t s) {
   const int H = d->dims.n_head;
   const VaKvCache kv = va_kv_cache(d, layer);

@@ -16,11 +16,8 @@ unsigned va_debug_flags_get() { return va_debug_flags; }
 
 // second flag word (vaura_set_debug_flags2), bit 0: more than one row block -> still ONE row block per weight pass (round 4's walk: the
 // A/B of the two-row-block instances and the control of their bit-identity test); bit 1: the one-launch MLP refuses 17..32 rows;
-// bit 2: EXPERIMENT, the next layer's attention as a fourth phase of the one-launch MLP (api.hip: measured slower);
 // bit 3: fp8 weights keep round 4's one-workgroup-per-tile kernels for wo / w2 (the A/B of the fp8 row-split instances);
-// bit 4: fp8 weights never take the one-launch MLP; bits 5, 6, 12..15: row f2's linear layers (vit.hip); bit 7 and bits 16..22: experiment
-// builds only (-DVAURA_EXPERIMENT_ENGINES: hand-off 1 of the one-launch MLP polled per wave; Infinity-Cache warm-up by its idle
-// workgroups — both measured negative in round 6)
+// bit 4: fp8 weights never take the one-launch MLP; bits 5, 6, 12..15: row f2's linear layers (vit.hip)
 unsigned va_debug_flags2 = 0;
 unsigned va_debug_flags2_get() { return va_debug_flags2; }
 static bool rb2(const Gemv3Args& a) { return a.R >= 2 && !(va_debug_flags2 & 1u); }
@@ -250,35 +247,19 @@ bool va_mlp_engine_eligible(const vaura_decoder* d) {
   return cus[dev] >= 256;
 }
 
-template <int WT, bool QKV, int RBK = 1, bool ATT = false>
+template <int WT, bool QKV, int RBK = 1>
 static int launch_mlp_engine_t(const MlpEngineArgs& e, hipStream_t s) {
   using SH = MlpEngineShape<WT, RBK>;
   static unsigned long long big = 0;
-  if (va_big_lds_once(reinterpret_cast<const void*>(mlp_engine_kernel<WT, QKV, RBK, ATT>), SH::LDS, &big)) return VAURA_ERR_STATE;
-  VA_LAUNCH((mlp_engine_kernel<WT, QKV, RBK, ATT>), dim3(256), dim3(MLPE_NW * 64), SH::LDS, s, e.p1.W, e.p1.XP, e.p2.W, e);
+  if (va_big_lds_once(reinterpret_cast<const void*>(mlp_engine_kernel<WT, QKV, RBK>), SH::LDS, &big)) return VAURA_ERR_STATE;
+  VA_LAUNCH((mlp_engine_kernel<WT, QKV, RBK>), dim3(256), dim3(MLPE_NW * 64), SH::LDS, s, e.p1.W, e.p1.XP, e.p2.W, e);
   return 0;
 }
 
 // aq != nullptr: the next layer's qkv GEMV (K-split, two partial outputs) as a third phase of the same launch
-// att != nullptr (with aq, one row block): the next layer's attention as a fourth phase (flags: 704 words)
 int va_launch_mlp_engine(const Gemv3Args& a13, const Gemv3Args& a2, const Gemv3Args* aq, uint32_t* flags, int32_t* state, int layer,
-                         hipStream_t s, const VaEngineAttention* att, const void* warm_ptr, size_t warm_bytes, const void* warm0_ptr,
-                         size_t warm0_bytes) {
+                         hipStream_t s) {
   MlpEngineArgs e;
-  // second flag word, bits 16..20: sixteenths (1..16) of `warm_bytes` the idle workgroups touch (0 = off); bit 21: start early
-  const unsigned six = (va_debug_flags2 >> 16) & 31u;
-  e.pf_ptr = static_cast<const unsigned char*>(warm_ptr);
-  e.pf_lines = (warm_ptr && six) ? (int)((warm_bytes / 128) * (six > 16 ? 16 : six) / 16) : 0;
-  e.pf_early = (int)((va_debug_flags2 >> 21) & 1u);
-  e.pf_ptr0 = static_cast<const unsigned char*>(warm0_ptr);                 // bit 22: the first region (the next layer's wo), whole
-  e.pf_lines0 = (warm0_ptr && (va_debug_flags2 & 0x400000u)) ? (int)(warm0_bytes / 128) : 0;
-  e.att_rope = nullptr; e.att_kc = e.att_vc = e.att_out = nullptr; e.att_outp = nullptr; e.att_max_len = 0;
-  if (att) {
-    if (!aq || a13.R != 1 || !att->rope || !att->kv.k || !att->kv.v || att->kv.dtype != 0 || !att->out || att->n_head != 16 || att->kv.max_len > 256 ||
-        att->kv.max_len < 1)
-      return VAURA_ERR_ARG;
-    e.att_rope = att->rope; e.att_kc = att->kv.k; e.att_vc = att->kv.v; e.att_out = att->out; e.att_outp = att->outp; e.att_max_len = att->kv.max_len;
-  }
   e.p1 = a13;
   e.p2 = a2;
   e.p3 = aq ? *aq : a2;
@@ -288,57 +269,21 @@ int va_launch_mlp_engine(const Gemv3Args& a13, const Gemv3Args& a2, const Gemv3A
     e.p3.wscale = weight_scales(*aq, 3 * 1536, 1536);
   }
   if (!a13.W || !a13.XP || !a2.W || !a2.XP || !flags || !state || a13.R < 1 || a13.R > 2 || a2.R != a13.R) return VAURA_ERR_ARG;
-  if (a13.wq != a2.wq || a13.wq < 0 || a13.wq > 3 || ((a13.wq == 1 || a13.wq == 3) && (a13.R != 2 || att)) || a13.N != 4096 || a2.N != 1536 || a13.k_total != 1536 ||
+  if (a13.wq != a2.wq || a13.wq < 0 || a13.wq > 3 || ((a13.wq == 1 || a13.wq == 3) && a13.R != 2) || a13.N != 4096 || a2.N != 1536 || a13.k_total != 1536 ||
       a13.n_ss_in != 96) return VAURA_ERR_SHAPE;
   e.p1.wscale = weight_scales(a13, 2 * 4096, 1536);
   e.p2.wscale = weight_scales(a2, 1536, 4096);
   e.flags = flags; e.state = state; e.state_rw = state; e.layer = layer;
   e.abl = (int)((va_debug_flags >> 28) & 15u);      // bits 28..31: timing ablations of the engine (tools only)
-  e.qlocal = (int)((va_debug_flags2 >> 23) & 1u);
-  e.pollwave = ((va_debug_flags2 >> 7) & 1u) && !(e.abl & 4);    // second flag word, bit 7 (experiment builds): hand-off 1 polled per wave
   if (a13.R == 2) {       // 17..32 decoder rows: both row blocks per weight fragment
     if (a13.wq == 1) return aq ? launch_mlp_engine_t<1, true, 2>(e, s) : launch_mlp_engine_t<1, false, 2>(e, s);
     if (a13.wq == 3) return aq ? launch_mlp_engine_t<3, true, 2>(e, s) : launch_mlp_engine_t<3, false, 2>(e, s);
     if (aq) return a13.wq == 2 ? launch_mlp_engine_t<2, true, 2>(e, s) : launch_mlp_engine_t<0, true, 2>(e, s);
     return a13.wq == 2 ? launch_mlp_engine_t<2, false, 2>(e, s) : launch_mlp_engine_t<0, false, 2>(e, s);
   }
-#ifdef VAURA_EXPERIMENT_ENGINES
-  if (att) return a13.wq == 2 ? launch_mlp_engine_t<2, true, 1, true>(e, s) : launch_mlp_engine_t<0, true, 1, true>(e, s);
-#else
-  if (att) return VAURA_ERR_STATE;       // the attention phase exists in experiment builds only (DESIGN_HISTORY.md round 5)
-#endif
   if (aq) return a13.wq == 2 ? launch_mlp_engine_t<2, true>(e, s) : launch_mlp_engine_t<0, true>(e, s);
   return a13.wq == 2 ? launch_mlp_engine_t<2, false>(e, s) : launch_mlp_engine_t<0, false>(e, s);
 }
-
-#ifdef VAURA_EXPERIMENT_ENGINES
-template <int WT>
-static int launch_tail_engine_t(const TailEngineArgs& e, hipStream_t s) {
-  using SH = MlpEngineShape<WT>;
-  static unsigned long long big = 0;
-  if (va_big_lds_once(reinterpret_cast<const void*>(tail_engine_kernel<WT>), SH::LDS, &big)) return VAURA_ERR_STATE;
-  VA_LAUNCH((tail_engine_kernel<WT>), dim3(256), dim3(MLPE_NW * 64), SH::LDS, s, e.p0.W, e.p0.XP, e.p1.W, e.p2.W, e);
-  return 0;
-}
-
-// wo -> w1||w3 -> w2 of one layer as ONE launch (tail_engine_kernel); flags: 512 words
-int va_launch_tail_engine(const Gemv3Args& awo, const Gemv3Args& a13, const Gemv3Args& a2, uint32_t* flags, int32_t* state, int layer,
-                          hipStream_t s) {
-  TailEngineArgs e;
-  e.p0 = awo; e.p1 = a13; e.p2 = a2;
-  if (!awo.W || !awo.XP || !a13.W || !a13.XP || !a2.W || !a2.XP || !flags || !state || awo.R != 1 || a13.R != 1 || a2.R != 1) return VAURA_ERR_ARG;
-  if (!awo.res || !awo.out || !awo.outp || !awo.gain_out || !awo.ss_out || !a2.out || !a2.outp || !a2.gain_out || !a2.ss_out || !a13.outp ||
-      !a13.ss_in) return VAURA_ERR_ARG;
-  if (awo.wq != a13.wq || a13.wq != a2.wq || (a13.wq != 0 && a13.wq != 2) || awo.N != 1536 || a13.N != 4096 || a2.N != 1536 ||
-      a13.k_total != 1536 || a13.n_ss_in != 96 || awo.out != a2.res || awo.outp != a13.XP || a13.outp != a2.XP) return VAURA_ERR_SHAPE;
-  e.p0.wscale = weight_scales(awo, 1536, 1536);
-  e.p1.wscale = weight_scales(a13, 2 * 4096, 1536);
-  e.p2.wscale = weight_scales(a2, 1536, 4096);
-  e.flags = flags; e.state = state; e.state_rw = state; e.layer = layer;
-  e.abl = (int)((va_debug_flags >> 28) & 15u);
-  return a13.wq == 2 ? launch_tail_engine_t<2>(e, s) : launch_tail_engine_t<0>(e, s);
-}
-#endif
 
 // ---------------------------------------------------------------------------- fp16-plane weight ingress
 // power-of-two row scale 2^E with amax / 2^E in [2^13, 2^14): both planes of a weight of ordinary size are normal fp16 numbers

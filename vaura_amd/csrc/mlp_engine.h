@@ -17,6 +17,28 @@
 #pragma once
 #include "gemv3_kernel.h"
 
+// Stamps (-DVAURA_STAMPS builds, common.h; record kind 11, read by tools/engine_stamps.py).  A record has too few slots for every point
+// of interest, so -DMLPE_STAMP_SET=0 / 1 / 2 chooses what slots 1, 2, 3 and 5 hold; slots 0, 4 and 6 are the same in every set:
+//   slot  set 0 (default)                       set 1 (phase 1's publish chain)            set 2 (the phase 2 -> 3 chain)
+//   0     wave start                            =                                          =
+//   1     phase 1: first batch requested        row-block waves: saw all phase-1 tiles     phase 2: products done, tiles in LDS
+//   2     phase 1: products done, tiles in LDS  =                                          row-block waves: saw all phase-2 tiles, stores issued
+//   3     wave 0: phase 1 published;            =                                          row-block waves: phase 2 published (drained + flag)
+//         waves 1..7: w2 slice requested
+//   4     hand-off 1 passed                     =                                          =
+//   5     phase 2: weights and planes landed    row-block waves: phase-1 stores issued     hand-off 2 passed
+//   6     done (epilogue stores acknowledged)   =                                          =
+// (row-block waves: wave 0, and wave 1 with two row blocks; in set 1 the other waves keep set 0's slot 1 and leave slot 5 empty; set 2
+//  belongs to the QKV instances: without a phase 3 its slots 1, 2, 3 and 5 stay empty.)
+#ifndef MLPE_STAMP_SET
+#define MLPE_STAMP_SET 0
+#endif
+#define MLPE_S0 1
+#define MLPE_S1 2
+#define MLPE_S2 4
+// a stamp that only the sets in `sets` (MLPE_S0 | ...) take; a stamp of every set is a plain VA_STAMP
+#define MLPE_STAMP(sets, st, i) do { if constexpr ((((sets) >> MLPE_STAMP_SET) & 1) != 0) VA_STAMP(st, i); } while (0)
+
 // Run-ahead throttle (round 4, second half).  A CU serves its vector-memory requests in order: the seven waves' run-ahead requests,
 // issued the moment their products are done, sit in front of wave 0's epilogue stores, and a hand-off passes only when the SLOWEST
 // producer has published (stamps: publish 5.3 us behind the products where the 64 workgroups without a run-ahead need 2.9).  Holding
@@ -24,47 +46,15 @@
 // Q2 quarters of their w2 slice (phase 2) / PRE3 of their three qkv k-groups (phase 3) at once and the rest when wave 0 has issued its
 // stores (an LDS word).  Measured on whole loops (tools/experiment.sh lib-ab, profiles/r04_ab_mlp_engine.txt): two planes best at
 // (2, 1): 211.3 -> 202.0 ms; one plane at (1, 2): 167.0 -> 161.6 ms; neighbours are 1-4 % worse, no hold at all is ablation bit 3.
-// -DMLPE_Q2 / -DMLPE_PRE3 override both storages (experiment builds).
-#ifndef MLPE_REL
-#define MLPE_REL 0        // 1: the held part is released behind the publish (drained stores + flag) instead of behind the stores' issue
-#endif
+// The same pair holds with two row blocks per pass.
+template <int WT> constexpr int mlpe_q2 = WT == 2 ? 2 : 1;                // Q2
+template <int WT> constexpr int mlpe_pre3u = 3 * (WT == 2 ? 1 : 2);       // PRE3 in ninths (k-group, tile) of the qkv slice
 template <typename F>
 __device__ __forceinline__ void va_static_for9(F&& f) {
   f(std::integral_constant<int, 0>{}); f(std::integral_constant<int, 1>{}); f(std::integral_constant<int, 2>{});
   f(std::integral_constant<int, 3>{}); f(std::integral_constant<int, 4>{}); f(std::integral_constant<int, 5>{});
   f(std::integral_constant<int, 6>{}); f(std::integral_constant<int, 7>{}); f(std::integral_constant<int, 8>{});
 }
-template <int WT, int RBK = 1>
-struct MlpeThrottle {
-#ifdef MLPE_Q2
-  static constexpr int Q2_1 = MLPE_Q2;
-#else
-  static constexpr int Q2_1 = WT == 2 ? 2 : 1;
-#endif
-#ifdef MLPE_PRE3
-  static constexpr int PRE3 = MLPE_PRE3;
-#else
-  static constexpr int PRE3 = WT == 2 ? 1 : 2;
-#endif
-#ifdef MLPE_PRE3U
-  static constexpr int PRE3U_1 = MLPE_PRE3U;      // the same in ninths (finer experiment builds)
-#else
-  static constexpr int PRE3U_1 = 3 * PRE3;
-#endif
-  // two row blocks per pass (RBK = 2): their own optimum (-DMLPE_Q2R / -DMLPE_PRE3UR in experiment builds)
-#ifdef MLPE_Q2R
-  static constexpr int Q2_2 = MLPE_Q2R;
-#else
-  static constexpr int Q2_2 = Q2_1;
-#endif
-#ifdef MLPE_PRE3UR
-  static constexpr int PRE3U_2 = MLPE_PRE3UR;
-#else
-  static constexpr int PRE3U_2 = PRE3U_1;
-#endif
-  static constexpr int Q2 = RBK == 2 ? Q2_2 : Q2_1;
-  static constexpr int PRE3U = RBK == 2 ? PRE3U_2 : PRE3U_1;
-};
 struct MlpEngineArgs {
   Gemv3Args p1;            // w1||w3: W, XP (h planes), ss_in, outp (ffn planes), N = ffn_dim, rows, R = 1, eps, k_total, wscale
   Gemv3Args p2;            // w2: W, XP (= p1.outp), res / out (h), outp (h planes), gain_out, ss_out, N = d_model, wscale
@@ -75,37 +65,15 @@ struct MlpEngineArgs {
   int layer;
   int abl;                 // timing ablations (tools only; 1 gives wrong results): 1 = no flag wait, 4 = no run-ahead (w2's weights requested
                            // behind the hand-off barrier)
-  int qlocal;              // experiment builds only (no effect, round 6): the qkv phase's work items of head h on XCD h % 8 + plain stores
-  int pollwave;            // experiment builds only (measured negative, round 6): 1 = every wave polls the 32 producers of its own K slice
-  // EXPERIMENT builds only (-DVAURA_EXPERIMENT_ENGINES; measured negative: the launch grows by 6.8 .. 10.7 us, profiles/r06_ab_mall_warm.txt).
-  // Infinity-Cache warm-up by the 64 workgroups that have no phase-2 / phase-3 duty (round 6): once the first hand-off has passed (the
-  // HBM pipe then runs far below its rate until the launch ends) they touch one dword per 128-byte line of pf_lines lines of what a
-  // LATER launch will stream — the next layer's w1||w3 — so that stream is served from the 256 MiB memory-side cache instead of HBM.
-  const unsigned char* pf_ptr;
-  int pf_lines;            // 0 = off
-  const unsigned char* pf_ptr0;      // a first region touched before it (the next layer's wo)
-  int pf_lines0;
-  int pf_early;            // 1: start right behind the workgroup's own publish instead of behind the first hand-off
-  // ATT instances (round 5): the NEXT layer's attention as a fourth phase — K / V cache of that layer (this (row, head)'s rows are
-  // requested while the qkv phase still runs), rope table, outputs (fp32 packed rows + planes for wo); flags + 512 .. 703: qkv producers
-  const float* att_rope;
-  float* att_kc;           // (rows, n_head, max_len, 96) of layer + 1
-  float* att_vc;
-  float* att_out;
-  uint16_t* att_outp;
-  int att_max_len;
+  // Where the fields of the removed experiments were (nothing writes or reads them).  Dropping the 88 bytes changes no instruction of the
+  // product build, but the hidden kernel arguments follow the struct and -DVAURA_STAMPS builds load one of them at a fixed offset: that
+  // immediate would move, so the size stays until a change that re-records those builds (profiles/mlp_engine_cleanup_device_code.txt).
+  uint64_t reserved[11];
 };
+static_assert(sizeof(MlpEngineArgs) == 480, "the kernel-argument layout of mlp_engine_kernel");
 
 #define MLPE_NW 8
 #define MLPE_SPIN_LIMIT 20000
-// TIMING-ONLY ablation (experiment builds: -DMLPE_ABL_X8, WRONG RESULTS): the activation planes fetched 8 bytes per lane instead of 16 — what an
-// fp8 activation format would move — to price that format before building it (round 6)
-#ifdef MLPE_ABL_X8
-#define MLPE_XLOAD(rs, voff, soff, aux) [&] { const auto v2_ = __builtin_amdgcn_raw_buffer_load_b64(rs, voff, soff, aux); return u32x4{v2_[0], v2_[1], 0x3c003c00u, 0x3c003c00u}; }()
-#else
-#define MLPE_XLOAD(rs, voff, soff, aux) __builtin_amdgcn_raw_buffer_load_b128(rs, voff, soff, aux)
-#endif
-
 // RBK = row blocks per weight pass (round 5; gemv3_kernel.h): 2 for 17..32 decoder rows.  The reduction tiles double (48 KB), so the
 // ring gives up a quarter (12 KB per wave) and one more k-group pair per plane travels in registers.
 template <int WT, int RBK = 1>
@@ -168,21 +136,14 @@ __device__ __forceinline__ uint32_t mlpe_ld_sc1(const uint32_t* p) {
 // set, the planes of both requested together); wave r finishes row block r of a phase (waves 3 r .. 3 r + 2 in the qkv phase) and wave
 // 0 publishes once wave 1 has drained its stores too (an LDS word).  Per row block the same products in the same order as the separate
 // two-row-block launches (gemv3_kernel / gemv3h_kernel RBK = 2): bit-identical to them.
-// ATT (QKV instances, one row block, 16 heads, cache <= 256 positions: the headline shape): the NEXT layer's attention as a FOURTH
-// phase.  All 256 workgroups stay; workgroup b is (head b & 15, row b >> 4) of attention_step256_kernel's grid and runs its arithmetic
-// (csrc/attention.hip attention256_body: same sums in the same order -> bit-identical).  What the fusion buys over the separate launch:
-// the cached K / V rows of that (row, head) depend on nothing this launch computes, so they are requested as soon as a wave's qkv
-// products are issued (workgroups 192..255, which have no w2 / qkv tile: right after phase 1) and stream under the qkv epilogue and its
-// hand-off — and the kernel boundary in front of the attention (~2.7 us of ramp + the dispatch gap) is gone.  The hand-off itself is
-// small: (row, head) needs the q, k and v quads of ITS head = 18 column tiles = 12 of the 192 qkv producers (three aligned groups of
-// four flags), not all of them.
-template <int WT, bool QKV, int RBK = 1, bool ATT = false>
+// The unnamed fourth parameter keeps the kernels' symbols (mlp_engine_kernel<2, true, 1, false>) as the committed profiles spell them.
+template <int WT, bool QKV, int RBK = 1, bool = false>
 __global__ __launch_bounds__(MLPE_NW * 64) void mlp_engine_kernel(const void* __restrict__ W13q, const uint16_t* __restrict__ XPq,
                                                                   const void* __restrict__ W2q, MlpEngineArgs e) {
   using SH = MlpEngineShape<WT, RBK>;
   constexpr bool F32 = WTag<WT>::F32, FP8 = WTag<WT>::FP8;
   constexpr int XPL = WTag<WT>::XPL;
-  static_assert(!FP8 || (RBK == 2 && !ATT), "fp8 tile pairs: the two-row-block instances only (configs[4]'s shape)");
+  static_assert(!FP8 || RBK == 2, "fp8 tile pairs: the two-row-block instances only (configs[4]'s shape)");
   constexpr int WH = SH::WH, NW = MLPE_NW, NACC = 2;
   extern __shared__ __attribute__((aligned(16))) unsigned char mlpe_lds[];
   unsigned char* ring = mlpe_lds;
@@ -207,176 +168,6 @@ __global__ __launch_bounds__(MLPE_NW * 64) void mlp_engine_kernel(const void* __
   f32x4 ws1[2] = {f32x4{1.f, 1.f, 1.f, 1.f}, f32x4{1.f, 1.f, 1.f, 1.f}}, ws2 = f32x4{1.f, 1.f, 1.f, 1.f};
   // LDS words of the two-row-block instances: arrive[18] / arrive[19] <- wave 1 has drained its phase-1 / phase-2 epilogue stores
   const bool epw = wid < RBK;                  // this wave finishes a row block (wave r: row block r) in phases 1 and 2
-  static_assert(!ATT || (QKV && RBK == 1), "the attention phase follows the qkv phase of a one-row-block launch");
-
-  // ---- attention phase (ATT): the cached K / V rows of this workgroup's (row, head), 8 lanes per position, 64 positions per pass,
-  //      up to four passes (cache <= 256); requested by att_request() wherever the wave has registers and nothing left to request
-  constexpr int AQ = 3;                        // 16-byte quads of a 96-wide row per lane (8 lanes per position)
-  const int att_h = bid & 15, att_row = bid >> 4;
-  const int att_pos = ATT ? e.state[0] : 0;    // the cache holds positions [0, pos)
-  const int att_nu = (att_pos + 63) >> 6;
-  const bool att_live = ATT && att_row < e.p1.rows;
-  f32x4 kf[ATT ? 4 : 1][AQ], vf[ATT ? 4 : 1][AQ];
-  auto att_request = [&]() {
-    if constexpr (ATT) {
-      if (!att_live) return;
-      const int sub = threadIdx.x & 7, prow = threadIdx.x >> 3;
-      const float* kc = e.att_kc + ((size_t)att_row * 16 + att_h) * (size_t)e.att_max_len * 96;
-      const float* vc = e.att_vc + ((size_t)att_row * 16 + att_h) * (size_t)e.att_max_len * 96;
-#pragma unroll
-      for (int u = 0; u < 4; ++u)
-        if (u < att_nu) {                      // uniform: whole passes only (slots past the end of the last pass re-read the last row)
-          const int p = min(u * 64 + prow, att_pos - 1);
-#pragma unroll
-          for (int i = 0; i < AQ; ++i) kf[u][i] = reinterpret_cast<const f32x4*>(kc + (size_t)p * 96)[sub + 8 * i];
-        }
-#pragma unroll
-      for (int u = 0; u < 4; ++u)
-        if (u < att_nu) {
-          const int p = min(u * 64 + prow, att_pos - 1);
-#pragma unroll
-          for (int i = 0; i < AQ; ++i) vf[u][i] = reinterpret_cast<const f32x4*>(vc + (size_t)p * 96)[sub + 8 * i];
-        }
-    }
-  };
-
-  // ----============================================================ phase 4 (ATT): the next layer's attention for (head att_h, row att_row)
-  auto att_phase = [&]() {
-    if (!att_live) return;
-    constexpr int HD = 96, QUADS = HD / 4, DM = 16 * HD;
-    f32x4* sqkv = red;                                   // rotated q | rotated k | v of the new position | scratch   (3 QUADS + 64 quads)
-    f32x4(*wacc)[QUADS] = reinterpret_cast<f32x4(*)[QUADS]>(red + 3 * QUADS + 64);     // [NW][QUADS]
-    float* wm = reinterpret_cast<float*>(red + 3 * QUADS + 64 + NW * QUADS);
-    float* wl = wm + NW;
-    // ---- hand-off: the q, k and v quads of head h are column tiles 6h .. 6h + 5 of each section = qkv producers 4h .. 4h + 3,
-    //      64 + 4h .. and 128 + 4h .. (workgroup = 2 (tile / 3) + K half): lanes 0 .. 2 of wave 0 poll one aligned group of four
-    if (wid == 0) {
-      const bool broken = (mlpe_ld_sc1(reinterpret_cast<const uint32_t*>(e.state + 4)) & VAURA_STATUS_HANDOFF_TIMEOUT) != 0;
-      const uint32_t* fp = e.flags + 512 + 64 * (lane < 3 ? lane : 0) + 4 * att_h;
-      int spin = 0;
-      for (;;) {
-        u32x4 f;
-        asm volatile("global_load_dwordx4 %0, %1, off sc1\n\ts_waitcnt vmcnt(0)" : "=&v"(f) : "v"(fp) : "memory");
-        const bool ok = f.x == epoch && f.y == epoch && f.z == epoch && f.w == epoch;
-        if (__builtin_amdgcn_ballot_w64(ok) == ~0ull || broken || (e.abl & 1)) break;
-        if (++spin >= MLPE_SPIN_LIMIT) {
-          if (lane == 0) __hip_atomic_fetch_or(e.state_rw + 4, VAURA_STATUS_HANDOFF_TIMEOUT, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-          break;
-        }
-        __builtin_amdgcn_s_sleep(2);
-      }
-    }
-    __builtin_amdgcn_s_barrier();
-    asm volatile("" ::: "memory");
-    // ---- from here on: attention256_body (csrc/attention.hip), steps 2 .. 5, on the rows requested above
-    const int tid = threadIdx.x;
-    const int sub = tid & 7, prow = tid >> 3;
-    const float scale = 1.0f / sqrtf((float)HD);
-    const int gt = min(tid, 3 * QUADS - 1);
-    const int which = gt / QUADS, cq = gt % QUADS;
-    const Gemv3Args& aq = e.p3;
-    // the new position's q / k / v quad: both K-half partials, written in THIS launch -> sc1
-    const __amdgpu_buffer_rsrc_t q1 = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(aq.out), 0, 16 * 3 * DM * 4, 0x00020000);
-    const __amdgpu_buffer_rsrc_t q2 = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(aq.out2), 0, 16 * 3 * DM * 4, 0x00020000);
-    const int qoff = (int)(packed_quad(att_row, (which * DM + att_h * HD + cq * 4) >> 2, 3 * DM) * 16);
-    constexpr int QAUX = 16;     // sc1: past L1, served by L2 (MLPE_ATT_LOCAL: the producers' plain stores left the lines in THIS XCD's L2)
-    f32x4 gx = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(q1, qoff, 0, QAUX));
-    const f32x4 gx2 = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(q2, qoff, 0, QAUX));
-    const f32x4 gcs = *reinterpret_cast<const f32x4*>(e.att_rope + ((size_t)att_pos * (HD / 2) + cq * 2) * 2);  // c0 s0 c1 s1
-    float* kc = e.att_kc + ((size_t)att_row * 16 + att_h) * (size_t)e.att_max_len * HD;
-    float* vc = e.att_vc + ((size_t)att_row * 16 + att_h) * (size_t)e.att_max_len * HD;
-    gx = gx + gx2;
-    f32x4 y;
-    y[0] = gx[0] * gcs[0] - gx[1] * gcs[1];
-    y[1] = gx[1] * gcs[0] + gx[0] * gcs[1];
-    y[2] = gx[2] * gcs[2] - gx[3] * gcs[3];
-    y[3] = gx[3] * gcs[2] + gx[2] * gcs[3];
-    if (which == 2) y = gx;   // v is not rotated
-    sqkv[tid < 3 * QUADS ? tid : 3 * QUADS + (tid & 63)] = y;
-    if (tid >= QUADS && tid < 3 * QUADS)
-      va_st16(reinterpret_cast<f32x4*>((which == 1 ? kc : vc) + (size_t)att_pos * HD) + cq, y);
-    __syncthreads();                                       // (also drains this wave's K / V requests: needed next anyway)
-    const f32x4* sq4 = sqkv;
-    const f32x4* sk4 = sqkv + QUADS;
-    const f32x4* sv4 = sqkv + 2 * QUADS;
-    f32x4 qf[AQ];
-#pragma unroll
-    for (int i = 0; i < AQ; ++i) qf[i] = sq4[sub + 8 * i];
-    auto dot8 = [&](const f32x4* kv) {
-      float d = 0.f;
-#pragma unroll
-      for (int i = 0; i < AQ; ++i)
-#pragma unroll
-        for (int c = 0; c < 4; ++c) d = fmaf(qf[i][c], kv[i][c], d);
-      d += va_dpp<VA_DPP_XOR1>(d);
-      d += va_dpp<VA_DPP_XOR2>(d);
-      d += va_dpp<VA_DPP_HALF_MIRROR>(d);
-      return d;
-    };
-    f32x4 knew[AQ];
-#pragma unroll
-    for (int i = 0; i < AQ; ++i) knew[i] = sk4[sub + 8 * i];
-    const float snew = dot8(knew) * scale;
-    float sc[4];
-    float m = snew;
-#pragma unroll
-    for (int u = 0; u < 4; ++u)
-      if (u < att_nu) {
-        const float d = dot8(kf[u]) * scale;
-        sc[u] = (u * 64 + prow < att_pos) ? d : -INFINITY;
-        m = fmaxf(m, sc[u]);
-      }
-    m = wave_max(m);
-    float l = 0.f;
-    f32x4 av[AQ];
-#pragma unroll
-    for (int i = 0; i < AQ; ++i) av[i] = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int u = 0; u < 4; ++u)
-      if (u < att_nu) {
-        const float ex = expf(sc[u] - m);
-        if (sub == 0) l += ex;
-#pragma unroll
-        for (int i = 0; i < AQ; ++i) av[i] += vf[u][i] * ex;
-      }
-    l = wave_sum(l);
-#pragma unroll
-    for (int i = 0; i < AQ; ++i)
-#pragma unroll
-      for (int c = 0; c < 4; ++c) {
-        float v = av[i][c];
-        v += va_dpp<VA_DPP_ROR8>(v);
-        v += va_xor16(v);
-        v += va_xor32(v);
-        av[i][c] = v;
-      }
-    if (lane < 8) {
-#pragma unroll
-      for (int i = 0; i < AQ; ++i) wacc[wid][lane + 8 * i] = av[i];
-    }
-    if (lane == 0) { wm[wid] = m; wl[wid] = l; }
-    __syncthreads();
-    if (tid < QUADS) {
-      float M = wm[0];
-#pragma unroll
-      for (int w = 1; w < NW; ++w) M = fmaxf(M, wm[w]);
-      const float en = expf(snew - M);
-      float denom = en;
-      f32x4 o = sv4[tid] * en;
-#pragma unroll
-      for (int w = 0; w < NW; ++w) {
-        const float f = expf(wm[w] - M);
-        denom += f * wl[w];
-        o += wacc[w][tid] * f;
-      }
-      o *= 1.0f / denom;
-      va_st16(reinterpret_cast<f32x4*>(e.att_out) + packed_quad(att_row, (att_h * HD) / 4 + tid, DM), o);
-      if (e.att_outp) store_split4(e.att_outp, att_row, att_h * HD + 4 * tid, DM, o);
-    }
-    VA_WAIT_VM(0);
-    VA_STAMP(stamps, 6);
-    VA_STAMP_FLUSH(stamps, 11);
-  };
 
   // ================================================================ phase 1: w1||w3 + SwiGLU (gemv3_kernel<6, 8, 2, E3_SWIGLU, true>)
   {
@@ -420,7 +211,7 @@ __global__ __launch_bounds__(MLPE_NW * 64) void mlp_engine_kernel(const void* __
         for (int g = 0; g < GB; ++g)
 #pragma unroll
           for (int p = 0; p < XPL; ++p)
-            xb[r][b % NXB][g][p] = MLPE_XLOAD(xrs, xl16, (int)(((r * VA_NPL + p) * (K / 8) * 16 + (w * G + b * GB + g) * 64) * 16), 0);
+            xb[r][b % NXB][g][p] = __builtin_amdgcn_raw_buffer_load_b128(xrs, xl16, (int)(((r * VA_NPL + p) * (K / 8) * 16 + (w * G + b * GB + g) * 64) * 16), 0);
       }
     };
     if constexpr (WBATCH) load_w(0, GB, 0);
@@ -446,9 +237,7 @@ __global__ __launch_bounds__(MLPE_NW * 64) void mlp_engine_kernel(const void* __
       ws1[1] = *reinterpret_cast<const f32x4*>(e.p1.wscale + (size_t)(bid * 2 + 1) * 16 + 4 * q);
     }
     __builtin_amdgcn_sched_barrier(0);                 // every request of the first batch is out before anything is waited for
-#ifndef MLPE_DIAG2
-    VA_STAMP(stamps, 1);                               // phase 1: first batch requested
-#endif
+    MLPE_STAMP(MLPE_S0 | MLPE_S1, stamps, 1);          // phase 1: first batch requested
     f32x4 acc[RBK][T][NACC];
 #pragma unroll
     for (int r = 0; r < RBK; ++r)
@@ -493,9 +282,7 @@ __global__ __launch_bounds__(MLPE_NW * 64) void mlp_engine_kernel(const void* __
     // opens the kernel.  LDS operations of a wave execute in order:
     // the word lands behind the tiles (release: the compiler keeps that order too).
     if (lane == 0) __hip_atomic_store(arrive + wid, ltag, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
-#ifndef MLPE_DIAG2
-    VA_STAMP(stamps, 2);                               // phase 1: products done, tiles in LDS
-#endif
+    MLPE_STAMP(MLPE_S0 | MLPE_S1, stamps, 2);          // phase 1: products done, tiles in LDS
     if (epw) {
       float ssp = 0.f;
 #pragma unroll
@@ -510,9 +297,7 @@ __global__ __launch_bounds__(MLPE_NW * 64) void mlp_engine_kernel(const void* __
         if (all) break;
         __builtin_amdgcn_s_sleep(1);
       }
-#ifdef MLPE_DIAG       // diagnostic stamps build with -DMLPE_DIAG: slot 1 <- wave 0 has seen all eight waves' phase-1 tiles, slot 5 <- its stores are issued
-      VA_STAMP(stamps, 1);
-#endif
+      MLPE_STAMP(MLPE_S1, stamps, 1);                  // wave 0 has seen all eight waves' phase-1 tiles
       f32x4 v[T];
 #pragma unroll
       for (int t = 0; t < T; ++t) {
@@ -523,9 +308,7 @@ __global__ __launch_bounds__(MLPE_NW * 64) void mlp_engine_kernel(const void* __
         v[t] = sacc * rinv;
       }
       if (wid * 16 < a.rows) gemv3_epilogue<T, E3_SWIGLU>(a, wid, tile0, lane, v, nullptr);
-#ifdef MLPE_DIAG
-      VA_STAMP(stamps, 5);
-#endif
+      MLPE_STAMP(MLPE_S1, stamps, 5);                  // its epilogue stores are issued
       if constexpr (RBK == 2) {
         if (wid == 1) {      // the second row block's tile: stored (write-through), drained, then the word wave 0 waits for before it publishes
           asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -534,7 +317,7 @@ __global__ __launch_bounds__(MLPE_NW * 64) void mlp_engine_kernel(const void* __
       }
     }
     if (wid == 0) {
-      if (!MLPE_REL && lane == 0) __hip_atomic_store(arrive + 16, ltag, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);   // releases the held part of the other waves' run-ahead (phase 2)
+      if (lane == 0) __hip_atomic_store(arrive + 16, ltag, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);   // releases the held part of the other waves' run-ahead (phase 2)
       // (Measured and rejected, round 4: holding the other waves' run-ahead requests back until these stores are in the CU's memory
       // pipeline.  A CU serves its vector-memory requests in order, so the publish waits behind the seven waves' 224 KB of requests
       // — 2.6 us median in the stamps — and with the hold it comes 2.8 us earlier; but the run-ahead then starts 2.3 us later, wave
@@ -546,50 +329,11 @@ __global__ __launch_bounds__(MLPE_NW * 64) void mlp_engine_kernel(const void* __
         while (__hip_atomic_load(arrive + 18, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP) != ltag) __builtin_amdgcn_s_sleep(1);
       }
       if (lane == 0) asm volatile("global_store_dword %0, %1, off sc0 sc1" ::"v"(e.flags + bid), "v"(epoch) : "memory");
-      if (MLPE_REL && lane == 0) __hip_atomic_store(arrive + 16, ltag, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
-#ifndef MLPE_DIAG2
-      VA_STAMP(stamps, 3);                             // wave 0: published
-#endif
+      MLPE_STAMP(MLPE_S0 | MLPE_S1, stamps, 3);        // wave 0: published
     }
   }
   if (bid >= 192) {
-    if constexpr (!ATT) {
-#ifdef VAURA_EXPERIMENT_ENGINES      // measured negative (round 6, profiles/r06_ab_mall_warm.txt): experiment builds only
-      if (e.pf_lines + e.pf_lines0 > 0) {
-        // helper: wait (bounded, like a consumer) until every phase-1 producer has published, then touch
-        if (!e.pf_early) {
-          (void)mlpe_poll_flags(e.flags, 64, epoch, e, wid, lane);
-          __builtin_amdgcn_s_barrier();
-          asm volatile("" ::: "memory");
-        }
-        const int t0 = (bid - 192) * (MLPE_NW * 64) + (int)threadIdx.x;       // 0 .. 32767
-        // at most 12 lines per thread (w1||w3 on two planes: 393 216 lines over 32 768 threads); every load is issued before anything
-        // waits, and the destination registers stay live up to the wait (the compiler does not know these asm statements are loads).
-        // Two regions: [0, pf_lines0) of pf_ptr0 (the next layer's wo) first, then [0, pf_lines) of pf_ptr (its w1||w3).
-        uint32_t v[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-        const int total = e.pf_lines0 + e.pf_lines;
-        const int npt = (total + 64 * MLPE_NW * 64 - 1) / (64 * MLPE_NW * 64);        // uniform
-#pragma unroll
-        for (int j = 0; j < 12; ++j) {
-          if (j < npt) {
-            int i = t0 + j * (64 * MLPE_NW * 64);
-            if (i >= total) i = t0 % total;                                            // past the end: a line already requested
-            const unsigned char* ptr = i < e.pf_lines0 ? e.pf_ptr0 + (size_t)i * 128 : e.pf_ptr + (size_t)(i - e.pf_lines0) * 128;
-            asm volatile("global_load_dword %0, %1, off nt" : "=v"(v[j]) : "v"(ptr) : "memory");
-          }
-        }
-        asm volatile("s_waitcnt vmcnt(0)"
-                     : "+v"(v[0]), "+v"(v[1]), "+v"(v[2]), "+v"(v[3]), "+v"(v[4]), "+v"(v[5]), "+v"(v[6]), "+v"(v[7]), "+v"(v[8]), "+v"(v[9]),
-                       "+v"(v[10]), "+v"(v[11])
-                     :
-                     : "memory");
-      }
-#endif
-      VA_STAMP_FLUSH(stamps, 11);
-    } else {
-      att_request();                           // no w2 / qkv tile here: this (row, head)'s K / V rows at once,
-      att_phase();                             // then straight to the attention (its own copy of the code: the rows' registers are not
-    }                                          // live through the phases these workgroups skip)
+    VA_STAMP_FLUSH(stamps, 11);
     return;
   }
 
@@ -646,9 +390,9 @@ __global__ __launch_bounds__(MLPE_NW * 64) void mlp_engine_kernel(const void* __
       prefetch_q(std::integral_constant<int, 2>{}); prefetch_q(std::integral_constant<int, 3>{});
     };
     if (!(e.abl & 8) && !(e.abl & 4)) {
-      // partial hold: waves 1..7 request MLPE_Q2 quarters of their slice at once and the rest only when wave 0's epilogue stores are in
+      // partial hold: waves 1..7 request Q2 quarters of their slice at once and the rest only when wave 0's epilogue stores are in
       // the CU's memory pipeline (ablation bit 3: no hold, round 4's first form); wave 0 comes here behind its publish and holds nothing
-      constexpr int Q2 = MlpeThrottle<WT, RBK>::Q2;
+      constexpr int Q2 = mlpe_q2<WT>;
       const bool hold = wid >= RBK;                    // (the waves that finish a row block come here behind their own stores and hold nothing)
       if (!hold || Q2 > 0) prefetch_q(std::integral_constant<int, 0>{});
       if (!hold || Q2 > 1) prefetch_q(std::integral_constant<int, 1>{});
@@ -662,35 +406,13 @@ __global__ __launch_bounds__(MLPE_NW * 64) void mlp_engine_kernel(const void* __
         if (Q2 < 4) prefetch_q(std::integral_constant<int, 3>{});
       }
     } else if (!(e.abl & 4)) prefetch_w2();
-#ifndef MLPE_DIAG2
-    if (wid != 0) VA_STAMP(stamps, 3);                 // waves 1..7: w2 slice requested
-#endif
+    if (wid != 0) MLPE_STAMP(MLPE_S0 | MLPE_S1, stamps, 3);      // waves 1..7: w2 slice requested
 
     // ---- hand-off 1: wave 0 polls the 256 producer flags (lane i: flags 4i .. 4i + 3), bounded; the barrier releases the rest.
-    //      (Round 6, measured NEGATIVE and kept in experiment builds only — -DVAURA_EXPERIMENT_ENGINES, second flag word bit 7: every wave
-    //      polling just the 32 producers of its own K slice, no workgroup barrier.  Bit-identical, and slower: two planes + 0.6 %, one plane
-    //      + 3.3 %, fp8h + 2.1 % on whole loops (profiles/r06_ab_pollwave.txt) — eight pollers per consumer instead of one hammer the flag
-    //      lines the producers are still storing to, and a wave's poll waits for its own w2 prefetch.)
-#ifdef VAURA_EXPERIMENT_ENGINES
-    if (e.pollwave) {
-      const bool broken = (mlpe_ld_sc1(reinterpret_cast<const uint32_t*>(e.state + 4)) & VAURA_STATUS_HANDOFF_TIMEOUT) != 0;
-      const uint32_t* fp = e.flags + 32 * w + 4 * (lane & 7);
-      int spin = 0;
-      for (;;) {
-        u32x4 f;
-        asm volatile("global_load_dwordx4 %0, %1, off sc1\n\ts_waitcnt vmcnt(0)" : "=&v"(f) : "v"(fp) : "memory");
-        const bool ok = f.x == epoch && f.y == epoch && f.z == epoch && f.w == epoch;
-        if (__builtin_amdgcn_ballot_w64(ok) == ~0ull || broken || (e.abl & 1)) break;
-        if (++spin >= MLPE_SPIN_LIMIT) {
-          if (lane == 0) __hip_atomic_fetch_or(e.state_rw + 4, VAURA_STATUS_HANDOFF_TIMEOUT, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-          break;
-        }
-        __builtin_amdgcn_s_sleep(2);
-      }
-      asm volatile("" ::: "memory");
-    } else
-#endif
-    {
+    //      (Round 6, measured negative and removed: every wave polling just the 32 producers of its own K slice, no workgroup barrier.
+    //      Bit-identical, and slower: two planes + 0.6 %, one plane + 3.3 %, fp8h + 2.1 % on whole loops (profiles/r06_ab_pollwave.txt) —
+    //      eight pollers per consumer instead of one hammer the flag lines the producers are still storing to, and a wave's poll waits
+    //      for its own w2 prefetch.)
     if (wid == 0) {
       const bool broken = (mlpe_ld_sc1(reinterpret_cast<const uint32_t*>(e.state + 4)) & VAURA_STATUS_HANDOFF_TIMEOUT) != 0;
       int spin = 0;
@@ -710,7 +432,6 @@ __global__ __launch_bounds__(MLPE_NW * 64) void mlp_engine_kernel(const void* __
     // before anybody may request the planes.  Only control has to pass here: the planes are requested behind it in program order.
     __builtin_amdgcn_s_barrier();
     asm volatile("" ::: "memory");
-    }
     VA_STAMP(stamps, 4);                               // hand-off barrier passed (wave 0: its poll matched just before)
     if (e.abl & 4) prefetch_w2();
 
@@ -725,7 +446,7 @@ __global__ __launch_bounds__(MLPE_NW * 64) void mlp_engine_kernel(const void* __
       for (int j = j0; j < j1; ++j)
 #pragma unroll
         for (int p = 0; p < XPL; ++p)
-          xb[r][j][p] = MLPE_XLOAD(xrs, vx, ((r * VA_NPL + p) * (K / 8) * 16 + (w * G2 + j) * 128) * 16, 16 /* sc1 */);
+          xb[r][j][p] = __builtin_amdgcn_raw_buffer_load_b128(xrs, vx, ((r * VA_NPL + p) * (K / 8) * 16 + (w * G2 + j) * 128) * 16, 16 /* sc1 */);
     };
     using I0 = std::integral_constant<int, 0>;
     using I1 = std::integral_constant<int, 1>;
@@ -742,9 +463,7 @@ __global__ __launch_bounds__(MLPE_NW * 64) void mlp_engine_kernel(const void* __
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __builtin_amdgcn_sched_barrier(0);
     VA_WAIT_VM(0);
-#if !defined(MLPE_DIAG) && !defined(MLPE_DIAG2)
-    VA_STAMP(stamps, 5);                               // (diagnostic build) weights and planes landed
-#endif
+    MLPE_STAMP(MLPE_S0, stamps, 5);                    // weights and planes landed
     f32x4 acc[RBK][2][NACC];
 #pragma unroll
     for (int r = 0; r < RBK; ++r)
@@ -771,21 +490,9 @@ __global__ __launch_bounds__(MLPE_NW * 64) void mlp_engine_kernel(const void* __
     // Round 6: the fragments of pair j + 1 are fetched (LDS read, fp8 widening) BEFORE the products of pair j are issued — the stamps
     // (profiles/r06_engine_stamps_diag2.txt) show 1.0 .. 1.7 us between "planes landed" and "products done" for 0.2 .. 0.4 us of matrix
     // instructions: every pair paid its LDS round trip (and the fp8 -> fp16 conversion) in front of its own products.  Same products into
-    // the same accumulators in the same order: bit-identical.  (-DMLPE_NO_WPIPE: the previous form, for the A/B.)
+    // the same accumulators in the same order: bit-identical.  (The previous form's A/B: profiles/r06_ab_wpipe.txt.)
     auto products = [&](auto rc, auto j0c, auto j1c) {
       constexpr int r = decltype(rc)::value, j0 = decltype(j0c)::value, j1 = decltype(j1c)::value;
-#ifdef MLPE_NO_WPIPE
-#pragma unroll
-      for (int j = j0; j < j1; ++j) {
-#pragma unroll
-        for (int nh = 0; nh < 2; ++nh) {
-          f16x8 wf[WFN];
-          wfetch(j, nh, wf);
-          mfma_group<WT>(wf, xb[r][j], acc[r][nh]);
-        }
-        __builtin_amdgcn_sched_barrier(0);
-      }
-#else
       f16x8 cur[2][WFN], nxt[2][WFN];
       wfetch(j0, 0, cur[0]);
       wfetch(j0, 1, cur[1]);
@@ -803,7 +510,6 @@ __global__ __launch_bounds__(MLPE_NW * 64) void mlp_engine_kernel(const void* __
 #pragma unroll
           for (int i = 0; i < WFN; ++i) cur[nh][i] = nxt[nh][i];
       }
-#endif
     };
     if constexpr (RBK == 1) {
       products(I0{}, I0{}, IG{});
@@ -857,20 +563,7 @@ __global__ __launch_bounds__(MLPE_NW * 64) void mlp_engine_kernel(const void* __
       // tile) — the slices, products and 4-wave reduction of gemv3_kernel<6, 4, 3, E3_STORE, true, 1, 0, 1, 2> — waves 4 .. 7 only
       // pass the barriers (and finish tiles: any wave can run an epilogue)
       constexpr int G = FP8 ? 6 : 3, NWQ = FP8 ? 4 : NW, GF = 3, TQ = 3, KQ = 1536, KGQ = KQ / 32;
-      // EXPERIMENT build -DMLPE_ATT_LOCAL (ATT instances): the qkv work items of head h on the XCD of h's attention workgroups (XCD =
-      // workgroup id % 8 = h % 8): item s 64 + 4 h + sub goes to workgroup (h % 8) + 8 ((h / 8) 12 + 4 s + sub), so that the hand-off
-      // of the q / k / v quads stays inside one L2 (consumer loads sc0 instead of sc1)
-      // Round 6 (e.qlocal, second flag word bit 23 — A/B): the same relabelling for the ordinary instances, ACROSS the kernel boundary: the
-      // attention launch that follows puts (head h, row r) on XCD h % 8 too, so if an XCD's L2 keeps what its own workgroups stored
-      // (plain stores, written back by the end-of-kernel release) the new q / k / v quads are L2 hits there instead of a memory-side read.
-#ifdef MLPE_ATT_LOCAL
-      const int qid = ATT ? (((bid >> 3) % 12) >> 2) * 64 + 4 * ((bid & 7) + 8 * ((bid >> 3) / 12)) + (((bid >> 3) % 12) & 3) : bid;
-#elif defined(VAURA_EXPERIMENT_ENGINES)      // measured: no effect (profiles/r06_ab_qlocal.txt) — the kernel-start acquire leaves nothing of the previous launch in L2
-      const int qid = (!ATT && e.qlocal) ? (((bid >> 3) % 12) >> 2) * 64 + 4 * ((bid & 7) + 8 * ((bid >> 3) / 12)) + (((bid >> 3) % 12) & 3) : bid;
-#else
-      const int qid = bid;
-#endif
-      const int ks = qid & 1, tile0q = (qid >> 1) * TQ, kgo = ks * G * NWQ;
+      const int ks = bid & 1, tile0q = (bid >> 1) * TQ, kgo = ks * G * NWQ;
       const bool actq = wid < NWQ;                     // this wave multiplies in the qkv phase
       const int w3 = (wid + bid) % NWQ;
       const int mq = lane & 15;
@@ -898,16 +591,14 @@ __global__ __launch_bounds__(MLPE_NW * 64) void mlp_engine_kernel(const void* __
         load_wq_g(std::integral_constant<int, 2>{});
       };
       if (lane == 0) __hip_atomic_store(arrive2 + wid, ltag, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
-#ifdef MLPE_DIAG2      // second diagnostic stamp set (-DVAURA_STAMPS -DMLPE_DIAG2): the phase 2 -> 3 chain.  slot 1 <- phase-2 products done, 2 <- wave 0
-      VA_STAMP(stamps, 1);   // saw all tiles + epilogue stores issued, 3 <- phase 2 published (drained + flag), 5 <- hand-off 2 passed, 6 <- done
-#endif
+      MLPE_STAMP(MLPE_S2, stamps, 1);                  // phase 2: products done, tiles in LDS
       f32x4 wsq = f32x4{1.f, 1.f, 1.f, 1.f};
       const bool epq = wid < TQ * RBK;                 // this wave finishes tile (wid % TQ) of row block (wid / TQ) of the qkv phase
       const int rq = wid / TQ, tq = wid - rq * TQ;
       if (!epw && actq) {
         if (!(e.abl & 8)) {   // PRE3 of the three k-groups at once, the rest once wave 0's phase-2 stores are in the memory pipeline
           // in ninths (k-group g, tile t; unit = 3 g + t): PRE3U of them at once, the rest behind the hold
-          constexpr int PRE3U = MlpeThrottle<WT, RBK>::PRE3U;
+          constexpr int PRE3U = mlpe_pre3u<WT>;
           auto unit = [&](auto uc) {
             constexpr int u = decltype(uc)::value, g = u / 3, t = u % 3;
 #pragma unroll
@@ -933,10 +624,8 @@ __global__ __launch_bounds__(MLPE_NW * 64) void mlp_engine_kernel(const void* __
         for (int i = 1; i < NW; ++i) v += red[((wid * NW + i) * 2 + (q >> 1)) * 64 + src];
         v *= ws2;
         if (mine && wid * 16 < a.rows) gemv3_epilogue<1, E3_RESID>(a, wid, tile, lane, &v, &pre);
-#ifdef MLPE_DIAG2
-        VA_STAMP(stamps, 2);
-#endif
-        if (wid == 0 && !MLPE_REL && lane == 0) __hip_atomic_store(arrive + 17, ltag, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
+        MLPE_STAMP(MLPE_S2, stamps, 2);                // wave 0 saw all tiles, epilogue stores issued
+        if (wid == 0 && lane == 0) __hip_atomic_store(arrive + 17, ltag, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
         // publish phase 2: h, its partial sums of squares and its planes are out (write-through), drained, then the flag (two row
         // blocks: wave 1 drains its block's stores and tells wave 0, which publishes for both)
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -948,18 +637,13 @@ __global__ __launch_bounds__(MLPE_NW * 64) void mlp_engine_kernel(const void* __
           }
         }
         if (wid == 0 && lane == 0) asm volatile("global_store_dword %0, %1, off sc0 sc1" ::"v"(e.flags + 256 + bid), "v"(epoch) : "memory");
-        if (wid == 0 && MLPE_REL && lane == 0) __hip_atomic_store(arrive + 17, ltag, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
-#ifdef MLPE_DIAG2
-        VA_STAMP(stamps, 3);
-#endif
+        MLPE_STAMP(MLPE_S2, stamps, 3);                // phase 2 published (drained + flag)
         load_wq();
       }
       (void)mlpe_poll_flags(e.flags + 256, 48, epoch, e, wid, lane);
       __builtin_amdgcn_s_barrier();
       asm volatile("" ::: "memory");
-#ifdef MLPE_DIAG2
-      VA_STAMP(stamps, 5);
-#endif
+      MLPE_STAMP(MLPE_S2, stamps, 5);                  // hand-off 2 passed
       const __amdgpu_buffer_rsrc_t hrs = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint16_t*>(aq.XP), 0, aq.R * VA_NPL * (KQ / 8) * 256, 0x00020000);
       const __amdgpu_buffer_rsrc_t srs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(aq.ss_in), 0, RBK * 96 * 16 * 4, 0x00020000);
       u32x4 xq[RBK][G][XPL];
@@ -970,7 +654,7 @@ __global__ __launch_bounds__(MLPE_NW * 64) void mlp_engine_kernel(const void* __
         for (int g = 0; g < G; ++g)
 #pragma unroll
           for (int p = 0; p < XPL; ++p)
-            xq[r][g][p] = MLPE_XLOAD(hrs, xl16, (int)(((r * VA_NPL + p) * (KQ / 8) * 16 + (kgo + w3 * G + g) * 64) * 16), 16 /* sc1 */);
+            xq[r][g][p] = __builtin_amdgcn_raw_buffer_load_b128(hrs, xl16, (int)(((r * VA_NPL + p) * (KQ / 8) * 16 + (kgo + w3 * G + g) * 64) * 16), 16 /* sc1 */);
       }
       constexpr int NSSQ = KQ / 64;
       float ssq[NSSQ];
@@ -1021,8 +705,6 @@ __global__ __launch_bounds__(MLPE_NW * 64) void mlp_engine_kernel(const void* __
         ssp += va_xor32(ssp);
         rinvq = 1.0f / sqrtf(ssp * (1.0f / (float)aq.k_total) + aq.eps);
       }
-      // ATT: the waves without a tile to finish have nothing left to request for this phase: their share of the K / V rows now
-      if (ATT && !epq) att_request();
       __syncthreads();
       if (epq && rq * 16 < aq.rows) {
         f32x4 sacc = red[((rq * NW + 0) * TQ + tq) * 64 + lane];
@@ -1031,51 +713,11 @@ __global__ __launch_bounds__(MLPE_NW * 64) void mlp_engine_kernel(const void* __
         sacc *= wsq;
         const f32x4 v = sacc * rinvq;
         if (ks > 0) aq.out = aq.out2;
-#ifdef MLPE_ATT_LOCAL
-        if constexpr (ATT) {     // plain store: the line stays in this XCD's L2, where the head's attention workgroups read it (sc1 loads)
-          reinterpret_cast<f32x4*>(aq.out)[((size_t)rq * (aq.N / 4) + (size_t)(tile0q + tq) * 4) * 16 + lane] = v;
-        } else
-#endif
-#ifdef VAURA_EXPERIMENT_ENGINES
-        if (!ATT && e.qlocal) {  // plain store (see qid above)
-          reinterpret_cast<f32x4*>(aq.out)[((size_t)rq * (aq.N / 4) + (size_t)(tile0q + tq) * 4) * 16 + lane] = v;
-        } else
-#endif
         gemv3_epilogue<1, E3_STORE>(aq, rq, tile0q + tq, lane, &v, nullptr);
       }
-      if constexpr (ATT) {
-        // publish the qkv tiles (write-through stores): waves 0 .. 2 stored one each — drained, waves 1 and 2 tell wave 0 (LDS words),
-        // wave 0 stores the flag; then these waves request their share of the K / V rows (behind their stores: a wave's vector-memory
-        // counter retires in order, a drain in front of the flag would otherwise wait for the rows)
-        if (epq) {
-          asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-          if (wid > 0) {
-            if (lane == 0) __hip_atomic_store(arrive + 20 + wid, ltag, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
-          } else {
-            while (__hip_atomic_load(arrive + 21, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP) != ltag ||
-                   __hip_atomic_load(arrive + 22, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP) != ltag)
-              __builtin_amdgcn_s_sleep(1);
-#ifdef MLPE_ATT_LOCAL
-            if (lane == 0) asm volatile("global_store_dword %0, %1, off" ::"v"(e.flags + 512 + qid), "v"(epoch) : "memory");
-#else
-            if (lane == 0) asm volatile("global_store_dword %0, %1, off sc0 sc1" ::"v"(e.flags + 512 + qid), "v"(epoch) : "memory");
-#endif
-          }
-          att_request();
-        }
-      } else {
-        VA_WAIT_VM(0);
-        VA_STAMP(stamps, 6);
-        VA_STAMP_FLUSH(stamps, 11);
-      }
+      VA_WAIT_VM(0);
+      VA_STAMP(stamps, 6);
+      VA_STAMP_FLUSH(stamps, 11);
     }
   }
-
-  if constexpr (ATT) att_phase();
 }
-
-#ifdef VAURA_EXPERIMENT_ENGINES
-// measured-negative engines (the layer tail as one launch; DESIGN_HISTORY.md round 4): experiment builds only
-// (python -m vaura_amd.csrc.build --tag engines -DVAURA_EXPERIMENT_ENGINES=1), never part of libvaura_hip.so
-#include "experiments/tail_engine.h"
-#endif
