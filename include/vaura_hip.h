@@ -211,7 +211,8 @@ typedef struct vaura_decoder {
   int32_t pattern_delays[16];
   /* Bytes of extension that FOLLOW this struct in the caller's memory: 0 (a zero-filled descriptor: none), or
    * sizeof(vaura_decoder_ext) - sizeof(vaura_decoder) when `dec` is the first member of a vaura_decoder_ext (below), or
-   * sizeof(vaura_decoder_ext2) - sizeof(vaura_decoder) when that in turn is the first member of a vaura_decoder_ext2; anything else is
+   * sizeof(vaura_decoder_ext2) - sizeof(vaura_decoder) when that in turn is the first member of a vaura_decoder_ext2, or
+   * sizeof(vaura_decoder_ext3) - sizeof(vaura_decoder) when that is the first member of a vaura_decoder_ext3; anything else is
    * VAURA_ERR_ARG.  It occupies what was alignment padding in front of `kscale`: no field moved and the struct keeps its size, so a
    * caller compiled against the descriptor without it (and zero-filling it, as every field's default asks) runs unchanged. */
   int32_t ext_bytes;
@@ -285,6 +286,23 @@ typedef struct vaura_decoder_ext2 {
   const int32_t* clip_timesteps;
   const int32_t* clip_cond_tokens;
 } vaura_decoder_ext2;
+
+/* vaura_decoder_ext2 with the per-clip audio PROMPT lengths of a batch appended behind it.  Every entry point takes
+ * `&ext3.ext2.ext.dec`; the library reads the pointer only when dec.ext_bytes = sizeof(vaura_decoder_ext3) - sizeof(vaura_decoder).
+ *   row_prompt_steps  `rows` int32 in device memory, or NULL (every clip starts where the loop starts, as without this struct).
+ *                     Entry r is n_r = P_b + delays[0] for the clip b = r % batch of row r: the number of teacher-forced positions of
+ *                     that clip, i.e. the position of its first sampled step.  0 <= n_r <= seq_len - 1.
+ * With it the sampler keys clip b's Philox counter by (position - n_b) instead of the loop's step index — the step index the call
+ * with the common prompt of P_b frames has at that position — so a clip draws what it draws in that call wherever the loop of this
+ * call started.  An explicit `noise` tensor and the near-tie detector's "first flagged step" keep the loop's step.  Nothing else of
+ * the step changes: a row that is still inside its prompt holds known tokens in every slot the sampler visits, and the fix-up
+ * writes (and reports, and counts) only where a slot still holds -1.
+ * vaura_prefill_rows (below) reads the same array to append K / V for one group of rows.
+ * A captured step graph holds the POINTER; the host-side range check follows the rules of clip_timesteps. */
+typedef struct vaura_decoder_ext3 {
+  vaura_decoder_ext2 ext2;  /* ext2.ext.dec.ext_bytes = sizeof(vaura_decoder_ext3) - sizeof(vaura_decoder) */
+  const int32_t* row_prompt_steps;
+} vaura_decoder_ext3;
 
 /* -------------------------------------------------------------------------------------------
  * Weight ingress (once, at load).  Replaces nn.Module.load_state_dict for the streamed matrices.
@@ -398,6 +416,21 @@ int vaura_sequence_logprob_clips(const float* logprobs, int seq_len, const int32
 int vaura_sample_seq(const float* logits, int B, int K, int vocab, const vaura_sampling* sp, const vaura_clip_sampling* clips,
                      const float* noise, int32_t* seq, int T, int S, int32_t* state, const int32_t* delays_host,
                      const int32_t* clip_timesteps, float* lp_seq, float* cond_seq, float* null_seq, vaura_stream_t s);
+/* vaura_sample_seq with per-clip first sampled positions (vaura_decoder_ext3.row_prompt_steps; clip_first_steps: B int32 in device
+ * memory, 0 <= n_b <= S - 1): clip b's Philox counter step is state[0] - n_b instead of state[2].  Clip by clip the result equals
+ * vaura_sample_seq on a state whose step index state[2] is state[0] - n_b.  An explicit noise keeps state[2].  VAURA_ERR_ARG: a NULL
+ * clip_first_steps, a value out of range (read back: one small copy and a wait on the stream), and what vaura_sample_seq refuses. */
+int vaura_sample_seq_starts(const float* logits, int B, int K, int vocab, const vaura_sampling* sp, const vaura_clip_sampling* clips,
+                            const float* noise, int32_t* seq, int T, int S, int32_t* state, const int32_t* delays_host,
+                            const int32_t* clip_timesteps, const int32_t* clip_first_steps, float* lp_seq, float* cond_seq,
+                            float* null_seq, vaura_stream_t s);
+/* vaura_sequence_logprob / vaura_sequence_logprob_clips with a per-clip first frame: the means of clip b run over frames
+ * clip_t0[b] .. T_b - 1 (clip_t0: B int32 in device memory; clip_timesteps: B lengths or NULL, every clip then has T).  Clip by clip
+ * the bits of those entries called with t0 = clip_t0[b].  VAURA_ERR_ARG: a NULL clip_t0, a value outside 0 .. T_b - 1 (both arrays
+ * are read back), and what the scalar forms refuse. */
+int vaura_sequence_logprob_starts(const float* logprobs, int seq_len, const int32_t* delays_host, int B, int K, int T,
+                                  const int32_t* clip_t0, const int32_t* clip_timesteps, float* per_codebook, float* per_clip,
+                                  vaura_stream_t s);
 /* The input embedding of the decode step (pos_host < 0, n_pos = 1: the position is state[0]) or of n_pos prefill positions from
  * pos_host on, alone: dec->ws_h (packed rows; prefill: one block of rows_padded rows per position) and, on the plane storages, the
  * planes and sums of squares behind it.  Obeys vaura_decoder_ext2.clip_cond_tokens.  Nothing advances.  Every token of dec->seq at the
@@ -424,6 +457,17 @@ typedef void* vaura_step_graph_t;
 int vaura_generate_loop(const vaura_decoder* dec, const vaura_sampling* sp, int n_prefill, int n_steps,
                         vaura_step_graph_t graph, vaura_stream_t s);
 int vaura_step_graph_build(const vaura_decoder* dec, const vaura_sampling* sp, vaura_stream_t s, vaura_step_graph_t* out);
+/* The prefill pass of ONE group of rows of a call with per-clip prompt lengths (vaura_decoder_ext3.row_prompt_steps), on the plane
+ * storages (prefill_positions > 0): exactly the chunk sequence vaura_generate_loop runs for n_prefill teacher-forced positions — from
+ * position 0, in chunks of prefill_positions, every row computed, so every launch is the instance that call picks — except that K / V
+ * (and the exponent bytes of kv_dtype 3) are appended only to the rows r with row_prompt_steps[r] == n_sel; the cache rows of every
+ * other row keep their bytes.  It neither reads nor advances `state`: the caller runs it between two vaura_generate_loop calls, just
+ * before the step at position n_sel.  Every token of dec->seq at positions [0, n_prefill) must be known for EVERY row (the embedding
+ * gathers by token and does not clamp): that holds at that moment, and not earlier.
+ * VAURA_ERR_ARG, before any launch: a descriptor without the array or without prefill workspaces, n_sel outside 1 .. seq_len - 1,
+ * n_prefill outside 1 .. n_sel, a value of the array outside 0 .. seq_len - 1 (the array is read back: one small copy and a wait on
+ * the stream). */
+int vaura_prefill_rows(const vaura_decoder* dec, int n_prefill, int n_sel, vaura_stream_t s);
 void vaura_step_graph_free(vaura_step_graph_t graph);
 
 /* Measurement aid (bench.py): runs `n_steps` sampled steps eagerly on `s` with a hipEvent pair
@@ -537,6 +581,11 @@ int vaura_attention_step_kv(const float* qkv, const float* qkv2, const float* ro
  * n_pos <= 0, p0 + n_pos > max_len; VAURA_ERR_SHAPE: head_dim != 96, or a narrow cache (kv_dtype != 0) of more than 256 positions.
  * Debug flag bit 4 selects the per-position kernel (fp32 cache).                                                                      */
 int vaura_attention_prefill(const vaura_decoder* d, int layer, int p0, int n_pos, vaura_stream_t s);
+/* Op-level access to the masked append of vaura_prefill_rows: rope of q (in place, EVERY row) and of k, and the K / V append of the
+ * chunk [p0, p0 + n_pos) of one layer only for the rows r with row_n[r] == n_sel (row_n: d->rows int32 in device memory); the cache
+ * rows and exponent bytes of every other row keep their bytes.  On the selected rows the bytes are those of the append that
+ * vaura_attention_prefill starts with.  Reads of `d` as there (no ws_attn).  VAURA_ERR_ARG: a NULL row_n, and what that entry refuses. */
+int vaura_rope_append_rows(const vaura_decoder* d, int layer, int p0, int n_pos, const int32_t* row_n, int n_sel, vaura_stream_t s);
 
 /* -------------------------------------------------------------------------------------------
  * a16 DacModelWrapper.decode (models/modules/dac/model.py:41-48): quantizer.from_codes + DAC
@@ -895,7 +944,8 @@ long long vaura_debug_counter(int which);
 
 const char* vaura_version(void);
 /* sizeof() of the descriptor structs as compiled into the library (0 dims, 1 layer_weights, 2 sampling, 3 decoder,
- * 4 conv, 5 codec, 6 codec_encoder, 7 vit, 8 vit_block, 9 clip_sampling, 10 decoder_ext, 11 decoder_ext2): a binding checks its mirrored struct layouts against these before the first call.            */
+ * 4 conv, 5 codec, 6 codec_encoder, 7 vit, 8 vit_block, 9 clip_sampling, 10 decoder_ext, 11 decoder_ext2, 13 decoder_ext3; 12 is
+ * unassigned and answers 0 like every unknown index): a binding checks its mirrored struct layouts against these before the first call.            */
 size_t vaura_struct_size(int which);
 
 #ifdef __cplusplus

@@ -74,6 +74,13 @@ class DecoderExt2(C.Structure):
     _fields_ = [("ext", DecoderExt), ("clip_timesteps", C.c_void_p), ("clip_cond_tokens", C.c_void_p)]
 
 
+class DecoderExt3(C.Structure):
+    """vaura_decoder_ext3: the descriptor with the per-clip prompt lengths of a batch behind everything else (one device pointer to
+    ``rows`` int32, n_r = P_b + delays[0] of every row; may be NULL).  Entry points take ``byref(ext3.ext2.ext.dec)``; ``dec.ext_bytes`` = 40
+    tells the library that all five pointers follow."""
+    _fields_ = [("ext2", DecoderExt2), ("row_prompt_steps", C.c_void_p)]
+
+
 class Conv(C.Structure):
     _fields_ = [("w", C.c_void_p), ("bias", C.c_void_p), ("wscale", C.c_void_p), ("cin", C.c_int32), ("cout", C.c_int32),
                 ("taps", C.c_int32), ("dilation", C.c_int32), ("stride", C.c_int32), ("_pad", C.c_int32)]
@@ -206,6 +213,13 @@ SIGNATURES = {
                                                C.c_void_p, C.c_void_p, C.c_void_p]),
     "vaura_sample_seq": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(Sampling), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
                                    C.c_int, C.c_void_p, C.POINTER(C.c_int32), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "vaura_sample_seq_starts": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(Sampling), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
+                                          C.c_int, C.c_void_p, C.POINTER(C.c_int32), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                          C.c_void_p]),
+    "vaura_sequence_logprob_starts": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int32), C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                                C.c_void_p, C.c_void_p, C.c_void_p]),
+    "vaura_prefill_rows": (C.c_int, [C.POINTER(Decoder), C.c_int, C.c_int, C.c_void_p]),
+    "vaura_rope_append_rows": (C.c_int, [C.POINTER(Decoder), C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
     "vaura_embed": (C.c_int, [C.POINTER(Decoder), C.c_int, C.c_int, C.c_void_p]),
     "vaura_decode_step": (C.c_int, [C.POINTER(Decoder), C.POINTER(Sampling), C.c_int, C.c_void_p]),
     "vaura_generate_loop": (C.c_int, [C.POINTER(Decoder), C.POINTER(Sampling), C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
@@ -283,7 +297,9 @@ def lib() -> C.CDLL:
             fn = getattr(handle, name)  # AttributeError if the symbol is not exported
             fn.restype = res
             fn.argtypes = args
-        for which, cls in enumerate([Dims, LayerWeights, Sampling, Decoder, Conv, Codec, CodecEncoder, Vit, VitBlock, ClipSampling, DecoderExt, DecoderExt2]):
+        structs = dict(enumerate([Dims, LayerWeights, Sampling, Decoder, Conv, Codec, CodecEncoder, Vit, VitBlock, ClipSampling, DecoderExt, DecoderExt2]))
+        structs[13] = DecoderExt3      # vaura_struct_size: 12 is unassigned
+        for which, cls in structs.items():
             if C.sizeof(cls) != handle.vaura_struct_size(which):
                 raise VauraHipError(f"{LIB_PATH} was built from a different include/vaura_hip.h: sizeof({cls.__name__}) is "
                                     f"{handle.vaura_struct_size(which)} there, {C.sizeof(cls)} here (rebuild the library)")

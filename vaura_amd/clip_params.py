@@ -215,3 +215,68 @@ def score_list_lengths(codes, num_codebooks: int) -> List[int]:
             raise _error(f"codes of clip {b} must be ({num_codebooks}, Ta_b) or (1, {num_codebooks}, Ta_b), got {tuple(getattr(c, 'shape', ()))}")
         lens.append(int(shape[1]))
     return lens
+
+
+# ---- per-clip audio prompt lengths of one batched call: prompt_lengths = [P_0 .. P_{B-1}], 0 <= P_b < T_b, on a prompt (B, K, P_max).
+# Resolved and checked here, before any device work (include/vaura_hip.h vaura_decoder_ext3).
+def resolve_prompt_lengths(batch: Optional[int], prompt_lengths, prompt_len: Optional[int], t_max: int, lens: Optional[List[int]] = None):
+    """[P_b] of a call, or None without the keyword.  ``prompt_lengths``: one int per clip (list / tuple / 1-D integer tensor), 0 <= P_b
+    <= ``prompt_len`` (P_max, the prompt tensor's last dimension; None: there is no prompt, which is refused) and P_b < T_b, T_b =
+    ``lens[b]`` or ``t_max``.  ``batch`` None: not known yet, checked by a later call."""
+    if prompt_lengths is None:
+        return None
+    if prompt_len is None:
+        raise _error("prompt_lengths needs an audio prompt: it says how many frames of each clip's prompt are real")
+    if not is_per_clip(prompt_lengths):
+        raise _error(f"prompt_lengths must be one integer per clip (a list, tuple or 1-D tensor), got {prompt_lengths!r}")
+    P = _int_list("prompt_lengths", prompt_lengths)
+    if batch is not None and len(P) != batch:
+        raise _error(f"prompt_lengths has {len(P)} values for a batch of {batch} clips")
+    if lens is not None and len(P) != len(lens):
+        raise _error(f"prompt_lengths has {len(P)} values but max_new_tokens has {len(lens)}: one value per clip")
+    if not P or min(P) < 0 or max(P) > prompt_len:
+        raise _error(f"prompt_lengths must lie in 0 .. {prompt_len} (the frames of the prompt tensor), got {P}")
+    for b, p in enumerate(P):
+        T_b = lens[b] if lens is not None else t_max
+        if p >= T_b:
+            raise _error(f"the audio prompt of clip {b} ({p} frames) must be shorter than its max_new_tokens ({T_b})")
+    return P
+
+
+def prompt_rows(clips: List[int], batch: int, cfg: bool = False, num_candidates: int = 1) -> List[int]:
+    """The decoder rows of the given clips of a call over ``batch`` clips: candidate j of clip b is row b * N + j, and with the
+    null-condition rows its twin is row batch * N + b * N + j."""
+    N = int(num_candidates)
+    rows = [b * N + j for b in clips for j in range(N)]
+    return rows + [batch * N + r for r in rows] if cfg else rows
+
+
+def prompt_schedule(prompt_lengths: List[int], first_delay: int, seq_len: int, cfg: bool = False, num_candidates: int = 1) -> List[tuple]:
+    """The order of work of a call with per-clip prompt lengths, as a list of ("prefill", n, rows) and ("steps", count) entries.
+    n_b = P_b + ``first_delay`` positions of clip b are teacher-forced; n_(1) < .. < n_(G) are the distinct values.  Sampled steps run for
+    the whole batch from position n_(1) to ``seq_len`` - 2 (the last one fills slot ``seq_len`` - 1); just before the step at position
+    n_(g) comes group g's prefill pass over positions [0, n_(g)), whose K / V go to ``rows`` — the rows of the group's clips, their
+    null-condition rows (``cfg``) and candidates — only.  At that moment every row holds a known token at every position below n_(g);
+    no earlier.  A group with n = 0 has no pass.  Equal lengths give the scalar call's plan: at most one pass over every row, then
+    ``seq_len`` - 1 - n steps."""
+    B = len(prompt_lengths)
+    n = [int(p) + int(first_delay) for p in prompt_lengths]
+    if not n or min(n) < 0 or max(n) > seq_len - 1:
+        raise _error(f"teacher-forced positions {n} must lie in 0 .. {seq_len - 1}")
+    plan, at = [], min(n)
+    for n_g in sorted(set(n)):
+        if n_g > at:
+            plan.append(("steps", n_g - at))
+            at = n_g
+        if n_g > 0:
+            plan.append(("prefill", n_g, prompt_rows([b for b in range(B) if n[b] == n_g], B, cfg, num_candidates)))
+    if seq_len - 1 > at:
+        plan.append(("steps", seq_len - 1 - at))
+    return plan
+
+
+def prompt_row_steps(prompt_lengths: List[int], first_delay: int, cfg: bool = False, num_candidates: int = 1) -> List[int]:
+    """n_r of every decoder row (``vaura_decoder_ext3.row_prompt_steps``): the clip's P_b + ``first_delay``, per candidate, then once more
+    for the null-condition rows."""
+    n = [int(p) + int(first_delay) for p in prompt_lengths for _ in range(int(num_candidates))]
+    return n + n if cfg else n

@@ -92,7 +92,8 @@ static Gemv3Args g3(const void* W, const uint16_t* xp, const float* ss_in, const
 // sliding-window caller, scripts/generate.py:327-365): every GEMV keeps its weight slice in registers and
 // loops over the positions' row blocks, K/V of the whole chunk are rotated/appended first, then each
 // (row, head, position) attends causally over the cache.  No heads, no sampling.
-static int enqueue_prefill_chunk_bf16(const vaura_decoder* d, int p0, int n, hipStream_t s) {
+// row_n != NULL (vaura_prefill_rows): the same launches, except that K / V are appended only to the rows r with row_n[r] == n_sel.
+static int enqueue_prefill_chunk_bf16(const vaura_decoder* d, int p0, int n, hipStream_t s, const int32_t* row_n = nullptr, int n_sel = 0) {
   const vaura_dims& m = d->dims;
   const int D = m.d_model, F = m.ffn_dim;
   int rc = va_launch_embed(d, p0, n, s);
@@ -103,7 +104,7 @@ static int enqueue_prefill_chunk_bf16(const vaura_decoder* d, int p0, int n, hip
     rc = va_launch_gemv3(g3(L.wqkv, d->ws_h_split, d->ws_ss, nullptr, d->ws_qkv, nullptr, nullptr, nullptr, d, 3 * D, n), 3 * D, D,
                          E3_STORE, true, s);
     if (rc) return rc;
-    rc = va_launch_rope_append(d, l, p0, n, s);
+    rc = row_n ? va_launch_rope_append_rows(d, l, p0, n, row_n, n_sel, s) : va_launch_rope_append(d, l, p0, n, s);
     if (rc) return rc;
     rc = va_launch_attention_prefill(d, l, p0, n, s);
     if (rc) return rc;
@@ -133,8 +134,10 @@ static int enqueue_prefill_chunk_heads(const vaura_decoder* d, int p0, int n, fl
 
 // per-clip lengths of a decoder call (vaura_decoder_ext2): 1 <= T_b <= timesteps, 1 <= Tv_b <= n_cond_tokens (step.hip va_check_clip_lengths)
 static int check_clip_lengths(const vaura_decoder* d, hipStream_t s) {
-  const int rc = va_check_clip_lengths(va_clip_timesteps(d), d->batch, 1, d->timesteps, s);
-  return rc ? rc : va_check_clip_lengths(va_clip_cond_tokens(d), d->batch, 1, d->n_cond_tokens, s);
+  int rc = va_check_clip_lengths(va_clip_timesteps(d), d->batch, 1, d->timesteps, s);
+  if (!rc) rc = va_check_clip_lengths(va_clip_cond_tokens(d), d->batch, 1, d->n_cond_tokens, s);
+  // per-clip prompt lengths (vaura_decoder_ext3): 0 <= n_r <= seq_len - 1 for every row
+  return rc ? rc : va_check_clip_lengths(va_row_prompt_steps(d), d->rows, 0, d->seq_len - 1, s);
 }
 
 // per-clip sampling records of a decoder call (vaura_decoder.clip_sampling): refused with probability rows, and with a clip scale > 1
@@ -172,6 +175,7 @@ static VaSampleLaunch sample_launch(const vaura_decoder* d, const vaura_sampling
   if (const vaura_decoder_ext* x = va_decoder_ext(d)) { a.cond_seq = x->logprobs_cond; a.null_seq = x->logprobs_null; }
   a.null_rows = d->rows == 2 * d->batch;
   a.clip_T = va_clip_timesteps(d);
+  a.clip_n = va_row_prompt_steps(d);      // its first `batch` entries are the clips'
   return a;
 }
 
@@ -360,6 +364,7 @@ size_t vaura_struct_size(int which) {
     case 9: return sizeof(vaura_clip_sampling);
     case 10: return sizeof(vaura_decoder_ext);
     case 11: return sizeof(vaura_decoder_ext2);
+    case 13: return sizeof(vaura_decoder_ext3);      // (12 stays unassigned and answers 0)
     default: return 0;
   }
 }
@@ -465,6 +470,22 @@ int vaura_generate_loop(const vaura_decoder* dec, const vaura_sampling* sp, int 
   }
   for (int i = 0; i < n_steps; ++i) {
     rc = enqueue_step(dec, sp, 1, st);
+    if (rc) return rc;
+  }
+  return 0;
+}
+
+int vaura_prefill_rows(const vaura_decoder* dec, int n_prefill, int n_sel, vaura_stream_t s) {
+  int rc = check_decoder(dec);
+  if (rc) return rc;
+  const int32_t* row_n = va_row_prompt_steps(dec);
+  if (!row_n || !dec->ws_h_split || dec->prefill_positions <= 0) return VAURA_ERR_ARG;
+  if (n_sel < 1 || n_sel > dec->seq_len - 1 || n_prefill < 1 || n_prefill > n_sel || n_prefill > dec->max_len) return VAURA_ERR_ARG;
+  hipStream_t st = as_stream(s);
+  if ((rc = check_clip_lengths(dec, st))) return rc;      // every array behind the descriptor, row_prompt_steps among them
+  for (int p0 = 0; p0 < n_prefill; p0 += dec->prefill_positions) {
+    const int n = (n_prefill - p0 < dec->prefill_positions) ? n_prefill - p0 : dec->prefill_positions;
+    rc = enqueue_prefill_chunk_bf16(dec, p0, n, st, row_n, n_sel);
     if (rc) return rc;
   }
   return 0;

@@ -852,6 +852,73 @@ __global__ __launch_bounds__(128) void rope_append_kernel(float* __restrict__ qk
   }
 }
 
+// rope_append_kernel with the K / V append held to one group of rows (vaura_prefill_rows: the prefill pass of the clips whose prompt
+// ends at n_sel, run while the other rows of the batch are somewhere else in their sequences): q is rotated in place for EVERY row
+// (the chunk's attention runs on every row), k / v — and the exponent byte of the scaled e4m3 cache — are stored only where
+// row_n[row] == n_sel; the cache rows of every other row keep their bytes.  On a selected row the bytes are those of
+// rope_append_kernel.  One vector load per workgroup, clamped to nothing: the value only decides whether this row stores.  A copy of the
+// kernel above and not a shared body, for the reason given at embed_clips_kernel (csrc/step.hip).
+template <int HD, int KVT = 0>
+__global__ __launch_bounds__(128) void rope_append_rows_kernel(float* __restrict__ qkv, const float* __restrict__ rope,
+                                                               float* __restrict__ kcache, float* __restrict__ vcache, int n_head,
+                                                               int max_len, int p0, int rows16, uint8_t* __restrict__ kscale,
+                                                               uint8_t* __restrict__ vscale, const int32_t* __restrict__ row_n,
+                                                               int n_sel) {
+  constexpr int QUADS = HD / 4;
+  const int h = blockIdx.x, row = blockIdx.y, pos = p0 + (int)blockIdx.z, tid = threadIdx.x;
+  if constexpr (KVT != 3) {
+    if (tid >= 3 * QUADS) return;
+  }
+  int lane0 = 0;
+  asm volatile("" : "+v"(lane0));
+  const bool sel = __builtin_amdgcn_readfirstlane(row_n[row + lane0]) == n_sel;      // uniform over the workgroup
+  const int D = n_head * HD;
+  const int vrow = (int)blockIdx.z * rows16 + row;
+  const int gt = KVT == 3 ? min(tid, 3 * QUADS - 1) : tid;      // KVT = 3: every thread reaches the barrier below (the spare ones redo the last quad, store nothing)
+  const int which = gt / QUADS, cq = gt % QUADS;
+  const int col = which * D + h * HD + cq * 4;
+  f32x4* src = reinterpret_cast<f32x4*>(qkv) + packed_quad(vrow, col >> 2, 3 * D);
+  f32x4 x = *src;
+  if (which < 2) {
+    const f32x4 cs = *reinterpret_cast<const f32x4*>(rope + ((size_t)pos * (HD / 2) + cq * 2) * 2);
+    f32x4 y;
+    y[0] = x[0] * cs[0] - x[1] * cs[1];
+    y[1] = x[1] * cs[0] + x[0] * cs[1];
+    y[2] = x[2] * cs[2] - x[3] * cs[3];
+    y[3] = x[3] * cs[2] + x[2] * cs[3];
+    x = y;
+  }
+  const size_t cbase = (((size_t)row * n_head + h) * (size_t)max_len + pos) * HD;
+  if constexpr (KVT == 3) {      // scaled e4m3: the vector's max |x_c| over its 24 quads through LDS (as attention256_body), same bytes
+    __shared__ uint32_t amx[3 * QUADS];
+    if (tid < 3 * QUADS) amx[tid] = kv_absmax_bits(x);
+    __syncthreads();
+    if (tid >= 3 * QUADS) return;
+    if (which == 0) { *src = x; return; }
+    if (!sel) return;
+    uint32_t a = 0u;
+#pragma unroll
+    for (int i = 0; i < QUADS / 4; ++i) {
+      const uint4 t = reinterpret_cast<const uint4*>(amx + which * QUADS)[i];
+      a = max(max(a, max(t.x, t.y)), max(t.z, t.w));
+    }
+    const uint32_t sb = kv_scale_byte(a);
+    reinterpret_cast<uint32_t*>(reinterpret_cast<uint8_t*>(which == 1 ? kcache : vcache) + cbase)[cq] = kv_quad_to_f8s(x, sb);
+    if (cq == 0) (which == 1 ? kscale : vscale)[cbase / HD] = (uint8_t)sb;
+    return;
+  }
+  if (which == 0) *src = x;
+  if (!sel) return;
+  if constexpr (KVT == 1 || KVT == 2) {
+    using KV = KvT<KVT>;
+    if (which == 1) reinterpret_cast<typename KV::Q*>(reinterpret_cast<typename KV::E*>(kcache) + cbase)[cq] = KV::narrow(x);
+    if (which == 2) reinterpret_cast<typename KV::Q*>(reinterpret_cast<typename KV::E*>(vcache) + cbase)[cq] = KV::narrow(x);
+  } else {
+    if (which == 1) reinterpret_cast<f32x4*>(kcache + cbase)[cq] = x;
+    if (which == 2) reinterpret_cast<f32x4*>(vcache + cbase)[cq] = x;
+  }
+}
+
 // ---------------------------------------------------------------------------------------------------
 // Prefill attention on the matrix cores (round 2): a teacher-forced chunk of n positions (the prompt of the sliding-window
 // caller) attends causally over the cache.  The per-(row, head, position) workgroups of attention_step_kernel's prefill mode
@@ -1046,6 +1113,18 @@ int va_launch_rope_append(const vaura_decoder* d, int layer, int p0, int n_pos, 
   });
 }
 
+int va_launch_rope_append_rows(const vaura_decoder* d, int layer, int p0, int n_pos, const int32_t* row_n, int n_sel, hipStream_t s) {
+  if (!row_n) return VAURA_ERR_ARG;
+  const int H = d->dims.n_head;
+  const VaKvCache kv = va_kv_cache(d, layer);
+  if (int rc = va_kv_check(kv, d->dims.d_model / H, false, false)) return rc;
+  return va_kv_dispatch(kv.dtype, [&](auto kvt) -> int {
+    VA_LAUNCH((rope_append_rows_kernel<96, decltype(kvt)::value>), dim3(H, d->rows, n_pos), dim3(128), 0, s, d->ws_qkv, d->rope, kv.k, kv.v, H, kv.max_len,
+              p0, (d->rows + 15) / 16 * 16, kv.kscale, kv.vscale, row_n, n_sel);
+    return 0;
+  });
+}
+
 extern unsigned va_debug_flags;   // gemv3.hip; bit 4: the per-position prefill attention (A/B of the MFMA kernel)
 int va_launch_attention_prefill(const vaura_decoder* d, int layer, int p0, int n_pos, hipStream_t s) {
   const int H = d->dims.n_head, rows16 = (d->rows + 15) / 16 * 16;
@@ -1125,4 +1204,13 @@ extern "C" int vaura_attention_prefill(const vaura_decoder* d, int layer, int p0
   int rc = va_launch_rope_append(d, layer, p0, n_pos, as_stream(s));
   if (rc) return rc;
   return va_launch_attention_prefill(d, layer, p0, n_pos, as_stream(s));
+}
+
+extern "C" int vaura_rope_append_rows(const vaura_decoder* d, int layer, int p0, int n_pos, const int32_t* row_n, int n_sel, vaura_stream_t s) {
+  if (!d || !row_n || !d->rope || !d->ws_qkv || !d->kcache || !d->vcache) return VAURA_ERR_ARG;
+  if (d->rows <= 0 || d->dims.n_head <= 0 || d->dims.n_layer <= 0 || layer < 0 || layer >= d->dims.n_layer) return VAURA_ERR_ARG;
+  if (d->kv_dtype < 0 || d->kv_dtype > 3) return VAURA_ERR_ARG;
+  if (d->kv_dtype == 3 && (!d->kscale || !d->vscale)) return VAURA_ERR_ARG;
+  if (p0 < 0 || n_pos <= 0 || p0 + n_pos > d->max_len) return VAURA_ERR_ARG;
+  return va_launch_rope_append_rows(d, layer, p0, n_pos, row_n, n_sel, as_stream(s));
 }

@@ -251,15 +251,23 @@ int va_launch_embed(const vaura_decoder* d, int pos_host, int n_pos, hipStream_t
 // the relevance pointers behind a descriptor (vaura_decoder_ext), or NULL when the caller passed a plain vaura_decoder
 inline const vaura_decoder_ext* va_decoder_ext(const vaura_decoder* d) {
   return (d->ext_bytes == (int32_t)(sizeof(vaura_decoder_ext) - sizeof(vaura_decoder)) ||
-          d->ext_bytes == (int32_t)(sizeof(vaura_decoder_ext2) - sizeof(vaura_decoder)))
+          d->ext_bytes == (int32_t)(sizeof(vaura_decoder_ext2) - sizeof(vaura_decoder)) ||
+          d->ext_bytes == (int32_t)(sizeof(vaura_decoder_ext3) - sizeof(vaura_decoder)))
              ? reinterpret_cast<const vaura_decoder_ext*>(d) : nullptr;
 }
 // the per-clip lengths behind those (vaura_decoder_ext2), or NULL
 inline const vaura_decoder_ext2* va_decoder_ext2(const vaura_decoder* d) {
-  return d->ext_bytes == (int32_t)(sizeof(vaura_decoder_ext2) - sizeof(vaura_decoder)) ? reinterpret_cast<const vaura_decoder_ext2*>(d) : nullptr;
+  return (d->ext_bytes == (int32_t)(sizeof(vaura_decoder_ext2) - sizeof(vaura_decoder)) ||
+          d->ext_bytes == (int32_t)(sizeof(vaura_decoder_ext3) - sizeof(vaura_decoder)))
+             ? reinterpret_cast<const vaura_decoder_ext2*>(d) : nullptr;
 }
 inline const int32_t* va_clip_timesteps(const vaura_decoder* d) { const vaura_decoder_ext2* x = va_decoder_ext2(d); return x ? x->clip_timesteps : nullptr; }
 inline const int32_t* va_clip_cond_tokens(const vaura_decoder* d) { const vaura_decoder_ext2* x = va_decoder_ext2(d); return x ? x->clip_cond_tokens : nullptr; }
+// the per-clip prompt lengths behind those (vaura_decoder_ext3): n_r of every row, or NULL
+inline const int32_t* va_row_prompt_steps(const vaura_decoder* d) {
+  return d->ext_bytes == (int32_t)(sizeof(vaura_decoder_ext3) - sizeof(vaura_decoder))
+             ? reinterpret_cast<const vaura_decoder_ext3*>(d)->row_prompt_steps : nullptr;
+}
 struct VaSampleLaunch {              // one sampler launch over (B, K) rows of logits
   const float* logits = nullptr;
   int B = 0, K = 0, vocab = 0;
@@ -277,6 +285,7 @@ struct VaSampleLaunch {              // one sampler launch over (B, K) rows of l
   float *cond_out = nullptr, *cond_seq = nullptr, *null_out = nullptr, *null_seq = nullptr;
   bool null_rows = false;
   const int32_t* clip_T = nullptr;        // per-clip timesteps T_b (vaura_decoder_ext2.clip_timesteps) or NULL: every clip has T
+  const int32_t* clip_n = nullptr;        // per-clip first sampled positions n_b (vaura_decoder_ext3.row_prompt_steps) or NULL: the loop's step
 };
 int va_launch_sample(const VaSampleLaunch& a, hipStream_t s);
 int va_check_clip_sampling(const vaura_sampling* sp, const vaura_clip_sampling* clips, int B, bool doubled, hipStream_t s);
@@ -286,6 +295,8 @@ int va_launch_advance(int32_t* state, int set_to, hipStream_t s);
 int va_launch_linear_pair(const uint16_t* in, const uint16_t* w, const float* bias, const float* res, float* out_raw,
                           uint16_t* out_act, int act, int B, int Lin, int Lout, int oshift, int Cin, int Cout, hipStream_t s);
 int va_launch_rope_append(const vaura_decoder* d, int layer, int p0, int n_pos, hipStream_t s);
+// the same with the K / V append held to the rows r with row_n[r] == n_sel (vaura_prefill_rows)
+int va_launch_rope_append_rows(const vaura_decoder* d, int layer, int p0, int n_pos, const int32_t* row_n, int n_sel, hipStream_t s);
 int va_launch_attention_prefill(const vaura_decoder* d, int layer, int p0, int n_pos, hipStream_t s);
 // teacher-forced scoring (score.hip); clip_T: per-clip timesteps (vaura_decoder_ext2.clip_timesteps) or NULL: every clip has Ta
 int va_launch_score_nll(const float* logits, int rows_per_pos, int p0, int n_pos, int B, int K, int V, int Ta, const int32_t* delays_host,

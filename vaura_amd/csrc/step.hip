@@ -303,8 +303,22 @@ struct SampleRelevance {
 struct SampleLengths {
   const int32_t* T;   // (B) timesteps of every clip, 1 .. a.T (checked on the host; a larger value only keeps slots valid that a.S bounds anyway)
 };
+// The per-clip first sampled POSITIONS of an instance (vaura_decoder_ext3.row_prompt_steps): one more member of the pack, always its
+// last — told by its type, like the lengths: the twelve instances without it keep their symbols, argument lists and instruction
+// streams.  With it the workgroup of clip b keys its Philox counter by pos - n[b], the step index the call with that clip's prompt
+// alone has at this position, instead of the loop's step; an explicit noise tensor and the near-tie detector's "first flagged step"
+// keep the loop's step.  One vector load per workgroup, for the reason given at PC.
+struct SampleStarts {
+  const int32_t* n;   // (B) position of every clip's first sampled step, 0 .. a.S - 1 (checked on the host; the value only enters the counter)
+};
 template <typename T, typename... R>
 __device__ __forceinline__ T va_first(T t, R...) { return t; }
+// the member of a pack that has type W (instances with SampleStarts: the lengths are no longer the last member)
+template <typename W, typename T, typename... R>
+__device__ __forceinline__ W va_pick(T t, R... r) {
+  if constexpr (std::is_same<T, W>::value) return t;
+  else return va_pick<W>(r...);
+}
 template <typename T>
 __device__ __forceinline__ T va_last(T t) { return t; }
 template <typename T, typename... R>
@@ -324,8 +338,9 @@ __global__ __launch_bounds__(SMP_THREADS) void sample_kernel(const float* __rest
                                                              SampleArgs a, const int32_t* __restrict__ clips, LpArgs... lp_args) {
   constexpr bool REL = (std::is_same<LpArgs, SampleRelevance>::value || ...);      // mode 2
   constexpr bool CL = (std::is_same<LpArgs, SampleLengths>::value || ...);         // per-clip lengths
-  static_assert(sizeof...(LpArgs) == (LP ? 1 : 0) + (CL ? 1 : 0),
-                "LP instances take one SampleLogprobs / SampleRelevance, the others nothing; SampleLengths follows where the clips have lengths");
+  constexpr bool ST = (std::is_same<LpArgs, SampleStarts>::value || ...);          // per-clip first sampled positions
+  static_assert(sizeof...(LpArgs) == (LP ? 1 : 0) + (CL ? 1 : 0) + (ST ? 1 : 0),
+                "LP instances take one SampleLogprobs / SampleRelevance, the others nothing; SampleLengths follows where the clips have lengths, SampleStarts last");
   [[maybe_unused]] float* lp_out = nullptr;
   [[maybe_unused]] float* lp_seq = nullptr;
   if constexpr (LP) { lp_out = va_first(lp_args...).out; lp_seq = va_first(lp_args...).seq; }
@@ -367,7 +382,14 @@ __global__ __launch_bounds__(SMP_THREADS) void sample_kernel(const float* __rest
   if constexpr (CL) {      // this clip's timesteps: everything below reads them through `a`, like the per-clip parameters
     int lane0 = 0;
     asm volatile("" : "+v"(lane0));
-    a.T = __builtin_amdgcn_readfirstlane(va_last(lp_args...).T[b + lane0]);
+    if constexpr (ST) a.T = __builtin_amdgcn_readfirstlane(va_pick<SampleLengths>(lp_args...).T[b + lane0]);
+    else a.T = __builtin_amdgcn_readfirstlane(va_last(lp_args...).T[b + lane0]);
+  }
+  [[maybe_unused]] long long cstep = 0;      // ST only: this clip's own step index, the Philox counter's
+  if constexpr (ST) {
+    int lane0 = 0;
+    asm volatile("" : "+v"(lane0));
+    cstep = (long long)pos - (long long)__builtin_amdgcn_readfirstlane(va_last(lp_args...).n[b + lane0]);
   }
   float x[4] = {lc[0], lc[1], lc[2], lc[3]};
   // near-tie detector: magnitude of the rows this decision is made from (both branches, before the mix)
@@ -461,7 +483,7 @@ __global__ __launch_bounds__(SMP_THREADS) void sample_kernel(const float* __rest
     } else {
       uint32_t r[4];
       const uint64_t clip = a.clip_base + (uint64_t)b;
-      philox4x32_10((uint32_t)tid, (uint32_t)step, (uint32_t)(clip * (uint64_t)a.K + k), (uint32_t)((clip * a.K + k) >> 32),
+      philox4x32_10((uint32_t)tid, ST ? (uint32_t)cstep : (uint32_t)step, (uint32_t)(clip * (uint64_t)a.K + k), (uint32_t)((clip * a.K + k) >> 32),
                     (uint32_t)a.seed, (uint32_t)(a.seed >> 32), r);
 #pragma unroll
       for (int j = 0; j < 4; ++j) q[j] = -logf(((float)r[j] + 0.5f) * 2.3283064365386963e-10f);
@@ -806,6 +828,44 @@ int va_launch_sample(const VaSampleLaunch& l, hipStream_t s) {
   a.probs_in = sp->input_is_probs;
   a.tie_eps = sp->tie_eps > 0.f ? sp->tie_eps : 0.f;
   const int32_t* rec = reinterpret_cast<const int32_t*>(l.clips);
+  if (l.clip_n) {      // per-clip first sampled positions: SampleStarts behind the pack, with or without the lengths in front of it
+    if (!l.seq || !l.state) return VAURA_ERR_ARG;   // the counter step is position - n_b: the position lives in the state
+    const SampleStarts cs{l.clip_n};
+    const SampleLengths cl{l.clip_T};
+    const dim3 grid(K, B), block(SMP_THREADS);
+    const SampleRelevance r{l.lp_out, l.lp_seq, l.cond_out, l.cond_seq, l.null_out, l.null_seq};
+    const SampleLogprobs q{l.lp_out, l.lp_seq};
+    if (l.clip_T) {
+      if (rel) {
+        const auto k0 = sample_kernel<false, true, SampleRelevance, SampleLengths, SampleStarts>, k1 = sample_kernel<true, true, SampleRelevance, SampleLengths, SampleStarts>;
+        if (l.clips) VA_LAUNCH(k1, grid, block, 0, s, a.logits, a.state, a, rec, r, cl, cs);
+        else VA_LAUNCH(k0, grid, block, 0, s, a.logits, a.state, a, rec, r, cl, cs);
+      } else if (lp) {
+        const auto k0 = sample_kernel<false, true, SampleLogprobs, SampleLengths, SampleStarts>, k1 = sample_kernel<true, true, SampleLogprobs, SampleLengths, SampleStarts>;
+        if (l.clips) VA_LAUNCH(k1, grid, block, 0, s, a.logits, a.state, a, rec, q, cl, cs);
+        else VA_LAUNCH(k0, grid, block, 0, s, a.logits, a.state, a, rec, q, cl, cs);
+      } else {
+        const auto k0 = sample_kernel<false, false, SampleLengths, SampleStarts>, k1 = sample_kernel<true, false, SampleLengths, SampleStarts>;
+        if (l.clips) VA_LAUNCH(k1, grid, block, 0, s, a.logits, a.state, a, rec, cl, cs);
+        else VA_LAUNCH(k0, grid, block, 0, s, a.logits, a.state, a, rec, cl, cs);
+      }
+      return 0;
+    }
+    if (rel) {
+      const auto k0 = sample_kernel<false, true, SampleRelevance, SampleStarts>, k1 = sample_kernel<true, true, SampleRelevance, SampleStarts>;
+      if (l.clips) VA_LAUNCH(k1, grid, block, 0, s, a.logits, a.state, a, rec, r, cs);
+      else VA_LAUNCH(k0, grid, block, 0, s, a.logits, a.state, a, rec, r, cs);
+    } else if (lp) {
+      const auto k0 = sample_kernel<false, true, SampleLogprobs, SampleStarts>, k1 = sample_kernel<true, true, SampleLogprobs, SampleStarts>;
+      if (l.clips) VA_LAUNCH(k1, grid, block, 0, s, a.logits, a.state, a, rec, q, cs);
+      else VA_LAUNCH(k0, grid, block, 0, s, a.logits, a.state, a, rec, q, cs);
+    } else {
+      const auto k0 = sample_kernel<false, false, SampleStarts>, k1 = sample_kernel<true, false, SampleStarts>;
+      if (l.clips) VA_LAUNCH(k1, grid, block, 0, s, a.logits, a.state, a, rec, cs);
+      else VA_LAUNCH(k0, grid, block, 0, s, a.logits, a.state, a, rec, cs);
+    }
+    return 0;
+  }
   if (l.clip_T) {      // per-clip lengths: the same six instances with SampleLengths behind their pack
     if (!l.seq) return VAURA_ERR_ARG;               // lengths decide the validity of sequence slots: nothing to decide without a sequence
     const SampleLengths cl{l.clip_T};
@@ -1032,6 +1092,29 @@ __global__ __launch_bounds__(1024) void sequence_logprob_clips_kernel(const floa
   if (lane == 0) per_codebook[(size_t)b * K + q] = (tot != tot) ? tot : means[q];
   if (threadIdx.x == 0) per_clip[b] = tot;
 }
+// The same with a per-clip first frame (vaura_sequence_logprob_starts: per-clip prompt lengths): the means of clip b run over frames
+// [clip_t0[b], T_b), T_b = clip_T[b] or T where clip_T is NULL — the launch with t0 = clip_t0[b] (a copy, like the kernel above).
+__global__ __launch_bounds__(1024) void sequence_logprob_starts_kernel(const float* __restrict__ lp, int B, int K, int T, int S,
+                                                                 const int32_t* __restrict__ clip_t0, PatternDelays pd,
+                                                                 float* __restrict__ per_codebook, float* __restrict__ per_clip,
+                                                                 const int32_t* __restrict__ clip_T) {
+  __shared__ float means[16];
+  const int lane = threadIdx.x & 63, q = threadIdx.x >> 6, b = blockIdx.x;
+  if (clip_T) T = clip_T[b];
+  const int t0 = clip_t0[b];
+  const int dq = pattern_delay(pd, q);
+  const float* row = lp + ((size_t)b * K + q) * S + 1 + dq;
+  float acc = 0.f;
+  for (int t = t0 + lane; t < T; t += 64) acc += (t + 1 + dq < S) ? row[t] : 0.f;
+  acc = wave_sum(acc);
+  if (lane == 0) means[q] = acc / (float)(T - t0);
+  __syncthreads();
+  float tot = 0.f;
+  for (int j = 0; j < K; ++j) tot += means[j];
+  tot = tot / (float)K;
+  if (lane == 0) per_codebook[(size_t)b * K + q] = (tot != tot) ? tot : means[q];
+  if (threadIdx.x == 0) per_clip[b] = tot;
+}
 
 // Best-of-N: one workgroup per clip picks the candidate with the largest score — the first index wins a tie, a NaN never beats a
 // number, candidate 0 when every score is NaN — and copies its (K, T) codes.
@@ -1197,6 +1280,54 @@ int vaura_sample_seq(const float* logits, int B, int K, int vocab, const vaura_s
   a.seq = seq; a.T = T; a.S = S; a.state = state; a.delays_host = delays_host; a.clip_T = clip_timesteps;
   a.lp_seq = lp_seq; a.cond_seq = cond_seq; a.null_seq = null_seq; a.null_rows = sp->cfg_scale > 1.0f;
   return va_launch_sample(a, as_stream(s));
+}
+
+int vaura_sample_seq_starts(const float* logits, int B, int K, int vocab, const vaura_sampling* sp, const vaura_clip_sampling* clips,
+                            const float* noise, int32_t* seq, int T, int S, int32_t* state, const int32_t* delays_host,
+                            const int32_t* clip_timesteps, const int32_t* clip_first_steps, float* lp_seq, float* cond_seq,
+                            float* null_seq, vaura_stream_t s) {
+  if (!logits || !sp || !seq || !state || !clip_first_steps || B <= 0 || K <= 0 || T <= 0 || S <= 0) return VAURA_ERR_ARG;
+  if (sp->input_is_probs && (clips || lp_seq || cond_seq || null_seq)) return VAURA_ERR_ARG;
+  if (!cond_seq != !null_seq) return VAURA_ERR_ARG;
+  if (delays_host) {
+    PatternDelays pd;
+    const int span = pattern_delays_arg(delays_host, K, &pd);
+    if (span < 0) return span;
+  }
+  int rc = va_check_clip_sampling(sp, clips, B, sp->cfg_scale > 1.0f, as_stream(s));
+  if (!rc) rc = va_check_clip_lengths(clip_timesteps, B, 1, T, as_stream(s));
+  if (!rc) rc = va_check_clip_lengths(clip_first_steps, B, 0, S - 1, as_stream(s));
+  if (rc) return rc;
+  VaSampleLaunch a;
+  a.logits = logits; a.B = B; a.K = K; a.vocab = vocab; a.sp = sp; a.clips = clips; a.noise = noise;
+  a.seq = seq; a.T = T; a.S = S; a.state = state; a.delays_host = delays_host; a.clip_T = clip_timesteps; a.clip_n = clip_first_steps;
+  a.lp_seq = lp_seq; a.cond_seq = cond_seq; a.null_seq = null_seq; a.null_rows = sp->cfg_scale > 1.0f;
+  return va_launch_sample(a, as_stream(s));
+}
+
+int vaura_sequence_logprob_starts(const float* logprobs, int seq_len, const int32_t* delays_host, int B, int K, int T,
+                                  const int32_t* clip_t0, const int32_t* clip_timesteps, float* per_codebook, float* per_clip,
+                                  vaura_stream_t s) {
+  if (!logprobs || !clip_t0 || !per_codebook || !per_clip || B <= 0 || K <= 0 || T <= 0 || seq_len <= 0) return VAURA_ERR_ARG;
+  if (K > 16) return VAURA_ERR_SHAPE;
+  PatternDelays pd;
+  const int span = pattern_delays_arg(delays_host, K, &pd);
+  if (span < 0) return span;
+  if (seq_len != T + span) return VAURA_ERR_SHAPE;
+  if (((uintptr_t)clip_t0 & 3u) != 0 || ((uintptr_t)clip_timesteps & 3u) != 0) return VAURA_ERR_ARG;
+  // both arrays are read back (one small copy each + a wait on the stream): 1 <= T_b <= T and 0 <= t0_b < T_b, every clip has a frame
+  // behind its prompt
+  std::vector<int32_t> t0((size_t)B), tb((size_t)B, T);
+  hipError_t e = hipMemcpyAsync(t0.data(), clip_t0, t0.size() * sizeof(int32_t), hipMemcpyDeviceToHost, as_stream(s));
+  if (e == hipSuccess && clip_timesteps)
+    e = hipMemcpyAsync(tb.data(), clip_timesteps, tb.size() * sizeof(int32_t), hipMemcpyDeviceToHost, as_stream(s));
+  if (e == hipSuccess) e = hipStreamSynchronize(as_stream(s));
+  if (e != hipSuccess) return (int)e;
+  for (int b = 0; b < B; ++b)
+    if (tb[b] < 1 || tb[b] > T || t0[b] < 0 || t0[b] >= tb[b]) return VAURA_ERR_ARG;
+  VA_LAUNCH(sequence_logprob_starts_kernel, dim3((unsigned)B), dim3(64 * K), 0, as_stream(s), logprobs, B, K, T, seq_len, clip_t0, pd,
+            per_codebook, per_clip, clip_timesteps);
+  return 0;
 }
 
 int vaura_select_candidates(const float* scores, const int32_t* codes, int B, int N, int K, int T, int32_t* codes_out, int32_t* winner,

@@ -126,7 +126,8 @@ def shard(total: int, rank: int, world: int) -> Tuple[int, int]:
 
 def shard_params(params: dict, total: int, rank: int, world: int) -> dict:
     """The per-clip arguments (``use_sampling``, ``temp``, ``top_k``, ``top_p``, ``cfg_scale``, and the lengths ``max_new_tokens`` /
-    ``video_lengths``, and the sliding window's ``durations`` / ``segments``; other keys pass through) of the clips
+    ``video_lengths``, the prompt lengths ``prompt_lengths`` / ``audio_lengths``, and the sliding window's ``durations`` / ``segments``;
+    other keys pass through) of the clips
     ``shard(total, rank, world)`` gives this rank: per-clip sequences are cut by the same contiguous split, scalars are kept.  With
     ``clip_base`` = the rank's first clip, a per-clip call then gives the same tokens for every world size, as scalar calls do."""
     from . import clip_params
@@ -140,7 +141,7 @@ def shard_params(params: dict, total: int, rank: int, world: int) -> dict:
         if v is not None and (not clip_params.is_per_clip(v) or len(v) != total):
             raise clip_params._error(f"{k} has {len(v) if clip_params.is_per_clip(v) else 'no per-clip'} values for a batch of {total} clips")
     first, count = shard(total, rank, world)
-    cut = clip_params.NAMES + ("max_new_tokens", "video_lengths", "durations", "segments")
+    cut = clip_params.NAMES + ("max_new_tokens", "video_lengths", "durations", "segments", "prompt_lengths", "audio_lengths")
     return {k: (clip_params.take(v, first, count) if k in cut else v) for k, v in params.items()}
 
 

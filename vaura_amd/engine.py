@@ -363,11 +363,17 @@ class DecoderEngine:
             # captured step graph hold the POINTERS, _set_lengths() rewrites the values
             self.clip_T = torch.zeros(batch, dtype=torch.int32, device=self.dev)
             self.clip_Tv = torch.zeros(batch, dtype=torch.int32, device=self.dev)
+            # per-clip prompt lengths (vaura_decoder_ext3): n_r = P_b + delays[0] of every row, and P_b of every clip (the first frame
+            # of its means).  Engine-owned for the same reason: _set_prompt_lengths() rewrites the values
+            self.row_n = torch.zeros(rows, dtype=torch.int32, device=self.dev)
+            self.clip_P = torch.zeros(batch, dtype=torch.int32, device=self.dev)
         self.lengths = self.video_lengths = None      # the host lists of the call being run (None: every clip has T / Tv)
-        self.dec_ext2 = L.DecoderExt2()    # the descriptor + the relevance pointers + the per-clip lengths behind it (all NULL: the descriptor alone)
-        self.dec_ext = self.dec_ext2.ext   # views: byref(self.dec) points into dec_ext2
+        self.prompt_lengths = None                    # likewise: P of every clip of the batch (None: one prompt length for the call)
+        self.dec_ext3 = L.DecoderExt3()    # the descriptor + the relevance pointers + the per-clip lengths + the prompt lengths behind it (all NULL: the descriptor alone)
+        self.dec_ext2 = self.dec_ext3.ext2
+        self.dec_ext = self.dec_ext2.ext   # views: byref(self.dec) points into dec_ext3
         d = self.dec_ext.dec
-        d.ext_bytes = C.sizeof(L.DecoderExt2) - C.sizeof(L.Decoder)
+        d.ext_bytes = C.sizeof(L.DecoderExt3) - C.sizeof(L.Decoder)
         d.dims = self.dims
         d.dims.tokens_per_frame = tokens_per_frame
         d.wdtype, d.batch, d.rows, d.max_len = self.wd, batch, rows, max_len
@@ -496,16 +502,35 @@ class DecoderEngine:
             setattr(self.dec_ext2, name, L.ptr(buf) if vals is not None else 0)
         self.lengths = None if lengths is None else list(lengths)
         self.video_lengths = None if video_lengths is None else list(video_lengths)
+        self._set_prompt_lengths(None)     # a call has per-clip prompt lengths only where it says so right after this (generate_codes)
+
+    def _set_prompt_lengths(self, prompt_lengths: Optional[Sequence[int]]):
+        """The per-clip prompt lengths of the call about to run (one int per clip of the prepared batch, candidates repeated; already
+        checked by ``clip_params.resolve_prompt_lengths``; None: one prompt length for the whole call): n_r of every row and P_b of
+        every clip go into the engine-owned device arrays on the current stream, and the descriptor points at the first or holds NULL."""
+        if prompt_lengths is not None:
+            assert len(prompt_lengths) == self.batch
+            d0 = self.delays[0] if self.delays else 0
+            self.row_n.copy_(torch.tensor(clip_params.prompt_row_steps(prompt_lengths, d0, self.rows == 2 * self.batch), dtype=torch.int32))
+            self.clip_P.copy_(torch.tensor(list(prompt_lengths), dtype=torch.int32))
+        self.dec_ext3.row_prompt_steps = L.ptr(self.row_n) if prompt_lengths is not None else 0
+        self.prompt_lengths = None if prompt_lengths is None else list(prompt_lengths)
 
     def _delays_arg(self):
         return L.delays_host(self.delays) if self.delays is not None else None
 
     def start_sequence(self, prompt: Optional[torch.Tensor]):
-        """codes = -1 everywhere but the prompt -> pattern sequence on device; returns Tp."""
+        """codes = -1 everywhere but the prompt -> pattern sequence on device; returns Tp.  With per-clip prompt lengths
+        (``_set_prompt_lengths``) clip b takes ``prompt[b, :, :P_b]`` and holds -1 behind it; Tp is then the shortest prompt."""
         K, T = self.cfg.num_codebooks, self.T
         self.codes_i32.fill_(-1)
         Tp = 0
-        if prompt is not None and prompt.shape[-1] > 0:
+        if self.prompt_lengths is not None:
+            Pm = prompt.shape[-1]
+            real = torch.arange(Pm, device=self.dev)[None, None, :] < self.clip_P.to(torch.int64)[:, None, None]
+            self.codes_i32[..., :Pm] = torch.where(real, prompt.to(self.dev, torch.int32), self.codes_i32[..., :Pm])
+            Tp = min(self.prompt_lengths)
+        elif prompt is not None and prompt.shape[-1] > 0:
             Tp = prompt.shape[-1]
             assert Tp < (min(self.lengths) if self.lengths else T), "gt audio prompt can not be longer than max_new_tokens"
             self.codes_i32[..., :Tp] = prompt.to(self.dev, torch.int32)
@@ -524,13 +549,31 @@ class DecoderEngine:
         return Tp
 
     def run(self, n_prefill: int, n_steps: int, sp: L.Sampling, noise: Optional[torch.Tensor] = None,
-            use_graph: bool = True):
+            use_graph: bool = True, plan: Optional[list] = None):
         """Enqueue `n_prefill` teacher-forced positions and `n_steps` sampled ones (asynchronous).
         With `use_graph` one decode step is captured once into a hipGraph and replayed per step; HIP
         cannot capture on the legacy default stream, so the loop then runs on a private stream that is
-        ordered after / before the caller's current stream."""
+        ordered after / before the caller's current stream.
+        ``plan`` (per-clip prompt lengths, ``clip_params.prompt_schedule``; `n_prefill` / `n_steps` are then not read): its steps run
+        through the same loop — one captured graph for all of them —, the first group's prefill is that loop's own, and every later
+        group's pass is ``vaura_prefill_rows`` between two loops, on the plane storages; the tile storages need none (their prefill
+        is the decode step without sampling, so the steps the rows were carried through already left the K / V of the scalar call)."""
         self.dec.noise = L.ptr(noise)
         self._noise_keepalive = noise
+        calls = [("loop", n_prefill, n_steps)]
+        if plan is not None:
+            calls, first = [], 0
+            for i, e in enumerate(plan):
+                if e[0] == "steps":
+                    calls.append(("loop", first, e[1]))
+                    first = 0
+                elif i == 0:
+                    first = e[1]               # group 1: the existing prefill, with the loop's n_prefill
+                elif self._prefill_positions:
+                    calls.append(("rows", e[1]))
+            if first:                          # (a plan without steps: cannot happen for P_b < T_b, kept whole anyway)
+                calls.append(("loop", first, 0))
+            n_steps = sum(c[2] for c in calls if c[0] == "loop")
         use_graph = bool(use_graph and n_steps > 0)
         with (off_null_stream(self.dev) if use_graph else contextlib.nullcontext()):
             st = L.current_stream(self.dev)
@@ -539,15 +582,21 @@ class DecoderEngine:
                 key = (self._shape, L.ptr(noise), bytes(sp), int(self.dec.clip_sampling or 0), int(self.dec.logprobs or 0),
                        int(self.dec_ext.logprobs_cond or 0), int(self.dec_ext.logprobs_null or 0),
                        # per-clip lengths: the POINTERS (engine-owned arrays, rewritten per call) — other lengths replay the same graph
-                       int(self.dec_ext2.clip_timesteps or 0), int(self.dec_ext2.clip_cond_tokens or 0))
+                       int(self.dec_ext2.clip_timesteps or 0), int(self.dec_ext2.clip_cond_tokens or 0),
+                       # per-clip prompt lengths: the POINTER as well
+                       int(self.dec_ext3.row_prompt_steps or 0))
                 if self._graph_key != key:       # the captured step is tied to these buffers / parameters
                     self._free_graph()
                     handle = C.c_void_p()
                     L.check(self.lib.vaura_step_graph_build(C.byref(self.dec), C.byref(sp), st, C.byref(handle)),
                             "vaura_step_graph_build")
                     self._graph, self._graph_key = handle, key
-            L.check(self.lib.vaura_generate_loop(C.byref(self.dec), C.byref(sp), n_prefill, n_steps,
-                                                 self._graph if use_graph else None, st), "vaura_generate_loop")
+            for c in calls:
+                if c[0] == "rows":
+                    L.check(self.lib.vaura_prefill_rows(C.byref(self.dec), c[1], c[1], st), "vaura_prefill_rows")
+                else:
+                    L.check(self.lib.vaura_generate_loop(C.byref(self.dec), C.byref(sp), c[1], c[2],
+                                                         self._graph if (use_graph and c[2] > 0) else None, st), "vaura_generate_loop")
 
     def _free_graph(self):
         if getattr(self, "_graph", None):
@@ -649,7 +698,7 @@ class DecoderEngine:
     def generate_codes(self, feats: torch.Tensor, max_new_tokens, *, prompt: Optional[torch.Tensor] = None,
                        use_sampling=False, temp=1.0, top_k=0, top_p=0.0, cfg_scale=1.0, noise=None, seed=0,
                        clip_base=0, use_graph=True, tokens_per_frame=7, delays=None, return_logprobs=False, num_candidates=1,
-                       return_relevance=False, video_lengths=None):
+                       return_relevance=False, video_lengths=None, prompt_lengths=None):
         """The hot loop of generate(): (B, Tv, 768) -> codes (B, K, T) int64 (device).  ``delays``: the codebook delay pattern
         (codebook_patterns.py:374-419; None = 0..K-1, ParallelPatternProvider = all zeros): S = T + max(d) + 1 sequence steps, the
         loop samples steps Tp + 1 + d_0 .. S - 1, and an explicit ``noise`` has S - (Tp + 1 + d_0) steps.
@@ -677,16 +726,27 @@ class DecoderEngine:
         ``empty_video_emb``; what lies in ``feats[b, Tv_b:]`` does not matter).  With Philox noise or greedy decoding clip b's frames
         [0, T_b) — tokens, log-probabilities, relevance, and their means — are the bits of the scalar call at the same batch with
         ``max_new_tokens=T_b`` (and ``feats[:, :Tv_b]``).  A common prompt must be shorter than every T_b.  An explicit ``noise`` is
-        consumed per step of the call, so such a call works but is not comparable with a stand-alone one."""
+        consumed per step of the call, so such a call works but is not comparable with a stand-alone one.
+        ``prompt_lengths``: None, or one int per clip, 0 <= P_b < T_b, on a ``prompt`` (B, K, P_max): only ``prompt[b, :, :P_b]`` is
+        clip b's prompt (what lies behind it is never used).  With Philox noise or greedy decoding clip b's frames [0, T_b) — tokens,
+        log-probabilities, relevance and their means — are the bits of the same call at the same batch with the common prompt
+        ``prompt[..., :P_b]`` (no prompt for P_b = 0), on every storage.  The loop samples from the shortest prompt's end for the whole
+        batch (one captured graph) and, on the plane storages, runs one prefill pass per further distinct length over positions
+        [0, P_b + d_0) just before that group's first sampled step (``clip_params.prompt_schedule``): G distinct lengths cost one loop
+        plus sum_g (P_g + d_0) prefill positions.  Lengths that are all equal are the scalar call with ``prompt[..., :P]``, on its path.
+        An explicit ``noise`` starts at the shortest prompt's first step and is not comparable, as above."""
         B, Tv, _ = feats.shape
         N = num_candidates
         if isinstance(N, bool) or not isinstance(N, int) or N < 1:
             raise L.VauraHipError(f"num_candidates must be an int >= 1, got {N!r}")
         clip_params.check_lengths(B, use_sampling=use_sampling, temp=temp, top_k=top_k, top_p=top_p, cfg_scale=cfg_scale)
         t_max, lengths, tv_lengths = clip_params.resolve_lengths(B, max_new_tokens, video_lengths, Tv,
-                                                                 0 if prompt is None else int(prompt.shape[-1]))
+                                                                 0 if (prompt is None or prompt_lengths is not None) else int(prompt.shape[-1]))
+        P = clip_params.resolve_prompt_lengths(B, prompt_lengths, None if prompt is None else int(prompt.shape[-1]), t_max, lengths)
+        if P is not None and len(set(P)) == 1:      # one length after all: the scalar call with that prompt, on its path
+            prompt, P = (prompt[..., :P[0]] if P[0] else None), None
         if N > 1:                          # candidate j of clip b is row b * N + j: it has clip b's lengths
-            lengths, tv_lengths = (clip_params.repeat(v, N) if v is not None else None for v in (lengths, tv_lengths))
+            lengths, tv_lengths, P = (clip_params.repeat(v, N) if v is not None else None for v in (lengths, tv_lengths, P))
         cfg_on = clip_params.any_cfg(cfg_scale)     # some clip mixes: the whole batch carries the null-condition rows
         if N > 1:
             use_sampling, temp, top_k, top_p, cfg_scale = (clip_params.repeat(v, N) for v in (use_sampling, temp, top_k, top_p, cfg_scale))
@@ -703,9 +763,11 @@ class DecoderEngine:
         with off_null_stream(self.dev) as caller:
             self.prepare(B * N, t_max, Tv, cfg_on, tokens_per_frame, block_size=self.cfg.block_size, delays=delays)
             self._set_lengths(lengths, tv_lengths)
+            self._set_prompt_lengths(P)
             self.set_condition(feats, replicate=N)
-            Tp = self.start_sequence(prompt)
+            Tp = self.start_sequence(prompt)       # per-clip prompt lengths: the shortest — where the loop starts sampling
             start = Tp + 1 + (self.delays[0] if self.delays else 0)  # Pattern.get_first_step_with_timesteps(Tp), sorted delays
+            plan = None if P is None else clip_params.prompt_schedule(P, self.delays[0] if self.delays else 0, self.S, self.rows == 2 * self.batch)
             sp = self._sampling(use_sampling, temp, top_k, top_p, cfg_scale, seed, clip_base)
             if noise is not None:
                 noise = noise.to(self.dev, torch.float32).contiguous()
@@ -721,7 +783,7 @@ class DecoderEngine:
                     self.logprobs_null.zero_()
             self.dec_ext.logprobs_cond = L.ptr(self.logprobs_cond) if return_relevance else 0
             self.dec_ext.logprobs_null = L.ptr(self.logprobs_null) if return_relevance else 0
-            self.run(start - 1, self.S - start, sp, noise, use_graph)
+            self.run(start - 1, self.S - start, sp, noise, use_graph, plan)
             out = self.revert().to(torch.int64)
             extra = self._sequence_logprobs(Tp) if return_logprobs else None
             if return_relevance:
@@ -751,6 +813,11 @@ class DecoderEngine:
         f32 = dict(dtype=torch.float32, device=self.dev)
         pcb, score = torch.empty(Bn, K, **f32), torch.empty(Bn, **f32)
         dl = L.delays_host(self.delays) if self.delays is not None else None
+        if self.prompt_lengths is not None:       # every clip's means over its own frames P_b .. T_b - 1
+            L.check(self.lib.vaura_sequence_logprob_starts(L.ptr(buf), self.S, dl, Bn, K, T, L.ptr(self.clip_P),
+                                                           L.ptr(self.clip_T) if self.lengths is not None else None, L.ptr(pcb), L.ptr(score),
+                                                           L.current_stream(self.dev)), "vaura_sequence_logprob_starts")
+            return pcb, score
         if self.lengths is not None:       # every clip's means over its own frames Tp .. T_b - 1
             L.check(self.lib.vaura_sequence_logprob_clips(L.ptr(buf), self.S, dl, Bn, K, T, Tp, L.ptr(self.clip_T), L.ptr(pcb), L.ptr(score),
                                                           L.current_stream(self.dev)), "vaura_sequence_logprob_clips")

@@ -279,6 +279,23 @@ class VAURAModel(nn.Module):
                                   "is returned (pointless: it would stream the null-condition rows for no result)")
         return N
 
+    @staticmethod
+    def _check_prompt_lengths(frames, audio, prompt_is_encoded, prompt_lengths, audio_lengths, t_max, lengths) -> None:
+        """The per-clip prompt keywords of generate() / generate_tokens(), checked on the host alone with what is known before any
+        device work (the batch from the frames, an encoded prompt's frames)."""
+        if prompt_lengths is None and audio_lengths is None:
+            return
+        if prompt_lengths is not None and audio_lengths is not None:
+            raise L.VauraHipError("prompt_lengths (frames of an encoded prompt) and audio_lengths (samples of raw audio) both say how long "
+                                  "each clip's prompt is: pass one of them")
+        if audio is None:
+            raise L.VauraHipError("prompt_lengths / audio_lengths needs an audio prompt: it says how much of each clip's prompt is real")
+        if audio_lengths is not None and prompt_is_encoded:
+            raise L.VauraHipError("audio_lengths counts the samples of raw audio; an encoded prompt takes prompt_lengths (frames)")
+        if prompt_lengths is not None:   # an encoded prompt: everything is known; raw audio: its frames are checked once it is encoded
+            clip_params.resolve_prompt_lengths(frames.shape[0] if hasattr(frames, "shape") else None, prompt_lengths,
+                                               int(audio.shape[-1]) if prompt_is_encoded else t_max, t_max, lengths)
+
     @torch.no_grad()
     def generate_tokens(self, frames=None, audio: Union[torch.Tensor, None] = None, clip_indices=None,
                         max_new_tokens: int = 512, return_attention_weights: bool = False,
@@ -286,7 +303,7 @@ class VAURAModel(nn.Module):
                         temp: float = 1.0, top_k: int = 256, top_p: float = 0.0, remove_prompts: bool = False,
                         prompt_is_encoded: bool = False, cfg_scale: float = 1.0, return_logprobs: bool = False,
                         num_candidates: int = 1, return_all_candidates: bool = False, return_relevance: bool = False,
-                        rank_by: str = "logprob", video_lengths=None, video_segments=None):
+                        rank_by: str = "logprob", video_lengths=None, video_segments=None, prompt_lengths=None, audio_lengths=None):
         """generate() up to and including revert_pattern_sequence (vaura_model.py:410-572): (B, K, T') int64 tokens on
         the device, no codec decode.  The sliding-window caller (vaura_amd.longform) uses this for every chunk and
         decodes the concatenated tokens once, as the reference's script does (scripts/generate.py:366-369).
@@ -325,22 +342,35 @@ class VAURAModel(nn.Module):
         ``video_segments``: ``video_lengths`` counted in segments of ``frames`` (dim 1) instead of video tokens — one int per clip,
         1 <= n_b <= S, the leading segments of clip b that are real.  How many tokens a segment gives is known only once the extractor
         has run, so it is turned into ``video_lengths`` = n_b * (Tv // S) from the features' own shape.  It needs the flattened AVCLIP
-        layout (``flatten_vis_feats``) and excludes ``video_lengths``; a call without it takes the path it always took."""
+        layout (``flatten_vis_feats``) and excludes ``video_lengths``; a call without it takes the path it always took.
+        Per-clip prompt lengths: ``prompt_lengths`` = one int per clip, 0 <= P_b < T_b, on an encoded prompt (B, K, P_max) (or on raw audio,
+        counted in the frames its plain encode gives): only the first P_b frames of clip b's prompt are its prompt, what lies behind them
+        is never used.  ``audio_lengths`` = one int per clip for raw ``audio`` (B, 1, N), the real samples of each row (what
+        ``audio_from_pcm(..., lengths=)`` returns): the clips are encoded in one pass, each cut to its own samples, and P_b is the frames
+        the encoder gives clip b.  The two exclude each other.  The result is the dict of the per-clip lengths plus "prompt_lengths"
+        (B,).  With ``noise_mode="philox"`` or greedy decoding clip b's frames [0, T_b) — tokens and every reported value, means taken
+        over frames [P_b, T_b) — are the bits of the same call with the common prompt ``audio[..., :P_b]``: one batched call continues
+        recordings of different lengths (``DecoderEngine.generate_codes``: one decode loop plus, on the plane storages, a prefill pass
+        over P_g + d_0 positions for every further distinct length).  ``noise_mode="torch_cpu"`` works but is not comparable.  With
+        ``remove_prompts`` clip b's frames [P_b, T_b) are left-aligned — "tokens" (B, K, T_max - min P) with the special id behind them,
+        the per-token values with zeros — and "lengths" = T_b - P_b."""
         assert not self.training, "do not use generation in training mode"
         N = self._check_candidates(num_candidates, return_all_candidates, use_sampling, temp, rank_by, return_relevance)   # refused before any device work
         # per-clip parameter sequences of the wrong length: refused here, before any device work (frames carry the batch on dim 0)
         clip_params.check_lengths(frames.shape[0] if hasattr(frames, "shape") else None, use_sampling=use_sampling, temp=temp,
                                   top_k=top_k, top_p=top_p, cfg_scale=cfg_scale)
         # per-clip lengths: resolved and checked here with what is known before any device work (the batch from the frames, an encoded prompt)
+        per_clip_prompt = prompt_lengths is not None or audio_lengths is not None
         t_max, lengths, tv_lengths = clip_params.resolve_lengths(
             frames.shape[0] if hasattr(frames, "shape") else None, max_new_tokens, video_lengths, None,
-            int(audio.shape[-1]) if (audio is not None and prompt_is_encoded) else 0)
+            int(audio.shape[-1]) if (audio is not None and prompt_is_encoded and not per_clip_prompt) else 0)
+        self._check_prompt_lengths(frames, audio, prompt_is_encoded, prompt_lengths, audio_lengths, t_max, lengths)   # refused here, before any device work
         n_segments = None
         if video_segments is not None:       # refused here, before any device work
             n_segments = clip_params.resolve_segments(frames.shape[0] if hasattr(frames, "shape") else None, video_segments, video_lengths,
                                                       frames.shape[1] if hasattr(frames, "shape") and len(frames.shape) > 1 else None,
                                                       self.flatten_vis_feats, lengths)
-        ragged = lengths is not None or tv_lengths is not None or n_segments is not None
+        ragged = lengths is not None or tv_lengths is not None or n_segments is not None or per_clip_prompt
         max_new_tokens = t_max               # the call runs to the longest clip
         if return_attention_weights:
             # the reference's own llama sampler returns (logits, None, None) (llama.py:520-539), so its generate() fails on
@@ -353,10 +383,17 @@ class VAURAModel(nn.Module):
         if delays != list(range(K)) and max_new_tokens + max(delays) + 1 > block:   # (the engine refuses it too, before allocating)
             raise L.VauraHipError(f"{max_new_tokens} timesteps under the delays {delays} need {max_new_tokens + max(delays) + 1} sequence "
                                   f"steps; block_size is {block}")
+        P = None
         if audio is not None and not prompt_is_encoded:
             # vaura_model.py:463-469 encodes the prompt here.  (Its unpacking `cat([encoded[0] for encoded in audio])`
             # expects EnCodec's frame list and breaks on DacModelWrapper's (B, 9, T) tensor; the tensor is used as is.)
-            audio = self.audio_encoder.encode(audio)
+            if audio_lengths is not None:    # one encoder pass over the clips, each cut to its own samples: P_b = the frames it returns
+                audio, P = self._encode_clips(audio, audio_lengths)
+            else:
+                audio = self.audio_encoder.encode(audio)
+        if per_clip_prompt:
+            P = clip_params.resolve_prompt_lengths(frames.shape[0] if hasattr(frames, "shape") else None, P if P is not None else prompt_lengths,
+                                                   int(audio.shape[-1]), t_max, lengths)
         vis = self._handle_visual_conditioning(frames, clip_indices)
         if vis is None:
             # the reference's llama sampler refuses a missing condition itself: `raise Exception("Not implemented")` under
@@ -365,13 +402,17 @@ class VAURAModel(nn.Module):
                                       "(the reference raises here too, llama.py:474-476)")
         B = vis.shape[0]
         Tp = 0 if audio is None else int(audio.shape[-1])
+        if P is not None:                    # again with the batch known; the loop starts sampling behind the shortest prompt
+            P = clip_params.resolve_prompt_lengths(B, P, Tp, t_max, lengths)
+            Tp = min(P)
         assert lengths is not None or Tp < max_new_tokens, "gt audio prompt can not be longer than max_new_tokens"
         if n_segments is not None:           # segments -> video tokens, from the features' own shape
             if int(vis.shape[1]) % int(frames.shape[1]):
                 raise L.VauraHipError(f"video_segments: {int(vis.shape[1])} video tokens are no multiple of the {int(frames.shape[1])} segments")
             tv_lengths = [n * (int(vis.shape[1]) // int(frames.shape[1])) for n in n_segments]
         if ragged:                           # again with the batch, the video tokens and the prompt known: still before the engine is touched
-            _, lengths, tv_lengths = clip_params.resolve_lengths(B, lengths if lengths is not None else t_max, tv_lengths, int(vis.shape[1]), Tp)
+            _, lengths, tv_lengths = clip_params.resolve_lengths(B, lengths if lengths is not None else t_max, tv_lengths, int(vis.shape[1]),
+                                                                 0 if P is not None else Tp)
         use_cfg = clip_params.any_cfg(cfg_scale) and self.sampler.__class__.__name__ == "Transformer"   # any clip's scale > 1
         eng = self.sampler.engine()
         if self.sampler.audio_tokens_per_video_frame is None:
@@ -391,7 +432,8 @@ class VAURAModel(nn.Module):
         if want_rel:
             extra_kw.update(return_relevance=True)
         codes = eng.generate_codes_checked(
-            vis.float(), lengths if lengths is not None else max_new_tokens, prompt=audio if Tp else None, use_sampling=use_sampling, temp=temp,
+            vis.float(), lengths if lengths is not None else max_new_tokens, prompt=audio if (Tp or (P is not None and max(P))) else None,
+            use_sampling=use_sampling, temp=temp, **(dict(prompt_lengths=P) if (P is not None and max(P)) else {}),
             top_k=top_k, top_p=top_p, cfg_scale=cfg_scale if use_cfg else 1.0, noise=noise, seed=self.seed,
             clip_base=self.clip_base, tokens_per_frame=self.sampler.audio_tokens_per_video_frame,
             delays=None if delays == list(range(K)) else delays, **extra_kw,
@@ -428,6 +470,12 @@ class VAURAModel(nn.Module):
         out = {}
         if ragged:
             out["lengths"] = torch.tensor(lengths if lengths is not None else [max_new_tokens] * B, device=codes.device) - lo
+        if P is not None:
+            out["prompt_lengths"] = torch.tensor(P, device=codes.device)
+            if remove_prompts:               # clip b's frames [P_b, T_b) left-aligned; everything below is cut through `cut`
+                out["lengths"] = out["lengths"] + lo - out["prompt_lengths"]
+                return self._finish_without_prompts(out, codes, lp, P, lengths, B, N, K, max_new_tokens, by_rel, return_all_candidates,
+                                                    return_logprobs, return_relevance, eng)
         if N > 1:
             rank = lp["sequence_relevance" if by_rel else "score"]
             out["candidate_indices"] = codes[..., lo:max_new_tokens]
@@ -454,13 +502,56 @@ class VAURAModel(nn.Module):
             out["sequence_relevance"] = lp["sequence_relevance"]
         return out
 
+    def _finish_without_prompts(self, out, codes, lp, P, lengths, B, N, K, T, by_rel, return_all_candidates, return_logprobs,
+                                return_relevance, eng) -> dict:
+        """The result dict of ``generate_tokens(prompt_lengths=..., remove_prompts=True)``: every per-frame entry holds clip b's frames
+        [P_b, T_b) from column 0 on — (rows, K, T - min P) — with the special id (tokens) or zeros (values) behind them."""
+        dev = codes.device
+        width = T - min(P)
+        Tb = lengths if lengths is not None else [T] * B
+
+        def cut(x, fill):
+            n = x.shape[0] // B              # candidates per clip in this tensor
+            first = torch.tensor(clip_params.repeat(P, n), device=dev)[:, None, None]
+            end = torch.tensor(clip_params.repeat(Tb, n), device=dev)[:, None, None]
+            src = torch.arange(width, device=dev)[None, None, :] + first
+            got = torch.gather(x, 2, src.clamp(max=T - 1).expand(-1, x.shape[1], -1))
+            return torch.where(src < end, got, torch.full_like(got, fill))
+        sp = self.special_token_id
+        if N > 1:
+            rank = lp["sequence_relevance" if by_rel else "score"]
+            out["candidate_indices"] = cut(codes[..., :T], sp)
+            out["candidate_scores"] = rank.view(B, N)
+            if not return_all_candidates:
+                c32 = codes.to(torch.int32).contiguous()
+                won = torch.empty(B, K, T, dtype=torch.int32, device=dev)
+                winner = torch.empty(B, dtype=torch.int32, device=dev)
+                L.check(eng.lib.vaura_select_candidates(L.ptr(rank), L.ptr(c32), B, N, K, T, L.ptr(won), L.ptr(winner),
+                                                        L.current_stream(eng.dev)), "vaura_select_candidates")
+                rows = torch.arange(B, device=dev) * N + winner.to(torch.int64)
+                codes = won.to(torch.int64)
+                lp = {k: v[rows] for k, v in lp.items()}
+                out["selected_candidate"] = winner.to(torch.int64)
+        out["tokens"] = cut(codes[..., :T], sp)
+        if return_logprobs:
+            out["logprobs"] = cut(lp["logprobs"][..., :T], 0.0)
+            out["logprob_per_codebook"] = lp["per_codebook"]
+            out["sequence_logprob"] = lp["score"]
+        if return_relevance:
+            for k in ("relevance", "logprob_cond", "logprob_null"):
+                out[k] = cut(lp[k][..., :T], 0.0)
+            out["relevance_per_codebook"] = lp["relevance_per_codebook"]
+            out["sequence_relevance"] = lp["sequence_relevance"]
+        return out
+
     @torch.no_grad()
     def generate(self, frames=None, audio: Union[torch.Tensor, None] = None, clip_indices=None, max_new_tokens: int = 512,
                  return_attention_weights: bool = False, return_sampled_indices: bool = False, check: bool = False,
                  use_sampling: bool = True, temp: float = 1.0, top_k: int = 256, top_p: float = 0.0,
                  remove_prompts: bool = False, prompt_is_encoded: bool = False, cfg_scale: float = 1.0,
                  return_logprobs: bool = False, num_candidates: int = 1, return_all_candidates: bool = False,
-                 return_relevance: bool = False, rank_by: str = "logprob", video_lengths=None) -> dict:
+                 return_relevance: bool = False, rank_by: str = "logprob", video_lengths=None, prompt_lengths=None,
+                 audio_lengths=None) -> dict:
         """``return_logprobs`` / ``num_candidates`` / ``return_all_candidates`` / ``return_relevance`` / ``rank_by``: see ``generate_tokens`` — its extra entries are added
         to the result ("sampled_indices" takes "tokens"); the codec decodes the winners (B clips), or with ``return_all_candidates``
         all B * N takes.  With the defaults the result is the dict it always was.
@@ -468,11 +559,15 @@ class VAURAModel(nn.Module):
         one pass (``decode_clips``: the clips packed into one sequence; clips that all have one length: the plain ``decode``), "generated_audio" is (B, 1, T_max * hop) with zeros past each clip's end, and the result gains
         "lengths" (B,) in frames and "audio_lengths" (B,) in samples.  With an int and no ``video_lengths`` nothing is added.
         The post stage takes that batch in one call: ``post.normalize_audio(r["generated_audio"], ..., lengths=r["audio_lengths"])``,
-        or ``post.scale_batch`` / ``post.save_wavs`` for the per-clip tensors and files."""
+        or ``post.scale_batch`` / ``post.save_wavs`` for the per-clip tensors and files.
+        ``prompt_lengths`` / ``audio_lengths`` (see ``generate_tokens``): per-clip prompt lengths; the result gains "prompt_lengths" (B,) next
+        to "lengths" / "audio_lengths", and with ``remove_prompts`` the codec decodes each clip's own T_b - P_b generated frames."""
         K = self.num_codebooks
         self._check_candidates(num_candidates, return_all_candidates, use_sampling, temp, rank_by, return_relevance)    # before the engine is touched
-        clip_params.resolve_lengths(frames.shape[0] if hasattr(frames, "shape") else None, max_new_tokens, video_lengths, None,
-                                    int(audio.shape[-1]) if (audio is not None and prompt_is_encoded) else 0)           # likewise
+        t_max, lens, _ = clip_params.resolve_lengths(
+            frames.shape[0] if hasattr(frames, "shape") else None, max_new_tokens, video_lengths, None,
+            int(audio.shape[-1]) if (audio is not None and prompt_is_encoded and prompt_lengths is None and audio_lengths is None) else 0)   # likewise
+        self._check_prompt_lengths(frames, audio, prompt_is_encoded, prompt_lengths, audio_lengths, t_max, lens)
         extra = {}
         with off_null_stream(self.sampler.engine().dev) as caller:   # decode loop + codec leave HIP's null stream together
             out_codes = self.generate_tokens(
@@ -481,7 +576,9 @@ class VAURAModel(nn.Module):
                 top_k=top_k, top_p=top_p, remove_prompts=remove_prompts, prompt_is_encoded=prompt_is_encoded,
                 cfg_scale=cfg_scale, return_logprobs=return_logprobs, num_candidates=num_candidates,
                 return_all_candidates=return_all_candidates, return_relevance=return_relevance, rank_by=rank_by,
-                **(dict(video_lengths=video_lengths) if video_lengths is not None else {}))
+                **(dict(video_lengths=video_lengths) if video_lengths is not None else {}),
+                **(dict(prompt_lengths=prompt_lengths) if prompt_lengths is not None else {}),
+                **(dict(audio_lengths=audio_lengths) if audio_lengths is not None else {}))
             if isinstance(out_codes, dict):
                 extra = out_codes
                 out_codes = extra.pop("tokens")
