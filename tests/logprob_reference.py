@@ -1,6 +1,7 @@
 """Pure-Python restatement of what the library does with token log-probabilities after the sampler has written them (csrc/step.hip:
-pattern_revert_f32_kernel, sequence_logprob_kernel, select_candidates_kernel; include/vaura_hip.h vaura_sequence_logprob /
-vaura_select_candidates) — every fp32 operation in the order the kernels perform it, so that GPU results can be compared bit for bit.
+pattern_revert_kernel<float>, sequence_logprob_kernel, select_candidates_kernel; include/vaura_hip.h vaura_pattern_revert_*_f32 /
+vaura_sequence_logprob[_clips | _starts] / vaura_select_candidates: per-clip lengths and first frames are the same functions applied
+to clip b's slice [:, :, :T_b] with t0 = t0_b) — every fp32 operation in the order the kernels perform it, so that GPU results can be compared bit for bit.
 tests/test_logprobs_host.py pins these functions against hand-made cases."""
 import numpy as np
 

@@ -1,6 +1,6 @@
 """Per-clip lengths in one batched call, on the device: vaura_decoder_ext2.clip_timesteps / clip_cond_tokens, the per-clip forms of the
-step's small kernels (csrc/step.hip: sample_kernel<.., SampleLengths>, embed_clips_kernel, pattern_build_clips_kernel,
-pattern_revert_clips_kernel, sequence_logprob_clips_kernel), DecoderEngine.generate_codes(max_new_tokens=[..], video_lengths=[..]) and
+step's small kernels (csrc/step.hip: sample_kernel<.., SampleLengths>, embed_clips_kernel, pattern_build_kernel,
+pattern_revert_kernel, sequence_logprob_kernel with clip_T), DecoderEngine.generate_codes(max_new_tokens=[..], video_lengths=[..]) and
 VAURAModel.generate / generate_tokens on top of them.
 
 The contract is bit equality: clip b of the batched call, over its own frames [0, T_b), is what the scalar call AT THE SAME BATCH with
@@ -18,7 +18,9 @@ import torch
 pytestmark = pytest.mark.gpu
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import logprob_reference as R  # noqa: E402
 import test_gpu_logprobs as G  # noqa: E402  (record / struct helpers, the tiny plugin model)
+import test_gpu_step_dispatch as D  # noqa: E402  (same_f32, the CPU restatement of the pattern ops)
 from oracle import generate_oracle as go  # noqa: E402
 from oracle.decoder_oracle import DecoderOracle  # noqa: E402
 from vaura_amd import _lib as L  # noqa: E402
@@ -70,6 +72,14 @@ def test_op_pattern_build_and_reverts(delays):
     backf = torch.full((B, K, TMAX), -7.0, device=DEV)
     assert lib.vaura_pattern_revert_clips(L.ptr(seq), L.ptr(back), B, K, TMAX, S, -1, V, dl_arg(delays), L.ptr(i32(T)), stream()) == 0
     assert lib.vaura_pattern_revert_clips_f32(L.ptr(seqf), L.ptr(backf), B, K, TMAX, S, 0.0, 0.0, dl_arg(delays), L.ptr(i32(T)), stream()) == 0
+    # against the CPU (the entry points compared below share their kernels with the ones above): the pattern's index maps, and
+    # logprob_reference.revert for the fp32 values
+    assert torch.equal(seq.cpu(), D.ref_build(codes.cpu(), delays, V, T))
+    assert torch.equal(back.cpu(), D.ref_revert(seq.cpu(), delays, TMAX, -1, V, T))
+    wantf = torch.from_numpy(R.revert(seqf.cpu().numpy(), delays, TMAX))
+    for b, Tb in enumerate(T):
+        wantf[b, :, Tb:] = 0.0
+    assert torch.equal(backf.cpu().view(torch.int32), wantf.view(torch.int32))
     for b, Tb in enumerate(T):
         Sb = Tb + span
         cb = codes[b:b + 1, :, :Tb].contiguous()
@@ -96,7 +106,10 @@ def test_op_sequence_means(delays):
     for t0, Tl in ((0, T), (1, [12, 5, 2, 9])):
         pcb, clip = torch.zeros(B, K, device=DEV), torch.zeros(B, device=DEV)
         assert lib.vaura_sequence_logprob_clips(L.ptr(lp), S, dl_arg(delays), B, K, TMAX, t0, L.ptr(i32(Tl)), L.ptr(pcb), L.ptr(clip), stream()) == 0
+        frames = R.revert(lp.cpu().numpy(), delays, TMAX)
         for b, Tb in enumerate(Tl):
+            rp, rc = R.sequence_logprob(frames[b:b + 1, :, :Tb], t0)      # the CPU restatement: the sibling below runs the same kernel
+            assert D.same_f32(pcb[b], rp[0]) and D.same_f32(clip[b:b + 1], rc), (t0, b)
             one = lp[b:b + 1, :, :Tb + span].contiguous()
             wp, wc = torch.zeros(1, K, device=DEV), torch.zeros(1, device=DEV)
             assert lib.vaura_sequence_logprob(L.ptr(one), Tb + span, dl_arg(delays), 1, K, Tb, t0, L.ptr(wp), L.ptr(wc), stream()) == 0

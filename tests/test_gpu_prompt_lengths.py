@@ -1,6 +1,6 @@
 """Per-clip audio prompt lengths in one batched call, on the device: vaura_decoder_ext3.row_prompt_steps, the masked append of the
 group prefill pass (csrc/attention.hip rope_append_rows_kernel, vaura_prefill_rows), the sampler's per-clip counter step (csrc/step.hip
-sample_kernel<.., SampleStarts>), the per-clip first frame of the means (sequence_logprob_starts_kernel),
+sample_kernel<.., SampleStarts>), the per-clip first frame of the means (sequence_logprob_kernel with clip_t0),
 DecoderEngine.generate_codes(prompt_lengths=[..]) and VAURAModel.generate / generate_tokens on top of them.
 
 The contract is bit equality: clip b of the ragged call, over its own frames [0, T_b), is what the same call AT THE SAME BATCH with the
@@ -18,7 +18,9 @@ import torch
 pytestmark = pytest.mark.gpu
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import logprob_reference as R  # noqa: E402
 import test_gpu_logprobs as G  # noqa: E402  (record / struct helpers, the tiny plugin model)
+import test_gpu_step_dispatch as D  # noqa: E402  (same_f32)
 from oracle import generate_oracle as go  # noqa: E402
 from oracle.decoder_oracle import DecoderOracle  # noqa: E402
 from vaura_amd import _lib as L  # noqa: E402
@@ -179,15 +181,20 @@ def test_op_sampler_counter_step_is_the_clips_own(delays, per_clip, lengths):
 
 
 def test_op_sequence_means(delays):
+    """the per-clip first frame against the sibling entry points called with t0 = P_b — the same kernel since the entry points share
+    one —, and against the CPU restatement of clip b's frames [:, :, :T_b] with t0 = P_b"""
     lib, span = L.lib(), max(delays) + 1
     S = TMAX + span
     lp = -torch.rand(B, K, S, generator=torch.Generator().manual_seed(4)).to(DEV)
+    frames = R.revert(lp.cpu().numpy(), delays, TMAX)
     dl = L.delays_host(delays)
     for Tl in (None, TL):
         pcb, clip = torch.zeros(B, K, device=DEV), torch.zeros(B, device=DEV)
         assert lib.vaura_sequence_logprob_starts(L.ptr(lp), S, dl, B, K, TMAX, L.ptr(i32(PL)), L.ptr(i32(Tl)) if Tl else None, L.ptr(pcb),
                                                  L.ptr(clip), stream()) == 0
         for b, t0 in enumerate(PL):
+            rp, rc = R.sequence_logprob(frames[b:b + 1, :, :Tl[b] if Tl else TMAX], t0)
+            assert D.same_f32(pcb[b], rp[0]) and D.same_f32(clip[b:b + 1], rc), (Tl, b)
             wp, wc = torch.zeros(B, K, device=DEV), torch.zeros(B, device=DEV)
             if Tl is None:
                 assert lib.vaura_sequence_logprob(L.ptr(lp), S, dl, B, K, TMAX, t0, L.ptr(wp), L.ptr(wc), stream()) == 0

@@ -313,16 +313,12 @@ struct SampleStarts {
 };
 template <typename T, typename... R>
 __device__ __forceinline__ T va_first(T t, R...) { return t; }
-// the member of a pack that has type W (instances with SampleStarts: the lengths are no longer the last member)
+// the member of a pack that has type W (the lengths and the first positions, wherever they stand behind the reporting member)
 template <typename W, typename T, typename... R>
 __device__ __forceinline__ W va_pick(T t, R... r) {
   if constexpr (std::is_same<T, W>::value) return t;
   else return va_pick<W>(r...);
 }
-template <typename T>
-__device__ __forceinline__ T va_last(T t) { return t; }
-template <typename T, typename... R>
-__device__ __forceinline__ auto va_last(T, R... r) { return va_last(r...); }
 // two sums with ONE barrier pair (block_sum's order for each)
 __device__ __forceinline__ void block_sum2(float& a, float& b, float* sv) {
   a = wave_sum(a);
@@ -382,14 +378,13 @@ __global__ __launch_bounds__(SMP_THREADS) void sample_kernel(const float* __rest
   if constexpr (CL) {      // this clip's timesteps: everything below reads them through `a`, like the per-clip parameters
     int lane0 = 0;
     asm volatile("" : "+v"(lane0));
-    if constexpr (ST) a.T = __builtin_amdgcn_readfirstlane(va_pick<SampleLengths>(lp_args...).T[b + lane0]);
-    else a.T = __builtin_amdgcn_readfirstlane(va_last(lp_args...).T[b + lane0]);
+    a.T = __builtin_amdgcn_readfirstlane(va_pick<SampleLengths>(lp_args...).T[b + lane0]);
   }
   [[maybe_unused]] long long cstep = 0;      // ST only: this clip's own step index, the Philox counter's
   if constexpr (ST) {
     int lane0 = 0;
     asm volatile("" : "+v"(lane0));
-    cstep = (long long)pos - (long long)__builtin_amdgcn_readfirstlane(va_last(lp_args...).n[b + lane0]);
+    cstep = (long long)pos - (long long)__builtin_amdgcn_readfirstlane(va_pick<SampleStarts>(lp_args...).n[b + lane0]);
   }
   float x[4] = {lc[0], lc[1], lc[2], lc[3]};
   // near-tie detector: magnitude of the rows this decision is made from (both branches, before the mix)
@@ -767,41 +762,48 @@ __global__ __launch_bounds__(SMP_THREADS) void sample_kernel(const float* __rest
   }
 }
 
+// The read-back behind every host-side check of a per-clip array: capture query, one small copy, a wait on `s`.  While `s` is being
+// captured nothing may wait: *captured is set and nothing is copied — the caller skips its check, the kernels' own clamps keep such
+// a launch inside its rows.  captured = NULL does not ask: a capturing stream then answers with HIP's own error.
+static int va_read_back(void* host, const void* dev, size_t bytes, hipStream_t s, bool* captured) {
+  if (captured) {
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    const hipError_t ce = hipStreamIsCapturing(s, &cs);
+    if (ce != hipSuccess) { (void)hipGetLastError(); return (int)ce; }      // no answer: refuse, never skip silently
+    *captured = cs != hipStreamCaptureStatusNone;
+    if (*captured) return 0;
+  }
+  hipError_t e = hipMemcpyAsync(host, dev, bytes, hipMemcpyDeviceToHost, s);
+  if (e == hipSuccess) e = hipStreamSynchronize(s);
+  return (int)e;
+}
+
 // Host side of the per-clip records' contract (the public entry points call it, never a captured launch): no records with probability
 // rows, and no record may ask for the CFG mix unless the call carries the null-condition rows (`doubled`, and the scalar cfg_scale > 1
-// that says so to the kernel).  Reads the B records back (one small copy + a wait on `s`); skipped while `s` is being captured, where
-// nothing may wait — the kernel's own clamp keeps such a launch inside its rows.
+// that says so to the kernel).  Reads the B records back (va_read_back: skipped while `s` is being captured).
 int va_check_clip_sampling(const vaura_sampling* sp, const vaura_clip_sampling* clips, int B, bool doubled, hipStream_t s) {
   if (!clips) return 0;
   if (!sp || B <= 0 || sp->input_is_probs) return VAURA_ERR_ARG;
   if (((uintptr_t)clips & 15u) != 0) return VAURA_ERR_ARG;
-  hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-  const hipError_t ce = hipStreamIsCapturing(s, &cs);
-  if (ce != hipSuccess) { (void)hipGetLastError(); return (int)ce; }      // no answer: refuse, never skip silently
-  if (cs != hipStreamCaptureStatusNone) return 0;
   std::vector<vaura_clip_sampling> host((size_t)B);
-  hipError_t e = hipMemcpyAsync(host.data(), clips, host.size() * sizeof(vaura_clip_sampling), hipMemcpyDeviceToHost, s);
-  if (e == hipSuccess) e = hipStreamSynchronize(s);
-  if (e != hipSuccess) return (int)e;
+  bool captured = false;
+  const int rc = va_read_back(host.data(), clips, host.size() * sizeof(vaura_clip_sampling), s, &captured);
+  if (rc || captured) return rc;
   const bool rows = doubled && sp->cfg_scale > 1.0f;
   for (const vaura_clip_sampling& r : host)
     if (r.cfg_scale > 1.0f && !rows) return VAURA_ERR_ARG;
   return 0;
 }
 
-// Host side of the per-clip lengths' contract, under the rules of va_check_clip_sampling: the B values are read back (one small copy + a
-// wait on `s`) and held to lo .. hi; skipped while `s` is being captured — the kernels' own clamps keep such a launch inside its rows.
+// Host side of the per-clip lengths' contract, under the rules of va_check_clip_sampling: the B values are read back and held to
+// lo .. hi; skipped while `s` is being captured.
 int va_check_clip_lengths(const int32_t* lengths, int B, int lo, int hi, hipStream_t s) {
   if (!lengths) return 0;
   if (B <= 0 || ((uintptr_t)lengths & 3u) != 0) return VAURA_ERR_ARG;
-  hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-  const hipError_t ce = hipStreamIsCapturing(s, &cs);
-  if (ce != hipSuccess) { (void)hipGetLastError(); return (int)ce; }
-  if (cs != hipStreamCaptureStatusNone) return 0;
   std::vector<int32_t> host((size_t)B);
-  hipError_t e = hipMemcpyAsync(host.data(), lengths, host.size() * sizeof(int32_t), hipMemcpyDeviceToHost, s);
-  if (e == hipSuccess) e = hipStreamSynchronize(s);
-  if (e != hipSuccess) return (int)e;
+  bool captured = false;
+  const int rc = va_read_back(host.data(), lengths, host.size() * sizeof(int32_t), s, &captured);
+  if (rc || captured) return rc;
   for (const int32_t v : host)
     if (v < lo || v > hi) return VAURA_ERR_ARG;
   return 0;
@@ -819,6 +821,8 @@ int va_launch_sample(const VaSampleLaunch& l, hipStream_t s) {
   if (rel && (!(l.cond_out || l.cond_seq) || !(l.null_out || l.null_seq) || !l.null_rows || !(sp->cfg_scale > 1.0f))) return VAURA_ERR_ARG;
   if (l.vocab != 1024) return VAURA_ERR_SHAPE;
   if (l.delays_host && K > 16) return VAURA_ERR_ARG;
+  if (l.clip_T && !l.seq) return VAURA_ERR_ARG;                 // lengths decide the validity of sequence slots: nothing to decide without a sequence
+  if (l.clip_n && (!l.seq || !l.state)) return VAURA_ERR_ARG;   // the counter step is position - n_b: the position lives in the state
   SampleArgs a;
   a.logits = l.logits; a.noise = l.noise; a.state = l.state; a.state_rw = l.state; a.tokens_out = l.tokens_out; a.seq = l.seq;
   a.B = B; a.K = K; a.V = l.vocab; a.T = l.T; a.S = l.S;
@@ -828,82 +832,23 @@ int va_launch_sample(const VaSampleLaunch& l, hipStream_t s) {
   a.probs_in = sp->input_is_probs;
   a.tie_eps = sp->tie_eps > 0.f ? sp->tie_eps : 0.f;
   const int32_t* rec = reinterpret_cast<const int32_t*>(l.clips);
-  if (l.clip_n) {      // per-clip first sampled positions: SampleStarts behind the pack, with or without the lengths in front of it
-    if (!l.seq || !l.state) return VAURA_ERR_ARG;   // the counter step is position - n_b: the position lives in the state
-    const SampleStarts cs{l.clip_n};
-    const SampleLengths cl{l.clip_T};
-    const dim3 grid(K, B), block(SMP_THREADS);
-    const SampleRelevance r{l.lp_out, l.lp_seq, l.cond_out, l.cond_seq, l.null_out, l.null_seq};
-    const SampleLogprobs q{l.lp_out, l.lp_seq};
-    if (l.clip_T) {
-      if (rel) {
-        const auto k0 = sample_kernel<false, true, SampleRelevance, SampleLengths, SampleStarts>, k1 = sample_kernel<true, true, SampleRelevance, SampleLengths, SampleStarts>;
-        if (l.clips) VA_LAUNCH(k1, grid, block, 0, s, a.logits, a.state, a, rec, r, cl, cs);
-        else VA_LAUNCH(k0, grid, block, 0, s, a.logits, a.state, a, rec, r, cl, cs);
-      } else if (lp) {
-        const auto k0 = sample_kernel<false, true, SampleLogprobs, SampleLengths, SampleStarts>, k1 = sample_kernel<true, true, SampleLogprobs, SampleLengths, SampleStarts>;
-        if (l.clips) VA_LAUNCH(k1, grid, block, 0, s, a.logits, a.state, a, rec, q, cl, cs);
-        else VA_LAUNCH(k0, grid, block, 0, s, a.logits, a.state, a, rec, q, cl, cs);
-      } else {
-        const auto k0 = sample_kernel<false, false, SampleLengths, SampleStarts>, k1 = sample_kernel<true, false, SampleLengths, SampleStarts>;
-        if (l.clips) VA_LAUNCH(k1, grid, block, 0, s, a.logits, a.state, a, rec, cl, cs);
-        else VA_LAUNCH(k0, grid, block, 0, s, a.logits, a.state, a, rec, cl, cs);
-      }
-      return 0;
-    }
-    if (rel) {
-      const auto k0 = sample_kernel<false, true, SampleRelevance, SampleStarts>, k1 = sample_kernel<true, true, SampleRelevance, SampleStarts>;
-      if (l.clips) VA_LAUNCH(k1, grid, block, 0, s, a.logits, a.state, a, rec, r, cs);
-      else VA_LAUNCH(k0, grid, block, 0, s, a.logits, a.state, a, rec, r, cs);
-    } else if (lp) {
-      const auto k0 = sample_kernel<false, true, SampleLogprobs, SampleStarts>, k1 = sample_kernel<true, true, SampleLogprobs, SampleStarts>;
-      if (l.clips) VA_LAUNCH(k1, grid, block, 0, s, a.logits, a.state, a, rec, q, cs);
-      else VA_LAUNCH(k0, grid, block, 0, s, a.logits, a.state, a, rec, q, cs);
-    } else {
-      const auto k0 = sample_kernel<false, false, SampleStarts>, k1 = sample_kernel<true, false, SampleStarts>;
-      if (l.clips) VA_LAUNCH(k1, grid, block, 0, s, a.logits, a.state, a, rec, cs);
-      else VA_LAUNCH(k0, grid, block, 0, s, a.logits, a.state, a, rec, cs);
-    }
+  // The instance is told by the TYPES of its pack, in the fixed order [SampleLogprobs | SampleRelevance] [SampleLengths] [SampleStarts]:
+  // each step below appends its member where the launch carries the array and hands the pack on; the last one derives LP from the
+  // pack, picks PC by the records and launches.  3 x 2 x 2 packs x 2 values of PC: the 24 instances, each reached from one place.
+  const dim3 grid(K, B), block(SMP_THREADS);
+  const auto launch = [&](auto... pack) -> int {
+    constexpr bool LP = ((std::is_same<decltype(pack), SampleLogprobs>::value || std::is_same<decltype(pack), SampleRelevance>::value) || ...);
+    // (named outside the macro: the commas of the template arguments would split its argument list)
+    const auto k_plain = sample_kernel<false, LP, decltype(pack)...>, k_pc = sample_kernel<true, LP, decltype(pack)...>;
+    if (l.clips) VA_LAUNCH(k_pc, grid, block, 0, s, a.logits, a.state, a, rec, pack...);
+    else VA_LAUNCH(k_plain, grid, block, 0, s, a.logits, a.state, a, rec, pack...);
     return 0;
-  }
-  if (l.clip_T) {      // per-clip lengths: the same six instances with SampleLengths behind their pack
-    if (!l.seq) return VAURA_ERR_ARG;               // lengths decide the validity of sequence slots: nothing to decide without a sequence
-    const SampleLengths cl{l.clip_T};
-    const dim3 grid(K, B), block(SMP_THREADS);
-    if (rel) {
-      const auto k_rel = sample_kernel<false, true, SampleRelevance, SampleLengths>, k_pc_rel = sample_kernel<true, true, SampleRelevance, SampleLengths>;
-      const SampleRelevance r{l.lp_out, l.lp_seq, l.cond_out, l.cond_seq, l.null_out, l.null_seq};
-      if (l.clips) VA_LAUNCH(k_pc_rel, grid, block, 0, s, a.logits, a.state, a, rec, r, cl);
-      else VA_LAUNCH(k_rel, grid, block, 0, s, a.logits, a.state, a, rec, r, cl);
-    } else if (lp) {
-      const auto k_lp = sample_kernel<false, true, SampleLogprobs, SampleLengths>, k_pc_lp = sample_kernel<true, true, SampleLogprobs, SampleLengths>;
-      if (l.clips) VA_LAUNCH(k_pc_lp, grid, block, 0, s, a.logits, a.state, a, rec, SampleLogprobs{l.lp_out, l.lp_seq}, cl);
-      else VA_LAUNCH(k_lp, grid, block, 0, s, a.logits, a.state, a, rec, SampleLogprobs{l.lp_out, l.lp_seq}, cl);
-    } else {
-      const auto k_plain = sample_kernel<false, false, SampleLengths>, k_pc = sample_kernel<true, false, SampleLengths>;
-      if (l.clips) VA_LAUNCH(k_pc, grid, block, 0, s, a.logits, a.state, a, rec, cl);
-      else VA_LAUNCH(k_plain, grid, block, 0, s, a.logits, a.state, a, rec, cl);
-    }
-    return 0;
-  }
-  // (named outside the macro: the commas of the template arguments would split its argument list)
-  const auto k_plain = sample_kernel<false, false>, k_pc = sample_kernel<true, false>;
-  const auto k_lp = sample_kernel<false, true, SampleLogprobs>, k_pc_lp = sample_kernel<true, true, SampleLogprobs>;
-  if (rel) {
-    const auto k_rel = sample_kernel<false, true, SampleRelevance>, k_pc_rel = sample_kernel<true, true, SampleRelevance>;
-    const SampleRelevance r{l.lp_out, l.lp_seq, l.cond_out, l.cond_seq, l.null_out, l.null_seq};
-    if (l.clips) VA_LAUNCH(k_pc_rel, dim3(K, B), dim3(SMP_THREADS), 0, s, a.logits, a.state, a, rec, r);
-    else VA_LAUNCH(k_rel, dim3(K, B), dim3(SMP_THREADS), 0, s, a.logits, a.state, a, rec, r);
-    return 0;
-  }
-  if (lp) {
-    if (l.clips) VA_LAUNCH(k_pc_lp, dim3(K, B), dim3(SMP_THREADS), 0, s, a.logits, a.state, a, rec, SampleLogprobs{l.lp_out, l.lp_seq});
-    else VA_LAUNCH(k_lp, dim3(K, B), dim3(SMP_THREADS), 0, s, a.logits, a.state, a, rec, SampleLogprobs{l.lp_out, l.lp_seq});
-    return 0;
-  }
-  if (l.clips) VA_LAUNCH(k_pc, dim3(K, B), dim3(SMP_THREADS), 0, s, a.logits, a.state, a, rec);
-  else VA_LAUNCH(k_plain, dim3(K, B), dim3(SMP_THREADS), 0, s, a.logits, a.state, a, rec);
-  return 0;
+  };
+  const auto with_starts = [&](auto... pack) -> int { return l.clip_n ? launch(pack..., SampleStarts{l.clip_n}) : launch(pack...); };
+  const auto with_lengths = [&](auto... pack) -> int { return l.clip_T ? with_starts(pack..., SampleLengths{l.clip_T}) : with_starts(pack...); };
+  if (rel) return with_lengths(SampleRelevance{l.lp_out, l.lp_seq, l.cond_out, l.cond_seq, l.null_out, l.null_seq});
+  if (lp) return with_lengths(SampleLogprobs{l.lp_out, l.lp_seq});
+  return with_lengths();
 }
 
 __global__ void advance_kernel(int32_t* state, int set_to) {
@@ -929,43 +874,28 @@ __device__ __forceinline__ int pattern_delay(const PatternDelays& pd, int q) {
   return dq;
 }
 
+// Per-clip lengths (clip_T, or NULL: every clip holds T frames): clip b holds T_b = clip_T[b] <= T frames.  build: a slot whose timestep
+// is >= T_b holds the special token, as in the sequence built for T = T_b; revert (tokens or fp32 values in the layout of seq): frames
+// from T_b on get `pad`.  T_b is clamped to T in build: no value can send a read out of the clip's rows.  One kernel each for every
+// entry point: they run once or a handful of times per call, outside the decode loop.
 __global__ void pattern_build_kernel(const int32_t* __restrict__ codes, int32_t* __restrict__ seq, int B, int K, int T, int S,
-                                     int special, PatternDelays pd) {
+                                     int special, PatternDelays pd, const int32_t* __restrict__ clip_T) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= (int64_t)B * K * S) return;
   const int s = (int)(i % S), q = (int)((i / S) % K), b = (int)(i / ((int64_t)S * K));
   const int t = s - 1 - pattern_delay(pd, q);
-  seq[i] = (t >= 0 && t < T) ? codes[((size_t)b * K + q) * T + t] : special;
+  const int Tb = clip_T ? min(clip_T[b], T) : T;
+  seq[i] = (t >= 0 && t < Tb) ? codes[((size_t)b * K + q) * T + t] : special;
 }
-__global__ void pattern_revert_kernel(const int32_t* __restrict__ seq, int32_t* __restrict__ codes, int B, int K, int T,
-                                      int S, int fill, PatternDelays pd) {
-  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= (int64_t)B * K * T) return;
-  const int t = (int)(i % T), q = (int)((i / T) % K), b = (int)(i / ((int64_t)T * K));
-  const int s = t + 1 + pattern_delay(pd, q);
-  codes[i] = (s < S) ? seq[((size_t)b * K + q) * S + s] : fill;
-}
-
-// Per-clip lengths (vaura_pattern_*_clips): clip b holds T_b = clip_T[b] <= T frames.  build: a slot whose timestep is >= T_b holds the
-// special token, as in the sequence built for T = T_b; revert (tokens or fp32 values): frames from T_b on get `pad`.  T_b is clamped
-// to T: no value can send a read out of the clip's rows.
-__global__ void pattern_build_clips_kernel(const int32_t* __restrict__ codes, int32_t* __restrict__ seq, int B, int K, int T, int S,
-                                           int special, PatternDelays pd, const int32_t* __restrict__ clip_T) {
-  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= (int64_t)B * K * S) return;
-  const int s = (int)(i % S), q = (int)((i / S) % K), b = (int)(i / ((int64_t)S * K));
-  const int t = s - 1 - pattern_delay(pd, q);
-  seq[i] = (t >= 0 && t < min(clip_T[b], T)) ? codes[((size_t)b * K + q) * T + t] : special;
-}
-template <typename E>
-__global__ void pattern_revert_clips_kernel(const E* __restrict__ seq, E* __restrict__ out, int B, int K, int T, int S, E fill, E pad,
-                                            PatternDelays pd, const int32_t* __restrict__ clip_T) {
+template <typename E>      // tokens (int32_t) or their log-probabilities (float): the same index map
+__global__ void pattern_revert_kernel(const E* __restrict__ seq, E* __restrict__ out, int B, int K, int T, int S, E fill, E pad,
+                                      PatternDelays pd, const int32_t* __restrict__ clip_T) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= (int64_t)B * K * T) return;
   const int t = (int)(i % T), q = (int)((i / T) % K);
   const int64_t b = i / ((int64_t)T * K);
   const int s = t + 1 + pattern_delay(pd, q);
-  out[i] = t < clip_T[b] ? ((s < S) ? seq[((size_t)b * K + q) * S + s] : fill) : pad;
+  out[i] = (!clip_T || t < clip_T[b]) ? ((s < S) ? seq[((size_t)b * K + q) * S + s] : fill) : pad;
 }
 
 // delays_host: K sorted, non-negative delays (K <= 16), or NULL for d_q = q.  Returns max(d) + 1 (K for NULL), or an error.
@@ -980,70 +910,33 @@ static int pattern_delays_arg(const int32_t* delays_host, int K, PatternDelays* 
   return delays_host[K - 1] + 1;
 }
 
+// clip_T: the lengths (read back and held to 1 .. T) or NULL; an entry point that requires either array refuses its NULL itself
 static int pattern_build(const int32_t* codes, int32_t* seq, int B, int K, int T, int S, int special, const int32_t* delays_host,
-                         hipStream_t s) {
+                         const int32_t* clip_T, hipStream_t s) {
   if (!codes || !seq || B <= 0 || K <= 0 || T <= 0) return VAURA_ERR_ARG;
   PatternDelays pd;
   const int span = pattern_delays_arg(delays_host, K, &pd);
   if (span < 0) return span;
   if (S != T + span) return VAURA_ERR_SHAPE;
-  const int64_t n = (int64_t)B * K * S;
-  VA_LAUNCH(pattern_build_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, codes, seq, B, K, T, S, special, pd);
-  return 0;
-}
-
-static int pattern_build_clips(const int32_t* codes, int32_t* seq, int B, int K, int T, int S, int special, const int32_t* delays_host,
-                               const int32_t* clip_T, hipStream_t s) {
-  if (!codes || !seq || !clip_T || B <= 0 || K <= 0 || T <= 0) return VAURA_ERR_ARG;
-  PatternDelays pd;
-  const int span = pattern_delays_arg(delays_host, K, &pd);
-  if (span < 0) return span;
-  if (S != T + span) return VAURA_ERR_SHAPE;
   const int rc = va_check_clip_lengths(clip_T, B, 1, T, s);
   if (rc) return rc;
   const int64_t n = (int64_t)B * K * S;
-  VA_LAUNCH(pattern_build_clips_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, codes, seq, B, K, T, S, special, pd, clip_T);
+  VA_LAUNCH(pattern_build_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, codes, seq, B, K, T, S, special, pd, clip_T);
   return 0;
 }
 
-// float twin of pattern_revert_kernel (token log-probabilities live in the layout of seq): the same index map
-__global__ void pattern_revert_f32_kernel(const float* __restrict__ seq, float* __restrict__ out, int B, int K, int T, int S, float fill,
-                                          PatternDelays pd) {
-  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= (int64_t)B * K * T) return;
-  const int t = (int)(i % T), q = (int)((i / T) % K);
-  const int64_t b = i / ((int64_t)T * K);
-  const int s = t + 1 + pattern_delay(pd, q);
-  out[i] = (s < S) ? seq[((size_t)b * K + q) * S + s] : fill;
-}
-
-// tokens (int32_t) or their log-probabilities (float): the two kernels above
 template <typename E>
-static int pattern_revert(const E* seq, E* out, int B, int K, int T, int S, E fill, const int32_t* delays_host, hipStream_t s) {
+static int pattern_revert(const E* seq, E* out, int B, int K, int T, int S, E fill, E pad, const int32_t* delays_host,
+                          const int32_t* clip_T, hipStream_t s) {
   if (!out || !seq || B <= 0 || K <= 0 || T <= 0 || S <= 0) return VAURA_ERR_ARG;
   PatternDelays pd;
   const int span = pattern_delays_arg(delays_host, K, &pd);
   if (span < 0) return span;
   if (delays_host && S > T + span) return VAURA_ERR_SHAPE;
-  const int64_t n = (int64_t)B * K * T;
-  const dim3 grid((unsigned)((n + 255) / 256));
-  if constexpr (std::is_same<E, float>::value) VA_LAUNCH(pattern_revert_f32_kernel, grid, dim3(256), 0, s, seq, out, B, K, T, S, fill, pd);
-  else VA_LAUNCH(pattern_revert_kernel, grid, dim3(256), 0, s, seq, out, B, K, T, S, fill, pd);
-  return 0;
-}
-
-template <typename E>
-static int pattern_revert_clips(const E* seq, E* out, int B, int K, int T, int S, E fill, E pad, const int32_t* delays_host,
-                                const int32_t* clip_T, hipStream_t s) {
-  if (!out || !seq || !clip_T || B <= 0 || K <= 0 || T <= 0 || S <= 0) return VAURA_ERR_ARG;
-  PatternDelays pd;
-  const int span = pattern_delays_arg(delays_host, K, &pd);
-  if (span < 0) return span;
-  if (delays_host && S > T + span) return VAURA_ERR_SHAPE;
   const int rc = va_check_clip_lengths(clip_T, B, 1, T, s);
   if (rc) return rc;
   const int64_t n = (int64_t)B * K * T;
-  const auto kern = pattern_revert_clips_kernel<E>;
+  const auto kern = pattern_revert_kernel<E>;
   VA_LAUNCH(kern, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, seq, out, B, K, T, S, fill, pad, pd, clip_T);
   return 0;
 }
@@ -1053,55 +946,16 @@ static int pattern_revert_clips(const E* seq, E* out, int B, int K, int T, int S
 // fixed butterfly (wave_sum: neighbours at distance 1, 2, 4, .., 32) adds the lanes, the mean is sum / (T - t0); thread 0 then adds the K
 // means in codebook order and divides by K.  Two runs give the same bits; a NaN anywhere in the clip reaches the clip's score through
 // the sums (and every codebook's mean is then reported NaN as well: the clip's scores are not to be used).
+// The means of clip b run over frames [t0_b, T_b): t0_b = clip_t0[b] (per-clip prompt lengths) or the scalar t0 where clip_t0 is NULL,
+// T_b = clip_T[b] (per-clip lengths) or the scalar T where clip_T is NULL — the launch with t0 = t0_b and T = T_b.
 __global__ __launch_bounds__(1024) void sequence_logprob_kernel(const float* __restrict__ lp, int B, int K, int T, int S, int t0,
                                                                 PatternDelays pd, float* __restrict__ per_codebook,
-                                                                float* __restrict__ per_clip) {
-  __shared__ float means[16];
-  const int lane = threadIdx.x & 63, q = threadIdx.x >> 6, b = blockIdx.x;
-  const int dq = pattern_delay(pd, q);
-  const float* row = lp + ((size_t)b * K + q) * S + 1 + dq;
-  float acc = 0.f;
-  for (int t = t0 + lane; t < T; t += 64) acc += (t + 1 + dq < S) ? row[t] : 0.f;
-  acc = wave_sum(acc);
-  if (lane == 0) means[q] = acc / (float)(T - t0);
-  __syncthreads();
-  float tot = 0.f;
-  for (int j = 0; j < K; ++j) tot += means[j];
-  tot = tot / (float)K;
-  if (lane == 0) per_codebook[(size_t)b * K + q] = (tot != tot) ? tot : means[q];
-  if (threadIdx.x == 0) per_clip[b] = tot;
-}
-// The same with per-clip lengths (vaura_sequence_logprob_clips): the means of clip b run over frames [t0, T_b), T_b = clip_T[b] — the
-// launch with T = T_b (a copy for the reason given at embed_clips_kernel).
-__global__ __launch_bounds__(1024) void sequence_logprob_clips_kernel(const float* __restrict__ lp, int B, int K, int T, int S, int t0,
-                                                                PatternDelays pd, float* __restrict__ per_codebook,
-                                                                float* __restrict__ per_clip, const int32_t* __restrict__ clip_T) {
-  __shared__ float means[16];
-  const int lane = threadIdx.x & 63, q = threadIdx.x >> 6, b = blockIdx.x;
-  T = clip_T[b];
-  const int dq = pattern_delay(pd, q);
-  const float* row = lp + ((size_t)b * K + q) * S + 1 + dq;
-  float acc = 0.f;
-  for (int t = t0 + lane; t < T; t += 64) acc += (t + 1 + dq < S) ? row[t] : 0.f;
-  acc = wave_sum(acc);
-  if (lane == 0) means[q] = acc / (float)(T - t0);
-  __syncthreads();
-  float tot = 0.f;
-  for (int j = 0; j < K; ++j) tot += means[j];
-  tot = tot / (float)K;
-  if (lane == 0) per_codebook[(size_t)b * K + q] = (tot != tot) ? tot : means[q];
-  if (threadIdx.x == 0) per_clip[b] = tot;
-}
-// The same with a per-clip first frame (vaura_sequence_logprob_starts: per-clip prompt lengths): the means of clip b run over frames
-// [clip_t0[b], T_b), T_b = clip_T[b] or T where clip_T is NULL — the launch with t0 = clip_t0[b] (a copy, like the kernel above).
-__global__ __launch_bounds__(1024) void sequence_logprob_starts_kernel(const float* __restrict__ lp, int B, int K, int T, int S,
-                                                                 const int32_t* __restrict__ clip_t0, PatternDelays pd,
-                                                                 float* __restrict__ per_codebook, float* __restrict__ per_clip,
-                                                                 const int32_t* __restrict__ clip_T) {
+                                                                float* __restrict__ per_clip, const int32_t* __restrict__ clip_t0,
+                                                                const int32_t* __restrict__ clip_T) {
   __shared__ float means[16];
   const int lane = threadIdx.x & 63, q = threadIdx.x >> 6, b = blockIdx.x;
   if (clip_T) T = clip_T[b];
-  const int t0 = clip_t0[b];
+  if (clip_t0) t0 = clip_t0[b];
   const int dq = pattern_delay(pd, q);
   const float* row = lp + ((size_t)b * K + q) * S + 1 + dq;
   float acc = 0.f;
@@ -1114,6 +968,35 @@ __global__ __launch_bounds__(1024) void sequence_logprob_starts_kernel(const flo
   tot = tot / (float)K;
   if (lane == 0) per_codebook[(size_t)b * K + q] = (tot != tot) ? tot : means[q];
   if (threadIdx.x == 0) per_clip[b] = tot;
+}
+
+// The three vaura_sequence_logprob* entry points.  clip_t0 = NULL: the scalar t0, and clip_T (or NULL) is held to t0 + 1 .. T through
+// va_check_clip_lengths — every clip has a frame behind the prompt; skipped while `s` is being captured.  With clip_t0 both arrays are
+// read back without asking (a capturing stream gets HIP's error): 1 <= T_b <= T and 0 <= t0_b < T_b.
+static int sequence_logprob(const float* logprobs, int seq_len, const int32_t* delays_host, int B, int K, int T, int t0,
+                            const int32_t* clip_t0, const int32_t* clip_T, float* per_codebook, float* per_clip, hipStream_t s) {
+  if (!logprobs || !per_codebook || !per_clip || B <= 0 || K <= 0 || T <= 0 || seq_len <= 0) return VAURA_ERR_ARG;
+  if (!clip_t0 && (t0 < 0 || t0 >= T)) return VAURA_ERR_ARG;
+  if (K > 16) return VAURA_ERR_SHAPE;
+  PatternDelays pd;
+  const int span = pattern_delays_arg(delays_host, K, &pd);
+  if (span < 0) return span;
+  if (seq_len != T + span) return VAURA_ERR_SHAPE;      // every frame of every codebook has its slot
+  if (clip_t0) {
+    if (((uintptr_t)clip_t0 & 3u) != 0 || ((uintptr_t)clip_T & 3u) != 0) return VAURA_ERR_ARG;
+    std::vector<int32_t> h0((size_t)B), hT((size_t)B, T);
+    int rc = va_read_back(h0.data(), clip_t0, h0.size() * sizeof(int32_t), s, nullptr);
+    if (!rc && clip_T) rc = va_read_back(hT.data(), clip_T, hT.size() * sizeof(int32_t), s, nullptr);
+    if (rc) return rc;
+    for (int b = 0; b < B; ++b)
+      if (hT[b] < 1 || hT[b] > T || h0[b] < 0 || h0[b] >= hT[b]) return VAURA_ERR_ARG;
+  } else {
+    const int rc = va_check_clip_lengths(clip_T, B, t0 + 1, T, s);
+    if (rc) return rc;
+  }
+  VA_LAUNCH(sequence_logprob_kernel, dim3((unsigned)B), dim3(64 * K), 0, s, logprobs, B, K, T, seq_len, t0, pd, per_codebook, per_clip,
+            clip_t0, clip_T);
+  return 0;
 }
 
 // Best-of-N: one workgroup per clip picks the candidate with the largest score — the first index wins a tie, a NaN never beats a
@@ -1133,26 +1016,91 @@ __global__ __launch_bounds__(256) void select_candidates_kernel(const float* __r
   if (threadIdx.x == 0) winner[b] = best;
 }
 
+// What vaura_sample_clips / _logprobs / _relevance share: the rules of the standalone and the sequence form, the records' check, the
+// launch.  Each entry point states its own required pointers first.
+static int sample_step(const float* logits, int B, int K, int vocab, const vaura_sampling* sp, const vaura_clip_sampling* clips,
+                       const float* noise, int64_t step, int32_t* tokens_out, int32_t* seq, int T, int S, int32_t* state,
+                       float* logprobs_out, float* cond_out, float* null_out, hipStream_t s) {
+  if (!logits || !sp || (!tokens_out && !seq) || B <= 0 || K <= 0) return VAURA_ERR_ARG;
+  if (seq && (!state || T <= 0 || S <= 0)) return VAURA_ERR_ARG;
+  const int rc = va_check_clip_sampling(sp, clips, B, sp->cfg_scale > 1.0f, s);
+  if (rc) return rc;
+  VaSampleLaunch a;
+  a.logits = logits; a.B = B; a.K = K; a.vocab = vocab; a.sp = sp; a.clips = clips; a.noise = noise; a.step_host = step;
+  a.tokens_out = tokens_out; a.seq = seq; a.T = T; a.S = S;
+  a.state = seq ? state : nullptr;      // the standalone form keeps no state, like vaura_sample
+  a.lp_out = logprobs_out;
+  a.cond_out = cond_out; a.null_out = null_out; a.null_rows = cond_out || null_out;      // (vaura_sample_relevance has checked cfg_scale > 1)
+  return va_launch_sample(a, s);
+}
+
+// vaura_sample_seq and vaura_sample_seq_starts: clip_first_steps = NULL is the former (its range check passes a NULL)
+static int sample_seq(const float* logits, int B, int K, int vocab, const vaura_sampling* sp, const vaura_clip_sampling* clips,
+                      const float* noise, int32_t* seq, int T, int S, int32_t* state, const int32_t* delays_host,
+                      const int32_t* clip_timesteps, const int32_t* clip_first_steps, float* lp_seq, float* cond_seq, float* null_seq,
+                      hipStream_t s) {
+  if (!logits || !sp || !seq || !state || B <= 0 || K <= 0 || T <= 0 || S <= 0) return VAURA_ERR_ARG;
+  if (sp->input_is_probs && (clips || lp_seq || cond_seq || null_seq)) return VAURA_ERR_ARG;
+  if (!cond_seq != !null_seq) return VAURA_ERR_ARG;
+  if (delays_host) {
+    PatternDelays pd;
+    const int span = pattern_delays_arg(delays_host, K, &pd);
+    if (span < 0) return span;
+  }
+  int rc = va_check_clip_sampling(sp, clips, B, sp->cfg_scale > 1.0f, s);
+  if (!rc) rc = va_check_clip_lengths(clip_timesteps, B, 1, T, s);
+  if (!rc) rc = va_check_clip_lengths(clip_first_steps, B, 0, S - 1, s);
+  if (rc) return rc;
+  VaSampleLaunch a;
+  a.logits = logits; a.B = B; a.K = K; a.vocab = vocab; a.sp = sp; a.clips = clips; a.noise = noise;
+  a.seq = seq; a.T = T; a.S = S; a.state = state; a.delays_host = delays_host; a.clip_T = clip_timesteps; a.clip_n = clip_first_steps;
+  a.lp_seq = lp_seq; a.cond_seq = cond_seq; a.null_seq = null_seq; a.null_rows = sp->cfg_scale > 1.0f;
+  return va_launch_sample(a, s);
+}
+
 extern "C" {
 
 int vaura_pattern_build(const int32_t* codes, int32_t* seq, int B, int K, int T, int special, vaura_stream_t s) {
-  return pattern_build(codes, seq, B, K, T, T + K, special, nullptr, as_stream(s));
+  return pattern_build(codes, seq, B, K, T, T + K, special, nullptr, nullptr, as_stream(s));
 }
 
 int vaura_pattern_revert(const int32_t* seq, int32_t* codes, int B, int K, int T, int S, int fill, vaura_stream_t s) {
-  return pattern_revert(seq, codes, B, K, T, S, fill, nullptr, as_stream(s));
+  return pattern_revert<int32_t>(seq, codes, B, K, T, S, fill, 0, nullptr, nullptr, as_stream(s));
 }
 
 int vaura_pattern_build_delays(const int32_t* codes, int32_t* seq, int B, int K, int T, int S, int special,
                                const int32_t* delays_host, vaura_stream_t s) {
   if (!delays_host) return VAURA_ERR_ARG;
-  return pattern_build(codes, seq, B, K, T, S, special, delays_host, as_stream(s));
+  return pattern_build(codes, seq, B, K, T, S, special, delays_host, nullptr, as_stream(s));
 }
 
 int vaura_pattern_revert_delays(const int32_t* seq, int32_t* codes, int B, int K, int T, int S, int fill,
                                 const int32_t* delays_host, vaura_stream_t s) {
   if (!delays_host) return VAURA_ERR_ARG;
-  return pattern_revert(seq, codes, B, K, T, S, fill, delays_host, as_stream(s));
+  return pattern_revert<int32_t>(seq, codes, B, K, T, S, fill, 0, delays_host, nullptr, as_stream(s));
+}
+
+int vaura_pattern_revert_delays_f32(const float* seq, float* out, int B, int K, int T, int S, float fill, const int32_t* delays_host,
+                                    vaura_stream_t s) {
+  return pattern_revert<float>(seq, out, B, K, T, S, fill, 0.f, delays_host, nullptr, as_stream(s));
+}
+
+int vaura_pattern_build_clips(const int32_t* codes, int32_t* seq, int B, int K, int T, int S, int special, const int32_t* delays_host,
+                              const int32_t* clip_timesteps, vaura_stream_t s) {
+  if (!clip_timesteps) return VAURA_ERR_ARG;
+  return pattern_build(codes, seq, B, K, T, S, special, delays_host, clip_timesteps, as_stream(s));
+}
+
+int vaura_pattern_revert_clips(const int32_t* seq, int32_t* codes, int B, int K, int T, int S, int fill, int pad,
+                               const int32_t* delays_host, const int32_t* clip_timesteps, vaura_stream_t s) {
+  if (!clip_timesteps) return VAURA_ERR_ARG;
+  return pattern_revert<int32_t>(seq, codes, B, K, T, S, fill, pad, delays_host, clip_timesteps, as_stream(s));
+}
+
+int vaura_pattern_revert_clips_f32(const float* seq, float* out, int B, int K, int T, int S, float fill, float pad,
+                                   const int32_t* delays_host, const int32_t* clip_timesteps, vaura_stream_t s) {
+  if (!clip_timesteps) return VAURA_ERR_ARG;
+  return pattern_revert<float>(seq, out, B, K, T, S, fill, pad, delays_host, clip_timesteps, as_stream(s));
 }
 
 int vaura_sample(const float* logits, int B, int K, int vocab, const vaura_sampling* sp, const float* noise,
@@ -1166,168 +1114,60 @@ int vaura_sample(const float* logits, int B, int K, int vocab, const vaura_sampl
 int vaura_sample_clips(const float* logits, int B, int K, int vocab, const vaura_sampling* sp, const vaura_clip_sampling* clips,
                        const float* noise, int64_t step, int32_t* tokens_out, int32_t* seq, int T, int S, int32_t* state,
                        vaura_stream_t s) {
-  if (!clips || (!tokens_out && !seq)) return VAURA_ERR_ARG;
-  if (seq && (!state || T <= 0 || S <= 0)) return VAURA_ERR_ARG;
-  if (!logits || !sp || B <= 0 || K <= 0) return VAURA_ERR_ARG;
-  const int rc = va_check_clip_sampling(sp, clips, B, sp->cfg_scale > 1.0f, as_stream(s));
-  if (rc) return rc;
-  VaSampleLaunch a;
-  a.logits = logits; a.B = B; a.K = K; a.vocab = vocab; a.sp = sp; a.clips = clips; a.noise = noise; a.step_host = step;
-  a.tokens_out = tokens_out; a.seq = seq; a.T = T; a.S = S;
-  a.state = seq ? state : nullptr;      // the standalone form keeps no state, like vaura_sample
-  return va_launch_sample(a, as_stream(s));
+  if (!clips) return VAURA_ERR_ARG;
+  return sample_step(logits, B, K, vocab, sp, clips, noise, step, tokens_out, seq, T, S, state, nullptr, nullptr, nullptr, as_stream(s));
 }
 
 int vaura_sample_logprobs(const float* logits, int B, int K, int vocab, const vaura_sampling* sp, const vaura_clip_sampling* clips,
                           const float* noise, int64_t step, int32_t* tokens_out, int32_t* seq, int T, int S, int32_t* state,
                           float* logprobs_out, vaura_stream_t s) {
-  if (!logits || !sp || !logprobs_out || (!tokens_out && !seq) || B <= 0 || K <= 0) return VAURA_ERR_ARG;
-  if (seq && (!state || T <= 0 || S <= 0)) return VAURA_ERR_ARG;
-  if (sp->input_is_probs) return VAURA_ERR_ARG;
-  const int rc = va_check_clip_sampling(sp, clips, B, sp->cfg_scale > 1.0f, as_stream(s));
-  if (rc) return rc;
-  VaSampleLaunch a;
-  a.logits = logits; a.B = B; a.K = K; a.vocab = vocab; a.sp = sp; a.clips = clips; a.noise = noise; a.step_host = step;
-  a.tokens_out = tokens_out; a.seq = seq; a.T = T; a.S = S;
-  a.state = seq ? state : nullptr;      // the standalone form keeps no state, like vaura_sample
-  a.lp_out = logprobs_out;
-  return va_launch_sample(a, as_stream(s));
+  if (!sp || !logprobs_out || sp->input_is_probs) return VAURA_ERR_ARG;
+  return sample_step(logits, B, K, vocab, sp, clips, noise, step, tokens_out, seq, T, S, state, logprobs_out, nullptr, nullptr,
+                     as_stream(s));
 }
 
 int vaura_sample_relevance(const float* logits, int B, int K, int vocab, const vaura_sampling* sp, const vaura_clip_sampling* clips,
                            const float* noise, int64_t step, int32_t* tokens_out, int32_t* seq, int T, int S, int32_t* state,
                            float* logprobs_out, float* cond_out, float* null_out, vaura_stream_t s) {
-  if (!logits || !sp || !cond_out || !null_out || (!tokens_out && !seq) || B <= 0 || K <= 0) return VAURA_ERR_ARG;
-  if (seq && (!state || T <= 0 || S <= 0)) return VAURA_ERR_ARG;
-  if (sp->input_is_probs) return VAURA_ERR_ARG;
+  if (!sp || !cond_out || !null_out || sp->input_is_probs) return VAURA_ERR_ARG;
   if (!(sp->cfg_scale > 1.0f)) return VAURA_ERR_ARG;      // no null-condition rows: nothing to compare the conditional row with
-  const int rc = va_check_clip_sampling(sp, clips, B, true, as_stream(s));
-  if (rc) return rc;
-  VaSampleLaunch a;
-  a.logits = logits; a.B = B; a.K = K; a.vocab = vocab; a.sp = sp; a.clips = clips; a.noise = noise; a.step_host = step;
-  a.tokens_out = tokens_out; a.seq = seq; a.T = T; a.S = S;
-  a.state = seq ? state : nullptr;      // the standalone form keeps no state, like vaura_sample
-  a.lp_out = logprobs_out;              // optional here: NULL = lc and lu only
-  a.cond_out = cond_out; a.null_out = null_out; a.null_rows = true;
-  return va_launch_sample(a, as_stream(s));
-}
-
-int vaura_pattern_revert_delays_f32(const float* seq, float* out, int B, int K, int T, int S, float fill, const int32_t* delays_host,
-                                    vaura_stream_t s) {
-  return pattern_revert(seq, out, B, K, T, S, fill, delays_host, as_stream(s));
-}
-
-int vaura_sequence_logprob(const float* logprobs, int seq_len, const int32_t* delays_host, int B, int K, int T, int t0,
-                           float* per_codebook, float* per_clip, vaura_stream_t s) {
-  if (!logprobs || !per_codebook || !per_clip || B <= 0 || K <= 0 || T <= 0 || seq_len <= 0 || t0 < 0 || t0 >= T) return VAURA_ERR_ARG;
-  if (K > 16) return VAURA_ERR_SHAPE;
-  PatternDelays pd;
-  const int span = pattern_delays_arg(delays_host, K, &pd);
-  if (span < 0) return span;
-  if (seq_len != T + span) return VAURA_ERR_SHAPE;      // every frame of every codebook has its slot
-  VA_LAUNCH(sequence_logprob_kernel, dim3((unsigned)B), dim3(64 * K), 0, as_stream(s), logprobs, B, K, T, seq_len, t0, pd, per_codebook,
-            per_clip);
-  return 0;
-}
-
-int vaura_pattern_build_clips(const int32_t* codes, int32_t* seq, int B, int K, int T, int S, int special, const int32_t* delays_host,
-                              const int32_t* clip_timesteps, vaura_stream_t s) {
-  return pattern_build_clips(codes, seq, B, K, T, S, special, delays_host, clip_timesteps, as_stream(s));
-}
-
-int vaura_pattern_revert_clips(const int32_t* seq, int32_t* codes, int B, int K, int T, int S, int fill, int pad,
-                               const int32_t* delays_host, const int32_t* clip_timesteps, vaura_stream_t s) {
-  return pattern_revert_clips<int32_t>(seq, codes, B, K, T, S, fill, pad, delays_host, clip_timesteps, as_stream(s));
-}
-
-int vaura_pattern_revert_clips_f32(const float* seq, float* out, int B, int K, int T, int S, float fill, float pad,
-                                   const int32_t* delays_host, const int32_t* clip_timesteps, vaura_stream_t s) {
-  return pattern_revert_clips<float>(seq, out, B, K, T, S, fill, pad, delays_host, clip_timesteps, as_stream(s));
-}
-
-int vaura_sequence_logprob_clips(const float* logprobs, int seq_len, const int32_t* delays_host, int B, int K, int T, int t0,
-                                 const int32_t* clip_timesteps, float* per_codebook, float* per_clip, vaura_stream_t s) {
-  if (!logprobs || !clip_timesteps || !per_codebook || !per_clip || B <= 0 || K <= 0 || T <= 0 || seq_len <= 0 || t0 < 0 || t0 >= T)
-    return VAURA_ERR_ARG;
-  if (K > 16) return VAURA_ERR_SHAPE;
-  PatternDelays pd;
-  const int span = pattern_delays_arg(delays_host, K, &pd);
-  if (span < 0) return span;
-  if (seq_len != T + span) return VAURA_ERR_SHAPE;
-  const int rc = va_check_clip_lengths(clip_timesteps, B, t0 + 1, T, as_stream(s));      // every clip has a frame behind the prompt
-  if (rc) return rc;
-  VA_LAUNCH(sequence_logprob_clips_kernel, dim3((unsigned)B), dim3(64 * K), 0, as_stream(s), logprobs, B, K, T, seq_len, t0, pd,
-            per_codebook, per_clip, clip_timesteps);
-  return 0;
+  // logprobs_out is optional here: NULL = lc and lu only
+  return sample_step(logits, B, K, vocab, sp, clips, noise, step, tokens_out, seq, T, S, state, logprobs_out, cond_out, null_out,
+                     as_stream(s));
 }
 
 int vaura_sample_seq(const float* logits, int B, int K, int vocab, const vaura_sampling* sp, const vaura_clip_sampling* clips,
                      const float* noise, int32_t* seq, int T, int S, int32_t* state, const int32_t* delays_host,
                      const int32_t* clip_timesteps, float* lp_seq, float* cond_seq, float* null_seq, vaura_stream_t s) {
-  if (!logits || !sp || !seq || !state || B <= 0 || K <= 0 || T <= 0 || S <= 0) return VAURA_ERR_ARG;
-  if (sp->input_is_probs && (clips || lp_seq || cond_seq || null_seq)) return VAURA_ERR_ARG;
-  if (!cond_seq != !null_seq) return VAURA_ERR_ARG;
-  if (delays_host) {
-    PatternDelays pd;
-    const int span = pattern_delays_arg(delays_host, K, &pd);
-    if (span < 0) return span;
-  }
-  int rc = va_check_clip_sampling(sp, clips, B, sp->cfg_scale > 1.0f, as_stream(s));
-  if (!rc) rc = va_check_clip_lengths(clip_timesteps, B, 1, T, as_stream(s));
-  if (rc) return rc;
-  VaSampleLaunch a;
-  a.logits = logits; a.B = B; a.K = K; a.vocab = vocab; a.sp = sp; a.clips = clips; a.noise = noise;
-  a.seq = seq; a.T = T; a.S = S; a.state = state; a.delays_host = delays_host; a.clip_T = clip_timesteps;
-  a.lp_seq = lp_seq; a.cond_seq = cond_seq; a.null_seq = null_seq; a.null_rows = sp->cfg_scale > 1.0f;
-  return va_launch_sample(a, as_stream(s));
+  return sample_seq(logits, B, K, vocab, sp, clips, noise, seq, T, S, state, delays_host, clip_timesteps, nullptr, lp_seq, cond_seq,
+                    null_seq, as_stream(s));
 }
 
 int vaura_sample_seq_starts(const float* logits, int B, int K, int vocab, const vaura_sampling* sp, const vaura_clip_sampling* clips,
                             const float* noise, int32_t* seq, int T, int S, int32_t* state, const int32_t* delays_host,
                             const int32_t* clip_timesteps, const int32_t* clip_first_steps, float* lp_seq, float* cond_seq,
                             float* null_seq, vaura_stream_t s) {
-  if (!logits || !sp || !seq || !state || !clip_first_steps || B <= 0 || K <= 0 || T <= 0 || S <= 0) return VAURA_ERR_ARG;
-  if (sp->input_is_probs && (clips || lp_seq || cond_seq || null_seq)) return VAURA_ERR_ARG;
-  if (!cond_seq != !null_seq) return VAURA_ERR_ARG;
-  if (delays_host) {
-    PatternDelays pd;
-    const int span = pattern_delays_arg(delays_host, K, &pd);
-    if (span < 0) return span;
-  }
-  int rc = va_check_clip_sampling(sp, clips, B, sp->cfg_scale > 1.0f, as_stream(s));
-  if (!rc) rc = va_check_clip_lengths(clip_timesteps, B, 1, T, as_stream(s));
-  if (!rc) rc = va_check_clip_lengths(clip_first_steps, B, 0, S - 1, as_stream(s));
-  if (rc) return rc;
-  VaSampleLaunch a;
-  a.logits = logits; a.B = B; a.K = K; a.vocab = vocab; a.sp = sp; a.clips = clips; a.noise = noise;
-  a.seq = seq; a.T = T; a.S = S; a.state = state; a.delays_host = delays_host; a.clip_T = clip_timesteps; a.clip_n = clip_first_steps;
-  a.lp_seq = lp_seq; a.cond_seq = cond_seq; a.null_seq = null_seq; a.null_rows = sp->cfg_scale > 1.0f;
-  return va_launch_sample(a, as_stream(s));
+  if (!clip_first_steps) return VAURA_ERR_ARG;
+  return sample_seq(logits, B, K, vocab, sp, clips, noise, seq, T, S, state, delays_host, clip_timesteps, clip_first_steps, lp_seq,
+                    cond_seq, null_seq, as_stream(s));
+}
+
+int vaura_sequence_logprob(const float* logprobs, int seq_len, const int32_t* delays_host, int B, int K, int T, int t0,
+                           float* per_codebook, float* per_clip, vaura_stream_t s) {
+  return sequence_logprob(logprobs, seq_len, delays_host, B, K, T, t0, nullptr, nullptr, per_codebook, per_clip, as_stream(s));
+}
+
+int vaura_sequence_logprob_clips(const float* logprobs, int seq_len, const int32_t* delays_host, int B, int K, int T, int t0,
+                                 const int32_t* clip_timesteps, float* per_codebook, float* per_clip, vaura_stream_t s) {
+  if (!clip_timesteps) return VAURA_ERR_ARG;
+  return sequence_logprob(logprobs, seq_len, delays_host, B, K, T, t0, nullptr, clip_timesteps, per_codebook, per_clip, as_stream(s));
 }
 
 int vaura_sequence_logprob_starts(const float* logprobs, int seq_len, const int32_t* delays_host, int B, int K, int T,
                                   const int32_t* clip_t0, const int32_t* clip_timesteps, float* per_codebook, float* per_clip,
                                   vaura_stream_t s) {
-  if (!logprobs || !clip_t0 || !per_codebook || !per_clip || B <= 0 || K <= 0 || T <= 0 || seq_len <= 0) return VAURA_ERR_ARG;
-  if (K > 16) return VAURA_ERR_SHAPE;
-  PatternDelays pd;
-  const int span = pattern_delays_arg(delays_host, K, &pd);
-  if (span < 0) return span;
-  if (seq_len != T + span) return VAURA_ERR_SHAPE;
-  if (((uintptr_t)clip_t0 & 3u) != 0 || ((uintptr_t)clip_timesteps & 3u) != 0) return VAURA_ERR_ARG;
-  // both arrays are read back (one small copy each + a wait on the stream): 1 <= T_b <= T and 0 <= t0_b < T_b, every clip has a frame
-  // behind its prompt
-  std::vector<int32_t> t0((size_t)B), tb((size_t)B, T);
-  hipError_t e = hipMemcpyAsync(t0.data(), clip_t0, t0.size() * sizeof(int32_t), hipMemcpyDeviceToHost, as_stream(s));
-  if (e == hipSuccess && clip_timesteps)
-    e = hipMemcpyAsync(tb.data(), clip_timesteps, tb.size() * sizeof(int32_t), hipMemcpyDeviceToHost, as_stream(s));
-  if (e == hipSuccess) e = hipStreamSynchronize(as_stream(s));
-  if (e != hipSuccess) return (int)e;
-  for (int b = 0; b < B; ++b)
-    if (tb[b] < 1 || tb[b] > T || t0[b] < 0 || t0[b] >= tb[b]) return VAURA_ERR_ARG;
-  VA_LAUNCH(sequence_logprob_starts_kernel, dim3((unsigned)B), dim3(64 * K), 0, as_stream(s), logprobs, B, K, T, seq_len, clip_t0, pd,
-            per_codebook, per_clip, clip_timesteps);
-  return 0;
+  if (!clip_t0) return VAURA_ERR_ARG;
+  return sequence_logprob(logprobs, seq_len, delays_host, B, K, T, 0, clip_t0, clip_timesteps, per_codebook, per_clip, as_stream(s));
 }
 
 int vaura_select_candidates(const float* scores, const int32_t* codes, int B, int N, int K, int T, int32_t* codes_out, int32_t* winner,

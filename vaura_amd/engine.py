@@ -20,6 +20,7 @@ import torch
 
 from . import _lib as L
 from . import clip_params
+from . import ops
 from .synth import CodecCfg, SamplerCfg, fold_weight_norm
 
 
@@ -519,10 +520,43 @@ class DecoderEngine:
     def _delays_arg(self):
         return L.delays_host(self.delays) if self.delays is not None else None
 
+    # The pattern ops (ops.pattern_build_into / pattern_revert_into) and the sequence scores (_means) come in three forms each, and a
+    # call without lengths must not take the lengths' entry point.  The choice is stated once per op, there and below.
+    def _pattern_build(self):
+        """``codes_i32`` -> ``seq``; with per-clip lengths a slot past a clip's own end holds the special token, as in the sequence
+        built for T_b."""
+        ops.pattern_build_into(self.codes_i32, self.seq, self.cfg.d_codebook, self.delays,
+                               self.clip_T if self.lengths is not None else None, L.current_stream(self.dev))
+
+    def _pattern_revert(self, buf: torch.Tensor, out: torch.Tensor, fill, pad) -> torch.Tensor:
+        """Tokens (int32) or fp32 values in the layout of seq -> ``out`` (batch, K, T): ``fill`` where the sequence holds no frame, ``pad``
+        in the frames past a clip's own end (per-clip lengths only)."""
+        ops.pattern_revert_into(buf, out, fill, pad, self.delays, self.clip_T if self.lengths is not None else None,
+                                L.current_stream(self.dev))
+        return out
+
+    def _means(self, buf: torch.Tensor, S: int, delays, T: int, t0: Optional[int]):
+        """Fixed-order means of fp32 values ``buf`` (batch, K, S) in the pattern layout of ``delays`` (None: the default) over frames
+        t0 .. T - 1 — T_b - 1 with per-clip lengths; t0 = None: from every clip's own prompt length P_b — -> (per codebook (batch, K),
+        per clip (batch,))."""
+        Bn, K = self.batch, self.cfg.num_codebooks
+        f32 = dict(dtype=torch.float32, device=self.dev)
+        pcb, score = torch.empty(Bn, K, **f32), torch.empty(Bn, **f32)
+        a = (L.ptr(buf), S, L.delays_host(delays) if delays is not None else None, Bn, K, T)
+        clip_T = L.ptr(self.clip_T) if self.lengths is not None else None
+        o = (L.ptr(pcb), L.ptr(score), L.current_stream(self.dev))
+        if t0 is None:
+            L.check(self.lib.vaura_sequence_logprob_starts(*a, L.ptr(self.clip_P), clip_T, *o), "vaura_sequence_logprob_starts")
+        elif self.lengths is not None:
+            L.check(self.lib.vaura_sequence_logprob_clips(*a, t0, clip_T, *o), "vaura_sequence_logprob_clips")
+        else:
+            L.check(self.lib.vaura_sequence_logprob(*a, t0, *o), "vaura_sequence_logprob")
+        return pcb, score
+
     def start_sequence(self, prompt: Optional[torch.Tensor]):
         """codes = -1 everywhere but the prompt -> pattern sequence on device; returns Tp.  With per-clip prompt lengths
         (``_set_prompt_lengths``) clip b takes ``prompt[b, :, :P_b]`` and holds -1 behind it; Tp is then the shortest prompt."""
-        K, T = self.cfg.num_codebooks, self.T
+        T = self.T
         self.codes_i32.fill_(-1)
         Tp = 0
         if self.prompt_lengths is not None:
@@ -534,17 +568,7 @@ class DecoderEngine:
             Tp = prompt.shape[-1]
             assert Tp < (min(self.lengths) if self.lengths else T), "gt audio prompt can not be longer than max_new_tokens"
             self.codes_i32[..., :Tp] = prompt.to(self.dev, torch.int32)
-        if self.lengths is not None:       # a slot past a clip's own end holds the special token, as in the sequence built for T_b
-            L.check(self.lib.vaura_pattern_build_clips(L.ptr(self.codes_i32), L.ptr(self.seq), self.batch, K, T, self.S, self.cfg.d_codebook,
-                                                       self._delays_arg(), L.ptr(self.clip_T), L.current_stream(self.dev)),
-                    "vaura_pattern_build_clips")
-        elif self.delays is None:
-            L.check(self.lib.vaura_pattern_build(L.ptr(self.codes_i32), L.ptr(self.seq), self.batch, K, T,
-                                                 self.cfg.d_codebook, L.current_stream(self.dev)), "vaura_pattern_build")
-        else:
-            L.check(self.lib.vaura_pattern_build_delays(L.ptr(self.codes_i32), L.ptr(self.seq), self.batch, K, T, self.S,
-                                                        self.cfg.d_codebook, L.delays_host(self.delays), L.current_stream(self.dev)),
-                    "vaura_pattern_build_delays")
+        self._pattern_build()
         self._reset_state()
         return Tp
 
@@ -680,19 +704,7 @@ class DecoderEngine:
             raise err
 
     def revert(self) -> torch.Tensor:
-        K, T = self.cfg.num_codebooks, self.T
-        if self.lengths is not None:       # frames past a clip's own end: the special id
-            L.check(self.lib.vaura_pattern_revert_clips(L.ptr(self.seq), L.ptr(self.codes_i32), self.batch, K, T, self.S, -1,
-                                                        self.cfg.d_codebook, self._delays_arg(), L.ptr(self.clip_T),
-                                                        L.current_stream(self.dev)), "vaura_pattern_revert_clips")
-        elif self.delays is None:
-            L.check(self.lib.vaura_pattern_revert(L.ptr(self.seq), L.ptr(self.codes_i32), self.batch, K, T, self.S, -1,
-                                                  L.current_stream(self.dev)), "vaura_pattern_revert")
-        else:
-            L.check(self.lib.vaura_pattern_revert_delays(L.ptr(self.seq), L.ptr(self.codes_i32), self.batch, K, T, self.S, -1,
-                                                         L.delays_host(self.delays), L.current_stream(self.dev)),
-                    "vaura_pattern_revert_delays")
-        return self.codes_i32
+        return self._pattern_revert(self.seq, self.codes_i32, -1, self.cfg.d_codebook)      # frames past a clip's own end: the special id
 
     @torch.no_grad()
     def generate_codes(self, feats: torch.Tensor, max_new_tokens, *, prompt: Optional[torch.Tensor] = None,
@@ -796,35 +808,13 @@ class DecoderEngine:
 
     def _revert_f32(self, buf: torch.Tensor) -> torch.Tensor:
         """fp32 values in the layout of seq -> (batch, K, T), 0 where the sequence holds no frame."""
-        K, T, Bn = self.cfg.num_codebooks, self.T, self.batch
-        out = torch.empty(Bn, K, T, dtype=torch.float32, device=self.dev)
-        dl = L.delays_host(self.delays) if self.delays is not None else None
-        if self.lengths is not None:
-            L.check(self.lib.vaura_pattern_revert_clips_f32(L.ptr(buf), L.ptr(out), Bn, K, T, self.S, 0.0, 0.0, dl, L.ptr(self.clip_T),
-                                                            L.current_stream(self.dev)), "vaura_pattern_revert_clips_f32")
-            return out
-        L.check(self.lib.vaura_pattern_revert_delays_f32(L.ptr(buf), L.ptr(out), Bn, K, T, self.S, 0.0, dl, L.current_stream(self.dev)),
-                "vaura_pattern_revert_delays_f32")
-        return out
+        out = torch.empty(self.batch, self.cfg.num_codebooks, self.T, dtype=torch.float32, device=self.dev)
+        return self._pattern_revert(buf, out, 0.0, 0.0)
 
     def _sequence_means(self, buf: torch.Tensor, Tp: int):
         """Fixed-order means of values in the layout of seq over frames Tp .. T - 1 -> (per codebook (batch, K), per clip (batch,))."""
-        K, T, Bn = self.cfg.num_codebooks, self.T, self.batch
-        f32 = dict(dtype=torch.float32, device=self.dev)
-        pcb, score = torch.empty(Bn, K, **f32), torch.empty(Bn, **f32)
-        dl = L.delays_host(self.delays) if self.delays is not None else None
-        if self.prompt_lengths is not None:       # every clip's means over its own frames P_b .. T_b - 1
-            L.check(self.lib.vaura_sequence_logprob_starts(L.ptr(buf), self.S, dl, Bn, K, T, L.ptr(self.clip_P),
-                                                           L.ptr(self.clip_T) if self.lengths is not None else None, L.ptr(pcb), L.ptr(score),
-                                                           L.current_stream(self.dev)), "vaura_sequence_logprob_starts")
-            return pcb, score
-        if self.lengths is not None:       # every clip's means over its own frames Tp .. T_b - 1
-            L.check(self.lib.vaura_sequence_logprob_clips(L.ptr(buf), self.S, dl, Bn, K, T, Tp, L.ptr(self.clip_T), L.ptr(pcb), L.ptr(score),
-                                                          L.current_stream(self.dev)), "vaura_sequence_logprob_clips")
-            return pcb, score
-        L.check(self.lib.vaura_sequence_logprob(L.ptr(buf), self.S, dl, Bn, K, T, Tp, L.ptr(pcb), L.ptr(score), L.current_stream(self.dev)),
-                "vaura_sequence_logprob")
-        return pcb, score
+        # with per-clip prompt lengths: every clip's means over its own frames P_b .. T_b - 1
+        return self._means(buf, self.S, self.delays, self.T, None if self.prompt_lengths is not None else Tp)
 
     def _sequence_logprobs(self, Tp: int) -> Dict[str, torch.Tensor]:
         """The finished call's log-probabilities, reverted to (batch, K, T), and their fixed-order means over frames Tp .. T - 1."""
@@ -1078,17 +1068,7 @@ class DecoderEngine:
             else:                          # clip b: build_pattern_sequence(codes_b[..., :Ta_b - 1]) — the special id from Ta_b - 1 on
                 self.codes_i32.copy_(torch.where(torch.arange(Ta, device=self.dev).view(1, 1, Ta) < last, targets,
                                                  torch.full_like(targets, c.d_codebook)))
-            if lengths is not None:
-                L.check(self.lib.vaura_pattern_build_clips(L.ptr(self.codes_i32), L.ptr(self.seq), B, K, Ta, self.S, c.d_codebook,
-                                                           self._delays_arg(), L.ptr(self.clip_T), L.current_stream(self.dev)),
-                        "vaura_pattern_build_clips")
-            elif self.delays is None:
-                L.check(self.lib.vaura_pattern_build(L.ptr(self.codes_i32), L.ptr(self.seq), B, K, Ta, c.d_codebook,
-                                                     L.current_stream(self.dev)), "vaura_pattern_build")
-            else:
-                L.check(self.lib.vaura_pattern_build_delays(L.ptr(self.codes_i32), L.ptr(self.seq), B, K, Ta, self.S, c.d_codebook,
-                                                            L.delays_host(self.delays), L.current_stream(self.dev)),
-                        "vaura_pattern_build_delays")
+            self._pattern_build()
             self._reset_state()
             f32 = dict(dtype=torch.float32, device=self.dev)
             nll = torch.empty(B, K, Ta, **f32)
@@ -1154,14 +1134,7 @@ class DecoderEngine:
         B, K, Ta = nll.shape
         lay = torch.zeros(B, K, Ta + 1, dtype=torch.float32, device=self.dev)
         lay[..., 1:] = nll
-        pcb, clip = torch.empty(B, K, dtype=torch.float32, device=self.dev), torch.empty(B, dtype=torch.float32, device=self.dev)
-        if self.lengths is not None:
-            L.check(self.lib.vaura_sequence_logprob_clips(L.ptr(lay), Ta + 1, L.delays_host([0] * K), B, K, Ta, 0, L.ptr(self.clip_T),
-                                                          L.ptr(pcb), L.ptr(clip), L.current_stream(self.dev)), "vaura_sequence_logprob_clips")
-            return pcb, clip
-        L.check(self.lib.vaura_sequence_logprob(L.ptr(lay), Ta + 1, L.delays_host([0] * K), B, K, Ta, 0, L.ptr(pcb), L.ptr(clip),
-                                                L.current_stream(self.dev)), "vaura_sequence_logprob")
-        return pcb, clip
+        return self._means(lay, Ta + 1, [0] * K, Ta, 0)
 
 
 @torch.no_grad()

@@ -155,20 +155,45 @@ def sample(logits: torch.Tensor, batch: int, *, use_sampling: bool, temp: float 
     return out.to(torch.int64)[..., None]
 
 
+# The pattern ops come in three forms — per-clip lengths / the default delays / explicit delays —, and a call without lengths must not
+# take the lengths' entry point: that one reads the array back and waits on the stream.  The choice is stated once, in the two
+# functions below (enqueue only: no allocation, no wait), for the ops behind them and for the engine.
+def pattern_build_into(codes: torch.Tensor, seq: torch.Tensor, special: int, delays, clip_T: Optional[torch.Tensor], stream: int) -> None:
+    """codes (B, K, T) int32 -> seq (B, K, S) int32; ``delays`` None = the default 0..K-1, ``clip_T`` (B,) int32 = per-clip lengths."""
+    (B, K, T), S = codes.shape, seq.shape[-1]
+    a = (L.ptr(codes), L.ptr(seq), B, K, T)
+    dl = L.delays_host(delays) if delays is not None else None
+    if clip_T is not None:
+        L.check(L.lib().vaura_pattern_build_clips(*a, S, special, dl, L.ptr(clip_T), stream), "vaura_pattern_build_clips")
+    elif delays is None:
+        L.check(L.lib().vaura_pattern_build(*a, special, stream), "vaura_pattern_build")
+    else:
+        L.check(L.lib().vaura_pattern_build_delays(*a, S, special, dl, stream), "vaura_pattern_build_delays")
+
+
+def pattern_revert_into(seq: torch.Tensor, out: torch.Tensor, fill, pad, delays, clip_T: Optional[torch.Tensor], stream: int) -> None:
+    """seq (B, K, S) -> out (B, K, T), both int32 (tokens) or both fp32 (values in the layout of seq): ``fill`` where the sequence holds
+    no frame, ``pad`` in the frames past a clip's own end (``clip_T`` only)."""
+    (B, K, S), T, f32 = seq.shape, out.shape[-1], out.dtype == torch.float32
+    a = (L.ptr(seq), L.ptr(out), B, K, T, S, fill)
+    dl = L.delays_host(delays) if delays is not None else None
+    if clip_T is not None:
+        name = "vaura_pattern_revert_clips_f32" if f32 else "vaura_pattern_revert_clips"
+        L.check(getattr(L.lib(), name)(*a, pad, dl, L.ptr(clip_T), stream), name)
+    elif f32 or delays is not None:        # (fp32 has no default-delays entry point of its own: NULL delays there)
+        name = "vaura_pattern_revert_delays_f32" if f32 else "vaura_pattern_revert_delays"
+        L.check(getattr(L.lib(), name)(*a, dl, stream), name)
+    else:
+        L.check(L.lib().vaura_pattern_revert(*a, stream), "vaura_pattern_revert")
+
+
 def pattern_build(codes: torch.Tensor, special: int, delays: Optional[Sequence[int]] = None) -> torch.Tensor:
     """codes (B, K, T) -> pattern sequence (B, K, T + max(d) + 1); ``delays`` None = the default 0..K-1."""
     _cuda(codes)
     B, K, T = codes.shape
-    ci = codes.to(torch.int32).contiguous()
-    if delays is None:
-        seq = torch.empty(B, K, T + K, dtype=torch.int32, device=codes.device)
-        L.check(L.lib().vaura_pattern_build(L.ptr(ci), L.ptr(seq), B, K, T, special, L.current_stream()), "vaura_pattern_build")
-    else:
-        d = L.check_delays(delays, K)
-        S = T + max(d) + 1
-        seq = torch.empty(B, K, S, dtype=torch.int32, device=codes.device)
-        L.check(L.lib().vaura_pattern_build_delays(L.ptr(ci), L.ptr(seq), B, K, T, S, special, L.delays_host(d), L.current_stream()),
-                "vaura_pattern_build_delays")
+    d = None if delays is None else L.check_delays(delays, K)
+    seq = torch.empty(B, K, T + (K if d is None else max(d) + 1), dtype=torch.int32, device=codes.device)
+    pattern_build_into(codes.to(torch.int32).contiguous(), seq, special, d, None, L.current_stream())
     torch.cuda.current_stream().synchronize()
     return seq.to(codes.dtype)
 
@@ -177,15 +202,9 @@ def pattern_revert(seq: torch.Tensor, timesteps: int, fill: int, delays: Optiona
     """pattern sequence (B, K, S) -> codes (B, K, timesteps); ``delays`` None = the default 0..K-1."""
     _cuda(seq)
     B, K, S = seq.shape
-    si = seq.to(torch.int32).contiguous()
+    d = None if delays is None else L.check_delays(delays, K)
     codes = torch.empty(B, K, timesteps, dtype=torch.int32, device=seq.device)
-    if delays is None:
-        L.check(L.lib().vaura_pattern_revert(L.ptr(si), L.ptr(codes), B, K, timesteps, S, fill, L.current_stream()),
-                "vaura_pattern_revert")
-    else:
-        d = L.check_delays(delays, K)
-        L.check(L.lib().vaura_pattern_revert_delays(L.ptr(si), L.ptr(codes), B, K, timesteps, S, fill, L.delays_host(d),
-                                                    L.current_stream()), "vaura_pattern_revert_delays")
+    pattern_revert_into(seq.to(torch.int32).contiguous(), codes, fill, 0, d, None, L.current_stream())
     torch.cuda.current_stream().synchronize()
     return codes.to(seq.dtype)
 
