@@ -662,6 +662,32 @@ size_t vaura_dac_decode_clips_workspace_elems(const vaura_codec* c, int B, const
 /* gap (latent frames) of vaura_dac_decode_clips for this geometry, from the convs' taps, dilations and the rates; -1: c NULL or not a
  * geometry the decode pass takes.  Reads no device pointer.                                                                          */
 int vaura_dac_clips_gap(const vaura_codec* c);
+/* A WINDOW of every clip in one decode pass: the samples of clip b's frames [starts[b], starts[b] + counts[b]), bit for bit those of
+ * the whole clip's decode (vaura_dac_decode / vaura_dac_decode_clips), at the cost and the workspace of the window.
+ * codes (B, K, T_max) int32, the caller's padded tensor (read only); lengths, starts, counts: B ints each ON THE HOST; clip b has
+ * lengths[b] frames, 1 .. T_max (lengths NULL: T_max each) -> wav (B, 1, N_max*hop): wav[b, 0, :counts[b]*hop] are the samples of
+ * those frames, every sample behind them is 0.  counts[b] == 0 — a clip that is finished or parked — is allowed: nothing of the clip
+ * is read or decoded, its row is 0.
+ * How: the decoder is a finite-support conv stack, so the samples of a frame depend on the codes of H = vaura_dac_decode_halo(c)
+ * frames either side and no further.  Per clip the frames [max(0, s - H), min(len, s + n + H)) are packed behind one another as
+ * the clips of vaura_dac_decode_clips are (the same gap, the same pass, the same kernels and instance choice), and unpacking skips
+ * the halo samples in front.  A window that reaches an end of its clip is clamped there, so the zero padding at that end is the
+ * clip's own.  Nothing in the call waits for the device or copies from it; the host arrays are read before it returns.
+ * The 4 workspaces must hold vaura_dac_decode_window_workspace_elems(c, B, lengths, starts, counts) floats each (0: c / starts /
+ * counts NULL, B <= 0, arguments the call refuses, or a sequence beyond the int range; lengths NULL there: no window is clamped at
+ * its clip's end, an upper bound).
+ * VAURA_ERR_ARG: NULL c / codes / wav / starts / counts (not dereferenced), B, T_max or N_max <= 0, a length outside 1 .. T_max,
+ * starts[b] < 0, counts[b] < 0, starts[b] + counts[b] > lengths[b], counts[b] > N_max, every count 0, workspaces NULL or too small;
+ * VAURA_ERR_SHAPE: as vaura_dac_decode, a descriptor without a halo, or packed windows whose largest level (rows x channels) does
+ * not fit an int; VAURA_ERR_DTYPE: precision.  All before any launch.                                                                */
+int vaura_dac_decode_window(const vaura_codec* c, const int32_t* codes, int B, int T_max, const int32_t* lengths, const int32_t* starts,
+                            const int32_t* counts, float* wav, int N_max, vaura_stream_t s);
+size_t vaura_dac_decode_window_workspace_elems(const vaura_codec* c, int B, const int32_t* lengths, const int32_t* starts,
+                                               const int32_t* counts);
+/* H of vaura_dac_decode_window: the frames of context either side that the samples of one latent frame depend on, from the convs'
+ * taps, dilations and strides (the sample interval of a frame taken backwards through the layers; a transposed conv has k = 2r and
+ * pad ceil(r / 2)): 10 for the 44.1 kHz geometry.  -1: c NULL or not such a geometry.  Reads no device pointer.                      */
+int vaura_dac_decode_halo(const vaura_codec* c);
 /* Op-level access for parity tests: ONE convolution of the decoder (WNConv1d / WNConvTranspose1d of descript-audio-codec's
  * DecoderBlock / ResidualUnit) in the arithmetic of `precision` (vaura_codec.precision; weights laid out for it).
  * in (B, Lin, Cin) fp32 channels-last, already activated -> out (B, Lout, Cout) fp32 = conv(in) + bias,

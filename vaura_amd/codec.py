@@ -168,6 +168,19 @@ class DacModelWrapper(nn.Module):
         return self.engine().decode_clips(codes, lengths)
 
     @torch.no_grad()
+    def decode_window(self, codes: torch.Tensor, starts, counts, lengths=None):
+        """The samples of frames [starts[b], starts[b] + counts[b]) of every clip in ONE codec pass over the windows: codes (B, 9, T_max),
+        the whole padded tensor -> wav (B, 1, 512*max(counts)), the bits the whole decode has there, zeros behind them
+        (``CodecEngine.decode_window``)."""
+        return self.engine().decode_window(codes, starts, counts, lengths)
+
+    @torch.no_grad()
+    def decode_windowed(self, codes: torch.Tensor, window: int, lengths=None):
+        """``decode`` / ``decode_clips`` bit for bit as successive window calls of ``window`` frames: the codec's workspaces follow the
+        window, not the clip (``CodecEngine.decode_windowed``)."""
+        return self.engine().decode_windowed(codes, window, lengths)
+
+    @torch.no_grad()
     def encode_clips(self, wav: torch.Tensor, sample_lengths):
         """A padded batch in ONE encoder pass: wav (B, 1, N) | (B, N), ``sample_lengths`` one int per clip -> codes (B, 9, ceil(N / 512))
         with ``codes[b, :, :ceil(n_b / 512)]`` the bits of ``encode(wav[b:b+1, :, :n_b])`` and 0 behind them

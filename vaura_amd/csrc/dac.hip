@@ -1919,12 +1919,14 @@ struct ClipChunk {                    // up to VA_CLIP_CHUNK clips by value: a l
   int len[VA_CLIP_CHUNK];             // its latent frames
   int64_t aux[VA_CLIP_CHUNK];         // its samples (encode)
 };
+struct WindowLayout;
 struct ClipLayout {
   int B, gap;
   int64_t total;                      // latent rows of the packed sequence: off[B - 1] + len[B - 1]
   const int* off;
   const int* len;
   const int64_t* aux;
+  const WindowLayout* win = nullptr;  // vaura_dac_decode_window: the packed clips are windows of the caller's clips (see WindowLayout)
 };
 static ClipChunk va_clip_chunk(const ClipLayout& l, int b0, int bend) {
   ClipChunk k;
@@ -1974,6 +1976,67 @@ __global__ __launch_bounds__(256) void clips_unpack_wav_kernel(const float* __re
   const float* src = packed + (size_t)k.off[i] * hop;
   for (int64_t u = (int64_t)blockIdx.x * 256 + threadIdx.x; u < n_out; u += (int64_t)gridDim.x * 256)
     wav[(size_t)b * n_out + u] = u < n ? src[u] : 0.f;
+}
+
+// A window of every clip in ONE pass (vaura_dac_decode_window).  The decoder is a finite-support conv stack: the samples of latent
+// frame f depend on the codes of frames f - H .. f + H only (H = va_decode_halo, from the conv descriptors).  So the frames
+// [lo, hi) = [max(0, s - H), min(len, s + n + H)) of a clip, decoded as a clip of their own, give the samples of [s, s + n) exactly:
+// a frame at least H from a cut end sees what it sees in the whole clip, and an end that is the clip's own (lo = 0, hi = len) has the
+// zero padding the whole clip has there.  The windows are the clips of a ClipLayout (a clip with count 0 has none): packing reads
+// from frame lo of the caller's tensor, unpacking skips the (s - lo) * hop samples in front.
+struct WindowChunk {                  // up to VA_CLIP_CHUNK entries by value
+  int n;
+  int b[VA_CLIP_CHUNK];               // the caller's clip
+  int off[VA_CLIP_CHUNK];             // pack: first latent row of the window in the packed sequence; unpack: of the frames asked for
+  int len[VA_CLIP_CHUNK];             // pack: latent frames of the window (the gap behind it included); unpack: the frames asked for
+  int src[VA_CLIP_CHUNK];             // pack: first frame of the window in the clip
+  int aux[VA_CLIP_CHUNK];             // pack: the window's own frames (len without the gap)
+};
+struct WindowLayout {
+  int B, n_max;                       // the caller's clips, the width of its output in frames
+  const int* clip;                    // per window: the caller's clip
+  const int* lo;                      // per window: its first frame in the clip
+  const int* skip;                    // per window: halo frames in front of the frames asked for
+  const int* window;                  // per caller's clip (B): index of its window, -1 for count 0
+  const int* count;                   // per caller's clip (B)
+};
+// codes (B, K, Tmax) -> packed (K, total): the window's frames from frame src[i] of clip b[i] on, code 0 on the gap frames behind it
+__global__ __launch_bounds__(256) void window_pack_codes_kernel(const int32_t* __restrict__ codes, int32_t* __restrict__ packed, WindowChunk k,
+                                                                int K, int Tmax, int64_t total) {
+  const int i = blockIdx.y, kk = blockIdx.z;
+  const int32_t* src = codes + ((size_t)k.b[i] * K + kk) * Tmax + k.src[i];
+  for (int t = blockIdx.x * 256 + threadIdx.x; t < k.len[i]; t += gridDim.x * 256)
+    packed[(size_t)kk * total + k.off[i] + t] = t < k.aux[i] ? src[t] : 0;
+}
+// packed samples -> wav (B, n_out): the len[i] * hop samples from packed frame off[i] on, 0 behind them (len 0: a row of zeros, nothing read)
+__global__ __launch_bounds__(256) void window_unpack_wav_kernel(const float* __restrict__ packed, float* __restrict__ wav, WindowChunk k,
+                                                                int64_t n_out, int hop) {
+  const int i = blockIdx.y, b = k.b[i];
+  const int64_t n = (int64_t)k.len[i] * hop;
+  const float* src = packed + (size_t)k.off[i] * hop;
+  for (int64_t u = (int64_t)blockIdx.x * 256 + threadIdx.x; u < n_out; u += (int64_t)gridDim.x * 256)
+    wav[(size_t)b * n_out + u] = u < n ? src[u] : 0.f;
+}
+// windows w0 .. of the layout: what window_pack_codes_kernel reads and where it writes
+static WindowChunk va_window_pack_chunk(const ClipLayout& l, int w0) {
+  WindowChunk k;
+  k.n = l.B - w0 < VA_CLIP_CHUNK ? l.B - w0 : VA_CLIP_CHUNK;
+  for (int i = 0; i < k.n; ++i) {
+    const int w = w0 + i;
+    k.b[i] = l.win->clip[w]; k.off[i] = l.off[w]; k.src[i] = l.win->lo[w]; k.aux[i] = l.len[w];
+    k.len[i] = l.len[w] + (w + 1 < l.B ? l.gap : 0);
+  }
+  return k;
+}
+// the caller's clips b0 .. : where window_unpack_wav_kernel finds the frames asked for (a clip with count 0 has no window: len 0)
+static WindowChunk va_window_unpack_chunk(const ClipLayout& l, int b0) {
+  WindowChunk k;
+  k.n = l.win->B - b0 < VA_CLIP_CHUNK ? l.win->B - b0 : VA_CLIP_CHUNK;
+  for (int i = 0; i < k.n; ++i) {
+    const int b = b0 + i, w = l.win->window[b];
+    k.b[i] = b; k.len[i] = l.win->count[b]; k.off[i] = w < 0 ? 0 : l.off[w] + l.win->skip[w]; k.src[i] = k.aux[i] = 0;
+  }
+  return k;
 }
 
 static unsigned va_clip_gx(int64_t items) {                     // workgroups along x for `items` per clip: grid-stride beyond 256
@@ -2072,7 +2135,14 @@ static int va_dac_decode_pass(const vaura_codec* c, const int32_t* codes, int B,
   int rc = 0;
   if (lay) {
     int32_t* packed = reinterpret_cast<int32_t*>(Z);              // Z is first written by the first transposed conv
-    for (int b0 = 0; b0 < Bc; b0 += VA_CLIP_CHUNK) {
+    for (int w0 = 0; lay->win && w0 < lay->B; w0 += VA_CLIP_CHUNK) {
+      const WindowChunk k = va_window_pack_chunk(*lay, w0);
+      int widest = 0;
+      for (int i = 0; i < k.n; ++i) widest = std::max(widest, k.len[i]);
+      VA_LAUNCH(window_pack_codes_kernel, dim3(va_clip_gx(widest), k.n, c->n_codebooks), dim3(256), 0, s, codes, packed, k,
+                c->n_codebooks, Tc, lay->total);
+    }
+    for (int b0 = 0; !lay->win && b0 < Bc; b0 += VA_CLIP_CHUNK) {
       const ClipChunk k = va_clip_chunk(*lay, b0, Bc);
       VA_LAUNCH(clips_pack_codes_kernel, dim3(va_clip_gx(Tc + lay->gap), k.n, c->n_codebooks), dim3(256), 0, s, codes, packed, k,
                 c->n_codebooks, Tc, lay->total, lay->gap, Bc);
@@ -2120,7 +2190,12 @@ static int va_dac_decode_pass(const vaura_codec* c, const int32_t* codes, int B,
   const int hop = L / T;
   rc = launch_conv_out(c->conv_out, A, R, B, L, pr, s);            // the last residual stream has been consumed: R takes the packed samples
   if (rc) return rc;
-  for (int b0 = 0; b0 < Bc; b0 += VA_CLIP_CHUNK) {
+  for (int b0 = 0; lay->win && b0 < Bc; b0 += VA_CLIP_CHUNK) {
+    const WindowChunk k = va_window_unpack_chunk(*lay, b0);
+    const int64_t n_out = (int64_t)lay->win->n_max * hop;
+    VA_LAUNCH(window_unpack_wav_kernel, dim3(va_clip_gx(n_out), k.n), dim3(256), 0, s, R, wav, k, n_out, hop);
+  }
+  for (int b0 = 0; !lay->win && b0 < Bc; b0 += VA_CLIP_CHUNK) {
     const ClipChunk k = va_clip_chunk(*lay, b0, Bc);
     VA_LAUNCH(clips_unpack_wav_kernel, dim3(va_clip_gx((int64_t)Tc * hop), k.n), dim3(256), 0, s, R, wav, k, (int64_t)Tc * hop, hop);
   }
@@ -2181,6 +2256,101 @@ int vaura_dac_decode_clips(const vaura_codec* c, const int32_t* codes, int B, in
   for (int i = 0; i < 4; ++i) if (!c->ws[i]) return VAURA_ERR_ARG;
   const int pr = c->precision;
   if (pr < 0 || pr > 4) return VAURA_ERR_DTYPE;
+  return va_dac_decode_pass(c, codes, B, T_max, wav, &lay, as_stream(s_));
+}
+
+static inline int64_t va_floor_div(int64_t a, int64_t b) { return a >= 0 ? a / b : -((-a + b - 1) / b); }
+// Frames of context either side that the samples of one latent frame depend on: the rows [0, hop) of the last level, taken backwards
+// through the layers.  A k-tap conv of dilation d widens the interval by (k - 1) / 2 * d rows either side; a transposed conv (stride
+// r, k = 2r, pad ceil(r / 2)) writes row o from the input rows j with o = j * r - pad + t, 0 <= t < k, so [lo, hi] comes from
+// [ceil((lo + pad - k + 1) / r), floor((hi + pad) / r)].  At the latent level the frame itself is row 0.  -1: not such a geometry.
+static int va_decode_halo(const vaura_codec* c) {
+  if (va_clips_gap_decode(c) < 0) return -1;
+  auto plain = [](const vaura_conv& cv) { return cv.stride == 1 && cv.taps >= 1 && (cv.taps & 1) && cv.dilation >= 1; };
+  if (!plain(c->conv_in) || !plain(c->conv_out)) return -1;
+  int64_t hop = 1;
+  for (int b = 0; b < c->n_blocks; ++b) {
+    if (c->up[b].stride != c->rates[b] || c->up[b].taps != 2 || hop > 0x7fffffff / c->rates[b]) return -1;
+    hop *= c->rates[b];
+    for (int u = 0; u < 3; ++u)
+      for (int i = 0; i < 2; ++i) if (!plain(c->res[b][u][i])) return -1;
+  }
+  int64_t lo = -va_conv_reach(c->conv_out), hi = hop - 1 + va_conv_reach(c->conv_out);
+  for (int b = c->n_blocks - 1; b >= 0; --b) {
+    for (int u = 0; u < 3; ++u)
+      for (int i = 0; i < 2; ++i) { lo -= va_conv_reach(c->res[b][u][i]); hi += va_conv_reach(c->res[b][u][i]); }
+    const int64_t r = c->rates[b], pad = (r + 1) / 2, k = 2 * r;
+    lo = -va_floor_div(-(lo + pad - k + 1), r);
+    hi = va_floor_div(hi + pad, r);
+  }
+  lo -= va_conv_reach(c->conv_in); hi += va_conv_reach(c->conv_in);
+  const int64_t h = std::max(-lo, hi);
+  return h < 0 || h > 0x3fffffff ? -1 : (int)h;
+}
+
+int vaura_dac_decode_halo(const vaura_codec* c) { return c ? va_decode_halo(c) : -1; }
+
+// the windows of a decode_window call on the host: one per clip with count > 0
+struct WindowPlan {
+  std::vector<int> clip, lo, skip, len, off, window, count;
+  int64_t total = 0;                  // latent rows of the packed windows; 0: refused arguments, -1: beyond the int range
+  int gap = 0;
+};
+// T_max <= 0: lengths are checked against >= 1 only; lengths NULL: every clip has T_max frames (T_max <= 0: no end to clamp at, an
+// upper bound of the window).  n_max <= 0: counts are not checked against it.
+static WindowPlan va_window_plan(const vaura_codec* c, int B, int T_max, const int32_t* lengths, const int32_t* starts, const int32_t* counts,
+                                 int n_max) {
+  WindowPlan p;
+  const int H = va_decode_halo(c);
+  p.gap = va_clips_gap_decode(c);
+  if (H < 0 || p.gap < 0) return p;
+  p.window.assign((size_t)B, -1);
+  p.count.assign(counts, counts + B);
+  for (int b = 0; b < B; ++b) {
+    const int64_t len = lengths ? lengths[b] : (T_max > 0 ? T_max : 0x7fffffff);
+    const int64_t s = starts[b], n = counts[b];
+    if (len < 1 || (T_max > 0 && len > T_max) || s < 0 || n < 0 || s + n > len || (n_max > 0 && n > n_max)) { p.clip.clear(); return p; }
+    if (n == 0) continue;
+    const int64_t lo = std::max<int64_t>(0, s - H), hi = std::min(len, s + n + H);
+    p.window[(size_t)b] = (int)p.clip.size();
+    p.clip.push_back(b); p.lo.push_back((int)lo); p.skip.push_back((int)(s - lo)); p.len.push_back((int)(hi - lo));
+  }
+  if (p.clip.empty()) return p;                        // every count is 0
+  p.off.resize(p.clip.size());
+  if (!va_clips_offsets(p.len.data(), (int)p.clip.size(), p.gap, p.off.data(), &p.total)) p.total = -1;
+  return p;
+}
+
+size_t vaura_dac_decode_window_workspace_elems(const vaura_codec* c, int B, const int32_t* lengths, const int32_t* starts,
+                                               const int32_t* counts) {
+  if (!c || !starts || !counts || B <= 0) return 0;
+  const WindowPlan p = va_window_plan(c, B, 0, lengths, starts, counts, 0);
+  return p.total > 0 ? va_decode_clips_elems(c, p.total) : 0;
+}
+
+int vaura_dac_decode_window(const vaura_codec* c, const int32_t* codes, int B, int T_max, const int32_t* lengths, const int32_t* starts,
+                            const int32_t* counts, float* wav, int N_max, vaura_stream_t s_) {
+  if (!c || !codes || !wav || !starts || !counts || B <= 0 || T_max <= 0 || N_max <= 0) return VAURA_ERR_ARG;
+  if (c->n_blocks < 1 || c->n_blocks > 4 || c->n_units != 3 || c->n_codebooks > 16 || c->codebook_dim > 8)
+    return VAURA_ERR_SHAPE;
+  if (va_decode_halo(c) < 0) return VAURA_ERR_SHAPE;
+  const WindowPlan p = va_window_plan(c, B, T_max, lengths, starts, counts, N_max);
+  if (p.total == 0) return VAURA_ERR_ARG;                // a length, start or count out of range, or nothing to decode
+  int64_t hop = 1;
+  for (int b = 0; b < c->n_blocks; ++b) hop *= c->rates[b];
+  // as vaura_dac_decode_clips: the largest level of the packed windows must fit the int arithmetic of the launches
+  if (p.total < 0 || va_decode_clips_elems(c, p.total) > (size_t)0x7fffffff || (int64_t)B * T_max > 0x7fffffff ||
+      (int64_t)N_max * hop > 0x7fffffff) return VAURA_ERR_SHAPE;
+  if (c->ws_elems < va_decode_clips_elems(c, p.total)) return VAURA_ERR_ARG;
+  for (int i = 0; i < 4; ++i) if (!c->ws[i]) return VAURA_ERR_ARG;
+  const int pr = c->precision;
+  if (pr < 0 || pr > 4) return VAURA_ERR_DTYPE;
+  WindowLayout win;
+  win.B = B; win.n_max = N_max; win.clip = p.clip.data(); win.lo = p.lo.data(); win.skip = p.skip.data();
+  win.window = p.window.data(); win.count = p.count.data();
+  ClipLayout lay;
+  lay.B = (int)p.clip.size(); lay.gap = p.gap; lay.total = p.total; lay.off = p.off.data(); lay.len = p.len.data(); lay.aux = nullptr;
+  lay.win = &win;
   return va_dac_decode_pass(c, codes, B, T_max, wav, &lay, as_stream(s_));
 }
 

@@ -1312,6 +1312,87 @@ class CodecEngine:
             wav.record_stream(caller)
         return wav
 
+    def _window_call(self, ci: torch.Tensor, n, starts, counts) -> torch.Tensor:
+        """vaura_dac_decode_window on int32 codes of this device, inside the engine's stream context; grows the workspaces to the
+        window's size when they are smaller."""
+        B, K, T = ci.shape
+        host = [(C.c_int32 * B)(*v) for v in (n, starts, counts)]
+        need = self.lib.vaura_dac_decode_window_workspace_elems(C.byref(self.c), B, *host)
+        if need == 0:
+            raise L.VauraHipError(f"decode_window: windows {list(zip(starts, counts))} of clips of {n} frames are beyond what one pass can index")
+        if self._ws_key is None or self._ws_key < need:
+            self._ws = [torch.empty(need, dtype=torch.float32, device=self.dev) for _ in range(4)]
+            for i in range(4):
+                self.c.ws[i] = L.ptr(self._ws[i])
+            self.c.ws_elems = need
+            self._ws_key = need
+        N = max(counts)
+        wav = torch.empty(B, 1, N * self.cfg.hop, dtype=torch.float32, device=self.dev)
+        L.check(self.lib.vaura_dac_decode_window(C.byref(self.c), L.ptr(ci), B, T, *host, L.ptr(wav), N, L.current_stream(self.dev)),
+                "vaura_dac_decode_window")
+        return wav
+
+    @staticmethod
+    def _window_args(B: int, n, starts, counts):
+        from . import clip_params
+        out = []
+        for name, v in (("starts", starts), ("counts", counts)):
+            if not clip_params.is_per_clip(v):
+                raise L.VauraHipError(f"{name} must be one integer per clip (a list, tuple or 1-D tensor), got {v!r}")
+            v = clip_params._int_list(name, v)
+            if len(v) != B:
+                raise L.VauraHipError(f"{name} has {len(v)} values for a batch of {B} clips")
+            out.append(v)
+        s, c = out
+        if any(a < 0 or k < 0 or a + k > t for a, k, t in zip(s, c, n)):
+            raise L.VauraHipError(f"every window must lie inside its clip: lengths {n}, starts {s}, counts {c}")
+        if max(c) < 1:
+            raise L.VauraHipError(f"decode_window: every count is 0, there is nothing to decode (counts {c})")
+        return s, c
+
+    @torch.no_grad()
+    def decode_window(self, codes: torch.Tensor, starts, counts, lengths=None) -> torch.Tensor:
+        """A window of every clip: codes (B, K, T_max) on device, the whole padded tensor; ``starts`` / ``counts`` one int per clip
+        (host values), ``lengths`` as in ``decode_clips`` (None: T_max each) -> wav (B, 1, max(counts)*hop):
+        ``wav[b, :, :counts[b]*hop]`` is bit for bit ``decode_clips(codes, lengths)[b, :, starts[b]*hop:(starts[b] + counts[b])*hop]``,
+        zeros behind it.  A count of 0 (a finished clip) gives a row of zeros and reads nothing of the clip.  ONE codec pass over the
+        windows, each with ``codec_clips.decode_halo`` frames of context either side (``codec_clips.window_layout``;
+        vaura_dac_decode_window): its cost and its workspaces follow the windows, not T_max."""
+        B, K, T = codes.shape
+        n = [T] * B if lengths is None else _clip_lengths("lengths", lengths, B, T)
+        s, c = self._window_args(B, n, starts, counts)
+        with off_null_stream(self.dev) as caller:
+            ci = codes.to(self.dev, torch.int32).contiguous()
+            wav = self._window_call(ci, n, s, c)
+            self._codes_keepalive = ci
+        if caller is not None:
+            wav.record_stream(caller)
+        return wav
+
+    @torch.no_grad()
+    def decode_windowed(self, codes: torch.Tensor, window: int, lengths=None) -> torch.Tensor:
+        """``decode(codes)`` — with ``lengths``, ``decode_clips(codes, lengths)`` — bit for bit, as successive ``decode_window`` calls of
+        ``window`` frames: codes (B, K, T) -> wav (B, 1, T*hop).  The workspaces are sized by the window (plus its halo), not by T.
+        A clip that has ended gets count 0 in the later calls.  ``window`` >= T: the one pass itself."""
+        B, K, T = codes.shape
+        if isinstance(window, bool) or not isinstance(window, int) or window < 1:
+            raise L.VauraHipError(f"window must be a positive number of frames, got {window!r}")
+        n = [T] * B if lengths is None else _clip_lengths("lengths", lengths, B, T)
+        if window >= T:
+            return self.decode(codes) if lengths is None or min(n) == T else self.decode_clips(codes, n)
+        hop = self.cfg.hop
+        with off_null_stream(self.dev) as caller:
+            ci = codes.to(self.dev, torch.int32).contiguous()
+            wav = torch.zeros(B, 1, T * hop, dtype=torch.float32, device=self.dev)
+            for s in range(0, max(n), window):
+                counts = [max(0, min(window, t - s)) for t in n]
+                part = self._window_call(ci, n, [min(s, t) for t in n], counts)
+                wav[:, :, s * hop:s * hop + part.shape[-1]] = part
+            self._codes_keepalive = ci
+        if caller is not None:
+            wav.record_stream(caller)
+        return wav
+
 
 class CodecConvOp:
     """ONE decoder convolution through ``vaura_dac_conv`` (op-level parity tests): folded Conv1d (Cout, Cin, k) or

@@ -10,6 +10,11 @@ the rest by the captured decode-step graph; the waveform of the whole clip is de
 ``generate_long`` keeps one duration per call.  ``generate_long_clips`` takes one duration per clip: clip b follows its own
 ``chunk_schedule``, and the schedules are merged into ONE ``generate_tokens`` call per chunk index (``clip_chunk_plan``) over the
 per-clip lengths that call already serves; a clip whose schedule has ended stays in the batch, parked, until the longest is done.
+
+``generate_long_stream`` / ``generate_long_clips_stream`` run the same loops as generators and hand out audio while the window slides:
+after chunk c the tokens of the frames [0, N_c) are final, and the samples of a frame depend on ``codec_clips.decode_halo`` frames
+either side, so [emitted, N_c - halo) is decoded then — one ``decode_window`` codec pass over that block and its halo — and the rest
+on the last chunk.  The blocks are bit for bit the slices of the one decode at the end.
 """
 from __future__ import annotations
 
@@ -45,39 +50,28 @@ def chunk_schedule(duration: float, model_max_duration: float = 2.56, stride: fl
     return out
 
 
-@torch.no_grad()
-def generate_long(model, frames: torch.Tensor, duration: float, *, stride: float = 0.64, model_max_duration: Optional[float] = None,
-                  vfps: float = 25, frame_step: int = 1, clip_indices=None, use_sampling: bool = True, temp: float = 1.0,
-                  top_k: int = 128, top_p: float = 0.0, cfg_scale: float = 1.0, return_relevance: bool = False, video_lengths=None) -> dict:
-    """frames: whatever the feature-extractor plugin accepts, segments on dim 1 — raw (B, S, C, T, H, W) or, with the
-    pass-through ``MotionFormer``, features (B, S, t, 768).  Returns {"generated_audio", "sampled_indices"}.
-    ``use_sampling``, ``temp``, ``top_k``, ``top_p``, ``cfg_scale``: scalars, or one value per clip (length-B list / tuple / 1-D
-    tensor) — every chunk of clip b is sampled with clip b's values (``VAURAModel.generate_tokens``).
-    ``return_relevance``: passed to every chunk; the result gains "relevance", "logprob_cond" and "logprob_null" (B, K, T), the chunks'
-    values concatenated with the prompt overlap removed the way the tokens are (every frame carries the values of the chunk that
-    GENERATED it).  No sequence means are returned here: chunks overlap, and a mean per chunk is not a mean of the clip — reduce the
-    (B, K, T) values as needed.
-    One ``duration`` for the whole call: a per-clip sequence of durations, or ``video_lengths``, is refused (per-clip lengths are a
-    feature of one ``generate()`` call; the chunk schedule here is shared by the batch)."""
-    REL = ("relevance", "logprob_cond", "logprob_null")
+REL = ("relevance", "logprob_cond", "logprob_null")
+
+
+def _long_setup(model, frames, duration, stride, model_max_duration, vfps, clip_indices, use_sampling, temp, top_k, top_p, cfg_scale,
+                video_lengths, who):
+    """The checks of ``generate_long`` and what its loop needs: (schedule, keywords of every generate call)."""
     from .clip_params import check_lengths, refuse_lengths
-    refuse_lengths("generate_long", duration, video_lengths)
+    refuse_lengths(who, duration, video_lengths)
     check_lengths(frames.shape[0], use_sampling=use_sampling, temp=temp, top_k=top_k, top_p=top_p, cfg_scale=cfg_scale)
     if model_max_duration is None:   # scripts/generate.py:221-226
         model_max_duration = 2.56 if model.sampler.config.block_size > 64 else 0.64
     sched = chunk_schedule(duration, model_max_duration, stride, vfps)
     kw = dict(clip_indices=clip_indices, return_sampled_indices=True, use_sampling=use_sampling, temp=temp, top_k=top_k,
               top_p=top_p, remove_prompts=False, prompt_is_encoded=True, cfg_scale=cfg_scale)
-    if len(sched) == 1 and sched[0]["positions"] is None:     # single chunk (:309-324)
-        selected = frames[:, :, ::frame_step, ...] if frame_step != 1 else frames
-        item = model.generate(frames=selected, audio=None, max_new_tokens=sched[0]["max_gen_len"],
-                              **(dict(kw, return_relevance=True) if return_relevance else kw))
-        return {"generated_audio": item["generated_audio"], "sampled_indices": item["sampled_indices"],
-                **({k: item[k] for k in REL} if return_relevance else {})}
-    stride_tokens = int(COMPRESSION_MODEL_FRAME_RATE * stride)
-    all_tokens, prompt_tokens = [], None
-    all_rel = {k: [] for k in REL}
-    for ch in sched:                                            # chunked generation (:327-365)
+    return sched, kw
+
+
+def _long_chunks(model, frames, sched, stride_tokens, frame_step, kw, return_relevance):
+    """The chunked generation of ``generate_long`` (:327-365), one ``generate_tokens`` call per step of the iteration: yields
+    (chunk, the frames it generated (B, K, new_tokens), their relevance values or {})."""
+    prompt_tokens = None
+    for ch in sched:
         lo, hi = ch["positions"]
         positions = torch.arange(lo, hi, device=frames.device)
         selected = frames[:, positions % frames.shape[1], ...]
@@ -86,16 +80,125 @@ def generate_long(model, frames: torch.Tensor, duration: float, *, stride: float
         # tokens only: the reference decodes every chunk inside generate() and throws the audio away (:344-357)
         gen_tokens = model.generate_tokens(frames=selected, audio=prompt_tokens, max_new_tokens=ch["max_gen_len"],
                                            **(dict(kw, return_relevance=True) if return_relevance else kw))
+        new_rel = {}
         if return_relevance:
             rel, gen_tokens = gen_tokens, gen_tokens["tokens"]
-            for k in REL:
-                all_rel[k].append(rel[k] if prompt_tokens is None else rel[k][:, :, prompt_tokens.shape[-1]:])
-        all_tokens.append(gen_tokens if prompt_tokens is None else gen_tokens[:, :, prompt_tokens.shape[-1]:])
+            new_rel = {k: rel[k] if prompt_tokens is None else rel[k][:, :, prompt_tokens.shape[-1]:] for k in REL}
+        new = gen_tokens if prompt_tokens is None else gen_tokens[:, :, prompt_tokens.shape[-1]:]
         prompt_tokens = gen_tokens[:, :, stride_tokens:]
+        yield ch, new, new_rel
+
+
+def _check_codec_window(codec_window):
+    if codec_window is not None and (isinstance(codec_window, bool) or not isinstance(codec_window, int) or codec_window < 1):
+        raise _error(f"codec_window must be None or a positive number of frames, got {codec_window!r}")
+
+
+def _check_emit_chunks(emit_chunks):
+    if isinstance(emit_chunks, bool) or not isinstance(emit_chunks, int) or emit_chunks < 1:
+        raise _error(f"emit_chunks must be a positive number of chunks, got {emit_chunks!r}")
+
+
+@torch.no_grad()
+def generate_long(model, frames: torch.Tensor, duration: float, *, stride: float = 0.64, model_max_duration: Optional[float] = None,
+                  vfps: float = 25, frame_step: int = 1, clip_indices=None, use_sampling: bool = True, temp: float = 1.0,
+                  top_k: int = 128, top_p: float = 0.0, cfg_scale: float = 1.0, return_relevance: bool = False, video_lengths=None,
+                  codec_window: Optional[int] = None) -> dict:
+    """frames: whatever the feature-extractor plugin accepts, segments on dim 1 — raw (B, S, C, T, H, W) or, with the
+    pass-through ``MotionFormer``, features (B, S, t, 768).  Returns {"generated_audio", "sampled_indices"}.
+    ``use_sampling``, ``temp``, ``top_k``, ``top_p``, ``cfg_scale``: scalars, or one value per clip (length-B list / tuple / 1-D
+    tensor) — every chunk of clip b is sampled with clip b's values (``VAURAModel.generate_tokens``).
+    ``return_relevance``: passed to every chunk; the result gains "relevance", "logprob_cond" and "logprob_null" (B, K, T), the chunks'
+    values concatenated with the prompt overlap removed the way the tokens are (every frame carries the values of the chunk that
+    GENERATED it).  No sequence means are returned here: chunks overlap, and a mean per chunk is not a mean of the clip — reduce the
+    (B, K, T) values as needed.
+    ``codec_window``: None — the waveform is decoded in one codec pass, as always; an int — in successive windows of that many frames
+    (``DacModelWrapper.decode_windowed``): the same bits, with codec workspaces that follow the window instead of the duration.
+    One ``duration`` for the whole call: a per-clip sequence of durations, or ``video_lengths``, is refused (per-clip lengths are a
+    feature of one ``generate()`` call; the chunk schedule here is shared by the batch)."""
+    _check_codec_window(codec_window)
+    sched, kw = _long_setup(model, frames, duration, stride, model_max_duration, vfps, clip_indices, use_sampling, temp, top_k, top_p,
+                            cfg_scale, video_lengths, "generate_long")
+    if len(sched) == 1 and sched[0]["positions"] is None:     # single chunk (:309-324)
+        selected = frames[:, :, ::frame_step, ...] if frame_step != 1 else frames
+        item = model.generate(frames=selected, audio=None, max_new_tokens=sched[0]["max_gen_len"],
+                              **(dict(kw, return_relevance=True) if return_relevance else kw))
+        if codec_window is not None:
+            item["generated_audio"] = model.audio_encoder.decode_windowed(item["sampled_indices"][..., : model.num_codebooks, :], codec_window)
+        return {"generated_audio": item["generated_audio"], "sampled_indices": item["sampled_indices"],
+                **({k: item[k] for k in REL} if return_relevance else {})}
+    stride_tokens = int(COMPRESSION_MODEL_FRAME_RATE * stride)
+    all_tokens = []
+    all_rel = {k: [] for k in REL}
+    for _, new, new_rel in _long_chunks(model, frames, sched, stride_tokens, frame_step, kw, return_relevance):   # chunked generation (:327-365)
+        all_tokens.append(new)
+        for k, v in new_rel.items():
+            all_rel[k].append(v)
     gen_tokens = torch.cat(all_tokens, dim=-1)
-    audio = model.audio_encoder.decode([(gen_tokens[..., : model.num_codebooks, :], None)])   # :366-369
+    codes = gen_tokens[..., : model.num_codebooks, :]
+    if codec_window is None:
+        audio = model.audio_encoder.decode([(codes, None)])   # :366-369
+    else:
+        audio = model.audio_encoder.decode_windowed(codes, codec_window)
     return {"generated_audio": audio, "sampled_indices": gen_tokens,
             **({k: torch.cat(v, dim=-1) for k, v in all_rel.items()} if return_relevance else {})}
+
+
+def _decode_halo(model) -> int:
+    from .codec_clips import decode_halo
+    return decode_halo(model.audio_encoder.cfg)
+
+
+def generate_long_stream(model, frames: torch.Tensor, duration: float, *, emit_chunks: int = 1, stride: float = 0.64,
+                         model_max_duration: Optional[float] = None, vfps: float = 25, frame_step: int = 1, clip_indices=None,
+                         use_sampling: bool = True, temp: float = 1.0, top_k: int = 128, top_p: float = 0.0, cfg_scale: float = 1.0,
+                         return_relevance: bool = False, video_lengths=None):
+    """``generate_long`` as a generator of finished audio: the arguments are checked here, the returned iterator runs the chunks.
+    After every ``emit_chunks`` chunks, and after the last one, it yields {"audio" (B, 1, n * hop), "start_frame", "frames" (n),
+    "sampled_indices" (B, K, n), "final"} — with ``return_relevance`` also "relevance", "logprob_cond", "logprob_null" (B, K, n) — for
+    the frames [start_frame, start_frame + n).  The blocks tile the clip without overlap, and their concatenation is, bit for bit,
+    ``generate_long``'s "generated_audio" / "sampled_indices" / relevance values of the same call.
+    After chunk c the tokens of the frames [0, N_c), N_c = offset_c + max_gen_len_c, are final: later chunks are prompted with them
+    and generate behind them.  The samples of a frame depend on ``codec_clips.decode_halo`` = H frames either side, so the frames
+    [emitted, N_c - H) are decoded then (``DacModelWrapper.decode_window``: one codec pass over that window and its halo), and on
+    the last chunk everything up to N_c.  A single-chunk duration yields once, what ``generate_long`` returns."""
+    _check_emit_chunks(emit_chunks)
+    sched, kw = _long_setup(model, frames, duration, stride, model_max_duration, vfps, clip_indices, use_sampling, temp, top_k, top_p,
+                            cfg_scale, video_lengths, "generate_long_stream")
+    return _long_stream(model, frames, sched, int(COMPRESSION_MODEL_FRAME_RATE * stride), frame_step, kw, return_relevance, emit_chunks)
+
+
+@torch.no_grad()
+def _long_stream(model, frames, sched, stride_tokens, frame_step, kw, return_relevance, emit_chunks):
+    if len(sched) == 1 and sched[0]["positions"] is None:
+        selected = frames[:, :, ::frame_step, ...] if frame_step != 1 else frames
+        item = model.generate(frames=selected, audio=None, max_new_tokens=sched[0]["max_gen_len"],
+                              **(dict(kw, return_relevance=True) if return_relevance else kw))
+        yield {"audio": item["generated_audio"], "start_frame": 0, "frames": int(item["sampled_indices"].shape[-1]),
+               "sampled_indices": item["sampled_indices"], "final": True, **({k: item[k] for k in REL} if return_relevance else {})}
+        return
+    H, K = _decode_halo(model), model.num_codebooks
+    held, held_rel, held_from, emitted = [], {k: [] for k in REL}, 0, 0     # generated and not yet emitted: frames [held_from, N_c)
+    for c, (ch, new, new_rel) in enumerate(_long_chunks(model, frames, sched, stride_tokens, frame_step, kw, return_relevance)):
+        held.append(new)
+        for k, v in new_rel.items():
+            held_rel[k].append(v)
+        final = c + 1 == len(sched)
+        N = ch["offset"] + ch["max_gen_len"]
+        upto = N if final else N - H
+        if not final and ((c + 1) % emit_chunks or upto <= emitted):
+            continue
+        tok = torch.cat(held, dim=-1)                                       # frames [held_from, N): held_from <= emitted - H
+        rel = {k: torch.cat(v, dim=-1) for k, v in held_rel.items()} if return_relevance else {}
+        B, n = tok.shape[0], upto - emitted
+        audio = model.audio_encoder.decode_window(tok[..., :K, :], [emitted - held_from] * B, [n] * B)
+        yield {"audio": audio, "start_frame": emitted, "frames": n, "sampled_indices": tok[..., emitted - held_from:upto - held_from],
+               "final": final, **{k: v[..., emitted - held_from:upto - held_from] for k, v in rel.items()}}
+        emitted = upto
+        keep = max(held_from, emitted - H)                                  # the halo in front of the next block stays
+        held = [tok[..., keep - held_from:]]
+        held_rel = {k: [rel[k][..., keep - held_from:]] if return_relevance else [] for k in REL}
+        held_from = keep
 
 
 # ---- one duration per clip: the schedules of the clips merged into one call per chunk index
@@ -207,14 +310,12 @@ def clip_chunk_plan(durations, segments=None, S: Optional[int] = None, *, model_
     return dict(stride_tokens=stride_tokens, clips=clips, chunks=chunks)
 
 
-REL = ("relevance", "logprob_cond", "logprob_null")
-
-
 @torch.no_grad()
 def generate_long_clips(model, frames: torch.Tensor, durations, *, segments=None, stride: float = 0.64,
                         model_max_duration: Optional[float] = None, vfps: float = 25, frame_step: int = 1, clip_indices=None,
                         use_sampling: bool = True, temp: float = 1.0, top_k: int = 128, top_p: float = 0.0, cfg_scale: float = 1.0,
-                        return_relevance: bool = False, video_lengths=None, num_candidates=None) -> dict:
+                        return_relevance: bool = False, video_lengths=None, num_candidates=None,
+                        codec_window: Optional[int] = None) -> dict:
     """``generate_long`` for a batch whose clips differ in duration, in one call: ``durations`` holds one positive float per clip
     (list / tuple / 1-D tensor of length B), and clip b's tokens, relevance values and waveform are, bit for bit (``noise_mode=
     "philox"`` or greedy decoding), those of ``generate_long(model, frames, durations[b], ...)`` on the same batch.
@@ -233,7 +334,8 @@ def generate_long_clips(model, frames: torch.Tensor, durations, *, segments=None
     "audio_lengths" (B,) = L_b * hop: ``post.normalize_audio(r["generated_audio"], ..., lengths=r["audio_lengths"])`` and
     ``post.save_wavs`` take it as it is.  ``return_relevance`` adds "relevance", "logprob_cond", "logprob_null" (B, K, L_max), zero past
     L_b (no sequence means, as in ``generate_long``).  Equal durations without ``segments``: ``generate_long`` itself (what it
-    refuses included) plus the two lengths.
+    refuses included) plus the two lengths.  ``codec_window``: as in ``generate_long`` — an int decodes the waveform in successive windows
+    of that many frames (``decode_windowed``, the same bits), None in the one pass.
     Refused before any device work: durations that are no per-clip sequence of length B, not finite, <= 0 or without a frame;
     ``segments`` out of range; ``video_lengths`` (a chunk's video length follows from the clip's duration) and ``num_candidates``;
     and ``frame_step`` != 1 for a batch that mixes single-chunk clips (d_b <= model_max_duration) with chunked ones — the two
@@ -243,12 +345,45 @@ def generate_long_clips(model, frames: torch.Tensor, durations, *, segments=None
     a full window (``clip_chunk_plan``: "width"), and such a clip is served the way ``generate_tokens(video_lengths=...)`` serves a
     clip with fewer video tokens than the batch: it has no scalar ``generate_long`` to be compared with under guidance; its scalar
     counterpart is the one-duration loop over calls of the same width."""
+    _check_codec_window(codec_window)
+    d, seg, single, kw, sample_kw = _clips_setup(model, frames, durations, segments, stride, model_max_duration, vfps, frame_step, clip_indices,
+                                                 use_sampling, temp, top_k, top_p, cfg_scale, video_lengths, num_candidates, "generate_long_clips")
+    B, S = int(frames.shape[0]), int(frames.shape[1])
+    if segments is None and len(set(d)) == 1:          # one duration after all: the scalar call, plus the lengths
+        r = generate_long(model, frames, d[0], frame_step=frame_step, return_relevance=return_relevance, codec_window=codec_window,
+                          **kw, **sample_kw)
+        L_b = int(r["sampled_indices"].shape[-1])
+        r["lengths"] = torch.full((B,), L_b, dtype=torch.int64, device=r["sampled_indices"].device)
+        r["audio_lengths"] = r["lengths"] * (int(r["generated_audio"].shape[-1]) // L_b)
+        return r
+    plan = clip_chunk_plan(d, seg, S, **kw)
+    K = model.num_codebooks
+    lengths = [cl["length"] for cl in plan["clips"]]
+    L_max = max(lengths)
+    st = {}
+    for _ in _clips_chunks(model, frames, plan, single, frame_step, sample_kw, return_relevance, st):
+        pass
+    tokens, rel = st["tokens"], st["rel"]
+    if codec_window is not None:
+        audio = model.audio_encoder.decode_windowed(tokens[..., :K, :], codec_window, None if len(set(lengths)) == 1 else lengths)
+    elif len(set(lengths)) == 1:
+        audio = model.audio_encoder.decode([(tokens[..., :K, :], None)])
+    else:
+        audio = model.audio_encoder.decode_clips(tokens[..., :K, :], lengths)
+    lens = torch.tensor(lengths, dtype=torch.int64, device=tokens.device)
+    return {"generated_audio": audio, "sampled_indices": tokens, "lengths": lens,
+            "audio_lengths": lens * (int(audio.shape[-1]) // L_max), **rel}
+
+
+def _clips_setup(model, frames, durations, segments, stride, model_max_duration, vfps, frame_step, clip_indices, use_sampling, temp, top_k,
+                 top_p, cfg_scale, video_lengths, num_candidates, who):
+    """The checks of ``generate_long_clips`` -> (durations, segments, which clips are single-chunk, schedule keywords, sampling keywords)."""
     from .clip_params import check_lengths
     if video_lengths is not None:
-        raise _error("generate_long_clips takes no video_lengths: the video length of a chunk follows from the clip's duration "
+        raise _error(f"{who} takes no video_lengths: the video length of a chunk follows from the clip's duration "
                      "(pass `segments` for videos of different lengths)")
     if num_candidates is not None:
-        raise _error("generate_long_clips takes no num_candidates: best-of-N is a feature of one generate() call")
+        raise _error(f"{who} takes no num_candidates: best-of-N is a feature of one generate() call")
     if not hasattr(frames, "shape") or len(frames.shape) < 2:
         raise _error("frames must carry the clips on dim 0 and the segments on dim 1")
     B, S = int(frames.shape[0]), int(frames.shape[1])
@@ -264,17 +399,17 @@ def generate_long_clips(model, frames: torch.Tensor, durations, *, segments=None
                      "the two groups separately")
     kw = dict(stride=stride, model_max_duration=model_max_duration, vfps=vfps)
     sample_kw = dict(clip_indices=clip_indices, use_sampling=use_sampling, temp=temp, top_k=top_k, top_p=top_p, cfg_scale=cfg_scale)
-    if segments is None and len(set(d)) == 1:          # one duration after all: the scalar call, plus the lengths
-        r = generate_long(model, frames, d[0], frame_step=frame_step, return_relevance=return_relevance, **kw, **sample_kw)
-        L_b = int(r["sampled_indices"].shape[-1])
-        r["lengths"] = torch.full((B,), L_b, dtype=torch.int64, device=r["sampled_indices"].device)
-        r["audio_lengths"] = r["lengths"] * (int(r["generated_audio"].shape[-1]) // L_b)
-        return r
-    plan = clip_chunk_plan(d, seg, S, **kw)
+    return d, seg, single, kw, sample_kw
+
+
+def _clips_chunks(model, frames, plan, single, frame_step, sample_kw, return_relevance, st):
+    """The merged chunk loop of ``generate_long_clips``, one ``generate_tokens`` call per step of the iteration.  ``st`` receives
+    "tokens" (B, K, L_max; the special id where nothing is generated yet) and "rel" (the relevance values, or {}), filled chunk by
+    chunk; yields (chunk index, chunk of the plan) behind each call."""
+    B = int(frames.shape[0])
     dev = frames.device
-    K, special, stride_tokens = model.num_codebooks, model.special_token_id, plan["stride_tokens"]
-    lengths = [cl["length"] for cl in plan["clips"]]
-    L_max = max(lengths)
+    special, stride_tokens = model.special_token_id, plan["stride_tokens"]
+    L_max = max(cl["length"] for cl in plan["clips"])
     tokens = None
     rel = {}
     rows = torch.arange(B, device=dev)[:, None]
@@ -291,6 +426,7 @@ def generate_long_clips(model, frames: torch.Tensor, durations, *, segments=None
         if tokens is None:
             tokens = torch.full((B, tok.shape[1], L_max), special, dtype=tok.dtype, device=tok.device)
             rel = {k: torch.zeros(B, tok.shape[1], L_max, dtype=out[k].dtype, device=tok.device) for k in REL} if return_relevance else {}
+            st["tokens"], st["rel"] = tokens, rel
         for b in range(B):                                  # every frame from the chunk that GENERATED it
             if not ch["parked"][b]:
                 off, T_b = c * stride_tokens, ch["T"][b]
@@ -306,10 +442,77 @@ def generate_long_clips(model, frames: torch.Tensor, durations, *, segments=None
                 T_b = ch["T"][b]
                 n = min(T_b, P_next)
                 prompt[b, :, P_next - n:] = tok[b, :, T_b - n:T_b]
-    if len(set(lengths)) == 1:
-        audio = model.audio_encoder.decode([(tokens[..., :K, :], None)])
-    else:
-        audio = model.audio_encoder.decode_clips(tokens[..., :K, :], lengths)
-    lens = torch.tensor(lengths, dtype=torch.int64, device=tokens.device)
-    return {"generated_audio": audio, "sampled_indices": tokens, "lengths": lens,
-            "audio_lengths": lens * (int(audio.shape[-1]) // L_max), **rel}
+        yield c, ch
+
+
+def generate_long_clips_stream(model, frames: torch.Tensor, durations, segments=None, *, emit_chunks: int = 1, stride: float = 0.64,
+                               model_max_duration: Optional[float] = None, vfps: float = 25, frame_step: int = 1, clip_indices=None,
+                               use_sampling: bool = True, temp: float = 1.0, top_k: int = 128, top_p: float = 0.0, cfg_scale: float = 1.0,
+                               return_relevance: bool = False, video_lengths=None, num_candidates=None):
+    """``generate_long_clips`` as a generator of finished audio (``generate_long_stream`` for one duration per clip): the arguments are
+    checked here, the returned iterator runs the chunks.  After every ``emit_chunks`` chunks, and after the last one, it yields
+    {"audio" (B, 1, max(frames) * hop), "start_frames" and "frames" (one int per clip), "sampled_indices" (B, K, max(frames)), "final"},
+    with ``return_relevance`` the three (B, K, max(frames)) values as well: clip b's frames [start_frames[b], start_frames[b] +
+    frames[b]), left-aligned, with zeros (the special id in "sampled_indices") behind them.  Per clip the blocks tile [0, L_b) without
+    overlap and concatenate to the bits of ``generate_long_clips``.  Clip b's last chunk releases everything up to L_b; a clip whose
+    schedule has ended has frames[b] = 0 from then on (ONE ``decode_window`` pass per block, over the clips that have something)."""
+    _check_emit_chunks(emit_chunks)
+    d, seg, single, kw, sample_kw = _clips_setup(model, frames, durations, segments, stride, model_max_duration, vfps, frame_step, clip_indices,
+                                                 use_sampling, temp, top_k, top_p, cfg_scale, video_lengths, num_candidates,
+                                                 "generate_long_clips_stream")
+    if segments is None and len(set(d)) == 1:          # one duration after all: the scalar stream with per-clip bookkeeping
+        inner = generate_long_stream(model, frames, d[0], emit_chunks=emit_chunks, frame_step=frame_step, return_relevance=return_relevance,
+                                     **kw, **sample_kw)
+        return _same_for_every_clip(inner, int(frames.shape[0]))
+    plan = clip_chunk_plan(d, seg, int(frames.shape[1]), **kw)
+    return _clips_stream(model, frames, plan, single, frame_step, sample_kw, return_relevance, emit_chunks)
+
+
+def _same_for_every_clip(blocks, B):
+    for blk in blocks:
+        blk["start_frames"], blk["frames"] = [blk.pop("start_frame")] * B, [blk["frames"]] * B
+        yield blk
+
+
+def clip_emission(plan, c: int, halo: int, emitted: List[int]) -> List[int]:
+    """Per clip, the frame up to which audio can be released after chunk ``c`` of ``clip_chunk_plan``: L_b once the clip's last chunk
+    has run, else c * stride_tokens + max_gen_len - halo (never below what is out already) — pure bookkeeping."""
+    out = []
+    for b, cl in enumerate(plan["clips"]):
+        if c + 1 >= len(cl["schedule"]):
+            out.append(cl["length"])
+        else:
+            out.append(max(emitted[b], c * plan["stride_tokens"] + plan["chunks"][c]["T"][b] - halo))
+    return out
+
+
+@torch.no_grad()
+def _clips_stream(model, frames, plan, single, frame_step, sample_kw, return_relevance, emit_chunks):
+    H, K, B = _decode_halo(model), model.num_codebooks, int(frames.shape[0])
+    emitted = [0] * B
+    st = {}
+    for c, ch in _clips_chunks(model, frames, plan, single, frame_step, sample_kw, return_relevance, st):
+        final = c + 1 == len(plan["chunks"])
+        upto = clip_emission(plan, c, H, emitted)
+        counts = [u - e for u, e in zip(upto, emitted)]
+        if not final and ((c + 1) % emit_chunks or max(counts) < 1):
+            continue
+        if max(counts) < 1:                                  # cannot happen: the last chunk generates at least one frame of the longest clip
+            raise _error("the last chunk released no frame")
+        tokens, rel = st["tokens"], st["rel"]
+        # the frames every clip holds by now, and the stretch of the token tensor that the windows and their halos lie in
+        known = [cl["length"] if c + 1 >= len(cl["schedule"]) else c * plan["stride_tokens"] + ch["T"][b] for b, cl in enumerate(plan["clips"])]
+        lo = min(max(0, e - H) for e, n in zip(emitted, counts) if n)
+        hi = max(k for k, n in zip(known, counts) if n)
+        starts = [e - lo if n else 0 for e, n in zip(emitted, counts)]
+        lens = [min(k, hi) - lo if n else 1 for k, n in zip(known, counts)]
+        audio = model.audio_encoder.decode_window(tokens[..., :K, lo:hi], starts, counts, lens)
+        n_max = max(counts)
+        blk_tok = torch.full((B, tokens.shape[1], n_max), model.special_token_id, dtype=tokens.dtype, device=tokens.device)
+        blk_rel = {k: torch.zeros(B, v.shape[1], n_max, dtype=v.dtype, device=v.device) for k, v in rel.items()}
+        for b in range(B):
+            blk_tok[b, :, :counts[b]] = tokens[b, :, emitted[b]:upto[b]]
+            for k, v in rel.items():
+                blk_rel[k][b, :, :counts[b]] = v[b, :, emitted[b]:upto[b]]
+        yield {"audio": audio, "start_frames": list(emitted), "frames": counts, "sampled_indices": blk_tok, "final": final, **blk_rel}
+        emitted = upto
