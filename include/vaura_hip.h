@@ -921,6 +921,36 @@ int vaura_video_preprocess(const uint8_t* video, int channels_last, int n_clips,
 /* dynamic LDS bytes of one workgroup for these table sizes (0 for sizes the kernel does not take) */
 size_t vaura_video_preprocess_lds_bytes(int channels_last, int crop_w, int h_taps, int span, int tile_src_rows);
 
+/* The same from decoder surfaces: 8-bit 4:2:0 YUV -> RGB uint8 -> the resize / crop / scale / normalise above, in one launch.
+ *   video     uint8, n_clips * T frames, frame i at byte i * frame_stride; H and W even.  In a frame, luma row y starts at byte
+ *             y * pitch; the chroma plane starts at byte chroma_offset:
+ *               VAURA_YUV_NV12  H / 2 rows of W / 2 interleaved (Cb, Cr) pairs, row to row `pitch` bytes
+ *               VAURA_YUV_I420  the U plane, H / 2 rows of W / 2 bytes, row to row pitch / 2 bytes, then the V plane at byte
+ *                               chroma_offset + (H / 2) * (pitch / 2), laid out the same
+ *             The base address needs no alignment.  Bytes outside the planes (the padding of a decoder surface) never reach the
+ *             result; the aligned 4-byte word around a plane's first or last byte may be loaded.
+ *   video_bytes  the bytes that may be read from `video` on; the last plane byte of the last frame must lie inside them
+ *   colour    level = clamp((cy * (Y - y_off) + cu * (U - 128) + cv * (V - 128) + 2^13) >> 14, 0, 255), arithmetic shift, with
+ *             (cu, cv) = (0, crv) for R, (cgu, cgv) for G, (cbu, 0) for B; the sample at (y >> 1, x >> 1) serves its 2 x 2 luma
+ *             block (no interpolation).  The host decides the integers (vaura_amd/preprocess.py: yuv_coefficients — BT.601
+ *             limited range is 16, 19077, 26149, -6419, -13320, 33050); the result is RGB uint8 before the resize, as if
+ *             vaura_video_preprocess had been given the converted frames.
+ *   the rest  as vaura_video_preprocess (C is 3).
+ * VAURA_ERR_SHAPE, before any launch: odd H or W; everything vaura_video_preprocess lists (the LDS size is
+ * vaura_video_preprocess_yuv420_lds_bytes).  VAURA_ERR_ARG: an unknown layout; pitch < W; an odd pitch with VAURA_YUV_I420;
+ * chroma_offset inside the luma plane or frame_stride inside the chroma plane (planes or frames that overlap); a last plane byte
+ * behind video_bytes; y_off outside 0..255 or a coefficient beyond +-2^20 (the accumulator is an int32); and what
+ * vaura_video_preprocess answers with VAURA_ERR_ARG.                                                                              */
+enum { VAURA_YUV_NV12 = 0, VAURA_YUV_I420 = 1 };
+int vaura_video_preprocess_yuv420(const uint8_t* video, int64_t video_bytes, int layout, int64_t pitch, int64_t chroma_offset,
+                                  int64_t frame_stride, int n_clips, int T, int H, int W, int y_off, int cy, int crv, int cgu, int cgv,
+                                  int cbu, int resize, int crop_h, int crop_w, int F, int S, int seg_start, int seg_stride,
+                                  const int32_t* h_rel, const int16_t* h_w, int h_taps, int h_prec, const int32_t* v_start,
+                                  const int16_t* v_w, int v_taps, int v_prec, int x0, int span, int tile_rows, int tile_src_rows,
+                                  const float* lut, float* out, vaura_stream_t s);
+/* dynamic LDS bytes of one workgroup of that launch (0 for sizes the kernel does not take) */
+size_t vaura_video_preprocess_yuv420_lds_bytes(int layout, int crop_w, int h_taps, int span, int tile_src_rows);
+
 /* -------------------------------------------------------------------------------------------
  * Audio preprocessing (csrc/audio_pre.hip): decoded PCM -> the codec's padded mono input.  The `audio_transforms_test` list of
  * configs/generate_vas.yaml:43-54 (AudioStereoToMono -> AudioResample(44100) -> AudioTrim; models/data/transforms/

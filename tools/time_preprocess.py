@@ -8,6 +8,12 @@ Bytes: what the algorithm needs per frame (the source rows and columns that surv
 kernel time, against the 6.29 TB/s copy rate measured on this part (MI355X_MICROARCH.md).
 
     python tools/time_preprocess.py [rounds] > profiles/preprocess_timing.txt
+
+--yuv: the same batch as 4:2:0 decoder surfaces (input_format="nv12" / "i420": vaura_video_preprocess_yuv420, 1.5 bytes per pixel over
+the link instead of 3) beside the RGB rows, which are the comparison: the RGB input is the host's conversion of the same planes, so all
+six rows compute the same output (checked before timing).  The rows alternate inside every round, so they share clocks and neighbours.
+
+    python tools/time_preprocess.py [rounds] --yuv > profiles/preprocess_yuv_timing.txt
 """
 import json
 import os
@@ -20,7 +26,7 @@ import torch
 import torch.nn.functional as Fn
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from vaura_amd.preprocess import VideoPreprocessor, crop_offset, resized_size  # noqa: E402
+from vaura_amd.preprocess import VideoPreprocessor, crop_offset, resized_size, yuv420_to_rgb_u8  # noqa: E402
 
 COPY_RATE = 6.29e12
 B, T, H, W = 8, 64, 360, 640
@@ -36,6 +42,65 @@ def _events(stream, fn, rounds):
         torch.cuda.synchronize()
         ts.append(a.elapsed_time(b))
     return statistics.median(ts), min(ts), max(ts)
+
+
+def _events_alternating(stream, fns, rounds):
+    """Every row once per round, in turn: {name: (median, min, max)} ms."""
+    ts = {name: [] for name in fns}
+    for _ in range(rounds):
+        for name, fn in fns.items():
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record(stream)
+            fn()
+            b.record(stream)
+            torch.cuda.synchronize()
+            ts[name].append(a.elapsed_time(b))
+    return {name: (statistics.median(t), min(t), max(t)) for name, t in ts.items()}
+
+
+def main_yuv(rounds):
+    dev = torch.device("cuda:0")
+    g = torch.Generator().manual_seed(0)
+    y = torch.randint(0, 256, (B, T, H, W), dtype=torch.uint8, generator=g)
+    u = torch.randint(0, 256, (B, T, H // 2, W // 2), dtype=torch.uint8, generator=g)
+    v = torch.randint(0, 256, (B, T, H // 2, W // 2), dtype=torch.uint8, generator=g)
+    nv12 = torch.cat([y, torch.stack([u, v], dim=-1).reshape(B, T, H // 2, W)], dim=2)             # (B, T, 3H/2, W)
+    i420 = torch.cat([y, u.reshape(B, T, H // 4, W), v.reshape(B, T, H // 4, W)], dim=2)
+    rgb = torch.stack([yuv420_to_rgb_u8(y[b], u[b], v[b]) for b in range(B)])                       # (B, T, 3, H, W), clip by clip
+    pres = {"rgb": VideoPreprocessor(device=dev), "nv12": VideoPreprocessor(device=dev, input_format="nv12"),
+            "i420": VideoPreprocessor(device=dev, input_format="i420")}
+    host = {"rgb": rgb, "nv12": nv12, "i420": i420}
+    geo = pres["rgb"].geometry(H, W)
+    rec = {"shape": {"clips": B, "frames": T, "H": H, "W": W, "out": [B, T // 16, 3, 16, 224, 224]},
+           "input_bytes": {k: t.numel() for k, t in host.items()},
+           "tiles": {"rgb": geo.tiles(False), "nv12": geo.tiles(False, "nv12"), "i420": geo.tiles(False, "i420")},
+           "clocks_before": _clocks(), "rows": {}}
+    stream = torch.cuda.Stream(dev)
+    with torch.cuda.stream(stream):
+        on_dev = {k: t.to(dev) for k, t in host.items()}
+        pinned = {k: t.pin_memory() for k, t in host.items()}
+        want = pres["rgb"](on_dev["rgb"])
+        for k in ("nv12", "i420"):
+            if not (torch.equal(pres[k](on_dev[k]), want) and torch.equal(pres[k](pinned[k]), want)):
+                raise SystemExit(f"{k}: the output differs from the RGB kernel's on the converted frames")
+        fns = {}
+        for k, label in (("rgb", ""), ("nv12", " nv12"), ("i420", " i420")):
+            fns["device" + label] = lambda k=k: pres[k](on_dev[k])
+            fns["pinned" + label] = lambda k=k: pres[k](pinned[k])
+        for _ in range(3):
+            for fn in fns.values():
+                fn()
+        torch.cuda.synchronize()
+        res = _events_alternating(stream, fns, rounds)
+    rec["clocks_after"] = _clocks()
+    print(f"# {B} x {T} frames of {H} x {W}: RGB {rgb.numel() / 1e6:.0f} MB, 4:2:0 {nv12.numel() / 1e6:.0f} MB; outputs equal to the bit; "
+          f"{rounds} rounds, the six rows in turn inside each", flush=True)
+    for name, (med, lo, hi) in res.items():
+        rec["rows"][name] = {"ms": med, "min_ms": lo, "max_ms": hi}
+        base = res["pinned" if name.startswith("pinned") else "device"]
+        print(f"{name:>12}: {med:8.3f} ms per batch (min {lo:.3f}, max {hi:.3f})  {med / base[0]:.2f}x the RGB row "
+              f"(whose min-max spread is {base[2] - base[1]:.3f} ms)", flush=True)
+    print(json.dumps(rec))
 
 
 def _cpu_route(video, threads, rounds):
@@ -68,7 +133,10 @@ def _clocks():
 
 
 def main():
-    rounds = int(sys.argv[1]) if len(sys.argv) > 1 else 20
+    args = [a for a in sys.argv[1:] if a != "--yuv"]
+    rounds = int(args[0]) if args else 20
+    if "--yuv" in sys.argv:
+        return main_yuv(rounds)
     dev = torch.device("cuda:0")
     video = torch.randint(0, 256, (B, T, 3, H, W), dtype=torch.uint8, generator=torch.Generator().manual_seed(0))
     pre = VideoPreprocessor(device=dev)

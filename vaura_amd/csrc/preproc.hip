@@ -19,6 +19,13 @@
 //           device result is the host's to the bit) and stores 16 bytes.
 // Bytes per 360 x 640 -> 224 x 224 frame: read 3 x 318 of 360 rows x 319 of 640 columns = 0.30 MB (+ the rows adjacent tiles share,
 // which come from L2), write 3 x 224 x 224 x 4 = 0.60 MB.
+//
+// video_preprocess_yuv_kernel takes what a decoder hands over instead: 8-bit 4:2:0 surfaces (NV12: luma, then interleaved Cb,Cr rows at
+// the same pitch; I420: luma, then the U and the V plane at half the pitch), 1.5 bytes per pixel.  Same grid, same phase 2; phase 1
+// copies the needed bytes of one luma row and of its chroma row to the wave's slab, converts them ONCE to three planar uint8 rows in
+// LDS (the host's integer formula: 2^14-scaled coefficients, chroma replicated over its 2 x 2 block, no interpolation) and filters
+// each of the three as the NCHW instance filters a row.  yuv -> RGB uint8 -> the resize above: the same function as converting on the
+// host first (vaura_amd/preprocess.py: yuv420_to_rgb_u8) and calling the RGB kernel.
 #include "common.h"
 
 #define PREPROC_MAX_TAPS VAURA_PREPROC_MAX_TAPS
@@ -141,13 +148,176 @@ __global__ __launch_bounds__(64 * PREPROC_WAVES) void video_preprocess_kernel(co
   }
 }
 
+struct PreprocYuvArgs {
+  const uint8_t* src;
+  const int32_t* h_rel;
+  const int16_t* h_w;
+  const int32_t* v_start;
+  const int16_t* v_w;
+  const float* lut;
+  float* out;
+  int64_t pitch, chroma_offset, frame_stride;   // bytes: luma row to row, frame start to chroma plane, frame to frame
+  int y_off, cy, crv, cgu, cgv, cbu;            // the host's colour formula, coefficients scaled by 2^14
+  int T, H, W, S, F, seg_start, seg_stride;
+  int crop_h, crop_w, h_taps, h_prec, v_taps, v_prec, x0, span, tile_rows, tile_src_rows, slab_dwords;
+};
+
+#define PREPROC_YUV_PREC 14
+
+// one wave's slab: the luma bytes, the chroma bytes (NV12: one run of pairs; I420: the U run, then the V run), three planar RGB rows.
+// Each raw run starts at an aligned word, so it holds up to 3 bytes in front of its first needed byte and ends on a whole word.
+__host__ __device__ static inline int yuv_luma_dwords(int span) { return (span + 3 + 3) >> 2; }
+__host__ __device__ static inline int yuv_plane_dwords(int span) { return ((span >> 1) + 1 + 3 + 3) >> 2; }    // I420: span / 2 + 1 samples at most
+__host__ __device__ static inline int yuv_chroma_dwords(int span) { return (span + 16) >> 2; }                  // >= span + 2 + 3 bytes (NV12), >= 2 planes (I420)
+__host__ __device__ static inline int yuv_rgb_dwords(int span) { return (span + 3) >> 2; }
+__host__ __device__ static inline int yuv_slab_dwords(int span) { return yuv_luma_dwords(span) + yuv_chroma_dwords(span) + 3 * yuv_rgb_dwords(span); }
+
+static size_t preproc_yuv_lds_bytes(int crop_w, int h_taps, int span, int tile_src_rows) {
+  return 4 * ((size_t)768 + crop_w + (((size_t)crop_w * h_taps) >> 1) + (size_t)PREPROC_WAVES * yuv_slab_dwords(span) + (size_t)3 * tile_src_rows * (crop_w >> 2));
+}
+
+// The colour accumulators ARE negative for out-of-gamut input, so the lower clamp comes first and level_u8 (unsigned, see its comment)
+// takes the upper one.
+__device__ __forceinline__ uint32_t color_u8(int acc) { return level_u8(max(acc, 0), PREPROC_YUV_PREC); }
+
+// copy `nbytes` bytes that start at `p` into `dst` with aligned 4-byte loads; returns where the first byte sits in dst (0..3)
+__device__ __forceinline__ int stage_bytes(uint32_t* dst, const uint8_t* p, int nbytes, int lane) {
+  const uintptr_t u = reinterpret_cast<uintptr_t>(p);
+  const int shift = (int)(u & 3);
+  const uint32_t* pa = reinterpret_cast<const uint32_t*>(u - shift);
+  const int ndw = (shift + nbytes + 3) >> 2;
+  for (int i = lane; i < ndw; i += 64) dst[i] = pa[i];
+  return shift;
+}
+
+template <int LAYOUT>   // VAURA_YUV_NV12 / VAURA_YUV_I420
+__global__ __launch_bounds__(64 * PREPROC_WAVES) void video_preprocess_yuv_kernel(const PreprocYuvArgs a) {
+  extern __shared__ uint32_t smem[];
+  const int nq = a.crop_w >> 2;                                       // 4-column groups per kept row
+  float* lut = reinterpret_cast<float*>(smem);                         // 768 floats
+  int32_t* hrel = reinterpret_cast<int32_t*>(smem + 768);              // crop_w
+  int16_t* hw = reinterpret_cast<int16_t*>(smem + 768 + a.crop_w);     // crop_w * h_taps (an even count: crop_w % 4 == 0)
+  uint32_t* slabs = smem + 768 + a.crop_w + ((a.crop_w * a.h_taps) >> 1);
+  uint32_t* tile = slabs + PREPROC_WAVES * a.slab_dwords;              // [3][tile_src_rows][nq] words of 4 uint8
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+
+  const int of = blockIdx.y;                                           // output frame (b, s, f)
+  const int f = of % a.F, bs = of / a.F, s = bs % a.S, b = bs / a.S;
+  const size_t n = (size_t)b * a.T + a.seg_start + s * a.seg_stride + f;   // source frame
+  const int r0 = blockIdx.x * a.tile_rows;
+  const int nr = min(a.tile_rows, a.crop_h - r0);
+  // source rows [ylo, ylo + nrows): clamped so that no table content can index outside the frame or the tile
+  const int ylo = min(max(a.v_start[r0], 0), a.H - a.v_taps);
+  const int nrows = min(a.tile_src_rows, a.H - ylo);
+
+  for (int i = tid; i < 768; i += 64 * PREPROC_WAVES) lut[i] = a.lut[i];
+  for (int i = tid; i < a.crop_w; i += 64 * PREPROC_WAVES) hrel[i] = min(max(a.h_rel[i], 0), a.span - a.h_taps);
+  for (int i = tid; i < a.crop_w * a.h_taps; i += 64 * PREPROC_WAVES) hw[i] = a.h_w[i];
+  __syncthreads();
+
+  // ---- phase 1: one source row per wave: stage luma + chroma, convert once, horizontal pass of the three channels into the tile
+  uint32_t* luma = slabs + wave * a.slab_dwords;
+  uint32_t* chroma = luma + yuv_luma_dwords(a.span);
+  uint32_t* rgb = chroma + yuv_chroma_dwords(a.span);
+  const int rgbw = yuv_rgb_dwords(a.span);
+  const int c0 = a.x0 >> 1;                                            // first chroma sample of the span
+  const int nc = ((a.x0 + a.span - 1) >> 1) - c0 + 1;                  // chroma samples the span touches (<= span / 2 + 1)
+  const uint8_t* frame = a.src + n * (size_t)a.frame_stride;
+  const int hhalf = 1 << (a.h_prec - 1);
+  for (int j0 = 0; j0 < nrows; j0 += PREPROC_WAVES) {
+    const int yy = j0 + wave;                                          // wave-uniform
+    int ysh = 0, ush = 0, vsh = 0;
+    if (yy < nrows) {
+      const int y = ylo + yy;
+      ysh = stage_bytes(luma, frame + (size_t)y * a.pitch + a.x0, a.span, lane);
+      const uint8_t* cplane = frame + a.chroma_offset;
+      if (LAYOUT == VAURA_YUV_NV12) {
+        ush = stage_bytes(chroma, cplane + (size_t)(y >> 1) * a.pitch + 2 * c0, 2 * nc, lane);
+      } else {
+        const size_t cp = (size_t)(a.pitch >> 1);
+        ush = stage_bytes(chroma, cplane + (size_t)(y >> 1) * cp + c0, nc, lane);
+        vsh = stage_bytes(chroma + yuv_plane_dwords(a.span), cplane + ((size_t)(a.H >> 1) + (y >> 1)) * cp + c0, nc, lane);
+      }
+    }
+    __syncthreads();
+    if (yy < nrows) {
+      const uint8_t* yb = reinterpret_cast<const uint8_t*>(luma) + ysh;
+      const uint8_t* ub = reinterpret_cast<const uint8_t*>(chroma) + ush;
+      const uint8_t* vb = reinterpret_cast<const uint8_t*>(chroma + yuv_plane_dwords(a.span)) + vsh;
+      for (int m = lane; m < rgbw; m += 64) {                          // 4 pixels per lane, one word per channel
+        uint32_t wr = 0, wg = 0, wb = 0;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          const int i = min(4 * m + e, a.span - 1);                    // the last word may pass the span: its spare bytes are never read
+          const int ci = ((a.x0 + i) >> 1) - c0;
+          const int u = (LAYOUT == VAURA_YUV_NV12 ? (int)ub[2 * ci] : (int)ub[ci]) - 128;
+          const int v = (LAYOUT == VAURA_YUV_NV12 ? (int)ub[2 * ci + 1] : (int)vb[ci]) - 128;
+          const int yv = a.cy * ((int)yb[i] - a.y_off) + (1 << (PREPROC_YUV_PREC - 1));
+          wr |= color_u8(yv + a.crv * v) << (8 * e);
+          wg |= color_u8(yv + a.cgu * u + a.cgv * v) << (8 * e);
+          wb |= color_u8(yv + a.cbu * u) << (8 * e);
+        }
+        rgb[m] = wr;
+        rgb[rgbw + m] = wg;
+        rgb[2 * rgbw + m] = wb;
+      }
+    }
+    __syncthreads();
+    if (yy < nrows) {
+#pragma unroll 1
+      for (int c = 0; c < 3; ++c) {
+        const uint8_t* sb = reinterpret_cast<const uint8_t*>(rgb + c * rgbw);
+        for (int q = lane; q < nq; q += 64) {
+          uint32_t word = 0;
+#pragma unroll
+          for (int e = 0; e < 4; ++e) {
+            const int x = 4 * q + e;
+            const uint8_t* t = sb + hrel[x];
+            const int16_t* w = hw + x * a.h_taps;
+            int acc = hhalf;
+            for (int k = 0; k < a.h_taps; ++k) acc += (int)t[k] * (int)w[k];
+            word |= level_u8(acc, a.h_prec) << (8 * e);
+          }
+          tile[((size_t)c * a.tile_src_rows + yy) * nq + q] = word;
+        }
+      }
+    }
+    __syncthreads();
+  }
+
+  // ---- phase 2: vertical pass, level -> fp32 table, 16-byte stores.  A copy of video_preprocess_kernel's phase 2 and not a shared
+  // inlined body, for the reason given at embed_clips_kernel (csrc/step.hip): the kernels every RGB call runs stay untouched source.
+  const int vhalf = 1 << (a.v_prec - 1);
+  const int items = 3 * nr * nq;
+  for (int it = tid; it < items; it += 64 * PREPROC_WAVES) {
+    const int q = it % nq, rc = it / nq, rr = rc % nr, c = rc / nr;
+    const int r = r0 + rr;
+    const int ys = min(max(a.v_start[r] - ylo, 0), nrows - a.v_taps);
+    const int16_t* w = a.v_w + (size_t)r * a.v_taps;
+    const uint32_t* t = tile + ((size_t)c * a.tile_src_rows + ys) * nq + q;
+    int a0 = vhalf, a1 = vhalf, a2 = vhalf, a3 = vhalf;
+    for (int k = 0; k < a.v_taps; ++k) {
+      const uint32_t d = t[(size_t)k * nq];
+      const int wk = w[k];
+      a0 += (int)(d & 255u) * wk;
+      a1 += (int)((d >> 8) & 255u) * wk;
+      a2 += (int)((d >> 16) & 255u) * wk;
+      a3 += (int)(d >> 24) * wk;
+    }
+    const float* l = lut + 256 * c;
+    const f32x4 o = {l[level_u8(a0, a.v_prec)], l[level_u8(a1, a.v_prec)], l[level_u8(a2, a.v_prec)], l[level_u8(a3, a.v_prec)]};
+    float* dst = a.out + ((((size_t)bs * 3 + c) * a.F + f) * a.crop_h + r) * a.crop_w + 4 * q;
+    *reinterpret_cast<f32x4*>(dst) = o;
+  }
+}
+
 extern "C" {
 
-int vaura_video_preprocess(const uint8_t* video, int channels_last, int n_clips, int T, int C, int H, int W, int resize, int crop_h,
-                           int crop_w, int F, int S, int seg_start, int seg_stride, const int32_t* h_rel, const int16_t* h_w, int h_taps,
-                           int h_prec, const int32_t* v_start, const int16_t* v_w, int v_taps, int v_prec, int x0, int span,
-                           int tile_rows, int tile_src_rows, const float* lut, float* out, vaura_stream_t s) {
-  if (!video || !h_rel || !h_w || !v_start || !v_w || !lut || !out) return VAURA_ERR_ARG;
+// what both entry points refuse about the resize / crop / segments / tables, in vaura_video_preprocess's order
+static int preproc_check(int n_clips, int T, int C, int H, int W, int resize, int crop_h, int crop_w, int F, int S, int seg_start,
+                         int seg_stride, const int32_t* h_rel, const int16_t* h_w, int h_taps, int h_prec, const int32_t* v_start,
+                         const int16_t* v_w, int v_taps, int v_prec, int x0, int span, int tile_rows, int tile_src_rows, const float* lut,
+                         const float* out) {
   if (n_clips <= 0 || T <= 0 || H <= 0 || W <= 0 || resize <= 0 || crop_h <= 0 || crop_w <= 0 || F <= 0) return VAURA_ERR_ARG;
   if (C != 3) return VAURA_ERR_SHAPE;
   // torchvision's Resize(int): the short side to `resize`, the long side to int(resize * long / short)
@@ -164,8 +334,19 @@ int vaura_video_preprocess(const uint8_t* video, int channels_last, int n_clips,
   if ((reinterpret_cast<uintptr_t>(out) & 15) || (reinterpret_cast<uintptr_t>(h_rel) & 3) || (reinterpret_cast<uintptr_t>(v_start) & 3) ||
       (reinterpret_cast<uintptr_t>(h_w) & 1) || (reinterpret_cast<uintptr_t>(v_w) & 1) || (reinterpret_cast<uintptr_t>(lut) & 3))
     return VAURA_ERR_ARG;
+  if ((int64_t)n_clips * S * F > 65535) return VAURA_ERR_SHAPE;       // gridDim.y
+  return 0;
+}
+
+int vaura_video_preprocess(const uint8_t* video, int channels_last, int n_clips, int T, int C, int H, int W, int resize, int crop_h,
+                           int crop_w, int F, int S, int seg_start, int seg_stride, const int32_t* h_rel, const int16_t* h_w, int h_taps,
+                           int h_prec, const int32_t* v_start, const int16_t* v_w, int v_taps, int v_prec, int x0, int span,
+                           int tile_rows, int tile_src_rows, const float* lut, float* out, vaura_stream_t s) {
+  if (!video || !h_rel || !h_w || !v_start || !v_w || !lut || !out) return VAURA_ERR_ARG;
+  if (const int st = preproc_check(n_clips, T, C, H, W, resize, crop_h, crop_w, F, S, seg_start, seg_stride, h_rel, h_w, h_taps, h_prec,
+                                   v_start, v_w, v_taps, v_prec, x0, span, tile_rows, tile_src_rows, lut, out))
+    return st;
   const int64_t frames_out = (int64_t)n_clips * S * F;
-  if (frames_out > 65535) return VAURA_ERR_SHAPE;                      // gridDim.y
   PreprocArgs a;
   a.src = video; a.h_rel = h_rel; a.h_w = h_w; a.v_start = v_start; a.v_w = v_w; a.lut = lut; a.out = out;
   a.T = T; a.H = H; a.W = W; a.S = S; a.F = F; a.seg_start = seg_start; a.seg_stride = seg_stride;
@@ -184,6 +365,56 @@ int vaura_video_preprocess(const uint8_t* video, int channels_last, int n_clips,
 size_t vaura_video_preprocess_lds_bytes(int channels_last, int crop_w, int h_taps, int span, int tile_src_rows) {
   if (crop_w <= 0 || (crop_w & 3) || h_taps <= 0 || span <= 0 || tile_src_rows <= 0) return 0;
   return preproc_lds_bytes(channels_last, crop_w, h_taps, span, tile_src_rows);
+}
+
+int vaura_video_preprocess_yuv420(const uint8_t* video, int64_t video_bytes, int layout, int64_t pitch, int64_t chroma_offset,
+                                  int64_t frame_stride, int n_clips, int T, int H, int W, int y_off, int cy, int crv, int cgu, int cgv,
+                                  int cbu, int resize, int crop_h, int crop_w, int F, int S, int seg_start, int seg_stride,
+                                  const int32_t* h_rel, const int16_t* h_w, int h_taps, int h_prec, const int32_t* v_start,
+                                  const int16_t* v_w, int v_taps, int v_prec, int x0, int span, int tile_rows, int tile_src_rows,
+                                  const float* lut, float* out, vaura_stream_t s) {
+  if (!video || !h_rel || !h_w || !v_start || !v_w || !lut || !out) return VAURA_ERR_ARG;
+  if (layout != VAURA_YUV_NV12 && layout != VAURA_YUV_I420) return VAURA_ERR_ARG;
+  if (const int st = preproc_check(n_clips, T, 3, H, W, resize, crop_h, crop_w, F, S, seg_start, seg_stride, h_rel, h_w, h_taps, h_prec,
+                                   v_start, v_w, v_taps, v_prec, x0, span, tile_rows, tile_src_rows, lut, out))
+    return st;
+  if ((H & 1) || (W & 1)) return VAURA_ERR_SHAPE;                      // 4:2:0: one chroma sample per 2 x 2 luma block
+  // |acc| <= 3 * 2^20 * 256 < 2^31 for any such coefficients (the host's are below 2^16)
+  const int lim = 1 << 20;
+  if (y_off < 0 || y_off > 255 || cy < -lim || cy > lim || crv < -lim || crv > lim || cgu < -lim || cgu > lim || cgv < -lim || cgv > lim ||
+      cbu < -lim || cbu > lim)
+    return VAURA_ERR_ARG;
+  if (pitch < W || pitch > (int64_t)1 << 30 || (layout == VAURA_YUV_I420 && (pitch & 1))) return VAURA_ERR_ARG;
+  // the planes of one frame, in bytes from its start: luma [0, luma_end), chroma [chroma_offset, frame_end)
+  const int64_t luma_end = (int64_t)(H - 1) * pitch + W;
+  const int64_t chroma_bytes = layout == VAURA_YUV_NV12 ? (int64_t)(H / 2 - 1) * pitch + W
+                                                         : (int64_t)(H / 2) * (pitch / 2) + (int64_t)(H / 2 - 1) * (pitch / 2) + W / 2;
+  if (chroma_offset < luma_end || chroma_offset > (int64_t)1 << 40) return VAURA_ERR_ARG;      // planes overlap
+  const int64_t frame_end = chroma_offset + chroma_bytes;
+  if (frame_stride < frame_end || frame_stride > (int64_t)1 << 40) return VAURA_ERR_ARG;       // frames overlap
+  const int64_t n_frames = (int64_t)n_clips * T;
+  if (video_bytes < 0 || n_frames - 1 > (video_bytes - frame_end) / frame_stride || video_bytes < frame_end) return VAURA_ERR_ARG;
+  PreprocYuvArgs a;
+  a.src = video; a.h_rel = h_rel; a.h_w = h_w; a.v_start = v_start; a.v_w = v_w; a.lut = lut; a.out = out;
+  a.pitch = pitch; a.chroma_offset = chroma_offset; a.frame_stride = frame_stride;
+  a.y_off = y_off; a.cy = cy; a.crv = crv; a.cgu = cgu; a.cgv = cgv; a.cbu = cbu;
+  a.T = T; a.H = H; a.W = W; a.S = S; a.F = F; a.seg_start = seg_start; a.seg_stride = seg_stride;
+  a.crop_h = crop_h; a.crop_w = crop_w; a.h_taps = h_taps; a.h_prec = h_prec; a.v_taps = v_taps; a.v_prec = v_prec;
+  a.x0 = x0; a.span = span; a.tile_rows = tile_rows; a.tile_src_rows = tile_src_rows;
+  a.slab_dwords = yuv_slab_dwords(span);
+  const size_t lds = preproc_yuv_lds_bytes(crop_w, h_taps, span, tile_src_rows);
+  if (lds > PREPROC_LDS_LIMIT) return VAURA_ERR_SHAPE;
+  const dim3 grid((unsigned)((crop_h + tile_rows - 1) / tile_rows), (unsigned)((int64_t)n_clips * S * F));
+  hipStream_t st = as_stream(s);
+  if (layout == VAURA_YUV_NV12) VA_LAUNCH(video_preprocess_yuv_kernel<VAURA_YUV_NV12>, grid, dim3(64 * PREPROC_WAVES), lds, st, a);
+  else VA_LAUNCH(video_preprocess_yuv_kernel<VAURA_YUV_I420>, grid, dim3(64 * PREPROC_WAVES), lds, st, a);
+  return 0;
+}
+
+size_t vaura_video_preprocess_yuv420_lds_bytes(int layout, int crop_w, int h_taps, int span, int tile_src_rows) {
+  if ((layout != VAURA_YUV_NV12 && layout != VAURA_YUV_I420) || crop_w <= 0 || (crop_w & 3) || h_taps <= 0 || span <= 0 || tile_src_rows <= 0)
+    return 0;
+  return preproc_yuv_lds_bytes(crop_w, h_taps, span, tile_src_rows);
 }
 
 }  // extern "C"

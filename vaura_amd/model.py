@@ -197,23 +197,29 @@ class VAURAModel(nn.Module):
             vis_feats = self.visual_feature_extractor(frames)
         return self.visual_bridge(vis_feats.detach())
 
-    def frames_from_video(self, video, video_transforms=None, channels_last: bool = False, **segment_kw) -> torch.Tensor:
+    def frames_from_video(self, video, video_transforms=None, channels_last: bool = False, input_format: str = "rgb",
+                          color_matrix: str = "bt601", color_range: str = "limited", size=None, chroma_row=None,
+                          **segment_kw) -> torch.Tensor:
         """Decoded uint8 video -> what ``generate(frames=...)`` takes: (B, S, 3, 16, 224, 224) fp32 on the sampler's device.
         ``video``: uint8 (B, T, C, H, W), (T, C, H, W) or a list of per-clip tensors (``channels_last``: (.., H, W, C)).
+        ``input_format`` "nv12" / "i420": decoder surfaces instead, uint8 (B, T, R, P), (T, R, P) or a list of them, converted with
+        ``color_matrix`` ("bt601" / "bt709") and ``color_range`` ("limited" / "full") in the same launch; ``size=(H, W)`` and
+        ``chroma_row`` describe a padded surface (VideoPreprocessor.__call__).
         ``video_transforms``: the ``video_transforms_test`` list of configs/generate_*.yaml (Resize -> CenterCrop -> ToFloat32DType ->
         Normalize); None = its values in generate_vgg.yaml:53-65.  ``segment_kw``: segment_size_vframes / n_segments / step_size_seg
         of GenerateMultipleSegments.  The preprocessor (tap tables, device copies) is built once per distinct configuration."""
         from .preprocess import VideoPreprocessor
         key = (repr(_plain(video_transforms)) if video_transforms is not None else None, bool(channels_last),
-               tuple(sorted(segment_kw.items())))
+               tuple(sorted(segment_kw.items())), input_format, color_matrix, color_range)
         cache = self.__dict__.setdefault("_video_preprocessors", {})
         if key not in cache:
-            kw = dict(segment_kw, channels_last=channels_last)
+            kw = dict(segment_kw, channels_last=channels_last, input_format=input_format, color_matrix=color_matrix,
+                      color_range=color_range)
             cache[key] = (VideoPreprocessor(**kw) if video_transforms is None
                           else VideoPreprocessor.from_transforms_config(_plain(video_transforms), **kw))
         pre = cache[key]
         pre.device = self.device
-        return pre(video)
+        return pre(video) if input_format == "rgb" else pre(video, size=size, chroma_row=chroma_row)
 
     def audio_from_pcm(self, pcm, sample_rate: int, *, lengths=None, audio_transforms=None, duration: Optional[float] = None,
                        interleaved: bool = False):

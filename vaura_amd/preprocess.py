@@ -17,6 +17,13 @@ geometry the tests use, ``reference_u8`` equals torch's uint8 path on every pixe
 Segments (video_transforms.py:146-156, 205-236, ``is_start_random=False``, video only): ``stride = int(step_size_seg * F)``,
 ``S = floor((T - F) / stride) + 1`` (or ``n_segments``), and the run of segments is CENTRED in the clip: it starts at frame
 ``(T - int((S * step + 1 - step) * F)) // 2``; segment ``s`` holds frames ``start + s * stride .. + F``.  Frames outside are dropped.
+
+Decoder surfaces.  No decoder produces RGB: hardware decode hands over NV12 surfaces in device memory, software decode planar
+yuv420p.  With ``input_format="nv12"`` / ``"i420"`` the input is 8-bit 4:2:0 (1.5 bytes per pixel over the link) and one launch of
+``vaura_video_preprocess_yuv420`` computes ``yuv -> RGB uint8 -> the transforms above``.  The colour step is an integer formula the host
+defines (``yuv_coefficients``: 2^14-scaled BT.601 / BT.709 coefficients, limited or full range, chroma replicated over its 2 x 2 luma
+block) and the kernel only applies; ``yuv420_to_rgb_u8`` restates it on the CPU.  The reference does not pin it: its loader gets RGB
+from torchvision / PyAV (swscale); what pins it is a float64 evaluation of the same real coefficients (tests/test_preprocess_yuv_host.py).
 """
 from __future__ import annotations
 
@@ -122,6 +129,94 @@ def segment_starts(T: int, F: int, step_size_seg: float = 1.0, n_segments: Optio
     return S, (T - seq) // 2, stride
 
 
+INPUT_FORMATS = ("rgb", "nv12", "i420")
+_YUV_LAYOUT = {"nv12": 0, "i420": 1}                                  # VAURA_YUV_NV12 / VAURA_YUV_I420 (include/vaura_hip.h)
+_COLOR_MATRIX = {"bt601": (0.299, 0.114), "bt709": (0.2126, 0.0722)}   # (Kr, Kb)
+_COLOR_RANGE = {"limited": (16, 255 / 219, 255 / 224), "full": (0, 1.0, 1.0)}   # (y_off, luma scale, chroma scale)
+YUV_PREC = 14
+
+
+def yuv_coefficients_f64(color_matrix: str = "bt601", color_range: str = "limited") -> Tuple[int, Tuple[float, ...]]:
+    """(y_off, (cy, crv, cgu, cgv, cbu)) as real numbers: R = cy (Y - y_off) + crv (V - 128), G = .. + cgu (U - 128) + cgv (V - 128),
+    B = .. + cbu (U - 128)."""
+    if color_matrix not in _COLOR_MATRIX:
+        raise L.VauraHipError(f"color_matrix {color_matrix!r} is not built; one of {sorted(_COLOR_MATRIX)}")
+    if color_range not in _COLOR_RANGE:
+        raise L.VauraHipError(f"color_range {color_range!r} is not built; one of {sorted(_COLOR_RANGE)}")
+    kr, kb = _COLOR_MATRIX[color_matrix]
+    kg = 1 - kr - kb
+    y_off, sy, sc = _COLOR_RANGE[color_range]
+    return y_off, (sy, 2 * sc * (1 - kr), -2 * sc * kb * (1 - kb) / kg, -2 * sc * kr * (1 - kr) / kg, 2 * sc * (1 - kb))
+
+
+def yuv_coefficients(color_matrix: str = "bt601", color_range: str = "limited") -> Tuple[int, int, int, int, int, int]:
+    """(y_off, cy, crv, cgu, cgv, cbu): the integers the kernel applies, ``int(round(c * 2^14))``."""
+    y_off, cs = yuv_coefficients_f64(color_matrix, color_range)
+    return (y_off, *[int(round(c * (1 << YUV_PREC))) for c in cs])
+
+
+def yuv_surface(frames: torch.Tensor, layout: str, size: Optional[Tuple[int, int]] = None,
+                chroma_row: Optional[int] = None) -> Tuple[int, int, int, int, int]:
+    """(.., R, P) uint8 surfaces -> (H, W, R, P, chroma_row), with every refusal about the surface.  ``size=None``: tight frames,
+    R = 3H/2 and P = W; else P >= W is the pitch, luma sits in rows [0, H), the chroma plane starts at row ``chroma_row`` (default H)
+    and R >= chroma_row + H/2."""
+    if layout not in _YUV_LAYOUT:
+        raise L.VauraHipError(f"input_format {layout!r} is not a 4:2:0 layout; one of {sorted(_YUV_LAYOUT)}")
+    R, P = int(frames.shape[-2]), int(frames.shape[-1])
+    if size is None:
+        if R % 3:
+            raise L.VauraHipError(f"tight {layout} frames have R = 3H/2 rows; R = {R} is no multiple of 3 (pass size=(H, W) for a padded "
+                                  "surface)")
+        if chroma_row is not None:
+            raise L.VauraHipError("chroma_row needs size=(H, W)")
+        H, W = 2 * R // 3, P
+    else:
+        H, W = int(size[0]), int(size[1])
+    if H < 2 or W < 2 or H % 2 or W % 2:
+        raise L.VauraHipError(f"a 4:2:0 frame has even height and width; got H = {H}, W = {W}")
+    crow = H if chroma_row is None else int(chroma_row)
+    if P < W:
+        raise L.VauraHipError(f"pitch P = {P} is shorter than a row of W = {W} pixels")
+    if layout == "i420" and P % 2:
+        raise L.VauraHipError(f"i420 with an odd pitch P = {P}: the chroma planes have pitch P / 2")
+    if crow < H:
+        raise L.VauraHipError(f"chroma_row = {crow} lies inside the luma plane of H = {H} rows")
+    if R < crow + H // 2:
+        raise L.VauraHipError(f"R = {R} rows do not hold the chroma plane: chroma_row + H / 2 = {crow + H // 2}")
+    if frames.stride(-1) != 1 or frames.stride(-2) != P:
+        raise L.VauraHipError(f"the last two dims of a {layout} input must be contiguous; strides are {tuple(frames.stride())}")
+    return H, W, R, P, crow
+
+
+def yuv420_planes(frames: torch.Tensor, layout: str, size: Optional[Tuple[int, int]] = None, chroma_row: Optional[int] = None):
+    """(.., R, P) uint8 surfaces (``yuv_surface``) -> ``(y (.., H, W), u (.., H/2, W/2), v (.., H/2, W/2))``."""
+    H, W, R, P, crow = yuv_surface(frames, layout, size, chroma_row)
+    lead = tuple(frames.shape[:-2])
+    y = frames[..., :H, :W]
+    c = frames[..., crow:crow + H // 2, :].reshape(*lead, -1)          # the chroma plane(s) as bytes
+    if layout == "nv12":
+        c = c.reshape(*lead, H // 2, P)[..., :W].reshape(*lead, H // 2, W // 2, 2)
+        return y, c[..., 0], c[..., 1]
+    c = c.reshape(*lead, 2, H // 2, P // 2)[..., :W // 2]
+    return y, c[..., 0, :, :], c[..., 1, :, :]
+
+
+def yuv420_to_rgb_u8(y: torch.Tensor, u: torch.Tensor, v: torch.Tensor, color_matrix: str = "bt601",
+                     color_range: str = "limited") -> torch.Tensor:
+    """The kernel's colour step on the CPU (torch int32): y (.., H, W), u and v (.., H/2, W/2) uint8 -> RGB uint8 (.., 3, H, W).
+    ``level = clamp((cy (Y - y_off) + cu (U - 128) + cv (V - 128) + 2^13) >> 14, 0, 255)``, arithmetic shift; the chroma sample at
+    ``(y >> 1, x >> 1)`` serves its 2 x 2 luma block."""
+    y_off, cy, crv, cgu, cgv, cbu = yuv_coefficients(color_matrix, color_range)
+    H, W = y.shape[-2:]
+    if tuple(u.shape[-2:]) != (H // 2, W // 2) or u.shape != v.shape or H % 2 or W % 2:
+        raise L.VauraHipError(f"4:2:0 planes: y {tuple(y.shape)} needs u, v of (.., {H // 2}, {W // 2}); got {tuple(u.shape)}, {tuple(v.shape)}")
+    up = lambda c: (c.cpu().to(torch.int32) - 128).repeat_interleave(2, -2).repeat_interleave(2, -1)  # noqa: E731
+    yy = (y.cpu().to(torch.int32) - y_off) * cy + (1 << (YUV_PREC - 1))
+    uu, vv = up(u), up(v)
+    rgb = torch.stack([yy + crv * vv, yy + cgu * uu + cgv * vv, yy + cbu * uu], dim=-3)
+    return (rgb >> YUV_PREC).clamp_(0, 255).to(torch.uint8)
+
+
 class _Geometry:
     """Tables of one (H, W, resize, crop): host copies, and device copies per device."""
 
@@ -144,28 +239,33 @@ class _Geometry:
         self.span = int(self.h["start"].max()) + self.h["taps"] - self.x0
         self.h_rel = (self.h["start"] - self.x0).astype(np.int32)
         self._dev: Dict[str, tuple] = {}
-        self._tiles: Dict[bool, Tuple[int, int]] = {}
+        self._tiles: Dict[object, Tuple[int, int]] = {}
 
     def tile_src_rows(self, tile_rows: int) -> int:
         st, ch, k = self.v["start"], self.crop[0], self.v["taps"]
         return max(int(st[min(r0 + tile_rows, ch) - 1]) + k - int(st[r0]) for r0 in range(0, ch, tile_rows))
 
-    def tiles(self, channels_last: bool) -> Tuple[int, int]:
-        """(tile_rows, tile_src_rows): the largest power of two <= 32 output rows whose workgroup stays below the LDS target."""
-        if channels_last not in self._tiles:
+    def tiles(self, channels_last: bool, yuv_layout: Optional[str] = None) -> Tuple[int, int]:
+        """(tile_rows, tile_src_rows): the largest power of two <= 32 output rows whose workgroup stays below the LDS target.
+        ``yuv_layout`` ("nv12" / "i420"): for the launch from 4:2:0 surfaces, whose row slabs are larger."""
+        key = channels_last if yuv_layout is None else yuv_layout
+        if key not in self._tiles:
             lib = L.lib()
             pick = None
             for tr in (32, 16, 8, 4, 2, 1):
                 rows = self.tile_src_rows(tr)
-                need = lib.vaura_video_preprocess_lds_bytes(int(channels_last), self.crop[1], self.h["taps"], self.span, rows)
+                if yuv_layout is None:
+                    need = lib.vaura_video_preprocess_lds_bytes(int(channels_last), self.crop[1], self.h["taps"], self.span, rows)
+                else:
+                    need = lib.vaura_video_preprocess_yuv420_lds_bytes(_YUV_LAYOUT[yuv_layout], self.crop[1], self.h["taps"], self.span, rows)
                 if need <= _LDS_TARGET or (tr == 1 and need <= _LDS_LIMIT):
                     pick = (tr, rows)
                     break
             if pick is None:
                 raise L.VauraHipError(f"a {self.H} x {self.W} source does not fit the kernel's {_LDS_LIMIT // 1024} KiB of LDS at one "
                                       "output row per workgroup")
-            self._tiles[channels_last] = pick
-        return self._tiles[channels_last]
+            self._tiles[key] = pick
+        return self._tiles[key]
 
     def device_tables(self, dev: torch.device):
         key = str(dev)
@@ -189,7 +289,14 @@ def _resample_axis(x: torch.Tensor, tab: dict, axis: int) -> torch.Tensor:
 class VideoPreprocessor:
     def __init__(self, resize: int = 256, crop: Sequence[int] = (224, 224), mean: Sequence[float] = (0.5, 0.5, 0.5),
                  std: Sequence[float] = (0.5, 0.5, 0.5), segment_size_vframes: int = 16, n_segments: Optional[int] = None,
-                 step_size_seg: float = 1.0, channels_last: bool = False, device: Union[str, torch.device, None] = None):
+                 step_size_seg: float = 1.0, channels_last: bool = False, device: Union[str, torch.device, None] = None,
+                 input_format: str = "rgb", color_matrix: str = "bt601", color_range: str = "limited"):
+        if input_format not in INPUT_FORMATS:
+            raise L.VauraHipError(f"input_format {input_format!r} is not built; one of {list(INPUT_FORMATS)}")
+        self.input_format, self.color_matrix, self.color_range = input_format, color_matrix, color_range
+        self.yuv = yuv_coefficients(color_matrix, color_range)          # refuses an unknown matrix / range
+        if input_format != "rgb" and channels_last:
+            raise L.VauraHipError(f"channels_last=True with input_format={input_format!r}: a 4:2:0 surface has planes, not channels")
         if isinstance(crop, int):
             crop = (crop, crop)
         if isinstance(resize, (list, tuple)):
@@ -255,23 +362,32 @@ class VideoPreprocessor:
 
     # ---- input handling
     def _clips(self, video) -> List[torch.Tensor]:
-        """-> list of (b, T, C, H, W) / (b, T, H, W, C) uint8 tensors, one per group of consecutive clips of one shape."""
+        """-> list of (b, T, C, H, W) / (b, T, H, W, C) uint8 tensors ((b, T, R, P) surfaces for a 4:2:0 format), one per clip or
+        batch of one shape."""
         items = list(video) if isinstance(video, (list, tuple)) else [video]
         if not items:
             raise L.VauraHipError("VideoPreprocessor: no clips")
+        yuv = self.input_format != "rgb"
+        nd = 3 if yuv else 4                                               # dims of one clip
         out = []
         for v in items:
             if not torch.is_tensor(v):
                 raise L.VauraHipError(f"VideoPreprocessor takes uint8 tensors, got {type(v).__name__}")
             if v.dtype != torch.uint8:
+                if yuv:
+                    raise L.VauraHipError(f"input_format={self.input_format!r} takes 8-bit surfaces (uint8); {v.dtype} (10-bit P010 and "
+                                          "the like) is not built")
                 raise L.VauraHipError(f"VideoPreprocessor takes decoded uint8 frames; a {v.dtype} input has been transformed already")
             if isinstance(video, (list, tuple)):
-                if v.dim() != 4:
-                    raise L.VauraHipError(f"clips of a list are (T, C, H, W) or (T, H, W, C); got {tuple(v.shape)}")
+                if v.dim() != nd:
+                    raise L.VauraHipError(f"clips of a list are {'(T, R, P) surfaces' if yuv else '(T, C, H, W) or (T, H, W, C)'}; "
+                                          f"got {tuple(v.shape)}")
                 v = v[None]
-            elif v.dim() == 4:
+            elif v.dim() == nd:
                 v = v[None]
-            elif v.dim() != 5:
+            elif v.dim() != nd + 1:
+                if yuv:
+                    raise L.VauraHipError(f"{self.input_format} video must be (B, T, R, P) or (T, R, P) surfaces; got {tuple(v.shape)}")
                 raise L.VauraHipError(f"video must be (B, T, C, H, W) or (T, C, H, W) (channels last: (.., H, W, C)); got {tuple(v.shape)}")
             out.append(v)
         return out
@@ -284,10 +400,13 @@ class VideoPreprocessor:
         return b, T, C, H, W
 
     # ---- CPU restatement
-    def reference_u8(self, video) -> torch.Tensor:
-        """The kernel's integer arithmetic on the CPU with the same tap tables: uint8 levels (B, S, C, F, h, w) before the scaling."""
+    def reference_u8(self, video, size: Optional[Tuple[int, int]] = None, chroma_row: Optional[int] = None) -> torch.Tensor:
+        """The kernel's integer arithmetic on the CPU with the same tap tables: uint8 levels (B, S, C, F, h, w) before the scaling.
+        A 4:2:0 input goes through ``yuv420_to_rgb_u8`` first (``size`` / ``chroma_row`` as in ``__call__``)."""
         outs = []
         for v in self._clips(video):
+            if self.input_format != "rgb":
+                v = yuv420_to_rgb_u8(*yuv420_planes(v.cpu(), self.input_format, size, chroma_row), self.color_matrix, self.color_range)
             b, T, C, H, W = self._dims(v)
             g = self.geometry(H, W)
             S, first, stride = segment_starts(T, self.segment_size_vframes, self.step_size_seg, self.n_segments)
@@ -335,18 +454,42 @@ class VideoPreprocessor:
             first, stride, L.ptr(h_rel), L.ptr(h_w), g.h["taps"], g.h["prec"], L.ptr(v_start), L.ptr(v_w), g.v["taps"], g.v["prec"],
             g.x0, g.span, tile_rows, tile_src, L.ptr(self._lut_dev[key]), L.ptr(out), L.current_stream(dev)), "vaura_video_preprocess")
 
+    def _launch_yuv(self, v: torch.Tensor, out: torch.Tensor, dev: torch.device, size, chroma_row) -> None:
+        b, T = v.shape[:2]
+        H, W, R, P, crow = yuv_surface(v, self.input_format, size, chroma_row)
+        # frame n = clip * T + t sits at byte n * frame_stride: true of a contiguous batch and of the usual views of one
+        fs = v.stride(1) if T > 1 else (v.stride(0) if b > 1 else R * P)
+        if fs < R * P or (b > 1 and T > 1 and v.stride(0) != T * fs):
+            v = v.contiguous()
+            fs = R * P
+        g = self.geometry(H, W)
+        S, first, stride = segment_starts(T, self.segment_size_vframes, self.step_size_seg, self.n_segments)
+        if tuple(out.shape) != (b, S, 3, self.segment_size_vframes, *self.crop):
+            raise L.VauraHipError(f"clips of one call must give the same number of segments; this group gives {S}, the first {out.shape[1]}")
+        tile_rows, tile_src = g.tiles(False, self.input_format)
+        h_rel, h_w, v_start, v_w = g.device_tables(dev)
+        key = str(dev)
+        if key not in self._lut_dev:
+            self._lut_dev[key] = self.lut.to(dev)
+        L.check(L.lib().vaura_video_preprocess_yuv420(
+            L.ptr(v), (b * T - 1) * fs + R * P, _YUV_LAYOUT[self.input_format], P, crow * P, fs, b, T, H, W, *self.yuv, self.resize,
+            self.crop[0], self.crop[1], self.segment_size_vframes, S, first, stride, L.ptr(h_rel), L.ptr(h_w), g.h["taps"], g.h["prec"],
+            L.ptr(v_start), L.ptr(v_w), g.v["taps"], g.v["prec"], g.x0, g.span, tile_rows, tile_src, L.ptr(self._lut_dev[key]),
+            L.ptr(out), L.current_stream(dev)), "vaura_video_preprocess_yuv420")
+
     @torch.no_grad()
-    def __call__(self, video) -> torch.Tensor:
+    def __call__(self, video, size: Optional[Tuple[int, int]] = None, chroma_row: Optional[int] = None) -> torch.Tensor:
         """uint8 (B, T, C, H, W), (T, C, H, W) or a list of per-clip (T, C, H, W) tensors whose H, W may differ (channels last:
-        (.., H, W, C)) -> fp32 (B, S, C, F, crop_h, crop_w) on the device.  Host tensors are copied once, as uint8."""
+        (.., H, W, C)) -> fp32 (B, S, C, F, crop_h, crop_w) on the device.  Host tensors are copied once, as uint8.
+
+        ``input_format`` "nv12" / "i420": uint8 (B, T, R, P), (T, R, P) or a list of per-clip (T, R, P) surfaces.  Tight frames have
+        R = 3H/2 rows of P = W bytes (H rows of luma, then the chroma plane).  A padded decoder surface passes ``size=(H, W)``: P >= W
+        is the pitch, luma sits in rows [0, H), the chroma plane starts at row ``chroma_row`` (default H) and R >= chroma_row + H/2;
+        bytes outside the planes never reach the result.  Host surfaces are copied once, as they are (1.5 bytes per pixel)."""
+        yuv = self.input_format != "rgb"
+        if not yuv and (size is not None or chroma_row is not None):
+            raise L.VauraHipError("size / chroma_row describe a 4:2:0 surface; input_format is 'rgb'")
         clips = self._clips(video)
-        dev = self.device
-        if dev is None:
-            dev = next((v.device for v in clips if v.device.type == "cuda"), None)
-            if dev is None:
-                if not torch.cuda.is_available():
-                    raise L.VauraHipError("VideoPreprocessor runs on a HIP device only (reference_u8 is the CPU restatement)")
-                dev = torch.device("cuda", torch.cuda.current_device())
         # one launch per run of consecutive clips of one geometry (the output keeps the clips' order)
         groups: List[List[torch.Tensor]] = []
         for v in clips:
@@ -355,9 +498,21 @@ class VideoPreprocessor:
             else:
                 groups.append([v])
         for grp in groups:                                                   # every refusal before any device work
-            _, T, _, H, W = self._dims(grp[0])
+            if yuv:
+                T = grp[0].shape[1]
+                for v in grp:
+                    H, W = yuv_surface(v, self.input_format, size, chroma_row)[:2]
+            else:
+                _, T, _, H, W = self._dims(grp[0])
             self.geometry(H, W)
             segment_starts(T, self.segment_size_vframes, self.step_size_seg, self.n_segments)
+        dev = self.device
+        if dev is None:
+            dev = next((v.device for v in clips if v.device.type == "cuda"), None)
+            if dev is None:
+                if not torch.cuda.is_available():
+                    raise L.VauraHipError("VideoPreprocessor runs on a HIP device only (reference_u8 is the CPU restatement)")
+                dev = torch.device("cuda", torch.cuda.current_device())
         S = segment_starts(clips[0].shape[1], self.segment_size_vframes, self.step_size_seg, self.n_segments)[0]
         B = sum(v.shape[0] for v in clips)
         with torch.cuda.device(dev):
@@ -365,7 +520,11 @@ class VideoPreprocessor:
             b0 = 0
             for grp in groups:
                 grp = [v.to(dev, non_blocking=True) for v in grp]               # uint8 over the link, once
-                v = (grp[0] if len(grp) == 1 else torch.cat(grp, dim=0)).contiguous()
-                self._launch(v, out[b0:b0 + v.shape[0]], dev)                  # same stream as the copy: v may be freed after it
+                if yuv:
+                    v = grp[0] if len(grp) == 1 else torch.cat(grp, dim=0)      # a single surface stays the view it is
+                    self._launch_yuv(v, out[b0:b0 + v.shape[0]], dev, size, chroma_row)
+                else:
+                    v = (grp[0] if len(grp) == 1 else torch.cat(grp, dim=0)).contiguous()
+                    self._launch(v, out[b0:b0 + v.shape[0]], dev)              # same stream as the copy: v may be freed after it
                 b0 += v.shape[0]
         return out
