@@ -688,6 +688,22 @@ size_t vaura_dac_decode_window_workspace_elems(const vaura_codec* c, int B, cons
  * taps, dilations and strides (the sample interval of a frame taken backwards through the layers; a transposed conv has k = 2r and
  * pad ceil(r / 2)): 10 for the 44.1 kHz geometry.  -1: c NULL or not such a geometry.  Reads no device pointer.                      */
 int vaura_dac_decode_halo(const vaura_codec* c);
+/* vaura_dac_decode_window straight from the decode loop's pattern sequence: seq (B, K, S) int32 as vaura_pattern_build_delays lays it
+ * out and the loop fills it — frame t of codebook q at step t + 1 + d_q, d = delays_host (K ints ON THE HOST, sorted as the pattern ops
+ * take them; NULL: d_q = q), T = S - 1 - max(d) frames per clip, K >= c->n_codebooks (the first c->n_codebooks rows are decoded).
+ * Only the pack differs: it gathers seq[b, q, t + 1 + d_q] where the window call reads codes[b, q, t]; the plan of the windows, the gap,
+ * the pass, the kernels and the instance choice are vaura_dac_decode_window's with T_max = T, and so are the samples, bit for bit, of
+ * the call on the reverted codes.  A caller that streams audio while the loop still runs needs no reverted tensor: the frames a window
+ * and its halo cover must be FINAL in seq (every codebook's slot sampled), lengths[b] is the clip's whole length T_b, not what is final
+ * so far.  A slot that holds no code (unknown, special token) is never used as an index: it is packed as code 0.
+ * The 4 workspaces must hold vaura_dac_decode_window_seq_workspace_elems(...) floats each (0: arguments the call refuses).
+ * VAURA_ERR_ARG: what vaura_dac_decode_window refuses, K < c->n_codebooks or > 16, S < 2, a delay < 0 or > S - 2, or a window whose
+ * halo reaches a step >= S; VAURA_ERR_SHAPE / VAURA_ERR_DTYPE as there.  All before any launch.                                       */
+int vaura_dac_decode_window_seq(const vaura_codec* c, const int32_t* seq, int B, int K, int S, const int32_t* delays_host,
+                                const int32_t* lengths, const int32_t* starts, const int32_t* counts, float* wav, int N_max,
+                                vaura_stream_t s);
+size_t vaura_dac_decode_window_seq_workspace_elems(const vaura_codec* c, int B, int K, int S, const int32_t* delays_host,
+                                                   const int32_t* lengths, const int32_t* starts, const int32_t* counts);
 /* Op-level access for parity tests: ONE convolution of the decoder (WNConv1d / WNConvTranspose1d of descript-audio-codec's
  * DecoderBlock / ResidualUnit) in the arithmetic of `precision` (vaura_codec.precision; weights laid out for it).
  * in (B, Lin, Cin) fp32 channels-last, already activated -> out (B, Lout, Cout) fp32 = conv(in) + bias,

@@ -277,6 +277,11 @@ SIGNATURES = {
     "vaura_dac_decode_window_workspace_elems": (C.c_size_t, [C.POINTER(Codec), C.c_int, C.POINTER(C.c_int32), C.POINTER(C.c_int32),
                                                              C.POINTER(C.c_int32)]),
     "vaura_dac_decode_halo": (C.c_int, [C.POINTER(Codec)]),
+    "vaura_dac_decode_window_seq": (C.c_int, [C.POINTER(Codec), C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int32),
+                                              C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_void_p, C.c_int,
+                                              C.c_void_p]),
+    "vaura_dac_decode_window_seq_workspace_elems": (C.c_size_t, [C.POINTER(Codec), C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int32),
+                                                                 C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "vaura_dac_encode_clips": (C.c_int, [C.POINTER(CodecEncoder), C.c_void_p, C.c_int, C.c_int64, C.POINTER(C.c_int64), C.c_void_p,
                                          C.c_void_p]),
     "vaura_dac_encode_clips_workspace_elems": (C.c_size_t, [C.POINTER(CodecEncoder), C.c_int, C.POINTER(C.c_int64)]),

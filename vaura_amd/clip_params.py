@@ -280,3 +280,60 @@ def prompt_row_steps(prompt_lengths: List[int], first_delay: int, cfg: bool = Fa
     for the null-condition rows."""
     n = [int(p) + int(first_delay) for p in prompt_lengths for _ in range(int(num_candidates))]
     return n + n if cfg else n
+
+
+# ---- audio out of one generate() call while its decode loop still runs (DecoderEngine.generate_codes_stream): which frames may leave
+# after how many sampled steps.  Pure bookkeeping, no tensors.
+def check_block_frames(block_frames) -> int:
+    if isinstance(block_frames, bool) or not isinstance(block_frames, int) or block_frames < 1:
+        raise _error(f"block_frames must be a positive number of frames, got {block_frames!r}")
+    return block_frames
+
+
+def final_frames(j: int, T: int, start: int, d_max: int) -> int:
+    """F(j): frames of a T-frame clip that are final after ``j`` sampled steps of a loop that starts sampling at step ``start``.  Frame t
+    of codebook q is written at step t + 1 + d_q, and steps [start, start + j) are filled: t is final once t + 1 + max(d) < start + j."""
+    return max(0, min(T, start + j - 1 - d_max))
+
+
+def releasable_frames(j: int, T_b: int, T: int, start: int, d_max: int, H: int) -> int:
+    """Frames of clip b (T_b of the call's T) whose SAMPLES are final after ``j`` sampled steps: a frame's samples depend on ``H`` frames
+    either side, so all but the last H of the F_b = min(F(j), T_b) final frames — and all T_b once the clip is complete."""
+    F_b = min(final_frames(j, T, start, d_max), T_b)
+    return T_b if F_b == T_b else max(0, F_b - H)
+
+
+def stream_schedule(T: int, lengths: Optional[List[int]], start: int, delays: Optional[List[int]], H: int, block_frames: int,
+                    num_codebooks: Optional[int] = None) -> List[tuple]:
+    """The pieces a streaming call cuts its S - ``start`` sampled steps into, S = T + max(d) + 1: a list of (n_steps, [(lo_b, hi_b) per
+    clip]) — after the piece's n_steps further steps the frames [lo_b, hi_b) of clip b have become releasable (``releasable_frames``;
+    lo == hi: nothing for that clip in this piece).  ``lengths``: T_b per clip (None: one clip of T frames — every clip of the batch);
+    ``delays``: the codebook delays (None: 0 .. ``num_codebooks`` - 1); ``H``: the codec's halo (``codec_clips.decode_halo``).
+    A piece ends at the first step count at which the call's longest clip has ``block_frames`` more releasable frames than at the
+    previous boundary's target — m = k * block_frames is releasable from j = m + H + 1 + max(d) - start on —, the last one at S - start,
+    where every clip is complete.  Every piece has at least one step (a long prompt makes several targets due at once: one piece),
+    so the steps sum to S - start and the ranges of a clip tile [0, T_b) in order."""
+    block_frames = check_block_frames(block_frames)
+    if delays is None:
+        if num_codebooks is None:
+            raise _error("stream_schedule needs the delays or the number of codebooks")
+        delays = list(range(int(num_codebooks)))
+    d_max = max(int(d) for d in delays)
+    lens = [int(T)] if lengths is None else [int(n) for n in lengths]
+    if T < 1 or not lens or min(lens) < 1 or max(lens) > T:
+        raise _error(f"stream_schedule: clip lengths {lens} must lie in 1 .. T = {T}")
+    total = T + d_max + 1 - int(start)
+    if start < 1 or total < 1:
+        raise _error(f"stream_schedule: the first sampled step {start} must lie in 1 .. {T + d_max}")
+    bounds = []
+    for m in range(block_frames, T, block_frames):
+        j = min(total, max(1, m + H + 1 + d_max - start))
+        if j < total and (not bounds or j > bounds[-1]):
+            bounds.append(j)
+    bounds.append(total)
+    out, prev, done = [], 0, [0] * len(lens)
+    for j in bounds:
+        upto = [releasable_frames(j, n, T, start, d_max, H) for n in lens]
+        out.append((j - prev, [(a, z) for a, z in zip(done, upto)]))
+        prev, done = j, upto
+    return out

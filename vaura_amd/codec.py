@@ -175,6 +175,12 @@ class DacModelWrapper(nn.Module):
         return self.engine().decode_window(codes, starts, counts, lengths)
 
     @torch.no_grad()
+    def decode_window_seq(self, seq: torch.Tensor, starts, counts, lengths=None, delays=None):
+        """``decode_window`` straight from the decode loop's pattern sequence (B, K, S) int32 under the codebook ``delays`` (None:
+        0 .. K - 1): the same samples without a reverted code tensor (``CodecEngine.decode_window_seq``)."""
+        return self.engine().decode_window_seq(seq, starts, counts, lengths, delays)
+
+    @torch.no_grad()
     def decode_windowed(self, codes: torch.Tensor, window: int, lengths=None):
         """``decode`` / ``decode_clips`` bit for bit as successive window calls of ``window`` frames: the codec's workspaces follow the
         window, not the clip (``CodecEngine.decode_windowed``)."""

@@ -1999,6 +1999,9 @@ struct WindowLayout {
   const int* skip;                    // per window: halo frames in front of the frames asked for
   const int* window;                  // per caller's clip (B): index of its window, -1 for count 0
   const int* count;                   // per caller's clip (B)
+  // vaura_dac_decode_window_seq: the caller's tensor is the decode loop's pattern sequence (B, seq_K, seq_S), not codes (seq_S = 0)
+  int seq_K = 0, seq_S = 0;
+  int seq_delays[16] = {0};
 };
 // codes (B, K, Tmax) -> packed (K, total): the window's frames from frame src[i] of clip b[i] on, code 0 on the gap frames behind it
 __global__ __launch_bounds__(256) void window_pack_codes_kernel(const int32_t* __restrict__ codes, int32_t* __restrict__ packed, WindowChunk k,
@@ -2007,6 +2010,19 @@ __global__ __launch_bounds__(256) void window_pack_codes_kernel(const int32_t* _
   const int32_t* src = codes + ((size_t)k.b[i] * K + kk) * Tmax + k.src[i];
   for (int t = blockIdx.x * 256 + threadIdx.x; t < k.len[i]; t += gridDim.x * 256)
     packed[(size_t)kk * total + k.off[i] + t] = t < k.aux[i] ? src[t] : 0;
+}
+// The same pack from the decode loop's pattern sequence (vaura_dac_decode_window_seq): seq (B, K, S) holds frame t of codebook q at step
+// t + 1 + d_q (vaura_pattern_build_delays), so the window's frames are gathered from there and no reverted tensor exists.  A value that
+// is no code (an unknown slot, the special token: the host's checks keep every window off them) is packed as code 0, never used as an index.
+struct SeqDelays { int d[16]; };
+__global__ __launch_bounds__(256) void window_pack_seq_kernel(const int32_t* __restrict__ seq, int32_t* __restrict__ packed, WindowChunk k,
+                                                              SeqDelays dl, int K, int S, int64_t total, int card) {
+  const int i = blockIdx.y, kk = blockIdx.z;
+  const int32_t* src = seq + ((size_t)k.b[i] * K + kk) * S + k.src[i] + 1 + dl.d[kk];
+  for (int t = blockIdx.x * 256 + threadIdx.x; t < k.len[i]; t += gridDim.x * 256) {
+    const int32_t v = t < k.aux[i] ? src[t] : 0;
+    packed[(size_t)kk * total + k.off[i] + t] = (uint32_t)v < (uint32_t)card ? v : 0;
+  }
 }
 // packed samples -> wav (B, n_out): the len[i] * hop samples from packed frame off[i] on, 0 behind them (len 0: a row of zeros, nothing read)
 __global__ __launch_bounds__(256) void window_unpack_wav_kernel(const float* __restrict__ packed, float* __restrict__ wav, WindowChunk k,
@@ -2139,6 +2155,13 @@ static int va_dac_decode_pass(const vaura_codec* c, const int32_t* codes, int B,
       const WindowChunk k = va_window_pack_chunk(*lay, w0);
       int widest = 0;
       for (int i = 0; i < k.n; ++i) widest = std::max(widest, k.len[i]);
+      if (lay->win->seq_S > 0) {
+        SeqDelays dl;
+        for (int q = 0; q < 16; ++q) dl.d[q] = lay->win->seq_delays[q];
+        VA_LAUNCH(window_pack_seq_kernel, dim3(va_clip_gx(widest), k.n, c->n_codebooks), dim3(256), 0, s, codes, packed, k, dl,
+                  lay->win->seq_K, lay->win->seq_S, lay->total, c->codebook_size);
+        continue;
+      }
       VA_LAUNCH(window_pack_codes_kernel, dim3(va_clip_gx(widest), k.n, c->n_codebooks), dim3(256), 0, s, codes, packed, k,
                 c->n_codebooks, Tc, lay->total);
     }
@@ -2328,18 +2351,24 @@ size_t vaura_dac_decode_window_workspace_elems(const vaura_codec* c, int B, cons
   return p.total > 0 ? va_decode_clips_elems(c, p.total) : 0;
 }
 
-int vaura_dac_decode_window(const vaura_codec* c, const int32_t* codes, int B, int T_max, const int32_t* lengths, const int32_t* starts,
-                            const int32_t* counts, float* wav, int N_max, vaura_stream_t s_) {
+// the window pass on a caller's tensor of T_max frames per clip: codes (B, K, T_max), or with `sq` the pattern sequence it describes
+struct SeqSource { int K, S, d_max; int delays[16]; };
+static int va_dac_decode_window_any(const vaura_codec* c, const int32_t* codes, int B, int T_max, const int32_t* lengths, const int32_t* starts,
+                                    const int32_t* counts, float* wav, int N_max, const SeqSource* sq, vaura_stream_t s_) {
   if (!c || !codes || !wav || !starts || !counts || B <= 0 || T_max <= 0 || N_max <= 0) return VAURA_ERR_ARG;
   if (c->n_blocks < 1 || c->n_blocks > 4 || c->n_units != 3 || c->n_codebooks > 16 || c->codebook_dim > 8)
     return VAURA_ERR_SHAPE;
   if (va_decode_halo(c) < 0) return VAURA_ERR_SHAPE;
   const WindowPlan p = va_window_plan(c, B, T_max, lengths, starts, counts, N_max);
   if (p.total == 0) return VAURA_ERR_ARG;                // a length, start or count out of range, or nothing to decode
+  if (sq)                                                // the last frame a window reads (its halo included) lies at a step of the sequence
+    for (size_t w = 0; w < p.clip.size(); ++w)
+      if ((int64_t)p.lo[w] + p.len[w] + sq->d_max > (int64_t)sq->S - 1) return VAURA_ERR_ARG;
   int64_t hop = 1;
   for (int b = 0; b < c->n_blocks; ++b) hop *= c->rates[b];
   // as vaura_dac_decode_clips: the largest level of the packed windows must fit the int arithmetic of the launches
-  if (p.total < 0 || va_decode_clips_elems(c, p.total) > (size_t)0x7fffffff || (int64_t)B * T_max > 0x7fffffff ||
+  const int64_t src_elems = sq ? (int64_t)B * sq->K * sq->S : (int64_t)B * T_max;
+  if (p.total < 0 || va_decode_clips_elems(c, p.total) > (size_t)0x7fffffff || src_elems > 0x7fffffff ||
       (int64_t)N_max * hop > 0x7fffffff) return VAURA_ERR_SHAPE;
   if (c->ws_elems < va_decode_clips_elems(c, p.total)) return VAURA_ERR_ARG;
   for (int i = 0; i < 4; ++i) if (!c->ws[i]) return VAURA_ERR_ARG;
@@ -2348,10 +2377,48 @@ int vaura_dac_decode_window(const vaura_codec* c, const int32_t* codes, int B, i
   WindowLayout win;
   win.B = B; win.n_max = N_max; win.clip = p.clip.data(); win.lo = p.lo.data(); win.skip = p.skip.data();
   win.window = p.window.data(); win.count = p.count.data();
+  if (sq) {
+    win.seq_K = sq->K; win.seq_S = sq->S;
+    for (int q = 0; q < 16; ++q) win.seq_delays[q] = sq->delays[q];
+  }
   ClipLayout lay;
   lay.B = (int)p.clip.size(); lay.gap = p.gap; lay.total = p.total; lay.off = p.off.data(); lay.len = p.len.data(); lay.aux = nullptr;
   lay.win = &win;
   return va_dac_decode_pass(c, codes, B, T_max, wav, &lay, as_stream(s_));
+}
+
+int vaura_dac_decode_window(const vaura_codec* c, const int32_t* codes, int B, int T_max, const int32_t* lengths, const int32_t* starts,
+                            const int32_t* counts, float* wav, int N_max, vaura_stream_t s_) {
+  return va_dac_decode_window_any(c, codes, B, T_max, lengths, starts, counts, wav, N_max, nullptr, s_);
+}
+
+// the pattern sequence of a window_seq call: K rows of S steps under `delays_host` (NULL: 0 .. K - 1) hold T = S - 1 - max(d) frames
+static bool va_seq_source(const vaura_codec* c, int K, int S, const int32_t* delays_host, SeqSource* out) {
+  if (!c || K < c->n_codebooks || K < 1 || K > 16 || S < 2) return false;
+  out->K = K; out->S = S; out->d_max = 0;
+  for (int q = 0; q < 16; ++q) {
+    const int d = q < K ? (delays_host ? delays_host[q] : q) : 0;
+    if (d < 0 || d > S - 2) return false;
+    out->delays[q] = d;
+    out->d_max = std::max(out->d_max, d);
+  }
+  return true;
+}
+
+size_t vaura_dac_decode_window_seq_workspace_elems(const vaura_codec* c, int B, int K, int S, const int32_t* delays_host,
+                                                   const int32_t* lengths, const int32_t* starts, const int32_t* counts) {
+  SeqSource sq;
+  if (!c || !starts || !counts || B <= 0 || !va_seq_source(c, K, S, delays_host, &sq)) return 0;
+  const WindowPlan p = va_window_plan(c, B, S - 1 - sq.d_max, lengths, starts, counts, 0);
+  return p.total > 0 ? va_decode_clips_elems(c, p.total) : 0;
+}
+
+int vaura_dac_decode_window_seq(const vaura_codec* c, const int32_t* seq, int B, int K, int S, const int32_t* delays_host,
+                                const int32_t* lengths, const int32_t* starts, const int32_t* counts, float* wav, int N_max,
+                                vaura_stream_t s_) {
+  SeqSource sq;
+  if (!c || !seq || B <= 0 || !va_seq_source(c, K, S, delays_host, &sq)) return VAURA_ERR_ARG;
+  return va_dac_decode_window_any(c, seq, B, S - 1 - sq.d_max, lengths, starts, counts, wav, N_max, &sq, s_);
 }
 
 int vaura_snake(const float* x, const float* alpha, float* y, int64_t rows, int C, vaura_stream_t s_) {

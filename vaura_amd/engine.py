@@ -687,6 +687,13 @@ class DecoderEngine:
             self.near_ties += int(words[6])
             self.state[6:8].zero_()
             st &= ~4
+        err = self._status_error(st)
+        if err is not None:
+            raise err
+
+    @staticmethod
+    def _status_error(st: int) -> Optional["L.VauraHipError"]:
+        """The error of a status word whose bits 1 / 2 are set (None otherwise): ONE error naming every condition, carrying ``.status``."""
         msgs = []
         if st & 2:
             msgs.append(
@@ -701,7 +708,8 @@ class DecoderEngine:
         if msgs:
             err = L.VauraHipError(f"decode loop (status word {st:#x}): " + "; ALSO: ".join(msgs))
             err.status = st
-            raise err
+            return err
+        return None
 
     def revert(self) -> torch.Tensor:
         return self._pattern_revert(self.seq, self.codes_i32, -1, self.cfg.d_codebook)      # frames past a clip's own end: the special id
@@ -773,28 +781,9 @@ class DecoderEngine:
         K = self.cfg.num_codebooks
         self._fc = None                       # the K/V cache is about to be reused: forward_cached must start over
         with off_null_stream(self.dev) as caller:
-            self.prepare(B * N, t_max, Tv, cfg_on, tokens_per_frame, block_size=self.cfg.block_size, delays=delays)
-            self._set_lengths(lengths, tv_lengths)
-            self._set_prompt_lengths(P)
-            self.set_condition(feats, replicate=N)
-            Tp = self.start_sequence(prompt)       # per-clip prompt lengths: the shortest — where the loop starts sampling
-            start = Tp + 1 + (self.delays[0] if self.delays else 0)  # Pattern.get_first_step_with_timesteps(Tp), sorted delays
-            plan = None if P is None else clip_params.prompt_schedule(P, self.delays[0] if self.delays else 0, self.S, self.rows == 2 * self.batch)
-            sp = self._sampling(use_sampling, temp, top_k, top_p, cfg_scale, seed, clip_base)
-            if noise is not None:
-                noise = noise.to(self.dev, torch.float32).contiguous()
-                assert noise.shape == (self.S - start, B * N * K, self.cfg.d_codebook), noise.shape
-            if return_logprobs:
-                self.logprobs.zero_()         # slots the sampler does not fill (prompt, special) read 0
-            self.dec.logprobs = L.ptr(self.logprobs) if return_logprobs else 0
-            if return_relevance:
-                if self.logprobs_cond is None:
-                    self.logprobs_cond, self.logprobs_null = torch.zeros_like(self.logprobs), torch.zeros_like(self.logprobs)
-                else:
-                    self.logprobs_cond.zero_()
-                    self.logprobs_null.zero_()
-            self.dec_ext.logprobs_cond = L.ptr(self.logprobs_cond) if return_relevance else 0
-            self.dec_ext.logprobs_null = L.ptr(self.logprobs_null) if return_relevance else 0
+            Tp, start, plan, sp, noise = self._begin_sequence(feats, N, t_max, lengths, tv_lengths, P, cfg_on, tokens_per_frame, delays, prompt,
+                                                              use_sampling, temp, top_k, top_p, cfg_scale, seed, clip_base, noise,
+                                                              return_logprobs, return_relevance)
             self.run(start - 1, self.S - start, sp, noise, use_graph, plan)
             out = self.revert().to(torch.int64)
             extra = self._sequence_logprobs(Tp) if return_logprobs else None
@@ -805,6 +794,37 @@ class DecoderEngine:
             for t in (extra or {}).values():
                 t.record_stream(caller)
         return (out, extra) if (return_logprobs or return_relevance) else out
+
+    def _begin_sequence(self, feats, N, t_max, lengths, tv_lengths, P, cfg_on, tokens_per_frame, delays, prompt, use_sampling, temp, top_k,
+                        top_p, cfg_scale, seed, clip_base, noise, return_logprobs, return_relevance):
+        """Everything of a ``generate_codes`` call in front of its loop, on resolved arguments, enqueued on the current stream: the
+        prepared shape, the per-clip arrays, the condition, the pattern sequence, the sampling struct, and the log-probability /
+        relevance buffers -> (Tp, first sampled step, prompt plan or None, vaura_sampling, noise on the device or None)."""
+        B, Tv, _ = feats.shape
+        K = self.cfg.num_codebooks
+        self.prepare(B * N, t_max, Tv, cfg_on, tokens_per_frame, block_size=self.cfg.block_size, delays=delays)
+        self._set_lengths(lengths, tv_lengths)
+        self._set_prompt_lengths(P)
+        self.set_condition(feats, replicate=N)
+        Tp = self.start_sequence(prompt)       # per-clip prompt lengths: the shortest — where the loop starts sampling
+        start = Tp + 1 + (self.delays[0] if self.delays else 0)  # Pattern.get_first_step_with_timesteps(Tp), sorted delays
+        plan = None if P is None else clip_params.prompt_schedule(P, self.delays[0] if self.delays else 0, self.S, self.rows == 2 * self.batch)
+        sp = self._sampling(use_sampling, temp, top_k, top_p, cfg_scale, seed, clip_base)
+        if noise is not None:
+            noise = noise.to(self.dev, torch.float32).contiguous()
+            assert noise.shape == (self.S - start, B * N * K, self.cfg.d_codebook), noise.shape
+        if return_logprobs:
+            self.logprobs.zero_()         # slots the sampler does not fill (prompt, special) read 0
+        self.dec.logprobs = L.ptr(self.logprobs) if return_logprobs else 0
+        if return_relevance:
+            if self.logprobs_cond is None:
+                self.logprobs_cond, self.logprobs_null = torch.zeros_like(self.logprobs), torch.zeros_like(self.logprobs)
+            else:
+                self.logprobs_cond.zero_()
+                self.logprobs_null.zero_()
+        self.dec_ext.logprobs_cond = L.ptr(self.logprobs_cond) if return_relevance else 0
+        self.dec_ext.logprobs_null = L.ptr(self.logprobs_null) if return_relevance else 0
+        return Tp, start, plan, sp, noise
 
     def _revert_f32(self, buf: torch.Tensor) -> torch.Tensor:
         """fp32 values in the layout of seq -> (batch, K, T), 0 where the sequence holds no frame."""
@@ -876,6 +896,157 @@ class DecoderEngine:
             codes = self._twin().generate_codes(feats, max_new_tokens, **kw)
             self._range_twin.check_status()
         return codes
+
+    # ------------------------------------------------------------------ the loop in pieces: frames leave while it still runs
+    def generate_codes_stream(self, feats: torch.Tensor, max_new_tokens, *, block_frames: int = 16, halo: int = 0, **kw):
+        """``generate_codes`` as a generator that says which frames are final while the loop is still running.  The arguments are checked
+        here, at call time; the returned generator runs the call.  ``kw``: the keywords of ``generate_codes``.
+        The S - start sampled steps run in pieces (``clip_params.stream_schedule``): a piece ends where ``block_frames`` more frames of
+        the longest clip have become RELEASABLE — final in every codebook (frame t of codebook q is written at step t + 1 + d_q and never
+        changes afterwards) and at least ``halo`` frames in front of the last final one (the codec's ``decode_halo``: the samples of a
+        frame depend on that many frames either side; 0 for a caller that wants tokens only); a complete clip releases everything.  The
+        captured single step is the one ``generate_codes`` replays, and the position lives in the device state word, so the tokens are
+        its tokens whatever the piece lengths (they need not be multiples of the loop's graph grouping).
+        Each ``next()`` yields [(lo_b, hi_b) per clip]: the frames of ``self.seq`` (and of ``self.logprobs`` / ``logprobs_cond`` /
+        ``logprobs_null`` when asked for — ``stream_frames`` reads them) that became releasable; the generator's return value
+        (``StopIteration.value``) is what ``generate_codes`` returns.  At most two pieces are in flight: piece k + 1 is enqueued
+        before the host waits for the event behind piece k, so the device does not idle on the host; whatever the consumer enqueues for
+        block k (a codec window) therefore runs behind piece k + 1 on the stream.  Closing the generator early leaves at most those two
+        pieces running; the engine is reusable at once (the next call is ordered behind them on the stream).
+        Status word: behind every piece the state words are copied to pinned host memory in front of the piece's event — no extra
+        stall.  Bit 1 (non-finite logits) or 2 (a hand-off gave up) BEFORE anything was yielded: what ``generate_codes_checked`` does —
+        the separate launches, or the exact-fp32 twin, with the same noise — and the stream continues from there.  AFTER a block has
+        gone out the audio cannot be taken back: ``VauraHipError`` with ``.status`` and ``.frames_emitted`` (per clip).
+        Refused here, before the engine is touched: ``num_candidates`` > 1 (the winner is known only at the end), more than one distinct
+        ``prompt_lengths`` value (that path interleaves prefill passes with the loop; not served by this version), ``near_tie="rerun"``
+        (it decides at the end of the call), and a ``block_frames`` that is no positive int."""
+        clip_params.check_block_frames(block_frames)
+        if kw.get("num_candidates", 1) != 1:
+            raise L.VauraHipError("streaming takes num_candidates = 1: the winning candidate is known only at the end of the call")
+        if self.near_tie == "rerun":
+            raise L.VauraHipError('streaming is refused on an engine with near_tie="rerun": the re-run is decided at the end of the call, '
+                                  'after audio has left (use "report" or "off")')
+        if isinstance(halo, bool) or not isinstance(halo, int) or halo < 0:
+            raise L.VauraHipError(f"halo must be a non-negative number of frames, got {halo!r}")
+        B, Tv, _ = feats.shape
+        prompt, prompt_lengths = kw.get("prompt"), kw.get("prompt_lengths")
+        clip_params.check_lengths(B, **{n: kw[n] for n in clip_params.NAMES if n in kw})
+        t_max, lengths, tv_lengths = clip_params.resolve_lengths(B, max_new_tokens, kw.get("video_lengths"), Tv,
+                                                                 0 if (prompt is None or prompt_lengths is not None) else int(prompt.shape[-1]))
+        P = clip_params.resolve_prompt_lengths(B, prompt_lengths, None if prompt is None else int(prompt.shape[-1]), t_max, lengths)
+        if P is not None and len(set(P)) > 1:
+            raise L.VauraHipError(f"streaming takes one prompt length for the call, got prompt_lengths {P}: distinct lengths interleave "
+                                  "prefill passes with the loop and are not served by this version")
+        Tp = 0 if prompt is None else (P[0] if P is not None else int(prompt.shape[-1]))
+        if Tp >= (min(lengths) if lengths else t_max):
+            raise L.VauraHipError(f"the audio prompt ({Tp} frames) must be shorter than max_new_tokens ({lengths or t_max})")
+        return self._codes_stream(feats, max_new_tokens, int(block_frames), int(halo), (t_max, lengths, tv_lengths, P), dict(kw))
+
+    def _stream_status(self, words: torch.Tensor) -> int:
+        """Bits 1 | 2 of the state words a piece left in pinned memory (its event has been waited for), with what ``prepare`` carried over."""
+        return (int(words[4]) | self._carried_status) & 3
+
+    def stream_frames(self, buf: torch.Tensor, ranges, fill) -> torch.Tensor:
+        """The frames [lo_b, hi_b) of every clip out of ``buf`` in the layout of seq (tokens, or fp32 per-token values) -> (batch, K, max
+        count), clip b's frames left-aligned with ``fill`` behind them: what the revert of the finished call holds there, bit for bit
+        (frame t of codebook q sits at step t + 1 + d_q), read while the loop may still be filling later steps."""
+        K = self.cfg.num_codebooks
+        n = max(hi - lo for lo, hi in ranges)
+        d = torch.tensor(self.delays if self.delays is not None else list(range(K)), device=self.dev)
+        lo = torch.tensor([r[0] for r in ranges], device=self.dev)
+        cnt = torch.tensor([r[1] - r[0] for r in ranges], device=self.dev)
+        t = torch.arange(n, device=self.dev)
+        step = (lo[:, None, None] + 1 + d[None, :, None] + t[None, None, :]).clamp(max=self.S - 1)
+        got = torch.gather(buf, 2, step)
+        return torch.where(t[None, None, :] < cnt[:, None, None], got, torch.full_like(got, fill))
+
+    @torch.no_grad()
+    def _codes_stream(self, feats, max_new_tokens, block_frames, halo, resolved, kw):
+        t_max, lengths, tv_lengths, P = resolved
+        self.stream_engine = self              # whose seq / per-token buffers the yielded ranges refer to (the twin after a range fallback)
+        prompt = kw.get("prompt")
+        if P is not None:                      # one length after all: the scalar call with that prompt
+            prompt = prompt[..., :P[0]] if P[0] else None
+        g = lambda name, default: kw.get(name, default)
+        cfg_scale, want_lp, want_rel, use_graph = g("cfg_scale", 1.0), bool(g("return_logprobs", False)), bool(g("return_relevance", False)), g("use_graph", True)
+        cfg_on = clip_params.any_cfg(cfg_scale)
+        B = feats.shape[0]
+        if want_rel and not cfg_on:            # as generate_codes: relevance reads the null rows
+            cfg_on = True
+            if not clip_params.is_per_clip(cfg_scale):
+                cfg_scale = [float(clip_params._scalar(cfg_scale))] * B
+        self._fc = None
+        if getattr(self, "_stream_pinned", None) is None:      # the state words of the two pieces in flight, on the host
+            self._stream_pinned = [torch.zeros(8, dtype=torch.int32).pin_memory() for _ in range(2)]
+        pinned = self._stream_pinned
+        with off_null_stream(self.dev):
+            Tp, start, _, sp, noise = self._begin_sequence(
+                feats, 1, t_max, lengths, tv_lengths, None, cfg_on, g("tokens_per_frame", 7), g("delays", None), prompt, g("use_sampling", False),
+                g("temp", 1.0), g("top_k", 0), g("top_p", 0.0), cfg_scale, g("seed", 0), g("clip_base", 0), g("noise", None), want_lp, want_rel)
+            pieces = clip_params.stream_schedule(self.T, self.lengths, start, self.delays, halo, block_frames, self.cfg.num_codebooks)
+            if self.lengths is None:           # one length: every clip of the batch has the one range
+                pieces = [(n, r * self.batch) for n, r in pieces]
+            assert sum(n for n, _ in pieces) == self.S - start
+            events = []
+
+            def enqueue(k):                    # piece k, its state words behind it, its event behind those
+                self.run(start - 1 if k == 0 else 0, pieces[k][0], sp, noise, use_graph)
+                pinned[k % 2].copy_(self.state, non_blocking=True)
+                events.append(torch.cuda.Event())
+                events[-1].record(torch.cuda.current_stream(self.dev))
+            enqueue(0)
+        emitted = [0] * self.batch
+        for k, (_, ranges) in enumerate(pieces):
+            if k + 1 < len(pieces):
+                with off_null_stream(self.dev):
+                    enqueue(k + 1)
+            events[k].synchronize()
+            st = self._stream_status(pinned[k % 2])
+            if st:
+                events[-1].synchronize()       # nothing of this call is running any more
+                self.state[4:5].zero_()
+                self._carried_status = 0
+                err = self._status_error(st)
+                if any(emitted):
+                    err.frames_emitted = list(emitted)
+                    err.args = (f"{err.args[0]} — after frames {emitted} of the clips had been streamed out: they cannot be taken back",)
+                    raise err
+                return (yield from self._stream_fallback(err, st, feats, max_new_tokens, block_frames, halo, resolved, kw))
+            if any(hi > lo for lo, hi in ranges):
+                yield list(ranges)
+                emitted = [hi for _, hi in ranges]
+        with off_null_stream(self.dev) as caller:
+            out = self.revert().to(torch.int64)
+            extra = self._sequence_logprobs(Tp) if want_lp else None
+            if want_rel:
+                extra = dict(extra or {}, **self._sequence_relevance(Tp))
+        if caller is not None:
+            out.record_stream(caller)
+            for t in (extra or {}).values():
+                t.record_stream(caller)
+        self.check_status()                    # the near-tie counters of the call (informational); the loop's bits were read piece by piece
+        return (out, extra) if (want_lp or want_rel) else out
+
+    def _stream_fallback(self, err, st, feats, max_new_tokens, block_frames, halo, resolved, kw):
+        """A dirty status word before any frame has left: ``generate_codes_checked``'s two ways out, as a stream."""
+        import warnings
+        if (st & 2) and self.one_launch_mlp:
+            warnings.warn("vaura_amd: the one-launch MLP's in-launch hand-off timed out (GPU shared?); this engine now uses the "
+                          "separate launches (slower by 5-7 %, same results)")
+            self.one_launch_mlp = False
+            self.handoff_fallbacks += 1
+            if self.dec is not None:
+                self.dec.ws_sync = 0
+            self._free_graph()
+            return (yield from self._codes_stream(feats, max_new_tokens, block_frames, halo, resolved, kw))
+        if st != 1 or self.wdtype == "f32" or self._twin_sd is None:       # nothing wider to fall back to
+            raise err
+        if self.range_fallbacks == 0:
+            warnings.warn("vaura_amd: an activation left the fp16-plane range (non-finite logits at the sampler); this call is re-run "
+                          "on the exact-fp32 twin engine (1.5 x slower, ~2.7 GB more)")
+        self.range_fallbacks += 1
+        self.stream_engine = self._twin()      # whoever reads seq / the per-token buffers of the running stream reads the twin's
+        return (yield from self.stream_engine._codes_stream(feats, max_new_tokens, block_frames, halo, resolved, kw))
 
     # ------------------------------------------------------------------ the reference host's call pattern, with a cache
     def forward_cached(self, idx: torch.Tensor, feats: torch.Tensor, tokens_per_frame: int = 7) -> torch.Tensor:
@@ -1312,14 +1483,21 @@ class CodecEngine:
             wav.record_stream(caller)
         return wav
 
-    def _window_call(self, ci: torch.Tensor, n, starts, counts) -> torch.Tensor:
+    def _window_call(self, ci: torch.Tensor, n, starts, counts, seq_delays=False) -> torch.Tensor:
         """vaura_dac_decode_window on int32 codes of this device, inside the engine's stream context; grows the workspaces to the
-        window's size when they are smaller."""
+        window's size when they are smaller.  ``seq_delays`` not False: ``ci`` is the decode loop's pattern sequence (B, K, S) under
+        those delays (None: 0 .. K - 1) and the call is vaura_dac_decode_window_seq."""
         B, K, T = ci.shape
         host = [(C.c_int32 * B)(*v) for v in (n, starts, counts)]
-        need = self.lib.vaura_dac_decode_window_workspace_elems(C.byref(self.c), B, *host)
+        if seq_delays is False:
+            name, src = "vaura_dac_decode_window", (B, T)
+            need = self.lib.vaura_dac_decode_window_workspace_elems(C.byref(self.c), B, *host)
+        else:
+            name, src = "vaura_dac_decode_window_seq", (B, K, T, None if seq_delays is None else L.delays_host(seq_delays))
+            need = self.lib.vaura_dac_decode_window_seq_workspace_elems(C.byref(self.c), *src, *host)
         if need == 0:
-            raise L.VauraHipError(f"decode_window: windows {list(zip(starts, counts))} of clips of {n} frames are beyond what one pass can index")
+            raise L.VauraHipError(f"{name[10:]}: windows {list(zip(starts, counts))} of clips of {n} frames are beyond what one pass can index"
+                                  + ("" if seq_delays is False else f", or not inside a pattern sequence of {T} steps"))
         if self._ws_key is None or self._ws_key < need:
             self._ws = [torch.empty(need, dtype=torch.float32, device=self.dev) for _ in range(4)]
             for i in range(4):
@@ -1328,8 +1506,7 @@ class CodecEngine:
             self._ws_key = need
         N = max(counts)
         wav = torch.empty(B, 1, N * self.cfg.hop, dtype=torch.float32, device=self.dev)
-        L.check(self.lib.vaura_dac_decode_window(C.byref(self.c), L.ptr(ci), B, T, *host, L.ptr(wav), N, L.current_stream(self.dev)),
-                "vaura_dac_decode_window")
+        L.check(getattr(self.lib, name)(C.byref(self.c), L.ptr(ci), *src, *host, L.ptr(wav), N, L.current_stream(self.dev)), name)
         return wav
 
     @staticmethod
@@ -1365,6 +1542,30 @@ class CodecEngine:
             ci = codes.to(self.dev, torch.int32).contiguous()
             wav = self._window_call(ci, n, s, c)
             self._codes_keepalive = ci
+        if caller is not None:
+            wav.record_stream(caller)
+        return wav
+
+    @torch.no_grad()
+    def decode_window_seq(self, seq: torch.Tensor, starts, counts, lengths=None, delays: Optional[Sequence[int]] = None) -> torch.Tensor:
+        """``decode_window`` straight from the decode loop's pattern sequence: seq (B, K, S) int32 on this device (``DecoderEngine.seq``)
+        under the codebook ``delays`` (None: 0 .. K - 1) holds T = S - 1 - max(d) frames per clip, frame t of codebook q at step
+        t + 1 + d_q -> wav (B, 1, max(counts)*hop), bit for bit ``decode_window`` on the reverted codes (vaura_dac_decode_window_seq:
+        the pack gathers from the sequence, everything else is that call).  No revert launch, no copy of ``seq``; it may be called
+        while the sequence is still being filled, for windows whose frames AND halo are final (``clip_params.releasable_frames``):
+        ``lengths`` stays every clip's whole length."""
+        if seq.dim() != 3 or seq.dtype != torch.int32 or not seq.is_cuda or not seq.is_contiguous():
+            raise L.VauraHipError(f"seq must be a contiguous (B, K, S) int32 tensor on {self.dev}, got {tuple(seq.shape)} {seq.dtype} on {seq.device}")
+        B, K, S = seq.shape
+        d = None if delays is None else L.check_delays(delays, K)
+        T = S - 1 - (K - 1 if d is None else max(d))
+        if K < self.cfg.n_codebooks or T < 1:
+            raise L.VauraHipError(f"a pattern sequence of {K} codebooks and {S} steps under the delays {list(d) if d else list(range(K))} holds "
+                                  f"no frame of the codec's {self.cfg.n_codebooks} codebooks")
+        n = [T] * B if lengths is None else _clip_lengths("lengths", lengths, B, T)
+        s, c = self._window_args(B, n, starts, counts)
+        with off_null_stream(self.dev) as caller:
+            wav = self._window_call(seq, n, s, c, seq_delays=d)
         if caller is not None:
             wav.record_stream(caller)
         return wav

@@ -152,7 +152,7 @@ def _decode_halo(model) -> int:
 def generate_long_stream(model, frames: torch.Tensor, duration: float, *, emit_chunks: int = 1, stride: float = 0.64,
                          model_max_duration: Optional[float] = None, vfps: float = 25, frame_step: int = 1, clip_indices=None,
                          use_sampling: bool = True, temp: float = 1.0, top_k: int = 128, top_p: float = 0.0, cfg_scale: float = 1.0,
-                         return_relevance: bool = False, video_lengths=None):
+                         return_relevance: bool = False, video_lengths=None, block_frames: Optional[int] = None):
     """``generate_long`` as a generator of finished audio: the arguments are checked here, the returned iterator runs the chunks.
     After every ``emit_chunks`` chunks, and after the last one, it yields {"audio" (B, 1, n * hop), "start_frame", "frames" (n),
     "sampled_indices" (B, K, n), "final"} — with ``return_relevance`` also "relevance", "logprob_cond", "logprob_null" (B, K, n) — for
@@ -161,10 +161,24 @@ def generate_long_stream(model, frames: torch.Tensor, duration: float, *, emit_c
     After chunk c the tokens of the frames [0, N_c), N_c = offset_c + max_gen_len_c, are final: later chunks are prompted with them
     and generate behind them.  The samples of a frame depend on ``codec_clips.decode_halo`` = H frames either side, so the frames
     [emitted, N_c - H) are decoded then (``DacModelWrapper.decode_window``: one codec pass over that window and its halo), and on
-    the last chunk everything up to N_c.  A single-chunk duration yields once, what ``generate_long`` returns."""
+    the last chunk everything up to N_c.  A single-chunk duration yields once, what ``generate_long`` returns.
+    ``block_frames``: None — the generator above; an int — audio also leaves INSIDE a chunk: every chunk runs through
+    ``VAURAModel.generate_stream(decode=False)`` (``DecoderEngine.generate_codes_stream``: the decode loop in pieces that end where
+    ``block_frames`` more frames are final), and by the same rule on global frame indices — chunk offset + local frame; a chunk's prompt
+    frames were final before it began — the frames [emitted, known - H) are decoded as soon as ``known`` frames are final, and at a
+    chunk's end what the generator above releases there.  The first block of a call is then due after about ``block_frames`` + max(delay)
+    decode steps and one small codec window instead of after the first whole chunk; a single-chunk duration streams as well.  The blocks
+    still tile the clip and concatenate to the bits of ``generate_long``.  ``emit_chunks`` must stay 1 with it."""
     _check_emit_chunks(emit_chunks)
+    if block_frames is not None:
+        from .clip_params import check_block_frames
+        check_block_frames(block_frames)
+        if emit_chunks != 1:
+            raise _error(f"block_frames releases audio inside every chunk: emit_chunks must stay 1, got {emit_chunks}")
     sched, kw = _long_setup(model, frames, duration, stride, model_max_duration, vfps, clip_indices, use_sampling, temp, top_k, top_p,
                             cfg_scale, video_lengths, "generate_long_stream")
+    if block_frames is not None:
+        return _long_stream_blocks(model, frames, sched, int(COMPRESSION_MODEL_FRAME_RATE * stride), frame_step, kw, return_relevance, block_frames)
     return _long_stream(model, frames, sched, int(COMPRESSION_MODEL_FRAME_RATE * stride), frame_step, kw, return_relevance, emit_chunks)
 
 
@@ -199,6 +213,50 @@ def _long_stream(model, frames, sched, stride_tokens, frame_step, kw, return_rel
         held = [tok[..., keep - held_from:]]
         held_rel = {k: [rel[k][..., keep - held_from:]] if return_relevance else [] for k in REL}
         held_from = keep
+
+
+@torch.no_grad()
+def _long_stream_blocks(model, frames, sched, stride_tokens, frame_step, kw, return_relevance, block_frames):
+    """``_long_stream`` with audio leaving inside the chunks (``generate_long_stream(block_frames=...)``)."""
+    H, K = _decode_halo(model), model.num_codebooks
+    skw = {k: v for k, v in kw.items() if k not in ("return_sampled_indices", "remove_prompts")}      # generate_stream has neither
+    held, held_rel, held_from, emitted = [], {k: [] for k in REL}, 0, 0     # final and not yet dropped: frames [held_from, known)
+    prompt_tokens = None
+    for c, ch in enumerate(sched):
+        final = c + 1 == len(sched)
+        if ch["positions"] is None:                                         # single chunk (:309-324)
+            selected = frames[:, :, ::frame_step, ...] if frame_step != 1 else frames
+        else:
+            lo, hi = ch["positions"]
+            selected = frames[:, torch.arange(lo, hi, device=frames.device) % frames.shape[1], ...]
+            if frame_step != 1:
+                selected = selected[:, :, :, ::frame_step, ...]
+        P, T, off = (0 if prompt_tokens is None else int(prompt_tokens.shape[-1])), ch["max_gen_len"], ch["offset"]
+        chunk = []
+        for blk in model.generate_stream(frames=selected, audio=prompt_tokens, max_new_tokens=T, block_frames=block_frames, decode=False,
+                                         return_relevance=return_relevance, **skw):
+            lo, hi = blk["start_frame"], blk["start_frame"] + blk["frames"]
+            chunk.append(blk["sampled_indices"])
+            if hi > P:                                                      # frames this chunk GENERATED: the others are held already
+                held.append(blk["sampled_indices"][..., max(lo, P) - lo:])
+                for k in (REL if return_relevance else ()):
+                    held_rel[k].append(blk[k][..., max(lo, P) - lo:])
+            known = off + max(hi, P)
+            upto = (known if final else known - H) if hi == T else known - H
+            if upto <= emitted:
+                continue
+            tok = torch.cat(held, dim=-1)                                   # frames [held_from, known): held_from <= emitted - H
+            rel = {k: torch.cat(v, dim=-1) for k, v in held_rel.items()} if return_relevance else {}
+            B, n = tok.shape[0], upto - emitted
+            audio = model.audio_encoder.decode_window(tok[..., :K, :], [emitted - held_from] * B, [n] * B)
+            yield {"audio": audio, "start_frame": emitted, "frames": n, "sampled_indices": tok[..., emitted - held_from:upto - held_from],
+                   "final": final and hi == T, **{k: v[..., emitted - held_from:upto - held_from] for k, v in rel.items()}}
+            emitted = upto
+            keep = max(held_from, emitted - H)                              # the halo in front of the next block stays
+            held = [tok[..., keep - held_from:]]
+            held_rel = {k: [rel[k][..., keep - held_from:]] if return_relevance else [] for k in REL}
+            held_from = keep
+        prompt_tokens = torch.cat(chunk, dim=-1)[:, :, stride_tokens:]
 
 
 # ---- one duration per clip: the schedules of the clips merged into one call per chunk index
@@ -455,7 +513,9 @@ def generate_long_clips_stream(model, frames: torch.Tensor, durations, segments=
     with ``return_relevance`` the three (B, K, max(frames)) values as well: clip b's frames [start_frames[b], start_frames[b] +
     frames[b]), left-aligned, with zeros (the special id in "sampled_indices") behind them.  Per clip the blocks tile [0, L_b) without
     overlap and concatenate to the bits of ``generate_long_clips``.  Clip b's last chunk releases everything up to L_b; a clip whose
-    schedule has ended has frames[b] = 0 from then on (ONE ``decode_window`` pass per block, over the clips that have something)."""
+    schedule has ended has frames[b] = 0 from then on (ONE ``decode_window`` pass per block, over the clips that have something).
+    Audio leaves at chunk ends only: this generator has no ``block_frames`` (``generate_long_stream`` releases inside a chunk; the
+    merged per-clip schedules stay as they are)."""
     _check_emit_chunks(emit_chunks)
     d, seg, single, kw, sample_kw = _clips_setup(model, frames, durations, segments, stride, model_max_duration, vfps, frame_step, clip_indices,
                                                  use_sampling, temp, top_k, top_p, cfg_scale, video_lengths, num_candidates,

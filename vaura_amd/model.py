@@ -614,6 +614,132 @@ class VAURAModel(nn.Module):
         return {"generated_audio": generated_audio, "s_attn_weights": None, "mha_attn_weights": None,
                 "sampled_indices": out_codes if return_sampled_indices else None, **extra}
 
+    # ------------------------------------------------------------------ generate, audio out while the decode loop still runs
+    def generate_stream(self, frames=None, audio: Union[torch.Tensor, None] = None, clip_indices=None, max_new_tokens: int = 512,
+                        use_sampling: bool = True, temp: float = 1.0, top_k: int = 256, top_p: float = 0.0,
+                        prompt_is_encoded: bool = False, cfg_scale: float = 1.0, return_logprobs: bool = False, num_candidates: int = 1,
+                        return_relevance: bool = False, video_lengths=None, prompt_lengths=None, audio_lengths=None,
+                        block_frames: int = 16, decode: bool = True):
+        """``generate`` as a generator of finished audio: the arguments are checked here, the returned iterator runs the call and yields
+        {"audio" (B, 1, n * hop), "start_frame", "frames" (n), "sampled_indices" (B, K, n), "final"} for the frames [start_frame,
+        start_frame + n) as soon as they can no longer change — about ``block_frames`` + ``decode_halo`` + max(delay) decode steps
+        into the call for the first block instead of after all of them (``DecoderEngine.generate_codes_stream``: the loop runs in
+        pieces; every block is ONE codec pass over its window and halo, gathered straight from the loop's pattern sequence,
+        ``decode_window_seq``).  With per-clip lengths (``max_new_tokens`` as a sequence, ``video_lengths``) the dicts carry
+        "start_frames" and "frames" as lists and clip b's samples / tokens are left-aligned with zeros / the special id behind them — the
+        keys of the long-form streams.  ``return_logprobs`` adds "logprobs", ``return_relevance`` "relevance", "logprob_cond" and
+        "logprob_null" (B, K, n): the per-token values travel with their frames (the sequence means exist only at the end of a call:
+        ``generate``).  A block in which no clip releases a frame is skipped; a clip of at most ``decode_halo`` frames appears once.
+        Contract: per clip the blocks tile [0, T_b) without overlap, and concatenated they are bit for bit ``generate``'s
+        "generated_audio" (over the clip's own samples), "sampled_indices" and per-token values of the same call (``noise_mode=
+        "philox"`` or greedy; ``"torch_cpu"`` draws the same tensor when the generator state is the same).  Prompt frames are part of
+        the stream (there is no ``remove_prompts``).
+        ``decode=False``: tokens only — no "audio" entry, no codec pass, and a frame is released as soon as its TOKENS are final (no halo
+        held back): for a caller that decodes on frames of its own (``longform.generate_long_stream`` on global frame indices).
+        Status rule: a non-finite logit or a hand-off give-up detected BEFORE the first block re-runs the call the way ``generate``
+        does (separate launches / exact-fp32 twin) and streams from there; AFTER a block has left, ``VauraHipError`` with ``.status``
+        and ``.frames_emitted`` — audio that has been handed out cannot be taken back.
+        Refused here, before the engine is touched: ``num_candidates`` > 1 (the winner is known only at the end), more than one distinct
+        prompt length (``prompt_lengths`` / ``audio_lengths``), a sampler with ``near_tie="rerun"`` (it decides at the end), and a
+        ``block_frames`` that is no positive int.  Closing the iterator early leaves at most two pieces of the loop running and the
+        model usable at once."""
+        assert not self.training, "do not use generation in training mode"
+        clip_params.check_block_frames(block_frames)
+        if isinstance(num_candidates, bool) or not isinstance(num_candidates, int) or num_candidates != 1:
+            raise L.VauraHipError(f"generate_stream takes num_candidates = 1 (got {num_candidates!r}): the winning candidate is known only "
+                                  "at the end of the call")
+        if getattr(self.sampler, "near_tie", None) == "rerun":
+            raise L.VauraHipError('generate_stream is refused with near_tie="rerun": the re-run is decided at the end of the call, after '
+                                  'audio has left (use "report" or "off")')
+        B0 = frames.shape[0] if hasattr(frames, "shape") else None
+        clip_params.check_lengths(B0, use_sampling=use_sampling, temp=temp, top_k=top_k, top_p=top_p, cfg_scale=cfg_scale)
+        per_clip_prompt = prompt_lengths is not None or audio_lengths is not None
+        t_max, lengths, _ = clip_params.resolve_lengths(
+            B0, max_new_tokens, video_lengths, None,
+            int(audio.shape[-1]) if (audio is not None and prompt_is_encoded and not per_clip_prompt) else 0)
+        self._check_prompt_lengths(frames, audio, prompt_is_encoded, prompt_lengths, audio_lengths, t_max, lengths)
+        P = None
+        if prompt_lengths is not None:
+            P = clip_params._int_list("prompt_lengths", prompt_lengths)
+        elif audio_lengths is not None:        # the frames the encoder gives each clip: known from the samples alone
+            from .codec_clips import clip_layout
+            n = clip_params._int_list("audio_lengths", audio_lengths) if clip_params.is_per_clip(audio_lengths) else [audio_lengths]
+            P = list(clip_layout(n, self.audio_encoder.cfg, "encode").frames)
+        if P is not None and len(set(P)) > 1:
+            raise L.VauraHipError(f"generate_stream takes one prompt length for the call, got {P} frames per clip: distinct lengths are not "
+                                  "served by this version (generate() serves them)")
+        delays = self._pattern_delays(t_max)
+        if delays != list(range(self.num_codebooks)) and t_max + max(delays) + 1 > self.sampler.block_size:
+            raise L.VauraHipError(f"{t_max} timesteps under the delays {delays} need {t_max + max(delays) + 1} sequence steps; block_size is "
+                                  f"{self.sampler.block_size}")
+        return self._generate_stream(frames, audio, clip_indices, t_max, lengths, delays, use_sampling, temp, top_k, top_p, prompt_is_encoded,
+                                     cfg_scale, bool(return_logprobs), bool(return_relevance), video_lengths, prompt_lengths, audio_lengths,
+                                     block_frames, bool(decode))
+
+    @torch.no_grad()
+    def _generate_stream(self, frames, audio, clip_indices, t_max, lengths, delays, use_sampling, temp, top_k, top_p, prompt_is_encoded,
+                         cfg_scale, want_lp, want_rel, video_lengths, prompt_lengths, audio_lengths, block_frames, decode):
+        K = self.num_codebooks
+        P = None
+        if audio is not None and not prompt_is_encoded:      # as generate_tokens (vaura_model.py:463-469)
+            if audio_lengths is not None:
+                audio, P = self._encode_clips(audio, audio_lengths)
+            else:
+                audio = self.audio_encoder.encode(audio)
+        if prompt_lengths is not None:
+            P = clip_params._int_list("prompt_lengths", prompt_lengths)
+        vis = self._handle_visual_conditioning(frames, clip_indices)
+        if vis is None:
+            raise NotImplementedError("unconditional generation: the llama sampler always needs video features "
+                                      "(the reference raises here too, llama.py:474-476)")
+        B = vis.shape[0]
+        Tp = 0 if audio is None else int(audio.shape[-1])
+        if P is not None:
+            Tp = clip_params.resolve_prompt_lengths(B, P, Tp, t_max, lengths)[0]      # one length for the call (checked at call time)
+        ragged = lengths is not None or video_lengths is not None
+        tv_lengths = None
+        if ragged:
+            _, lengths, tv_lengths = clip_params.resolve_lengths(B, lengths if lengths is not None else t_max, video_lengths, int(vis.shape[1]), Tp)
+        if self.sampler.audio_tokens_per_video_frame is None:
+            raise L.VauraHipError("sampler.audio_tokens_per_video_frame must be set (scripts/generate.py:216 sets 7)")
+        use_cfg = clip_params.any_cfg(cfg_scale) and self.sampler.__class__.__name__ == "Transformer"
+        start = Tp + 1 + delays[0]
+        S = t_max + max(delays) + 1
+        greedy = not clip_params.any_sampled(use_sampling, temp)
+        noise = None if greedy else self._exp_noise(S - start, B * K, self.sampler.d_codebook)
+        codec = self.audio_encoder
+        first = self.sampler.engine()
+        blocks = first.generate_codes_stream(
+            vis.float(), lengths if lengths is not None else t_max, block_frames=block_frames, halo=_codec_halo(codec) if decode else 0,
+            prompt=audio[..., :Tp] if Tp else None, use_sampling=use_sampling, temp=temp, top_k=top_k, top_p=top_p,
+            cfg_scale=cfg_scale if use_cfg else 1.0, noise=noise, seed=self.seed, clip_base=self.clip_base,
+            tokens_per_frame=self.sampler.audio_tokens_per_video_frame, delays=None if delays == list(range(K)) else delays,
+            **(dict(return_logprobs=True) if want_lp else {}), **(dict(return_relevance=True) if want_rel else {}),
+            **(dict(video_lengths=tv_lengths) if tv_lengths is not None else {}))
+        T_b = lengths if lengths is not None else [t_max] * B
+        for ranges in blocks:
+            eng = first.stream_engine          # the engine whose sequence these ranges refer to (the exact-fp32 twin after a range fallback)
+            starts, counts = [lo for lo, _ in ranges], [hi - lo for lo, hi in ranges]
+            with off_null_stream(eng.dev) as caller:
+                blk = {"sampled_indices": eng.stream_frames(eng.seq, ranges, self.special_token_id).to(torch.int64)}
+                if decode:
+                    blk["audio"] = codec.decode_window_seq(eng.seq, starts, counts, lengths, eng.delays)
+                if want_lp:
+                    blk["logprobs"] = eng.stream_frames(eng.logprobs, ranges, 0.0)
+                if want_rel:
+                    blk["logprob_cond"] = eng.stream_frames(eng.logprobs_cond, ranges, 0.0)
+                    blk["logprob_null"] = eng.stream_frames(eng.logprobs_null, ranges, 0.0)
+                    blk["relevance"] = blk["logprob_cond"] - blk["logprob_null"]
+            if caller is not None:
+                for t in blk.values():
+                    t.record_stream(caller)
+            if ragged:
+                blk.update(start_frames=starts, frames=counts)
+            else:
+                blk.update(start_frame=starts[0], frames=counts[0])
+            blk["final"] = all(hi == n for (_, hi), n in zip(ranges, T_b))
+            yield blk
+
     # ------------------------------------------------------------------ one step, reference signature
     @torch.no_grad()
     def _sample_next_token(self, sequence: torch.Tensor, condition: torch.Tensor, use_sampling: bool = False,
@@ -770,3 +896,10 @@ class VAURAModel(nn.Module):
         _, _, loss, loss_per_cb = self._shared_step(batch, batch_idx)
         self._shared_log("test", loss, loss_per_cb)
         return loss
+
+
+
+def _codec_halo(codec) -> int:
+    """Frames of context either side that the samples of one frame depend on, for the codec plugin in use (``codec_clips.decode_halo``)."""
+    from .codec_clips import decode_halo
+    return decode_halo(codec.cfg)
