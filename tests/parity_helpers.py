@@ -104,7 +104,7 @@ def assert_tokens_or_recorded_near_tie(report, golden, storage, what, tok, ref, 
 
 
 # ------------------------------------------------------------------------------------------------------------------
-# Activation formats of the codec kernels (csrc/dac.hip store_act_octet / store_pair4), decoded on the CPU for the op-level
+# Activation formats of the codec kernels (csrc/conv_kernels.h store_act_octet / store_pair4), decoded on the CPU for the op-level
 # parity tests of tests/test_gpu_codec_stages.py.  tests/test_codec_stage_host.py checks these decoders themselves.
 
 def pair_planes_to_f64(buf: torch.Tensor, rows: int, Cc: int):

@@ -1,6 +1,6 @@
 """CPU checks (-m "not gpu") of the format decoders the codec stage parity tests read kernel outputs with
 (tests/parity_helpers.py: pair planes, block-scaled e4m3), against vaura_amd.quant and a host restatement of the layouts written
-element by element from csrc/dac.hip::store_act_octet — a decoder bug must not pass as a kernel bug, nor hide one — and of what the
+element by element from csrc/conv_kernels.h::store_act_octet — a decoder bug must not pass as a kernel bug, nor hide one — and of what the
 op-level entry points refuse without a GPU."""
 import torch
 

@@ -68,7 +68,7 @@ def test_plugin_feeds_the_generate_path(golden):
 
 
 def test_lds_dma_linear_layers_are_bit_identical_to_the_register_staged_ones(avclip_engine):
-    """csrc/dac.hip linear_dma_kernel (operands by LDS-DMA in whole cache lines, fragments read early, per-wave epilogue; the default
+    """csrc/linear.hip linear_dma_kernel (operands by LDS-DMA in whole cache lines, fragments read early, per-wave epilogue; the default
     since round 5) against round 4's register-staged linear_pair_kernel (second debug word, bit 5), its late-read instance (bit 6)
     and round 4's tile order (bits 12..15 = 15: no column panels): the same products summed in the same order, so the features must be
     BIT-identical — 2 clips x 2 segments, a ragged last row tile (1 x 1: 1569 rows = 12 tiles + 33) and 12 segments (147 row tiles)."""

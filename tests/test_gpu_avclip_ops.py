@@ -1,4 +1,4 @@
-"""Extractor kernels (csrc/vit.hip and the linear-layer launcher of csrc/dac.hip) op by op against torch fp64 on the CPU
+"""Extractor kernels (csrc/vit.hip and the linear-layer launcher of csrc/linear.hip) op by op against torch fp64 on the CPU
 (tests/vit_reference.py), through the op-level entry points that call the SAME static launchers as vaura_avclip_forward.
 
 Conventions of every case
@@ -441,6 +441,8 @@ LINEAR_KINDS = {
     "proj 768x768 + res in place": (768, 768, 1, 0, "inplace", False),
     "fc1 768x3072 gelu planes": (768, 3072, 1, 0, None, True),
     "fc2 3072x768 + res": (3072, 768, 1, 0, "separate", False),
+    # Cout % 192 != 0: no shape of the extractor, the launcher's way onto the codec's 128 x 96 conv tile (129 rows: a full tile and a ragged one)
+    "conv tile 96x96 oshift 1 + res": (96, 96, 2, 1, "separate", False),
 }
 
 

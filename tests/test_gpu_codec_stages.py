@@ -408,6 +408,107 @@ def test_large_instances_against_fp64(Cc, precision):
     check_act(cls + " unit", precision, outs["one"][1], rows, Cc, raw32, ref1, res.double(), alpha_next)
 
 
+# ------------------------------------------------------------------------------- b2. the 256-row gate, on both sides of it
+# launch_conv takes the 256-row instances when g256 x column tiles x B x phases >= 384, g256 = ceil(jcount / 256); launch_conv_unit
+# the one-launch unit (C = 96) when ceil(L / 256) x B >= 384.  (name, Cin, Cout, k, dilation, stride, precisions, ((Lin, product), ..))
+_PAIR3 = ("f16pair", "f16pair_w8", "f16")
+_GATE_CASES = [("one-tap", 96, 192, 1, 1, 1, _PAIR3, ((24576, 384), (24320, 380))),             # 96 x 2 tiles x 2 clips / 95 x 2 x 2
+               ("64-columns", 64, 128, 1, 1, 1, _PAIR3[:2], ((24576, 384), (24320, 380))),      # the f16 mode has no 64-column 256-row instance
+               ("transposed", 96, 96, 4, 1, 2, _PAIR3, ((24320, 384), (24319, 380)))]           # jcount = Lin + 1: 96 / 95 x 1 x 2 x 2 phases
+_GATE_PARAMS = [(c[:6], p, Lin, prod) for c in _GATE_CASES for p in c[6] for Lin, prod in c[7]]
+
+
+@functools.lru_cache(maxsize=None)
+def _gate_problem(case, Lin):
+    _, cin, cout, k, _, stride = case
+    g = torch.Generator().manual_seed(8000 + cin + cout + k + stride)
+    x = two_clips((2, Lin, cin), g)
+    w = torch.randn(cin, cout, k, generator=g) / (cin * 2) ** 0.5 if stride > 1 else torch.randn(cout, cin, k, generator=g) / (cin * k) ** 0.5
+    return x, w, torch.randn(cout, generator=g) * 0.1, torch.rand(cout, generator=g) * 3 + 0.05
+
+
+@pytest.mark.parametrize("case,precision,Lin,product", _GATE_PARAMS, ids=lambda v: str(v) if isinstance(v, (str, int)) else v[0])
+def test_256_row_gate_of_the_conv_launcher(case, precision, Lin, product):
+    """vaura_dac_conv_ex at the two lengths either side of the gate, per instance family (96-column tiles, 64-column tiles, the two phases
+    of a transposed conv with its jcount = Lin + 1) and pair precision: vaura_debug_counter(0) reads 1 at a product of exactly 384 and 0
+    at 380, and 0 under debug flag bit 20 (128-row instances only); the activated output of the two runs is equal byte for byte and the
+    guards are intact.  No fp64 reference: the smaller shapes above carry the numeric bars.  The largest tensor of a case is 37.7 MB."""
+    from vaura_amd.engine import CodecConvOp, codec_act_bytes
+    name, cin, cout, k, dil, stride = case
+    ph_count, tiles = (stride if stride > 1 else 1), cout // (96 if cout % 96 == 0 else 64)
+    jcount = Lin + 1 if stride > 1 else Lin
+    assert -(-jcount // 256) * tiles * 2 * ph_count == product       # the case is what its comment says
+    x, w, bias, alpha = _gate_problem(case, Lin)
+    flat = (lambda t: t.permute(1, 0, 2).reshape(cout, -1)) if stride > 1 else (lambda t: t.reshape(cout, -1))
+    unflat = (lambda t: t.reshape(cout, cin, k).permute(1, 0, 2)) if stride > 1 else (lambda t: t.reshape(cout, cin, k))
+    _, we = effective_operands(precision, x[:, :1], w, flat, unflat)
+    rows = 2 * Lin * stride
+    lib = L.lib()
+    op = CodecConvOp(we, bias, dil, stride, precision, DEV)
+    xd, ad = x.to(DEV), alpha.to(DEV)
+    outs, counts = [], []
+    try:
+        for flags in (0, 1 << 20):
+            lib.vaura_set_debug_flags(flags)
+            lib.vaura_debug_counter(0)
+            act_g = Guarded(codec_act_bytes(precision, rows, cout), guard_bytes(cout * 4))
+            op.ex(xd, alpha=ad, out_act=act_g.view())
+            torch.cuda.synchronize()
+            counts.append(int(lib.vaura_debug_counter(0)))
+            outs.append(act_g.host())
+            del act_g
+    finally:
+        lib.vaura_set_debug_flags(0)
+    print(f"[codec-stage] gate {name} {precision} Lin={Lin}: product {product}, 256-row launches {counts[0]} (flag bit 20: {counts[1]})")
+    assert counts == [1 if product >= 384 else 0, 0], counts
+    assert bool((outs[0].view(torch.int16) != -1).all()), "fp16 plane entries were never written"
+    assert torch.equal(outs[0], outs[1]), "256-row / 128-row selection changed the output"
+
+
+@pytest.mark.parametrize("precision", _PAIR3)
+@pytest.mark.parametrize("Ln,product", [(49152, 384), (48896, 382)])
+def test_256_row_gate_of_the_unit_launcher(Ln, product, precision):
+    """vaura_dac_unit, C = 96, 7 taps of dilation 9, B = 2, either side of ceil(L / 256) x B >= 384: vaura_debug_counter(1) reads 1 at 384
+    (one launch) and 0 at 382, where the unit runs as two convs whose own products are 382 as well (counter 0 == 0).  Under debug flag
+    bit 21 (always two launches) the output is equal byte for byte; at 384 those two convs take the 256-row instances (counter 0 == 2)."""
+    from vaura_amd.engine import CodecUnitOp, codec_act_bytes
+    Cc, dil = 96, 9
+    assert -(-Ln // 256) * 2 == product
+    g = torch.Generator().manual_seed(8800)
+    res = two_clips((2, Ln, Cc), g, scale=1.0)
+    x = two_clips((2, Ln, Cc), g)
+    w7, w1 = torch.randn(Cc, Cc, 7, generator=g) / (Cc * 7) ** 0.5, torch.randn(Cc, Cc, 1, generator=g) / Cc ** 0.5
+    b7, b1 = torch.randn(Cc, generator=g) * 0.1, torch.randn(Cc, generator=g) * 0.1
+    am, an = (torch.rand(Cc, generator=g) * 3 + 0.05).to(DEV), (torch.rand(Cc, generator=g) * 3 + 0.05).to(DEV)
+    flat = lambda t: t.reshape(Cc, -1)
+    _, w7e = effective_operands(precision, x[:, :1], w7, flat, lambda t: t.reshape(Cc, Cc, 7))
+    _, w1e = effective_operands(precision, x[:, :1], w1, flat, lambda t: t.reshape(Cc, Cc, 1))
+    rows, gb = 2 * Ln, guard_bytes(Cc * 4)
+    lib = L.lib()
+    unit = CodecUnitOp(w7e, b7, dil, w1e, b1, precision, DEV)
+    xd, resd = x.to(DEV), res.to(DEV)
+    mid = torch.empty(codec_act_bytes(precision, rows, Cc), dtype=torch.uint8, device=DEV)
+    outs, seen = [], []
+    try:
+        for flags in (0, 1 << 21):
+            lib.vaura_set_debug_flags(flags)
+            lib.vaura_debug_counter(0)
+            lib.vaura_debug_counter(1)
+            act_g = Guarded(codec_act_bytes(precision, rows, Cc), gb)
+            fused = unit(xd, resd, am, an, None, act_g.view(), mid)
+            torch.cuda.synchronize()
+            seen.append((fused, int(lib.vaura_debug_counter(1)), int(lib.vaura_debug_counter(0))))
+            outs.append(act_g.host())
+            del act_g
+    finally:
+        lib.vaura_set_debug_flags(0)
+    print(f"[codec-stage] gate unit {precision} L={Ln}: product {product}, (one launch, counter 1, counter 0) = {seen[0]}; flag bit 21: {seen[1]}")
+    big = product >= 384
+    assert seen == [(big, 1 if big else 0, 0), (False, 0, 2 if big else 0)], seen
+    assert bool((outs[0].view(torch.int16) != -1).all()), "fp16 plane entries were never written"
+    assert torch.equal(outs[0], outs[1]), "one launch != two launches"
+
+
 # ----------------------------------------------------------------------------------------------------------------- c. from_codes
 @pytest.mark.parametrize("pairs", [False, True], ids=["fp32", "pairs"])
 @pytest.mark.parametrize("K,dim,latent", [(9, 8, 1024), (4, 5, 1024)])

@@ -508,7 +508,7 @@ _CONV_SHAPES = [  # (Cin, Cout, k, dilation, stride)  — the decoder's layer ge
 
 def test_snake_sine():
     """The codec's activation (vaura_snake = the snake_f of every conv epilogue; Snake1d of descript-audio-codec 1.0.0, restated in
-    oracle/dac_oracle.py::snake) with its own sin^2 (csrc/dac.hip::snake_sin2) against fp64 and against the oracle's fp32 form:
+    oracle/dac_oracle.py::snake) with its own sin^2 (csrc/conv_kernels.h::snake_sin2) against fp64 and against the oracle's fp32 form:
     ordinary activations, the whole fp16-plane range (|x| up to 6e4, alpha up to 8), tiny alpha, exact zeros and multiples of pi/2.
     The bar is absolute on sin^2 in [0, 1]: 4e-7 (the fp32 torch.sin squared is itself 1.3e-7 from fp64), i.e. error / alpha-inverse."""
     from oracle import dac_oracle

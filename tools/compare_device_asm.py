@@ -13,7 +13,12 @@ same-set : not identical, but equal after splitting at the function symbols and 
 subset   : for a change that ADDS kernels to the unit: every function of OLD and every metadata record of OLD's kernels is in NEW,
            equal byte for byte under the same masking; the functions NEW adds are listed.  The padding the assembler puts behind the
            LAST function of the unit (.p2alignl / .fill of s_code_end words) is taken off first: it follows whichever function the
-           unit ends with, not that function's code.  Anything else exits 1."""
+           unit ends with, not that function's code.  Anything else exits 1.
+
+    python tools/compare_device_asm.py --moved OLD.s NEW1.s [NEW2.s ..] [--gone SYMBOL ..]
+moved    : for a change that SPLITS a unit: the functions and metadata records of OLD are those of the NEW units taken together, equal
+           byte for byte under the same masking, every one in exactly one NEW unit, none added, and the ones missing are exactly the
+           SYMBOLs expected to disappear.  Anything else exits 1."""
 import hashlib
 import re
 import sys
@@ -48,6 +53,24 @@ def subset(a, b):
     return missing, added, sha("".join(fa + ra))
 
 
+def symbol(piece):
+    # of a function or of a kernel's metadata record; None for what stands in front of a unit's first function / record
+    m = re.search(r"\t\.(?:protected|globl|weak)\t(\S+)|^    \.name: +(\S+)", piece, re.M)
+    return m and (m.group(1) or m.group(2))
+
+
+def moved(old, news):
+    def split(t):
+        p = [PAD.sub("", x) for x in pieces(t)]
+        i = p.index("<metadata>")
+        return [x for x in p[:i - 1] + p[i + 1:-1] if symbol(x)]      # functions and records, without trailer and tail
+    po, pn = split(old), [x for t in news for x in split(t)]
+    twice = sorted({symbol(x) for x in pn if pn.count(x) > 1})
+    lost = sorted({symbol(x) for x in po if x not in pn})
+    added = sorted({symbol(x) for x in pn if x not in po})
+    return twice, lost, added, len(po), len(pn), sha("".join(sorted(pn)))
+
+
 def sha(s):
     return hashlib.sha256(s.encode()).hexdigest()
 
@@ -61,6 +84,19 @@ if __name__ == "__main__":
         print("subset   ", h, f"(every old function and metadata record is in the new unit; {len(added)} functions added)")
         for name in added:
             print("  added:", name)
+        sys.exit(0)
+    if sys.argv[1] == "--moved":
+        args = sys.argv[2:]
+        files, gone = (args[:args.index("--gone")], args[args.index("--gone") + 1:]) if "--gone" in args else (args, [])
+        twice, lost, added, n_old, n_new, h = moved(load(files[0]), [load(f) for f in files[1:]])
+        # a symbol that differs shows up as lost AND added; one that disappeared as lost only
+        if twice or added or lost != sorted(gone):
+            print("DIFFERENT", f"in two units: {twice}; differ or added: {added}; not in the new units: {lost}; expected to go: {sorted(gone)}")
+            sys.exit(1)
+        print("moved    ", h, f"({n_new} of the old unit's {n_old} functions and metadata records, each in one of {len(files) - 1} units; "
+              f"{len(lost)} symbols gone, none added)")
+        for name in lost:
+            print("  gone:", name)
         sys.exit(0)
     a, b = load(sys.argv[1]), load(sys.argv[2])
     if a == b:

@@ -12,10 +12,6 @@
 #   graph-steps                         decode steps per graph launch (debug flag bits 24..27): 1 / 4 / 12, alternating
 #   chains                              the batch as 2 / 4 independent decode chains on separate streams against one chain of all rows
 #   plain-stores                        write-through output stores (product) against ordinary ones (build --plain-stores), alternating
-#   codec-abl [tags ..]                 codec decode (mfma_driver codec 8, precisions 1 and 4) on experiment builds `python -m vaura_amd.csrc.build --tag T -DVA_CONV_ABL=n`
-#                                       (timing ablations of conv_pair_kernel, csrc/dac.hip) next to the product library
-#   linear-abl [tags ..]                extractor forward (mfma_driver avclip 8) on experiment builds `python -m vaura_amd.csrc.build --tag T -DVA_LIN_ABL=n`
-#                                       (timing ablations of linear_pair_kernel, csrc/dac.hip) next to the product library
 #   codec-pmc                           SQ wait / issue / LDS counters of the codec kernels (mfma_driver codec 8 under rocprofv3 --pmc, four passes), per kernel
 #   codec-layers                        per-dispatch durations of one codec decode (kernel trace of mfma_driver codec 8)
 #   avclip-stats                        per-kernel averages of one extractor forward (mfma_driver avclip 8 under rocprofv3 --stats)
@@ -79,16 +75,6 @@ plain-stores)
   for w in h2 h1; do for rep in 1 2; do for lib in libvaura_hip.so libvaura_hip_plain.so; do
     timeout 300 /tmp/pmc_driver vaura_amd/csrc/$lib --time 5 --weights $w > $OUT/t.log 2>&1; echo "$w $lib: $(grep 'loop of 228' $OUT/t.log | cut -c1-110)"
   done; done; done | tee $OUT/plain_stores.log ;;
-codec-abl)
-  mfma_driver
-  for rep in 1 2; do for t in "" ${@:-_cabl1 _cabl2 _cabl4 _cabl3}; do for pr in 1 4; do
-    echo "lib$t precision $pr: $(timeout 120 /tmp/mfma_driver vaura_amd/csrc/libvaura_hip$t.so codec 8 $pr 5 2>&1 | grep -o 'last decode [0-9.]* ms')" | tee -a $OUT/codec_abl.log
-  done; done; done ;;
-linear-abl)
-  mfma_driver
-  for rep in 1 2; do for t in "" ${@:-_labl1 _labl2 _labl4 _labl8}; do
-    echo "lib$t: $(timeout 120 /tmp/mfma_driver vaura_amd/csrc/libvaura_hip$t.so avclip 8 1 3 2>&1 | grep -o 'last forward [0-9.]* ms')" | tee -a $OUT/linear_abl.log
-  done; done ;;
 codec-pmc)
   mfma_driver; cd /tmp && export TMPDIR=/tmp
   i=0
@@ -184,5 +170,5 @@ suite)
   { timeout 600 python3 tools/time_codec.py; timeout 600 python3 tools/time_avclip.py; timeout 900 python3 tools/time_sliding_window.py
     timeout 900 python3 tools/bench_longform.py; } 2>&1 | tee $OUT/secondary.log ;;
 *)
-  sed -n 2,26p $0; exit 1 ;;
+  sed -n 2,22p $0; exit 1 ;;
 esac

@@ -3,68 +3,23 @@
 //   arithmetic         descript-audio-codec==1.0.0 (un-vendored; conda_env_cuda12.1.yaml:298):
 //                      Decoder / DecoderBlock / ResidualUnit / Snake1d / WNConv1d / WNConvTranspose1d
 //
-// Bound: MFMA.  Every Conv1d / ConvTranspose1d is one "multi-tap GEMM"
+// Every Conv1d / ConvTranspose1d is one "multi-tap GEMM"
 //     out[j*ostride + oshift][co] = bias[co] + sum_t sum_ci  act[j + off_t][ci] * W_t[co][ci]
 // over channels-last activations (B, L, C): a k=7 dilated conv has 7 taps (off_t = (t-3)*dil), a k=1
 // conv one, and a stride-r transposed conv (k = 2r, pad = r/2) is r independent 2-tap problems, one
-// per output phase (off = {0, -1}, ostride = r, oshift = phase - r/2).  Products run on
-// v_mfma_f32_16x16x4_f32 (exact fp32), with A = weight tile (rows = co) and B = activation tile
-// (cols = position), so each lane ends up holding 4 consecutive channels of one position and the
-// epilogue is float4: + bias, + residual, raw store, and Snake with the NEXT layer's alpha — the
-// activation is evaluated once per element by its producer, never per tap by the consumer.
-#include "common.h"
-#include <algorithm>
-#include <vector>
-
-#define BM 128   // positions per workgroup tile
-#define BN 96    // output channels per workgroup tile (divides 1536, 768, 384, 192, 96)
-#define BK 32    // input channels per k-tile
-
-struct ConvArgs {
-  const float* in;     // (B, Lin, Cin) already activated
-  const float* w;      // [phase][tap][Cout][Cin]
-  const float* bias;   // (Cout)
-  const float* res;    // optional (B, Lout, Cout)
-  const float* alpha;  // (Cout) Snake alpha for out_act
-  float* out_raw;      // optional (B, Lout, Cout)
-  float* out_act;      // optional (B, Lout, Cout)
-  int Lin, Lout, Cin, Cout, NT;
-  int off_base, off_step;   // off_t = off_base + t*off_step
-  int ostride, oshift0;     // output row = j*ostride + oshift0 + phase
-  int jcount;               // j in [0, jcount)
-};
-
-// mx8 activation buffers keep their scale words behind the e4m3 bytes of the whole (B, L, C) tensor
-__host__ __device__ __forceinline__ size_t mx8_scale_offset(size_t elems) { return (elems + 15) & ~(size_t)15; }
-
-#ifndef VA_CONV_ABL
-#define VA_CONV_ABL 0      // timing ablations, see conv_pair_kernel
-#endif
-// sin^2(x) for Snake.  The library sinf (Payne-Hanek path, sign / quadrant selects; inlined at every call site) was 2.3 ms of the 11.2 ms
-// decode of 8 clips (profiles/r04_codec_ablations.txt: the activation, not the matrix pipe, was the codec's largest single cost).  Only
-// the SQUARE is needed, and sin^2 has period pi and no sign: n = rint(x / pi), r = x - n pi in two fused steps (pi = PI_A + PI_B; the
-// fma keeps n PI_A exact), sin r on [-pi/2, pi/2] as r + r t p(t), t = r^2 (degree-4 fit of sin(r)/r - 1: 7e-9 before rounding).
-// Measured against fp64 over |x| <= 3e4: max abs error 2.5e-7, rms 3.7e-8 — the fp32 sinf squared gives 1.2e-7 / 2.9e-8; both are
-// rounding noise of the final multiply.  The error stays at that level while n is exact (|x| < ~1e6; the fp16-plane activation
-// format itself ends at 65504) and grows smoothly beyond.  tests/test_gpu_ops.py::test_snake_sine.
-__device__ __forceinline__ float snake_sin2(float x) {
-  const float n = __builtin_rintf(x * 0.318309886183790672f);
-  float r = fmaf(-n, 3.14159274101257324f, x);
-  r = fmaf(-n, -8.74227765734758577e-8f, r);
-  const float t = r * r;
-  float p = fmaf(t, 2.6051661734527443e-06f, -0.00019809046352747828f);
-  p = fmaf(t, p, 0.008333050645887852f);
-  p = fmaf(t, p, -0.16666658222675323f);
-  const float sn = fmaf(r, t * p, r);
-  return sn * sn;
-}
-// inv = 1.0f / (al + 1e-9f): one IEEE division per CHANNEL where a thread keeps its channels (the tile store, the fused unit), not per element
-__device__ __forceinline__ float snake_fi(float v, float al, float inv) {
-  if constexpr ((VA_CONV_ABL & 64) != 0) { const float sn = sinf(al * v); return v + inv * (sn * sn); }      // round 3's sine, for the A/B
-  const float s2 = (VA_CONV_ABL & 16) ? al * v : snake_sin2(al * v);
-  return v + inv * s2;
-}
-__device__ __forceinline__ float snake_f(float v, float al) { return snake_fi(v, al, 1.0f / (al + 1e-9f)); }
+// per output phase (off = {0, -1}, ostride = r, oshift = phase - r/2; va_conv_geometry).  A = weight tile
+// (rows = co), B = activation tile (cols = position): a lane ends up holding 4 consecutive channels of
+// one position, and the epilogue adds bias and residual, stores the raw row and applies Snake with the
+// NEXT layer's alpha — the activation is evaluated once per element by its producer, never per tap by
+// the consumer.
+// Arithmetic: (hi, lo) fp16 pairs on v_mfma_f32_16x16x32_f16 (conv_pair_kernel, conv_unit_kernel; precisions 1, 2, 4),
+// block-scaled e4m3 (conv_mx8_kernel, precision 3); conv_mfma_kernel (exact fp32, precision 0) is the yardstick.
+// Bound: the activation streams, not the matrix pipe (profiles/r04_codec_ablations.txt).
+// This file: the four conv kernels and the codec's small kernels, their launchers, the decode and encode passes and
+// the extern "C" surface.  conv_kernels.h: argument structs, the epilogue helpers and the tile store (shared with
+// linear.hip, the extractor's linear layers).  dac_clips.h: packing clips / windows into one sequence.
+#include "conv_kernels.h"
+#include "dac_clips.h"
 
 __global__ __launch_bounds__(256) void conv_mfma_kernel(ConvArgs a) {
   __shared__ f32x4 Ws[2][BK / 4][BN + 1];
@@ -164,179 +119,6 @@ __global__ __launch_bounds__(256) void conv_mfma_kernel(ConvArgs a) {
   }
 }
 
-// ---------------------------------------------------------------------------------------------
-// fp16-pair variant (codec precision 1): activations and weights travel as (hi, lo) fp16 pairs,
-//   x = fp16(x) + fp16(x - fp16(x))   (22 significand bits; |rel err| <= 2^-22),
-// and a product is three v_mfma_f32_16x16x32_f16: lo_w*hi_x + hi_w*lo_x + hi_w*hi_x (fp16 x fp16 products
-// are exact in fp32; the dropped lo*lo term is < 2^-22).  5.3x fewer matrix-pipe cycles than the exact
-// fp32 MFMA above at an error far inside the codec's 1e-4 RMS budget (measured).
-// "pair layout" of an activated (L x C) buffer / a weight tap (Cout x Cin): per row, C/8 octets of
-// [plane hi|lo][8] halves = 32 B -> one row of 32 channels is still one 128-B line, same bytes as fp32.
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-
-struct ConvPArgs {
-  const uint16_t* in;    // pair layout (B, Lin, Cin)
-  const uint16_t* w;     // pair layout [phase][tap][Cout][Cin]
-  const float* bias;
-  const float* res;      // fp32 (B, Lout, Cout)
-  const float* alpha;
-  float* out_raw;        // fp32
-  uint16_t* out_act;     // pair layout, Snake applied
-  int Lin, Lout, Cin, Cout, NT;
-  int off_base, off_step, ostride, oshift0, jcount;
-  int act;               // activation written to out_act: 0 Snake(alpha) (the codec), 1 exact GELU, 2 identity (row f2's linears)
-  // --- block-scaled fp8 ("mx8") activations (codec precision 3, conv_mx8_kernel below)
-  int act_fmt;           // out_act format: 0 (hi, lo) fp16 pairs, 1 mx8 = e4m3 bytes (B, Lout, Cout) + out_scale
-  uint8_t* out_scale;    // (B, Lout, ceil(Cout/128)) words of four E8M0 bytes: one power-of-two scale per 32 channels of a row
-  const uint32_t* in_scale;   // the same for an mx8 input
-  const float* wscale;   // (Cout) power-of-two scale of each output channel's e4m3 weights
-  // --- residual unit in one launch (conv_pair_kernel<.., FUSE = true>): this conv (7 taps) -> Snake(alpha_mid) -> 1 x 1 conv (w2, bias2)
-  //     -> + res -> out_raw / Snake(alpha) -> out_act.  bias / alpha_mid belong to the first conv, res / out_* / alpha to the second.
-  const uint16_t* w2;    // pair layout [Cout][Cout]
-  const float* bias2;
-  const float* alpha_mid;
-};
-
-// Exact (erf) GELU, 0.5 x (1 + erf(x / sqrt 2)), as row f2's fc1 epilogue applies it 1.85 G times per 8 clips.  The library erff (inlined,
-// branches) cost 1.2 ms of the extractor's 43.7 (experiment build -DVA_CONV_ABL=128).  Own form: with t = |x| / sqrt 2,
-//   1 + erf(x / sqrt 2) = erfc(t) for x < 0, 2 - erfc(t) for x >= 0,   erfc(t) = exp(-t^2) k P(k),  k = 1 / (1 + 0.35 t),
-// P a degree-8 fit of erfcx(t) / k on t in [0, 6] (3e-8 relative before rounding).  No cancellation on the negative side (the library
-// form rounds 1 + erf to 0 below x = -5.5).  Against fp64: |error| <= 1.3e-7 max(1, |x|) — the rounding of the final products; the fp32
-// 0.5 x (1 + erff(..)) form is at 4.5e-7.  tests/test_gpu_avclip.py keeps the features within 1e-4 of the reference's (observed 5e-6).
-__device__ __forceinline__ float gelu_erf_f(float x) {
-  if constexpr ((VA_CONV_ABL & 128) != 0) return 0.5f * x * (1.0f + x * 0.70710678118654752440f);      // timing ablation: no erf
-  if constexpr ((VA_CONV_ABL & 256) != 0) return 0.5f * x * (1.0f + erff(x * 0.70710678118654752440f)); // round 3's form, for the A/B
-  const float t = fabsf(x) * 0.70710678118654752440f;
-  const float k = __builtin_amdgcn_rcpf(fmaf(t, 0.35f, 1.0f));
-  float p = 0.06797561794519424f;
-  p = fmaf(p, k, -0.4044332206249237f);
-  p = fmaf(p, k, 0.8392713069915771f);
-  p = fmaf(p, k, -0.7225478887557983f);
-  p = fmaf(p, k, 0.6403822898864746f);
-  p = fmaf(p, k, -0.046077974140644073f);
-  p = fmaf(p, k, 0.23748238384723663f);
-  p = fmaf(p, k, 0.1900186985731125f);
-  p = fmaf(p, k, 0.1979287713766098f);
-  const float e = (k * p) * __builtin_amdgcn_exp2f(-(t * t) * 1.4426950408889634f);
-  return (0.5f * x) * (x < 0.f ? e : 2.0f - e);
-}
-
-__device__ __forceinline__ void store_pair4(uint16_t* base, size_t row, int c0, int C, const f32x4 v) {
-  // 4 consecutive channels c0..c0+3 (c0 % 4 == 0) of one row
-  _Float16 h[4], l[4];
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const float x = v[i];
-    h[i] = (_Float16)x;
-    l[i] = (_Float16)(x - (float)h[i]);
-  }
-  typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
-  f16x4* p = reinterpret_cast<f16x4*>(base + ((row * (size_t)(C >> 3) + (size_t)(c0 >> 3)) * 2) * 8 + (c0 & 7));
-  p[0] = f16x4{h[0], h[1], h[2], h[3]};
-  p[2] = f16x4{l[0], l[1], l[2], l[3]};   // +8 halves = the lo plane of the same octet
-}
-
-// E8M0 byte of the smallest power of two s with amax <= 448 * s (448 = 1.75 * 2^8 = the e4m3 maximum); same rule as
-// vaura_amd/quant.py::fp8_row_scales, clamped to the bytes whose reciprocal is a normal float.
-__device__ __forceinline__ int mx8_scale_byte(float amax) {
-  const uint32_t bits = __builtin_bit_cast(uint32_t, amax);
-  const int ea = (int)((bits >> 23) & 0xffu);
-  const int e8 = ea - ((bits & 0x7fffffu) <= 0x600000u ? 8 : 7);
-  return e8 < 1 ? 1 : (e8 > 253 ? 253 : e8);
-}
-
-// One octet (8 consecutive channels co..co+7 of global row `grow`) of an activated tensor in the next layer's input format.
-// mx8: the 4 threads of a 32-channel block must be consecutive lanes, all active.
-__device__ __forceinline__ void store_act_octet(void* out_act, uint8_t* out_scale, int fmt, size_t grow, int co, int C,
-                                                const float (&sv)[8]) {
-  if (fmt == 0) {
-    f16x8 hi, lo;
-#pragma unroll
-    for (int r = 0; r < 8; ++r) { hi[r] = (_Float16)sv[r]; lo[r] = (_Float16)(sv[r] - (float)hi[r]); }
-    f16x8* dst = reinterpret_cast<f16x8*>(reinterpret_cast<uint16_t*>(out_act) + ((grow * (size_t)(C >> 3) + (size_t)(co >> 3)) * 2) * 8);
-    dst[0] = hi;
-    dst[1] = lo;
-  } else {
-    float amax = 0.f;
-#pragma unroll
-    for (int r = 0; r < 8; ++r) amax = fmaxf(amax, fabsf(sv[r]));
-    amax = fmaxf(amax, __shfl_xor(amax, 1, 64));
-    amax = fmaxf(amax, __shfl_xor(amax, 2, 64));
-    const int e8 = mx8_scale_byte(amax);
-    const float inv = __builtin_bit_cast(float, (uint32_t)(254 - e8) << 23);
-    int q0 = 0, q1 = 0;
-    q0 = __builtin_amdgcn_cvt_pk_fp8_f32(sv[0] * inv, sv[1] * inv, q0, false);
-    q0 = __builtin_amdgcn_cvt_pk_fp8_f32(sv[2] * inv, sv[3] * inv, q0, true);
-    q1 = __builtin_amdgcn_cvt_pk_fp8_f32(sv[4] * inv, sv[5] * inv, q1, false);
-    q1 = __builtin_amdgcn_cvt_pk_fp8_f32(sv[6] * inv, sv[7] * inv, q1, true);
-    typedef int i32x2 __attribute__((ext_vector_type(2)));
-    *reinterpret_cast<i32x2*>(reinterpret_cast<uint8_t*>(out_act) + grow * (size_t)C + co) = i32x2{q0, q1};
-    if (((co >> 3) & 3) == 0) out_scale[(grow * (size_t)((C + 127) >> 7) + (co >> 7)) * 4 + ((co >> 5) & 3)] = (uint8_t)e8;
-  }
-}
-
-// Second half of the conv epilogue, shared by the pair and the mx8 kernel: `stage` holds the BM x BN_ fp32 tile (bias
-// added), every thread owns whole octets of a row: + residual, raw store, activation, and the activated copy in the next
-// layer's input format.
-// Snake for an fp8 consumer: hardware sine (v_sin_f32, argument in revolutions) and reciprocal — absolute error ~1e-6 of a
-// value that is about to be rounded to 3 mantissa bits; the library sinf (argument reduction + polynomial, ~10x the
-// instructions) costs more than the layer's matrix instructions once those run at the fp8 rate.
-__device__ __forceinline__ float snake_fast(float v, float al) {
-  const float sn = __builtin_amdgcn_sinf(__builtin_amdgcn_fractf(al * v * 0.15915494309189535f));   // v_sin_f32's domain is +-256 revolutions
-  return v + __builtin_amdgcn_rcpf(al + 1e-9f) * (sn * sn);
-}
-
-template <int BN_, int SP, bool FAST = false, int ROWS = BM>
-__device__ __forceinline__ void conv_tile_store(const ConvPArgs& a, const float* stage, int b, int ph, int j0, int n0, int tid) {
-  constexpr int OCT = BN_ / 8;              // octets per tile row
-  static_assert(OCT % 4 == 0, "a 32-channel scale block = 4 consecutive threads of one row");
-  // a thread keeps ONE octet column and walks the rows (256 / OCT rows per sweep: 21 for 96 columns — threads 252..255 sit out, a whole
-  // 4-thread scale group — 32 for 64): its eight Snake alphas and their inverses are loaded / divided once, not per element
-  constexpr int RSTEP = 256 / OCT;
-  if (tid >= RSTEP * OCT) return;
-  const int oc = tid % OCT, row0 = tid / OCT;
-  const int co = n0 + oc * 8;
-  const size_t obase = (size_t)b * a.Lout;
-  f32x4 al0 = f32x4{0.f, 0.f, 0.f, 0.f}, al1 = al0, iv0 = al0, iv1 = al0;
-  if (a.out_act && a.act == 0) {
-    al0 = *reinterpret_cast<const f32x4*>(a.alpha + co);
-    al1 = *reinterpret_cast<const f32x4*>(a.alpha + co + 4);
-#pragma unroll
-    for (int r = 0; r < 4; ++r) { iv0[r] = 1.0f / (al0[r] + 1e-9f); iv1[r] = 1.0f / (al1[r] + 1e-9f); }
-  }
-  for (int row = row0; row < ROWS; row += RSTEP) {
-    const int jr = j0 + row;
-    if (jr >= a.jcount) continue;
-    const int orow = jr * a.ostride + a.oshift0 + ph;
-    if (orow < 0 || orow >= a.Lout) continue;
-    const size_t o = (obase + (size_t)orow) * a.Cout + co;
-    f32x4 v0 = *reinterpret_cast<const f32x4*>(stage + row * SP + oc * 8);
-    f32x4 v1 = *reinterpret_cast<const f32x4*>(stage + row * SP + oc * 8 + 4);
-    if (a.res) {
-      v0 = *reinterpret_cast<const f32x4*>(a.res + o) + v0;
-      v1 = *reinterpret_cast<const f32x4*>(a.res + o + 4) + v1;
-    }
-    if (a.out_raw) {
-      *reinterpret_cast<f32x4*>(a.out_raw + o) = v0;
-      *reinterpret_cast<f32x4*>(a.out_raw + o + 4) = v1;
-    }
-    if (a.out_act) {
-      float sv[8];
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        if (FAST && a.act == 0) {
-          sv[r] = snake_fast(v0[r], al0[r]);
-          sv[r + 4] = snake_fast(v1[r], al1[r]);
-        } else {
-          sv[r] = a.act == 0 ? snake_fi(v0[r], al0[r], iv0[r]) : (a.act == 1 ? gelu_erf_f(v0[r]) : v0[r]);
-          sv[r + 4] = a.act == 0 ? snake_fi(v1[r], al1[r], iv1[r]) : (a.act == 1 ? gelu_erf_f(v1[r]) : v1[r]);
-        }
-      }
-      store_act_octet(a.out_act, a.out_scale, a.act_fmt, obase + (size_t)orow, co, a.Cout, sv);
-    }
-  }
-}
-
 // Loop order: input-channel chunk (32 channels) outermost, taps inside.  The activation block of a chunk is staged in
 // LDS ONCE with its halo — rows [j0 + min offset, j0 + BM + max offset), at most BM + 6*9 — and every tap reads it at
 // its own row shift; only the weight tile (BN x 32) is re-staged per tap.  The previous order (one (tap, chunk) tile of
@@ -357,11 +139,6 @@ __device__ __forceinline__ void conv_tile_store(const ConvPArgs& a, const float*
 // faster).  With MJ = 8 one staged weight tile serves twice the rows: 756 KB per 256 x 96 outputs against 1 314.  The activation
 // block (256 + halo rows) then has ONE LDS buffer — it is restaged between two barriers once per chunk, every NT steps — so two
 // workgroups still share a CU (70 KB each); the output tile goes out in two 128-row passes.
-// VA_CONV_ABL: timing ablations for tools/experiment.sh codec-abl (WRONG RESULTS; product build = 0): 1 no weight-tile loads / stores
-// after the first, 2 no matrix instructions, 4 no per-step barrier, 16 Snake without its sine, 64 Snake on the library sinf (round 3)
-#ifndef VA_CONV_ABL
-#define VA_CONV_ABL 0
-#endif
 template <int NI, bool WS, bool XS = false, int MJ = 4, bool FUSE = false>
 __global__ __launch_bounds__(256, 2) void conv_pair_kernel(ConvPArgs a) {
   constexpr int BN_ = 32 * NI;
@@ -470,11 +247,11 @@ __global__ __launch_bounds__(256, 2) void conv_pair_kernel(ConvPArgs a) {
     const int xb = NXB == 2 ? (c & 1) : 0;
     for (int t = 0; t < NT; ++t, ++kt) {
       const int buf = kt & 1;
-      if (kt + 1 < nk && !(VA_CONV_ABL & 1)) load_w(kt + 1);
+      if (kt + 1 < nk) load_w(kt + 1);
       // (256 rows: the next chunk's block is requested at the LAST tap — its registers are free of the step's fragments only there —
       // and stored between two barriers below)
       if (t == (NXB == 2 ? 0 : NT - 1) && c + 1 < kc) load_x(c + 1);
-      const int shift = (VA_CONV_ABL & 8) ? 0 : a.off_base + t * a.off_step - lo_off;
+      const int shift = a.off_base + t * a.off_step - lo_off;
       f16x8 wh[NI], wl[NI];
 #pragma unroll
       for (int i = 0; i < NI; ++i) {
@@ -494,23 +271,17 @@ __global__ __launch_bounds__(256, 2) void conv_pair_kernel(ConvPArgs a) {
         for (int i = 0; i < NI; ++i)
 #pragma unroll
           for (int j = 0; j < JG; ++j) {
-            if constexpr (VA_CONV_ABL & 2) {
-              acc[i][jh + j][0] += (float)wh[i][0] * (float)xh[j][0];
-              if constexpr (!XS) acc[i][jh + j][1] += (float)xl[j][0];
-              if constexpr (!WS && !XS) acc[i][jh + j][2] += (float)wl[i][0];
-              continue;
-            }
             if constexpr (!WS && !XS) acc[i][jh + j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wl[i], xh[j], acc[i][jh + j], 0, 0, 0);
             if constexpr (!XS) acc[i][jh + j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wh[i], xl[j], acc[i][jh + j], 0, 0, 0);
             acc[i][jh + j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wh[i], xh[j], acc[i][jh + j], 0, 0, 0);
           }
       }
-      if (kt + 1 < nk && !(VA_CONV_ABL & 1)) store_w(buf ^ 1);
+      if (kt + 1 < nk) store_w(buf ^ 1);
       if (t == NT - 1 && c + 1 < kc) {
         if constexpr (NXB == 1) __syncthreads();        // every wave is done with the block before it is overwritten
         store_x(NXB == 2 ? (xb ^ 1) : 0);
       }
-      if constexpr (!(VA_CONV_ABL & 4)) __syncthreads();
+      __syncthreads();
     }
   }
 
@@ -1218,6 +989,20 @@ __global__ __launch_bounds__(256) void act_convert_kernel(const float* __restric
 // check those instances against the oracle asserts that they were the ones launched (vaura_debug_counter(0); read-and-clear)
 static long long va_conv256_launches = 0;
 
+// the instance of conv_pair_kernel for NI column tiles per wave (3: 96-column workgroups, 2: 64), the operand planes read (WS, XS) and
+// 128 or 256 (big) rows per workgroup: every stand-alone instance the library has
+typedef void (*ConvPairKernel)(ConvPArgs);
+static ConvPairKernel conv_pair_instance(int ni, bool ws, bool xs, bool big) {
+  if (ni == 3) {
+    if (xs) return big ? conv_pair_kernel<3, true, true, 8> : conv_pair_kernel<3, true, true>;
+    if (ws) return big ? conv_pair_kernel<3, true, false, 8> : conv_pair_kernel<3, true>;
+    return big ? conv_pair_kernel<3, false, false, 8> : conv_pair_kernel<3, false>;
+  }
+  if (xs) return conv_pair_kernel<2, true, true>;
+  if (ws) return big ? conv_pair_kernel<2, true, false, 8> : conv_pair_kernel<2, true>;
+  return big ? conv_pair_kernel<2, false, false, 8> : conv_pair_kernel<2, false>;
+}
+
 static int launch_conv(const vaura_conv& cv, const float* in, const float* res, const float* alpha, float* out_raw,
                        float* out_act, int B, int Lin, int pairs, hipStream_t s) {
   if (!cv.w || !cv.bias || (cv.cin % BK)) return VAURA_ERR_SHAPE;
@@ -1230,16 +1015,9 @@ static int launch_conv(const vaura_conv& cv, const float* in, const float* res, 
     p.Lin = Lin; p.Cin = cv.cin; p.Cout = cv.cout; p.act = 0;
     p.act_fmt = 0; p.out_scale = nullptr; p.in_scale = nullptr; p.wscale = nullptr;
     p.w2 = nullptr; p.bias2 = nullptr; p.alpha_mid = nullptr;
-    int ph = 1;
-    if (cv.stride > 1) {
-      if (cv.stride % 2) return VAURA_ERR_SHAPE;
-      p.NT = 2; p.off_base = 0; p.off_step = -1; p.ostride = cv.stride; p.oshift0 = -(cv.stride / 2);
-      p.Lout = Lin * cv.stride; p.jcount = Lin + 1; ph = cv.stride;
-    } else {
-      p.NT = cv.taps; p.off_base = -((cv.taps - 1) / 2) * cv.dilation; p.off_step = cv.dilation;
-      p.ostride = 1; p.oshift0 = 0; p.Lout = Lin; p.jcount = Lin;
-      if ((cv.taps - 1) * cv.dilation > XHALO) return VAURA_ERR_SHAPE;
-    }
+    if (cv.stride > 1 && (cv.stride % 2)) return VAURA_ERR_SHAPE;
+    if (cv.stride <= 1 && (cv.taps - 1) * cv.dilation > XHALO) return VAURA_ERR_SHAPE;
+    const int ph = va_conv_geometry(p, cv.taps, cv.dilation, cv.stride, Lin);
     if (pairs == 3) {   // mx8 activations out; in as well when the layer's weights are mx8 (everything but conv_in)
       if (out_act) {
         p.act_fmt = 1;
@@ -1254,52 +1032,32 @@ static int launch_conv(const vaura_conv& cv, const float* in, const float* res, 
       }
       pairs = 2;        // conv_in: fp8-valued weights in one fp16 plane, pair input from the quantizer
     }
-    if (pairs == 4) {   // "f16": one matrix instruction per product (hi planes only)
-      const int g256 = (p.jcount + 2 * BM - 1) / (2 * BM);
-      if (cv.cout % BN == 0 && !(va_debug_flags_get() & 0x100000u) && (int64_t)g256 * (cv.cout / BN) * B * ph >= 384) {
-        ++va_conv256_launches;
-        VA_LAUNCH((conv_pair_kernel<3, true, true, 8>), dim3(g256, cv.cout / BN, B * ph), dim3(256), 0, s, p);
-      } else if (cv.cout % BN == 0) VA_LAUNCH((conv_pair_kernel<3, true, true>), dim3((p.jcount + BM - 1) / BM, cv.cout / BN, B * ph), dim3(256), 0, s, p);
-      else VA_LAUNCH((conv_pair_kernel<2, true, true>), dim3((p.jcount + BM - 1) / BM, cv.cout / 64, B * ph), dim3(256), 0, s, p);
-      return 0;
-    }
-    if (cv.cout % BN == 0) {
-      // 256-row workgroups (half the weight bytes through L2 per output) where two per CU still fill the chip; debug flag bit 20: never
-      const int g256 = (p.jcount + 2 * BM - 1) / (2 * BM);
-      const bool big = !(va_debug_flags_get() & 0x100000u) && (int64_t)g256 * (cv.cout / BN) * B * ph >= 384;
-      if (big) {
-        ++va_conv256_launches;
-        if (pairs == 2) VA_LAUNCH((conv_pair_kernel<3, true, false, 8>), dim3(g256, cv.cout / BN, B * ph), dim3(256), 0, s, p);
-        else VA_LAUNCH((conv_pair_kernel<3, false, false, 8>), dim3(g256, cv.cout / BN, B * ph), dim3(256), 0, s, p);
-      } else if (pairs == 2) VA_LAUNCH((conv_pair_kernel<3, true>), dim3((p.jcount + BM - 1) / BM, cv.cout / BN, B * ph), dim3(256), 0, s, p);
-      else VA_LAUNCH((conv_pair_kernel<3, false>), dim3((p.jcount + BM - 1) / BM, cv.cout / BN, B * ph), dim3(256), 0, s, p);
-    } else {
-      const int g256 = (p.jcount + 2 * BM - 1) / (2 * BM);
-      const bool big = !(va_debug_flags_get() & 0x100000u) && (int64_t)g256 * (cv.cout / 64) * B * ph >= 384;
-      if (big) {
-        ++va_conv256_launches;
-        if (pairs == 2) VA_LAUNCH((conv_pair_kernel<2, true, false, 8>), dim3(g256, cv.cout / 64, B * ph), dim3(256), 0, s, p);
-        else VA_LAUNCH((conv_pair_kernel<2, false, false, 8>), dim3(g256, cv.cout / 64, B * ph), dim3(256), 0, s, p);
-      } else if (pairs == 2) VA_LAUNCH((conv_pair_kernel<2, true>), dim3((p.jcount + BM - 1) / BM, cv.cout / 64, B * ph), dim3(256), 0, s, p);
-      else VA_LAUNCH((conv_pair_kernel<2, false>), dim3((p.jcount + BM - 1) / BM, cv.cout / 64, B * ph), dim3(256), 0, s, p);
-    }
+    // pairs 1: three matrix instructions per product; 2: weights in one fp16 plane (WS); 4, "f16": hi planes only (WS and XS).
+    // 96-column tiles where the width allows, else 64.  256-row workgroups (half the weight bytes through L2 per output) where two
+    // per CU still fill the chip; debug flag bit 20: never.  The f16 mode has no 64-column instance of them.
+    const bool xs = pairs == 4, ws = xs || pairs == 2;
+    const int ni = cv.cout % BN == 0 ? 3 : 2, tiles = cv.cout / (32 * ni);
+    const int g256 = (p.jcount + 2 * BM - 1) / (2 * BM);
+    const bool big = (ni == 3 || !xs) && !(va_debug_flags_get() & 0x100000u) && (int64_t)g256 * tiles * B * ph >= 384;
+    if (big) ++va_conv256_launches;
+    VA_LAUNCH(conv_pair_instance(ni, ws, xs, big), dim3(big ? g256 : (p.jcount + BM - 1) / BM, tiles, B * ph), dim3(256), 0, s, p);
     return 0;
   }
   if (cv.cout % BN) return VAURA_ERR_SHAPE;
   ConvArgs a;
   a.in = in; a.w = cv.w; a.bias = cv.bias; a.res = res; a.alpha = alpha; a.out_raw = out_raw; a.out_act = out_act;
   a.Lin = Lin; a.Cin = cv.cin; a.Cout = cv.cout;
-  int phases = 1;
-  if (cv.stride > 1) {   // transposed: k = 2r, pad = r/2
-    if (cv.stride % 2) return VAURA_ERR_SHAPE;
-    a.NT = 2; a.off_base = 0; a.off_step = -1; a.ostride = cv.stride; a.oshift0 = -(cv.stride / 2);
-    a.Lout = Lin * cv.stride; a.jcount = Lin + 1; phases = cv.stride;
-  } else {
-    a.NT = cv.taps; a.off_base = -((cv.taps - 1) / 2) * cv.dilation; a.off_step = cv.dilation;
-    a.ostride = 1; a.oshift0 = 0; a.Lout = Lin; a.jcount = Lin;
-  }
+  if (cv.stride > 1 && (cv.stride % 2)) return VAURA_ERR_SHAPE;
+  const int phases = va_conv_geometry(a, cv.taps, cv.dilation, cv.stride, Lin);
   dim3 grid((a.jcount + BM - 1) / BM, cv.cout / BN, B * phases);
   VA_LAUNCH(conv_mfma_kernel, grid, dim3(256), 0, s, a);
+  return 0;
+}
+
+// the 128 x 96 pair tile for a one-tap problem that linear.hip's own kernels do not take (va_launch_linear_pair): launched from this
+// unit, which holds the kernel's only copy
+int va_launch_conv_pair_tile(const ConvPArgs& p, int B, hipStream_t s) {
+  VA_LAUNCH((conv_pair_kernel<3, false>), dim3((p.jcount + BM - 1) / BM, p.Cout / BN, B), dim3(256), 0, s, p);
   return 0;
 }
 
@@ -1327,10 +1085,9 @@ static int launch_conv_unit(const vaura_conv& c7, const vaura_conv& c1, const fl
   ConvPArgs p;
   p.in = reinterpret_cast<const uint16_t*>(in); p.w = reinterpret_cast<const uint16_t*>(c7.w); p.bias = c7.bias; p.res = res;
   p.alpha = alpha_next; p.out_raw = out_raw; p.out_act = reinterpret_cast<uint16_t*>(out_act);
-  p.Lin = L; p.Lout = L; p.Cin = C; p.Cout = C; p.act = 0;
+  p.Lin = L; p.Cin = C; p.Cout = C; p.act = 0;
   p.act_fmt = 0; p.out_scale = nullptr; p.in_scale = nullptr; p.wscale = nullptr;
-  p.NT = c7.taps; p.off_base = -((c7.taps - 1) / 2) * c7.dilation; p.off_step = c7.dilation;
-  p.ostride = 1; p.oshift0 = 0; p.jcount = L;
+  va_conv_geometry(p, c7.taps, c7.dilation, 1, L);
   p.w2 = reinterpret_cast<const uint16_t*>(c1.w); p.bias2 = c1.bias; p.alpha_mid = alpha_mid;
   ++va_conv_units_fused;
   const dim3 grid(gx, 1, B);
@@ -1347,425 +1104,7 @@ static int launch_conv_unit(const vaura_conv& c7, const vaura_conv& c1, const fl
 }
 
 
-// ---------------------------------------------------------------------------------------------
-// Row f2's linear layers (vit.hip) are one-tap problems: no halo to reuse, so per k-step both operand tiles come through
-// L2 and the 128 x 96 conv tile above moves 28 KB per 2.4 MFLOP — it sat at the L2 rate (130 TFLOP/s-equivalent).  This
-// kernel is the same pair arithmetic on a 128 x 192 tile (wave tile 64 x 96: 20 fragment reads per 72 MFMAs instead of
-// 14 per 36; 40 KB per 4.7 MFLOP), ONE LDS stage of 40 KB (global -> registers runs ahead by one step, two barriers per
-// step) so that two workgroups share a CU and one's epilogue / barriers sit under the other's matrix instructions, and
-// an XCD-aware tile order: workgroup id % 8 is the XCD, and an XCD walks "its" row tiles with the column tiles fastest,
-// so an activation tile is fetched into one L2 only and reused there by every column tile.
-#define LBN 192
-// VA_LIN_ABL: timing ablations for tools/experiment.sh linear-abl (WRONG RESULTS; product build = 0): 1 no global loads inside the
-// k loop, 2 no fragment reads / matrix instructions, 4 no LDS staging stores, 8 no global traffic in the epilogue
-#ifndef VA_LIN_ABL
-#define VA_LIN_ABL 0
-#endif
-// MW = wave rows: 2 -> 128 x 192 tile, 256 threads, two workgroups per CU; 4 -> 256 x 192 tile, 512 threads, one per CU
-template <int MW>
-__global__ __launch_bounds__(128 * MW, MW == 2 ? 2 : 1) void linear_pair_kernel(ConvPArgs a, int mtiles, int ntiles) {
-  constexpr int NTH = 128 * MW, LBM_ = 64 * MW, NWQ = LBN * 8 / NTH, NXQ = LBM_ * 8 / NTH;
-  __shared__ u32x4 smem[8 * (LBN + LBM_)];
-  // [kq][row ^ kq]: fragment reads (16 consecutive rows, one kq) and staging writes (one row, 8 kq) are both conflict-free
-  auto Ws = [&](int kq, int row) -> u32x4& { return smem[kq * LBN + (row ^ kq)]; };
-  auto Xs = [&](int kq, int row) -> u32x4& { return smem[8 * LBN + kq * LBM_ + (row ^ kq)]; };
-  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-  const int wn = wv & 1, wm = wv >> 1;
-  const int xcd = blockIdx.x & 7, local = blockIdx.x >> 3;
-  const int nt = local % ntiles, mt = (local / ntiles) * 8 + xcd;
-  if (mt >= mtiles) return;
-  const int b = blockIdx.y;
-  const int j0 = mt * LBM_, n0 = nt * LBN;
-  const int cq = a.Cin / 4;                 // 16-B quads per row (C/8 octets x 2 planes)
-  const u32x4* in = reinterpret_cast<const u32x4*>(a.in) + (size_t)b * a.Lin * cq;
-  const u32x4* wb = reinterpret_cast<const u32x4*>(a.w);
-  const int nk = a.Cin / BK;
-
-  u32x4 wreg[NWQ], xreg[NXQ];
-  auto load_regs = [&](int kt) {
-    const int q0 = kt * 8;
-#pragma unroll
-    for (int i = 0; i < NWQ; ++i) {
-      const int qd = tid + NTH * i;
-      wreg[i] = wb[(size_t)(n0 + (qd >> 3)) * cq + q0 + (qd & 7)];
-    }
-#pragma unroll
-    for (int i = 0; i < NXQ; ++i) {
-      const int qd = tid + NTH * i, jr = j0 + (qd >> 3);
-      xreg[i] = jr < a.Lin ? in[(size_t)jr * cq + q0 + (qd & 7)] : u32x4{0u, 0u, 0u, 0u};
-    }
-  };
-  auto store_lds = [&]() {
-#pragma unroll
-    for (int i = 0; i < NWQ; ++i) { const int qd = tid + NTH * i; Ws(qd & 7, qd >> 3) = wreg[i]; }
-#pragma unroll
-    for (int i = 0; i < NXQ; ++i) { const int qd = tid + NTH * i; Xs(qd & 7, qd >> 3) = xreg[i]; }
-  };
-
-  f32x4 acc[6][4];
-#pragma unroll
-  for (int i = 0; i < 6; ++i)
-#pragma unroll
-    for (int j = 0; j < 4; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-
-  const int g = lane >> 4, r16 = lane & 15;
-  load_regs(0);
-  for (int kt = 0; kt < nk; ++kt) {
-    if constexpr (VA_LIN_ABL & 4) { if (a.Cin == 12345) store_lds(); } else store_lds();
-    __syncthreads();
-    if (kt + 1 < nk && !(VA_LIN_ABL & 1)) load_regs(kt + 1);
-    f16x8 xh[4], xl[4];
-    if constexpr (!(VA_LIN_ABL & 2)) {
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      xh[j] = __builtin_bit_cast(f16x8, Xs(2 * g, wm * 64 + j * 16 + r16));
-      xl[j] = __builtin_bit_cast(f16x8, Xs(2 * g + 1, wm * 64 + j * 16 + r16));
-    }
-#pragma unroll
-    for (int i = 0; i < 6; ++i) {
-      const f16x8 wh = __builtin_bit_cast(f16x8, Ws(2 * g, wn * 96 + i * 16 + r16));
-      const f16x8 wl = __builtin_bit_cast(f16x8, Ws(2 * g + 1, wn * 96 + i * 16 + r16));
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wl, xh[j], acc[i][j], 0, 0, 0);
-        acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wh, xl[j], acc[i][j], 0, 0, 0);
-        acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wh, xh[j], acc[i][j], 0, 0, 0);
-      }
-    }
-    }
-    __syncthreads();
-  }
-
-  // ---- epilogue, one 16-row slab of every wave per pass (16 MW rows x 192 columns staged in LDS): every thread then owns whole
-  // octets of a row (32 contiguous bytes per stream), like conv_tile_store
-  constexpr int SP = LBN + 4, OCT = LBN / 8;
-  static_assert(8 * (LBN + LBM_) * 16 >= 16 * MW * SP * 4, "the staged slab must fit in the main loop's LDS");
-  float* stage = reinterpret_cast<float*>(smem);
-  const size_t obase = (size_t)b * a.Lout;
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-#pragma unroll
-    for (int i = 0; i < 6; ++i) {
-      const int col = wn * 96 + i * 16 + 4 * g;
-      *reinterpret_cast<f32x4*>(stage + (wm * 16 + r16) * SP + col) = acc[i][j] + *reinterpret_cast<const f32x4*>(a.bias + n0 + col);
-    }
-    __syncthreads();
-#pragma unroll
-    for (int it = 0; it < 16 * MW * OCT / NTH; ++it) {
-      const int u = tid + NTH * it, lr = u / OCT, oc = u - lr * OCT;
-      const int jr = j0 + (lr >> 4) * 64 + j * 16 + (lr & 15);
-      if (jr < a.Lin && (!(VA_LIN_ABL & 8) || stage[lr * SP + oc * 8] == 12345.678f)) {
-        const int co = n0 + oc * 8;
-        const size_t orow = obase + (size_t)(jr + a.oshift0);
-        const size_t o = orow * a.Cout + co;
-        f32x4 v0 = *reinterpret_cast<const f32x4*>(stage + lr * SP + oc * 8);
-        f32x4 v1 = *reinterpret_cast<const f32x4*>(stage + lr * SP + oc * 8 + 4);
-        if (a.res) {
-          v0 = *reinterpret_cast<const f32x4*>(a.res + o) + v0;
-          v1 = *reinterpret_cast<const f32x4*>(a.res + o + 4) + v1;
-        }
-        if (a.out_raw) {
-          *reinterpret_cast<f32x4*>(a.out_raw + o) = v0;
-          *reinterpret_cast<f32x4*>(a.out_raw + o + 4) = v1;
-        }
-        if (a.out_act) {
-          float sv[8];
-#pragma unroll
-          for (int r = 0; r < 4; ++r) {
-            sv[r] = a.act == 1 ? gelu_erf_f(v0[r]) : v0[r];
-            sv[r + 4] = a.act == 1 ? gelu_erf_f(v1[r]) : v1[r];
-          }
-          store_act_octet(a.out_act, nullptr, 0, orow, co, a.Cout, sv);
-        }
-      }
-    }
-    __syncthreads();
-  }
-}
-
-// The same tile, wave layout, products and summation order (bit-identical outputs) with the operands brought in by LDS-DMA: no
-// staging registers, no ds_write, NST stages of 40 KB in flight (2: two workgroups share a CU, the next chunk flies during this one's
-// matrix instructions; 3: one workgroup, two chunks ahead), ONE barrier per chunk.
-// A DMA piece (one global_load_lds_dwordx4: lane l's 16 bytes land at slot l of 1 KB) is 8 ROWS x the whole 128-byte chunk of each
-// (8 lanes = one cache line; the first cut fetched a fragment per piece — 16 rows x every other quad, 64 requests per instruction —
-// and was bound by the address path: 52 ms against 45).  What makes the fragment reads conflict-free on such an image: a block of 32
-// rows (two 16-row tiles) is four pieces; piece p holds rows p, p + 4, p + 8, p + 12 of each tile at k = 4 tile + 2 ((r >> 2) & 1) +
-// ((r >> 3) & 1), and stores a row's 8 quads ROTATED by s(p) = {0, 1, 4, 5}: quad q at position (q + s(p)) mod 8.  A ds_read_b128
-// is served in groups of 16 lanes holding 16 different rows with two neighbouring octets g (MI355X_MICROARCH.md, LDS): their slots
-// mod 16 are 8 (r >> 3 & 1) + (2 g + plane + s(r & 3)) mod 8 — sixteen different values.  The epilogue writes from the accumulators: a lane holds 4 consecutive output columns of one row (16 bytes
-// of the fp32 tensor); for the pair-layout copy the lanes g, g ^ 1 of a row swap halves (v_permlane16_swap) and write the octet's hi
-// and lo quad — no LDS staging, no barriers.  Measured by ablation on round 4's kernel (tools/experiment.sh linear-abl, 35 ms of
-// linears): global loads through registers 7 ms, the staging stores 8 ms, the staged epilogue 9 ms, matrix instructions 12 ms —
-// nothing overlapped well.
-// EARLY (two stages, the product): a chunk's fragments are all read into registers at the head of its step and a second barrier
-// frees its stage at once for chunk kt + 2 — a DMA piece then has two steps of matrix instructions to land instead of one, in the
-// same 80 KB.  Whole extractor forwards, 8 clips (round 4's kernel 44.2 ms): late reads 43.2, EARLY 42.0.
-// MW = wave rows, NWN = waves along the 192 columns; only <2, 2> (128 x 192, four waves of 64 x 96, two workgroups per CU) is
-// instantiated.  Measured and dropped (DESIGN_HISTORY.md, round 5): <NST 3, 2, 2> one workgroup of four waves 50.3 ms; <2, MW 4, 2>
-// 256 x 192 on eight waves (43 % less traffic from beyond L2) 43.6; <3 | 4, 2, NWN 4> eight waves of 64 x 48 with three / four
-// stages 45.2 / 45.4; the accumulators stored without the LDS turn-around 41.7 (no better: what the epilogue costs is its bytes).
-template <int NST, int MW = 2, int NWN = 2, bool EARLY = false>
-__global__ __launch_bounds__(64 * MW * NWN, (NST == 2 && MW * NWN == 4) ? 2 : 1) void linear_dma_kernel(ConvPArgs a, int mtiles, int ntiles, int panel) {
-  static_assert(!EARLY || NST == 2, "EARLY is the two-stage schedule");
-  typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
-  typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
-  constexpr int LBM_ = 64 * MW, NWV = NWN * MW, NI = 12 / NWN, WC = NI * 16, XF = (LBM_ / 16) * 2, WF = (LBN / 16) * 2, PPW = (XF + WF) / NWV, STB = (XF + WF) * 1024;
-  static_assert((XF + WF) % NWV == 0, "the same number of pieces per wave");
-  extern __shared__ __attribute__((aligned(16))) unsigned char lind_lds[];
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int wn = wv % NWN, wm = wv / NWN;
-  const int xcd = blockIdx.x & 7, local = blockIdx.x >> 3;
-  // Tile order inside an XCD: column tiles in PANELS of `panel` (a divisor of ntiles), all of the XCD's row tiles per panel, the
-  // panel's column tiles fastest.  With panel = ntiles (round 4's order) every group of workgroups in flight streams the WHOLE weight
-  // matrix through a 4 MB L2 (7 - 9 MB for 768 -> 2304 / 3072): measured 1.45 / 2.0 GB fetched from beyond L2 per launch for 0.16 GB
-  // of operands.  A panel of 4 column tiles (2.4 MB at K = 768) stays resident; the activations are then fetched once per panel.
-  const int rows_x = (mtiles + 7) >> 3, per_panel = rows_x * panel;
-  const int pn = local / per_panel, lp = local - pn * per_panel;
-  const int nt = pn * panel + lp % panel, mt = (lp / panel) * 8 + xcd;
-  if (mt >= mtiles) return;
-  const int b = blockIdx.y;
-  const int j0 = mt * LBM_, n0 = nt * LBN;
-  const int cq = a.Cin / 4;                 // 16-B quads per row (C/8 octets x 2 planes)
-  const int nk = a.Cin / BK;
-  const int g = lane >> 4, r16 = lane & 15;
-
-  // this wave's PPW pieces of a stage: piece P < XF = activation rows (32-row block P / 4, piece P % 4 of it), else weight rows.
-  // Rows past the end re-read the last one (their outputs are not stored).
-  const unsigned char* src[PPW];
-  {
-    const int k = lane >> 3, kk = k & 3;
-    const int rr = (k >> 2) * 16 + 4 * (kk >> 1) + 8 * (kk & 1);        // row of the block, before + p
-#pragma unroll
-    for (int j = 0; j < PPW; ++j) {
-      const int P = wv * PPW + j, pp = P & 3;
-      const int q = ((lane & 7) - (pp + (pp >> 1) * 2)) & 7;            // s(p) = {0, 1, 4, 5}
-      if (P < XF) {
-        const int row = min(j0 + (P >> 2) * 32 + rr + pp, a.Lin - 1);
-        src[j] = reinterpret_cast<const unsigned char*>(a.in) + (((size_t)b * a.Lin + row) * cq + q) * 16;
-      } else {
-        src[j] = reinterpret_cast<const unsigned char*>(a.w) + ((size_t)(n0 + ((P - XF) >> 2) * 32 + rr + pp) * cq + q) * 16;
-      }
-    }
-  }
-  auto issue = [&](int stage) {
-#pragma unroll
-    for (int j = 0; j < PPW; ++j) {
-      const int p = wv * PPW + j;
-      __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src[j],
-                                       (__attribute__((address_space(3))) void*)(lind_lds + stage * STB + p * 1024), 16, 0, 0);
-      src[j] += 128;                        // the next 32-channel chunk of the same rows
-    }
-  };
-  // fragment (16-row tile m of the stage's rows, plane pl) as lane (g, r16) reads it
-  int foff[2];
-  {
-    const int pp = r16 & 3, sp = pp + (pp >> 1) * 2, kq = (((r16 >> 3) & 1) + 2 * ((r16 >> 2) & 1)) * 8;
-    foff[0] = pp * 1024 + (kq + ((2 * g + sp) & 7)) * 16;
-    foff[1] = pp * 1024 + (kq + ((2 * g + 1 + sp) & 7)) * 16;
-  }
-  auto xfrag = [&](int stage, int m, int pl) -> f16x8 {
-    return __builtin_bit_cast(f16x8, *reinterpret_cast<const u32x4*>(lind_lds + stage * STB + (m >> 1) * 4096 + (m & 1) * 512 + foff[pl]));
-  };
-  auto wfrag = [&](int stage, int n, int pl) -> f16x8 {
-    return __builtin_bit_cast(f16x8, *reinterpret_cast<const u32x4*>(lind_lds + stage * STB + XF * 1024 + (n >> 1) * 4096 + (n & 1) * 512 + foff[pl]));
-  };
-
-  f32x4 acc[NI][4];
-#pragma unroll
-  for (int i = 0; i < NI; ++i)
-#pragma unroll
-    for (int j = 0; j < 4; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-
-  if constexpr (EARLY) {
-    issue(0);
-    if (nk > 1) issue(1);
-    for (int kt = 0; kt < nk; ++kt) {
-      const int st = kt & 1;
-      if (kt + 1 < nk) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(PPW) : "memory");      // chunk kt + 1 may still fly
-      else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      __builtin_amdgcn_s_barrier();
-      asm volatile("" ::: "memory");
-      f16x8 xh[4], xl[4], wh[NI], wl[NI];
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        xh[j] = xfrag(st, wm * 4 + j, 0);
-        xl[j] = xfrag(st, wm * 4 + j, 1);
-      }
-#pragma unroll
-      for (int i = 0; i < NI; ++i) {
-        wh[i] = wfrag(st, wn * NI + i, 0);
-        wl[i] = wfrag(st, wn * NI + i, 1);
-      }
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-      __builtin_amdgcn_s_barrier();          // every wave holds its fragments: the stage is free
-      asm volatile("" ::: "memory");
-      if (kt + 2 < nk && !(VA_LIN_ABL & 1)) issue(st);
-      if constexpr (!(VA_LIN_ABL & 2)) {
-#pragma unroll
-        for (int i = 0; i < NI; ++i)
-#pragma unroll
-          for (int j = 0; j < 4; ++j) {
-            acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wl[i], xh[j], acc[i][j], 0, 0, 0);
-            acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wh[i], xl[j], acc[i][j], 0, 0, 0);
-            acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wh[i], xh[j], acc[i][j], 0, 0, 0);
-          }
-      }
-    }
-  } else {
-#pragma unroll
-  for (int st = 0; st < NST - 1; ++st)
-    if (st < nk) issue(st);
-  int st0 = 0;                              // stage of chunk kt
-  for (int kt = 0; kt < nk; ++kt) {
-    // this wave's pieces of chunk kt have landed (chunks issued after it may still fly: none with two stages); the barrier publishes
-    // every wave's pieces and says that every wave is done reading chunk kt - 1, whose stage takes chunk kt + NST - 1
-    {
-      const int ahead = min(NST - 2, nk - 1 - kt);      // chunks issued after chunk kt
-      if (NST >= 4 && ahead >= 2) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * PPW) : "memory");
-      else if (NST >= 3 && ahead == 1) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(PPW) : "memory");
-      else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    }
-    __builtin_amdgcn_s_barrier();
-    asm volatile("" ::: "memory");
-    if (kt + NST - 1 < nk && !(VA_LIN_ABL & 1)) issue(st0 == 0 ? NST - 1 : st0 - 1);
-    if constexpr (!(VA_LIN_ABL & 2)) {
-      f16x8 xh[4], xl[4];
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        xh[j] = xfrag(st0, wm * 4 + j, 0);
-        xl[j] = xfrag(st0, wm * 4 + j, 1);
-      }
-#pragma unroll
-      for (int i = 0; i < NI; ++i) {
-        const f16x8 wh = wfrag(st0, wn * NI + i, 0);
-        const f16x8 wl = wfrag(st0, wn * NI + i, 1);
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wl, xh[j], acc[i][j], 0, 0, 0);
-          acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wh, xl[j], acc[i][j], 0, 0, 0);
-          acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(wh, xh[j], acc[i][j], 0, 0, 0);
-        }
-      }
-    }
-    st0 = st0 == NST - 1 ? 0 : st0 + 1;
-  }
-  }
-
-  // ---- epilogue: acc[i][j][r] = out[row j0 + wm 64 + 16 j + r16][column n0 + wn WC + 16 i + 4 g + r].  Stored straight from the
-  // accumulators a wave instruction covers 16 rows x 64 bytes with NEIGHBOURING LANES IN DIFFERENT ROWS — 64 separate 16-byte
-  // requests; that cut (no LDS, no barriers) cost as much as round 4's staged one (10 of 34 ms: tools/experiment.sh linear-abl).
-  // Here every wave turns its own 32 x WC slab around through a private piece of the (now idle) stages — no workgroup barrier —
-  // and reads it back with consecutive lanes on consecutive 16 bytes of a row: residual loads and both stores in whole lines.
-  constexpr int SPW = WC + 4, QPR = WC / 4;      // padded slab row (floats; stride = 4 mod 8 banks: conflict-free b128 stores), quads per row
-  static_assert(NWV * 32 * SPW * 4 <= NST * STB && (32 * QPR) % 64 == 0, "a 32-row slab per wave inside the stages");
-  float* slab = reinterpret_cast<float*>(lind_lds) + wv * (32 * SPW);
-  if constexpr (!EARLY) __syncthreads();         // the last chunk's fragment reads of the slower waves (EARLY: behind its second barrier)
-  const size_t obase = (size_t)b * a.Lout;
-  f32x4 bias4[NI];
-#pragma unroll
-  for (int i = 0; i < NI; ++i) bias4[i] = *reinterpret_cast<const f32x4*>(a.bias + n0 + wn * WC + i * 16 + 4 * g);
-#pragma unroll
-  for (int half = 0; half < 2; ++half) {
-#pragma unroll
-    for (int jj = 0; jj < 2; ++jj)
-#pragma unroll
-      for (int i = 0; i < NI; ++i)
-        *reinterpret_cast<f32x4*>(slab + (jj * 16 + r16) * SPW + i * 16 + 4 * g) = acc[i][2 * half + jj] + bias4[i];
-    // the residual quads of the whole half, requested before the first store: `res` may be `out_raw` (x += ...), so the compiler must
-    // keep every load behind the stores in front of it — one memory round trip per iteration if they are written where they are used
-    constexpr int NIT = 32 * QPR / 64;
-    f32x4 rq[NIT];
-    if (a.res && !(VA_LIN_ABL & 8)) {
-#pragma unroll
-      for (int it = 0; it < NIT; ++it) {
-        const int Q = it * 64 + lane, row = Q / QPR, cq = Q - row * QPR;
-        const int jr = min(j0 + wm * 64 + half * 32 + row, a.Lin - 1);
-        rq[it] = *reinterpret_cast<const f32x4*>(a.res + (obase + (size_t)(jr + a.oshift0)) * a.Cout + n0 + wn * WC + cq * 4);
-      }
-    }
-#pragma unroll
-    for (int it = 0; it < NIT; ++it) {
-      const int Q = it * 64 + lane, row = Q / QPR, cq = Q - row * QPR;
-      f32x4 v = *reinterpret_cast<const f32x4*>(slab + row * SPW + cq * 4);
-      const int jr = j0 + wm * 64 + half * 32 + row;
-      const bool live = jr < a.Lin && (!(VA_LIN_ABL & 8) || v[0] == 12345.678f);
-      const size_t orow = obase + (size_t)(min(jr, a.Lin - 1) + a.oshift0);
-      const int co = n0 + wn * WC + cq * 4;
-      if (a.res && !(VA_LIN_ABL & 8)) v = rq[it] + v;
-      if (a.out_raw && live) *reinterpret_cast<f32x4*>(a.out_raw + orow * a.Cout + co) = v;
-      if (a.out_act) {
-        f16x4 hi, lo;
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const float x = a.act == 1 ? gelu_erf_f(v[r]) : v[r];
-          hi[r] = (_Float16)x;
-          lo[r] = (_Float16)(x - (float)hi[r]);
-        }
-        // lanes l (even: columns 0-3 of the octet) and l ^ 1 (columns 4-7) trade halves: the even one writes the hi quad, the odd one the lo
-        const u32x2 h2 = __builtin_bit_cast(u32x2, hi), l2 = __builtin_bit_cast(u32x2, lo);
-        const bool odd = lane & 1;
-        const uint32_t s0 = odd ? h2[0] : l2[0], s1 = odd ? h2[1] : l2[1];
-        const uint32_t t0 = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)s0, VA_DPP_XOR1, 0xf, 0xf, true);
-        const uint32_t t1 = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)s1, VA_DPP_XOR1, 0xf, 0xf, true);
-        if (live) {
-          u32x4* dst = reinterpret_cast<u32x4*>(a.out_act) + (orow * (size_t)(a.Cout >> 3) + (size_t)(co >> 3)) * 2 + (odd ? 1 : 0);
-          *dst = odd ? u32x4{t0, t1, l2[0], l2[1]} : u32x4{h2[0], h2[1], t0, t1};
-        }
-      }
-    }
-  }
-}
-
 VA_STAMP_SETTER(vaura_stamps_set_dac)
-
-// Plain linear layer on the pair GEMM (row f2, vit.hip): out[b][row + oshift][:] = act( in[b][row][:] . W^T + bias (+ res) ).
-// in: pair layout (B, Lin, Cin); w: pair layout (Cout, Cin); out rows live in sequences of Lout rows per b.
-int va_launch_linear_pair(const uint16_t* in, const uint16_t* w, const float* bias, const float* res, float* out_raw,
-                          uint16_t* out_act, int act, int B, int Lin, int Lout, int oshift, int Cin, int Cout, hipStream_t s) {
-  if (!in || !w || !bias || (Cin % BK) || (Cout % BN) || B <= 0 || Lin <= 0) return VAURA_ERR_SHAPE;
-  ConvPArgs p;
-  p.in = in; p.w = w; p.bias = bias; p.res = res; p.alpha = nullptr; p.out_raw = out_raw; p.out_act = out_act;
-  p.Lin = Lin; p.Lout = Lout; p.Cin = Cin; p.Cout = Cout; p.NT = 1; p.off_base = 0; p.off_step = 1; p.ostride = 1;
-  p.oshift0 = oshift; p.jcount = Lin; p.act = act;
-  p.act_fmt = 0; p.out_scale = nullptr; p.in_scale = nullptr; p.wscale = nullptr;
-  p.w2 = nullptr; p.bias2 = nullptr; p.alpha_mid = nullptr;
-  if (Cout % LBN == 0 && act != 0 && !(va_debug_flags_get() & 64)) {     // debug flag bit 6: the 128 x 96 conv tile instead
-    const int ntiles = Cout / LBN;
-    // debug flag bit 8: 256 x 192 tiles (512 threads, one workgroup per CU) — 30 % fewer operand bytes per flop, and measured
-    // SLOWER (48.8 vs 46.2 ms per forward): eight waves behind one barrier lose more than the L2 traffic saved
-    if (Lin >= 256 * 64 && (va_debug_flags_get() & 256)) {
-      const int mtiles = (Lin + 255) / 256;
-      VA_LAUNCH(linear_pair_kernel<4>, dim3((unsigned)(((mtiles + 7) / 8) * 8 * ntiles), B), dim3(512), 0, s, p, mtiles, ntiles);
-    } else {
-      const int mtiles = (Lin + 127) / 128;
-#ifndef VA_LIN_F2
-#define VA_LIN_F2 0u       // experiment builds: instance bits forced on (tools/experiment.sh linear-abl drives a C++ program without flag control)
-#endif
-      const unsigned f2 = va_debug_flags2_get() | VA_LIN_F2;
-      // column-tile panel (see linear_dma_kernel): 4 tiles while a tile of the weights is <= 1 MB (K <= 1280), else the whole width;
-      // second flag word bits 12..15 override (1 .. 15 tiles; must divide ntiles)
-      int panel = (Cin <= 1280 && ntiles % 4 == 0) ? 4 : ntiles;
-      if (((f2 >> 12) & 15u) && ntiles % (int)((f2 >> 12) & 15u) == 0) panel = (int)((f2 >> 12) & 15u);
-      if (((f2 >> 12) & 15u) == 15u) panel = ntiles;
-      const dim3 grid((unsigned)(((mtiles + 7) / 8) * 8 * ntiles), B);
-      if (f2 & 32u) {                      // second flag word, bit 5: round 4's register-staged kernel
-        VA_LAUNCH(linear_pair_kernel<2>, grid, dim3(256), 0, s, p, mtiles, ntiles);
-      } else if (f2 & 64u) {               // bit 6: LDS-DMA with the fragments read next to their matrix instructions (one barrier per chunk)
-        static unsigned long long big2 = 0;
-        if (va_big_lds_once(reinterpret_cast<const void*>(linear_dma_kernel<2, 2, 2, false>), 2 * 40 * 1024, &big2)) return VAURA_ERR_STATE;
-        VA_LAUNCH((linear_dma_kernel<2, 2, 2, false>), grid, dim3(256), 2 * 40 * 1024, s, p, mtiles, ntiles, panel);
-      } else {
-        static unsigned long long bige = 0;
-        if (va_big_lds_once(reinterpret_cast<const void*>(linear_dma_kernel<2, 2, 2, true>), 2 * 40 * 1024, &bige)) return VAURA_ERR_STATE;
-        VA_LAUNCH((linear_dma_kernel<2, 2, 2, true>), grid, dim3(256), 2 * 40 * 1024, s, p, mtiles, ntiles, panel);
-      }
-    }
-    return 0;
-  }
-  VA_LAUNCH((conv_pair_kernel<3, false>), dim3((Lin + BM - 1) / BM, Cout / BN, B), dim3(256), 0, s, p);
-  return 0;
-}
 
 // ---------------------------------------------------------------------------------------------
 // Encode side (DacModelWrapper.encode, models/modules/dac/model.py:30-39).
@@ -1902,159 +1241,6 @@ static int launch_conv_out(const vaura_conv& co, const float* A, float* wav, int
   return 0;
 }
 
-// ---------------------------------------------------------------------------------------------
-// Clips of different lengths in ONE pass (vaura_dac_decode_clips / vaura_dac_encode_clips).  The B clips lie behind one another
-// on the time axis of a single sequence (B = 1 for every conv launch), `gap` latent frames of zeros between neighbours: clip b
-// starts at latent row off[b], at row off[b] * rate on a level with `rate` rows per latent frame, at sample off[b] * hop.  No conv
-// kernel knows about it.  A tap of a row of clip b lands inside the clip, in a gap — zeros, what the `jr >= 0 && jr < Lin` mask
-// gives the clip decoded alone — or past an end of the sequence, where that mask applies.  Residual and raw rows are read at their own
-// position only, a 1 x 1 conv is pointwise, and a transposed conv writes a row from one (j, phase).  A launch writes gap rows like
-// any other (from the neighbours' edges), so the gap rows of every ACTIVATED buffer that a conv with more than one tap reads are
-// cleared again behind the launch that wrote it (clips_zero_gaps_kernel).  The gap is the smallest number of latent frames that, on
-// every level, covers the largest one-sided reach of the convs that run there (va_clips_gap_*).
-#define VA_CLIP_CHUNK 64
-struct ClipChunk {                    // up to VA_CLIP_CHUNK clips by value: a launch per chunk, no table on the device
-  int n, b0;                          // clips in this chunk, index of the first
-  int off[VA_CLIP_CHUNK];             // first latent row of the clip in the packed sequence
-  int len[VA_CLIP_CHUNK];             // its latent frames
-  int64_t aux[VA_CLIP_CHUNK];         // its samples (encode)
-};
-struct WindowLayout;
-struct ClipLayout {
-  int B, gap;
-  int64_t total;                      // latent rows of the packed sequence: off[B - 1] + len[B - 1]
-  const int* off;
-  const int* len;
-  const int64_t* aux;
-  const WindowLayout* win = nullptr;  // vaura_dac_decode_window: the packed clips are windows of the caller's clips (see WindowLayout)
-};
-static ClipChunk va_clip_chunk(const ClipLayout& l, int b0, int bend) {
-  ClipChunk k;
-  k.b0 = b0; k.n = bend - b0 < VA_CLIP_CHUNK ? bend - b0 : VA_CLIP_CHUNK;
-  for (int i = 0; i < k.n; ++i) { k.off[i] = l.off[b0 + i]; k.len[i] = l.len[b0 + i]; k.aux[i] = l.aux ? l.aux[b0 + i] : 0; }
-  return k;
-}
-
-// the `gap` frames behind each clip of the chunk: unit = bytes of one latent frame of this buffer (rows per frame x bytes per row, a
-// multiple of 16).  0 is all-zero bytes in fp32, in both fp16 planes and in e4m3; an mx8 buffer keeps the scale bytes its producer wrote
-// (1 .. 253, mx8_scale_byte): 0 x 2^s is 0.
-__global__ __launch_bounds__(256) void clips_zero_gaps_kernel(unsigned char* __restrict__ buf, ClipChunk k, size_t unit, int gap) {
-  const int i = blockIdx.y;
-  u32x4* p = reinterpret_cast<u32x4*>(buf + (size_t)(k.off[i] + k.len[i]) * unit);
-  const size_t n16 = (size_t)gap * unit / 16;
-  for (size_t u = (size_t)blockIdx.x * 256 + threadIdx.x; u < n16; u += (size_t)gridDim.x * 256) p[u] = u32x4{0u, 0u, 0u, 0u};
-}
-// codes (B, K, Tmax) -> packed (K, total): a clip's own frames, code 0 on the `tail` frames behind it (the gap; 0 behind the last clip)
-__global__ __launch_bounds__(256) void clips_pack_codes_kernel(const int32_t* __restrict__ codes, int32_t* __restrict__ packed, ClipChunk k,
-                                                               int K, int Tmax, int64_t total, int gap, int B) {
-  const int i = blockIdx.y, kk = blockIdx.z, b = k.b0 + i;
-  const int n = k.len[i] + (b + 1 < B ? gap : 0);
-  for (int t = blockIdx.x * 256 + threadIdx.x; t < n; t += gridDim.x * 256)
-    packed[(size_t)kk * total + k.off[i] + t] = t < k.len[i] ? codes[((size_t)b * K + kk) * Tmax + t] : 0;
-}
-// packed (K, total) -> codes (B, K, Tmax): 0 behind a clip's frames
-__global__ __launch_bounds__(256) void clips_unpack_codes_kernel(const int32_t* __restrict__ packed, int32_t* __restrict__ codes, ClipChunk k,
-                                                                 int K, int Tmax, int64_t total) {
-  const int i = blockIdx.y, kk = blockIdx.z, b = k.b0 + i;
-  for (int t = blockIdx.x * 256 + threadIdx.x; t < Tmax; t += gridDim.x * 256)
-    codes[((size_t)b * K + kk) * Tmax + t] = t < k.len[i] ? packed[(size_t)kk * total + k.off[i] + t] : 0;
-}
-// wav (B, n_max) -> packed samples: aux[i] samples of the clip, zeros up to the end of its last frame (DAC.preprocess) and through the gap
-__global__ __launch_bounds__(256) void clips_pack_wav_kernel(const float* __restrict__ wav, float* __restrict__ packed, ClipChunk k,
-                                                             int64_t n_max, int hop, int gap, int B) {
-  const int i = blockIdx.y, b = k.b0 + i;
-  const int64_t n = (int64_t)(k.len[i] + (b + 1 < B ? gap : 0)) * hop;
-  float* dst = packed + (size_t)k.off[i] * hop;
-  for (int64_t u = (int64_t)blockIdx.x * 256 + threadIdx.x; u < n; u += (int64_t)gridDim.x * 256)
-    dst[u] = u < k.aux[i] ? wav[(size_t)b * n_max + u] : 0.f;
-}
-// packed samples -> wav (B, n_out): len[i] * hop samples of the clip, 0 behind them
-__global__ __launch_bounds__(256) void clips_unpack_wav_kernel(const float* __restrict__ packed, float* __restrict__ wav, ClipChunk k,
-                                                               int64_t n_out, int hop) {
-  const int i = blockIdx.y, b = k.b0 + i;
-  const int64_t n = (int64_t)k.len[i] * hop;
-  const float* src = packed + (size_t)k.off[i] * hop;
-  for (int64_t u = (int64_t)blockIdx.x * 256 + threadIdx.x; u < n_out; u += (int64_t)gridDim.x * 256)
-    wav[(size_t)b * n_out + u] = u < n ? src[u] : 0.f;
-}
-
-// A window of every clip in ONE pass (vaura_dac_decode_window).  The decoder is a finite-support conv stack: the samples of latent
-// frame f depend on the codes of frames f - H .. f + H only (H = va_decode_halo, from the conv descriptors).  So the frames
-// [lo, hi) = [max(0, s - H), min(len, s + n + H)) of a clip, decoded as a clip of their own, give the samples of [s, s + n) exactly:
-// a frame at least H from a cut end sees what it sees in the whole clip, and an end that is the clip's own (lo = 0, hi = len) has the
-// zero padding the whole clip has there.  The windows are the clips of a ClipLayout (a clip with count 0 has none): packing reads
-// from frame lo of the caller's tensor, unpacking skips the (s - lo) * hop samples in front.
-struct WindowChunk {                  // up to VA_CLIP_CHUNK entries by value
-  int n;
-  int b[VA_CLIP_CHUNK];               // the caller's clip
-  int off[VA_CLIP_CHUNK];             // pack: first latent row of the window in the packed sequence; unpack: of the frames asked for
-  int len[VA_CLIP_CHUNK];             // pack: latent frames of the window (the gap behind it included); unpack: the frames asked for
-  int src[VA_CLIP_CHUNK];             // pack: first frame of the window in the clip
-  int aux[VA_CLIP_CHUNK];             // pack: the window's own frames (len without the gap)
-};
-struct WindowLayout {
-  int B, n_max;                       // the caller's clips, the width of its output in frames
-  const int* clip;                    // per window: the caller's clip
-  const int* lo;                      // per window: its first frame in the clip
-  const int* skip;                    // per window: halo frames in front of the frames asked for
-  const int* window;                  // per caller's clip (B): index of its window, -1 for count 0
-  const int* count;                   // per caller's clip (B)
-  // vaura_dac_decode_window_seq: the caller's tensor is the decode loop's pattern sequence (B, seq_K, seq_S), not codes (seq_S = 0)
-  int seq_K = 0, seq_S = 0;
-  int seq_delays[16] = {0};
-};
-// codes (B, K, Tmax) -> packed (K, total): the window's frames from frame src[i] of clip b[i] on, code 0 on the gap frames behind it
-__global__ __launch_bounds__(256) void window_pack_codes_kernel(const int32_t* __restrict__ codes, int32_t* __restrict__ packed, WindowChunk k,
-                                                                int K, int Tmax, int64_t total) {
-  const int i = blockIdx.y, kk = blockIdx.z;
-  const int32_t* src = codes + ((size_t)k.b[i] * K + kk) * Tmax + k.src[i];
-  for (int t = blockIdx.x * 256 + threadIdx.x; t < k.len[i]; t += gridDim.x * 256)
-    packed[(size_t)kk * total + k.off[i] + t] = t < k.aux[i] ? src[t] : 0;
-}
-// The same pack from the decode loop's pattern sequence (vaura_dac_decode_window_seq): seq (B, K, S) holds frame t of codebook q at step
-// t + 1 + d_q (vaura_pattern_build_delays), so the window's frames are gathered from there and no reverted tensor exists.  A value that
-// is no code (an unknown slot, the special token: the host's checks keep every window off them) is packed as code 0, never used as an index.
-struct SeqDelays { int d[16]; };
-__global__ __launch_bounds__(256) void window_pack_seq_kernel(const int32_t* __restrict__ seq, int32_t* __restrict__ packed, WindowChunk k,
-                                                              SeqDelays dl, int K, int S, int64_t total, int card) {
-  const int i = blockIdx.y, kk = blockIdx.z;
-  const int32_t* src = seq + ((size_t)k.b[i] * K + kk) * S + k.src[i] + 1 + dl.d[kk];
-  for (int t = blockIdx.x * 256 + threadIdx.x; t < k.len[i]; t += gridDim.x * 256) {
-    const int32_t v = t < k.aux[i] ? src[t] : 0;
-    packed[(size_t)kk * total + k.off[i] + t] = (uint32_t)v < (uint32_t)card ? v : 0;
-  }
-}
-// packed samples -> wav (B, n_out): the len[i] * hop samples from packed frame off[i] on, 0 behind them (len 0: a row of zeros, nothing read)
-__global__ __launch_bounds__(256) void window_unpack_wav_kernel(const float* __restrict__ packed, float* __restrict__ wav, WindowChunk k,
-                                                                int64_t n_out, int hop) {
-  const int i = blockIdx.y, b = k.b[i];
-  const int64_t n = (int64_t)k.len[i] * hop;
-  const float* src = packed + (size_t)k.off[i] * hop;
-  for (int64_t u = (int64_t)blockIdx.x * 256 + threadIdx.x; u < n_out; u += (int64_t)gridDim.x * 256)
-    wav[(size_t)b * n_out + u] = u < n ? src[u] : 0.f;
-}
-// windows w0 .. of the layout: what window_pack_codes_kernel reads and where it writes
-static WindowChunk va_window_pack_chunk(const ClipLayout& l, int w0) {
-  WindowChunk k;
-  k.n = l.B - w0 < VA_CLIP_CHUNK ? l.B - w0 : VA_CLIP_CHUNK;
-  for (int i = 0; i < k.n; ++i) {
-    const int w = w0 + i;
-    k.b[i] = l.win->clip[w]; k.off[i] = l.off[w]; k.src[i] = l.win->lo[w]; k.aux[i] = l.len[w];
-    k.len[i] = l.len[w] + (w + 1 < l.B ? l.gap : 0);
-  }
-  return k;
-}
-// the caller's clips b0 .. : where window_unpack_wav_kernel finds the frames asked for (a clip with count 0 has no window: len 0)
-static WindowChunk va_window_unpack_chunk(const ClipLayout& l, int b0) {
-  WindowChunk k;
-  k.n = l.win->B - b0 < VA_CLIP_CHUNK ? l.win->B - b0 : VA_CLIP_CHUNK;
-  for (int i = 0; i < k.n; ++i) {
-    const int b = b0 + i, w = l.win->window[b];
-    k.b[i] = b; k.len[i] = l.win->count[b]; k.off[i] = w < 0 ? 0 : l.off[w] + l.win->skip[w]; k.src[i] = k.aux[i] = 0;
-  }
-  return k;
-}
-
 static unsigned va_clip_gx(int64_t items) {                     // workgroups along x for `items` per clip: grid-stride beyond 256
   const int64_t g = (items + 255) / 256;
   return (unsigned)(g < 1 ? 1 : (g > 256 ? 256 : g));
@@ -2070,50 +1256,6 @@ static int va_clips_zero(const ClipLayout& l, void* buf, int64_t rate, size_t ro
   }
   return 0;
 }
-static inline int va_ceil_div(int a, int b) { return (a + b - 1) / b; }
-static inline int va_conv_reach(const vaura_conv& cv) { return cv.stride > 1 ? 1 : ((cv.taps - 1) / 2) * cv.dilation; }
-// smallest gap (latent frames) with gap * rate(level) >= the one-sided reach of every conv on that level; -1: not a geometry of the pass
-static int va_clips_gap_decode(const vaura_codec* c) {
-  if (c->n_blocks < 1 || c->n_blocks > 4 || c->n_units != 3) return -1;
-  int g = va_conv_reach(c->conv_in), rate = 1;
-  for (int b = 0; b < c->n_blocks; ++b) {
-    if (c->rates[b] < 1) return -1;
-    g = std::max(g, va_ceil_div(va_conv_reach(c->up[b]), rate));     // reads rows j, j - 1 of its input level
-    rate *= c->rates[b];
-    for (int u = 0; u < 3; ++u)
-      for (int i = 0; i < 2; ++i) g = std::max(g, va_ceil_div(va_conv_reach(c->res[b][u][i]), rate));
-  }
-  g = std::max(g, va_ceil_div(va_conv_reach(c->conv_out), rate));
-  return g < 1 ? 1 : g;
-}
-static int va_clips_gap_encode(const vaura_codec_encoder* c, int64_t* hop_out) {
-  if (c->n_blocks < 1 || c->n_blocks > 4 || c->n_units != 3) return -1;
-  int64_t hop = 1;
-  for (int b = 0; b < c->n_blocks; ++b) { if (c->rates[b] < 1) return -1; hop *= c->rates[b]; }
-  if (hop_out) *hop_out = hop;
-  int rate = (int)hop;
-  int g = va_ceil_div(3, rate);                                  // the first conv: k = 7 on the samples
-  for (int b = 0; b < c->n_blocks; ++b) {
-    for (int u = 0; u < 3; ++u)
-      for (int i = 0; i < 2; ++i) g = std::max(g, va_ceil_div(va_conv_reach(c->res[b][u][i]), rate));
-    rate /= c->rates[b];
-    g = std::max(g, va_ceil_div(va_conv_reach(c->down[b]), rate));   // 3 taps over rows of r * C channels = rows of its OUTPUT level
-  }
-  g = std::max(g, va_ceil_div(va_conv_reach(c->conv_out), rate));
-  return g < 1 ? 1 : g;
-}
-// offsets of `B` clips of `frames[b]` latent frames; false when the packed sequence leaves the int range of the launch arithmetic
-static bool va_clips_offsets(const int* frames, int B, int gap, int* off, int64_t* total) {
-  int64_t o = 0;
-  for (int b = 0; b < B; ++b) {
-    if (o > 0x7fffffff) return false;
-    off[b] = (int)o;
-    o += frames[b] + (b + 1 < B ? gap : 0);
-  }
-  *total = o;
-  return o <= 0x7fffffff;
-}
-
 extern "C" {
 
 long long vaura_debug_counter(int which) {
@@ -2282,67 +1424,7 @@ int vaura_dac_decode_clips(const vaura_codec* c, const int32_t* codes, int B, in
   return va_dac_decode_pass(c, codes, B, T_max, wav, &lay, as_stream(s_));
 }
 
-static inline int64_t va_floor_div(int64_t a, int64_t b) { return a >= 0 ? a / b : -((-a + b - 1) / b); }
-// Frames of context either side that the samples of one latent frame depend on: the rows [0, hop) of the last level, taken backwards
-// through the layers.  A k-tap conv of dilation d widens the interval by (k - 1) / 2 * d rows either side; a transposed conv (stride
-// r, k = 2r, pad ceil(r / 2)) writes row o from the input rows j with o = j * r - pad + t, 0 <= t < k, so [lo, hi] comes from
-// [ceil((lo + pad - k + 1) / r), floor((hi + pad) / r)].  At the latent level the frame itself is row 0.  -1: not such a geometry.
-static int va_decode_halo(const vaura_codec* c) {
-  if (va_clips_gap_decode(c) < 0) return -1;
-  auto plain = [](const vaura_conv& cv) { return cv.stride == 1 && cv.taps >= 1 && (cv.taps & 1) && cv.dilation >= 1; };
-  if (!plain(c->conv_in) || !plain(c->conv_out)) return -1;
-  int64_t hop = 1;
-  for (int b = 0; b < c->n_blocks; ++b) {
-    if (c->up[b].stride != c->rates[b] || c->up[b].taps != 2 || hop > 0x7fffffff / c->rates[b]) return -1;
-    hop *= c->rates[b];
-    for (int u = 0; u < 3; ++u)
-      for (int i = 0; i < 2; ++i) if (!plain(c->res[b][u][i])) return -1;
-  }
-  int64_t lo = -va_conv_reach(c->conv_out), hi = hop - 1 + va_conv_reach(c->conv_out);
-  for (int b = c->n_blocks - 1; b >= 0; --b) {
-    for (int u = 0; u < 3; ++u)
-      for (int i = 0; i < 2; ++i) { lo -= va_conv_reach(c->res[b][u][i]); hi += va_conv_reach(c->res[b][u][i]); }
-    const int64_t r = c->rates[b], pad = (r + 1) / 2, k = 2 * r;
-    lo = -va_floor_div(-(lo + pad - k + 1), r);
-    hi = va_floor_div(hi + pad, r);
-  }
-  lo -= va_conv_reach(c->conv_in); hi += va_conv_reach(c->conv_in);
-  const int64_t h = std::max(-lo, hi);
-  return h < 0 || h > 0x3fffffff ? -1 : (int)h;
-}
-
 int vaura_dac_decode_halo(const vaura_codec* c) { return c ? va_decode_halo(c) : -1; }
-
-// the windows of a decode_window call on the host: one per clip with count > 0
-struct WindowPlan {
-  std::vector<int> clip, lo, skip, len, off, window, count;
-  int64_t total = 0;                  // latent rows of the packed windows; 0: refused arguments, -1: beyond the int range
-  int gap = 0;
-};
-// T_max <= 0: lengths are checked against >= 1 only; lengths NULL: every clip has T_max frames (T_max <= 0: no end to clamp at, an
-// upper bound of the window).  n_max <= 0: counts are not checked against it.
-static WindowPlan va_window_plan(const vaura_codec* c, int B, int T_max, const int32_t* lengths, const int32_t* starts, const int32_t* counts,
-                                 int n_max) {
-  WindowPlan p;
-  const int H = va_decode_halo(c);
-  p.gap = va_clips_gap_decode(c);
-  if (H < 0 || p.gap < 0) return p;
-  p.window.assign((size_t)B, -1);
-  p.count.assign(counts, counts + B);
-  for (int b = 0; b < B; ++b) {
-    const int64_t len = lengths ? lengths[b] : (T_max > 0 ? T_max : 0x7fffffff);
-    const int64_t s = starts[b], n = counts[b];
-    if (len < 1 || (T_max > 0 && len > T_max) || s < 0 || n < 0 || s + n > len || (n_max > 0 && n > n_max)) { p.clip.clear(); return p; }
-    if (n == 0) continue;
-    const int64_t lo = std::max<int64_t>(0, s - H), hi = std::min(len, s + n + H);
-    p.window[(size_t)b] = (int)p.clip.size();
-    p.clip.push_back(b); p.lo.push_back((int)lo); p.skip.push_back((int)(s - lo)); p.len.push_back((int)(hi - lo));
-  }
-  if (p.clip.empty()) return p;                        // every count is 0
-  p.off.resize(p.clip.size());
-  if (!va_clips_offsets(p.len.data(), (int)p.clip.size(), p.gap, p.off.data(), &p.total)) p.total = -1;
-  return p;
-}
 
 size_t vaura_dac_decode_window_workspace_elems(const vaura_codec* c, int B, const int32_t* lengths, const int32_t* starts,
                                                const int32_t* counts) {
@@ -2352,7 +1434,6 @@ size_t vaura_dac_decode_window_workspace_elems(const vaura_codec* c, int B, cons
 }
 
 // the window pass on a caller's tensor of T_max frames per clip: codes (B, K, T_max), or with `sq` the pattern sequence it describes
-struct SeqSource { int K, S, d_max; int delays[16]; };
 static int va_dac_decode_window_any(const vaura_codec* c, const int32_t* codes, int B, int T_max, const int32_t* lengths, const int32_t* starts,
                                     const int32_t* counts, float* wav, int N_max, const SeqSource* sq, vaura_stream_t s_) {
   if (!c || !codes || !wav || !starts || !counts || B <= 0 || T_max <= 0 || N_max <= 0) return VAURA_ERR_ARG;
@@ -2390,19 +1471,6 @@ static int va_dac_decode_window_any(const vaura_codec* c, const int32_t* codes, 
 int vaura_dac_decode_window(const vaura_codec* c, const int32_t* codes, int B, int T_max, const int32_t* lengths, const int32_t* starts,
                             const int32_t* counts, float* wav, int N_max, vaura_stream_t s_) {
   return va_dac_decode_window_any(c, codes, B, T_max, lengths, starts, counts, wav, N_max, nullptr, s_);
-}
-
-// the pattern sequence of a window_seq call: K rows of S steps under `delays_host` (NULL: 0 .. K - 1) hold T = S - 1 - max(d) frames
-static bool va_seq_source(const vaura_codec* c, int K, int S, const int32_t* delays_host, SeqSource* out) {
-  if (!c || K < c->n_codebooks || K < 1 || K > 16 || S < 2) return false;
-  out->K = K; out->S = S; out->d_max = 0;
-  for (int q = 0; q < 16; ++q) {
-    const int d = q < K ? (delays_host ? delays_host[q] : q) : 0;
-    if (d < 0 || d > S - 2) return false;
-    out->delays[q] = d;
-    out->d_max = std::max(out->d_max, d);
-  }
-  return true;
 }
 
 size_t vaura_dac_decode_window_seq_workspace_elems(const vaura_codec* c, int B, int K, int S, const int32_t* delays_host,

@@ -6,9 +6,8 @@
 // measurement aid (vaura_set_debug_flags): bit 0 = keep the one-workgroup-per-tile kernels for wo / w2 (A/B of the row split),
 // bit 2 = w1||w3 and w2 as two launches even where the one-launch MLP (mlp_engine.h) is eligible, bits 28..31 = its timing ablations,
 // bit 4 = per-position prefill attention,
-// bit 5 = 64-row prefill GEMM workgroups only, bit 6 = row f2's linears on the 128 x 96 conv tile instead of linear_pair_kernel,
-// bit 7 = row f2's space attention with one thread per query instead of the MFMA kernel, bit 8 = 256-row tiles in
-// linear_pair_kernel, bit 9 = unsplit CLS attention, bit 10 = time attention with one thread per (head, frame),
+// bit 5 = 64-row prefill GEMM workgroups only, (bits 6 and 8: unused since the linear-layer experiments left, DESIGN_HISTORY.md,)
+// bit 7 = row f2's space attention with one thread per query instead of the MFMA kernel, bit 9 = unsplit CLS attention, bit 10 = time attention with one thread per (head, frame),
 // bit 11 = space attention on the exact-fp32 MFMA instead of fp16 pairs, bit 13 = the codec's last conv without the LDS window
 unsigned va_debug_flags = 0;
 VA_STAMP_SETTER(vaura_stamps_set_gemv3)

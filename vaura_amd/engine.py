@@ -1344,6 +1344,10 @@ def _clip_lengths(name: str, lengths, batch: int, hi: int) -> list:
     return n
 
 
+# codec precision name -> vaura_codec.precision (include/vaura_hip.h); CodecEngine's docstring says what each is
+CODEC_PRECISIONS = {"f32": 0, "f16pair": 1, "f16pair_w8": 2, "mx8": 3, "f16": 4}
+
+
 class CodecEngine:
     """DAC decode (codes -> waveform) on the HIP path; weights from a DAC-1.0.0-keyed state dict."""
 
@@ -1358,7 +1362,7 @@ class CodecEngine:
         _require_cuda(device)
         self.cfg, self.dev, self.lib = cfg, torch.device(device), L.lib()
         self._keep = []
-        self.pairs = {"f32": 0, "f16pair": 1, "f16pair_w8": 2, "mx8": 3, "f16": 4}[precision]
+        self.pairs = CODEC_PRECISIONS[precision]
         if self.pairs in (2, 3):
             from .quant import fp8_effective_codec_state_dict
             sd = fp8_effective_codec_state_dict(sd)
@@ -1604,7 +1608,7 @@ class CodecConvOp:
                  device="cuda:0", mx8_weights: bool = True):
         _require_cuda(device)
         self.dev, self.lib, self._keep = torch.device(device), L.lib(), []
-        self.pairs = {"f32": 0, "f16pair": 1, "f16pair_w8": 2, "mx8": 3, "f16": 4}[precision]
+        self.pairs = CODEC_PRECISIONS[precision]
         self.cv = L.Conv()
         CodecEngine._pack_conv(self, self.cv, weight.float(), bias.float(), dilation, stride, mx8_weights)
         self.stride = stride
@@ -1668,7 +1672,7 @@ class CodecUnitOp:
                  precision: str = "f16pair", device="cuda:0"):
         _require_cuda(device)
         self.dev, self.lib, self._keep = torch.device(device), L.lib(), []
-        self.pairs = {"f32": 0, "f16pair": 1, "f16pair_w8": 2, "mx8": 3, "f16": 4}[precision]
+        self.pairs = CODEC_PRECISIONS[precision]
         self.c7, self.c1 = L.Conv(), L.Conv()
         CodecEngine._pack_conv(self, self.c7, w7.float(), b7.float(), dilation, 1)
         CodecEngine._pack_conv(self, self.c1, w1.float(), b1.float(), 1, 1)
@@ -1718,7 +1722,7 @@ def codec_conv_out(w: torch.Tensor, bias: torch.Tensor, x: torch.Tensor, out: to
     activation format of ``precision`` by the entry) -> out (B, L) fp32 = tanh(conv), the caller's tensor."""
     _cuda_contiguous(x, out)
     dev = x.device
-    pairs = {"f32": 0, "f16pair": 1, "f16pair_w8": 2, "mx8": 3, "f16": 4}[precision]
+    pairs = CODEC_PRECISIONS[precision]
     B, Ln, Cc = x.shape
     cv = L.Conv()
     wl = w.float()[0].t().contiguous().to(dev)          # [7][C]
