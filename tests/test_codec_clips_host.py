@@ -234,7 +234,7 @@ def cpu_model(tmp_path_factory):
 class Calls:
     def __init__(self, m, monkeypatch, tokens):
         self.decode, self.decode_clips, self.encode, self.encode_clips = [], [], [], []
-        monkeypatch.setattr(m, "generate_tokens", lambda **kw: tokens)
+        monkeypatch.setattr(m, "_generate_tokens", lambda *a, **kw: tokens)      # what generate() runs behind its host stage
         monkeypatch.setattr(m.sampler, "engine", lambda: type("E", (), {"dev": torch.device("cpu")})())
         monkeypatch.setattr(m.audio_encoder, "decode", lambda codes: self.decode.append(codes) or torch.zeros(codes[0][0].shape[0], 1, 512 * codes[0][0].shape[-1]))
         monkeypatch.setattr(m.audio_encoder, "decode_clips",

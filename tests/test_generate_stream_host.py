@@ -91,7 +91,7 @@ class Untouchable:
 def bare_engine(near_tie="report"):
     eng = object.__new__(DecoderEngine)      # no __init__: no library, no device
     eng.near_tie = near_tie
-    for name in ("prepare", "run", "set_condition", "start_sequence", "_begin_sequence", "_codes_stream"):
+    for name in ("prepare", "run", "set_condition", "start_sequence", "_begin_sequence", "_codes_stream", "_finish_sequence", "_status_fallback"):
         setattr(eng, name, Untouchable())
     return eng
 

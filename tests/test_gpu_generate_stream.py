@@ -342,3 +342,52 @@ def test_status_after_a_block_raises_with_what_has_left(engine, monkeypatch):
     monkeypatch.undo()
     assert torch.equal(engine.generate_codes(feats, 43), run_stream(engine, feats)[1])      # the engine is reusable
     engine.check_status()
+
+
+def status_once(eng, monkeypatch, st):
+    """the next check_status of `eng` reads (and clears) the true word, then raises the error of status word `st`; later ones are the real ones"""
+    real, done = eng.check_status, []
+
+    def fake():
+        real()
+        if not done:
+            done.append(st)
+            raise DecoderEngine._status_error(st)
+    monkeypatch.setattr(eng, "check_status", fake)
+
+
+def fallback_warnings(w):
+    return [str(x.message) for x in w if "separate launches" in str(x.message) or "exact-fp32 twin" in str(x.message)]
+
+
+def test_checked_call_and_stream_share_one_fallback(engine, tiny_sampler_sd, monkeypatch):
+    """generate_codes_checked and the stream leave a dirty status word through ONE method (DecoderEngine._status_fallback): the same
+    switches, counters and warning texts.  The status is faked on the host (check_status / _stream_status), the device word stays clean."""
+    feats = synth.video_features(2, tokens=TV, seed=31).to(DEV)
+    want = engine.generate_codes(feats, 43).clone()
+    engine.check_status()
+    texts = {}
+    for st, word in ((2, "separate launches"), (1, "exact-fp32 twin")):
+        status_once(engine, monkeypatch, st)
+        with warnings.catch_warnings(record=True) as w:
+            warnings.simplefilter("always")
+            got = engine.generate_codes_checked(feats, 43)
+        texts[st] = fallback_warnings(w)
+        assert len(texts[st]) == 1 and word in texts[st][0], texts[st]                   # the one warning, once
+        if st == 2:                                                                      # this engine again, on the separate launches
+            assert torch.equal(got, want) and engine.one_launch_mlp is False and engine.handoff_fallbacks == 1 and engine.range_fallbacks == 0
+        else:                                                                            # the twin's tokens
+            assert engine.range_fallbacks == 1 and engine.handoff_fallbacks == 1
+            assert torch.equal(got, engine._twin().generate_codes(feats, 43))
+    engine.check_status()
+    assert torch.equal(engine.generate_codes_checked(feats, 43), want) and engine.range_fallbacks == 1      # a clean call: no fallback
+    # the stream of a fresh engine of the same model under the same faked status: the checked path's texts, word for word
+    fresh = DecoderEngine(synth.tiny_sampler(2), tiny_sampler_sd, DEV, wdtype="h1")
+    for st in (2, 1):
+        status_at(fresh, monkeypatch, 0, st)
+        with warnings.catch_warnings(record=True) as w:
+            warnings.simplefilter("always")
+            run_stream(fresh, feats)
+        assert fallback_warnings(w) == texts[st]
+    assert fresh.one_launch_mlp is False and fresh.handoff_fallbacks == 1 and fresh.range_fallbacks == 1
+    fresh.check_status()

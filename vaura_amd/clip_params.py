@@ -7,8 +7,11 @@ the scalar call it always was.
 """
 from __future__ import annotations
 
+import functools
+import inspect
 import struct
-from typing import Dict, List, Optional
+from dataclasses import dataclass
+from typing import Dict, List, Optional, Sequence, Union
 
 NAMES = ("use_sampling", "temp", "top_k", "top_p", "cfg_scale")
 _CAST = {"use_sampling": lambda v: int(bool(v)), "temp": float, "top_k": int, "top_p": float, "cfg_scale": float}
@@ -280,6 +283,77 @@ def prompt_row_steps(prompt_lengths: List[int], first_delay: int, cfg: bool = Fa
     for the null-condition rows."""
     n = [int(p) + int(first_delay) for p in prompt_lengths for _ in range(int(num_candidates))]
     return n + n if cfg else n
+
+
+# ---- one ``DecoderEngine.generate_codes`` call with every host argument resolved: what ``generate_codes`` and ``generate_codes_stream``
+# both start from, and what the engine's private methods take instead of the arguments one by one.  No tensor, no device.
+@dataclass(frozen=True)
+class CodesCall:
+    batch: int                              # B clips of the features; the decoder runs batch * num_candidates rows (x 2 with cfg_on)
+    n_video_tokens: int                     # Tv of the features
+    num_candidates: int                     # N: candidate j of clip b is row b * N + j
+    t_max: int                              # the call runs to the longest clip
+    lengths: Optional[List[int]]            # T_b per row (None: every row has t_max)
+    tv_lengths: Optional[List[int]]         # Tv_b per row (None: every row has n_video_tokens)
+    P: Optional[List[int]]                  # P_b per row, at least two distinct values (None: one prompt length, ``prompt_frames``)
+    prompt_frames: int                      # the call's prompt is ``prompt[..., :prompt_frames]``; 0: no prompt
+    cfg_on: bool                            # the null-condition rows are carried
+    use_sampling: Union[bool, List]         # the five sampling values: a scalar, or one plain value per row
+    temp: Union[float, List]
+    top_k: Union[int, List]
+    top_p: Union[float, List]
+    cfg_scale: Union[float, List]
+    want_logprobs: bool
+    want_relevance: bool
+    tokens_per_frame: int
+    delays: Optional[Sequence[int]]
+    seed: int
+    clip_base: int
+    use_graph: bool
+
+
+@functools.lru_cache(maxsize=None)
+def _codes_signature() -> inspect.Signature:
+    """The signature of ``DecoderEngine.generate_codes``: its keyword defaults are written there and nowhere else."""
+    from .engine import DecoderEngine
+    return inspect.signature(DecoderEngine.generate_codes)
+
+
+def resolve_codes_call(batch: int, n_video_tokens: int, max_new_tokens, prompt_frames: Optional[int] = None, **kw) -> CodesCall:
+    """The checks and the resolution of one ``generate_codes`` call, before any device work.  ``batch``, ``n_video_tokens``: the shape
+    of the features; ``prompt_frames``: the last dimension of the prompt tensor (None: no prompt); ``kw``: the keywords of
+    ``generate_codes`` (its two tensors, ``prompt`` and ``noise``, are not read) — one it does not have is a TypeError, one left out
+    takes the default of its signature.  Lengths that disagree with the batch, with each other or with the prompt raise ``VauraHipError``."""
+    a = _codes_signature().bind(None, None, max_new_tokens, **kw)
+    a.apply_defaults()
+    a = a.arguments
+    B, N = batch, a["num_candidates"]
+    if isinstance(N, bool) or not isinstance(N, int) or N < 1:
+        raise _error(f"num_candidates must be an int >= 1, got {N!r}")
+    sampling = {n: a[n] for n in NAMES}
+    check_lengths(B, **sampling)
+    prompt_lengths = a["prompt_lengths"]
+    t_max, lengths, tv_lengths = resolve_lengths(B, max_new_tokens, a["video_lengths"], n_video_tokens,
+                                                 0 if (prompt_frames is None or prompt_lengths is not None) else int(prompt_frames))
+    P = resolve_prompt_lengths(B, prompt_lengths, prompt_frames, t_max, lengths)
+    prompt_frames = int(prompt_frames or 0)
+    if P is not None and len(set(P)) == 1:      # one length after all: the scalar call with prompt[..., :P], on its path
+        prompt_frames, P = P[0], None
+    if N > 1:                                   # candidate j of clip b is row b * N + j: it has clip b's lengths and values
+        lengths, tv_lengths, P = (repeat(v, N) if v is not None else None for v in (lengths, tv_lengths, P))
+    cfg_on = any_cfg(sampling["cfg_scale"])     # some clip mixes: the whole batch carries the null-condition rows
+    sampling = {n: repeat(v, N) if is_per_clip(v) else _scalar(v) for n, v in sampling.items()}
+    want_relevance = bool(a["return_relevance"])
+    if want_relevance and not cfg_on:
+        # relevance reads the null rows: carry them, and keep every clip un-mixed through its record (the scalar cfg_scale of the
+        # call's vaura_sampling then only says that the rows exist)
+        cfg_on = True
+        if not is_per_clip(sampling["cfg_scale"]):
+            sampling["cfg_scale"] = [float(sampling["cfg_scale"])] * (B * N)
+    return CodesCall(batch=B, n_video_tokens=n_video_tokens, num_candidates=N, t_max=t_max, lengths=lengths, tv_lengths=tv_lengths, P=P,
+                     prompt_frames=prompt_frames, cfg_on=cfg_on, want_logprobs=bool(a["return_logprobs"]), want_relevance=want_relevance,
+                     tokens_per_frame=a["tokens_per_frame"], delays=a["delays"], seed=a["seed"], clip_base=a["clip_base"],
+                     use_graph=a["use_graph"], **sampling)
 
 
 # ---- audio out of one generate() call while its decode loop still runs (DecoderEngine.generate_codes_stream): which frames may leave

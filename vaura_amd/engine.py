@@ -756,75 +756,61 @@ class DecoderEngine:
         plus sum_g (P_g + d_0) prefill positions.  Lengths that are all equal are the scalar call with ``prompt[..., :P]``, on its path.
         An explicit ``noise`` starts at the shortest prompt's first step and is not comparable, as above."""
         B, Tv, _ = feats.shape
-        N = num_candidates
-        if isinstance(N, bool) or not isinstance(N, int) or N < 1:
-            raise L.VauraHipError(f"num_candidates must be an int >= 1, got {N!r}")
-        clip_params.check_lengths(B, use_sampling=use_sampling, temp=temp, top_k=top_k, top_p=top_p, cfg_scale=cfg_scale)
-        t_max, lengths, tv_lengths = clip_params.resolve_lengths(B, max_new_tokens, video_lengths, Tv,
-                                                                 0 if (prompt is None or prompt_lengths is not None) else int(prompt.shape[-1]))
-        P = clip_params.resolve_prompt_lengths(B, prompt_lengths, None if prompt is None else int(prompt.shape[-1]), t_max, lengths)
-        if P is not None and len(set(P)) == 1:      # one length after all: the scalar call with that prompt, on its path
-            prompt, P = (prompt[..., :P[0]] if P[0] else None), None
-        if N > 1:                          # candidate j of clip b is row b * N + j: it has clip b's lengths
-            lengths, tv_lengths, P = (clip_params.repeat(v, N) if v is not None else None for v in (lengths, tv_lengths, P))
-        cfg_on = clip_params.any_cfg(cfg_scale)     # some clip mixes: the whole batch carries the null-condition rows
-        if N > 1:
-            use_sampling, temp, top_k, top_p, cfg_scale = (clip_params.repeat(v, N) for v in (use_sampling, temp, top_k, top_p, cfg_scale))
-            if prompt is not None:
-                prompt = prompt.repeat_interleave(N, dim=0)
-        if return_relevance and not cfg_on:
-            # relevance reads the null rows: carry them, and keep every clip un-mixed through its record (the scalar cfg_scale of the
-            # call's vaura_sampling then only says that the rows exist)
-            cfg_on = True
-            if not clip_params.is_per_clip(cfg_scale):
-                cfg_scale = [float(clip_params._scalar(cfg_scale))] * (B * N)
-        K = self.cfg.num_codebooks
-        self._fc = None                       # the K/V cache is about to be reused: forward_cached must start over
+        call = clip_params.resolve_codes_call(
+            B, Tv, max_new_tokens, None if prompt is None else int(prompt.shape[-1]), use_sampling=use_sampling, temp=temp, top_k=top_k,
+            top_p=top_p, cfg_scale=cfg_scale, seed=seed, clip_base=clip_base, use_graph=use_graph, tokens_per_frame=tokens_per_frame,
+            delays=delays, return_logprobs=return_logprobs, num_candidates=num_candidates, return_relevance=return_relevance,
+            video_lengths=video_lengths, prompt_lengths=prompt_lengths)
         with off_null_stream(self.dev) as caller:
-            Tp, start, plan, sp, noise = self._begin_sequence(feats, N, t_max, lengths, tv_lengths, P, cfg_on, tokens_per_frame, delays, prompt,
-                                                              use_sampling, temp, top_k, top_p, cfg_scale, seed, clip_base, noise,
-                                                              return_logprobs, return_relevance)
-            self.run(start - 1, self.S - start, sp, noise, use_graph, plan)
-            out = self.revert().to(torch.int64)
-            extra = self._sequence_logprobs(Tp) if return_logprobs else None
-            if return_relevance:
-                extra = dict(extra or {}, **self._sequence_relevance(Tp))
-        if caller is not None:
-            out.record_stream(caller)
-            for t in (extra or {}).values():
-                t.record_stream(caller)
-        return (out, extra) if (return_logprobs or return_relevance) else out
+            Tp, start, plan, sp, noise = self._begin_sequence(call, feats, prompt, noise)
+            self.run(start - 1, self.S - start, sp, noise, call.use_graph, plan)
+            return self._finish_sequence(call, Tp, caller)
 
-    def _begin_sequence(self, feats, N, t_max, lengths, tv_lengths, P, cfg_on, tokens_per_frame, delays, prompt, use_sampling, temp, top_k,
-                        top_p, cfg_scale, seed, clip_base, noise, return_logprobs, return_relevance):
-        """Everything of a ``generate_codes`` call in front of its loop, on resolved arguments, enqueued on the current stream: the
+    def _begin_sequence(self, call: clip_params.CodesCall, feats, prompt, noise):
+        """Everything of a ``generate_codes`` call in front of its loop, on the resolved call, enqueued on the current stream: the
         prepared shape, the per-clip arrays, the condition, the pattern sequence, the sampling struct, and the log-probability /
         relevance buffers -> (Tp, first sampled step, prompt plan or None, vaura_sampling, noise on the device or None)."""
-        B, Tv, _ = feats.shape
-        K = self.cfg.num_codebooks
-        self.prepare(B * N, t_max, Tv, cfg_on, tokens_per_frame, block_size=self.cfg.block_size, delays=delays)
-        self._set_lengths(lengths, tv_lengths)
-        self._set_prompt_lengths(P)
+        N, K = call.num_candidates, self.cfg.num_codebooks
+        prompt = prompt[..., :call.prompt_frames] if call.prompt_frames else None
+        if prompt is not None and N > 1:
+            prompt = prompt.repeat_interleave(N, dim=0)
+        self.prepare(call.batch * N, call.t_max, call.n_video_tokens, call.cfg_on, call.tokens_per_frame, self.cfg.block_size, call.delays)
+        self._set_lengths(call.lengths, call.tv_lengths)
+        self._set_prompt_lengths(call.P)
         self.set_condition(feats, replicate=N)
         Tp = self.start_sequence(prompt)       # per-clip prompt lengths: the shortest — where the loop starts sampling
         start = Tp + 1 + (self.delays[0] if self.delays else 0)  # Pattern.get_first_step_with_timesteps(Tp), sorted delays
-        plan = None if P is None else clip_params.prompt_schedule(P, self.delays[0] if self.delays else 0, self.S, self.rows == 2 * self.batch)
-        sp = self._sampling(use_sampling, temp, top_k, top_p, cfg_scale, seed, clip_base)
+        plan = None if call.P is None else clip_params.prompt_schedule(call.P, self.delays[0] if self.delays else 0, self.S,
+                                                                       self.rows == 2 * self.batch)
+        sp = self._sampling(call.use_sampling, call.temp, call.top_k, call.top_p, call.cfg_scale, call.seed, call.clip_base)
         if noise is not None:
             noise = noise.to(self.dev, torch.float32).contiguous()
-            assert noise.shape == (self.S - start, B * N * K, self.cfg.d_codebook), noise.shape
-        if return_logprobs:
+            assert noise.shape == (self.S - start, call.batch * N * K, self.cfg.d_codebook), noise.shape
+        if call.want_logprobs:
             self.logprobs.zero_()         # slots the sampler does not fill (prompt, special) read 0
-        self.dec.logprobs = L.ptr(self.logprobs) if return_logprobs else 0
-        if return_relevance:
+        self.dec.logprobs = L.ptr(self.logprobs) if call.want_logprobs else 0
+        if call.want_relevance:
             if self.logprobs_cond is None:
                 self.logprobs_cond, self.logprobs_null = torch.zeros_like(self.logprobs), torch.zeros_like(self.logprobs)
             else:
                 self.logprobs_cond.zero_()
                 self.logprobs_null.zero_()
-        self.dec_ext.logprobs_cond = L.ptr(self.logprobs_cond) if return_relevance else 0
-        self.dec_ext.logprobs_null = L.ptr(self.logprobs_null) if return_relevance else 0
+        self.dec_ext.logprobs_cond = L.ptr(self.logprobs_cond) if call.want_relevance else 0
+        self.dec_ext.logprobs_null = L.ptr(self.logprobs_null) if call.want_relevance else 0
         return Tp, start, plan, sp, noise
+
+    def _finish_sequence(self, call: clip_params.CodesCall, Tp: int, caller):
+        """The end of a call whose loop is enqueued, on the current stream: the revert, the log-probabilities and the relevance that
+        were asked for, all handed to the ``caller`` stream (``off_null_stream``) -> what ``generate_codes`` returns."""
+        out = self.revert().to(torch.int64)
+        extra = self._sequence_logprobs(Tp) if call.want_logprobs else None
+        if call.want_relevance:
+            extra = dict(extra or {}, **self._sequence_relevance(Tp))
+        if caller is not None:
+            out.record_stream(caller)
+            for t in (extra or {}).values():
+                t.record_stream(caller)
+        return (out, extra) if (call.want_logprobs or call.want_relevance) else out
 
     def _revert_f32(self, buf: torch.Tensor) -> torch.Tensor:
         """fp32 values in the layout of seq -> (batch, K, T), 0 where the sequence holds no frame."""
@@ -864,38 +850,44 @@ class DecoderEngine:
         try:
             self.check_status()
         except L.VauraHipError as e:
-            st = getattr(e, "status", 0)
-            if (st & 2) and self.one_launch_mlp:
-                # A consumer of the one-launch MLP gave up waiting: its 256 workgroups were not all resident — the GPU is shared
-                # (another process / tenant, a CU mask, a second engine on another stream).  Not an error of the model: switch THIS
-                # engine to the separate launches for good (no in-launch hand-off, nothing to starve; same bits) and run the call again.
-                import warnings
-                warnings.warn("vaura_amd: the one-launch MLP's in-launch hand-off timed out (GPU shared?); this engine now uses the "
-                              "separate launches (slower by 5-7 %, same results)")
-                self.one_launch_mlp = False
-                self.handoff_fallbacks += 1
-                if self.dec is not None:
-                    self.dec.ws_sync = 0
-                self._free_graph()
-                return self.generate_codes_checked(feats, max_new_tokens, **kw)
-            if st != 1 or self.wdtype == "f32" or self._twin_sd is None:       # nothing wider to fall back to
-                raise
-            if self.range_fallbacks == 0:
-                import warnings
-                warnings.warn("vaura_amd: an activation left the fp16-plane range (non-finite logits at the sampler); this call is re-run "
-                              "on the exact-fp32 twin engine (1.5 x slower, ~2.7 GB more)"
-                              + (" — built from the DEQUANTISED matrices this lossy storage holds" if self._twin_lossy else "")
-                              + ".  A checkpoint that does this on every call wants plane_shift=4..8 or weight_dtype='f32'")
-            self.range_fallbacks += 1
-            codes = self._twin().generate_codes(feats, max_new_tokens, **kw)
-            self._range_twin.check_status()
-            return codes
+            eng = self._status_fallback(getattr(e, "status", 0), e)
+            return self.generate_codes_checked(feats, max_new_tokens, **kw) if eng is self else self._on_twin(feats, max_new_tokens, kw)
         if self.near_tie == "rerun" and self.last_near_ties[0] > 0 and self.wdtype != "f32" and self._twin_sd is not None:
             # >= 1 used decision of this call was inside the plane arithmetic's noise: the same call on the exact-fp32 twin, same noise
             self.near_tie_reruns += 1
-            codes = self._twin().generate_codes(feats, max_new_tokens, **kw)
-            self._range_twin.check_status()
+            codes = self._on_twin(feats, max_new_tokens, kw)
         return codes
+
+    def _on_twin(self, feats, max_new_tokens, kw):
+        codes = self._twin().generate_codes(feats, max_new_tokens, **kw)
+        self._range_twin.check_status()
+        return codes
+
+    def _status_fallback(self, st: int, err) -> "DecoderEngine":
+        """What a call whose status word ``st`` gave the error ``err`` is run on again: this engine, switched to the separate launches
+        (``handoff_fallbacks``), or the exact-fp32 twin (``range_fallbacks``).  Where neither helps, ``err`` is raised."""
+        import warnings
+        if (st & 2) and self.one_launch_mlp:
+            # A consumer of the one-launch MLP gave up waiting: its 256 workgroups were not all resident — the GPU is shared
+            # (another process / tenant, a CU mask, a second engine on another stream).  Not an error of the model: switch THIS
+            # engine to the separate launches for good (no in-launch hand-off, nothing to starve; same bits) and run the call again.
+            warnings.warn("vaura_amd: the one-launch MLP's in-launch hand-off timed out (GPU shared?); this engine now uses the "
+                          "separate launches (slower by 5-7 %, same results)")
+            self.one_launch_mlp = False
+            self.handoff_fallbacks += 1
+            if self.dec is not None:
+                self.dec.ws_sync = 0
+            self._free_graph()
+            return self
+        if st != 1 or self.wdtype == "f32" or self._twin_sd is None:       # nothing wider to fall back to
+            raise err
+        if self.range_fallbacks == 0:
+            warnings.warn("vaura_amd: an activation left the fp16-plane range (non-finite logits at the sampler); this call is re-run "
+                          "on the exact-fp32 twin engine (1.5 x slower, ~2.7 GB more)"
+                          + (" — built from the DEQUANTISED matrices this lossy storage holds" if self._twin_lossy else "")
+                          + ".  A checkpoint that does this on every call wants plane_shift=4..8 or weight_dtype='f32'")
+        self.range_fallbacks += 1
+        return self._twin()
 
     # ------------------------------------------------------------------ the loop in pieces: frames leave while it still runs
     def generate_codes_stream(self, feats: torch.Tensor, max_new_tokens, *, block_frames: int = 16, halo: int = 0, **kw):
@@ -920,27 +912,24 @@ class DecoderEngine:
         Refused here, before the engine is touched: ``num_candidates`` > 1 (the winner is known only at the end), more than one distinct
         ``prompt_lengths`` value (that path interleaves prefill passes with the loop; not served by this version), ``near_tie="rerun"``
         (it decides at the end of the call), and a ``block_frames`` that is no positive int."""
+        B, Tv, _ = feats.shape
+        prompt, noise = kw.pop("prompt", None), kw.pop("noise", None)
+        call = clip_params.resolve_codes_call(B, Tv, max_new_tokens, None if prompt is None else int(prompt.shape[-1]), **kw)
         clip_params.check_block_frames(block_frames)
-        if kw.get("num_candidates", 1) != 1:
+        if call.num_candidates != 1:
             raise L.VauraHipError("streaming takes num_candidates = 1: the winning candidate is known only at the end of the call")
         if self.near_tie == "rerun":
             raise L.VauraHipError('streaming is refused on an engine with near_tie="rerun": the re-run is decided at the end of the call, '
                                   'after audio has left (use "report" or "off")')
         if isinstance(halo, bool) or not isinstance(halo, int) or halo < 0:
             raise L.VauraHipError(f"halo must be a non-negative number of frames, got {halo!r}")
-        B, Tv, _ = feats.shape
-        prompt, prompt_lengths = kw.get("prompt"), kw.get("prompt_lengths")
-        clip_params.check_lengths(B, **{n: kw[n] for n in clip_params.NAMES if n in kw})
-        t_max, lengths, tv_lengths = clip_params.resolve_lengths(B, max_new_tokens, kw.get("video_lengths"), Tv,
-                                                                 0 if (prompt is None or prompt_lengths is not None) else int(prompt.shape[-1]))
-        P = clip_params.resolve_prompt_lengths(B, prompt_lengths, None if prompt is None else int(prompt.shape[-1]), t_max, lengths)
-        if P is not None and len(set(P)) > 1:
-            raise L.VauraHipError(f"streaming takes one prompt length for the call, got prompt_lengths {P}: distinct lengths interleave "
+        if call.P is not None:
+            raise L.VauraHipError(f"streaming takes one prompt length for the call, got prompt_lengths {call.P}: distinct lengths interleave "
                                   "prefill passes with the loop and are not served by this version")
-        Tp = 0 if prompt is None else (P[0] if P is not None else int(prompt.shape[-1]))
-        if Tp >= (min(lengths) if lengths else t_max):
-            raise L.VauraHipError(f"the audio prompt ({Tp} frames) must be shorter than max_new_tokens ({lengths or t_max})")
-        return self._codes_stream(feats, max_new_tokens, int(block_frames), int(halo), (t_max, lengths, tv_lengths, P), dict(kw))
+        if call.prompt_frames >= (min(call.lengths) if call.lengths else call.t_max):
+            raise L.VauraHipError(f"the audio prompt ({call.prompt_frames} frames) must be shorter than max_new_tokens "
+                                  f"({call.lengths or call.t_max})")
+        return self._codes_stream(call, feats, prompt, noise, int(block_frames), int(halo))
 
     def _stream_status(self, words: torch.Tensor) -> int:
         """Bits 1 | 2 of the state words a piece left in pinned memory (its event has been waited for), with what ``prepare`` carried over."""
@@ -961,28 +950,13 @@ class DecoderEngine:
         return torch.where(t[None, None, :] < cnt[:, None, None], got, torch.full_like(got, fill))
 
     @torch.no_grad()
-    def _codes_stream(self, feats, max_new_tokens, block_frames, halo, resolved, kw):
-        t_max, lengths, tv_lengths, P = resolved
+    def _codes_stream(self, call: clip_params.CodesCall, feats, prompt, noise, block_frames: int, halo: int):
         self.stream_engine = self              # whose seq / per-token buffers the yielded ranges refer to (the twin after a range fallback)
-        prompt = kw.get("prompt")
-        if P is not None:                      # one length after all: the scalar call with that prompt
-            prompt = prompt[..., :P[0]] if P[0] else None
-        g = lambda name, default: kw.get(name, default)
-        cfg_scale, want_lp, want_rel, use_graph = g("cfg_scale", 1.0), bool(g("return_logprobs", False)), bool(g("return_relevance", False)), g("use_graph", True)
-        cfg_on = clip_params.any_cfg(cfg_scale)
-        B = feats.shape[0]
-        if want_rel and not cfg_on:            # as generate_codes: relevance reads the null rows
-            cfg_on = True
-            if not clip_params.is_per_clip(cfg_scale):
-                cfg_scale = [float(clip_params._scalar(cfg_scale))] * B
-        self._fc = None
         if getattr(self, "_stream_pinned", None) is None:      # the state words of the two pieces in flight, on the host
             self._stream_pinned = [torch.zeros(8, dtype=torch.int32).pin_memory() for _ in range(2)]
         pinned = self._stream_pinned
         with off_null_stream(self.dev):
-            Tp, start, _, sp, noise = self._begin_sequence(
-                feats, 1, t_max, lengths, tv_lengths, None, cfg_on, g("tokens_per_frame", 7), g("delays", None), prompt, g("use_sampling", False),
-                g("temp", 1.0), g("top_k", 0), g("top_p", 0.0), cfg_scale, g("seed", 0), g("clip_base", 0), g("noise", None), want_lp, want_rel)
+            Tp, start, _, sp, dev_noise = self._begin_sequence(call, feats, prompt, noise)
             pieces = clip_params.stream_schedule(self.T, self.lengths, start, self.delays, halo, block_frames, self.cfg.num_codebooks)
             if self.lengths is None:           # one length: every clip of the batch has the one range
                 pieces = [(n, r * self.batch) for n, r in pieces]
@@ -990,7 +964,7 @@ class DecoderEngine:
             events = []
 
             def enqueue(k):                    # piece k, its state words behind it, its event behind those
-                self.run(start - 1 if k == 0 else 0, pieces[k][0], sp, noise, use_graph)
+                self.run(start - 1 if k == 0 else 0, pieces[k][0], sp, dev_noise, call.use_graph)
                 pinned[k % 2].copy_(self.state, non_blocking=True)
                 events.append(torch.cuda.Event())
                 events[-1].record(torch.cuda.current_stream(self.dev))
@@ -1011,42 +985,17 @@ class DecoderEngine:
                     err.frames_emitted = list(emitted)
                     err.args = (f"{err.args[0]} — after frames {emitted} of the clips had been streamed out: they cannot be taken back",)
                     raise err
-                return (yield from self._stream_fallback(err, st, feats, max_new_tokens, block_frames, halo, resolved, kw))
+                # before any frame has left: ``generate_codes_checked``'s two ways out, as a stream.  Whoever reads seq / the per-token
+                # buffers of the running stream reads those of the engine it continues on
+                self.stream_engine = self._status_fallback(st, err)
+                return (yield from self.stream_engine._codes_stream(call, feats, prompt, noise, block_frames, halo))
             if any(hi > lo for lo, hi in ranges):
                 yield list(ranges)
                 emitted = [hi for _, hi in ranges]
         with off_null_stream(self.dev) as caller:
-            out = self.revert().to(torch.int64)
-            extra = self._sequence_logprobs(Tp) if want_lp else None
-            if want_rel:
-                extra = dict(extra or {}, **self._sequence_relevance(Tp))
-        if caller is not None:
-            out.record_stream(caller)
-            for t in (extra or {}).values():
-                t.record_stream(caller)
+            result = self._finish_sequence(call, Tp, caller)
         self.check_status()                    # the near-tie counters of the call (informational); the loop's bits were read piece by piece
-        return (out, extra) if (want_lp or want_rel) else out
-
-    def _stream_fallback(self, err, st, feats, max_new_tokens, block_frames, halo, resolved, kw):
-        """A dirty status word before any frame has left: ``generate_codes_checked``'s two ways out, as a stream."""
-        import warnings
-        if (st & 2) and self.one_launch_mlp:
-            warnings.warn("vaura_amd: the one-launch MLP's in-launch hand-off timed out (GPU shared?); this engine now uses the "
-                          "separate launches (slower by 5-7 %, same results)")
-            self.one_launch_mlp = False
-            self.handoff_fallbacks += 1
-            if self.dec is not None:
-                self.dec.ws_sync = 0
-            self._free_graph()
-            return (yield from self._codes_stream(feats, max_new_tokens, block_frames, halo, resolved, kw))
-        if st != 1 or self.wdtype == "f32" or self._twin_sd is None:       # nothing wider to fall back to
-            raise err
-        if self.range_fallbacks == 0:
-            warnings.warn("vaura_amd: an activation left the fp16-plane range (non-finite logits at the sampler); this call is re-run "
-                          "on the exact-fp32 twin engine (1.5 x slower, ~2.7 GB more)")
-        self.range_fallbacks += 1
-        self.stream_engine = self._twin()      # whoever reads seq / the per-token buffers of the running stream reads the twin's
-        return (yield from self.stream_engine._codes_stream(feats, max_new_tokens, block_frames, halo, resolved, kw))
+        return result
 
     # ------------------------------------------------------------------ the reference host's call pattern, with a cache
     def forward_cached(self, idx: torch.Tensor, feats: torch.Tensor, tokens_per_frame: int = 7) -> torch.Tensor:

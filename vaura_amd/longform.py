@@ -182,6 +182,35 @@ def generate_long_stream(model, frames: torch.Tensor, duration: float, *, emit_c
     return _long_stream(model, frames, sched, int(COMPRESSION_MODEL_FRAME_RATE * stride), frame_step, kw, return_relevance, emit_chunks)
 
 
+class _Held:
+    """The frames of a long-form stream that are final and not yet dropped, [start, start + held), with their relevance values, and
+    how many have been emitted: emitted - halo >= start, so the halo in front of the next block is always at hand."""
+
+    def __init__(self, model, return_relevance):
+        self.model, self.return_relevance = model, return_relevance
+        self.tok, self.rel, self.start, self.emitted = [], {k: [] for k in REL}, 0, 0
+
+    def add(self, tok, rel):
+        self.tok.append(tok)
+        for k, v in rel.items():
+            self.rel[k].append(v)
+
+    def release(self, upto: int, final: bool) -> dict:
+        """The block of the frames [emitted, upto): ONE ``decode_window`` pass over them and their halo; one halo stays held."""
+        H, K, at = _decode_halo(self.model), self.model.num_codebooks, self.start
+        tok = torch.cat(self.tok, dim=-1)
+        rel = {k: torch.cat(v, dim=-1) for k, v in self.rel.items()} if self.return_relevance else {}
+        B, n = tok.shape[0], upto - self.emitted
+        audio = self.model.audio_encoder.decode_window(tok[..., :K, :], [self.emitted - at] * B, [n] * B)
+        blk = {"audio": audio, "start_frame": self.emitted, "frames": n, "sampled_indices": tok[..., self.emitted - at:upto - at],
+               "final": final, **{k: v[..., self.emitted - at:upto - at] for k, v in rel.items()}}
+        self.emitted = upto
+        self.start = max(at, upto - H)                                      # the halo in front of the next block stays
+        self.tok = [tok[..., self.start - at:]]
+        self.rel = {k: [rel[k][..., self.start - at:]] if self.return_relevance else [] for k in REL}
+        return blk
+
+
 @torch.no_grad()
 def _long_stream(model, frames, sched, stride_tokens, frame_step, kw, return_relevance, emit_chunks):
     if len(sched) == 1 and sched[0]["positions"] is None:
@@ -191,36 +220,21 @@ def _long_stream(model, frames, sched, stride_tokens, frame_step, kw, return_rel
         yield {"audio": item["generated_audio"], "start_frame": 0, "frames": int(item["sampled_indices"].shape[-1]),
                "sampled_indices": item["sampled_indices"], "final": True, **({k: item[k] for k in REL} if return_relevance else {})}
         return
-    H, K = _decode_halo(model), model.num_codebooks
-    held, held_rel, held_from, emitted = [], {k: [] for k in REL}, 0, 0     # generated and not yet emitted: frames [held_from, N_c)
+    H, held = _decode_halo(model), _Held(model, return_relevance)            # generated and not yet emitted: frames [held.start, N_c)
     for c, (ch, new, new_rel) in enumerate(_long_chunks(model, frames, sched, stride_tokens, frame_step, kw, return_relevance)):
-        held.append(new)
-        for k, v in new_rel.items():
-            held_rel[k].append(v)
+        held.add(new, new_rel)
         final = c + 1 == len(sched)
         N = ch["offset"] + ch["max_gen_len"]
         upto = N if final else N - H
-        if not final and ((c + 1) % emit_chunks or upto <= emitted):
-            continue
-        tok = torch.cat(held, dim=-1)                                       # frames [held_from, N): held_from <= emitted - H
-        rel = {k: torch.cat(v, dim=-1) for k, v in held_rel.items()} if return_relevance else {}
-        B, n = tok.shape[0], upto - emitted
-        audio = model.audio_encoder.decode_window(tok[..., :K, :], [emitted - held_from] * B, [n] * B)
-        yield {"audio": audio, "start_frame": emitted, "frames": n, "sampled_indices": tok[..., emitted - held_from:upto - held_from],
-               "final": final, **{k: v[..., emitted - held_from:upto - held_from] for k, v in rel.items()}}
-        emitted = upto
-        keep = max(held_from, emitted - H)                                  # the halo in front of the next block stays
-        held = [tok[..., keep - held_from:]]
-        held_rel = {k: [rel[k][..., keep - held_from:]] if return_relevance else [] for k in REL}
-        held_from = keep
+        if final or not ((c + 1) % emit_chunks or upto <= held.emitted):
+            yield held.release(upto, final)
 
 
 @torch.no_grad()
 def _long_stream_blocks(model, frames, sched, stride_tokens, frame_step, kw, return_relevance, block_frames):
     """``_long_stream`` with audio leaving inside the chunks (``generate_long_stream(block_frames=...)``)."""
-    H, K = _decode_halo(model), model.num_codebooks
+    H, held = _decode_halo(model), _Held(model, return_relevance)            # final and not yet dropped: frames [held.start, known)
     skw = {k: v for k, v in kw.items() if k not in ("return_sampled_indices", "remove_prompts")}      # generate_stream has neither
-    held, held_rel, held_from, emitted = [], {k: [] for k in REL}, 0, 0     # final and not yet dropped: frames [held_from, known)
     prompt_tokens = None
     for c, ch in enumerate(sched):
         final = c + 1 == len(sched)
@@ -238,24 +252,12 @@ def _long_stream_blocks(model, frames, sched, stride_tokens, frame_step, kw, ret
             lo, hi = blk["start_frame"], blk["start_frame"] + blk["frames"]
             chunk.append(blk["sampled_indices"])
             if hi > P:                                                      # frames this chunk GENERATED: the others are held already
-                held.append(blk["sampled_indices"][..., max(lo, P) - lo:])
-                for k in (REL if return_relevance else ()):
-                    held_rel[k].append(blk[k][..., max(lo, P) - lo:])
+                held.add(blk["sampled_indices"][..., max(lo, P) - lo:],
+                         {k: blk[k][..., max(lo, P) - lo:] for k in (REL if return_relevance else ())})
             known = off + max(hi, P)
             upto = (known if final else known - H) if hi == T else known - H
-            if upto <= emitted:
-                continue
-            tok = torch.cat(held, dim=-1)                                   # frames [held_from, known): held_from <= emitted - H
-            rel = {k: torch.cat(v, dim=-1) for k, v in held_rel.items()} if return_relevance else {}
-            B, n = tok.shape[0], upto - emitted
-            audio = model.audio_encoder.decode_window(tok[..., :K, :], [emitted - held_from] * B, [n] * B)
-            yield {"audio": audio, "start_frame": emitted, "frames": n, "sampled_indices": tok[..., emitted - held_from:upto - held_from],
-                   "final": final and hi == T, **{k: v[..., emitted - held_from:upto - held_from] for k, v in rel.items()}}
-            emitted = upto
-            keep = max(held_from, emitted - H)                              # the halo in front of the next block stays
-            held = [tok[..., keep - held_from:]]
-            held_rel = {k: [rel[k][..., keep - held_from:]] if return_relevance else [] for k in REL}
-            held_from = keep
+            if upto > held.emitted:
+                yield held.release(upto, final and hi == T)
         prompt_tokens = torch.cat(chunk, dim=-1)[:, :, stride_tokens:]
 
 

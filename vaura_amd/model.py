@@ -18,6 +18,7 @@ What differs from the reference, on purpose:
 """
 from __future__ import annotations
 
+from dataclasses import dataclass
 from typing import Any, List, Optional, Tuple, Union
 
 import torch
@@ -42,6 +43,34 @@ def _plain(o):
                                         and not torch.is_tensor(o)):
         return [_plain(v) for v in o]
     return o
+
+
+@dataclass(frozen=True)
+class _GenerateCall:
+    """One generate() / generate_tokens() / generate_stream() call as its host stage (``VAURAModel._resolve_call``) left it."""
+    N: int                                   # candidates per clip
+    t_max: int                               # the call runs to the longest clip
+    lengths: Optional[List[int]]             # T_b (None: every clip has t_max)
+    tv_lengths: Optional[List[int]]          # video_lengths, checked as far as the host stage can
+    n_segments: Optional[List[int]]          # video_segments, turned into tv_lengths once the features exist
+    delays: List[int]
+    sampling: dict                           # use_sampling, temp, top_k, top_p, cfg_scale: each a scalar or one value per clip
+    prompt_is_encoded: bool
+    prompt_lengths: Any
+    audio_lengths: Any
+    return_logprobs: bool
+    return_relevance: bool
+    by_rel: bool                             # rank_by == "relevance"
+    return_all_candidates: bool
+    want_lp: bool                            # what the engine is asked for: the caller's flag, or the score the candidates are ranked by
+    want_rel: bool
+    remove_prompts: bool
+    check: bool
+
+    @property
+    def ragged(self) -> bool:
+        """Per-clip lengths of any kind: the result is then always a dict with "lengths"."""
+        return any(v is not None for v in (self.lengths, self.tv_lengths, self.n_segments, self.prompt_lengths, self.audio_lengths))
 
 
 class VAURAModel(nn.Module):
@@ -286,9 +315,9 @@ class VAURAModel(nn.Module):
         return N
 
     @staticmethod
-    def _check_prompt_lengths(frames, audio, prompt_is_encoded, prompt_lengths, audio_lengths, t_max, lengths) -> None:
+    def _check_prompt_lengths(batch, audio, prompt_is_encoded, prompt_lengths, audio_lengths, t_max, lengths) -> None:
         """The per-clip prompt keywords of generate() / generate_tokens(), checked on the host alone with what is known before any
-        device work (the batch from the frames, an encoded prompt's frames)."""
+        device work (the batch of the frames, an encoded prompt's frames)."""
         if prompt_lengths is None and audio_lengths is None:
             return
         if prompt_lengths is not None and audio_lengths is not None:
@@ -299,8 +328,90 @@ class VAURAModel(nn.Module):
         if audio_lengths is not None and prompt_is_encoded:
             raise L.VauraHipError("audio_lengths counts the samples of raw audio; an encoded prompt takes prompt_lengths (frames)")
         if prompt_lengths is not None:   # an encoded prompt: everything is known; raw audio: its frames are checked once it is encoded
-            clip_params.resolve_prompt_lengths(frames.shape[0] if hasattr(frames, "shape") else None, prompt_lengths,
-                                               int(audio.shape[-1]) if prompt_is_encoded else t_max, t_max, lengths)
+            clip_params.resolve_prompt_lengths(batch, prompt_lengths, int(audio.shape[-1]) if prompt_is_encoded else t_max, t_max, lengths)
+
+    def _resolve_call(self, frames, audio, max_new_tokens, *, use_sampling, temp, top_k, top_p, cfg_scale, prompt_is_encoded,
+                      return_logprobs, return_relevance, video_lengths, prompt_lengths, audio_lengths, num_candidates=1,
+                      return_all_candidates=False, rank_by="logprob", video_segments=None, return_attention_weights=False,
+                      remove_prompts=False, check=False) -> "_GenerateCall":
+        """The host stage of generate() / generate_tokens() / generate_stream(): everything that is known before any device work —
+        the batch from the frames, an encoded prompt's frames — is checked and resolved here, once per call."""
+        assert not self.training, "do not use generation in training mode"
+        N = self._check_candidates(num_candidates, return_all_candidates, use_sampling, temp, rank_by, return_relevance)
+        batch = frames.shape[0] if hasattr(frames, "shape") else None      # frames carry the batch on dim 0
+        # per-clip parameter sequences of the wrong length, and the per-clip lengths
+        sampling = dict(use_sampling=use_sampling, temp=temp, top_k=top_k, top_p=top_p, cfg_scale=cfg_scale)
+        clip_params.check_lengths(batch, **sampling)
+        per_clip_prompt = prompt_lengths is not None or audio_lengths is not None
+        t_max, lengths, tv_lengths = clip_params.resolve_lengths(
+            batch, max_new_tokens, video_lengths, None,
+            int(audio.shape[-1]) if (audio is not None and prompt_is_encoded and not per_clip_prompt) else 0)
+        self._check_prompt_lengths(batch, audio, prompt_is_encoded, prompt_lengths, audio_lengths, t_max, lengths)
+        n_segments = None if video_segments is None else clip_params.resolve_segments(
+            batch, video_segments, video_lengths, frames.shape[1] if batch is not None and len(frames.shape) > 1 else None,
+            self.flatten_vis_feats, lengths)
+        if return_attention_weights:
+            # the reference's own llama sampler returns (logits, None, None) (llama.py:520-539), so its generate() fails on
+            # `sa_w[-1, -1, :]` (vaura_model.py:529-531) with this flag: there is no behaviour to reproduce
+            raise NotImplementedError("attention-weight dumps are not produced by the fused decode path (nor by the reference's "
+                                      "llama sampler, which returns None for them)")
+        delays = self._pattern_delays(t_max)             # the layout the loop decodes; the call runs to the longest clip
+        block = self.sampler.block_size
+        if delays != list(range(self.num_codebooks)) and t_max + max(delays) + 1 > block:   # (the engine refuses it too, before allocating)
+            raise L.VauraHipError(f"{t_max} timesteps under the delays {delays} need {t_max + max(delays) + 1} sequence "
+                                  f"steps; block_size is {block}")
+        by_rel = rank_by == "relevance"
+        return _GenerateCall(
+            N=N, t_max=t_max, lengths=lengths, tv_lengths=tv_lengths, n_segments=n_segments, delays=delays, sampling=sampling, prompt_is_encoded=prompt_is_encoded,
+            prompt_lengths=prompt_lengths, audio_lengths=audio_lengths, return_logprobs=bool(return_logprobs),
+            return_relevance=bool(return_relevance), by_rel=by_rel, return_all_candidates=return_all_candidates,
+            # candidates are ranked by their sequence log-probability by default
+            want_lp=bool(return_logprobs) or (N > 1 and not by_rel), want_rel=bool(return_relevance) or (N > 1 and by_rel),
+            remove_prompts=remove_prompts, check=check)
+
+    def _bind_call(self, call: "_GenerateCall", frames, audio, clip_indices):
+        """The second stage: the prompt is encoded and the features are extracted, then the call's lengths are resolved again with the
+        batch, the video tokens and the prompt known — still before the engine is touched -> (features, B, Tp, P, lengths, tv_lengths,
+        the keywords of ``DecoderEngine.generate_codes``)."""
+        P = call.prompt_lengths
+        if audio is not None and not call.prompt_is_encoded:
+            # vaura_model.py:463-469 encodes the prompt here.  (Its unpacking `cat([encoded[0] for encoded in audio])`
+            # expects EnCodec's frame list and breaks on DacModelWrapper's (B, 9, T) tensor; the tensor is used as is.)
+            if call.audio_lengths is not None:    # one encoder pass over the clips, each cut to its own samples: P_b = the frames it returns
+                audio, P = self._encode_clips(audio, call.audio_lengths)
+            else:
+                audio = self.audio_encoder.encode(audio)
+        vis = self._handle_visual_conditioning(frames, clip_indices)
+        if vis is None:
+            # the reference's llama sampler refuses a missing condition itself: `raise Exception("Not implemented")` under
+            # "we should always have audio and video" (llama.py:474-476) — channel-concat conditioning has no unconditional form
+            raise NotImplementedError("unconditional generation: the llama sampler always needs video features "
+                                      "(the reference raises here too, llama.py:474-476)")
+        B, K, T, delays, lengths, tv_lengths = vis.shape[0], self.num_codebooks, call.t_max, call.delays, call.lengths, call.tv_lengths
+        Tp = 0 if audio is None else int(audio.shape[-1])
+        if P is not None:                    # the loop starts sampling behind the shortest prompt
+            P = clip_params.resolve_prompt_lengths(B, P, Tp, T, lengths)
+            Tp = min(P)
+        if call.n_segments is not None:      # segments -> video tokens, from the features' own shape
+            if int(vis.shape[1]) % int(frames.shape[1]):
+                raise L.VauraHipError(f"video_segments: {int(vis.shape[1])} video tokens are no multiple of the {int(frames.shape[1])} segments")
+            tv_lengths = [n * (int(vis.shape[1]) // int(frames.shape[1])) for n in call.n_segments]
+        if call.ragged:
+            _, lengths, tv_lengths = clip_params.resolve_lengths(B, lengths if lengths is not None else T, tv_lengths, int(vis.shape[1]),
+                                                                 0 if P is not None else Tp)
+        if self.sampler.audio_tokens_per_video_frame is None:
+            raise L.VauraHipError("sampler.audio_tokens_per_video_frame must be set (scripts/generate.py:216 sets 7)")
+        use_cfg = clip_params.any_cfg(call.sampling["cfg_scale"]) and self.sampler.__class__.__name__ == "Transformer"   # any clip's scale > 1
+        S = T + max(delays) + 1
+        start = Tp + 1 + delays[0]           # Pattern.get_first_step_with_timesteps(Tp) for sorted delays
+        greedy = not clip_params.any_sampled(call.sampling["use_sampling"], call.sampling["temp"])     # per-clip: noise for the batch as soon as one clip draws
+        noise = None if greedy else self._exp_noise(S - start, B * call.N * K, self.sampler.d_codebook)
+        per_clip = P is not None and max(P) > 0      # (equal lengths: the engine takes the common prompt ``audio[..., :P]``, on its path)
+        codes_kw = dict(call.sampling, cfg_scale=call.sampling["cfg_scale"] if use_cfg else 1.0, prompt=audio if (Tp or per_clip) else None,
+                        prompt_lengths=P if per_clip else None, noise=noise, seed=self.seed, clip_base=self.clip_base,
+                        tokens_per_frame=self.sampler.audio_tokens_per_video_frame, delays=None if delays == list(range(K)) else delays,
+                        return_logprobs=call.want_lp, return_relevance=call.want_rel, num_candidates=call.N, video_lengths=tv_lengths)
+        return vis.float(), B, Tp, P, lengths, tv_lengths, codes_kw
 
     @torch.no_grad()
     def generate_tokens(self, frames=None, audio: Union[torch.Tensor, None] = None, clip_indices=None,
@@ -360,107 +471,39 @@ class VAURAModel(nn.Module):
         over P_g + d_0 positions for every further distinct length).  ``noise_mode="torch_cpu"`` works but is not comparable.  With
         ``remove_prompts`` clip b's frames [P_b, T_b) are left-aligned — "tokens" (B, K, T_max - min P) with the special id behind them,
         the per-token values with zeros — and "lengths" = T_b - P_b."""
-        assert not self.training, "do not use generation in training mode"
-        N = self._check_candidates(num_candidates, return_all_candidates, use_sampling, temp, rank_by, return_relevance)   # refused before any device work
-        # per-clip parameter sequences of the wrong length: refused here, before any device work (frames carry the batch on dim 0)
-        clip_params.check_lengths(frames.shape[0] if hasattr(frames, "shape") else None, use_sampling=use_sampling, temp=temp,
-                                  top_k=top_k, top_p=top_p, cfg_scale=cfg_scale)
-        # per-clip lengths: resolved and checked here with what is known before any device work (the batch from the frames, an encoded prompt)
-        per_clip_prompt = prompt_lengths is not None or audio_lengths is not None
-        t_max, lengths, tv_lengths = clip_params.resolve_lengths(
-            frames.shape[0] if hasattr(frames, "shape") else None, max_new_tokens, video_lengths, None,
-            int(audio.shape[-1]) if (audio is not None and prompt_is_encoded and not per_clip_prompt) else 0)
-        self._check_prompt_lengths(frames, audio, prompt_is_encoded, prompt_lengths, audio_lengths, t_max, lengths)   # refused here, before any device work
-        n_segments = None
-        if video_segments is not None:       # refused here, before any device work
-            n_segments = clip_params.resolve_segments(frames.shape[0] if hasattr(frames, "shape") else None, video_segments, video_lengths,
-                                                      frames.shape[1] if hasattr(frames, "shape") and len(frames.shape) > 1 else None,
-                                                      self.flatten_vis_feats, lengths)
-        ragged = lengths is not None or tv_lengths is not None or n_segments is not None or per_clip_prompt
-        max_new_tokens = t_max               # the call runs to the longest clip
-        if return_attention_weights:
-            # the reference's own llama sampler returns (logits, None, None) (llama.py:520-539), so its generate() fails on
-            # `sa_w[-1, -1, :]` (vaura_model.py:529-531) with this flag: there is no behaviour to reproduce
-            raise NotImplementedError("attention-weight dumps are not produced by the fused decode path (nor by the reference's "
-                                      "llama sampler, which returns None for them)")
-        K = self.num_codebooks
-        delays = self._pattern_delays(max_new_tokens)    # the layout the loop decodes: refused here, before any device work
-        block = self.sampler.block_size
-        if delays != list(range(K)) and max_new_tokens + max(delays) + 1 > block:   # (the engine refuses it too, before allocating)
-            raise L.VauraHipError(f"{max_new_tokens} timesteps under the delays {delays} need {max_new_tokens + max(delays) + 1} sequence "
-                                  f"steps; block_size is {block}")
-        P = None
-        if audio is not None and not prompt_is_encoded:
-            # vaura_model.py:463-469 encodes the prompt here.  (Its unpacking `cat([encoded[0] for encoded in audio])`
-            # expects EnCodec's frame list and breaks on DacModelWrapper's (B, 9, T) tensor; the tensor is used as is.)
-            if audio_lengths is not None:    # one encoder pass over the clips, each cut to its own samples: P_b = the frames it returns
-                audio, P = self._encode_clips(audio, audio_lengths)
-            else:
-                audio = self.audio_encoder.encode(audio)
-        if per_clip_prompt:
-            P = clip_params.resolve_prompt_lengths(frames.shape[0] if hasattr(frames, "shape") else None, P if P is not None else prompt_lengths,
-                                                   int(audio.shape[-1]), t_max, lengths)
-        vis = self._handle_visual_conditioning(frames, clip_indices)
-        if vis is None:
-            # the reference's llama sampler refuses a missing condition itself: `raise Exception("Not implemented")` under
-            # "we should always have audio and video" (llama.py:474-476) — channel-concat conditioning has no unconditional form
-            raise NotImplementedError("unconditional generation: the llama sampler always needs video features "
-                                      "(the reference raises here too, llama.py:474-476)")
-        B = vis.shape[0]
-        Tp = 0 if audio is None else int(audio.shape[-1])
-        if P is not None:                    # again with the batch known; the loop starts sampling behind the shortest prompt
-            P = clip_params.resolve_prompt_lengths(B, P, Tp, t_max, lengths)
-            Tp = min(P)
-        assert lengths is not None or Tp < max_new_tokens, "gt audio prompt can not be longer than max_new_tokens"
-        if n_segments is not None:           # segments -> video tokens, from the features' own shape
-            if int(vis.shape[1]) % int(frames.shape[1]):
-                raise L.VauraHipError(f"video_segments: {int(vis.shape[1])} video tokens are no multiple of the {int(frames.shape[1])} segments")
-            tv_lengths = [n * (int(vis.shape[1]) // int(frames.shape[1])) for n in n_segments]
-        if ragged:                           # again with the batch, the video tokens and the prompt known: still before the engine is touched
-            _, lengths, tv_lengths = clip_params.resolve_lengths(B, lengths if lengths is not None else t_max, tv_lengths, int(vis.shape[1]),
-                                                                 0 if P is not None else Tp)
-        use_cfg = clip_params.any_cfg(cfg_scale) and self.sampler.__class__.__name__ == "Transformer"   # any clip's scale > 1
+        return self._generate_tokens(self._resolve_call(
+            frames, audio, max_new_tokens, use_sampling=use_sampling, temp=temp, top_k=top_k, top_p=top_p, cfg_scale=cfg_scale,
+            prompt_is_encoded=prompt_is_encoded, return_logprobs=return_logprobs, return_relevance=return_relevance,
+            video_lengths=video_lengths, prompt_lengths=prompt_lengths, audio_lengths=audio_lengths, num_candidates=num_candidates,
+            return_all_candidates=return_all_candidates, rank_by=rank_by, video_segments=video_segments,
+            return_attention_weights=return_attention_weights, remove_prompts=remove_prompts, check=check), frames, audio, clip_indices)
+
+    def _generate_tokens(self, call: _GenerateCall, frames, audio, clip_indices):
+        """``generate_tokens`` behind its host stage."""
+        N, K, T = call.N, self.num_codebooks, call.t_max
+        feats, B, Tp, P, lengths, tv_lengths, codes_kw = self._bind_call(call, frames, audio, clip_indices)
+        assert lengths is not None or Tp < T, "gt audio prompt can not be longer than max_new_tokens"
         eng = self.sampler.engine()
-        if self.sampler.audio_tokens_per_video_frame is None:
-            raise L.VauraHipError("sampler.audio_tokens_per_video_frame must be set (scripts/generate.py:216 sets 7)")
-        S = max_new_tokens + max(delays) + 1
-        start = Tp + 1 + delays[0]  # Pattern.get_first_step_with_timesteps(Tp) for sorted delays
-        greedy = not clip_params.any_sampled(use_sampling, temp)     # per-clip: noise for the batch as soon as one clip draws
-        noise = None if greedy else self._exp_noise(S - start, B * N * K, self.sampler.d_codebook)
         # decode loop + its status word in one synchronisation (the reference's own post-conditions, :550-572, synchronise too); an
         # activation beyond the fp16-plane range is re-run on the exact-fp32 engine instead of raising (engine.generate_codes_checked)
-        by_rel = rank_by == "relevance"
-        want_rel = bool(return_relevance) or (N > 1 and by_rel)
-        want_lp = bool(return_logprobs) or (N > 1 and not by_rel)      # candidates are ranked by their sequence log-probability by default
-        extra_kw = dict(num_candidates=N) if N > 1 else {}
-        if want_lp:
-            extra_kw.update(return_logprobs=True, num_candidates=N)
-        if want_rel:
-            extra_kw.update(return_relevance=True)
-        codes = eng.generate_codes_checked(
-            vis.float(), lengths if lengths is not None else max_new_tokens, prompt=audio if (Tp or (P is not None and max(P))) else None,
-            use_sampling=use_sampling, temp=temp, **(dict(prompt_lengths=P) if (P is not None and max(P)) else {}),
-            top_k=top_k, top_p=top_p, cfg_scale=cfg_scale if use_cfg else 1.0, noise=noise, seed=self.seed,
-            clip_base=self.clip_base, tokens_per_frame=self.sampler.audio_tokens_per_video_frame,
-            delays=None if delays == list(range(K)) else delays, **extra_kw,
-            **(dict(video_lengths=tv_lengths) if tv_lengths is not None else {}))
+        codes = eng.generate_codes_checked(feats, lengths if lengths is not None else T, **codes_kw)
         lp = None
-        if want_lp or want_rel:
+        if call.want_lp or call.want_rel:
             codes, lp = codes
         bad = (codes < 0) | (codes > self.sampler.d_codebook)
         row_len = None
         if lengths is not None:              # the special id past a clip's own end, and only there
             row_len = torch.tensor(clip_params.repeat(lengths, N), device=codes.device)
-            past = torch.arange(max_new_tokens, device=codes.device)[None, None, :] >= row_len[:, None, None]
+            past = torch.arange(T, device=codes.device)[None, None, :] >= row_len[:, None, None]
             bad = torch.where(past, codes != self.special_token_id, bad | (codes == self.special_token_id))
         assert not bool(bad.any()), "generated sequence is incomplete or out of range"
-        if check:
+        if call.check:
             # vaura_model.py:508-515 checks, every step, that the prefix is coherent with the pattern mask and holds no unknown
             # token; the device loop fills the sequence in place, so the same two properties are checked on the finished one
             # (they are monotone: a violation at any step is still there at the end).  :550-558 are these asserts, always on.
             seq = eng.seq[:B * N].to(torch.int64)
             if lengths is None:
-                _, mask = self.pattern_provider.get_pattern(max_new_tokens)._build_indexes(max_new_tokens, seq.device)
+                _, mask = self.pattern_provider.get_pattern(T)._build_indexes(T, seq.device)
                 mask = mask[None].expand_as(seq)
             else:                            # every clip against its OWN pattern mask: steps behind its sequence hold the special token
                 mask = torch.zeros_like(seq, dtype=torch.bool)
@@ -470,51 +513,25 @@ class VAURAModel(nn.Module):
             special = torch.full_like(seq, self.special_token_id)
             assert not bool((seq == -1).any()), "unknown tokens left in the generated sequence"
             assert bool((seq == torch.where(mask, seq, special)).all()), "sequence and pattern mask disagree"
-        lo = Tp if remove_prompts else 0
-        if not (want_lp or want_rel or ragged):
-            return codes[..., lo:max_new_tokens]
+        lo = Tp if call.remove_prompts else 0
+        if not (call.want_lp or call.want_rel or call.ragged):
+            return codes[..., lo:T]
         out = {}
-        if ragged:
-            out["lengths"] = torch.tensor(lengths if lengths is not None else [max_new_tokens] * B, device=codes.device) - lo
+        if call.ragged:
+            out["lengths"] = torch.tensor(lengths if lengths is not None else [T] * B, device=codes.device) - lo
+        cut = lambda x, fill: x[..., lo:T]
         if P is not None:
             out["prompt_lengths"] = torch.tensor(P, device=codes.device)
-            if remove_prompts:               # clip b's frames [P_b, T_b) left-aligned; everything below is cut through `cut`
+            if call.remove_prompts:          # clip b's frames [P_b, T_b) left-aligned
                 out["lengths"] = out["lengths"] + lo - out["prompt_lengths"]
-                return self._finish_without_prompts(out, codes, lp, P, lengths, B, N, K, max_new_tokens, by_rel, return_all_candidates,
-                                                    return_logprobs, return_relevance, eng)
-        if N > 1:
-            rank = lp["sequence_relevance" if by_rel else "score"]
-            out["candidate_indices"] = codes[..., lo:max_new_tokens]
-            out["candidate_scores"] = rank.view(B, N)
-            if not return_all_candidates:
-                c32 = codes.to(torch.int32).contiguous()
-                won = torch.empty(B, K, max_new_tokens, dtype=torch.int32, device=codes.device)
-                winner = torch.empty(B, dtype=torch.int32, device=codes.device)
-                L.check(eng.lib.vaura_select_candidates(L.ptr(rank), L.ptr(c32), B, N, K, max_new_tokens, L.ptr(won), L.ptr(winner),
-                                                        L.current_stream(eng.dev)), "vaura_select_candidates")
-                rows = torch.arange(B, device=codes.device) * N + winner.to(torch.int64)
-                codes = won.to(torch.int64)
-                lp = {k: v[rows] for k, v in lp.items()}
-                out["selected_candidate"] = winner.to(torch.int64)
-        out["tokens"] = codes[..., lo:max_new_tokens]
-        if return_logprobs:
-            out["logprobs"] = lp["logprobs"][..., lo:max_new_tokens]
-            out["logprob_per_codebook"] = lp["per_codebook"]
-            out["sequence_logprob"] = lp["score"]
-        if return_relevance:
-            for k in ("relevance", "logprob_cond", "logprob_null"):
-                out[k] = lp[k][..., lo:max_new_tokens]
-            out["relevance_per_codebook"] = lp["relevance_per_codebook"]
-            out["sequence_relevance"] = lp["sequence_relevance"]
-        return out
+                cut = self._cut_without_prompts(P, lengths if lengths is not None else [T] * B, T, codes.device)
+        return self._result_dict(call, out, codes, lp, cut, eng)
 
-    def _finish_without_prompts(self, out, codes, lp, P, lengths, B, N, K, T, by_rel, return_all_candidates, return_logprobs,
-                                return_relevance, eng) -> dict:
-        """The result dict of ``generate_tokens(prompt_lengths=..., remove_prompts=True)``: every per-frame entry holds clip b's frames
+    @staticmethod
+    def _cut_without_prompts(P, Tb, T, dev):
+        """The ``cut`` of ``generate_tokens(prompt_lengths=..., remove_prompts=True)``: every per-frame entry holds clip b's frames
         [P_b, T_b) from column 0 on — (rows, K, T - min P) — with the special id (tokens) or zeros (values) behind them."""
-        dev = codes.device
-        width = T - min(P)
-        Tb = lengths if lengths is not None else [T] * B
+        B, width = len(P), T - min(P)
 
         def cut(x, fill):
             n = x.shape[0] // B              # candidates per clip in this tensor
@@ -523,29 +540,35 @@ class VAURAModel(nn.Module):
             src = torch.arange(width, device=dev)[None, None, :] + first
             got = torch.gather(x, 2, src.clamp(max=T - 1).expand(-1, x.shape[1], -1))
             return torch.where(src < end, got, torch.full_like(got, fill))
-        sp = self.special_token_id
+        return cut
+
+    def _result_dict(self, call: _GenerateCall, out, codes, lp, cut, eng) -> dict:
+        """The result dict of ``generate_tokens`` from the engine's codes (B * N, K, T) and per-token values ``lp``: the candidate
+        selection, then every per-frame entry through ``cut(x, fill)`` — the slice ``[..., lo:T]``, or ``_cut_without_prompts``."""
+        N, K, T = call.N, self.num_codebooks, call.t_max
+        B, sp = codes.shape[0] // N, self.special_token_id
         if N > 1:
-            rank = lp["sequence_relevance" if by_rel else "score"]
-            out["candidate_indices"] = cut(codes[..., :T], sp)
+            rank = lp["sequence_relevance" if call.by_rel else "score"]
+            out["candidate_indices"] = cut(codes, sp)
             out["candidate_scores"] = rank.view(B, N)
-            if not return_all_candidates:
+            if not call.return_all_candidates:
                 c32 = codes.to(torch.int32).contiguous()
-                won = torch.empty(B, K, T, dtype=torch.int32, device=dev)
-                winner = torch.empty(B, dtype=torch.int32, device=dev)
+                won = torch.empty(B, K, T, dtype=torch.int32, device=codes.device)
+                winner = torch.empty(B, dtype=torch.int32, device=codes.device)
                 L.check(eng.lib.vaura_select_candidates(L.ptr(rank), L.ptr(c32), B, N, K, T, L.ptr(won), L.ptr(winner),
                                                         L.current_stream(eng.dev)), "vaura_select_candidates")
-                rows = torch.arange(B, device=dev) * N + winner.to(torch.int64)
+                rows = torch.arange(B, device=codes.device) * N + winner.to(torch.int64)
                 codes = won.to(torch.int64)
                 lp = {k: v[rows] for k, v in lp.items()}
                 out["selected_candidate"] = winner.to(torch.int64)
-        out["tokens"] = cut(codes[..., :T], sp)
-        if return_logprobs:
-            out["logprobs"] = cut(lp["logprobs"][..., :T], 0.0)
+        out["tokens"] = cut(codes, sp)
+        if call.return_logprobs:
+            out["logprobs"] = cut(lp["logprobs"], 0.0)
             out["logprob_per_codebook"] = lp["per_codebook"]
             out["sequence_logprob"] = lp["score"]
-        if return_relevance:
+        if call.return_relevance:
             for k in ("relevance", "logprob_cond", "logprob_null"):
-                out[k] = cut(lp[k][..., :T], 0.0)
+                out[k] = cut(lp[k], 0.0)
             out["relevance_per_codebook"] = lp["relevance_per_codebook"]
             out["sequence_relevance"] = lp["sequence_relevance"]
         return out
@@ -569,22 +592,15 @@ class VAURAModel(nn.Module):
         ``prompt_lengths`` / ``audio_lengths`` (see ``generate_tokens``): per-clip prompt lengths; the result gains "prompt_lengths" (B,) next
         to "lengths" / "audio_lengths", and with ``remove_prompts`` the codec decodes each clip's own T_b - P_b generated frames."""
         K = self.num_codebooks
-        self._check_candidates(num_candidates, return_all_candidates, use_sampling, temp, rank_by, return_relevance)    # before the engine is touched
-        t_max, lens, _ = clip_params.resolve_lengths(
-            frames.shape[0] if hasattr(frames, "shape") else None, max_new_tokens, video_lengths, None,
-            int(audio.shape[-1]) if (audio is not None and prompt_is_encoded and prompt_lengths is None and audio_lengths is None) else 0)   # likewise
-        self._check_prompt_lengths(frames, audio, prompt_is_encoded, prompt_lengths, audio_lengths, t_max, lens)
+        call = self._resolve_call(                                   # before the engine is touched
+            frames, audio, max_new_tokens, use_sampling=use_sampling, temp=temp, top_k=top_k, top_p=top_p, cfg_scale=cfg_scale,
+            prompt_is_encoded=prompt_is_encoded, return_logprobs=return_logprobs, return_relevance=return_relevance,
+            video_lengths=video_lengths, prompt_lengths=prompt_lengths, audio_lengths=audio_lengths, num_candidates=num_candidates,
+            return_all_candidates=return_all_candidates, rank_by=rank_by, return_attention_weights=return_attention_weights,
+            remove_prompts=remove_prompts, check=check)
         extra = {}
         with off_null_stream(self.sampler.engine().dev) as caller:   # decode loop + codec leave HIP's null stream together
-            out_codes = self.generate_tokens(
-                frames=frames, audio=audio, clip_indices=clip_indices, max_new_tokens=max_new_tokens,
-                return_attention_weights=return_attention_weights, check=check, use_sampling=use_sampling, temp=temp,
-                top_k=top_k, top_p=top_p, remove_prompts=remove_prompts, prompt_is_encoded=prompt_is_encoded,
-                cfg_scale=cfg_scale, return_logprobs=return_logprobs, num_candidates=num_candidates,
-                return_all_candidates=return_all_candidates, return_relevance=return_relevance, rank_by=rank_by,
-                **(dict(video_lengths=video_lengths) if video_lengths is not None else {}),
-                **(dict(prompt_lengths=prompt_lengths) if prompt_lengths is not None else {}),
-                **(dict(audio_lengths=audio_lengths) if audio_lengths is not None else {}))
+            out_codes = self._generate_tokens(call, frames, audio, clip_indices)
             if isinstance(out_codes, dict):
                 extra = out_codes
                 out_codes = extra.pop("tokens")
@@ -643,7 +659,6 @@ class VAURAModel(nn.Module):
         prompt length (``prompt_lengths`` / ``audio_lengths``), a sampler with ``near_tie="rerun"`` (it decides at the end), and a
         ``block_frames`` that is no positive int.  Closing the iterator early leaves at most two pieces of the loop running and the
         model usable at once."""
-        assert not self.training, "do not use generation in training mode"
         clip_params.check_block_frames(block_frames)
         if isinstance(num_candidates, bool) or not isinstance(num_candidates, int) or num_candidates != 1:
             raise L.VauraHipError(f"generate_stream takes num_candidates = 1 (got {num_candidates!r}): the winning candidate is known only "
@@ -651,72 +666,27 @@ class VAURAModel(nn.Module):
         if getattr(self.sampler, "near_tie", None) == "rerun":
             raise L.VauraHipError('generate_stream is refused with near_tie="rerun": the re-run is decided at the end of the call, after '
                                   'audio has left (use "report" or "off")')
-        B0 = frames.shape[0] if hasattr(frames, "shape") else None
-        clip_params.check_lengths(B0, use_sampling=use_sampling, temp=temp, top_k=top_k, top_p=top_p, cfg_scale=cfg_scale)
-        per_clip_prompt = prompt_lengths is not None or audio_lengths is not None
-        t_max, lengths, _ = clip_params.resolve_lengths(
-            B0, max_new_tokens, video_lengths, None,
-            int(audio.shape[-1]) if (audio is not None and prompt_is_encoded and not per_clip_prompt) else 0)
-        self._check_prompt_lengths(frames, audio, prompt_is_encoded, prompt_lengths, audio_lengths, t_max, lengths)
-        P = None
-        if prompt_lengths is not None:
-            P = clip_params._int_list("prompt_lengths", prompt_lengths)
-        elif audio_lengths is not None:        # the frames the encoder gives each clip: known from the samples alone
+        P = None if prompt_lengths is None else clip_params._int_list("prompt_lengths", prompt_lengths)
+        if P is None and clip_params.is_per_clip(audio_lengths):     # the frames the encoder gives each clip: known from the samples alone
             from .codec_clips import clip_layout
-            n = clip_params._int_list("audio_lengths", audio_lengths) if clip_params.is_per_clip(audio_lengths) else [audio_lengths]
-            P = list(clip_layout(n, self.audio_encoder.cfg, "encode").frames)
+            P = list(clip_layout(clip_params._int_list("audio_lengths", audio_lengths), self.audio_encoder.cfg, "encode").frames)
         if P is not None and len(set(P)) > 1:
             raise L.VauraHipError(f"generate_stream takes one prompt length for the call, got {P} frames per clip: distinct lengths are not "
                                   "served by this version (generate() serves them)")
-        delays = self._pattern_delays(t_max)
-        if delays != list(range(self.num_codebooks)) and t_max + max(delays) + 1 > self.sampler.block_size:
-            raise L.VauraHipError(f"{t_max} timesteps under the delays {delays} need {t_max + max(delays) + 1} sequence steps; block_size is "
-                                  f"{self.sampler.block_size}")
-        return self._generate_stream(frames, audio, clip_indices, t_max, lengths, delays, use_sampling, temp, top_k, top_p, prompt_is_encoded,
-                                     cfg_scale, bool(return_logprobs), bool(return_relevance), video_lengths, prompt_lengths, audio_lengths,
-                                     block_frames, bool(decode))
+        call = self._resolve_call(
+            frames, audio, max_new_tokens, use_sampling=use_sampling, temp=temp, top_k=top_k, top_p=top_p, cfg_scale=cfg_scale,
+            prompt_is_encoded=prompt_is_encoded, return_logprobs=return_logprobs, return_relevance=return_relevance,
+            video_lengths=video_lengths, prompt_lengths=prompt_lengths, audio_lengths=audio_lengths)
+        return self._generate_stream(call, frames, audio, clip_indices, block_frames, bool(decode))
 
     @torch.no_grad()
-    def _generate_stream(self, frames, audio, clip_indices, t_max, lengths, delays, use_sampling, temp, top_k, top_p, prompt_is_encoded,
-                         cfg_scale, want_lp, want_rel, video_lengths, prompt_lengths, audio_lengths, block_frames, decode):
-        K = self.num_codebooks
-        P = None
-        if audio is not None and not prompt_is_encoded:      # as generate_tokens (vaura_model.py:463-469)
-            if audio_lengths is not None:
-                audio, P = self._encode_clips(audio, audio_lengths)
-            else:
-                audio = self.audio_encoder.encode(audio)
-        if prompt_lengths is not None:
-            P = clip_params._int_list("prompt_lengths", prompt_lengths)
-        vis = self._handle_visual_conditioning(frames, clip_indices)
-        if vis is None:
-            raise NotImplementedError("unconditional generation: the llama sampler always needs video features "
-                                      "(the reference raises here too, llama.py:474-476)")
-        B = vis.shape[0]
-        Tp = 0 if audio is None else int(audio.shape[-1])
-        if P is not None:
-            Tp = clip_params.resolve_prompt_lengths(B, P, Tp, t_max, lengths)[0]      # one length for the call (checked at call time)
-        ragged = lengths is not None or video_lengths is not None
-        tv_lengths = None
-        if ragged:
-            _, lengths, tv_lengths = clip_params.resolve_lengths(B, lengths if lengths is not None else t_max, video_lengths, int(vis.shape[1]), Tp)
-        if self.sampler.audio_tokens_per_video_frame is None:
-            raise L.VauraHipError("sampler.audio_tokens_per_video_frame must be set (scripts/generate.py:216 sets 7)")
-        use_cfg = clip_params.any_cfg(cfg_scale) and self.sampler.__class__.__name__ == "Transformer"
-        start = Tp + 1 + delays[0]
-        S = t_max + max(delays) + 1
-        greedy = not clip_params.any_sampled(use_sampling, temp)
-        noise = None if greedy else self._exp_noise(S - start, B * K, self.sampler.d_codebook)
-        codec = self.audio_encoder
-        first = self.sampler.engine()
-        blocks = first.generate_codes_stream(
-            vis.float(), lengths if lengths is not None else t_max, block_frames=block_frames, halo=_codec_halo(codec) if decode else 0,
-            prompt=audio[..., :Tp] if Tp else None, use_sampling=use_sampling, temp=temp, top_k=top_k, top_p=top_p,
-            cfg_scale=cfg_scale if use_cfg else 1.0, noise=noise, seed=self.seed, clip_base=self.clip_base,
-            tokens_per_frame=self.sampler.audio_tokens_per_video_frame, delays=None if delays == list(range(K)) else delays,
-            **(dict(return_logprobs=True) if want_lp else {}), **(dict(return_relevance=True) if want_rel else {}),
-            **(dict(video_lengths=tv_lengths) if tv_lengths is not None else {}))
-        T_b = lengths if lengths is not None else [t_max] * B
+    def _generate_stream(self, call: _GenerateCall, frames, audio, clip_indices, block_frames, decode):
+        feats, B, _, _, lengths, tv_lengths, codes_kw = self._bind_call(call, frames, audio, clip_indices)
+        ragged = lengths is not None or tv_lengths is not None
+        codec, first = self.audio_encoder, self.sampler.engine()
+        blocks = first.generate_codes_stream(feats, lengths if lengths is not None else call.t_max, block_frames=block_frames,
+                                             halo=_codec_halo(codec) if decode else 0, **codes_kw)
+        T_b = lengths if lengths is not None else [call.t_max] * B
         for ranges in blocks:
             eng = first.stream_engine          # the engine whose sequence these ranges refer to (the exact-fp32 twin after a range fallback)
             starts, counts = [lo for lo, _ in ranges], [hi - lo for lo, hi in ranges]
@@ -724,9 +694,9 @@ class VAURAModel(nn.Module):
                 blk = {"sampled_indices": eng.stream_frames(eng.seq, ranges, self.special_token_id).to(torch.int64)}
                 if decode:
                     blk["audio"] = codec.decode_window_seq(eng.seq, starts, counts, lengths, eng.delays)
-                if want_lp:
+                if call.want_lp:
                     blk["logprobs"] = eng.stream_frames(eng.logprobs, ranges, 0.0)
-                if want_rel:
+                if call.want_rel:
                     blk["logprob_cond"] = eng.stream_frames(eng.logprobs_cond, ranges, 0.0)
                     blk["logprob_null"] = eng.stream_frames(eng.logprobs_null, ranges, 0.0)
                     blk["relevance"] = blk["logprob_cond"] - blk["logprob_null"]
