@@ -450,7 +450,7 @@ int vaura_decode_step(const vaura_decoder* dec, const vaura_sampling* sp, int sa
  * hipGraph per position (the position lives in dec->state); NULL launches every kernel eagerly.
  * vaura_step_graph_build captures one step of (dec, sp) on `s` (not the legacy null stream) into a handle the caller
  * owns: it is valid for exactly the buffers / shapes / sampling parameters it was built from.  The loop replays the step
- * `m` at a time where at least m steps remain (one graph launch per m steps; m = 4, or bits 24..27 of vaura_set_debug_flags
+ * `m` at a time where at least m steps remain (one graph launch per m steps; m = 4, or the GRAPH_STEPS field of vaura_set_debug_flags
  * at build time, 1..16): that longer graph is captured — same (dec, sp), on `s` — by the first vaura_generate_loop call with
  * n_steps >= m, so that call must use the dec / sp the handle was built from (it always must).  No process environment is read. */
 typedef void* vaura_step_graph_t;
@@ -579,7 +579,7 @@ int vaura_attention_step_kv(const float* qkv, const float* qkv2, const float* ro
  * z * rows16 .. ; q is rotated in place), kcache, vcache, ws_attn, ws_attn_split (NULL ok), with kv_dtype = 3 kscale and vscale.
  * VAURA_ERR_ARG: null pointers (kscale / vscale with kv_dtype = 3 included), p0 < 0,
  * n_pos <= 0, p0 + n_pos > max_len; VAURA_ERR_SHAPE: head_dim != 96, or a narrow cache (kv_dtype != 0) of more than 256 positions.
- * Debug flag bit 4 selects the per-position kernel (fp32 cache).                                                                      */
+ * PREFILL_ATTN_PER_POSITION selects the per-position kernel (fp32).                                                                      */
 int vaura_attention_prefill(const vaura_decoder* d, int layer, int p0, int n_pos, vaura_stream_t s);
 /* Op-level access to the masked append of vaura_prefill_rows: rope of q (in place, EVERY row) and of k, and the K / V append of the
  * chunk [p0, p0 + n_pos) of one layer only for the rows r with row_n[r] == n_sel (row_n: d->rows int32 in device memory); the cache
@@ -720,7 +720,7 @@ int vaura_dac_conv(const vaura_conv* cv, int precision, const float* in, float* 
 int vaura_dac_conv_ex(const vaura_conv* cv, int precision, const float* in, const float* res, const float* alpha, float* out_raw,
                       void* out_act, float* scratch, int B, int Lin, vaura_stream_t s);
 /* Returned by vaura_dac_unit when the unit is not eligible for the one-launch kernel (shape, precision, fewer than 384 workgroups, or
- * debug flag bit 20 / 21): not an error.                                                                                               */
+ * CODEC_128_ROWS / CODEC_UNIT_TWO_LAUNCHES): not an error.                                                                                       */
 #define VAURA_DAC_UNIT_TWO_LAUNCHES (-100)
 /* Op-level access for parity tests: ONE residual unit of the decoder, out = res + c1(Snake(alpha_mid)(c7(in))), as vaura_dac_decode runs
  * it.  in (B, L, C) fp32 = Snake of the unit's input, already applied; res (B, L, C) fp32 the unit's input; out_raw (NULL ok) and out_act
@@ -737,7 +737,7 @@ int vaura_dac_unit(const vaura_conv* c7, const vaura_conv* c1, int precision, co
 int vaura_dac_from_codes(const int32_t* codes, const float* codebooks, const float* out_proj_w, const float* out_proj_b, void* z,
                          int B, int K, int T, int size, int dim, int latent, int pairs, vaura_stream_t s);
 /* Op-level access for parity tests: the decoder's last convolution (C -> 1, k = 7, tanh; cv->w fp32 [7][C]) with the dispatch of
- * vaura_dac_decode (debug flag bit 13: the untiled kernel).  in (B, L, C) fp32, converted into `scratch` (>= B*L*C floats) in the
+ * vaura_dac_decode (CODEC_LAST_CONV_UNTILED: the untiled kernel).  in (B, L, C) fp32, converted into `scratch` (>= B*L*C floats) in the
  * activation format of `precision` (0: read as is; 1, 2, 4: pair planes; 3: mx8) -> wav (B, L) fp32.                                   */
 int vaura_dac_conv_out(const vaura_conv* cv, int precision, const float* in, float* wav, float* scratch, int B, int L,
                        vaura_stream_t s);
@@ -999,15 +999,10 @@ size_t vaura_audio_preprocess_lds_bytes(int o, int n, int w, int taps_per_phase)
 int vaura_audio_preprocess_tile(void);
 
 /* Measurement aid (tools/pmc_driver, A/B timing): selects kernel variants for launches enqueued (or graphs captured) afterwards.
- * bit 0: wo / w2 GEMVs as one workgroup per column tile instead of the row-split pair; bit 4: prefill attention as one workgroup
- * per position instead of the MFMA kernel (tools/README.md lists every bit).
- * 0 = the product configuration.                                                          */
+ * vaura_amd/csrc/variants.h is the table of every bit of both words, by name (e.g. bit 0, ROWSPLIT_OFF: wo / w2 GEMVs as one workgroup
+ * per column tile instead of the row-split pair); an entry never changes its value.  0 = the product configuration.   */
 void vaura_set_debug_flags(unsigned flags);
-/* A second word of the same kind (the first is full).  bit 0: with 17..32 decoder rows the GEMVs walk the two row blocks one after the
- * other (round 4) instead of taking both per weight pass; bit 1: the one-launch MLP refuses more than 16 rows; bit 2 (experiment, measured slower): the next layer's
- * attention as a fourth phase of the one-launch MLP; bits 3, 4: fp8 weights keep round 4's kernels for wo / w2 / never take the
- * one-launch MLP; bits 5, 6, 12..15: row f2's linear layers on round 4's kernel / with late fragment reads / column-tile panel width
- * (tools/README.md).  0 = the product. */
+/* A second word of the same kind, in the same table.  0 = the product. */
 void vaura_set_debug_flags2(unsigned flags);
 /* Host-side launch counters for tests that must know WHICH kernel instance a call took (read-and-clear; single caller thread):
  * 0 = codec conv launches on the 256-row workgroup instances (conv_pair_kernel<..., 8>, csrc/dac.hip) since the last read.

@@ -19,6 +19,7 @@ import attention_reference as A
 from oracle.decoder_oracle import rope_table
 from vaura_amd import _lib as L
 from vaura_amd import ops
+from vaura_amd.variants import Variant, variants
 
 DEV = "cuda:0"
 H, HD, D = A.H, A.HD, A.D
@@ -416,11 +417,10 @@ def test_prefill_chunks_every_storage(name, kv):
 @pytest.mark.parametrize("per_position", [False, True])
 @pytest.mark.parametrize("name", PREFILL_FAMILIES)
 def test_prefill_long_cache_and_per_position_kernel(name, per_position):
-    """fp32 cache, max_len = 1024 (several 64-key blocks before the chunk, chunks of three query blocks) and — debug flag bit 4 — the
+    """fp32 cache, max_len = 1024 (several 64-key blocks before the chunk, chunks of three query blocks) and — PREFILL_ATTN_PER_POSITION — the
     per-position kernel on the same cases and on the 256-position ones: both kernels within the bar of the same reference."""
     counts = [0, 0]
-    L.lib().vaura_set_debug_flags(16 if per_position else 0)
-    try:
+    with variants(Variant.PREFILL_ATTN_PER_POSITION if per_position else 0):
         kernel = "prefill_per_position" if per_position else "prefill_mfma"
         seq = seq_for(name, 5, 1024)
         for i, (p0, n) in enumerate(PREFILL_1024):
@@ -443,8 +443,6 @@ def test_prefill_long_cache_and_per_position_kernel(name, per_position):
                 finally:
                     if saved is not None:
                         seq.undo_hot(saved)
-    finally:
-        L.lib().vaura_set_debug_flags(0)
     assert_k_cap(counts, f"prefill long / per-position {name}")
 
 

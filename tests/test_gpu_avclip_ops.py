@@ -30,7 +30,6 @@ Bars (derived; none is tuned on the kernels)
                   |err| <= 1.3e-7 max(1, |x|) + 2^-22 |y| + 2^-25 (the kernel's stated bound + the planes' representation error), and the
                   sign is right wherever the fp64 value rounds to a nonzero pair.
 Measured values next to these bars: set VAURA_AVCLIP_PARITY_OUT=<file> (profiles/avclip_op_parity.txt is such a file)."""
-import contextlib
 import ctypes as C
 import functools
 import os
@@ -42,6 +41,7 @@ pytestmark = pytest.mark.gpu
 
 import vit_reference as R
 from vaura_amd import _lib as L
+from vaura_amd.variants import Variant, variants
 
 DEV = "cuda:0"
 D, NF, HEADS = R.D, R.NF, R.HEADS
@@ -130,16 +130,6 @@ def call(name, *args):
 
 def run(name, *args):
     L.check(call(name, *args), name)
-
-
-@contextlib.contextmanager
-def debug_flags(bits):
-    lib = L.lib()
-    try:
-        lib.vaura_set_debug_flags(bits)
-        yield
-    finally:
-        lib.vaura_set_debug_flags(0)
 
 
 RECORD = {}      # (op, kernel, case) -> (err, e_ref, bar)
@@ -351,11 +341,11 @@ def test_cls_attention(case, family):
     qd = dev(qkv)
     part = torch.full((2 * HEADS * 8 * 66,), float("nan"), device=DEV) if use_part else None
     v = make_vit(196)
-    for kern, bits in (("16-lane", 0), ("one-wg", 512)):      # 16-lane: vit_cls_attn_split_kernel, 8 splits + combine only where `part` is given and Lseq > 512
+    for kern, bits in (("16-lane", 0), ("one-wg", Variant.VIT_CLS_UNSPLIT)):      # 16-lane: vit_cls_attn_split_kernel, 8 splits + combine only where `part` is given and Lseq > 512
         for stride in (1, Lseq):
             rows = stride + 1
             out = guarded_rows(rows, D * 4)
-            with debug_flags(bits):
+            with variants(bits):
                 run("vaura_vit_cls_attention", C.byref(v), L.ptr(qd), out.ptr(), L.ptr(part), 2, Lseq, stride)
             written = torch.zeros(rows, dtype=torch.bool)
             written[[0, stride]] = True
@@ -393,9 +383,9 @@ def test_time_attention(n, family):
     qkv, ref, ref32, scale, written = _pattern_case(n, family, "time", 51 + n)
     qd = dev(qkv)
     v = make_vit(n)
-    for kern, bits in (("16-lane", 0), ("one-thread", 1024)):
+    for kern, bits in (("16-lane", 0), ("one-thread", Variant.VIT_TIME_THREAD_PER_HEAD_FRAME)):
         out = guarded_rows(written.numel(), D * 4)
-        with debug_flags(bits):
+        with variants(bits):
             run("vaura_vit_time_attention", C.byref(v), L.ptr(qd), out.ptr(), 2)
         got = pair_rows(out.host(), written.numel(), D, written)
         check_scaled("time", kern, f"np {n} {family}", got, ref, ref32, scale)
@@ -408,12 +398,13 @@ def test_space_attention(n, family):
     apriori = R.pair_attention_apriori(qkv, NF, n, "space").reshape(2 * NF * n, D)
     qd = dev(qkv)
     v = make_vit(n)
-    # above 207 patches the launcher takes vit_space_attn_kernel whatever the flags: one kernel, the fp32 class
-    kernels = (("pair", 0, apriori), ("mfma-f32", 2048, None), ("one-thread", 128, None)) if n <= 207 else (("generic", 0, None),)
+    # above 207 patches the launcher takes vit_space_attn_kernel whatever the switches: one kernel, the fp32 class
+    kernels = (("pair", 0, apriori), ("mfma-f32", Variant.VIT_SPACE_FP32_MFMA, None),
+               ("one-thread", Variant.VIT_SPACE_THREAD_PER_QUERY, None)) if n <= 207 else (("generic", 0, None),)
     outs = []
     for kern, bits, extra in kernels:
         out = guarded_rows(written.numel(), D * 4)
-        with debug_flags(bits):
+        with variants(bits):
             run("vaura_vit_space_attention", C.byref(v), L.ptr(qd), out.ptr(), 2)
         got = pair_rows(out.host(), written.numel(), D, written)
         bar = check_scaled("space", kern, f"np {n} {family}", got, ref, ref32, scale, extra=extra)

@@ -34,6 +34,7 @@ pytestmark = pytest.mark.gpu
 import parity_helpers as ph
 from vaura_amd import _lib as L
 from vaura_amd import quant
+from vaura_amd.variants import Variant, variants
 
 DEV = "cuda:0"
 PRECISIONS = ["f32", "f16pair", "f16", "f16pair_w8", "mx8"]
@@ -345,7 +346,7 @@ def _unit_problem(Cc):
 @pytest.mark.parametrize("Cc", [96, 192])
 def test_large_instances_against_fp64(Cc, precision):
     """One residual unit as ONE launch (C = 96: conv_pair_kernel<.., 8, true>, L = 191 x 256 + 37; C = 192: conv_unit_kernel<12, 2, ..>,
-    L = 191 x 128 + 37) against fp64 and against the two-launch form (debug flag bit 21), bit for bit.  The fp64 reference follows the
+    L = 191 x 128 + 37) against fp64 and against the two-launch form (CODEC_UNIT_TWO_LAUNCHES), bit for bit.  The fp64 reference follows the
     stages on the numbers the kernels multiply: the first conv's activated output (kept by the two-launch run) against Snake of the fp64
     conv, the unit's output against fp64 of res + conv1(that activated output — its hi planes for "f16").  At C = 96 the 7-tap conv also
     runs alone through vaura_dac_conv_ex on the 256-row instance (vaura_debug_counter(0) > 0) and is held to the same bars."""
@@ -364,9 +365,8 @@ def test_large_instances_against_fp64(Cc, precision):
     am, an = alpha_mid.to(DEV), alpha_next.to(DEV)
     gb = guard_bytes(Cc * 4)
     outs = {}
-    try:
-        for form, flags in (("one", 0), ("two", 1 << 21)):
-            lib.vaura_set_debug_flags(flags)
+    for form, flags in (("one", 0), ("two", Variant.CODEC_UNIT_TWO_LAUNCHES)):
+        with variants(flags):
             lib.vaura_debug_counter(0)
             lib.vaura_debug_counter(1)
             raw_g, act_g = Guarded(rows * Cc * 4, gb), Guarded(codec_act_bytes(precision, rows, Cc), gb)
@@ -379,17 +379,14 @@ def test_large_instances_against_fp64(Cc, precision):
             else:
                 assert not fused and n_fused == 0 and n_256 == 2, (fused, n_fused, n_256)
             outs[form] = (raw_g.host(), act_g.host(), None if mid_g is None else mid_g.host())
-        conv_alone = None
-        if Cc == 96:
-            lib.vaura_set_debug_flags(0)
-            lib.vaura_debug_counter(0)
-            alone_g = Guarded(codec_act_bytes(precision, rows, Cc), gb)
-            CodecConvOp(w7e, b7, dil, 1, precision, DEV).ex(xd, alpha=am, out_act=alone_g.view())
-            torch.cuda.synchronize()
-            assert int(lib.vaura_debug_counter(0)) > 0
-            conv_alone = alone_g.host()
-    finally:
-        lib.vaura_set_debug_flags(0)
+    conv_alone = None
+    if Cc == 96:
+        lib.vaura_debug_counter(0)
+        alone_g = Guarded(codec_act_bytes(precision, rows, Cc), gb)
+        CodecConvOp(w7e, b7, dil, 1, precision, DEV).ex(xd, alpha=am, out_act=alone_g.view())
+        torch.cuda.synchronize()
+        assert int(lib.vaura_debug_counter(0)) > 0
+        conv_alone = alone_g.host()
     assert torch.equal(outs["one"][0], outs["two"][0]), "raw output: one launch != two launches"
     assert torch.equal(outs["one"][1], outs["two"][1]), "activated output: one launch != two launches"
 
@@ -431,7 +428,7 @@ def _gate_problem(case, Lin):
 def test_256_row_gate_of_the_conv_launcher(case, precision, Lin, product):
     """vaura_dac_conv_ex at the two lengths either side of the gate, per instance family (96-column tiles, 64-column tiles, the two phases
     of a transposed conv with its jcount = Lin + 1) and pair precision: vaura_debug_counter(0) reads 1 at a product of exactly 384 and 0
-    at 380, and 0 under debug flag bit 20 (128-row instances only); the activated output of the two runs is equal byte for byte and the
+    at 380, and 0 under CODEC_128_ROWS (128-row instances only); the activated output of the two runs is equal byte for byte and the
     guards are intact.  No fp64 reference: the smaller shapes above carry the numeric bars.  The largest tensor of a case is 37.7 MB."""
     from vaura_amd.engine import CodecConvOp, codec_act_bytes
     name, cin, cout, k, dil, stride = case
@@ -447,9 +444,8 @@ def test_256_row_gate_of_the_conv_launcher(case, precision, Lin, product):
     op = CodecConvOp(we, bias, dil, stride, precision, DEV)
     xd, ad = x.to(DEV), alpha.to(DEV)
     outs, counts = [], []
-    try:
-        for flags in (0, 1 << 20):
-            lib.vaura_set_debug_flags(flags)
+    for flags in (0, Variant.CODEC_128_ROWS):
+        with variants(flags):
             lib.vaura_debug_counter(0)
             act_g = Guarded(codec_act_bytes(precision, rows, cout), guard_bytes(cout * 4))
             op.ex(xd, alpha=ad, out_act=act_g.view())
@@ -457,9 +453,7 @@ def test_256_row_gate_of_the_conv_launcher(case, precision, Lin, product):
             counts.append(int(lib.vaura_debug_counter(0)))
             outs.append(act_g.host())
             del act_g
-    finally:
-        lib.vaura_set_debug_flags(0)
-    print(f"[codec-stage] gate {name} {precision} Lin={Lin}: product {product}, 256-row launches {counts[0]} (flag bit 20: {counts[1]})")
+    print(f"[codec-stage] gate {name} {precision} Lin={Lin}: product {product}, 256-row launches {counts[0]} (CODEC_128_ROWS: {counts[1]})")
     assert counts == [1 if product >= 384 else 0, 0], counts
     assert bool((outs[0].view(torch.int16) != -1).all()), "fp16 plane entries were never written"
     assert torch.equal(outs[0], outs[1]), "256-row / 128-row selection changed the output"
@@ -469,8 +463,8 @@ def test_256_row_gate_of_the_conv_launcher(case, precision, Lin, product):
 @pytest.mark.parametrize("Ln,product", [(49152, 384), (48896, 382)])
 def test_256_row_gate_of_the_unit_launcher(Ln, product, precision):
     """vaura_dac_unit, C = 96, 7 taps of dilation 9, B = 2, either side of ceil(L / 256) x B >= 384: vaura_debug_counter(1) reads 1 at 384
-    (one launch) and 0 at 382, where the unit runs as two convs whose own products are 382 as well (counter 0 == 0).  Under debug flag
-    bit 21 (always two launches) the output is equal byte for byte; at 384 those two convs take the 256-row instances (counter 0 == 2)."""
+    (one launch) and 0 at 382, where the unit runs as two convs whose own products are 382 as well (counter 0 == 0).  Under
+    CODEC_UNIT_TWO_LAUNCHES (always two launches) the output is equal byte for byte; at 384 those two convs take the 256-row instances (counter 0 == 2)."""
     from vaura_amd.engine import CodecUnitOp, codec_act_bytes
     Cc, dil = 96, 9
     assert -(-Ln // 256) * 2 == product
@@ -489,9 +483,8 @@ def test_256_row_gate_of_the_unit_launcher(Ln, product, precision):
     xd, resd = x.to(DEV), res.to(DEV)
     mid = torch.empty(codec_act_bytes(precision, rows, Cc), dtype=torch.uint8, device=DEV)
     outs, seen = [], []
-    try:
-        for flags in (0, 1 << 21):
-            lib.vaura_set_debug_flags(flags)
+    for flags in (0, Variant.CODEC_UNIT_TWO_LAUNCHES):
+        with variants(flags):
             lib.vaura_debug_counter(0)
             lib.vaura_debug_counter(1)
             act_g = Guarded(codec_act_bytes(precision, rows, Cc), gb)
@@ -500,9 +493,7 @@ def test_256_row_gate_of_the_unit_launcher(Ln, product, precision):
             seen.append((fused, int(lib.vaura_debug_counter(1)), int(lib.vaura_debug_counter(0))))
             outs.append(act_g.host())
             del act_g
-    finally:
-        lib.vaura_set_debug_flags(0)
-    print(f"[codec-stage] gate unit {precision} L={Ln}: product {product}, (one launch, counter 1, counter 0) = {seen[0]}; flag bit 21: {seen[1]}")
+    print(f"[codec-stage] gate unit {precision} L={Ln}: product {product}, (one launch, counter 1, counter 0) = {seen[0]}; CODEC_UNIT_TWO_LAUNCHES: {seen[1]}")
     big = product >= 384
     assert seen == [(big, 1 if big else 0, 0), (False, 0, 2 if big else 0)], seen
     assert bool((outs[0].view(torch.int16) != -1).all()), "fp16 plane entries were never written"
@@ -548,7 +539,7 @@ def test_from_codes(K, dim, latent, pairs):
 @pytest.mark.parametrize("Cc,untiled_flag", [(96, False), (96, True), (160, False)], ids=["C96-tiled", "C96-untiled", "C160-untiled"])
 def test_conv_out(Cc, untiled_flag, precision):
     """The last conv (C -> 1, k = 7, tanh) on an input stored as fp32, pair planes or mx8: conv_out_tiled_kernel (C = 96), conv_out_kernel
-    by debug flag bit 13 and by shape (C = 160 > 128); L = 2 x 128 + 37.  Reference: tanh of the fp64 sum over the input AS STORED.  fp32
+    by CODEC_LAST_CONV_UNTILED and by shape (C = 160 > 128); L = 2 x 128 + 37.  Reference: tanh of the fp64 sum over the input AS STORED.  fp32
     chain: n = 7 C + 8; the pre-activation bound goes through tanh exactly (monotone), + 2^-21 for tanhf."""
     from vaura_amd.engine import codec_conv_out
     B, Ln = 2, 2 * 128 + 37
@@ -570,16 +561,12 @@ def test_conv_out(Cc, untiled_flag, precision):
     ref = torch.tanh(pre)
     allowed = torch.maximum(torch.tanh(pre + Epre) - ref, ref - torch.tanh(pre - Epre)) + 2.0 ** -21
     out = Guarded(B * Ln * 4, 256)
-    lib = L.lib()
-    try:
-        lib.vaura_set_debug_flags(8192 if untiled_flag else 0)
+    with variants(Variant.CODEC_LAST_CONV_UNTILED if untiled_flag else 0):
         codec_conv_out(w, bias, x.to(DEV), out.view(torch.float32).reshape(B, Ln), precision)
         torch.cuda.synchronize()
-    finally:
-        lib.vaura_set_debug_flags(0)
     got = fp32_out(out.host(), (B, Ln)).double()
     ratio = float(((got - ref).abs() / allowed).max())
-    note(f"conv_out C={Cc}{' flag 13' if untiled_flag else ''}", precision, ratio, 1.0)
+    note(f"conv_out C={Cc}{' CODEC_LAST_CONV_UNTILED' if untiled_flag else ''}", precision, ratio, 1.0)
     print(f"[codec-stage] conv_out C={Cc} {precision}: max |err| clip 0 {float((got - ref)[0].abs().max()):.2e}, clip 1 {float((got - ref)[1].abs().max()):.2e}")
     assert ratio <= 1.0, ratio
 

@@ -8,6 +8,7 @@ pytestmark = pytest.mark.gpu
 
 from vaura_amd import synth
 from vaura_amd.engine import CodecEngine, DecoderEngine
+from vaura_amd.variants import Variant, Variant2, variants
 from parity_helpers import assert_tokens_equal, assert_tokens_or_recorded_near_tie
 
 DEV = "cuda:0"
@@ -369,16 +370,14 @@ def test_long_context_single_pass_against_live_oracle():
     got = eng.generate_codes(feats.to(DEV), 300).cpu()
     assert eng.max_len >= 1024
     assert torch.equal(got, ref), float((got == ref).float().mean())
-    # the range-split attention merges its partials inside the launch (the last split of a (row, head) to arrive); debug flag bit 19 keeps
-    # the merge as its own launch: same sums in the same order, so the very same tokens, eager and through the captured graph
-    from vaura_amd import _lib as L
+    # the range-split attention merges its partials inside the launch (the last split of a (row, head) to arrive); ATTN_MERGE_OWN_LAUNCH
+    # keeps the merge as its own launch: same sums in the same order, so the very same tokens, eager and through the captured graph
     try:
-        L.lib().vaura_set_debug_flags(1 << 19)
-        eng._free_graph()
-        two = eng.generate_codes(feats.to(DEV), 300).cpu()
-        two_eager = eng.generate_codes(feats.to(DEV), 300, use_graph=False).cpu()
+        with variants(Variant.ATTN_MERGE_OWN_LAUNCH):
+            eng._free_graph()
+            two = eng.generate_codes(feats.to(DEV), 300).cpu()
+            two_eager = eng.generate_codes(feats.to(DEV), 300, use_graph=False).cpu()
     finally:
-        L.lib().vaura_set_debug_flags(0)
         eng._free_graph()
     assert torch.equal(two, got) and torch.equal(two_eager, got)
     assert torch.equal(eng.generate_codes(feats.to(DEV), 300, use_graph=False).cpu(), got)
@@ -601,9 +600,8 @@ def test_dac_decode_fp8_weights_against_oracle_on_dequantised_checkpoint():
 def test_dac_decode_256_row_workgroups_are_bit_identical(precision):
     """The codec's convs run in 256-row workgroups wherever enough of them remain (csrc/dac.hip, conv_pair_kernel<..., MJ = 8>):
     only at full length, which the oracle-checked cases above (12 frames) never reach.  Same products summed in the same order,
-    so the waveform of a full-length decode must equal, bit for bit, the one from 128-row workgroups (debug flag bit 20) — the
+    so the waveform of a full-length decode must equal, bit for bit, the one from 128-row workgroups (CODEC_128_ROWS) — the
     instances the oracle pins.  Also the encoder's 64-column instances (codes identical)."""
-    from vaura_amd import _lib as L
     from vaura_amd.engine import CodecEncoderEngine
     ccfg = synth.FULL_CODEC
     sd = dict(synth.codec_state_dict(ccfg, seed=1))
@@ -612,18 +610,15 @@ def test_dac_decode_256_row_workgroups_are_bit_identical(precision):
     dec = CodecEngine(ccfg, sd, DEV, precision=precision)
     enc = CodecEncoderEngine(ccfg, sd, DEV) if precision == "f16pair" else None
     out = {}
-    try:
-        for flags in (0, 1 << 20):
-            L.lib().vaura_set_debug_flags(flags)
+    for flags in (Variant(0), Variant.CODEC_128_ROWS):
+        with variants(flags):
             wav = dec.decode(codes)
             out[flags] = (wav.clone(), enc.encode(wav).clone() if enc else None)
-    finally:
-        L.lib().vaura_set_debug_flags(0)
     torch.cuda.synchronize()
     assert torch.isfinite(out[0][0]).all()
-    assert torch.equal(out[0][0], out[1 << 20][0])
+    assert torch.equal(out[0][0], out[Variant.CODEC_128_ROWS][0])
     if enc:
-        assert torch.equal(out[0][1], out[1 << 20][1])
+        assert torch.equal(out[0][1], out[Variant.CODEC_128_ROWS][1])
 
 
 def test_dac_decode_block_scaled_fp8_against_its_emulation():
@@ -847,9 +842,8 @@ def test_two_row_blocks_per_weight_pass_are_bit_identical_to_the_walk(wdtype):
     """17..32 decoder rows (the reference's default batch 16 under CFG, configs/generate_vgg.yaml:41 + :27; BASELINE configs[4]): every
     GEMV takes BOTH row blocks per weight fragment (gemv3_kernel / gemv3h_kernel RBK = 2: second accumulator set, one reduction
     barrier, the blocks' epilogues on different waves).  Per row block the products and their order are those of round 4's walk over
-    the blocks (second flag word, bit 0): logits bit for bit and tokens, at 20 rows (second block ragged), 32 rows (full) and 40 rows
+    the blocks (Variant2.ROW_BLOCKS_WALK): logits bit for bit and tokens, at 20 rows (second block ragged), 32 rows (full) and 40 rows
     (three blocks: a full pass + a half-empty one), eager and through the captured graph."""
-    from vaura_amd import _lib as L
     cfg = synth.tiny_sampler(2)
     sd = synth.sampler_state_dict(cfg, seed=91)
     eng = DecoderEngine(cfg, sd, DEV, wdtype=wdtype)
@@ -857,18 +851,17 @@ def test_two_row_blocks_per_weight_pass_are_bit_identical_to_the_walk(wdtype):
     out = {}
     try:
         for walk in (0, 1):
-            L.lib().vaura_set_debug_flags2(walk)
-            eng._free_graph()
-            for rows in (20, 32, 40):
-                feats = synth.video_features(rows, seed=93).to(DEV)
-                idx = torch.randint(0, 1025, (rows, 9, 5), generator=torch.Generator().manual_seed(94 + rows))
-                out[("lg", rows, walk)] = eng.logits_all_positions(idx.to(DEV), feats).cpu()
-            feats = synth.video_features(16, seed=95).to(DEV)
-            for ug in (True, False):
-                out[("tok", ug, walk)] = eng.generate_codes(feats, 14, cfg_scale=6.0, use_sampling=True, top_k=128, seed=7, use_graph=ug).cpu()
-                eng.check_status()
+            with variants(word2=Variant2.ROW_BLOCKS_WALK if walk else 0):
+                eng._free_graph()
+                for rows in (20, 32, 40):
+                    feats = synth.video_features(rows, seed=93).to(DEV)
+                    idx = torch.randint(0, 1025, (rows, 9, 5), generator=torch.Generator().manual_seed(94 + rows))
+                    out[("lg", rows, walk)] = eng.logits_all_positions(idx.to(DEV), feats).cpu()
+                feats = synth.video_features(16, seed=95).to(DEV)
+                for ug in (True, False):
+                    out[("tok", ug, walk)] = eng.generate_codes(feats, 14, cfg_scale=6.0, use_sampling=True, top_k=128, seed=7, use_graph=ug).cpu()
+                    eng.check_status()
     finally:
-        L.lib().vaura_set_debug_flags2(0)
         eng._free_graph()
     for rows in (20, 32, 40):
         assert torch.isfinite(out[("lg", rows, 0)]).all()
@@ -992,14 +985,11 @@ def test_full_length_codec_decode_and_encode_match_the_oracle_on_the_256_row_ins
     n256, nfused = int(L.lib().vaura_debug_counter(0)), int(L.lib().vaura_debug_counter(1))
     # 4 x (up + 3 x 2) = 28 of the 30 convs; a residual unit launched as ONE kernel (C = 96 and C = 192: the last two blocks' six) covers two of them
     assert n256 + 2 * nfused >= 28 and nfused == 6, f"only {n256} conv launches + {nfused} fused units took the 256-row instances"
-    # ... and the one-launch units are bit-identical to the two-launch form (debug flag bit 21), which is what the oracle is compared with below too
-    L.lib().vaura_set_debug_flags(1 << 21)
-    try:
+    # ... and the one-launch units are bit-identical to the two-launch form (CODEC_UNIT_TWO_LAUNCHES), which is what the oracle is compared with below too
+    with variants(Variant.CODEC_UNIT_TWO_LAUNCHES):
         two = dec.decode(codes.to(DEV))
         torch.cuda.synchronize()
         assert int(L.lib().vaura_debug_counter(1)) == 0 and int(L.lib().vaura_debug_counter(0)) >= 28
-    finally:
-        L.lib().vaura_set_debug_flags(0)
     assert torch.equal(two, got), float((two - got).abs().max())
     got = got.cpu()
     worst = 0.0
@@ -1202,8 +1192,8 @@ def test_plane_shift_moves_the_fp16_plane_range_up_at_the_same_speed(golden, ful
 @pytest.mark.parametrize("precision", ["f16pair", "f16", "f16pair_w8"])
 def test_one_launch_residual_units_are_bit_identical_to_two_launches(precision):
     """csrc/dac.hip: a residual unit (7-tap dilated conv -> Snake -> 1 x 1 conv -> + residual) of the last two decoder blocks (C = 192:
-    conv_unit_kernel, C = 96: conv_pair_kernel<..., FUSE>) runs as ONE launch wherever >= 384 workgroups remain; debug flag bit 21 keeps
-    the two launches.  Same matrix instructions on the same fragments in the same order: the waveform must be BIT-identical, in every
+    conv_unit_kernel, C = 96: conv_pair_kernel<..., FUSE>) runs as ONE launch wherever >= 384 workgroups remain; CODEC_UNIT_TWO_LAUNCHES
+    keeps the two launches.  Same matrix instructions on the same fragments in the same order: the waveform must be BIT-identical, in every
     pair-arithmetic precision (each has its own kernel instance), at a batch / length other than the bench's (B = 3, T = 130: six
     one-launch units, asserted through the library's counter), both sequence ends and the clip boundaries included."""
     from vaura_amd import _lib as L
@@ -1211,17 +1201,14 @@ def test_one_launch_residual_units_are_bit_identical_to_two_launches(precision):
     sd = synth.codec_state_dict(ccfg, seed=4)
     codes = torch.randint(0, 1024, (3, 9, 130), generator=torch.Generator().manual_seed(8)).to(DEV)
     dec = CodecEngine(ccfg, sd, DEV, precision=precision)
-    try:
-        L.lib().vaura_debug_counter(1)
-        one = dec.decode(codes).clone()
-        torch.cuda.synchronize()
-        assert int(L.lib().vaura_debug_counter(1)) == 6
-        L.lib().vaura_set_debug_flags(1 << 21)
+    L.lib().vaura_debug_counter(1)
+    one = dec.decode(codes).clone()
+    torch.cuda.synchronize()
+    assert int(L.lib().vaura_debug_counter(1)) == 6
+    with variants(Variant.CODEC_UNIT_TWO_LAUNCHES):
         two = dec.decode(codes).clone()
         torch.cuda.synchronize()
         assert int(L.lib().vaura_debug_counter(1)) == 0
-    finally:
-        L.lib().vaura_set_debug_flags(0)
     assert torch.isfinite(one).all() and float(one.abs().max()) > 0.01
     assert torch.equal(one, two), float((one - two).abs().max())
 
@@ -1282,8 +1269,8 @@ def test_heavy_tailed_checkpoint_rows_against_live_oracle(wdtype):
 @pytest.mark.parametrize("wdtype", ["h2", "h1", "fp8", "fp8h"])
 def test_one_launch_mlp_is_bit_identical_to_two_launches(wdtype, clips):
     """csrc/mlp_engine.h, the default where eligible: the MLP of a layer (w1||w3 + SwiGLU -> w2 + residual) as ONE launch with an
-    in-launch hand-off, w2's weights requested ahead of it (debug flag bit 2: every GEMV its own launch; bit 1: the next layer's
-    qkv stays its own launch).  Same products in the same order as the separate launches: teacher-forced
+    in-launch hand-off, w2's weights requested ahead of it (MLP_TWO_LAUNCHES: every GEMV its own launch; QKV_OWN_LAUNCH: the next
+    layer's qkv stays its own launch).  Same products in the same order as the separate launches: teacher-forced
     logits must be BIT-identical, tokens (greedy + CFG, and Philox-sampled) identical, through the eager path and through the
     captured step graph, and no consumer may have given up waiting (status word clean).  6 clips x cfg = 12 decoder rows (both row
     halves live) and 3 clips = 6 rows (configs[3]'s regime: one live half; the separate launches then use one workgroup per tile, the
@@ -1292,7 +1279,6 @@ def test_one_launch_mlp_is_bit_identical_to_two_launches(wdtype, clips):
     instances (mlp_engine_kernel<.., RBK = 2>) against the separate two-row-block launches.  fp8 tile pairs (configs[4]) take the one-launch form with 17..32 rows only
     (its qkv phase on four waves of six k-groups, like the separate fp8 K-split kernel): 16 and 10 clips test it, 6 and 3 are the
     separate launches either way."""
-    from vaura_amd import _lib as L
     cfg = synth.tiny_sampler(3)
     sd = synth.sampler_state_dict(cfg, seed=101, round_bf16=(wdtype == "h1"))
     eng = DecoderEngine(cfg, sd, DEV, wdtype=wdtype)
@@ -1304,27 +1290,24 @@ def test_one_launch_mlp_is_bit_identical_to_two_launches(wdtype, clips):
         # the default (w1||w3 -> w2 -> next layer's qkv in one launch) | qkv separate | every GEMV and the attention their own launches.
         # (The three measured-negative engines — attention + wo, the layer tail, the attention as a fourth phase — are no longer
         # in the tree; their bit-identity records are in DESIGN_HISTORY.md.)
-        for flags in (0, 0x2, 4):
-            f1, f2 = flags if isinstance(flags, tuple) else (flags, 0)
-            L.lib().vaura_set_debug_flags(f1)
-            L.lib().vaura_set_debug_flags2(f2)
-            eng._free_graph()
-            out[flags] = (eng.logits_all_positions(idx, f12).clone(),
-                          eng.generate_codes(feats, 24, cfg_scale=6.0).clone(),
-                          eng.generate_codes(feats, 24, cfg_scale=6.0, use_sampling=True, top_k=250, seed=9).clone(),
-                          eng.generate_codes(feats, 24, cfg_scale=6.0, use_graph=False).clone())
-            eng.check_status()
+        for flags in (Variant(0), Variant.QKV_OWN_LAUNCH, Variant.MLP_TWO_LAUNCHES):
+            with variants(flags):
+                eng._free_graph()
+                out[flags] = (eng.logits_all_positions(idx, f12).clone(),
+                              eng.generate_codes(feats, 24, cfg_scale=6.0).clone(),
+                              eng.generate_codes(feats, 24, cfg_scale=6.0, use_sampling=True, top_k=250, seed=9).clone(),
+                              eng.generate_codes(feats, 24, cfg_scale=6.0, use_graph=False).clone())
+                eng.check_status()
     finally:
-        L.lib().vaura_set_debug_flags(0)
-        L.lib().vaura_set_debug_flags2(0)
         eng._free_graph()
     torch.cuda.synchronize()
-    assert torch.isfinite(out[4][0]).all()
-    for flags in (0, 0x2):
-        assert torch.equal(out[flags][0], out[4][0]), (flags, float((out[flags][0] - out[4][0]).abs().max()))
+    two = out[Variant.MLP_TWO_LAUNCHES]
+    assert torch.isfinite(two[0]).all()
+    for flags in (Variant(0), Variant.QKV_OWN_LAUNCH):
+        assert torch.equal(out[flags][0], two[0]), (flags, float((out[flags][0] - two[0]).abs().max()))
         for i in (1, 2, 3):
-            assert torch.equal(out[flags][i], out[4][i]), (flags, i)
-    assert torch.equal(out[4][1], out[4][3])
+            assert torch.equal(out[flags][i], two[i]), (flags, i)
+    assert torch.equal(two[1], two[3])
 
 
 @pytest.mark.parametrize("clips", [8, 16])

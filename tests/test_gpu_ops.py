@@ -10,6 +10,7 @@ pytestmark = pytest.mark.gpu
 
 from vaura_amd import _lib as L
 from vaura_amd import ops, synth
+from vaura_amd.variants import Variant, variants
 
 DEV = "cuda:0"
 
@@ -187,7 +188,7 @@ def test_split_row_gemv_variants(K, N, epi, norm, rows, wdtype):
 def test_prefill_gemm_tilings_are_bit_identical(K, N, epi, norm):
     """The prefill GEMM picks a workgroup height per GEMM, cuts a GEMM into two launches, or uses 128 x 128 workgroups (gemv3.hip
     launch_gemm4): every output element is the same sum of the same products in the same k order whatever the tiling, so a
-    prompt-sized GEMM must come out bit-identical with the choices forced off (debug flag bits 5, 22, 23)."""
+    prompt-sized GEMM must come out bit-identical with the choices forced off (PREFILL_GEMM_NO_CUT, PREFILL_GEMM_64x256, PREFILL_GEMM_64_ROWS)."""
     rows = 2656
     g = torch.Generator().manual_seed(K + N)
     w = torch.randn(N, K, generator=g) * 0.02
@@ -198,14 +199,11 @@ def test_prefill_gemm_tilings_are_bit_identical(K, N, epi, norm):
     xs, ss = ops.split_rows(ops.pack_rows(x.to(DEV)), rows, K, gain if norm else None, want_ss=norm)
     wp = ops.pack_weight(w.to(DEV), L.W_H2)
     outs = []
-    try:
-        for flags in (0, 1 << 22, 1 << 23, 32):
-            L.lib().vaura_set_debug_flags(flags)
+    for flags in (0, Variant.PREFILL_GEMM_NO_CUT, Variant.PREFILL_GEMM_64x256, Variant.PREFILL_GEMM_64_ROWS):
+        with variants(flags):
             out, osp, oss = ops.gemv_pair(wp, xs, rows, N, K, epi, ss_in=ss if norm else None, residual=res, want_split=True,
                                           want_ss=epi == L.EPI_RESID, wdtype=L.W_H2)
             outs.append((out.clone(), osp.clone(), None if oss is None else oss.clone()))
-    finally:
-        L.lib().vaura_set_debug_flags(0)
     torch.cuda.synchronize()
     for o in outs[1:]:
         assert torch.equal(o[0], outs[0][0]) and torch.equal(o[1], outs[0][1])

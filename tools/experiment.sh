@@ -3,13 +3,13 @@
 #     gpurun --timeout 900 -- 'bash tools/experiment.sh <name> [args]'
 # Everything lands under gpurun_out/<name>/ (scratch; copy what should be judged into profiles/).
 #
-#   loop-ab [flags,flags,..] [rounds]   interleaved A/B of kernel variants (vaura_set_debug_flags values; tools/README.md lists the bits) over
+#   loop-ab [flags,flags,..] [rounds]   interleaved A/B of kernel variants (vaura_set_debug_flags values; vaura_amd/csrc/variants.h is the table) over
 #                                       whole 228-step graph-replayed loops of the PRODUCT library, both storages, + per-stage eager averages
 #   stamps [flags ..]                   in-kernel s_memrealtime timeline of the one-launch MLP (diagnostic build;
 #                                       ALLWAVES=1: every wave records — perturbs heavily)
 #   lib-ab [tags ..]                    whole 228-step loops on experiment builds (`python -m vaura_amd.csrc.build --tag T -DX=..` -> libvaura_hip_T.so) next to the
 #                                       product library, two rounds, both storages
-#   graph-steps                         decode steps per graph launch (debug flag bits 24..27): 1 / 4 / 12, alternating
+#   graph-steps                         decode steps per graph launch (the GRAPH_STEPS field, bits 24..27 of the first word): 1 / 4 / 12, alternating
 #   chains                              the batch as 2 / 4 independent decode chains on separate streams against one chain of all rows
 #   plain-stores                        write-through output stores (product) against ordinary ones (build --plain-stores), alternating
 #   codec-pmc                           SQ wait / issue / LDS counters of the codec kernels (mfma_driver codec 8 under rocprofv3 --pmc, four passes), per kernel

@@ -9,25 +9,23 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from vaura_amd import synth  # noqa: E402
 from vaura_amd.engine import AvclipEngine  # noqa: E402
+from vaura_amd.variants import from_env, variants  # noqa: E402
 
 B = int(sys.argv[1]) if len(sys.argv) > 1 else 8
 dev = "cuda:0"
-FLAGS = int(os.environ.get("VAURA_DEBUG_FLAGS", "0"))    # A/B: 128 = one-thread-per-query space attention
-FLAGS2 = int(os.environ.get("VAURA_DEBUG_FLAGS2", "0"))  # second flag word: 32 = linears on one LDS stage (two barriers per k-step)
-if FLAGS or FLAGS2:
-    from vaura_amd import _lib as L  # noqa: E402
-    L.lib().vaura_set_debug_flags(FLAGS)
-    L.lib().vaura_set_debug_flags2(FLAGS2)
-eng = AvclipEngine(synth.FULL_AVCLIP, synth.avclip_state_dict(seed=0), dev)
-frames = torch.randn(B, 4, 3, 16, 224, 224, device=dev)
-for _ in range(2):
-    eng.forward(frames)
-torch.cuda.synchronize()
-t0 = time.perf_counter()
-n = 5
-for _ in range(n):
-    out = eng.forward(frames)
-torch.cuda.synchronize()
+# A/B: VAURA_DEBUG_FLAGS=VIT_SPACE_THREAD_PER_QUERY (128), VAURA_DEBUG_FLAGS2=LINEAR_REGISTER_STAGED (32); names or integers
+FLAGS, FLAGS2 = from_env()
+with variants(FLAGS, FLAGS2):
+    eng = AvclipEngine(synth.FULL_AVCLIP, synth.avclip_state_dict(seed=0), dev)
+    frames = torch.randn(B, 4, 3, 16, 224, 224, device=dev)
+    for _ in range(2):
+        eng.forward(frames)
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    n = 5
+    for _ in range(n):
+        out = eng.forward(frames)
+    torch.cuda.synchronize()
 dt = (time.perf_counter() - t0) / n
 c = synth.FULL_AVCLIP
 L = 1 + c.t * c.n

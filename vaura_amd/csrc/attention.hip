@@ -269,19 +269,13 @@ template <> struct KvT<2> {
 
 // NU = number of 64-position passes that hold cached rows (0..4).  One straight-line body per NU: the compiler
 // then waits with exact vmcnt values (vmcnt retires in order), and short caches issue no dead loads.
-struct NoHook {
-  __device__ __forceinline__ void operator()() const {}
-};
-// `after_requests`: called once every request of the attention itself has been issued (the fused attention + wo launch queues
-// its wo weight requests there: behind the K/V rows, which the dependent chain needs first)
-template <int HD, int NU, typename HOOK = NoHook, int KVT = 0>
+template <int HD, int NU, int KVT = 0>
 __device__ __forceinline__ void attention256_body(const float* __restrict__ qkv, const float* __restrict__ qkv2,
                                                   const float* __restrict__ rope,
                                                   float* __restrict__ kc, float* __restrict__ vc, float* __restrict__ out,
                                                   uint16_t* __restrict__ outp, int n_head, int pos, f32x4* sqkv,
                                                   f32x4 (*wacc)[HD / 4], float* wm, float* wl, float pscale = 1.f,
-                                                  HOOK after_requests = HOOK(), uint8_t* __restrict__ ksc = nullptr,
-                                                  uint8_t* __restrict__ vsc = nullptr) {
+                                                  uint8_t* __restrict__ ksc = nullptr, uint8_t* __restrict__ vsc = nullptr) {
   constexpr int QUADS = HD / 4;   // 24
   constexpr int QPL = QUADS / 8;  // 3
   constexpr int NW = ATT1_THREADS / 64;
@@ -335,7 +329,6 @@ __device__ __forceinline__ void attention256_body(const float* __restrict__ qkv,
     if constexpr (KVT == 3) vsb[u] = vsc[p];
   }
 
-  after_requests();
   VA_STAMP(stamps, 1);                       // every request issued
   VA_WAIT_VM(2 * NU * (QPL + (KVT == 3 ? 1 : 0)));
   VA_STAMP(stamps, 2);                       // the new q / k / v quads (written by the previous kernel) and the rope entry have landed
@@ -510,11 +503,11 @@ __global__ __launch_bounds__(ATT1_THREADS) void attention_step256_kernel(
   uint8_t* ksc = kscale + soff;
   uint8_t* vsc = vscale + soff;
   switch ((pos + 63) >> 6) {
-    case 0: attention256_body<HD, 0, NoHook, KVT>(qkv, qkv2, rope, kc, vc, out, outp, n_head, pos, sqkv, wacc, wm, wl, pscale, NoHook(), ksc, vsc); break;
-    case 1: attention256_body<HD, 1, NoHook, KVT>(qkv, qkv2, rope, kc, vc, out, outp, n_head, pos, sqkv, wacc, wm, wl, pscale, NoHook(), ksc, vsc); break;
-    case 2: attention256_body<HD, 2, NoHook, KVT>(qkv, qkv2, rope, kc, vc, out, outp, n_head, pos, sqkv, wacc, wm, wl, pscale, NoHook(), ksc, vsc); break;
-    case 3: attention256_body<HD, 3, NoHook, KVT>(qkv, qkv2, rope, kc, vc, out, outp, n_head, pos, sqkv, wacc, wm, wl, pscale, NoHook(), ksc, vsc); break;
-    default: attention256_body<HD, 4, NoHook, KVT>(qkv, qkv2, rope, kc, vc, out, outp, n_head, pos, sqkv, wacc, wm, wl, pscale, NoHook(), ksc, vsc); break;
+    case 0: attention256_body<HD, 0, KVT>(qkv, qkv2, rope, kc, vc, out, outp, n_head, pos, sqkv, wacc, wm, wl, pscale, ksc, vsc); break;
+    case 1: attention256_body<HD, 1, KVT>(qkv, qkv2, rope, kc, vc, out, outp, n_head, pos, sqkv, wacc, wm, wl, pscale, ksc, vsc); break;
+    case 2: attention256_body<HD, 2, KVT>(qkv, qkv2, rope, kc, vc, out, outp, n_head, pos, sqkv, wacc, wm, wl, pscale, ksc, vsc); break;
+    case 3: attention256_body<HD, 3, KVT>(qkv, qkv2, rope, kc, vc, out, outp, n_head, pos, sqkv, wacc, wm, wl, pscale, ksc, vsc); break;
+    default: attention256_body<HD, 4, KVT>(qkv, qkv2, rope, kc, vc, out, outp, n_head, pos, sqkv, wacc, wm, wl, pscale, ksc, vsc); break;
   }
 }
 
@@ -1081,8 +1074,8 @@ int va_launch_attention(const VaAttentionStep& a, hipStream_t s) {
   if (int rc = va_kv_check(kv, a.head_dim, split, true)) return rc;
   if (split) {   // few (row, head) pairs over a long cache: split the range, then combine
     if (a.n_split > 8) return VAURA_ERR_ARG;
-    // arrivals (rows * n_head zeroed words, e.g. the decoder's ws_sync + 512): the last split to arrive merges; debug flag bit 19: own launch
-    uint32_t* arrivals = (va_debug_flags_get() & 0x80000u) ? nullptr : a.arrivals;
+    // arrivals (rows * n_head zeroed words, e.g. the decoder's ws_sync + 512): the last split to arrive merges
+    uint32_t* arrivals = va_variant(VV_ATTN_MERGE_OWN_LAUNCH) ? nullptr : a.arrivals;
     VA_LAUNCH(attention_split_kernel<96>, dim3(a.n_head, a.rows, a.n_split), dim3(ATT1_THREADS), 0, s, a.pos_dev, kv.k, kv.v, a.qkv, a.qkv2,
               a.rope, a.n_head, kv.max_len, a.pos_host, a.part, arrivals, a.out, a.out_split, a.pscale);
     if (!arrivals)
@@ -1125,13 +1118,12 @@ int va_launch_rope_append_rows(const vaura_decoder* d, int layer, int p0, int n_
   });
 }
 
-extern unsigned va_debug_flags;   // gemv3.hip; bit 4: the per-position prefill attention (A/B of the MFMA kernel)
 int va_launch_attention_prefill(const vaura_decoder* d, int layer, int p0, int n_pos, hipStream_t s) {
   const int H = d->dims.n_head, rows16 = (d->rows + 15) / 16 * 16;
   const float pscale = ldexpf(1.f, -d->plane_shift);
   const VaKvCache kv = va_kv_cache(d, layer);
   if (int rc = va_kv_check(kv, d->dims.d_model / H, false, false)) return rc;
-  if (kv.dtype == 0 && (va_debug_flags & 16u)) {      // fp32 only: one workgroup per (row, head, position)
+  if (kv.dtype == 0 && va_variant(VV_PREFILL_ATTN_PER_POSITION)) {      // fp32 only: one workgroup per (row, head, position)
     const size_t smem = sizeof(float) * (size_t)(3 * 96 + 4 * 96 + 8 + kv.max_len + 4);
     VA_LAUNCH(attention_step_kernel<96>, dim3(H, d->rows, n_pos), dim3(ATT_THREADS), smem, s, d->ws_qkv, (const float*)nullptr, d->rope, kv.k,
               kv.v, d->ws_attn, d->ws_attn_split, H, kv.max_len, nullptr, p0, rows16, pscale);

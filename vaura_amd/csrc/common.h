@@ -5,6 +5,7 @@
 #include <stdint.h>
 #include <type_traits>
 #include "../../include/vaura_hip.h"
+#include "variants.h"      // va_variant / va_variant_field: the kernel-variant switches for A/B measurements
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
@@ -239,8 +240,6 @@ struct VaAttentionStep {             // one decode-step attention: rope + cache 
 int va_launch_attention(const VaAttentionStep& a, hipStream_t s);
 struct Gemv3Args;
 static inline bool va_is_fp8(int wdtype) { return wdtype == VAURA_W_FP8 || wdtype == VAURA_W_FP8H; }   // e4m3 tile pairs (both activation arithmetics)
-unsigned va_debug_flags2_get();  // vaura_set_debug_flags2: the second word
-unsigned va_debug_flags_get();   // vaura_set_debug_flags (gemv3.hip): kernel-variant switches for A/B measurements
 int va_pack_weight_fp8(const float* src, void* dst, int64_t N, int64_t K, hipStream_t s);
 int va_pack_weight_h(const float* src, void* dst, int64_t N, int64_t K, int planes, hipStream_t s);   // fp16 plane(s) + row scales
 int va_launch_gemv3(const Gemv3Args& a, int64_t n_weight_rows, int64_t K, int epilogue, bool norm, hipStream_t s);
@@ -304,7 +303,7 @@ int va_launch_score_nll(const float* logits, int rows_per_pos, int p0, int n_pos
 int va_launch_score_reduce(float* nll, uint8_t* mask, float* logits_out, int B, int K, int V, int Ta, int n_scored, const int32_t* delays_host,
                            float* loss_per_cb, float* loss, const int32_t* clip_T, hipStream_t s);
 
-// Epoch of an in-launch hand-off (mlp_engine.h, the attention + wo experiment): neither the flag words in global memory nor the arrival
+// Epoch of an in-launch hand-off (mlp_engine.h): neither the flag words in global memory nor the arrival
 // words in LDS are ever reset — a hand-off passes when every producer's word holds THIS launch's epoch — so no two launches that can
 // see each other's words may share an epoch.  epoch = (sequence id state[3], 10 bits | launch-epoch counter state[5], 17 bits | layer)
 // + 1.  state[5] is OWNED BY THE LIBRARY: bumped by whatever ends a decode step (the sampler's last workgroup, advance_kernel), never

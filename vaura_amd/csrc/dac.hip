@@ -1034,11 +1034,11 @@ static int launch_conv(const vaura_conv& cv, const float* in, const float* res, 
     }
     // pairs 1: three matrix instructions per product; 2: weights in one fp16 plane (WS); 4, "f16": hi planes only (WS and XS).
     // 96-column tiles where the width allows, else 64.  256-row workgroups (half the weight bytes through L2 per output) where two
-    // per CU still fill the chip; debug flag bit 20: never.  The f16 mode has no 64-column instance of them.
+    // per CU still fill the chip.  The f16 mode has no 64-column instance of them.
     const bool xs = pairs == 4, ws = xs || pairs == 2;
     const int ni = cv.cout % BN == 0 ? 3 : 2, tiles = cv.cout / (32 * ni);
     const int g256 = (p.jcount + 2 * BM - 1) / (2 * BM);
-    const bool big = (ni == 3 || !xs) && !(va_debug_flags_get() & 0x100000u) && (int64_t)g256 * tiles * B * ph >= 384;
+    const bool big = (ni == 3 || !xs) && !va_variant(VV_CODEC_128_ROWS) && (int64_t)g256 * tiles * B * ph >= 384;
     if (big) ++va_conv256_launches;
     VA_LAUNCH(conv_pair_instance(ni, ws, xs, big), dim3(big ? g256 : (p.jcount + BM - 1) / BM, tiles, B * ph), dim3(256), 0, s, p);
     return 0;
@@ -1074,7 +1074,7 @@ static long long va_conv_units_fused = 0;
 static int launch_conv_unit(const vaura_conv& c7, const vaura_conv& c1, const float* in, const float* res, const float* alpha_mid,
                             const float* alpha_next, float* out_raw, float* out_act, int B, int L, int pairs, hipStream_t s) {
   if (pairs != 1 && pairs != 2 && pairs != 4) return VA_UNIT_NOT_ELIGIBLE;
-  if (va_debug_flags_get() & (0x200000u | 0x100000u)) return VA_UNIT_NOT_ELIGIBLE;       // debug flag bit 21: the two-launch form (bit 20: no 256-row instances at all)
+  if (va_variant(VV_CODEC_UNIT_TWO_LAUNCHES) || va_variant(VV_CODEC_128_ROWS)) return VA_UNIT_NOT_ELIGIBLE;
   const int C = c7.cin;
   if ((C != BN && C != 2 * BN) || c7.cout != C || c1.cin != C || c1.cout != C || c7.stride != 1 || c1.stride != 1 || c1.taps != 1 || c7.taps < 1 ||
       (c7.taps - 1) * c7.dilation > XHALO || !c7.w || !c7.bias || !c1.w || !c1.bias || !alpha_mid || !alpha_next || !res || !out_act || (const float*)out_act == in)
@@ -1230,7 +1230,7 @@ __global__ __launch_bounds__(256) void snake_kernel(const float* __restrict__ x,
 static int launch_conv_out(const vaura_conv& co, const float* A, float* wav, int B, int L, int pr, hipStream_t s) {
   const int C = co.cin;
   if (co.cout != 1 || co.taps != 7 || (C % 4)) return VAURA_ERR_SHAPE;
-  if (C <= 128 && C % 8 == 0 && !(va_debug_flags_get() & 8192)) {     // debug flag bit 13: the untiled kernel
+  if (C <= 128 && C % 8 == 0 && !va_variant(VV_CODEC_LAST_CONV_UNTILED)) {
     const size_t sm = sizeof(float) * ((size_t)(CO_TL + 6) * (C + 4) + CO_TL);
     static unsigned long long big = 0;
     if (va_big_lds_once(reinterpret_cast<const void*>(conv_out_tiled_kernel), 80 * 1024, &big)) return VAURA_ERR_STATE;

@@ -3,23 +3,17 @@
 #include "mlp_engine.h"
 #include <cstdlib>
 
-// measurement aid (vaura_set_debug_flags): bit 0 = keep the one-workgroup-per-tile kernels for wo / w2 (A/B of the row split),
-// bit 2 = w1||w3 and w2 as two launches even where the one-launch MLP (mlp_engine.h) is eligible, bits 28..31 = its timing ablations,
-// bit 4 = per-position prefill attention,
-// bit 5 = 64-row prefill GEMM workgroups only, (bits 6 and 8: unused since the linear-layer experiments left, DESIGN_HISTORY.md,)
-// bit 7 = row f2's space attention with one thread per query instead of the MFMA kernel, bit 9 = unsplit CLS attention, bit 10 = time attention with one thread per (head, frame),
-// bit 11 = space attention on the exact-fp32 MFMA instead of fp16 pairs, bit 13 = the codec's last conv without the LDS window
+// the two words of kernel-variant switches and their exported setters: csrc/variants.h is the table of what each bit selects, and
+// va_variant / va_variant_field (there) are the only readers
 unsigned va_debug_flags = 0;
-VA_STAMP_SETTER(vaura_stamps_set_gemv3)
-unsigned va_debug_flags_get() { return va_debug_flags; }
-
-// second flag word (vaura_set_debug_flags2), bit 0: more than one row block -> still ONE row block per weight pass (round 4's walk: the
-// A/B of the two-row-block instances and the control of their bit-identity test); bit 1: the one-launch MLP refuses 17..32 rows;
-// bit 3: fp8 weights keep round 4's one-workgroup-per-tile kernels for wo / w2 (the A/B of the fp8 row-split instances);
-// bit 4: fp8 weights never take the one-launch MLP; bits 5, 6, 12..15: row f2's linear layers (vit.hip)
 unsigned va_debug_flags2 = 0;
+unsigned va_debug_flags_get() { return va_debug_flags; }
 unsigned va_debug_flags2_get() { return va_debug_flags2; }
-static bool rb2(const Gemv3Args& a) { return a.R >= 2 && !(va_debug_flags2 & 1u); }
+extern "C" void vaura_set_debug_flags(unsigned flags) { va_debug_flags = flags; }
+extern "C" void vaura_set_debug_flags2(unsigned flags) { va_debug_flags2 = flags; }
+VA_STAMP_SETTER(vaura_stamps_set_gemv3)
+
+static bool rb2(const Gemv3Args& a) { return a.R >= 2 && !va_variant(VV_ROW_BLOCKS_WALK); }
 
 // RB2 = true: the instance exists with two row blocks per weight pass as well (the decode step's shapes), taken when there are >= 2
 // (XBR = plane batches of THAT instance: with two row blocks' planes and accumulators in registers the K = 1536 instances of two and
@@ -59,14 +53,14 @@ static int dispatch3(const Gemv3Args& a, int64_t tiles, int64_t K, int epilogue,
   constexpr int XB2 = WT == 2 ? 3 : 1, XB4 = 4;
   if constexpr (WT == 1 || WT == 3) {   // fp8 tile pairs (round 5; 3 = against the hi activation plane only, round 6): with 17..32 rows the residual GEMVs on the row-split pair kernel too — one workgroup
     // per tile takes in BOTH row blocks' planes (524 KB at K = 4096 next to 65 KB of weights): 217.5 -> 214.7 ms on the 32-row loop;
-    // at 16 rows the one-workgroup-per-tile kernels stay (162.3 against 164.8 ms).  Second flag word, bit 3: never (the A/B)
-    if (a.R >= 2 && !norm && !(va_debug_flags & 1u) && !(va_debug_flags2 & 8u) && tiles % 8 == 0 && epilogue == E3_RESID) {
+    // at 16 rows the one-workgroup-per-tile kernels stay (162.3 against 164.8 ms)
+    if (a.R >= 2 && !norm && !va_variant(VV_ROWSPLIT_OFF) && !va_variant(VV_FP8_ROWSPLIT_OFF) && tiles % 8 == 0 && epilogue == E3_RESID) {
       if (K == 1536) return launch3h<WT, 3, E3_RESID, 1, 2, 8, true>(a, tiles, s);
       if (K == 4096) return launch3h<WT, 8, E3_RESID, 1, 2, 8, true>(a, tiles, s);
     }
   }
   if constexpr (WT != 1 && WT != 3) {   // narrow outputs without a fused norm (wo, w2): two workgroups per tile, 8 rows each
-    if (!norm && !(va_debug_flags & 1u) && tiles % 8 == 0 && (epilogue == E3_RESID || epilogue == E3_STORE)) {
+    if (!norm && !va_variant(VV_ROWSPLIT_OFF) && tiles % 8 == 0 && (epilogue == E3_RESID || epilogue == E3_STORE)) {
       if (K == 1536 && epilogue == E3_RESID) return launch3h<WT, 3, E3_RESID, 1, 2, 8, true>(a, tiles, s);
       if (K == 1536 && epilogue == E3_STORE) return launch3h<WT, 3, E3_STORE, 1>(a, tiles, s);
       // fp32 weights at K = 4096: four batches of two k-group pairs, two in flight.  (Three in flight measured the same 11.4 us:
@@ -91,11 +85,11 @@ static int dispatch3(const Gemv3Args& a, int64_t tiles, int64_t K, int epilogue,
 template <int EPI, bool NORM>
 static int launch_gemm3(const Gemv3Args& a, int64_t tiles, int64_t K, hipStream_t s) {
   const int gx = (int)(tiles / (G3M_NW * G3M_T)), gy4 = (a.R + G3M_RB - 1) / G3M_RB, gy8 = (a.R + 7) / 8;
-  // 128-row workgroups once there are enough of them to fill the chip twice over (debug flag bit 14: at >= 64 row blocks whatever the
-  // count, round 2's rule — wo and w2 of a 166-position prompt then run 126 workgroups on 256 CUs)
-  const bool big = !(va_debug_flags & 32u) && ((va_debug_flags & 0x4000u) ? a.R >= 64 : gx * gy8 >= 320);
-  const int remap = (va_debug_flags & 0x8000u) ? 0 : 1;               // bit 15: blocks in launch order
-  const bool pf2 = !(va_debug_flags & 0x10000u) && (K / 32) % 2 == 0;     // bit 16: one weight k-group in flight
+  // 128-row workgroups once there are enough of them to fill the chip twice over (round 2's rule, at >= 64 row blocks whatever the
+  // count: wo and w2 of a 166-position prompt then run 126 workgroups on 256 CUs)
+  const bool big = !va_variant(VV_PREFILL_GEMM_64_ROWS) && (va_variant(VV_GEMM3_ROUND2_TILE_RULE) ? a.R >= 64 : gx * gy8 >= 320);
+  const int remap = va_variant(VV_PREFILL_GEMM_LAUNCH_ORDER) ? 0 : 1;
+  const bool pf2 = !va_variant(VV_GEMM3_ONE_KGROUP) && (K / 32) % 2 == 0;
   const int gy = big ? gy8 : gy4;
   const dim3 grid((unsigned)(gx * gy)), block(G3M_NW * 64);
   if (a.wq == 1 || a.wq == 3) {      // (a prompt pass of the hi-plane-only fp8 storage multiplies both planes: the exact fp8 arithmetic)
@@ -123,7 +117,7 @@ static int launch_gemm4_i(const Gemv3Args& a, int64_t K, int gx, int rb_off, int
   if (va_big_lds_once(reinterpret_cast<const void*>(gemm4_kernel<EPI, NORM, WT, RBW, CT>), SH::LDS, &big)) return VAURA_ERR_STATE;
   const int gy = (n_rb + RBW - 1) / RBW;
   VA_LAUNCH((gemm4_kernel<EPI, NORM, WT, RBW, CT>), dim3((unsigned)(gx * gy)), dim3(G4_NW * 64), SH::LDS, s, a, (int)K, gx, gy,
-            ((va_debug_flags & 0x8000u) ? 0 : 1) | ((va_debug_flags >> 17) & 2),      // bit 18: ablation (no DMA in the loop; timing only)
+            (va_variant(VV_PREFILL_GEMM_LAUNCH_ORDER) ? 0 : 1) | (va_variant(VV_GEMM4_NO_DMA) ? 2 : 0),      // the kernel's remap bits
             rb_off);
   return 0;
 }
@@ -141,19 +135,18 @@ static int launch_gemm4(const Gemv3Args& a, int64_t tiles, int64_t K, hipStream_
   // weight plane two such workgroups share a CU and fill each other's barrier gaps; 96 rows: one dead DMA slot in eight).  And one
   // cut: whole rounds of tall workgroups, then the remaining rows in ONE round of a lower height (a second launch), when that beats a
   // last round that is mostly empty.  A 166-position prompt, two planes: wo / w2 (6 column tiles) 252 x 64 rows; qkv (18) 504 x 96
-  // rows = 1.97 rounds; w1||w3 (32) 512 x 128 rows + 224 x 96 rows instead of 672 x 128 = 2.6 rounds.  Debug flag bit 5: 64 rows only;
-  // bit 22: no cut.
+  // rows = 1.97 rounds; w1||w3 (32) 512 x 128 rows + 224 x 96 rows instead of 672 x 128 = 2.6 rounds.
   const int cand[3] = {8, 6, 4};
   const float eff[3] = {1.0f, 1.03f, a.wq == 2 ? 1.12f : 0.95f};
   auto rounds = [&](int rb, int h) { return (float)((gx * ((rb + h - 1) / h) + 255) / 256); };
   int h1 = 4, h2 = 0, cut = 0;
-  if (!(va_debug_flags & 32u)) {
+  if (!va_variant(VV_PREFILL_GEMM_64_ROWS)) {
     float best = 1e30f;
     for (int i = 0; i < 3; ++i) {
       const float c1 = rounds(a.R, cand[i]) * cand[i] * eff[i];
       if (c1 < best) { best = c1; h1 = cand[i]; h2 = 0; cut = 0; }
       // (one plane: the co-resident 64-row pairs already smooth the last round; a cut measured 3 % slower there)
-      if (cand[i] == 4 || a.wq != 2 || (va_debug_flags & 0x400000u)) continue;
+      if (cand[i] == 4 || a.wq != 2 || va_variant(VV_PREFILL_GEMM_NO_CUT)) continue;
       const int full = gx * ((a.R + cand[i] - 1) / cand[i]) / 256;        // whole rounds of this height
       const int gy1 = full * 256 / gx, rb1 = gy1 * cand[i];
       if (full < 1 || gy1 < 1 || rb1 >= a.R) continue;
@@ -164,8 +157,8 @@ static int launch_gemm4(const Gemv3Args& a, int64_t tiles, int64_t K, hipStream_
     }
   }
   int rc;
-  // two planes, 64-row workgroups chosen (few column tiles): the same number of 128 x 128 workgroups instead (debug flag bit 23: no)
-  if (a.wq == 2 && h1 == 4 && !h2 && !(va_debug_flags & (0x800000u | 32u)))
+  // two planes, 64-row workgroups chosen (few column tiles): the same number of 128 x 128 workgroups instead
+  if (a.wq == 2 && h1 == 4 && !h2 && !va_variant(VV_PREFILL_GEMM_64x256) && !va_variant(VV_PREFILL_GEMM_64_ROWS))
     return launch_gemm4_i<EPI, NORM, 2, 8, 8>(a, K, 2 * gx, 0, a.R, s);
   if (a.wq == 2) {
     rc = launch_gemm4_h<EPI, NORM, 2>(a, K, gx, h1, 0, h2 ? cut : a.R, s);
@@ -179,7 +172,7 @@ static int launch_gemm4(const Gemv3Args& a, int64_t tiles, int64_t K, hipStream_
 
 // many row blocks (a prompt being teacher-forced): GEMM tiling instead of the register-resident GEMV loop
 static int dispatch_gemm3(const Gemv3Args& a, int64_t tiles, int64_t K, int epilogue, bool norm, hipStream_t s) {
-  if (a.wq != 1 && a.wq != 3 && !(va_debug_flags & 0x20000u)) {     // debug flag bit 17: the register-staged gemm3_kernel for every storage
+  if (a.wq != 1 && a.wq != 3 && !va_variant(VV_PREFILL_GEMM_REGISTER_STAGED)) {
     if (epilogue == E3_STORE && norm) return launch_gemm4<E3_STORE, true>(a, tiles, K, s);
     if (epilogue == E3_STORE && !norm) return launch_gemm4<E3_STORE, false>(a, tiles, K, s);
     if (epilogue == E3_RESID && !norm) return launch_gemm4<E3_RESID, false>(a, tiles, K, s);
@@ -230,9 +223,9 @@ int va_launch_gemv3(const Gemv3Args& a0, int64_t n_weight_rows, int64_t K, int e
 // configs[3] (4 rows, 10.24 s) 33.7 k -> 36.9 k tokens/s.
 bool va_mlp_engine_eligible(const vaura_decoder* d) {
   if (!d->ws_sync || !d->state || d->rows < 1 || d->rows > 32) return false;
-  if (d->rows > 16 && (va_debug_flags2 & 2u)) return false;          // second flag word, bit 1: 17..32 rows keep the separate launches
-  // fp8 tile pairs (round 5): the two-row-block instances only (17..32 rows: configs[4]'s per-GPU shape); second flag word, bit 4: no
-  if (va_is_fp8(d->wdtype)) { if (d->rows <= 16 || (va_debug_flags2 & 16u)) return false; }
+  if (d->rows > 16 && va_variant(VV_ENGINE_MAX_16_ROWS)) return false;
+  // fp8 tile pairs (round 5): the two-row-block instances only (17..32 rows: configs[4]'s per-GPU shape)
+  if (va_is_fp8(d->wdtype)) { if (d->rows <= 16 || va_variant(VV_FP8_NO_ENGINE)) return false; }
   else if (d->wdtype != VAURA_W_H1 && d->wdtype != VAURA_W_H2) return false;
   if (d->dims.d_model != 1536 || d->dims.ffn_dim != 4096) return false;
   static int cus[64] = {};
@@ -273,7 +266,7 @@ int va_launch_mlp_engine(const Gemv3Args& a13, const Gemv3Args& a2, const Gemv3A
   e.p1.wscale = weight_scales(a13, 2 * 4096, 1536);
   e.p2.wscale = weight_scales(a2, 1536, 4096);
   e.flags = flags; e.state = state; e.state_rw = state; e.layer = layer;
-  e.abl = (int)((va_debug_flags >> 28) & 15u);      // bits 28..31: timing ablations of the engine (tools only)
+  e.abl = (int)va_variant_field(VF_ENGINE_ABL);
   if (a13.R == 2) {       // 17..32 decoder rows: both row blocks per weight fragment
     if (a13.wq == 1) return aq ? launch_mlp_engine_t<1, true, 2>(e, s) : launch_mlp_engine_t<1, false, 2>(e, s);
     if (a13.wq == 3) return aq ? launch_mlp_engine_t<3, true, 2>(e, s) : launch_mlp_engine_t<3, false, 2>(e, s);
@@ -415,9 +408,6 @@ __global__ void split_rows_kernel(const float* __restrict__ src, uint16_t* __res
 }
 
 extern "C" {
-
-void vaura_set_debug_flags(unsigned flags) { va_debug_flags = flags; }
-void vaura_set_debug_flags2(unsigned flags) { va_debug_flags2 = flags; }
 
 int vaura_split_rows(const float* src, uint16_t* dst, const float* gain, float* ss, int64_t rows, int64_t C, vaura_stream_t s) {
   if (!src || !dst || rows <= 0 || C <= 0 || (C % 16)) return VAURA_ERR_ARG;

@@ -184,7 +184,9 @@ __device__ __forceinline__ void gemv3_epilogue(const Gemv3Args& a, int rb, int t
         const size_t idx = ((size_t)rb * (a.N / 4) + (size_t)tile * 4) * 16 + lane;
         f32x4 o = v[t];
         if constexpr (EPI == E3_RESID) o += (pre && pre->have && T == 1) ? pre->res : reinterpret_cast<const f32x4*>(a.res)[idx];
-        if (keep) keep[t] = o;      // the caller keeps the new residual rows in registers (layer-tail engine: wo's output is w2's residual)
+        // (no caller passes `keep` since the layer-tail engine left, DESIGN_HISTORY.md; taking the parameter out changes the instruction
+        // order of this unit's kernels, so it stays until a change that re-measures them)
+        if (keep) keep[t] = o;
         if (a.out) va_st16(reinterpret_cast<f32x4*>(a.out) + idx, o);
         if (a.ss_out) {
           float s = ((o[0] * o[0] + o[1] * o[1]) + o[2] * o[2]) + o[3] * o[3];

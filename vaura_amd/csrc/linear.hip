@@ -377,16 +377,15 @@ int va_launch_linear_pair(const uint16_t* in, const uint16_t* w, const float* bi
   p.w2 = nullptr; p.bias2 = nullptr; p.alpha_mid = nullptr;
   if (Cout % LBN != 0 || act == 0) return va_launch_conv_pair_tile(p, B, s);      // the 128 x 96 conv tile (dac.hip)
   const int ntiles = Cout / LBN, mtiles = (Lin + 127) / 128;
-  const unsigned f2 = va_debug_flags2_get();
-  // column-tile panel (see linear_dma_kernel): 4 tiles while a tile of the weights is <= 1 MB (K <= 1280), else the whole width;
-  // second flag word bits 12..15 override (1 .. 15 tiles; must divide ntiles)
+  // column-tile panel (see linear_dma_kernel): 4 tiles while a tile of the weights is <= 1 MB (K <= 1280), else the whole width
+  const int forced = (int)va_variant_field(VF_LINEAR_PANEL);
   int panel = (Cin <= 1280 && ntiles % 4 == 0) ? 4 : ntiles;
-  if (((f2 >> 12) & 15u) && ntiles % (int)((f2 >> 12) & 15u) == 0) panel = (int)((f2 >> 12) & 15u);
-  if (((f2 >> 12) & 15u) == 15u) panel = ntiles;
+  if (forced && ntiles % forced == 0) panel = forced;
+  if (forced == 15) panel = ntiles;
   const dim3 grid((unsigned)(((mtiles + 7) / 8) * 8 * ntiles), B);
-  if (f2 & 32u) {                      // second flag word, bit 5: round 4's register-staged kernel
+  if (va_variant(VV_LINEAR_REGISTER_STAGED)) {      // round 4's kernel
     VA_LAUNCH(linear_pair_kernel<2>, grid, dim3(256), 0, s, p, mtiles, ntiles);
-  } else if (f2 & 64u) {               // bit 6: LDS-DMA with the fragments read next to their matrix instructions (one barrier per chunk)
+  } else if (va_variant(VV_LINEAR_DMA_LATE_FRAGMENTS)) {      // one barrier per chunk
     static unsigned long long big2 = 0;
     if (va_big_lds_once(reinterpret_cast<const void*>(linear_dma_kernel<2, 2, 2, false>), 2 * 40 * 1024, &big2)) return VAURA_ERR_STATE;
     VA_LAUNCH((linear_dma_kernel<2, 2, 2, false>), grid, dim3(256), 2 * 40 * 1024, s, p, mtiles, ntiles, panel);

@@ -804,7 +804,7 @@ static int ln(const vaura_vit* v, const float* X, const float* w, const float* b
 // a third of the chip idle and took 205 us for 308 MB — with the partials in `part` (>= n_seq * heads * 8 * 66 floats).
 static int cls_attention(const vaura_vit* v, const float* qkv, uint16_t* out, float* part, int n_seq, int Lseq, int64_t out_stride, hipStream_t s) {
   const int D = v->dim;
-  if (va_debug_flags_get() & 512) {     // debug flag bit 9: the one-workgroup-per-(sequence, head) kernel
+  if (va_variant(VV_VIT_CLS_UNSPLIT)) {
     const size_t sm_cls = sizeof(float) * (size_t)(((Lseq + 3) & ~3) + 4 * VHD + 8);
     VA_LAUNCH(vit_cls_attn_kernel, dim3(v->heads, (unsigned)n_seq), dim3(256), sm_cls, s, qkv, out, Lseq, D, out_stride);
     return 0;
@@ -820,7 +820,7 @@ static int cls_attention(const vaura_vit* v, const float* qkv, uint16_t* out, fl
 // time pattern launcher
 static int time_attention(const vaura_vit* v, const float* qkv, uint16_t* out, int n_seg, hipStream_t s) {
   const int D = v->dim;
-  if ((va_debug_flags_get() & 1024) || (v->heads & 1))      // debug flag bit 10: one thread per (head, frame)
+  if (va_variant(VV_VIT_TIME_THREAD_PER_HEAD_FRAME) || (v->heads & 1))
     VA_LAUNCH(vit_time_attn_kernel<8>, dim3(v->n_patches, n_seg), dim3(128), 0, s, qkv, out, v->n_patches,
               v->heads, D);
   else
@@ -829,16 +829,16 @@ static int time_attention(const vaura_vit* v, const float* qkv, uint16_t* out, i
   return 0;
 }
 
-// space pattern launcher: the fp16-pair MFMA kernel for n_patches + 1 <= 208 keys, else (or under debug flags) the fp32 kernels
+// space pattern launcher: the fp16-pair MFMA kernel for n_patches + 1 <= 208 keys, else (or under a variant switch) the fp32 kernels
 static int space_attention(const vaura_vit* v, const float* qkv, uint16_t* out, int n_seg, hipStream_t s) {
   const int D = v->dim;
-  if (v->n_patches + 1 <= VS_NKT * 16 && !(va_debug_flags_get() & (128 | 2048))) {   // the fp16-pair MFMA kernel
+  if (v->n_patches + 1 <= VS_NKT * 16 && !va_variant(VV_VIT_SPACE_THREAD_PER_QUERY) && !va_variant(VV_VIT_SPACE_FP32_MFMA)) {   // the fp16-pair MFMA kernel
     const size_t sm = (size_t)2 * (VP_KEYS + VP_VROWS) * VP_ROWH * 2;               // 135 KB of the CU's 160 KB
     static unsigned long long big_lds_p = 0;
     if (va_big_lds_once(reinterpret_cast<const void*>(vit_space_attn_pair_kernel), sm, &big_lds_p)) return VAURA_ERR_STATE;
     VA_LAUNCH(vit_space_attn_pair_kernel, dim3(v->heads, v->n_frames, n_seg), dim3(512), sm, s, qkv, out, v->n_frames,
               v->n_patches, D);
-  } else if (v->n_patches + 1 <= VS_NKT * 16 && !(va_debug_flags_get() & 128)) {   // debug flag bit 11: exact-fp32 MFMA; bit 7: one thread per query
+  } else if (v->n_patches + 1 <= VS_NKT * 16 && !va_variant(VV_VIT_SPACE_THREAD_PER_QUERY)) {   // exact-fp32 MFMA
     const size_t sm = sizeof(float) * (size_t)(VS_NKT * 16) * (VSK + VSV);       // 108 KB of the CU's 160 KB
     static unsigned long long big_lds_m = 0;
     if (va_big_lds_once(reinterpret_cast<const void*>(vit_space_attn_mfma_kernel), sm, &big_lds_m)) return VAURA_ERR_STATE;
