@@ -998,6 +998,49 @@ size_t vaura_audio_preprocess_lds_bytes(int o, int n, int w, int taps_per_phase)
 /* output samples per workgroup (VAURA_AUDIO_PRE_TILE as the library was compiled) */
 int vaura_audio_preprocess_tile(void);
 
+/* -------------------------------------------------------------------------------------------
+ * Audio output (csrc/audio_out.hip): the codec's mono fp32 rows at 44.1 kHz -> PCM at the consumer's rate, format and channel
+ * layout, in one launch; one pass or block by block with the filter history carried, the blocks concatenated being the one-pass
+ * result bit for bit.
+ *   x         fp32 (B, in_stride): clip b's block of the stream, samples [r0, r0 + L) of the clip
+ *   records   device, (B, VAURA_AUDIO_OUT_RECORD) int64, 8-byte aligned: r0, L (held to 0 .. in_stride), m0, count (held to
+ *             0 .. out_stride), N.  The launch forms the outputs [m0, m0 + count) of clip b, absolute indices at the output rate, and
+ *             writes them from the start of the clip's row.  N >= 0 is the clip's total input length (this is its last block); N < 0:
+ *             not known yet.  x[s] is 0 for s < 0 and, when N >= 0, for s >= N; nothing at or behind r0 + L is read.
+ *   carry_in  fp32 (B, history): samples [r0 - history, r0) of clip b (zeros in front of the stream's start); NULL with history == 0
+ *   carry_out fp32 (B, history) or NULL: receives the last `history` samples of carry_in ++ block, written by extra workgroups of the
+ *             same launch.  It must not overlap carry_in (a ping-pong pair; VAURA_ERR_ARG when the two (B, history) spans do).
+ *   THE HOST RULE IS PART OF THE CONTRACT.  The kernel serves 0 for an index below the carry row and for one at or behind r0 + L of a
+ *             block that is not final, and it holds the start of a tap run inside the span it staged: memory safety, not arithmetic.
+ *             That no requested output ever needs such an index is the caller's to guarantee — `history` at least
+ *             vaura_amd/audio_out.py: history() of the rate pair, and m0 + count at most releasable(r0 + L) for a block that is not
+ *             final (output_total(N) for a final one).  A smaller history or a larger count gives wrong samples, silently.
+ *             vaura_amd/post.py (audio_to_pcm, PcmStream) is the caller that keeps the rule.
+ *   o, n, w, first, taps, phases, taps_per_phase   the table of the rate pair 44100 -> rate as for vaura_audio_preprocess
+ *             (resample_table(44100, rate)); o == n is the identity, the table is not read and may be NULL.
+ *   gain      device fp32 (B): one factor per clip
+ *   out       format VAURA_PCM_S16 / S32 / F32, C_out (1 .. 8) copies of the mono value: planar (B, C_out, out_stride) or,
+ *             interleaved != 0, (B, out_stride, C_out); zeros from `count` to the row's end; nothing outside the B rows is written.
+ *             out_stride == 0 writes no output (out may be NULL): only the carry moves.
+ *   clipped   device int32 (B), ADDED to (the caller zeroes it): samples whose y * scale lay outside the format's range or was NaN
+ * Arithmetic, all fp32: acc = 0, then acc = fmaf(tap_j, x[q o + first[p] - w + j], acc) in tap order for output m = q n + p;
+ * y = acc * gain[b]; S16 = rint(y * 32768), S32 = rint(y * 2^31) (half to even, saturated; NaN -> 0), F32 = y (counted outside
+ * [-1, 1], not altered).
+ * VAURA_ERR_ARG: a NULL required pointer or a misaligned one, B < 1, a negative length, in_stride == 0, phases != n.  VAURA_ERR_DTYPE: an
+ * unknown format.  VAURA_ERR_SHAPE: C_out outside 1 .. 8; more than 64 taps per phase; more than 2^20 table entries; a row of more
+ * than 2^31 - 1 samples; more than 65535 clips; a tile whose input span does not fit 64 KiB of LDS.  All before any launch and without
+ * dereferencing anything.                                                                                                          */
+#define VAURA_AUDIO_OUT_TILE 1024
+#define VAURA_AUDIO_OUT_RECORD 5
+int vaura_audio_output(const float* x, int B, int64_t in_stride, const int64_t* records, const float* carry_in, float* carry_out,
+                       int history, int o, int n, int w, const int32_t* first, const float* taps, int phases, int taps_per_phase,
+                       const float* gain, int format, int interleaved, int C_out, void* out, int64_t out_stride, int32_t* clipped,
+                       vaura_stream_t s);
+/* dynamic LDS bytes of one workgroup of that launch (0 for sizes the kernel does not take) */
+size_t vaura_audio_output_lds_bytes(int o, int n, int w, int taps_per_phase);
+/* output samples per workgroup (VAURA_AUDIO_OUT_TILE as the library was compiled) */
+int vaura_audio_output_tile(void);
+
 /* Measurement aid (tools/pmc_driver, A/B timing): selects kernel variants for launches enqueued (or graphs captured) afterwards.
  * vaura_amd/csrc/variants.h is the table of every bit of both words, by name (e.g. bit 0, ROWSPLIT_OFF: wo / w2 GEMVs as one workgroup
  * per column tile instead of the row-split pair); an entry never changes its value.  0 = the product configuration.   */

@@ -6,14 +6,20 @@ runs in libvaura_hip.so (``vaura_audio_normalize`` / ``vaura_audio_loudness``) o
 CPU path.  The 'loudness' strategy (``scale_audio``'s own default) is ITU-R BS.1770-4 integrated loudness as the reference's dependency
 torchaudio 2.2.1 computes it (``transforms.Loudness``) — third-party and absent here, so it is restated from the published algorithm
 and its parity is UNPINNED, like DAC's; the mp4 mux (PyAV) is host I/O outside this package.
+
+What a player, an Opus / WebRTC sender or the AAC encoder behind ``write_video`` takes is integer PCM at its own rate with its own
+channel count: ``PcmFormat`` / ``audio_to_pcm`` / ``PcmStream`` / ``stream_pcm`` / ``save_pcm_wavs`` turn the device waveform into that
+in one launch of ``vaura_audio_output`` (csrc/audio_out.hip) per call or per streamed block, the blocks concatenated being the one-pass
+result bit for bit (the filter history travels in a carry row on the device).
 """
 from __future__ import annotations
 
-from typing import List, Optional, Sequence
+from typing import Dict, Iterable, Iterator, List, Optional, Sequence, Tuple, Union
 
 import torch
 
 from . import _lib as L
+from . import audio_out as AO
 from . import clip_params
 
 _STRATEGIES = {"clip": 0, "peak": 1, "rms": 2, "": 3, "none": 3}
@@ -155,3 +161,264 @@ def save_wavs(paths: Sequence[str], audio, lengths=None, sample_rate: int = 4410
     host = audio.detach().to("cpu") if isinstance(audio, torch.Tensor) else audio      # one copy for a batch on the device
     for b, path in enumerate(paths):
         save_wav(path, host[b][..., :lens[b]], sample_rate)
+
+
+# ------------------------------------------------------------------------------------------------ PCM at the consumer's rate
+_PCM_FORMATS = {torch.int16: 0, torch.int32: 1, torch.float32: 2}      # VAURA_PCM_S16 / S32 / F32
+
+
+class PcmFormat:
+    """What the consumer of the audio takes: ``rate`` Hz, ``dtype`` int16 / int32 / float32, ``channels`` copies of the mono signal
+    (1 .. 8), interleaved (B, N, C) or planar (B, C, N), and a ``gain`` — one factor, or one per clip — applied before the
+    conversion (the only scaling a stream can have: ``normalize_audio`` needs whole-clip statistics).  Refused here: a rate the
+    resampler's table refuses (8 kHz and below need more than 64 taps per phase from 44.1 kHz), another dtype, ``channels`` outside 1 .. 8."""
+
+    def __init__(self, rate: int = 48000, dtype: torch.dtype = torch.int16, channels: int = 2, interleaved: bool = True,
+                 gain: Union[float, Sequence[float]] = 1.0):
+        if dtype not in _PCM_FORMATS:
+            raise L.VauraHipError(f"VAURA_ERR_DTYPE: PCM output is int16, int32 or float32; got {dtype}")
+        if isinstance(channels, bool) or not isinstance(channels, int) or not 1 <= channels <= AO.MAX_CHANNELS:
+            raise L.VauraHipError(f"VAURA_ERR_SHAPE: {channels!r} output channels; 1 .. {AO.MAX_CHANNELS}")
+        self.plan = AO.plan(rate)                                         # raises for rates the table refuses
+        self.rate, self.dtype, self.channels, self.interleaved = rate, dtype, channels, bool(interleaved)
+        if clip_params.is_per_clip(gain):
+            self.gain = [float(g) for g in (gain.tolist() if hasattr(gain, "tolist") else gain)]
+        else:
+            self.gain = float(gain)
+
+    def gains(self, clips: int) -> List[float]:
+        if isinstance(self.gain, list):
+            if len(self.gain) != clips:
+                raise L.VauraHipError(f"PcmFormat.gain has {len(self.gain)} values for a batch of {clips} clips")
+            return self.gain
+        return [self.gain] * clips
+
+    def __repr__(self):
+        return (f"PcmFormat(rate={self.rate}, dtype={self.dtype}, channels={self.channels}, interleaved={self.interleaved}, "
+                f"gain={self.gain})")
+
+
+_pcm_tables: Dict[Tuple[int, str], tuple] = {}
+
+
+def _pcm_table(pl: AO.OutputPlan, dev: torch.device):
+    """(first, taps tap-major (T, n)) of a rate on a device, built once"""
+    key = (pl.rate, str(dev))
+    if key not in _pcm_tables:
+        _pcm_tables[key] = (pl.table["first"].to(dev), pl.table["weights"].t().contiguous().to(dev))
+    return _pcm_tables[key]
+
+
+class _RecordRing:
+    """Pinned (B, 5) int64 buffers for the per-clip records, allocated once and reused in turn.  A slot is taken again only when the
+    copy that last read it has finished (its event is queried, never waited for); while it has not, a fresh pinned tensor serves
+    that one push, so the host never waits for the device."""
+    SLOTS = 4
+
+    def __init__(self, clips: int):
+        self.clips, self.slots, self.events, self.at = clips, [], [], 0
+
+    def send(self, records: List[List[int]], dev: torch.device) -> torch.Tensor:
+        host = torch.tensor(records, dtype=torch.int64)
+        if len(self.slots) < self.SLOTS:
+            self.slots.append(torch.empty(self.clips, AO.RECORD, dtype=torch.int64).pin_memory())
+            self.events.append(torch.cuda.Event())
+            i = len(self.slots) - 1
+        else:
+            i, self.at = self.at, (self.at + 1) % self.SLOTS
+            if not self.events[i].query():                                # still in flight: leave the slot alone
+                return host.pin_memory().to(dev, non_blocking=True)
+        self.slots[i].copy_(host)
+        rec = self.slots[i].to(dev, non_blocking=True)
+        self.events[i].record(torch.cuda.current_stream(dev))
+        return rec
+
+
+_pcm_rings: Dict[Tuple[int, str], _RecordRing] = {}
+_pcm_gains: Dict[Tuple[tuple, str], torch.Tensor] = {}
+
+
+def _pcm_gain(gains: List[float], dev: torch.device) -> torch.Tensor:
+    """the per-clip gains on the device, built once per (values, device)"""
+    key = (tuple(gains), str(dev))
+    if key not in _pcm_gains:
+        if len(_pcm_gains) >= 16:
+            _pcm_gains.clear()
+        _pcm_gains[key] = torch.tensor(gains, dtype=torch.float32).to(dev)
+    return _pcm_gains[key]
+
+
+def _pcm_launch(fmt: PcmFormat, x: torch.Tensor, in_stride: int, records: List[List[int]], gain: Optional[torch.Tensor],
+                carry_in: Optional[torch.Tensor], carry_out: Optional[torch.Tensor], n_row: int,
+                ring: Optional[_RecordRing] = None) -> torch.Tensor:
+    """One launch of vaura_audio_output over ``x`` (B rows of ``in_stride`` fp32 samples on a HIP device) -> the PCM tensor with its
+    ``clipped`` counts.  The records travel by one asynchronous copy from a pinned buffer of ``ring`` (default: the one kept per batch
+    size and device); ``gain`` None: ``fmt``'s, cached on the device.  Nothing here waits for the device."""
+    dev, B, pl = x.device, len(records), fmt.plan
+    if not x.is_cuda:
+        raise L.VauraHipError("PCM output runs on the HIP device that holds the decoded waveform; there is no CPU path")
+    lib = L.lib()
+    if not pl.identity and lib.vaura_audio_output_lds_bytes(pl.o, pl.n, pl.w, pl.T) > 64 * 1024:
+        raise L.VauraHipError(f"VAURA_ERR_SHAPE: {pl.source} -> {pl.rate} Hz: the input span of one tile does not fit 64 KiB of LDS")
+    with torch.cuda.device(dev):
+        first, taps = (None, None) if pl.identity else _pcm_table(pl, dev)
+        if ring is None:
+            ring = _pcm_rings.setdefault((B, str(dev)), _RecordRing(B))
+        rec = ring.send(records, dev)
+        if gain is None:
+            gain = _pcm_gain(fmt.gains(B), dev)
+        shape = (B, n_row, fmt.channels) if fmt.interleaved else (B, fmt.channels, n_row)
+        out = torch.empty(shape, dtype=fmt.dtype, device=dev)
+        clipped = torch.zeros(B, dtype=torch.int32, device=dev)
+        history = 0 if carry_in is None else carry_in.shape[-1]
+        L.check(lib.vaura_audio_output(L.ptr(x), B, in_stride, L.ptr(rec), L.ptr(carry_in), L.ptr(carry_out), history,
+                                       pl.o if not pl.identity else 1, pl.n if not pl.identity else 1, pl.w if not pl.identity else 0,
+                                       L.ptr(first), L.ptr(taps), pl.n if not pl.identity else 1, pl.T,
+                                       L.ptr(gain), _PCM_FORMATS[fmt.dtype], int(fmt.interleaved), fmt.channels,
+                                       L.ptr(out) if n_row else 0, n_row, L.ptr(clipped), L.current_stream(dev)), "vaura_audio_output")
+    out.clipped = clipped
+    return out
+
+
+def _mono_rows(wav: torch.Tensor, what: str) -> torch.Tensor:
+    """(B, 1, N) or (1, N) fp32 on a HIP device -> contiguous (B, 1, N)"""
+    if not torch.is_tensor(wav) or wav.dim() not in (2, 3) or wav.shape[-2] != 1:
+        raise L.VauraHipError(f"{what} takes the codec's mono waveform, (B, 1, N) or (1, N); got "
+                              f"{tuple(wav.shape) if torch.is_tensor(wav) else type(wav).__name__}")
+    if wav.dim() == 2:
+        wav = wav[None]
+    return wav.to(torch.float32).contiguous()
+
+
+def audio_to_pcm(wav: torch.Tensor, fmt: PcmFormat, lengths=None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """wav (B, 1, N) fp32 at 44.1 kHz on a HIP device -> (pcm, pcm_lengths): ``pcm`` (B, N_out, C) — planar: (B, C, N_out) — of
+    ``fmt.dtype`` on the same device, ``pcm_lengths`` (B,) int64 on the host, ``pcm.clipped`` (B,) int32 on the device: the samples that
+    left the format's range.  ``lengths`` (the "audio_lengths" of a ragged ``generate()``): clip b is exactly the clip converted alone
+    at its own length, zeros follow it, and nothing behind ``lengths[b]`` is read."""
+    x = _mono_rows(wav, "audio_to_pcm")
+    B, N = x.shape[0], x.shape[-1]
+    if N < 1:
+        raise L.VauraHipError(f"a waveform of shape {tuple(wav.shape)} holds no samples")
+    if lengths is None:
+        n_in = [N] * B
+    else:
+        if not clip_params.is_per_clip(lengths):
+            raise L.VauraHipError(f"lengths must be one integer per clip (a list, tuple or 1-D tensor), got {lengths!r}")
+        n_in = clip_params._int_list("lengths", lengths)
+        if len(n_in) != B:
+            raise L.VauraHipError(f"per-clip lengths has {len(n_in)} values for a batch of {B} clips")
+        if min(n_in) < 1 or max(n_in) > N:
+            raise L.VauraHipError(f"lengths must lie in 1 .. {N} (the samples of a row), got {n_in}")
+    n_out = [fmt.plan.output_total(n) for n in n_in]
+    if max(n_out) > (1 << 31) - 1:
+        raise L.VauraHipError(f"VAURA_ERR_SHAPE: output rows of {max(n_out)} samples; at most {(1 << 31) - 1}")
+    fmt.gains(B)                                                         # refuses another count than B before any device work
+    records = [[0, n, 0, m, n] for n, m in zip(n_in, n_out)]             # the stream's one and last block, from its start
+    pcm = _pcm_launch(fmt, x, N, records, None, None, None, max(n_out))
+    return pcm, torch.tensor(n_out, dtype=torch.int64)
+
+
+class PcmStream:
+    """``audio_to_pcm`` block by block: ``push`` takes the next samples of every clip and returns the PCM that can no longer change.
+    The pushes concatenated per clip are bit for bit ``audio_to_pcm`` of the whole clips.  State: two integers per clip on the host
+    (samples received, outputs emitted) and a ping-pong pair of carry rows on the device (``audio_out.history()`` samples per clip).
+    One push is one launch and one asynchronous copy of a (B, 5) record from a pinned buffer the stream keeps; nothing waits for the
+    device."""
+
+    def __init__(self, fmt: PcmFormat, batch: int, device):
+        if isinstance(batch, bool) or not isinstance(batch, int) or batch < 1:
+            raise L.VauraHipError(f"PcmStream takes a batch of at least one clip, got {batch!r}")
+        self.fmt, self.batch, self.device = fmt, batch, torch.device(device)
+        if self.device.type == "cuda" and self.device.index is None:
+            self.device = torch.device("cuda", torch.cuda.current_device())
+        gains = fmt.gains(batch)
+        self.received, self.emitted, self.finished = [0] * batch, [0] * batch, [False] * batch
+        H = fmt.plan.history()
+        self._carry = torch.zeros(2, batch, H, dtype=torch.float32, device=self.device) if H else None
+        self._cur = 0
+        self._gains, self._ring = gains, _RecordRing(batch)
+        self._empty = torch.zeros(batch, 1, 1, dtype=torch.float32, device=self.device)
+
+    def _per_clip(self, name, value, kind):
+        if clip_params.is_per_clip(value):
+            vals = [kind(v) for v in (value.tolist() if hasattr(value, "tolist") else value)]
+            if len(vals) != self.batch:
+                raise L.VauraHipError(f"{name} has {len(vals)} values for a stream of {self.batch} clips")
+            return vals
+        return [kind(value)] * self.batch
+
+    def push(self, audio: Optional[torch.Tensor], samples=None, final=False) -> Tuple[torch.Tensor, List[int]]:
+        """audio (B, 1, n) fp32 on the stream's device: the next ``samples[b]`` samples of clip b (default: all n; 0 is allowed, and
+        ``audio`` may be None when every clip gives 0) -> (pcm (B, max(counts), C) or planar (B, C, max(counts)), counts): clip b's next
+        ``counts[b]`` output samples, zeros behind them.  ``final`` (a bool, or one per clip) flushes the clip's tail up to
+        ``output_total`` of everything it received; a finished clip takes no more samples."""
+        if audio is None:
+            x, n = self._empty, 0
+        else:
+            x = _mono_rows(audio, "PcmStream.push")
+            n = x.shape[-1]
+            if x.shape[0] != self.batch or x.device != self.device:
+                raise L.VauraHipError(f"PcmStream of {self.batch} clips on {self.device}: got a block of shape {tuple(audio.shape)} on {x.device}")
+            if n == 0:
+                x = self._empty
+        counts_in = [n] * self.batch if samples is None else self._per_clip("samples", samples, int)
+        fin = self._per_clip("final", final, bool)
+        if min(counts_in) < 0 or max(counts_in) > n:
+            raise L.VauraHipError(f"samples must lie in 0 .. {n} (the samples of a block's row), got {counts_in}")
+        for b in range(self.batch):
+            if self.finished[b] and counts_in[b]:
+                raise L.VauraHipError(f"clip {b} of the stream was flushed (final) and takes no more samples; got {counts_in[b]}")
+        records, received, emitted = AO.push_records(self.fmt.plan, self.received, self.emitted, counts_in, fin)
+        counts = [r[3] for r in records]
+        if max(counts) > (1 << 31) - 1:
+            raise L.VauraHipError(f"VAURA_ERR_SHAPE: output rows of {max(counts)} samples; at most {(1 << 31) - 1}")
+        carry_in = carry_out = None
+        if self._carry is not None:
+            carry_in, carry_out = self._carry[self._cur], self._carry[1 - self._cur]
+        pcm = _pcm_launch(self.fmt, x, max(n, 1), records, None, carry_in, carry_out, max(counts), ring=self._ring)
+        self._cur = 1 - self._cur
+        self.received, self.emitted = received, emitted
+        self.finished = [a or b for a, b in zip(self.finished, fin)]
+        return pcm, counts
+
+
+def stream_pcm(blocks: Iterable[dict], fmt: PcmFormat) -> Iterator[dict]:
+    """Wrap a streaming generator (``generate_stream``, ``generate_long_stream`` with or without ``block_frames``,
+    ``generate_long_clips_stream``): every dict comes back with "pcm" (the block's audio in ``fmt``), "pcm_start" and "pcm_samples" (one
+    int per clip: where the block's output samples start in the clip's PCM and how many there are) and "pcm_clipped" (B int32 on the
+    device) added.  A clip's samples are ``frames`` times the hop (``audio.shape[-1] // max(frames)``).  The resampler holds a few
+    output samples back until their right-hand neighbours exist; the dict whose "final" is true carries every clip's tail."""
+    stream = None
+    for blk in blocks:
+        audio = blk["audio"]
+        B = audio.shape[0]
+        frames = blk["frames"]
+        frames = [int(f) for f in frames] if isinstance(frames, (list, tuple)) else [int(frames)] * B
+        hop = audio.shape[-1] // max(frames) if max(frames) > 0 else 0
+        if stream is None:
+            stream = PcmStream(fmt, B, audio.device)
+        start = list(stream.emitted)
+        pcm, counts = stream.push(audio, [f * hop for f in frames], final=bool(blk["final"]))
+        out = dict(blk)
+        out.update(pcm=pcm, pcm_start=start, pcm_samples=counts, pcm_clipped=pcm.clipped)
+        yield out
+
+
+def save_pcm_wavs(paths: Sequence[str], pcm: torch.Tensor, lengths, fmt: PcmFormat) -> None:
+    """The counterpart of ``save_wavs`` for ``audio_to_pcm``'s result: clip b's first ``lengths[b]`` frames go to ``paths[b]`` as an
+    int16, int32 or 32-bit float wav of ``fmt.channels`` channels at ``fmt.rate`` Hz (scipy.io.wavfile)."""
+    from scipy.io import wavfile
+    clips = pcm.shape[0]
+    lens = _host_lengths(lengths)
+    if len(paths) != clips or len(lens) != clips:
+        raise L.VauraHipError(f"{len(paths)} paths and {len(lens)} lengths for {clips} clips")
+    if pcm.dtype != fmt.dtype or pcm.dim() != 3 or pcm.shape[2 if fmt.interleaved else 1] != fmt.channels:
+        raise L.VauraHipError(f"a PCM tensor of shape {tuple(pcm.shape)} and {pcm.dtype} is not {fmt!r}")
+    host = pcm.detach().to("cpu")
+    if not fmt.interleaved:
+        host = host.transpose(1, 2)                                       # wavfile takes (frames, channels)
+    for b, path in enumerate(paths):
+        if lens[b] < 0 or lens[b] > host.shape[1]:
+            raise L.VauraHipError(f"lengths must lie in 0 .. {host.shape[1]} (the frames of clip {b}), got {lens}")
+        data = host[b, :lens[b]].contiguous().numpy()
+        wavfile.write(path, fmt.rate, data[:, 0] if fmt.channels == 1 else data)
