@@ -326,6 +326,21 @@ int vaura_unpack_rows(const float* src, float* dst, int64_t rows, int64_t C, vau
 int vaura_prefill_cond(const vaura_dims* d, const float* feats, const void* fc1, const void* fc2, int wdtype,
                        float* tmp, float* out, int64_t n_rows, vaura_stream_t s);
 
+/* The condition buffer of a live session, updated in place (dec->cond_proj is baked into a captured step graph; row index
+ * row * Tv + token, Tv = dec->n_cond_tokens).  ONE launch, for every decoder row:
+ *   conditional rows [0, batch): tokens [shift_tokens, Tv) move down to [0, Tv - shift_tokens) (0: nothing moves), then tokens
+ *     [first_token, first_token + n_tokens) are taken from new_rows — packed rows (batch * n_tokens x cond_dim), row index
+ *     b * n_tokens + t: the output of vaura_prefill_cond on the clips' n_tokens fresh feature rows;
+ *   null-condition rows [batch, 2 batch) (dec->rows == 2 dec->batch): nothing moves — the null embedding belongs to the window
+ *     position —, tokens [first_token, first_token + n_tokens) are taken from null_rows, packed rows (Tv x cond_dim), row index =
+ *     token: the projected null embedding, one copy for every clip.  Ignored (may be NULL) without those rows.
+ * Tokens outside both ranges keep what they hold.  One work item per (row, 4-column quad) walks the tokens in ascending order and
+ * reads token j + shift before it writes token j; items touch disjoint addresses.
+ * VAURA_ERR_ARG: dec, dec->cond_proj or new_rows NULL, null_rows NULL with the null rows present, rows neither batch nor 2 batch, a
+ * negative shift_tokens / first_token, n_tokens <= 0; VAURA_ERR_SHAPE: shift_tokens > Tv, first_token + n_tokens > Tv, cond_dim % 4.   */
+int vaura_cond_window(const vaura_decoder* dec, const float* new_rows, const float* null_rows, int shift_tokens, int first_token,
+                      int n_tokens, vaura_stream_t s);
+
 /* -------------------------------------------------------------------------------------------
  * a14 Pattern.build_pattern_sequence (codebook_patterns.py:180-207) for DelayedPatternProvider
  * (:390-406).  codes (B,K,T) int32 with -1 = unknown -> seq (B,K,T+K); special = d_codebook.     */

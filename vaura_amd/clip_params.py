@@ -411,3 +411,53 @@ def stream_schedule(T: int, lengths: Optional[List[int]], start: int, delays: Op
         out.append((j - prev, [(a, z) for a, z in zip(done, upto)]))
         prev, done = j, upto
     return out
+
+
+# ---- video in while audio streams out (live.LiveSession): how far the decode loop may run on the video received so far.  The decoder
+# reads video only in the embed of a step (csrc/step.hip embed_kernel, launched by va_launch_embed): the step at position p takes
+# condition token p // tokens_per_frame when that is < Tv, and ``empty_video_emb`` otherwise.  Pure bookkeeping, no tensors.
+def video_step_bound(n_tokens: int, Tv: int, tokens_per_frame: int, start: int, seq_len: int) -> int:
+    """Sampled steps of a loop that starts sampling at step ``start`` (``start`` - 1 teacher-forced positions in front of them) that may
+    run once the first ``n_tokens`` of the ``Tv`` condition tokens have arrived.  Sampled step j (0-based) embeds position ``start`` - 1 +
+    j, so it reads token (start - 1 + j) // tokens_per_frame: allowed while that is < n_tokens, i.e. j < n_tokens * tokens_per_frame -
+    (start - 1); positions from Tv * tokens_per_frame on read no video at all, so the whole window releases all ``seq_len`` - ``start``
+    steps.  0 when not even the teacher-forced positions are covered."""
+    n_tokens, Tv, tpf, start, seq_len = int(n_tokens), int(Tv), int(tokens_per_frame), int(start), int(seq_len)
+    if tpf < 1 or Tv < 1 or start < 1 or seq_len < start or n_tokens < 0:
+        raise _error(f"video_step_bound: tokens_per_frame {tpf}, Tv {Tv}, start {start}, seq_len {seq_len}, n_tokens {n_tokens}")
+    total = seq_len - start
+    if n_tokens >= Tv:
+        return total
+    return max(0, min(total, n_tokens * tpf - (start - 1)))
+
+
+def live_schedule(T: int, start: int, delays: Optional[List[int]], block_frames: int, tokens_per_frame: int, Tv: int,
+                  tokens_per_push: int, num_codebooks: Optional[int] = None) -> List[List[tuple]]:
+    """The pieces of a live session's first chunk: ``stream_schedule`` (halo 0: a frame is released once its TOKENS are final; the codec
+    halo is kept on global frames, ``longform._Held``) cut additionally at the video bound.  Entry i holds the pieces that may run once
+    push i has brought the received tokens to min(Tv, (i + 1) * ``tokens_per_push``): a list of (n_steps, (lo, hi)) — after the piece's
+    n_steps further sampled steps the frames [lo, hi) are final (``final_frames``; lo == hi: none).  ceil(Tv / tokens_per_push) entries;
+    every piece has at least one step, the steps of all entries sum to S - ``start`` and the ranges tile [0, T) in order."""
+    block_frames = check_block_frames(block_frames)
+    if delays is None:
+        if num_codebooks is None:
+            raise _error("live_schedule needs the delays or the number of codebooks")
+        delays = list(range(int(num_codebooks)))
+    if isinstance(tokens_per_push, bool) or not isinstance(tokens_per_push, int) or tokens_per_push < 1:
+        raise _error(f"tokens_per_push must be a positive number of condition tokens, got {tokens_per_push!r}")
+    d_max = max(int(d) for d in delays)
+    S = T + d_max + 1
+    ends, j = [], 0
+    for n, _ in stream_schedule(T, None, start, delays, 0, block_frames, num_codebooks):
+        j += n
+        ends.append(j)
+    out, prev, done = [], 0, 0
+    for i in range(-(-int(Tv) // tokens_per_push)):
+        bound = video_step_bound(min(int(Tv), (i + 1) * tokens_per_push), Tv, tokens_per_frame, start, S)
+        pieces = []
+        for j in sorted({e for e in ends if prev < e < bound} | ({bound} if bound > prev else set())):
+            upto = final_frames(j, T, start, d_max)
+            pieces.append((j - prev, (done, upto)))
+            prev, done = j, upto
+        out.append(pieces)
+    return out

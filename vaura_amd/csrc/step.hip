@@ -148,6 +148,48 @@ int va_launch_embed(const vaura_decoder* d, int pos_host, int n_pos, hipStream_t
   return 0;
 }
 
+// ------------------------------------------------------------------------------------ live condition window
+// The condition buffer of a live session (include/vaura_hip.h vaura_cond_window): cond_proj is baked into the captured step graph, so
+// the window slides IN PLACE.  One work item per (decoder row, column quad), walking the tokens in ascending order: token j + shift is
+// read before token j is written, and an item touches no address another item touches — no LDS, no barrier, no atomics.  A
+// conditional row moves tokens [shift, Tv) down to [0, Tv - shift) and takes its n fresh tokens from new_rows (packed rows, row index
+// row * n + t); a null-condition row (row >= B, CFG engines) does not move — the null embedding belongs to the window POSITION, not to
+// the video's clock — and takes tokens [first, first + n) of null_rows (packed rows, row index = token).  16-byte loads and stores only.
+__global__ __launch_bounds__(64) void cond_window_kernel(float* cond_proj, const float* __restrict__ new_rows,
+                                                         const float* __restrict__ null_rows, int B, int Tv, int cond_dim, int shift,
+                                                         int first, int n) {
+  const int row = blockIdx.x;
+  const int cq = blockIdx.y * 64 + threadIdx.x;   // 4-column quad
+  if (cq >= cond_dim / 4) return;
+  f32x4* dst = reinterpret_cast<f32x4*>(cond_proj);
+  if (row >= B) {
+    for (int t = 0; t < n; ++t)
+      dst[packed_quad(row * Tv + first + t, cq, cond_dim)] = reinterpret_cast<const f32x4*>(null_rows)[packed_quad(first + t, cq, cond_dim)];
+    return;
+  }
+  if (shift > 0)
+    for (int j = 0; j + shift < Tv; ++j) {
+      const f32x4 v = dst[packed_quad(row * Tv + j + shift, cq, cond_dim)];
+      dst[packed_quad(row * Tv + j, cq, cond_dim)] = v;
+    }
+  for (int t = 0; t < n; ++t)
+    dst[packed_quad(row * Tv + first + t, cq, cond_dim)] = reinterpret_cast<const f32x4*>(new_rows)[packed_quad(row * n + t, cq, cond_dim)];
+}
+
+extern "C" int vaura_cond_window(const vaura_decoder* d, const float* new_rows, const float* null_rows, int shift_tokens,
+                                 int first_token, int n_tokens, vaura_stream_t s) {
+  if (!d || !d->cond_proj || !new_rows) return VAURA_ERR_ARG;
+  const int Tv = d->n_cond_tokens, cd = d->dims.cond_dim;
+  if (d->batch <= 0 || Tv <= 0 || (d->rows != d->batch && d->rows != 2 * d->batch)) return VAURA_ERR_ARG;
+  if (d->rows != d->batch && !null_rows) return VAURA_ERR_ARG;
+  if (shift_tokens < 0 || first_token < 0 || n_tokens <= 0) return VAURA_ERR_ARG;
+  if (shift_tokens > Tv || (int64_t)first_token + n_tokens > Tv) return VAURA_ERR_SHAPE;
+  if (cd <= 0 || (cd % 4)) return VAURA_ERR_SHAPE;
+  VA_LAUNCH(cond_window_kernel, dim3(d->rows, (cd / 4 + 63) / 64), dim3(64), 0, as_stream(s), const_cast<float*>(d->cond_proj), new_rows,
+            null_rows, d->batch, Tv, cd, shift_tokens, first_token, n_tokens);
+  return 0;
+}
+
 extern "C" int vaura_build_token_table(const float* tok_emb, const float* proj_w, const float* proj_b, float* table, int K,
                                        int vocab1, int cdim, int tok_dim, vaura_stream_t s) {
   if (!tok_emb || !proj_w || !proj_b || !table || K <= 0) return VAURA_ERR_ARG;

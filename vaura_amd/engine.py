@@ -269,6 +269,7 @@ class DecoderEngine:
         self._shape = None
         self.delays: Optional[tuple] = None  # codebook delay pattern of the prepared shape (None = 0..K-1)
         self._graph, self._graph_key = None, None
+        self.live_owner = None               # the live session whose first chunk is in the buffers (begin_live), until the next prepare()
         self.weight_bytes = sum(t.numel() * t.element_size() for t in self._keep)
 
     # ------------------------------------------------------------------ helpers
@@ -314,6 +315,7 @@ class DecoderEngine:
         max_len = (max(S, block_size or 0) + 31) // 32 * 32
         key = (batch, timesteps, n_cond_tokens, cfg_on, tokens_per_frame, max_len, delays)
         self._fc = None                       # whoever prepares the engine is about to overwrite the K/V cache
+        self.live_owner = None                # ... and the sequence of a live session's first chunk (live.LiveSession checks before it goes on)
         if self._shape == key:
             return
         if getattr(self, "state", None) is not None:      # an unread status bit must survive the reallocation below
@@ -949,12 +951,99 @@ class DecoderEngine:
         got = torch.gather(buf, 2, step)
         return torch.where(t[None, None, :] < cnt[:, None, None], got, torch.full_like(got, fill))
 
+    def _pinned_words(self):
+        """The state words of the two pieces in flight, on the host."""
+        if getattr(self, "_stream_pinned", None) is None:
+            self._stream_pinned = [torch.zeros(8, dtype=torch.int32).pin_memory() for _ in range(2)]
+        return self._stream_pinned
+
+    def enqueue_piece(self, slot: int, n_prefill: int, n_steps: int, sp: L.Sampling, noise, use_graph: bool = True) -> "torch.cuda.Event":
+        """A bounded number of steps of a begun sequence (``_begin_sequence`` / ``begin_live``), on the current stream: ``n_prefill``
+        teacher-forced positions and ``n_steps`` sampled ones from where the device state word stands, the state words copied to the
+        pinned host buffer ``slot`` (0 | 1) behind them, and the returned event behind those.  Once the event has been waited for,
+        ``_stream_status(self._pinned_words()[slot])`` is the status of everything up to the end of this piece."""
+        self.run(n_prefill, n_steps, sp, noise, use_graph)
+        self._pinned_words()[slot].copy_(self.state, non_blocking=True)
+        ev = torch.cuda.Event()
+        ev.record(torch.cuda.current_stream(self.dev))
+        return ev
+
+    def stream_error(self, st: int, last_event) -> "L.VauraHipError":
+        """The error of a dirty status ``st`` read off a piece: waits for ``last_event`` (nothing of the call is running any more) and
+        clears the device word and what ``prepare`` carried, so that the engine is reusable whatever the caller does with the error."""
+        last_event.synchronize()
+        self.state[4:5].zero_()
+        self._carried_status = 0
+        return self._status_error(st)
+
+    # ------------------------------------------------------------------ video in while the loop runs (live.LiveSession)
+    def begin_live(self, call: clip_params.CodesCall, noise=None, owner=None):
+        """``_begin_sequence`` for a call whose video has not arrived yet, on the current stream -> (first sampled step, vaura_sampling,
+        noise on the device or None).  The whole condition buffer is then filled with NaN: a step that reads a token ahead of the
+        video gives non-finite logits, which the status word reports, instead of a wrong sample.  ``append_condition`` brings the
+        tokens in; on an engine with the null-condition rows the null embedding is projected here, once.  ``owner``: kept in
+        ``live_owner`` until the next ``prepare`` — any other call on this engine —, so that a session can tell that its sequence is
+        still the one in the buffers."""
+        if call.tv_lengths is not None or call.lengths is not None or call.P is not None or call.num_candidates != 1 or call.prompt_frames:
+            raise L.VauraHipError("a live sequence takes one length for the whole call, no prompt and num_candidates = 1")
+        c = self.cfg
+        zeros = torch.zeros(call.batch, call.n_video_tokens, c.cond_in, dtype=torch.float32, device=self.dev)
+        _, start, _, sp, noise = self._begin_sequence(call, zeros, None, noise)
+        self._live_null = None
+        if self.rows == 2 * self.batch:
+            self._live_null = self._project_rows(self.uncond.reshape(self.Tv, c.cond_in), "null")
+        self.cond_proj.fill_(float("nan"))
+        self.live_owner = owner
+        return start, sp, noise
+
+    def _project_rows(self, x: torch.Tensor, name: str) -> torch.Tensor:
+        """``vaura_prefill_cond`` on the rows of ``x`` (n, cond_in) -> compact packed rows (n x cond_dim), in buffers of this size kept
+        under ``name``.  A projected row depends on nothing but its own input row: these are the bits ``set_condition`` gives it."""
+        c, n = self.cfg, int(x.shape[0])
+        bufs = getattr(self, "_live_bufs", None)
+        if bufs is None:
+            bufs = self._live_bufs = {}
+        if (name, n) not in bufs:
+            rp = self._rows_padded(n)
+            bufs[(name, n)] = tuple(torch.zeros(rp * w, dtype=torch.float32, device=self.dev) for w in (c.cond_in, c.cond_dim, c.cond_dim))
+        inp, tmp, out = bufs[(name, n)]
+        x = x.to(self.dev, torch.float32).contiguous()
+        st = L.current_stream(self.dev)
+        L.check(self.lib.vaura_pack_rows(L.ptr(x), L.ptr(inp), n, c.cond_in, st), "vaura_pack_rows")
+        L.check(self.lib.vaura_prefill_cond(C.byref(self.dims), L.ptr(inp), L.ptr(self.fc1), L.ptr(self.fc2), L.W_F32, L.ptr(tmp),
+                                            L.ptr(out), n, st), "vaura_prefill_cond")
+        self._cond_keepalive = x
+        return out
+
+    def append_condition(self, feats: torch.Tensor, first_token: int, shift_tokens: int = 0):
+        """``feats`` (B, n, cond_in): n fresh video tokens of every clip into the prepared condition buffer IN PLACE (it is baked into
+        the captured step graph), on the current stream.  The MLP runs on the B * n new rows only; ``vaura_cond_window`` then moves
+        tokens [shift_tokens, Tv) of the conditional rows down by ``shift_tokens`` and writes the new ones at ``first_token``; the
+        null-condition rows take the projected null embedding at the same positions (``begin_live`` computed it; computed here for an
+        engine that ``set_condition`` filled).  ``shift_tokens`` = 0 appends; ``set_condition`` stays the way to set a whole window."""
+        assert self.dec is not None
+        self._fc = None
+        B, n, Cin = feats.shape
+        if B != self.batch or Cin != self.cfg.cond_in or n < 1:
+            raise L.VauraHipError(f"append_condition: features must be ({self.batch}, n, {self.cfg.cond_in}), got {tuple(feats.shape)}")
+        null = None
+        if self.rows == 2 * self.batch:
+            if getattr(self, "_live_null", None) is None:
+                self._live_null = self._project_rows(self.uncond.reshape(self.Tv, self.cfg.cond_in), "null")
+            null = self._live_null
+        new = self._project_rows(feats.reshape(B * n, Cin), "new")
+        L.check(self.lib.vaura_cond_window(C.byref(self.dec), L.ptr(new), L.ptr(null), int(shift_tokens), int(first_token), n,
+                                           L.current_stream(self.dev)), "vaura_cond_window")
+
+    def final_frames(self, steps_run: int, start: int) -> int:
+        """Frames of the begun sequence that are final in every codebook after ``steps_run`` sampled steps (``clip_params.final_frames``):
+        what ``stream_frames`` may read."""
+        return clip_params.final_frames(steps_run, self.T, start, max(self.delays) if self.delays is not None else self.cfg.num_codebooks - 1)
+
     @torch.no_grad()
     def _codes_stream(self, call: clip_params.CodesCall, feats, prompt, noise, block_frames: int, halo: int):
         self.stream_engine = self              # whose seq / per-token buffers the yielded ranges refer to (the twin after a range fallback)
-        if getattr(self, "_stream_pinned", None) is None:      # the state words of the two pieces in flight, on the host
-            self._stream_pinned = [torch.zeros(8, dtype=torch.int32).pin_memory() for _ in range(2)]
-        pinned = self._stream_pinned
+        pinned = self._pinned_words()
         with off_null_stream(self.dev):
             Tp, start, _, sp, dev_noise = self._begin_sequence(call, feats, prompt, noise)
             pieces = clip_params.stream_schedule(self.T, self.lengths, start, self.delays, halo, block_frames, self.cfg.num_codebooks)
@@ -964,10 +1053,7 @@ class DecoderEngine:
             events = []
 
             def enqueue(k):                    # piece k, its state words behind it, its event behind those
-                self.run(start - 1 if k == 0 else 0, pieces[k][0], sp, dev_noise, call.use_graph)
-                pinned[k % 2].copy_(self.state, non_blocking=True)
-                events.append(torch.cuda.Event())
-                events[-1].record(torch.cuda.current_stream(self.dev))
+                events.append(self.enqueue_piece(k % 2, start - 1 if k == 0 else 0, pieces[k][0], sp, dev_noise, call.use_graph))
             enqueue(0)
         emitted = [0] * self.batch
         for k, (_, ranges) in enumerate(pieces):
@@ -977,10 +1063,7 @@ class DecoderEngine:
             events[k].synchronize()
             st = self._stream_status(pinned[k % 2])
             if st:
-                events[-1].synchronize()       # nothing of this call is running any more
-                self.state[4:5].zero_()
-                self._carried_status = 0
-                err = self._status_error(st)
+                err = self.stream_error(st, events[-1])
                 if any(emitted):
                     err.frames_emitted = list(emitted)
                     err.args = (f"{err.args[0]} — after frames {emitted} of the clips had been streamed out: they cannot be taken back",)

@@ -233,7 +233,7 @@ def _long_stream(model, frames, sched, stride_tokens, frame_step, kw, return_rel
 @torch.no_grad()
 def _long_stream_blocks(model, frames, sched, stride_tokens, frame_step, kw, return_relevance, block_frames):
     """``_long_stream`` with audio leaving inside the chunks (``generate_long_stream(block_frames=...)``)."""
-    H, held = _decode_halo(model), _Held(model, return_relevance)            # final and not yet dropped: frames [held.start, known)
+    held = _Held(model, return_relevance)                                   # final and not yet dropped: frames [held.start, known)
     skw = {k: v for k, v in kw.items() if k not in ("return_sampled_indices", "remove_prompts")}      # generate_stream has neither
     prompt_tokens = None
     for c, ch in enumerate(sched):
@@ -245,20 +245,30 @@ def _long_stream_blocks(model, frames, sched, stride_tokens, frame_step, kw, ret
             selected = frames[:, torch.arange(lo, hi, device=frames.device) % frames.shape[1], ...]
             if frame_step != 1:
                 selected = selected[:, :, :, ::frame_step, ...]
-        P, T, off = (0 if prompt_tokens is None else int(prompt_tokens.shape[-1])), ch["max_gen_len"], ch["offset"]
-        chunk = []
-        for blk in model.generate_stream(frames=selected, audio=prompt_tokens, max_new_tokens=T, block_frames=block_frames, decode=False,
-                                         return_relevance=return_relevance, **skw):
-            lo, hi = blk["start_frame"], blk["start_frame"] + blk["frames"]
-            chunk.append(blk["sampled_indices"])
-            if hi > P:                                                      # frames this chunk GENERATED: the others are held already
-                held.add(blk["sampled_indices"][..., max(lo, P) - lo:],
-                         {k: blk[k][..., max(lo, P) - lo:] for k in (REL if return_relevance else ())})
-            known = off + max(hi, P)
-            upto = (known if final else known - H) if hi == T else known - H
-            if upto > held.emitted:
-                yield held.release(upto, final and hi == T)
-        prompt_tokens = torch.cat(chunk, dim=-1)[:, :, stride_tokens:]
+        chunk = yield from _stream_chunk(model, held, selected, prompt_tokens, ch["max_gen_len"], ch["offset"], final, block_frames,
+                                         return_relevance, skw)
+        prompt_tokens = chunk[:, :, stride_tokens:]
+
+
+def _stream_chunk(model, held, selected, prompt_tokens, T, off, final, block_frames, return_relevance, skw):
+    """One chunk of a long-form stream that releases inside its chunks (``_long_stream_blocks``; a live session's chunks c >= 1): the
+    call ``generate_stream(decode=False)`` on the chunk's video ``selected`` and prompt, its generated frames added to ``held``, and
+    the blocks that become due on global frames — chunk offset ``off`` + local frame — yielded.  Returns the chunk's tokens (B, K, T)."""
+    H = _decode_halo(model)
+    P = 0 if prompt_tokens is None else int(prompt_tokens.shape[-1])
+    chunk = []
+    for blk in model.generate_stream(frames=selected, audio=prompt_tokens, max_new_tokens=T, block_frames=block_frames, decode=False,
+                                     return_relevance=return_relevance, **skw):
+        lo, hi = blk["start_frame"], blk["start_frame"] + blk["frames"]
+        chunk.append(blk["sampled_indices"])
+        if hi > P:                                                      # frames this chunk GENERATED: the others are held already
+            held.add(blk["sampled_indices"][..., max(lo, P) - lo:],
+                     {k: blk[k][..., max(lo, P) - lo:] for k in (REL if return_relevance else ())})
+        known = off + max(hi, P)
+        upto = (known if final else known - H) if hi == T else known - H
+        if upto > held.emitted:
+            yield held.release(upto, final and hi == T)
+    return torch.cat(chunk, dim=-1)
 
 
 # ---- one duration per clip: the schedules of the clips merged into one call per chunk index

@@ -399,6 +399,12 @@ class VAURAModel(nn.Module):
         if call.ragged:
             _, lengths, tv_lengths = clip_params.resolve_lengths(B, lengths if lengths is not None else T, tv_lengths, int(vis.shape[1]),
                                                                  0 if P is not None else Tp)
+        return vis.float(), B, Tp, P, lengths, tv_lengths, self._codes_keywords(call, B, Tp, P, tv_lengths, audio)
+
+    def _codes_keywords(self, call: "_GenerateCall", B: int, Tp: int, P, tv_lengths, audio) -> dict:
+        """The keywords of ``DecoderEngine.generate_codes`` for a bound call: B clips, the common (or shortest) prompt length Tp, the
+        per-clip prompt lengths P or None, and the encoded prompt."""
+        K, T, delays = self.num_codebooks, call.t_max, call.delays
         if self.sampler.audio_tokens_per_video_frame is None:
             raise L.VauraHipError("sampler.audio_tokens_per_video_frame must be set (scripts/generate.py:216 sets 7)")
         use_cfg = clip_params.any_cfg(call.sampling["cfg_scale"]) and self.sampler.__class__.__name__ == "Transformer"   # any clip's scale > 1
@@ -411,7 +417,7 @@ class VAURAModel(nn.Module):
                         prompt_lengths=P if per_clip else None, noise=noise, seed=self.seed, clip_base=self.clip_base,
                         tokens_per_frame=self.sampler.audio_tokens_per_video_frame, delays=None if delays == list(range(K)) else delays,
                         return_logprobs=call.want_lp, return_relevance=call.want_rel, num_candidates=call.N, video_lengths=tv_lengths)
-        return vis.float(), B, Tp, P, lengths, tv_lengths, codes_kw
+        return codes_kw
 
     @torch.no_grad()
     def generate_tokens(self, frames=None, audio: Union[torch.Tensor, None] = None, clip_indices=None,
@@ -690,25 +696,40 @@ class VAURAModel(nn.Module):
         for ranges in blocks:
             eng = first.stream_engine          # the engine whose sequence these ranges refer to (the exact-fp32 twin after a range fallback)
             starts, counts = [lo for lo, _ in ranges], [hi - lo for lo, hi in ranges]
-            with off_null_stream(eng.dev) as caller:
-                blk = {"sampled_indices": eng.stream_frames(eng.seq, ranges, self.special_token_id).to(torch.int64)}
-                if decode:
-                    blk["audio"] = codec.decode_window_seq(eng.seq, starts, counts, lengths, eng.delays)
-                if call.want_lp:
-                    blk["logprobs"] = eng.stream_frames(eng.logprobs, ranges, 0.0)
-                if call.want_rel:
-                    blk["logprob_cond"] = eng.stream_frames(eng.logprobs_cond, ranges, 0.0)
-                    blk["logprob_null"] = eng.stream_frames(eng.logprobs_null, ranges, 0.0)
-                    blk["relevance"] = blk["logprob_cond"] - blk["logprob_null"]
-            if caller is not None:
-                for t in blk.values():
-                    t.record_stream(caller)
+            blk = self._stream_block(eng, ranges, call, lengths if decode else False)
             if ragged:
                 blk.update(start_frames=starts, frames=counts)
             else:
                 blk.update(start_frame=starts[0], frames=counts[0])
             blk["final"] = all(hi == n for (_, hi), n in zip(ranges, T_b))
             yield blk
+
+    def _stream_block(self, eng, ranges, call: _GenerateCall, lengths=False) -> dict:
+        """The tensors of one block of a running loop: the frames ``ranges`` = [(lo_b, hi_b) per clip] out of ``eng``'s pattern
+        sequence, and the per-token values the call asked for.  ``lengths`` not False (None, or T_b per clip): "audio" as well, ONE
+        codec pass over the windows gathered straight from the sequence."""
+        starts, counts = [lo for lo, _ in ranges], [hi - lo for lo, hi in ranges]
+        with off_null_stream(eng.dev) as caller:
+            blk = {"sampled_indices": eng.stream_frames(eng.seq, ranges, self.special_token_id).to(torch.int64)}
+            if lengths is not False:
+                blk["audio"] = self.audio_encoder.decode_window_seq(eng.seq, starts, counts, lengths, eng.delays)
+            if call.want_lp:
+                blk["logprobs"] = eng.stream_frames(eng.logprobs, ranges, 0.0)
+            if call.want_rel:
+                blk["logprob_cond"] = eng.stream_frames(eng.logprobs_cond, ranges, 0.0)
+                blk["logprob_null"] = eng.stream_frames(eng.logprobs_null, ranges, 0.0)
+                blk["relevance"] = blk["logprob_cond"] - blk["logprob_null"]
+        if caller is not None:
+            for t in blk.values():
+                t.record_stream(caller)
+        return blk
+
+    # ------------------------------------------------------------------ video in, segment by segment, while audio streams out
+    def open_live(self, batch: int, block_frames: int = 16, **kw):
+        """A live session (``live.LiveSession``): ``s.push(features=seg)`` / ``s.push(frames=seg)`` take the video one 16-frame segment
+        at a time and return the audio blocks that became due, ``s.close()`` the rest.  The keywords are ``live.open_live``'s."""
+        from .live import open_live
+        return open_live(self, batch, block_frames, **kw)
 
     # ------------------------------------------------------------------ one step, reference signature
     @torch.no_grad()
