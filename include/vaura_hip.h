@@ -212,7 +212,8 @@ typedef struct vaura_decoder {
   /* Bytes of extension that FOLLOW this struct in the caller's memory: 0 (a zero-filled descriptor: none), or
    * sizeof(vaura_decoder_ext) - sizeof(vaura_decoder) when `dec` is the first member of a vaura_decoder_ext (below), or
    * sizeof(vaura_decoder_ext2) - sizeof(vaura_decoder) when that in turn is the first member of a vaura_decoder_ext2, or
-   * sizeof(vaura_decoder_ext3) - sizeof(vaura_decoder) when that is the first member of a vaura_decoder_ext3; anything else is
+   * sizeof(vaura_decoder_ext3) - sizeof(vaura_decoder) when that is the first member of a vaura_decoder_ext3, or
+   * sizeof(vaura_decoder_ext4) - sizeof(vaura_decoder) when that is the first member of a vaura_decoder_ext4; anything else is
    * VAURA_ERR_ARG.  It occupies what was alignment padding in front of `kscale`: no field moved and the struct keeps its size, so a
    * caller compiled against the descriptor without it (and zero-filling it, as every field's default asks) runs unchanged. */
   int32_t ext_bytes;
@@ -303,6 +304,27 @@ typedef struct vaura_decoder_ext3 {
   vaura_decoder_ext2 ext2;  /* ext2.ext.dec.ext_bytes = sizeof(vaura_decoder_ext3) - sizeof(vaura_decoder) */
   const int32_t* row_prompt_steps;
 } vaura_decoder_ext3;
+
+/* vaura_decoder_ext3 with the attention-map request of a call appended behind it.  Every entry point takes `&ext4.ext3.ext2.ext.dec`;
+ * the library reads the fields only when dec.ext_bytes = sizeof(vaura_decoder_ext4) - sizeof(vaura_decoder) (64).
+ *   attn_probs  NULL: no maps — every layer launches the attention instance it always launched.  Otherwise fp32
+ *               (attn_steps, attn_rows, n_head, max_len) in device memory, zeroed by the caller: the decode step at cache position pos
+ *               (the cache holds [0, pos), the new position is key pos) writes, for layer attn_layer, row r < attn_rows and head h, the
+ *               softmax weights p[j] = softmax_j(q . k_j / sqrt(96)), j = 0 .. pos, to
+ *                   attn_probs[((pos - attn_pos0) * attn_rows + r) * n_head + h][0 .. pos]
+ *               and nothing behind them.  They are the numbers the kernel's output is formed from — expf(s_j - m_wave) *
+ *               expf(m_wave - M) * (1 / denom) for a cached key, expf(s_new - M) * (1 / denom) for the new one (csrc/attention.hip) — on
+ *               the fp32 scores of the keys AS STORED (widened fp16 / e4m3; the scaled e4m3 score carries the key's 2^e).  A step with
+ *               pos outside [attn_pos0, attn_pos0 + attn_steps) — the teacher-forced positions in front of the loop — and rows >=
+ *               attn_rows (the null-condition rows) write nothing.  The step's output, cache appends and tokens never depend on it.
+ * Served by the single-round-trip step kernel only: max_len <= 256 (VAURA_ERR_SHAPE otherwise).  VAURA_ERR_ARG, with attn_probs set:
+ * attn_layer outside [0, n_layer), attn_rows outside [1, rows], attn_steps < 1, attn_pos0 < 0.  All before any launch.  A captured step
+ * graph holds the pointer and the four values. */
+typedef struct vaura_decoder_ext4 {
+  vaura_decoder_ext3 ext3;  /* ext3.ext2.ext.dec.ext_bytes = sizeof(vaura_decoder_ext4) - sizeof(vaura_decoder) */
+  float* attn_probs;
+  int32_t attn_layer, attn_pos0, attn_steps, attn_rows;
+} vaura_decoder_ext4;
 
 /* -------------------------------------------------------------------------------------------
  * Weight ingress (once, at load).  Replaces nn.Module.load_state_dict for the streamed matrices.
@@ -588,6 +610,21 @@ int vaura_attention_step_ex(const float* qkv, const float* qkv2, const float* ro
 int vaura_attention_step_kv(const float* qkv, const float* qkv2, const float* rope, float* kcache, float* vcache, uint8_t* kscale,
                             uint8_t* vscale, float* out, uint16_t* out_split, float* part, uint32_t* arrivals, int rows, int n_head,
                             int head_dim, int max_len, int pos, int n_split, int plane_shift, int kv_dtype, vaura_stream_t s);
+/* vaura_attention_step_kv that also reports the softmax weights of the step (vaura_decoder_ext4.attn_probs, through the same launcher):
+ * probs fp32 (n_steps, rows_out, n_head, max_len); the call at `pos` writes probs[((pos - pos0) * rows_out + r) * n_head + h][0 .. pos]
+ * for rows r < rows_out when pos0 <= pos < pos0 + n_steps, and nothing otherwise.  out, out_split and the cache appends are the bits of
+ * vaura_attention_step_kv.  VAURA_ERR_ARG: probs NULL, pos0 < 0, n_steps < 1, rows_out outside [1, rows], and what that entry refuses;
+ * VAURA_ERR_SHAPE: max_len > 256 or n_split > 1 (the generic and range-split kernels report nothing).  Nothing is launched then.      */
+int vaura_attention_step_probs(const float* qkv, const float* qkv2, const float* rope, float* kcache, float* vcache, uint8_t* kscale,
+                               uint8_t* vscale, float* out, uint16_t* out_split, float* part, uint32_t* arrivals, int rows, int n_head,
+                               int head_dim, int max_len, int pos, int n_split, int plane_shift, int kv_dtype, float* probs, int pos0,
+                               int n_steps, int rows_out, vaura_stream_t s);
+/* The attention map of a finished call from its reported weights: probs fp32 (n_steps, n_rows, n_head, max_len) ->
+ *   all_heads = 0: out (n_rows, n_steps, W) = ((p_0 + p_1) + .. + p_{n_head-1}) * (1 / n_head), heads added in index order in fp32
+ *   all_heads = 1: out (n_rows, n_head, n_steps, W), a transposed copy
+ * over columns j < W <= max_len.  VAURA_ERR_ARG: NULL pointers, a count < 1, W > max_len.                                             */
+int vaura_attention_map(const float* probs, float* out, int n_steps, int n_rows, int n_head, int max_len, int W, int all_heads,
+                        vaura_stream_t s);
 /* Op-level access for parity tests: the attention of a teacher-forced chunk [p0, p0 + n_pos) of one layer — rope(q, k) + K / V append of
  * the chunk, then its causal attention over cache positions [0, p0 + n_pos) — on a caller-filled descriptor.  Read: dims (n_layer, n_head,
  * d_model = 96 n_head), rows, max_len, kv_dtype, plane_shift, rope, ws_qkv (packed rows: position z of the chunk is row block(s)

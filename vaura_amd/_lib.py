@@ -81,6 +81,15 @@ class DecoderExt3(C.Structure):
     _fields_ = [("ext2", DecoderExt2), ("row_prompt_steps", C.c_void_p)]
 
 
+class DecoderExt4(C.Structure):
+    """vaura_decoder_ext4: the descriptor with the attention-map request of a call behind everything else: ``attn_probs`` (device fp32
+    (attn_steps, attn_rows, n_head, max_len), zeroed by the caller; NULL: no maps), the layer that reports, the cache position of the
+    first reported step, the number of steps and of rows.  Entry points take ``byref(ext4.ext3.ext2.ext.dec)``; ``dec.ext_bytes`` = 64
+    tells the library that all of it follows."""
+    _fields_ = [("ext3", DecoderExt3), ("attn_probs", C.c_void_p), ("attn_layer", C.c_int32), ("attn_pos0", C.c_int32),
+                ("attn_steps", C.c_int32), ("attn_rows", C.c_int32)]
+
+
 class Conv(C.Structure):
     _fields_ = [("w", C.c_void_p), ("bias", C.c_void_p), ("wscale", C.c_void_p), ("cin", C.c_int32), ("cout", C.c_int32),
                 ("taps", C.c_int32), ("dilation", C.c_int32), ("stride", C.c_int32), ("_pad", C.c_int32)]
@@ -259,6 +268,10 @@ SIGNATURES = {
     "vaura_attention_step_kv": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                           C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                           C.c_int, C.c_void_p]),
+    "vaura_attention_step_probs": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                             C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                             C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    "vaura_attention_map": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "vaura_attention_prefill": (C.c_int, [C.POINTER(Decoder), C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "vaura_dac_decode": (C.c_int, [C.POINTER(Codec), C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "vaura_dac_workspace_elems": (C.c_size_t, [C.POINTER(Codec), C.c_int, C.c_int]),
@@ -319,6 +332,7 @@ def lib() -> C.CDLL:
             fn.argtypes = args
         structs = dict(enumerate([Dims, LayerWeights, Sampling, Decoder, Conv, Codec, CodecEncoder, Vit, VitBlock, ClipSampling, DecoderExt, DecoderExt2]))
         structs[13] = DecoderExt3      # vaura_struct_size: 12 is unassigned
+        structs[14] = DecoderExt4
         for which, cls in structs.items():
             if C.sizeof(cls) != handle.vaura_struct_size(which):
                 raise VauraHipError(f"{LIB_PATH} was built from a different include/vaura_hip.h: sizeof({cls.__name__}) is "

@@ -310,6 +310,47 @@ class CodesCall:
     seed: int
     clip_base: int
     use_graph: bool
+    want_attention: bool = False            # per-step self-attention weights of one layer (``return_attention_weights``)
+    attention_layer: int = -1               # as given: negative counts from the last layer (the engine knows how many there are)
+    attention_heads: str = "mean"           # "mean" | "all"
+
+
+# ---- attention maps of one call (return_attention_weights): what the reporting instance of the decode-step attention serves today.
+ATTENTION_MAX_LEN = 256      # attention_step256_kernel: caches of at most 256 positions
+ATTENTION_HEADS = ("mean", "all")
+
+
+def attention_max_len(seq_len: int, block_size: Optional[int]) -> int:
+    """The cache length ``DecoderEngine.prepare`` allocates for ``seq_len`` sequence steps under the model's ``block_size``."""
+    return (max(int(seq_len), int(block_size or 0)) + 31) // 32 * 32
+
+
+def check_attention_keywords(attention_layer, attention_heads, n_layer: Optional[int] = None) -> int:
+    """The two keywords of a call that asks for attention maps -> the layer as an index in [0, n_layer) (as given while ``n_layer`` is
+    not known).  Negative layers count from the last one, as in Python; out of range is refused."""
+    if attention_heads not in ATTENTION_HEADS:
+        raise _error(f'attention_heads must be "mean" or "all", got {attention_heads!r}')
+    if isinstance(attention_layer, bool) or not isinstance(attention_layer, int):
+        raise _error(f"attention_layer must be an int, got {attention_layer!r}")
+    if n_layer is None:
+        return attention_layer
+    if not -n_layer <= attention_layer < n_layer:
+        raise _error(f"attention_layer {attention_layer} is out of range for a decoder of {n_layer} layers")
+    return attention_layer % n_layer
+
+
+def check_attention_shape(seq_len: int, block_size: Optional[int]) -> None:
+    """Attention maps come from the single-round-trip step kernel: refused where the cache has more than 256 positions."""
+    if int(block_size or 0) > ATTENTION_MAX_LEN or attention_max_len(seq_len, block_size) > ATTENTION_MAX_LEN:
+        raise _error(f"return_attention_weights is served for caches of at most {ATTENTION_MAX_LEN} positions (block_size <= "
+                     f"{ATTENTION_MAX_LEN}); this call has block_size {block_size} and {seq_len} sequence steps")
+
+
+def refuse_attention(where: str, return_attention_weights) -> None:
+    """Callers that do not serve attention maps yet refuse the flag with a message."""
+    if return_attention_weights:
+        raise _error(f"{where} does not return attention weights in this version: generate() / generate_tokens() serve "
+                     "return_attention_weights")
 
 
 @functools.lru_cache(maxsize=None)
@@ -350,10 +391,19 @@ def resolve_codes_call(batch: int, n_video_tokens: int, max_new_tokens, prompt_f
         cfg_on = True
         if not is_per_clip(sampling["cfg_scale"]):
             sampling["cfg_scale"] = [float(sampling["cfg_scale"])] * (B * N)
+    want_attention = bool(a["return_attention_weights"])
+    if want_attention:
+        check_attention_keywords(a["attention_layer"], a["attention_heads"])
+        if N > 1:
+            raise _error(f"return_attention_weights takes num_candidates = 1 in this version (got {N}): one map per clip")
+        if lengths is not None or P is not None:
+            raise _error("return_attention_weights takes one length for the whole call in this version: per-clip max_new_tokens / "
+                         "prompt_lengths are not served together with it")
     return CodesCall(batch=B, n_video_tokens=n_video_tokens, num_candidates=N, t_max=t_max, lengths=lengths, tv_lengths=tv_lengths, P=P,
                      prompt_frames=prompt_frames, cfg_on=cfg_on, want_logprobs=bool(a["return_logprobs"]), want_relevance=want_relevance,
                      tokens_per_frame=a["tokens_per_frame"], delays=a["delays"], seed=a["seed"], clip_base=a["clip_base"],
-                     use_graph=a["use_graph"], **sampling)
+                     use_graph=a["use_graph"], want_attention=want_attention, attention_layer=a["attention_layer"],
+                     attention_heads=a["attention_heads"], **sampling)
 
 
 # ---- audio out of one generate() call while its decode loop still runs (DecoderEngine.generate_codes_stream): which frames may leave

@@ -37,6 +37,11 @@ static int check_decoder(const vaura_decoder* d) {
   }
   if (d->seq_len != d->timesteps + span) return VAURA_ERR_SHAPE;
   if (d->ext_bytes != 0 && !va_decoder_ext(d)) return VAURA_ERR_ARG;      // an extension of another size than vaura_decoder_ext's / _ext2's
+  if (const vaura_decoder_ext4* x = va_attention_maps(d)) {      // attention maps: one layer's reporting instance, refused before any launch
+    if (x->attn_layer < 0 || x->attn_layer >= m.n_layer || x->attn_rows < 1 || x->attn_rows > d->rows || x->attn_steps < 1 || x->attn_pos0 < 0)
+      return VAURA_ERR_ARG;
+    if (d->max_len > 256) return VAURA_ERR_SHAPE;      // the single-round-trip step kernel only (no range split at these lengths)
+  }
   return 0;
 }
 
@@ -162,6 +167,10 @@ static VaAttentionStep attention_step(const vaura_decoder* d, int l) {
   a.pos_dev = d->state;
   a.part = d->ws_attn_part;
   a.n_split = d->ws_attn_part ? va_attention_splits(d->rows, d->dims.n_head, d->max_len) : 1;
+  if (const vaura_decoder_ext4* x = va_attention_maps(d))      // the one layer that reports its softmax weights; every other layer
+    if (l == x->attn_layer) {                                   // launches the instance it always did
+      a.probs = x->attn_probs; a.probs_pos0 = x->attn_pos0; a.probs_steps = x->attn_steps; a.probs_rows = x->attn_rows;
+    }
   return a;
 }
 // ... and to the sampler that ends a step
@@ -362,6 +371,7 @@ size_t vaura_struct_size(int which) {
     case 10: return sizeof(vaura_decoder_ext);
     case 11: return sizeof(vaura_decoder_ext2);
     case 13: return sizeof(vaura_decoder_ext3);      // (12 stays unassigned and answers 0)
+    case 14: return sizeof(vaura_decoder_ext4);
     default: return 0;
   }
 }

@@ -269,13 +269,16 @@ template <> struct KvT<2> {
 
 // NU = number of 64-position passes that hold cached rows (0..4).  One straight-line body per NU: the compiler
 // then waits with exact vmcnt values (vmcnt retires in order), and short caches issue no dead loads.
-template <int HD, int NU, int KVT = 0>
+// PROBS: the reporting instance (vaura_decoder_ext4.attn_probs) — pdst points at this (step, row, head)'s max_len weights, or is NULL
+// for a workgroup that reports nothing (a row or a position outside the request): uniform over the workgroup.
+template <int HD, int NU, int KVT = 0, bool PROBS = false>
 __device__ __forceinline__ void attention256_body(const float* __restrict__ qkv, const float* __restrict__ qkv2,
                                                   const float* __restrict__ rope,
                                                   float* __restrict__ kc, float* __restrict__ vc, float* __restrict__ out,
                                                   uint16_t* __restrict__ outp, int n_head, int pos, f32x4* sqkv,
                                                   f32x4 (*wacc)[HD / 4], float* wm, float* wl, float pscale = 1.f,
-                                                  uint8_t* __restrict__ ksc = nullptr, uint8_t* __restrict__ vsc = nullptr) {
+                                                  uint8_t* __restrict__ ksc = nullptr, uint8_t* __restrict__ vsc = nullptr,
+                                                  float* __restrict__ pdst = nullptr) {
   constexpr int QUADS = HD / 4;   // 24
   constexpr int QPL = QUADS / 8;  // 3
   constexpr int NW = ATT1_THREADS / 64;
@@ -457,6 +460,28 @@ __device__ __forceinline__ void attention256_body(const float* __restrict__ qkv,
   if (lane == 0) { wm[wv] = m; wl[wv] = l; }
   __syncthreads();
   VA_STAMP(stamps, 5);                       // scores, softmax, P.V of every wave done (second barrier)
+  if constexpr (PROBS) {
+    // The weights the output below is formed from: every thread rebuilds M and 1 / denom from the waves' (m, l) — the sums and their
+    // order are those of step 5 — and the sub == 0 lane of each cached position stores expf(sc - m_wave) * expf(m_wave - M) / denom;
+    // one lane stores the new key's.  Entries behind pos are not written (the caller zeroed the buffer).
+    if (pdst) {
+      float M = wm[0];
+#pragma unroll
+      for (int w = 1; w < NW; ++w) M = fmaxf(M, wm[w]);
+      const float en = expf(snew - M);
+      float denom = en;
+#pragma unroll
+      for (int w = 0; w < NW; ++w) denom += expf(wm[w] - M) * wl[w];
+      const float inv = 1.0f / denom;
+      const float fw = expf(m - M);            // this wave's factor: m is its running max
+#pragma unroll
+      for (int u = 0; u < NU; ++u) {
+        const int p = u * 64 + prow;
+        if (sub == 0 && p < pos) pdst[p] = expf(sc[u] - m) * fw * inv;
+      }
+      if (tid == 0) pdst[pos] = en * inv;
+    }
+  }
 
   // ---- 5. combine the 8 waves and the new position
   if (tid < QUADS) {
@@ -508,6 +533,42 @@ __global__ __launch_bounds__(ATT1_THREADS) void attention_step256_kernel(
     case 2: attention256_body<HD, 2, KVT>(qkv, qkv2, rope, kc, vc, out, outp, n_head, pos, sqkv, wacc, wm, wl, pscale, ksc, vsc); break;
     case 3: attention256_body<HD, 3, KVT>(qkv, qkv2, rope, kc, vc, out, outp, n_head, pos, sqkv, wacc, wm, wl, pscale, ksc, vsc); break;
     default: attention256_body<HD, 4, KVT>(qkv, qkv2, rope, kc, vc, out, outp, n_head, pos, sqkv, wacc, wm, wl, pscale, ksc, vsc); break;
+  }
+}
+
+// The reporting instance of the kernel above (vaura_decoder_ext4.attn_probs: the softmax weights of one layer's steps).  A kernel of its
+// own and not a third template argument of attention_step256_kernel: that kernel's symbols and kernel-argument records then stay what
+// they were, byte for byte (profiles/attention_maps_device_code.txt), and the body is shared.  The four new arguments stand at the END:
+// the leading 14 dwords are preloaded into SGPRs and keep their places.
+// probs (n_steps, n_rows, n_head, max_len) fp32: row (pos - pos0, blockIdx.y, blockIdx.x) takes this workgroup's weights 0 .. pos; a
+// workgroup whose row is >= n_rows (the null-condition rows) or whose position lies outside [pos0, pos0 + n_steps) (the tile storages run
+// their prompt through this step) reports nothing.
+template <int HD, int KVT = 0>
+__global__ __launch_bounds__(ATT1_THREADS) void attention_step256_probs_kernel(
+    const int32_t* __restrict__ pos_dev, float* __restrict__ kcache, float* __restrict__ vcache, const float* __restrict__ qkv,
+    const float* __restrict__ qkv2, const float* __restrict__ rope, int n_head, int max_len, int pos_host,
+    float* __restrict__ out, uint16_t* __restrict__ outp, float pscale, uint8_t* __restrict__ kscale, uint8_t* __restrict__ vscale,
+    float* __restrict__ probs, int pos0, int n_steps, int n_rows) {
+  constexpr int QUADS = HD / 4;
+  __shared__ f32x4 sqkv[3 * QUADS + 64];
+  __shared__ f32x4 wacc[ATT1_THREADS / 64][QUADS];
+  __shared__ float wm[ATT1_THREADS / 64], wl[ATT1_THREADS / 64];
+  const int pos = pos_dev ? pos_dev[0] : pos_host;   // cache holds [0, pos), pos <= 255
+  const size_t off = ((size_t)blockIdx.y * n_head + blockIdx.x) * (size_t)max_len * HD;
+  float* kc = reinterpret_cast<float*>(reinterpret_cast<typename KvT<KVT>::E*>(kcache) + off);
+  float* vc = reinterpret_cast<float*>(reinterpret_cast<typename KvT<KVT>::E*>(vcache) + off);
+  const size_t soff = KVT == 3 ? ((size_t)blockIdx.y * n_head + blockIdx.x) * (size_t)max_len : 0;
+  uint8_t* ksc = kscale + soff;
+  uint8_t* vsc = vscale + soff;
+  const int step = pos - pos0;
+  float* pdst = ((int)blockIdx.y < n_rows && step >= 0 && step < n_steps)
+                    ? probs + (((size_t)step * n_rows + blockIdx.y) * n_head + blockIdx.x) * (size_t)max_len : nullptr;
+  switch ((pos + 63) >> 6) {
+    case 0: attention256_body<HD, 0, KVT, true>(qkv, qkv2, rope, kc, vc, out, outp, n_head, pos, sqkv, wacc, wm, wl, pscale, ksc, vsc, pdst); break;
+    case 1: attention256_body<HD, 1, KVT, true>(qkv, qkv2, rope, kc, vc, out, outp, n_head, pos, sqkv, wacc, wm, wl, pscale, ksc, vsc, pdst); break;
+    case 2: attention256_body<HD, 2, KVT, true>(qkv, qkv2, rope, kc, vc, out, outp, n_head, pos, sqkv, wacc, wm, wl, pscale, ksc, vsc, pdst); break;
+    case 3: attention256_body<HD, 3, KVT, true>(qkv, qkv2, rope, kc, vc, out, outp, n_head, pos, sqkv, wacc, wm, wl, pscale, ksc, vsc, pdst); break;
+    default: attention256_body<HD, 4, KVT, true>(qkv, qkv2, rope, kc, vc, out, outp, n_head, pos, sqkv, wacc, wm, wl, pscale, ksc, vsc, pdst); break;
   }
 }
 
@@ -1072,6 +1133,16 @@ int va_launch_attention(const VaAttentionStep& a, hipStream_t s) {
   const bool split = a.part && a.n_split > 1;
   if (!a.qkv || !a.rope || !kv.k || !kv.v || !a.out || a.rows <= 0 || a.n_head <= 0) return VAURA_ERR_ARG;
   if (int rc = va_kv_check(kv, a.head_dim, split, true)) return rc;
+  if (a.probs) {   // the softmax weights: the single-round-trip kernel has the reporting instance, the generic and range-split ones none
+    if (split || kv.max_len > 256) return VAURA_ERR_SHAPE;
+    if (a.probs_pos0 < 0 || a.probs_steps < 1 || a.probs_rows < 1 || a.probs_rows > a.rows) return VAURA_ERR_ARG;
+    return va_kv_dispatch(kv.dtype, [&](auto kvt) -> int {
+      VA_LAUNCH((attention_step256_probs_kernel<96, decltype(kvt)::value>), dim3(a.n_head, a.rows), dim3(ATT1_THREADS), 0, s, a.pos_dev, kv.k, kv.v, a.qkv,
+                a.qkv2, a.rope, a.n_head, kv.max_len, a.pos_host, a.out, a.out_split, a.pscale, kv.kscale, kv.vscale, a.probs, a.probs_pos0,
+                a.probs_steps, a.probs_rows);
+      return 0;
+    });
+  }
   if (split) {   // few (row, head) pairs over a long cache: split the range, then combine
     if (a.n_split > 8) return VAURA_ERR_ARG;
     // arrivals (rows * n_head zeroed words, e.g. the decoder's ws_sync + 512): the last split to arrive merges
@@ -1155,6 +1226,27 @@ extern "C" int vaura_attention_step_kv(const float* qkv, const float* qkv2, cons
   a.pos_host = pos;
   a.part = n_split > 1 ? part : nullptr; a.n_split = n_split; a.arrivals = arrivals;
   a.pscale = ldexpf(1.f, -plane_shift);
+  return va_launch_attention(a, as_stream(s));
+}
+
+// ... that also reports the step's softmax weights (the reporting instance of the single-round-trip kernel)
+extern "C" int vaura_attention_step_probs(const float* qkv, const float* qkv2, const float* rope, float* kcache, float* vcache, uint8_t* kscale,
+                                          uint8_t* vscale, float* out, uint16_t* out_split, float* part, uint32_t* arrivals, int rows,
+                                          int n_head, int head_dim, int max_len, int pos, int n_split, int plane_shift, int kv_dtype,
+                                          float* probs, int pos0, int n_steps, int rows_out, vaura_stream_t s) {
+  if (!probs || pos0 < 0 || n_steps < 1 || rows_out < 1 || rows_out > rows) return VAURA_ERR_ARG;
+  if (pos < 0 || pos >= max_len || n_split < 1 || n_split > 8 || (n_split > 1 && !part)) return VAURA_ERR_ARG;
+  if (plane_shift < 0 || plane_shift > 24 || kv_dtype < 0 || kv_dtype > 3) return VAURA_ERR_ARG;
+  VaAttentionStep a;
+  a.qkv = qkv; a.qkv2 = qkv2; a.rope = rope;
+  a.kv.k = kcache; a.kv.v = vcache; a.kv.dtype = kv_dtype; a.kv.max_len = max_len;
+  if (kv_dtype == 3) { a.kv.kscale = kscale; a.kv.vscale = vscale; }
+  a.out = out; a.out_split = out_split;
+  a.rows = rows; a.n_head = n_head; a.head_dim = head_dim;
+  a.pos_host = pos;
+  a.part = n_split > 1 ? part : nullptr; a.n_split = n_split; a.arrivals = arrivals;
+  a.pscale = ldexpf(1.f, -plane_shift);
+  a.probs = probs; a.probs_pos0 = pos0; a.probs_steps = n_steps; a.probs_rows = rows_out;
   return va_launch_attention(a, as_stream(s));
 }
 

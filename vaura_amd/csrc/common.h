@@ -236,6 +236,10 @@ struct VaAttentionStep {             // one decode-step attention: rope + cache 
   int n_split = 1;
   uint32_t* arrivals = nullptr;      // rows * n_head zeroed words: the last split to arrive merges; NULL: a combine launch follows
   float pscale = 1.f;                // scale of the out_split planes (2^-plane_shift)
+  // softmax weights of the step (vaura_decoder_ext4): NULL = the instances without them.  (probs_steps, probs_rows, n_head, max_len)
+  // fp32; written for rows < probs_rows when probs_pos0 <= position < probs_pos0 + probs_steps
+  float* probs = nullptr;
+  int probs_pos0 = 0, probs_steps = 0, probs_rows = 0;
 };
 int va_launch_attention(const VaAttentionStep& a, hipStream_t s);
 struct Gemv3Args;
@@ -251,21 +255,30 @@ int va_launch_embed(const vaura_decoder* d, int pos_host, int n_pos, hipStream_t
 inline const vaura_decoder_ext* va_decoder_ext(const vaura_decoder* d) {
   return (d->ext_bytes == (int32_t)(sizeof(vaura_decoder_ext) - sizeof(vaura_decoder)) ||
           d->ext_bytes == (int32_t)(sizeof(vaura_decoder_ext2) - sizeof(vaura_decoder)) ||
-          d->ext_bytes == (int32_t)(sizeof(vaura_decoder_ext3) - sizeof(vaura_decoder)))
+          d->ext_bytes == (int32_t)(sizeof(vaura_decoder_ext3) - sizeof(vaura_decoder)) ||
+          d->ext_bytes == (int32_t)(sizeof(vaura_decoder_ext4) - sizeof(vaura_decoder)))
              ? reinterpret_cast<const vaura_decoder_ext*>(d) : nullptr;
 }
 // the per-clip lengths behind those (vaura_decoder_ext2), or NULL
 inline const vaura_decoder_ext2* va_decoder_ext2(const vaura_decoder* d) {
   return (d->ext_bytes == (int32_t)(sizeof(vaura_decoder_ext2) - sizeof(vaura_decoder)) ||
-          d->ext_bytes == (int32_t)(sizeof(vaura_decoder_ext3) - sizeof(vaura_decoder)))
+          d->ext_bytes == (int32_t)(sizeof(vaura_decoder_ext3) - sizeof(vaura_decoder)) ||
+          d->ext_bytes == (int32_t)(sizeof(vaura_decoder_ext4) - sizeof(vaura_decoder)))
              ? reinterpret_cast<const vaura_decoder_ext2*>(d) : nullptr;
 }
 inline const int32_t* va_clip_timesteps(const vaura_decoder* d) { const vaura_decoder_ext2* x = va_decoder_ext2(d); return x ? x->clip_timesteps : nullptr; }
 inline const int32_t* va_clip_cond_tokens(const vaura_decoder* d) { const vaura_decoder_ext2* x = va_decoder_ext2(d); return x ? x->clip_cond_tokens : nullptr; }
 // the per-clip prompt lengths behind those (vaura_decoder_ext3): n_r of every row, or NULL
 inline const int32_t* va_row_prompt_steps(const vaura_decoder* d) {
-  return d->ext_bytes == (int32_t)(sizeof(vaura_decoder_ext3) - sizeof(vaura_decoder))
+  return (d->ext_bytes == (int32_t)(sizeof(vaura_decoder_ext3) - sizeof(vaura_decoder)) ||
+          d->ext_bytes == (int32_t)(sizeof(vaura_decoder_ext4) - sizeof(vaura_decoder)))
              ? reinterpret_cast<const vaura_decoder_ext3*>(d)->row_prompt_steps : nullptr;
+}
+// the attention-map request behind those (vaura_decoder_ext4) when it asks for maps (attn_probs set), or NULL
+inline const vaura_decoder_ext4* va_attention_maps(const vaura_decoder* d) {
+  if (d->ext_bytes != (int32_t)(sizeof(vaura_decoder_ext4) - sizeof(vaura_decoder))) return nullptr;
+  const vaura_decoder_ext4* x = reinterpret_cast<const vaura_decoder_ext4*>(d);
+  return x->attn_probs ? x : nullptr;
 }
 struct VaSampleLaunch {              // one sampler launch over (B, K) rows of logits
   const float* logits = nullptr;

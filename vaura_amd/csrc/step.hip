@@ -1058,6 +1058,41 @@ __global__ __launch_bounds__(256) void select_candidates_kernel(const float* __r
   if (threadIdx.x == 0) winner[b] = best;
 }
 
+// The attention map of a finished call from the weights its steps reported (vaura_decoder_ext4.attn_probs; csrc/attention.hip):
+// probs (n_steps, n_rows, H, max_len) -> out (n_rows, n_steps, W), the mean over the heads — p_0 + p_1 + .. + p_{H-1} added in that
+// order in fp32, times 1 / H once: nn.MultiheadAttention's averaged weights —, or with ALL out (n_rows, H, n_steps, W), a transposed
+// copy.  One work item per output element; columns behind a step's position hold the zeros the caller put there.
+template <bool ALL>
+__global__ __launch_bounds__(256) void attention_map_kernel(const float* __restrict__ probs, float* __restrict__ out, int n_steps, int n_rows,
+                                                            int H, int max_len, int W, long long total) {
+  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= total) return;
+  const int j = (int)(i % W);
+  long long r = i / W;
+  const int step = (int)(r % n_steps);
+  r /= n_steps;
+  if constexpr (ALL) {
+    const int h = (int)(r % H), b = (int)(r / H);
+    out[i] = probs[(((size_t)step * n_rows + b) * H + h) * (size_t)max_len + j];
+  } else {
+    const float* src = probs + ((size_t)step * n_rows + (size_t)r) * H * (size_t)max_len + j;
+    float acc = src[0];
+    for (int h = 1; h < H; ++h) acc += src[(size_t)h * max_len];
+    out[i] = acc * (1.0f / (float)H);
+  }
+}
+
+extern "C" int vaura_attention_map(const float* probs, float* out, int n_steps, int n_rows, int n_head, int max_len, int W, int all_heads,
+                                   vaura_stream_t s) {
+  if (!probs || !out || n_steps < 1 || n_rows < 1 || n_head < 1 || max_len < 1 || W < 1 || W > max_len) return VAURA_ERR_ARG;
+  const long long total = (long long)n_rows * (all_heads ? n_head : 1) * n_steps * W;
+  if (total > 0x7fffffffLL * 256) return VAURA_ERR_SHAPE;
+  const dim3 grid((unsigned)((total + 255) / 256));
+  if (all_heads) VA_LAUNCH(attention_map_kernel<true>, grid, dim3(256), 0, as_stream(s), probs, out, n_steps, n_rows, n_head, max_len, W, total);
+  else VA_LAUNCH(attention_map_kernel<false>, grid, dim3(256), 0, as_stream(s), probs, out, n_steps, n_rows, n_head, max_len, W, total);
+  return 0;
+}
+
 // What vaura_sample_clips / _logprobs / _relevance share: the rules of the standalone and the sequence form, the records' check, the
 // launch.  Each entry point states its own required pointers first.
 static int sample_step(const float* logits, int B, int K, int vocab, const vaura_sampling* sp, const vaura_clip_sampling* clips,

@@ -372,9 +372,14 @@ class DecoderEngine:
             self.clip_P = torch.zeros(batch, dtype=torch.int32, device=self.dev)
         self.lengths = self.video_lengths = None      # the host lists of the call being run (None: every clip has T / Tv)
         self.prompt_lengths = None                    # likewise: P of every clip of the batch (None: one prompt length for the call)
-        self.dec_ext3 = L.DecoderExt3()    # the descriptor + the relevance pointers + the per-clip lengths + the prompt lengths behind it (all NULL: the descriptor alone)
+        # the descriptor + the relevance pointers + the per-clip lengths + the prompt lengths + the attention-map request behind it (all
+        # NULL: the descriptor alone).  ext_bytes says how much of it the library reads: the ext3 part, and the whole of it only in a call
+        # that asks for attention maps (_set_attention)
+        self.dec_ext4 = L.DecoderExt4()
+        self.dec_ext3 = self.dec_ext4.ext3
         self.dec_ext2 = self.dec_ext3.ext2
-        self.dec_ext = self.dec_ext2.ext   # views: byref(self.dec) points into dec_ext3
+        self.dec_ext = self.dec_ext2.ext   # views: byref(self.dec) points into dec_ext4
+        self.attn_probs = None             # the reported weights of the call being run (return_attention_weights), else None
         d = self.dec_ext.dec
         d.ext_bytes = C.sizeof(L.DecoderExt3) - C.sizeof(L.Decoder)
         d.dims = self.dims
@@ -506,6 +511,7 @@ class DecoderEngine:
         self.lengths = None if lengths is None else list(lengths)
         self.video_lengths = None if video_lengths is None else list(video_lengths)
         self._set_prompt_lengths(None)     # a call has per-clip prompt lengths only where it says so right after this (generate_codes)
+        self._set_attention(None, 0, 0)    # ... and attention maps likewise
 
     def _set_prompt_lengths(self, prompt_lengths: Optional[Sequence[int]]):
         """The per-clip prompt lengths of the call about to run (one int per clip of the prepared batch, candidates repeated; already
@@ -518,6 +524,39 @@ class DecoderEngine:
             self.clip_P.copy_(torch.tensor(list(prompt_lengths), dtype=torch.int32))
         self.dec_ext3.row_prompt_steps = L.ptr(self.row_n) if prompt_lengths is not None else 0
         self.prompt_lengths = None if prompt_lengths is None else list(prompt_lengths)
+
+    def _set_attention(self, layer: Optional[int], pos0: int, n_steps: int):
+        """The attention-map request of the call about to run (``layer`` None: none — the descriptor ends behind its ext3 part, as in
+        every call before this keyword existed).  Otherwise layer ``layer`` reports the softmax weights of the ``n_steps`` decode steps
+        from cache position ``pos0`` on, for the ``batch`` conditional rows: (n_steps, batch, n_head, max_len) fp32, zeroed here on the
+        current stream — 4 * n_steps * batch * 16 * max_len bytes, 30 MB at 8 clips x 228 steps x 256 positions.  The buffer is kept
+        while the shape of the request stays, so that such calls replay one captured graph."""
+        x, d = self.dec_ext4, self.dec
+        if layer is None:
+            self.attn_probs = None
+            x.attn_probs, x.attn_layer, x.attn_pos0, x.attn_steps, x.attn_rows = 0, 0, 0, 0, 0
+            d.ext_bytes = C.sizeof(L.DecoderExt3) - C.sizeof(L.Decoder)
+            return
+        shape = (int(n_steps), self.batch, self.cfg.nhead, self.max_len)
+        buf = getattr(self, "_attn_buf", None)
+        if buf is None or tuple(buf.shape) != shape or buf.device != self.dev:
+            self._attn_buf = None          # (freed before the new one is allocated)
+            buf = self._attn_buf = torch.empty(shape, dtype=torch.float32, device=self.dev)
+        buf.zero_()                        # entries behind a step's position are never written
+        self.attn_probs = buf
+        x.attn_probs, x.attn_layer, x.attn_pos0, x.attn_steps, x.attn_rows = L.ptr(buf), int(layer), int(pos0), int(n_steps), self.batch
+        d.ext_bytes = C.sizeof(L.DecoderExt4) - C.sizeof(L.Decoder)
+
+    def attention_map(self, heads: str = "mean") -> torch.Tensor:
+        """The map of the finished call from ``attn_probs`` (``vaura_attention_map``): (batch, n_steps, S - 1), the fixed-order mean over
+        the heads, or with ``heads="all"`` (batch, n_head, n_steps, S - 1).  Row i is the step that samples sequence slot start + i; its
+        weights stand in columns 0 .. start + i - 1, exact zeros behind them."""
+        n_steps, B, H, max_len = self.attn_probs.shape
+        W = self.S - 1
+        out = torch.empty((B, H, n_steps, W) if heads == "all" else (B, n_steps, W), dtype=torch.float32, device=self.dev)
+        L.check(self.lib.vaura_attention_map(L.ptr(self.attn_probs), L.ptr(out), n_steps, B, H, max_len, W, int(heads == "all"),
+                                             L.current_stream(self.dev)), "vaura_attention_map")
+        return out
 
     def _delays_arg(self):
         return L.delays_host(self.delays) if self.delays is not None else None
@@ -610,7 +649,10 @@ class DecoderEngine:
                        # per-clip lengths: the POINTERS (engine-owned arrays, rewritten per call) — other lengths replay the same graph
                        int(self.dec_ext2.clip_timesteps or 0), int(self.dec_ext2.clip_cond_tokens or 0),
                        # per-clip prompt lengths: the POINTER as well
-                       int(self.dec_ext3.row_prompt_steps or 0))
+                       int(self.dec_ext3.row_prompt_steps or 0),
+                       # attention maps: the buffer, the layer and the first reported position (all 0 in a call without them)
+                       int(self.dec_ext4.attn_probs or 0), int(self.dec_ext4.attn_layer), int(self.dec_ext4.attn_pos0),
+                       int(self.dec_ext4.attn_steps))
                 if self._graph_key != key:       # the captured step is tied to these buffers / parameters
                     self._free_graph()
                     handle = C.c_void_p()
@@ -720,7 +762,8 @@ class DecoderEngine:
     def generate_codes(self, feats: torch.Tensor, max_new_tokens, *, prompt: Optional[torch.Tensor] = None,
                        use_sampling=False, temp=1.0, top_k=0, top_p=0.0, cfg_scale=1.0, noise=None, seed=0,
                        clip_base=0, use_graph=True, tokens_per_frame=7, delays=None, return_logprobs=False, num_candidates=1,
-                       return_relevance=False, video_lengths=None, prompt_lengths=None):
+                       return_relevance=False, video_lengths=None, prompt_lengths=None, return_attention_weights=False,
+                       attention_layer=-1, attention_heads="mean"):
         """The hot loop of generate(): (B, Tv, 768) -> codes (B, K, T) int64 (device).  ``delays``: the codebook delay pattern
         (codebook_patterns.py:374-419; None = 0..K-1, ParallelPatternProvider = all zeros): S = T + max(d) + 1 sequence steps, the
         loop samples steps Tp + 1 + d_0 .. S - 1, and an explicit ``noise`` has S - (Tp + 1 + d_0) steps.
@@ -756,17 +799,40 @@ class DecoderEngine:
         batch (one captured graph) and, on the plane storages, runs one prefill pass per further distinct length over positions
         [0, P_b + d_0) just before that group's first sampled step (``clip_params.prompt_schedule``): G distinct lengths cost one loop
         plus sum_g (P_g + d_0) prefill positions.  Lengths that are all equal are the scalar call with ``prompt[..., :P]``, on its path.
-        An explicit ``noise`` starts at the shortest prompt's first step and is not comparable, as above."""
+        An explicit ``noise`` starts at the shortest prompt's first step and is not comparable, as above.
+        ``return_attention_weights``: the dict (one dict for all three flags) gains "attention": the self-attention weights of layer
+        ``attention_layer`` (default -1: the last; negative as in Python) at every sampled step, fp32 (B, S - start, S - 1) — the mean over
+        the 16 heads, added in index order in fp32 and multiplied once by 1/16 — or with ``attention_heads="all"`` (B, 16, S - start,
+        S - 1).  Row i is the step that samples sequence slot start + i (cache position start + i - 1): columns 0 .. start + i - 1 hold
+        softmax_j(q . k_j / sqrt(96)) over the keys as the cache stores them — the numbers the kernel's output is formed from
+        (include/vaura_hip.h ``vaura_decoder_ext4``) —, everything to the right is exactly 0.  Position p carries video token p // 7, so
+        the map over positions is also the map over video time.  The conditional rows are reported (never the null-condition rows), the
+        tokens and every other reported value are those of the call without the flag.  It costs one fp32 buffer of (S - start, B, 16,
+        max_len) per call — 30 MB at 8 clips x 228 steps — and a store per weight in one layer's attention launch.  Served for caches of
+        at most 256 positions, ``num_candidates`` = 1 and one length / prompt length per call (``VauraHipError`` otherwise, before any
+        device work)."""
         B, Tv, _ = feats.shape
         call = clip_params.resolve_codes_call(
             B, Tv, max_new_tokens, None if prompt is None else int(prompt.shape[-1]), use_sampling=use_sampling, temp=temp, top_k=top_k,
             top_p=top_p, cfg_scale=cfg_scale, seed=seed, clip_base=clip_base, use_graph=use_graph, tokens_per_frame=tokens_per_frame,
             delays=delays, return_logprobs=return_logprobs, num_candidates=num_candidates, return_relevance=return_relevance,
-            video_lengths=video_lengths, prompt_lengths=prompt_lengths)
+            video_lengths=video_lengths, prompt_lengths=prompt_lengths, return_attention_weights=return_attention_weights,
+            attention_layer=attention_layer, attention_heads=attention_heads)
+        self._check_attention(call)
         with off_null_stream(self.dev) as caller:
             Tp, start, plan, sp, noise = self._begin_sequence(call, feats, prompt, noise)
             self.run(start - 1, self.S - start, sp, noise, call.use_graph, plan)
             return self._finish_sequence(call, Tp, caller)
+
+    def _check_attention(self, call: clip_params.CodesCall) -> Optional[int]:
+        """What only the engine knows about a call that asks for attention maps, before any device work -> the reporting layer as an
+        index (None: the call asks for none)."""
+        if not call.want_attention:
+            return None
+        K = self.cfg.num_codebooks
+        S = call.t_max + (K if call.delays is None else max(call.delays) + 1)
+        clip_params.check_attention_shape(S, self.cfg.block_size)
+        return clip_params.check_attention_keywords(call.attention_layer, call.attention_heads, self.cfg.num_layers)
 
     def _begin_sequence(self, call: clip_params.CodesCall, feats, prompt, noise):
         """Everything of a ``generate_codes`` call in front of its loop, on the resolved call, enqueued on the current stream: the
@@ -799,6 +865,8 @@ class DecoderEngine:
                 self.logprobs_null.zero_()
         self.dec_ext.logprobs_cond = L.ptr(self.logprobs_cond) if call.want_relevance else 0
         self.dec_ext.logprobs_null = L.ptr(self.logprobs_null) if call.want_relevance else 0
+        # attention maps: the step that samples slot start + i runs at cache position start + i - 1
+        self._set_attention(self._check_attention(call), start - 1, self.S - start)
         return Tp, start, plan, sp, noise
 
     def _finish_sequence(self, call: clip_params.CodesCall, Tp: int, caller):
@@ -808,11 +876,13 @@ class DecoderEngine:
         extra = self._sequence_logprobs(Tp) if call.want_logprobs else None
         if call.want_relevance:
             extra = dict(extra or {}, **self._sequence_relevance(Tp))
+        if call.want_attention:
+            extra = dict(extra or {}, attention=self.attention_map(call.attention_heads))
         if caller is not None:
             out.record_stream(caller)
             for t in (extra or {}).values():
                 t.record_stream(caller)
-        return (out, extra) if (call.want_logprobs or call.want_relevance) else out
+        return (out, extra) if (call.want_logprobs or call.want_relevance or call.want_attention) else out
 
     def _revert_f32(self, buf: torch.Tensor) -> torch.Tensor:
         """fp32 values in the layout of seq -> (batch, K, T), 0 where the sequence holds no frame."""
@@ -918,6 +988,7 @@ class DecoderEngine:
         prompt, noise = kw.pop("prompt", None), kw.pop("noise", None)
         call = clip_params.resolve_codes_call(B, Tv, max_new_tokens, None if prompt is None else int(prompt.shape[-1]), **kw)
         clip_params.check_block_frames(block_frames)
+        clip_params.refuse_attention("generate_codes_stream", call.want_attention)
         if call.num_candidates != 1:
             raise L.VauraHipError("streaming takes num_candidates = 1: the winning candidate is known only at the end of the call")
         if self.near_tie == "rerun":
@@ -986,6 +1057,7 @@ class DecoderEngine:
         still the one in the buffers."""
         if call.tv_lengths is not None or call.lengths is not None or call.P is not None or call.num_candidates != 1 or call.prompt_frames:
             raise L.VauraHipError("a live sequence takes one length for the whole call, no prompt and num_candidates = 1")
+        clip_params.refuse_attention("a live sequence", call.want_attention)
         c = self.cfg
         zeros = torch.zeros(call.batch, call.n_video_tokens, c.cond_in, dtype=torch.float32, device=self.dev)
         _, start, _, sp, noise = self._begin_sequence(call, zeros, None, noise)

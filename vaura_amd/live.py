@@ -160,11 +160,12 @@ class LiveBook:
 def open_live(model, batch: int, block_frames: int = 16, *, use_sampling: bool = True, temp: float = 1.0, top_k: int = 128, top_p: float = 0.0,
               cfg_scale: float = 1.0, return_relevance: bool = False, clip_indices=None, stride: float = 0.64, vfps: float = 25,
               model_max_duration: Optional[float] = None, num_candidates: int = 1, prompt_lengths=None, audio_lengths=None,
-              max_new_tokens=None, video_lengths=None) -> "LiveSession":
+              max_new_tokens=None, video_lengths=None, return_attention_weights: bool = False) -> "LiveSession":
     """``VAURAModel.open_live``: the checks, then the session.  The sampling keywords take scalars or one value per clip, as
     ``generate_long_stream`` does.  Refused here: ``num_candidates`` > 1, any ``prompt_lengths`` / ``audio_lengths`` / ``max_new_tokens``
     / ``video_lengths``, a sampler with ``near_tie="rerun"``, a stride that is not one segment (``live_plan``), and a model without
     the flattened AVCLIP layout (only there is a video token part of one segment)."""
+    clip_params.refuse_attention("a live session", return_attention_weights)
     check_open(batch, block_frames, num_candidates=num_candidates, prompt_lengths=prompt_lengths, audio_lengths=audio_lengths,
                max_new_tokens=max_new_tokens, video_lengths=video_lengths, near_tie=getattr(model.sampler, "near_tie", None))
     clip_params.check_lengths(batch, use_sampling=use_sampling, temp=temp, top_k=top_k, top_p=top_p, cfg_scale=cfg_scale)

@@ -23,6 +23,8 @@ from typing import List, Optional
 
 import torch
 
+from . import clip_params
+
 COMPRESSION_MODEL_FRAME_RATE = 86   # scripts/generate.py:30
 
 
@@ -103,7 +105,7 @@ def _check_emit_chunks(emit_chunks):
 def generate_long(model, frames: torch.Tensor, duration: float, *, stride: float = 0.64, model_max_duration: Optional[float] = None,
                   vfps: float = 25, frame_step: int = 1, clip_indices=None, use_sampling: bool = True, temp: float = 1.0,
                   top_k: int = 128, top_p: float = 0.0, cfg_scale: float = 1.0, return_relevance: bool = False, video_lengths=None,
-                  codec_window: Optional[int] = None) -> dict:
+                  codec_window: Optional[int] = None, return_attention_weights: bool = False) -> dict:
     """frames: whatever the feature-extractor plugin accepts, segments on dim 1 — raw (B, S, C, T, H, W) or, with the
     pass-through ``MotionFormer``, features (B, S, t, 768).  Returns {"generated_audio", "sampled_indices"}.
     ``use_sampling``, ``temp``, ``top_k``, ``top_p``, ``cfg_scale``: scalars, or one value per clip (length-B list / tuple / 1-D
@@ -116,6 +118,7 @@ def generate_long(model, frames: torch.Tensor, duration: float, *, stride: float
     (``DacModelWrapper.decode_windowed``): the same bits, with codec workspaces that follow the window instead of the duration.
     One ``duration`` for the whole call: a per-clip sequence of durations, or ``video_lengths``, is refused (per-clip lengths are a
     feature of one ``generate()`` call; the chunk schedule here is shared by the batch)."""
+    clip_params.refuse_attention("generate_long", return_attention_weights)
     _check_codec_window(codec_window)
     sched, kw = _long_setup(model, frames, duration, stride, model_max_duration, vfps, clip_indices, use_sampling, temp, top_k, top_p,
                             cfg_scale, video_lengths, "generate_long")
@@ -152,7 +155,8 @@ def _decode_halo(model) -> int:
 def generate_long_stream(model, frames: torch.Tensor, duration: float, *, emit_chunks: int = 1, stride: float = 0.64,
                          model_max_duration: Optional[float] = None, vfps: float = 25, frame_step: int = 1, clip_indices=None,
                          use_sampling: bool = True, temp: float = 1.0, top_k: int = 128, top_p: float = 0.0, cfg_scale: float = 1.0,
-                         return_relevance: bool = False, video_lengths=None, block_frames: Optional[int] = None):
+                         return_relevance: bool = False, video_lengths=None, block_frames: Optional[int] = None,
+                         return_attention_weights: bool = False):
     """``generate_long`` as a generator of finished audio: the arguments are checked here, the returned iterator runs the chunks.
     After every ``emit_chunks`` chunks, and after the last one, it yields {"audio" (B, 1, n * hop), "start_frame", "frames" (n),
     "sampled_indices" (B, K, n), "final"} — with ``return_relevance`` also "relevance", "logprob_cond", "logprob_null" (B, K, n) — for
@@ -169,6 +173,7 @@ def generate_long_stream(model, frames: torch.Tensor, duration: float, *, emit_c
     chunk's end what the generator above releases there.  The first block of a call is then due after about ``block_frames`` + max(delay)
     decode steps and one small codec window instead of after the first whole chunk; a single-chunk duration streams as well.  The blocks
     still tile the clip and concatenate to the bits of ``generate_long``.  ``emit_chunks`` must stay 1 with it."""
+    clip_params.refuse_attention("generate_long_stream", return_attention_weights)
     _check_emit_chunks(emit_chunks)
     if block_frames is not None:
         from .clip_params import check_block_frames
@@ -385,7 +390,7 @@ def generate_long_clips(model, frames: torch.Tensor, durations, *, segments=None
                         model_max_duration: Optional[float] = None, vfps: float = 25, frame_step: int = 1, clip_indices=None,
                         use_sampling: bool = True, temp: float = 1.0, top_k: int = 128, top_p: float = 0.0, cfg_scale: float = 1.0,
                         return_relevance: bool = False, video_lengths=None, num_candidates=None,
-                        codec_window: Optional[int] = None) -> dict:
+                        codec_window: Optional[int] = None, return_attention_weights: bool = False) -> dict:
     """``generate_long`` for a batch whose clips differ in duration, in one call: ``durations`` holds one positive float per clip
     (list / tuple / 1-D tensor of length B), and clip b's tokens, relevance values and waveform are, bit for bit (``noise_mode=
     "philox"`` or greedy decoding), those of ``generate_long(model, frames, durations[b], ...)`` on the same batch.
@@ -415,6 +420,7 @@ def generate_long_clips(model, frames: torch.Tensor, durations, *, segments=None
     a full window (``clip_chunk_plan``: "width"), and such a clip is served the way ``generate_tokens(video_lengths=...)`` serves a
     clip with fewer video tokens than the batch: it has no scalar ``generate_long`` to be compared with under guidance; its scalar
     counterpart is the one-duration loop over calls of the same width."""
+    clip_params.refuse_attention("generate_long_clips", return_attention_weights)
     _check_codec_window(codec_window)
     d, seg, single, kw, sample_kw = _clips_setup(model, frames, durations, segments, stride, model_max_duration, vfps, frame_step, clip_indices,
                                                  use_sampling, temp, top_k, top_p, cfg_scale, video_lengths, num_candidates, "generate_long_clips")
@@ -518,7 +524,8 @@ def _clips_chunks(model, frames, plan, single, frame_step, sample_kw, return_rel
 def generate_long_clips_stream(model, frames: torch.Tensor, durations, segments=None, *, emit_chunks: int = 1, stride: float = 0.64,
                                model_max_duration: Optional[float] = None, vfps: float = 25, frame_step: int = 1, clip_indices=None,
                                use_sampling: bool = True, temp: float = 1.0, top_k: int = 128, top_p: float = 0.0, cfg_scale: float = 1.0,
-                               return_relevance: bool = False, video_lengths=None, num_candidates=None):
+                               return_relevance: bool = False, video_lengths=None, num_candidates=None,
+                               return_attention_weights: bool = False):
     """``generate_long_clips`` as a generator of finished audio (``generate_long_stream`` for one duration per clip): the arguments are
     checked here, the returned iterator runs the chunks.  After every ``emit_chunks`` chunks, and after the last one, it yields
     {"audio" (B, 1, max(frames) * hop), "start_frames" and "frames" (one int per clip), "sampled_indices" (B, K, max(frames)), "final"},
@@ -528,6 +535,7 @@ def generate_long_clips_stream(model, frames: torch.Tensor, durations, segments=
     schedule has ended has frames[b] = 0 from then on (ONE ``decode_window`` pass per block, over the clips that have something).
     Audio leaves at chunk ends only: this generator has no ``block_frames`` (``generate_long_stream`` releases inside a chunk; the
     merged per-clip schedules stay as they are)."""
+    clip_params.refuse_attention("generate_long_clips_stream", return_attention_weights)
     _check_emit_chunks(emit_chunks)
     d, seg, single, kw, sample_kw = _clips_setup(model, frames, durations, segments, stride, model_max_duration, vfps, frame_step, clip_indices,
                                                  use_sampling, temp, top_k, top_p, cfg_scale, video_lengths, num_candidates,

@@ -66,6 +66,9 @@ class _GenerateCall:
     want_rel: bool
     remove_prompts: bool
     check: bool
+    want_attn: bool = False                  # return_attention_weights: the call's keyword, or the constructor flag where it is None
+    attention_layer: int = -1
+    attention_heads: str = "mean"
 
     @property
     def ragged(self) -> bool:
@@ -333,7 +336,7 @@ class VAURAModel(nn.Module):
     def _resolve_call(self, frames, audio, max_new_tokens, *, use_sampling, temp, top_k, top_p, cfg_scale, prompt_is_encoded,
                       return_logprobs, return_relevance, video_lengths, prompt_lengths, audio_lengths, num_candidates=1,
                       return_all_candidates=False, rank_by="logprob", video_segments=None, return_attention_weights=False,
-                      remove_prompts=False, check=False) -> "_GenerateCall":
+                      remove_prompts=False, check=False, attention_layer=-1, attention_heads="mean") -> "_GenerateCall":
         """The host stage of generate() / generate_tokens() / generate_stream(): everything that is known before any device work —
         the batch from the frames, an encoded prompt's frames — is checked and resolved here, once per call."""
         assert not self.training, "do not use generation in training mode"
@@ -350,13 +353,20 @@ class VAURAModel(nn.Module):
         n_segments = None if video_segments is None else clip_params.resolve_segments(
             batch, video_segments, video_lengths, frames.shape[1] if batch is not None and len(frames.shape) > 1 else None,
             self.flatten_vis_feats, lengths)
-        if return_attention_weights:
-            # the reference's own llama sampler returns (logits, None, None) (llama.py:520-539), so its generate() fails on
-            # `sa_w[-1, -1, :]` (vaura_model.py:529-531) with this flag: there is no behaviour to reproduce
-            raise NotImplementedError("attention-weight dumps are not produced by the fused decode path (nor by the reference's "
-                                      "llama sampler, which returns None for them)")
         delays = self._pattern_delays(t_max)             # the layout the loop decodes; the call runs to the longest clip
         block = self.sampler.block_size
+        # attention maps (the reference declares the switch, but its llama sampler
+        # returns None for the weights, llama.py:520-539, and its generate() then fails on `sa_w[-1, -1, :]`): served by the decode
+        # step's reporting attention instance; what that does not serve yet is refused here, before any device work
+        want_attn = bool(return_attention_weights)
+        if want_attn:
+            attention_layer = clip_params.check_attention_keywords(attention_layer, attention_heads, getattr(self.sampler, "n_layer", None))
+            clip_params.check_attention_shape(t_max + max(delays) + 1, block)
+            if N > 1:
+                raise L.VauraHipError(f"return_attention_weights takes num_candidates = 1 in this version (got {N}): one map per clip")
+            if lengths is not None or per_clip_prompt:
+                raise L.VauraHipError("return_attention_weights takes one length for the whole call in this version: per-clip "
+                                      "max_new_tokens / prompt_lengths / audio_lengths are not served together with it")
         if delays != list(range(self.num_codebooks)) and t_max + max(delays) + 1 > block:   # (the engine refuses it too, before allocating)
             raise L.VauraHipError(f"{t_max} timesteps under the delays {delays} need {t_max + max(delays) + 1} sequence "
                                   f"steps; block_size is {block}")
@@ -367,7 +377,8 @@ class VAURAModel(nn.Module):
             return_relevance=bool(return_relevance), by_rel=by_rel, return_all_candidates=return_all_candidates,
             # candidates are ranked by their sequence log-probability by default
             want_lp=bool(return_logprobs) or (N > 1 and not by_rel), want_rel=bool(return_relevance) or (N > 1 and by_rel),
-            remove_prompts=remove_prompts, check=check)
+            remove_prompts=remove_prompts, check=check, want_attn=want_attn, attention_layer=attention_layer,
+            attention_heads=attention_heads)
 
     def _bind_call(self, call: "_GenerateCall", frames, audio, clip_indices):
         """The second stage: the prompt is encoded and the features are extracted, then the call's lengths are resolved again with the
@@ -417,6 +428,8 @@ class VAURAModel(nn.Module):
                         prompt_lengths=P if per_clip else None, noise=noise, seed=self.seed, clip_base=self.clip_base,
                         tokens_per_frame=self.sampler.audio_tokens_per_video_frame, delays=None if delays == list(range(K)) else delays,
                         return_logprobs=call.want_lp, return_relevance=call.want_rel, num_candidates=call.N, video_lengths=tv_lengths)
+        if call.want_attn:                       # (a call without the flag passes the keywords it always passed)
+            codes_kw.update(return_attention_weights=True, attention_layer=call.attention_layer, attention_heads=call.attention_heads)
         return codes_kw
 
     @torch.no_grad()
@@ -426,7 +439,8 @@ class VAURAModel(nn.Module):
                         temp: float = 1.0, top_k: int = 256, top_p: float = 0.0, remove_prompts: bool = False,
                         prompt_is_encoded: bool = False, cfg_scale: float = 1.0, return_logprobs: bool = False,
                         num_candidates: int = 1, return_all_candidates: bool = False, return_relevance: bool = False,
-                        rank_by: str = "logprob", video_lengths=None, video_segments=None, prompt_lengths=None, audio_lengths=None):
+                        rank_by: str = "logprob", video_lengths=None, video_segments=None, prompt_lengths=None, audio_lengths=None,
+                        attention_layer: int = -1, attention_heads: str = "mean"):
         """generate() up to and including revert_pattern_sequence (vaura_model.py:410-572): (B, K, T') int64 tokens on
         the device, no codec decode.  The sliding-window caller (vaura_amd.longform) uses this for every chunk and
         decodes the concatenated tokens once, as the reference's script does (scripts/generate.py:366-369).
@@ -476,13 +490,24 @@ class VAURAModel(nn.Module):
         recordings of different lengths (``DecoderEngine.generate_codes``: one decode loop plus, on the plane storages, a prefill pass
         over P_g + d_0 positions for every further distinct length).  ``noise_mode="torch_cpu"`` works but is not comparable.  With
         ``remove_prompts`` clip b's frames [P_b, T_b) are left-aligned — "tokens" (B, K, T_max - min P) with the special id behind them,
-        the per-token values with zeros — and "lengths" = T_b - P_b."""
+        the per-token values with zeros — and "lengths" = T_b - P_b.
+        ``return_attention_weights`` (a dict as well):
+        "s_attn_weights", the self-attention weights of decoder layer ``attention_layer`` (default -1: the last; negative as in Python)
+        at every sampled step — fp32 (B, S - start, S - 1) on the device, S the pattern sequence length and start the first sampled
+        step: ``combine_attn_weights_to_tensor``'s layout, one map per clip.  Row i is the step that samples sequence slot start + i;
+        columns 0 .. start + i - 1 hold its softmax weights over the cache positions (the mean over the 16 heads in fixed order, or with
+        ``attention_heads="all"`` every head: (B, 16, S - start, S - 1)), everything to the right is exactly 0.  Position p carries video
+        token p // audio_tokens_per_video_frame, so the map over positions is the map over video time.  Under CFG the conditional rows
+        are reported.  Tokens and every other reported value are those of the call without the flag; ``remove_prompts`` does not cut
+        the map.  Served for block_size <= 256, ``num_candidates`` = 1 and one length / prompt length per call (``VauraHipError``
+        otherwise, at call time)."""
         return self._generate_tokens(self._resolve_call(
             frames, audio, max_new_tokens, use_sampling=use_sampling, temp=temp, top_k=top_k, top_p=top_p, cfg_scale=cfg_scale,
             prompt_is_encoded=prompt_is_encoded, return_logprobs=return_logprobs, return_relevance=return_relevance,
             video_lengths=video_lengths, prompt_lengths=prompt_lengths, audio_lengths=audio_lengths, num_candidates=num_candidates,
             return_all_candidates=return_all_candidates, rank_by=rank_by, video_segments=video_segments,
-            return_attention_weights=return_attention_weights, remove_prompts=remove_prompts, check=check), frames, audio, clip_indices)
+            return_attention_weights=return_attention_weights, remove_prompts=remove_prompts, check=check,
+            attention_layer=attention_layer, attention_heads=attention_heads), frames, audio, clip_indices)
 
     def _generate_tokens(self, call: _GenerateCall, frames, audio, clip_indices):
         """``generate_tokens`` behind its host stage."""
@@ -494,7 +519,7 @@ class VAURAModel(nn.Module):
         # activation beyond the fp16-plane range is re-run on the exact-fp32 engine instead of raising (engine.generate_codes_checked)
         codes = eng.generate_codes_checked(feats, lengths if lengths is not None else T, **codes_kw)
         lp = None
-        if call.want_lp or call.want_rel:
+        if call.want_lp or call.want_rel or call.want_attn:
             codes, lp = codes
         bad = (codes < 0) | (codes > self.sampler.d_codebook)
         row_len = None
@@ -520,7 +545,7 @@ class VAURAModel(nn.Module):
             assert not bool((seq == -1).any()), "unknown tokens left in the generated sequence"
             assert bool((seq == torch.where(mask, seq, special)).all()), "sequence and pattern mask disagree"
         lo = Tp if call.remove_prompts else 0
-        if not (call.want_lp or call.want_rel or call.ragged):
+        if not (call.want_lp or call.want_rel or call.ragged or call.want_attn):
             return codes[..., lo:T]
         out = {}
         if call.ragged:
@@ -568,6 +593,8 @@ class VAURAModel(nn.Module):
                 lp = {k: v[rows] for k, v in lp.items()}
                 out["selected_candidate"] = winner.to(torch.int64)
         out["tokens"] = cut(codes, sp)
+        if call.want_attn:
+            out["s_attn_weights"] = lp["attention"]
         if call.return_logprobs:
             out["logprobs"] = cut(lp["logprobs"], 0.0)
             out["logprob_per_codebook"] = lp["per_codebook"]
@@ -581,12 +608,12 @@ class VAURAModel(nn.Module):
 
     @torch.no_grad()
     def generate(self, frames=None, audio: Union[torch.Tensor, None] = None, clip_indices=None, max_new_tokens: int = 512,
-                 return_attention_weights: bool = False, return_sampled_indices: bool = False, check: bool = False,
+                 return_attention_weights: Optional[bool] = None, return_sampled_indices: bool = False, check: bool = False,
                  use_sampling: bool = True, temp: float = 1.0, top_k: int = 256, top_p: float = 0.0,
                  remove_prompts: bool = False, prompt_is_encoded: bool = False, cfg_scale: float = 1.0,
                  return_logprobs: bool = False, num_candidates: int = 1, return_all_candidates: bool = False,
                  return_relevance: bool = False, rank_by: str = "logprob", video_lengths=None, prompt_lengths=None,
-                 audio_lengths=None) -> dict:
+                 audio_lengths=None, attention_layer: int = -1, attention_heads: str = "mean") -> dict:
         """``return_logprobs`` / ``num_candidates`` / ``return_all_candidates`` / ``return_relevance`` / ``rank_by``: see ``generate_tokens`` — its extra entries are added
         to the result ("sampled_indices" takes "tokens"); the codec decodes the winners (B clips), or with ``return_all_candidates``
         all B * N takes.  With the defaults the result is the dict it always was.
@@ -596,14 +623,20 @@ class VAURAModel(nn.Module):
         The post stage takes that batch in one call: ``post.normalize_audio(r["generated_audio"], ..., lengths=r["audio_lengths"])``,
         or ``post.scale_batch`` / ``post.save_wavs`` for the per-clip tensors and files.
         ``prompt_lengths`` / ``audio_lengths`` (see ``generate_tokens``): per-clip prompt lengths; the result gains "prompt_lengths" (B,) next
-        to "lengths" / "audio_lengths", and with ``remove_prompts`` the codec decodes each clip's own T_b - P_b generated frames."""
+        to "lengths" / "audio_lengths", and with ``remove_prompts`` the codec decodes each clip's own T_b - P_b generated frames.
+        ``return_attention_weights`` (None: the constructor's flag, as the reference's ``_log_predict_run`` passes it) /
+        ``attention_layer`` / ``attention_heads`` (see ``generate_tokens``): "s_attn_weights" holds the
+        per-step self-attention map, fp32 (B, S - start, S - 1) on the device; "mha_attn_weights" stays None (channel-concat
+        conditioning has no cross-attention; the reference returns None there too)."""
         K = self.num_codebooks
+        if return_attention_weights is None:
+            return_attention_weights = self.return_attention_weights
         call = self._resolve_call(                                   # before the engine is touched
             frames, audio, max_new_tokens, use_sampling=use_sampling, temp=temp, top_k=top_k, top_p=top_p, cfg_scale=cfg_scale,
             prompt_is_encoded=prompt_is_encoded, return_logprobs=return_logprobs, return_relevance=return_relevance,
             video_lengths=video_lengths, prompt_lengths=prompt_lengths, audio_lengths=audio_lengths, num_candidates=num_candidates,
             return_all_candidates=return_all_candidates, rank_by=rank_by, return_attention_weights=return_attention_weights,
-            remove_prompts=remove_prompts, check=check)
+            remove_prompts=remove_prompts, check=check, attention_layer=attention_layer, attention_heads=attention_heads)
         extra = {}
         with off_null_stream(self.sampler.engine().dev) as caller:   # decode loop + codec leave HIP's null stream together
             out_codes = self._generate_tokens(call, frames, audio, clip_indices)
@@ -633,7 +666,7 @@ class VAURAModel(nn.Module):
             generated_audio.record_stream(caller)
             for t in extra.values():
                 t.record_stream(caller)
-        return {"generated_audio": generated_audio, "s_attn_weights": None, "mha_attn_weights": None,
+        return {"generated_audio": generated_audio, "s_attn_weights": extra.pop("s_attn_weights", None), "mha_attn_weights": None,
                 "sampled_indices": out_codes if return_sampled_indices else None, **extra}
 
     # ------------------------------------------------------------------ generate, audio out while the decode loop still runs
@@ -641,7 +674,7 @@ class VAURAModel(nn.Module):
                         use_sampling: bool = True, temp: float = 1.0, top_k: int = 256, top_p: float = 0.0,
                         prompt_is_encoded: bool = False, cfg_scale: float = 1.0, return_logprobs: bool = False, num_candidates: int = 1,
                         return_relevance: bool = False, video_lengths=None, prompt_lengths=None, audio_lengths=None,
-                        block_frames: int = 16, decode: bool = True):
+                        block_frames: int = 16, decode: bool = True, return_attention_weights: bool = False):
         """``generate`` as a generator of finished audio: the arguments are checked here, the returned iterator runs the call and yields
         {"audio" (B, 1, n * hop), "start_frame", "frames" (n), "sampled_indices" (B, K, n), "final"} for the frames [start_frame,
         start_frame + n) as soon as they can no longer change — about ``block_frames`` + ``decode_halo`` + max(delay) decode steps
@@ -666,6 +699,7 @@ class VAURAModel(nn.Module):
         ``block_frames`` that is no positive int.  Closing the iterator early leaves at most two pieces of the loop running and the
         model usable at once."""
         clip_params.check_block_frames(block_frames)
+        clip_params.refuse_attention("generate_stream", return_attention_weights)
         if isinstance(num_candidates, bool) or not isinstance(num_candidates, int) or num_candidates != 1:
             raise L.VauraHipError(f"generate_stream takes num_candidates = 1 (got {num_candidates!r}): the winning candidate is known only "
                                   "at the end of the call")
@@ -682,7 +716,7 @@ class VAURAModel(nn.Module):
         call = self._resolve_call(
             frames, audio, max_new_tokens, use_sampling=use_sampling, temp=temp, top_k=top_k, top_p=top_p, cfg_scale=cfg_scale,
             prompt_is_encoded=prompt_is_encoded, return_logprobs=return_logprobs, return_relevance=return_relevance,
-            video_lengths=video_lengths, prompt_lengths=prompt_lengths, audio_lengths=audio_lengths)
+            video_lengths=video_lengths, prompt_lengths=prompt_lengths, audio_lengths=audio_lengths, return_attention_weights=False)
         return self._generate_stream(call, frames, audio, clip_indices, block_frames, bool(decode))
 
     @torch.no_grad()

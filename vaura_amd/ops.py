@@ -119,6 +119,42 @@ def attention_step_kv(qkv_p: torch.Tensor, rope: torch.Tensor, kcache: torch.Ten
     return out, out_split
 
 
+def attention_step_probs(qkv_p: torch.Tensor, rope: torch.Tensor, kcache: torch.Tensor, vcache: torch.Tensor, rows: int, n_head: int,
+                         head_dim: int, pos: int, probs: torch.Tensor, pos0: int, *, kv_dtype: int = 0,
+                         kscale: Optional[torch.Tensor] = None, vscale: Optional[torch.Tensor] = None,
+                         qkv2_p: Optional[torch.Tensor] = None, n_split: int = 1, want_split: bool = False, plane_shift: int = 0,
+                         out: Optional[torch.Tensor] = None, out_split: Optional[torch.Tensor] = None):
+    """vaura_attention_step_probs: ``attention_step_kv`` that also reports the step's softmax weights into ``probs`` (n_steps, rows_out,
+    n_head, max_len) fp32 — row (pos - pos0) of it, for rows < rows_out, when pos0 <= pos < pos0 + n_steps.  Returns (out, out_split)."""
+    _cuda(qkv_p, qkv2_p, rope, kcache, vcache, kscale, vscale, out, out_split, probs)
+    max_len = kcache.shape[-2]
+    n_steps, rows_out = int(probs.shape[0]), int(probs.shape[1])
+    assert probs.dtype == torch.float32 and probs.is_contiguous() and tuple(probs.shape[2:]) == (n_head, max_len)
+    rp = (rows + 15) // 16 * 16
+    dev = qkv_p.device
+    if out is None:
+        out = torch.zeros(rp * n_head * head_dim, dtype=torch.float32, device=dev)
+    if want_split and out_split is None:
+        out_split = torch.zeros(rp * 2 * n_head * head_dim, dtype=torch.int16, device=dev)
+    part = torch.empty(rows * n_head * n_split * (head_dim + 8), dtype=torch.float32, device=dev) if n_split > 1 else None
+    L.check(L.lib().vaura_attention_step_probs(L.ptr(qkv_p), L.ptr(qkv2_p), L.ptr(rope), L.ptr(kcache), L.ptr(vcache), L.ptr(kscale),
+                                               L.ptr(vscale), L.ptr(out), L.ptr(out_split), L.ptr(part), None, rows, n_head, head_dim,
+                                               max_len, pos, n_split, plane_shift, kv_dtype, L.ptr(probs), pos0, n_steps, rows_out,
+                                               L.current_stream()), "vaura_attention_step_probs")
+    return out, out_split
+
+
+def attention_map(probs: torch.Tensor, width: int, heads: str = "mean") -> torch.Tensor:
+    """vaura_attention_map: reported weights (n_steps, n_rows, n_head, max_len) -> (n_rows, n_steps, width), the fixed-order mean over
+    the heads, or with ``heads="all"`` (n_rows, n_head, n_steps, width)."""
+    _cuda(probs)
+    n_steps, n_rows, H, max_len = probs.shape
+    out = torch.empty((n_rows, H, n_steps, width) if heads == "all" else (n_rows, n_steps, width), dtype=torch.float32, device=probs.device)
+    L.check(L.lib().vaura_attention_map(L.ptr(probs), L.ptr(out), n_steps, n_rows, H, max_len, width, int(heads == "all"),
+                                        L.current_stream()), "vaura_attention_map")
+    return out
+
+
 def attention_prefill(qkv_p: torch.Tensor, rope: torch.Tensor, kcache: torch.Tensor, vcache: torch.Tensor, attn: torch.Tensor,
                       attn_split: Optional[torch.Tensor], rows: int, n_head: int, head_dim: int, p0: int, n_pos: int, *,
                       kv_dtype: int = 0, plane_shift: int = 0, kscale: Optional[torch.Tensor] = None,
