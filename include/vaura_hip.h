@@ -1093,6 +1093,40 @@ size_t vaura_audio_output_lds_bytes(int o, int n, int w, int taps_per_phase);
 /* output samples per workgroup (VAURA_AUDIO_OUT_TILE as the library was compiled) */
 int vaura_audio_output_tile(void);
 
+/* -------------------------------------------------------------------------------------------
+ * Spectrogram (csrc/spectrogram.hip): the codec's mono fp32 rows at 44.1 kHz -> power, dB or log columns of the linear or the mel
+ * spectrum, in one launch; one pass or block by block with the window history carried, the blocks concatenated being the one-pass
+ * result bit for bit.  Column t of a clip is centred on sample hop t + hop/2 and covers lo = hop t + hop/2 - n_fft/2 ..
+ * lo + n_fft - 1 (x is 0 outside the clip); with hop 512 it is codec frame t.  All fp32: y[i] = window[i] x[lo + i]; X = the
+ * n_fft-point transform of y, bins 0 .. n_fft/2; P = re re + im im; M[m] = fmaf chain of f[m][k] P[k] over the filter's bins in
+ * ascending order; then the scale: VAURA_SPEC_POWER v, VAURA_SPEC_DB 10 log10f(max(v, amin)), VAURA_SPEC_LOG logf(max(v, amin)); a
+ * NaN stays a NaN.  VAURA_SPEC_COMPLEX (without a mel table only) gives X itself: out is (B, out_stride, F, 2), (re, im) pairs.
+ *   x, records, carry_in, carry_out, history   as for vaura_audio_output, the record being r0, L, t0, count, N: the launch forms the
+ *             columns [t0, t0 + count) of clip b and writes them from the start of the clip's rows.  The host rule is the same:
+ *             `history` at least n_fft - 1 and t0 + count at most vaura_amd/spectrogram.py: releasable(r0 + L) for a block that is
+ *             not final (columns(N) for a final one); vaura_amd/post.py (audio_to_spectrogram, SpectrogramStream) keeps it.
+ *   n_fft     512, 1024 or 2048;  hop  a power of two, at most n_fft
+ *   window    device fp32 (n_fft);  twiddles  device fp32 (3 n_fft / 4, 2), 8-byte aligned: cos and -sin of 2 pi t / n_fft
+ *   mel_bins  device int32 (F, 3): first bin, count, offset into mel_weights of every filter (the kernel holds them inside
+ *             0 .. n_fft/2 and inside the mel_total weights); mel_weights device fp32 (mel_total), the filters' weights packed in
+ *             filter order.  Both NULL: the linear spectrum, F == n_fft/2 + 1.
+ *   out       fp32 (B, out_stride, F), time-major: row i of clip b is column t0 + i, zeros from `count` to out_stride; nothing
+ *             outside is written.  out_stride == 0 writes no column (out may be NULL): only the carry moves.
+ * VAURA_ERR_ARG: a NULL required pointer or a misaligned one, one half of the mel table without the other, VAURA_SPEC_COMPLEX with a mel table, overlapping carry spans,
+ * B < 1, a negative length, in_stride == 0, amin not above 0.  VAURA_ERR_DTYPE: an unknown scale.  VAURA_ERR_SHAPE: another n_fft; a
+ * hop that is no power of two or exceeds n_fft; F above VAURA_SPECTROGRAM_MAX_MELS, or not n_fft/2 + 1 without a table; a table
+ * with fewer than F or more than F (n_fft/2 + 1) weights (a filter without a bin, or a support that leaves 0 .. n_fft/2); a row of
+ * more than 2^31 - 1 samples; more than 65535 clips.  All before any launch and without dereferencing anything.               */
+#define VAURA_SPECTROGRAM_RECORD 5
+#define VAURA_SPECTROGRAM_MAX_MELS 256
+enum { VAURA_SPEC_POWER = 0, VAURA_SPEC_DB = 1, VAURA_SPEC_LOG = 2, VAURA_SPEC_COMPLEX = 3 };
+int vaura_spectrogram(const float* x, int B, int64_t in_stride, const int64_t* records, const float* carry_in, float* carry_out,
+                      int history, int n_fft, int hop, const float* window, const float* twiddles, const int32_t* mel_bins,
+                      const float* mel_weights, int mel_total, int F, int scale, float amin, float* out, int64_t out_stride,
+                      vaura_stream_t s);
+/* dynamic LDS bytes of one workgroup of that launch: the two images of the transform (0 for sizes the kernel does not take) */
+size_t vaura_spectrogram_lds_bytes(int n_fft, int F);
+
 /* Measurement aid (tools/pmc_driver, A/B timing): selects kernel variants for launches enqueued (or graphs captured) afterwards.
  * vaura_amd/csrc/variants.h is the table of every bit of both words, by name (e.g. bit 0, ROWSPLIT_OFF: wo / w2 GEMVs as one workgroup
  * per column tile instead of the row-split pair); an entry never changes its value.  0 = the product configuration.   */

@@ -187,6 +187,10 @@ SIGNATURES = {
                                      C.c_void_p, C.c_void_p]),
     "vaura_audio_output_lds_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int]),
     "vaura_audio_output_tile": (C.c_int, []),
+    "vaura_spectrogram": (C.c_int, [C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int,
+                                    C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_void_p,
+                                    C.c_int64, C.c_void_p]),
+    "vaura_spectrogram_lds_bytes": (C.c_size_t, [C.c_int, C.c_int]),
     "vaura_version": (C.c_char_p, []),
     "vaura_set_debug_flags": (None, [C.c_uint]),
     "vaura_set_debug_flags2": (None, [C.c_uint]),

@@ -765,6 +765,15 @@ class VAURAModel(nn.Module):
         from .live import open_live
         return open_live(self, batch, block_frames, **kw)
 
+    # ------------------------------------------------------------------ a picture of the audio, one column per codec frame
+    @staticmethod
+    def audio_to_spectrogram(audio: torch.Tensor, fmt=None, lengths=None):
+        """``post.audio_to_spectrogram``: the (B, 1, N) waveform of ``generate()`` (with its "audio_lengths" when the call was ragged)
+        -> (spec (B, max columns, F) fp32 on the device, columns (B,) int64 on the host); ``fmt`` None: 128 log-mel bands in dB,
+        n_fft 2048, hop 512 — column t is codec frame t."""
+        from . import post
+        return post.audio_to_spectrogram(audio, post.SpectrogramFormat() if fmt is None else fmt, lengths=lengths)
+
     # ------------------------------------------------------------------ one step, reference signature
     @torch.no_grad()
     def _sample_next_token(self, sequence: torch.Tensor, condition: torch.Tensor, use_sampling: bool = False,

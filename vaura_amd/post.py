@@ -11,6 +11,10 @@ What a player, an Opus / WebRTC sender or the AAC encoder behind ``write_video``
 channel count: ``PcmFormat`` / ``audio_to_pcm`` / ``PcmStream`` / ``stream_pcm`` / ``save_pcm_wavs`` turn the device waveform into that
 in one launch of ``vaura_audio_output`` (csrc/audio_out.hip) per call or per streamed block, the blocks concatenated being the one-pass
 result bit for bit (the filter history travels in a carry row on the device).
+
+The picture of the audio — ``SpectrogramFormat`` / ``audio_to_spectrogram`` / ``SpectrogramStream`` / ``stream_spectrogram`` — is one
+launch of ``vaura_spectrogram`` (csrc/spectrogram.hip) in the same way: log-mel or linear columns, one per codec frame at hop 512, the
+streamed columns concatenated being the one-pass result bit for bit.
 """
 from __future__ import annotations
 
@@ -21,6 +25,7 @@ import torch
 from . import _lib as L
 from . import audio_out as AO
 from . import clip_params
+from . import spectrogram as SG
 
 _STRATEGIES = {"clip": 0, "peak": 1, "rms": 2, "": 3, "none": 3}
 
@@ -422,3 +427,175 @@ def save_pcm_wavs(paths: Sequence[str], pcm: torch.Tensor, lengths, fmt: PcmForm
             raise L.VauraHipError(f"lengths must lie in 0 .. {host.shape[1]} (the frames of clip {b}), got {lens}")
         data = host[b, :lens[b]].contiguous().numpy()
         wavfile.write(path, fmt.rate, data[:, 0] if fmt.channels == 1 else data)
+
+
+# ------------------------------------------------------------------------------------------------ spectrograms, one column per frame
+class SpectrogramFormat:
+    """Which picture of the audio: ``n_fft`` 512 / 1024 / 2048 samples per window, ``hop`` (a power of two, at most ``n_fft``; 512 is
+    the codec's hop: one column per codec frame), ``n_mels`` triangular mel bands between ``f_min`` and ``f_max`` Hz (None: the Nyquist
+    frequency) on the ``mel_scale`` "slaney" or "htk" with ``norm`` None or "slaney" — or ``n_mels=None``: the ``n_fft/2 + 1`` linear
+    bins — and the ``scale``: "power", "db" (``10 log10(max(v, amin))``) or "log" (``ln(max(v, amin))``); with ``n_mels=None`` also
+    "complex": the transform itself, a last axis of (re, im).  ``top_db`` is not served:
+    it needs the maximum of the whole clip, which a stream does not have.  Refused here: sizes the kernel refuses, and a filterbank in
+    which a filter has no non-zero weight (too many bands for the bins of ``n_fft``)."""
+
+    def __init__(self, n_fft: int = 2048, hop: int = 512, n_mels: Optional[int] = 128, f_min: float = 0.0, f_max: Optional[float] = None,
+                 mel_scale: str = "slaney", norm: Optional[str] = None, scale: str = "db", amin: float = 1e-10, top_db=None):
+        if top_db is not None:
+            raise L.VauraHipError("top_db is not served: it needs the maximum of the whole clip, which a stream does not have; "
+                                  "clamp the result yourself once the clip is complete")
+        self.plan = SG.SpectrogramPlan(n_fft, hop)
+        if scale not in SG.SCALES:
+            raise L.VauraHipError(f"VAURA_ERR_DTYPE: scale must be one of {sorted(SG.SCALES)}, got {scale!r}")
+        if isinstance(amin, bool) or not isinstance(amin, (int, float)) or not float(amin) > 0.0:
+            raise L.VauraHipError(f"amin must be a positive number, got {amin!r}")
+        if scale == "complex" and n_mels is not None:
+            raise L.VauraHipError('scale "complex" is the linear spectrum itself: it goes with n_mels=None')
+        self.n_fft, self.hop, self.n_mels, self.f_min, self.f_max = n_fft, hop, n_mels, float(f_min), f_max
+        self.mel_scale, self.norm, self.scale, self.amin = mel_scale, norm, scale, float(amin)
+        self.mel = None if n_mels is None else SG.mel_table(n_fft, n_mels, f_min, f_max, mel_scale, norm)
+        self.bins = n_fft // 2 + 1 if n_mels is None else n_mels         # F: the values of one column
+
+    def key(self):
+        return (self.n_fft, self.n_mels, self.f_min, self.f_max, self.mel_scale, self.norm)
+
+    def __repr__(self):
+        return (f"SpectrogramFormat(n_fft={self.n_fft}, hop={self.hop}, n_mels={self.n_mels}, f_min={self.f_min}, f_max={self.f_max}, "
+                f"mel_scale={self.mel_scale!r}, norm={self.norm!r}, scale={self.scale!r}, amin={self.amin})")
+
+
+_spec_tables: Dict[Tuple[tuple, str], tuple] = {}
+_spec_rings: Dict[Tuple[int, str], _RecordRing] = {}
+
+
+def _spec_table(fmt: SpectrogramFormat, dev: torch.device):
+    """(window, twiddles, mel bins, mel weights) of a format on a device, built once"""
+    key = (fmt.key(), str(dev))
+    if key not in _spec_tables:
+        if len(_spec_tables) >= 16:
+            _spec_tables.clear()
+        mel = (None, None) if fmt.mel is None else (fmt.mel["bins"].to(dev), fmt.mel["weights"].to(dev))
+        _spec_tables[key] = (SG.window(fmt.n_fft).to(dev), SG.twiddles(fmt.n_fft).to(dev), *mel)
+    return _spec_tables[key]
+
+
+def _spec_launch(fmt: SpectrogramFormat, x: torch.Tensor, in_stride: int, records: List[List[int]], carry_in: Optional[torch.Tensor],
+                 carry_out: Optional[torch.Tensor], n_row: int, ring: Optional[_RecordRing] = None) -> torch.Tensor:
+    """One launch of vaura_spectrogram over ``x`` (B rows of ``in_stride`` fp32 samples on a HIP device) -> (B, n_row, F) fp32.  The
+    records travel by one asynchronous copy from a pinned buffer of ``ring``; nothing here waits for the device."""
+    dev, B = x.device, len(records)
+    if not x.is_cuda:
+        raise L.VauraHipError("the spectrogram runs on the HIP device that holds the decoded waveform; there is no CPU path")
+    lib = L.lib()
+    with torch.cuda.device(dev):
+        win, tw, bins, weights = _spec_table(fmt, dev)
+        if ring is None:
+            ring = _spec_rings.setdefault((B, str(dev)), _RecordRing(B))
+        rec = ring.send(records, dev)
+        out = torch.empty((B, n_row, fmt.bins) + ((2,) if fmt.scale == "complex" else ()), dtype=torch.float32, device=dev)
+        history = 0 if carry_in is None else carry_in.shape[-1]
+        L.check(lib.vaura_spectrogram(L.ptr(x), B, in_stride, L.ptr(rec), L.ptr(carry_in), L.ptr(carry_out), history, fmt.n_fft, fmt.hop,
+                                      L.ptr(win), L.ptr(tw), L.ptr(bins), L.ptr(weights), 0 if weights is None else weights.numel(),
+                                      fmt.bins, SG.SCALES[fmt.scale], fmt.amin, L.ptr(out) if n_row else 0, n_row,
+                                      L.current_stream(dev)), "vaura_spectrogram")
+    return out
+
+
+def audio_to_spectrogram(wav: torch.Tensor, fmt: SpectrogramFormat, lengths=None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """wav (B, 1, N) fp32 at 44.1 kHz on a HIP device -> (spec, columns): ``spec`` (B, max(columns), F) fp32 on the same device,
+    time-major — row t is column t, centred on sample ``hop t + hop/2``; ``spec.transpose(1, 2)`` is torchaudio's (B, F, time) layout —
+    and ``columns`` (B,) int64 on the host, ``ceil(n_b / hop)``.  ``lengths`` (the "audio_lengths" of a ragged ``generate()``): clip b is
+    exactly the clip converted alone at its own length, zero rows follow it, and nothing behind ``lengths[b]`` is read."""
+    x = _mono_rows(wav, "audio_to_spectrogram")
+    B, N = x.shape[0], x.shape[-1]
+    if N < 1:
+        raise L.VauraHipError(f"a waveform of shape {tuple(wav.shape)} holds no samples")
+    if lengths is None:
+        n_in = [N] * B
+    else:
+        if not clip_params.is_per_clip(lengths):
+            raise L.VauraHipError(f"lengths must be one integer per clip (a list, tuple or 1-D tensor), got {lengths!r}")
+        n_in = clip_params._int_list("lengths", lengths)
+        if len(n_in) != B:
+            raise L.VauraHipError(f"per-clip lengths has {len(n_in)} values for a batch of {B} clips")
+        if min(n_in) < 1 or max(n_in) > N:
+            raise L.VauraHipError(f"lengths must lie in 1 .. {N} (the samples of a row), got {n_in}")
+    cols = [fmt.plan.columns(n) for n in n_in]
+    records = [[0, n, 0, c, n] for n, c in zip(n_in, cols)]              # the stream's one and last block, from its start
+    return _spec_launch(fmt, x, N, records, None, None, max(cols)), torch.tensor(cols, dtype=torch.int64)
+
+
+class SpectrogramStream:
+    """``audio_to_spectrogram`` block by block: ``push`` takes the next samples of every clip and returns the columns whose window is
+    complete.  The pushes concatenated per clip are bit for bit ``audio_to_spectrogram`` of the whole clips.  State: two integers per
+    clip on the host (samples received, columns emitted) and a ping-pong pair of carry rows on the device (``n_fft - 1`` samples per
+    clip).  One push is one launch and one asynchronous copy of a (B, 5) record from a pinned buffer the stream keeps; nothing waits
+    for the device."""
+
+    def __init__(self, fmt: SpectrogramFormat, batch: int, device):
+        if isinstance(batch, bool) or not isinstance(batch, int) or batch < 1:
+            raise L.VauraHipError(f"SpectrogramStream takes a batch of at least one clip, got {batch!r}")
+        self.fmt, self.batch, self.device = fmt, batch, torch.device(device)
+        if self.device.type == "cuda" and self.device.index is None:
+            self.device = torch.device("cuda", torch.cuda.current_device())
+        self.received, self.emitted, self.finished = [0] * batch, [0] * batch, [False] * batch
+        self._carry = torch.zeros(2, batch, fmt.plan.history(), dtype=torch.float32, device=self.device)
+        self._cur = 0
+        self._ring = _RecordRing(batch)
+        self._empty = torch.zeros(batch, 1, 1, dtype=torch.float32, device=self.device)
+
+    _per_clip = PcmStream._per_clip
+
+    def push(self, audio: Optional[torch.Tensor], samples=None, final=False) -> Tuple[torch.Tensor, List[int]]:
+        """audio (B, 1, n) fp32 on the stream's device: the next ``samples[b]`` samples of clip b (default: all n; 0 is allowed, and
+        ``audio`` may be None when every clip gives 0) -> (spec (B, max(counts), F), counts): clip b's next ``counts[b]`` columns, zero
+        rows behind them.  A column leaves once the last sample of its window is there; ``final`` (a bool, or one per clip) flushes the
+        clip's remaining columns up to ``ceil(received / hop)``, their windows zero-padded; a finished clip takes no more samples."""
+        if audio is None:
+            x, n = self._empty, 0
+        else:
+            x = _mono_rows(audio, "SpectrogramStream.push")
+            n = x.shape[-1]
+            if x.shape[0] != self.batch or x.device != self.device:
+                raise L.VauraHipError(f"SpectrogramStream of {self.batch} clips on {self.device}: got a block of shape "
+                                      f"{tuple(audio.shape)} on {x.device}")
+            if n == 0:
+                x = self._empty
+        counts_in = [n] * self.batch if samples is None else self._per_clip("samples", samples, int)
+        fin = self._per_clip("final", final, bool)
+        if min(counts_in) < 0 or max(counts_in) > n:
+            raise L.VauraHipError(f"samples must lie in 0 .. {n} (the samples of a block's row), got {counts_in}")
+        for b in range(self.batch):
+            if self.finished[b] and counts_in[b]:
+                raise L.VauraHipError(f"clip {b} of the stream was flushed (final) and takes no more samples; got {counts_in[b]}")
+        records, received, emitted = SG.push_records(self.fmt.plan, self.received, self.emitted, counts_in, fin)
+        counts = [r[3] for r in records]
+        spec = _spec_launch(self.fmt, x, max(n, 1), records, self._carry[self._cur], self._carry[1 - self._cur], max(counts),
+                            ring=self._ring)
+        self._cur = 1 - self._cur
+        self.received, self.emitted = received, emitted
+        self.finished = [a or b for a, b in zip(self.finished, fin)]
+        return spec, counts
+
+
+def stream_spectrogram(blocks: Iterable[dict], fmt: SpectrogramFormat) -> Iterator[dict]:
+    """Wrap a streaming generator (``generate_stream``, ``generate_long_stream`` with or without ``block_frames``,
+    ``generate_long_clips_stream``) or the blocks of a live session: every dict comes back with "spectrogram" ((B, max columns, F):
+    the columns that became complete with this block), "spec_start" and "spec_columns" (one int per clip: the first column's index in
+    the clip and how many there are) added; every other key passes through, so it composes with ``stream_pcm`` in either order.  A
+    column waits for the last sample of its window, ``(n_fft - hop) / 2`` samples beyond its frame; the dict whose "final" is true
+    carries every clip's remaining columns.  At hop 512 a clip's columns are its frames."""
+    stream = None
+    for blk in blocks:
+        audio = blk["audio"]
+        B = audio.shape[0]
+        frames = blk["frames"]
+        frames = [int(f) for f in frames] if isinstance(frames, (list, tuple)) else [int(frames)] * B
+        hop = audio.shape[-1] // max(frames) if max(frames) > 0 else 0
+        if stream is None:
+            stream = SpectrogramStream(fmt, B, audio.device)
+        start = list(stream.emitted)
+        spec, counts = stream.push(audio, [f * hop for f in frames], final=bool(blk["final"]))
+        out = dict(blk)
+        out.update(spectrogram=spec, spec_start=start, spec_columns=counts)
+        yield out
