@@ -1019,6 +1019,31 @@ int vaura_video_preprocess_yuv420(const uint8_t* video, int64_t video_bytes, int
 /* dynamic LDS bytes of one workgroup of that launch (0 for sizes the kernel does not take) */
 size_t vaura_video_preprocess_yuv420_lds_bytes(int layout, int crop_w, int h_taps, int span, int tile_src_rows);
 
+/* Both launches with the source frame of every output frame named by a table: video at its own frame rate, converted to the
+ * model's 25 fps by dropping and repeating frames (vaura_amd/preprocess.py: fps_plan restates ffmpeg's `fps` filter at its defaults
+ * — parity unpinned by the reference, which re-encoded its videos offline), in one pass or block by block (VideoFrameStream).
+ *   frame_map  device, int32 (n_clips, S * F): output frame (b, s, f) shows
+ *                e >= 0  source frame e of clip b (the kernel clamps e into [0, T); the host validates before the launch)
+ *                -1      nothing: the output frame's bytes stay as they are
+ *                -2      clip b's frame in `carry` (left as it is where carry is NULL)
+ *   carry      NULL, or one frame per clip in the source layout: (n_clips, C, H, W) / (n_clips, H, W, C) bytes; for the 4:2:0
+ *              entry clip b's surface at byte b * frame_stride.  carry_used != 0 says that the map holds a -2.
+ *   T          the frames per clip that `video` holds; any T >= 1 (a block of a stream is shorter than a segment)
+ * The siblings' seg_start / seg_stride are not taken: the table has them applied.  Everything else, the arithmetic and every
+ * refusal are the sibling's (T < F and segments outside [0, T) excepted), and VAURA_ERR_ARG for a NULL or misaligned frame_map and
+ * for carry_used with a NULL carry — all before any launch.                                                                        */
+int vaura_video_preprocess_frames(const uint8_t* video, int channels_last, int n_clips, int T, int C, int H, int W, int resize,
+                                  int crop_h, int crop_w, int F, int S, const int32_t* h_rel, const int16_t* h_w, int h_taps, int h_prec,
+                                  const int32_t* v_start, const int16_t* v_w, int v_taps, int v_prec, int x0, int span, int tile_rows,
+                                  int tile_src_rows, const float* lut, float* out, const int32_t* frame_map, const uint8_t* carry,
+                                  int carry_used, vaura_stream_t s);
+int vaura_video_preprocess_yuv420_frames(const uint8_t* video, int64_t video_bytes, int layout, int64_t pitch, int64_t chroma_offset,
+                                         int64_t frame_stride, int n_clips, int T, int H, int W, int y_off, int cy, int crv, int cgu,
+                                         int cgv, int cbu, int resize, int crop_h, int crop_w, int F, int S, const int32_t* h_rel,
+                                         const int16_t* h_w, int h_taps, int h_prec, const int32_t* v_start, const int16_t* v_w,
+                                         int v_taps, int v_prec, int x0, int span, int tile_rows, int tile_src_rows, const float* lut,
+                                         float* out, const int32_t* frame_map, const uint8_t* carry, int carry_used, vaura_stream_t s);
+
 /* -------------------------------------------------------------------------------------------
  * Audio preprocessing (csrc/audio_pre.hip): decoded PCM -> the codec's padded mono input.  The `audio_transforms_test` list of
  * configs/generate_vas.yaml:43-54 (AudioStereoToMono -> AudioResample(44100) -> AudioTrim; models/data/transforms/

@@ -14,6 +14,11 @@ the link instead of 3) beside the RGB rows, which are the comparison: the RGB in
 six rows compute the same output (checked before timing).  The rows alternate inside every round, so they share clocks and neighbours.
 
     python tools/time_preprocess.py [rounds] --yuv > profiles/preprocess_yuv_timing.txt
+
+--fps: video at its own frame rate (main_fps): the table launch beside the existing launch on the frames selected beforehand and
+beside index_select + the existing launch, 60 and 30 fps, RGB and NV12, device and pinned; then a VideoFrameStream per push.
+
+    python tools/time_preprocess.py [rounds] --fps > profiles/preprocess_fps_timing.txt
 """
 import json
 import os
@@ -26,7 +31,7 @@ import torch
 import torch.nn.functional as Fn
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from vaura_amd.preprocess import VideoPreprocessor, crop_offset, resized_size, yuv420_to_rgb_u8  # noqa: E402
+from vaura_amd.preprocess import VideoPreprocessor, crop_offset, fps_plan, resized_size, yuv420_to_rgb_u8  # noqa: E402
 
 COPY_RATE = 6.29e12
 B, T, H, W = 8, 64, 360, 640
@@ -103,6 +108,90 @@ def main_yuv(rounds):
     print(json.dumps(rec))
 
 
+def main_fps(rounds):
+    """8 clips x 77 frames of 360 x 640 at 60 fps (32 output frames, 2 segments) and at 30 fps (64, 4 segments), RGB and NV12:
+      table            the table launch on the source frames (vaura_video_preprocess_frames / _yuv420_frames)
+      preselected      the existing launch on the same frames selected beforehand (the selection is not timed)
+      select + plain   torch's index_select on the device, then the existing launch
+    from device memory and (table, preselected) from pinned host memory; then a VideoFrameStream of the 30 fps clips pushed 1 and 16
+    frames at a time: host time per push (the call returns without waiting for the kernel) and device time per push (events around
+    each push: its map upload, launches and carry copy)."""
+    dev = torch.device("cuda:0")
+    n = 77
+    g = torch.Generator().manual_seed(0)
+    y = torch.randint(0, 256, (B, n, H, W), dtype=torch.uint8, generator=g)
+    u = torch.randint(0, 256, (B, n, H // 2, W // 2), dtype=torch.uint8, generator=g)
+    v = torch.randint(0, 256, (B, n, H // 2, W // 2), dtype=torch.uint8, generator=g)
+    host = {"rgb": torch.randint(0, 256, (B, n, 3, H, W), dtype=torch.uint8, generator=g),
+            "nv12": torch.cat([y, torch.stack([u, v], dim=-1).reshape(B, n, H // 2, W)], dim=2)}
+    kw = {"rgb": {}, "nv12": {"input_format": "nv12"}}
+    rec = {"shape": {"clips": B, "frames": n, "H": H, "W": W}, "clocks_before": _clocks(), "one_pass": {}, "stream": {}}
+    stream = torch.cuda.Stream(dev)
+    print(f"# {B} x {n} frames of {H} x {W}; {rounds} rounds, the rows of a block in turn inside each round", flush=True)
+    with torch.cuda.stream(stream):
+        on_dev = {k: t.to(dev) for k, t in host.items()}
+        pinned = {k: t.pin_memory() for k, t in host.items()}
+        for rate in (60, 30):
+            table = fps_plan(n, rate).table
+            idx = torch.from_numpy(table.astype("int64"))
+            idx_dev = idx.to(dev)
+            for fmt in ("rgb", "nv12"):
+                plain, fps = VideoPreprocessor(device=dev, **kw[fmt]), VideoPreprocessor(device=dev, src_fps=rate, **kw[fmt])
+                sel_dev = on_dev[fmt].index_select(1, idx_dev)
+                sel_pin = host[fmt].index_select(1, idx).pin_memory()
+                want = plain(sel_dev)
+                if not (torch.equal(fps(on_dev[fmt]), want) and torch.equal(fps(pinned[fmt]), want)):
+                    raise SystemExit(f"{fmt} at {rate} fps: the table launch differs from the existing launch on the selected frames")
+                fns = {"device table": lambda: fps(on_dev[fmt]),
+                       "device preselected": lambda: plain(sel_dev),
+                       "device select + plain": lambda: plain(on_dev[fmt].index_select(1, idx_dev)),
+                       "pinned table": lambda: fps(pinned[fmt]),
+                       "pinned preselected": lambda: plain(sel_pin)}
+                for _ in range(3):
+                    for fn in fns.values():
+                        fn()
+                torch.cuda.synchronize()
+                res = _events_alternating(stream, fns, rounds)
+                key = f"{fmt} {rate} fps"
+                rec["one_pass"][key] = {"frames_out": int(len(table)), "frames_named": int(len(set(table.tolist()))),
+                                        "rows": {k: {"ms": m, "min_ms": lo, "max_ms": hi} for k, (m, lo, hi) in res.items()}}
+                print(f"{key}: {len(table)} output frames from {len(set(table.tolist()))} of {n} source frames", flush=True)
+                for name, (med, lo, hi) in res.items():
+                    base = res["pinned preselected" if name.startswith("pinned") else "device preselected"]
+                    print(f"{name:>24}: {med:8.3f} ms per batch (min {lo:.3f}, max {hi:.3f})  {med / base[0]:.2f}x the preselected row "
+                          f"(whose min-max spread is {base[2] - base[1]:.3f} ms)", flush=True)
+                del sel_dev, sel_pin, want
+        # the stream: 30 fps, frames already on the device
+        for fmt in ("rgb", "nv12"):
+            pre = VideoPreprocessor(device=dev, **kw[fmt])
+            for per_push in (1, 16):
+                host_ms, dev_ms = [], []
+                for r in range(rounds + 2):
+                    vs = pre.open_stream(B, src_fps=30)
+                    pushes, t_host, evs = 0, 0.0, []
+                    for lo in range(0, n, per_push):
+                        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                        a.record(stream)
+                        t0 = time.perf_counter()
+                        vs.push(on_dev[fmt][:, lo:lo + per_push])
+                        t_host += time.perf_counter() - t0
+                        b.record(stream)
+                        evs.append((a, b))
+                        pushes += 1
+                    torch.cuda.synchronize()
+                    vs.close()
+                    if r >= 2:                                           # two warm-up passes
+                        host_ms.append(1e3 * t_host / pushes)
+                        dev_ms.append(sum(a.elapsed_time(b) for a, b in evs) / pushes)
+                key = f"{fmt} {per_push} frame{'s' if per_push > 1 else ''} per push"
+                rec["stream"][key] = {"pushes": pushes, "host_ms_per_push": statistics.median(host_ms), "device_ms_per_push": statistics.median(dev_ms)}
+                print(f"stream {key:>24}: host {statistics.median(host_ms):7.3f} ms per push (min {min(host_ms):.3f}, max {max(host_ms):.3f}), "
+                      f"device {statistics.median(dev_ms):7.3f} ms per push (min {min(dev_ms):.3f}, max {max(dev_ms):.3f}); {pushes} pushes, "
+                      f"{B} clips", flush=True)
+    rec["clocks_after"] = _clocks()
+    print(json.dumps(rec))
+
+
 def _cpu_route(video, threads, rounds):
     torch.set_num_threads(threads)
     oh, ow = resized_size(H, W, 256)
@@ -133,10 +222,12 @@ def _clocks():
 
 
 def main():
-    args = [a for a in sys.argv[1:] if a != "--yuv"]
+    args = [a for a in sys.argv[1:] if a not in ("--yuv", "--fps")]
     rounds = int(args[0]) if args else 20
     if "--yuv" in sys.argv:
         return main_yuv(rounds)
+    if "--fps" in sys.argv:
+        return main_fps(rounds)
     dev = torch.device("cuda:0")
     video = torch.randint(0, 256, (B, T, 3, H, W), dtype=torch.uint8, generator=torch.Generator().manual_seed(0))
     pre = VideoPreprocessor(device=dev)

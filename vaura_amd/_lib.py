@@ -178,6 +178,11 @@ SIGNATURES = {
                                                 *[C.c_int] * 7, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
                                                 *[C.c_int] * 6, C.c_void_p, C.c_void_p, C.c_void_p]),
     "vaura_video_preprocess_yuv420_lds_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
+    "vaura_video_preprocess_frames": (C.c_int, [C.c_void_p, *[C.c_int] * 11, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                                *[C.c_int] * 6, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
+    "vaura_video_preprocess_yuv420_frames": (C.c_int, [C.c_void_p, C.c_int64, C.c_int, C.c_int64, C.c_int64, C.c_int64, *[C.c_int] * 10,
+                                                       *[C.c_int] * 5, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                                       *[C.c_int] * 6, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
     "vaura_audio_preprocess": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_void_p, C.c_int, C.c_int, C.c_int,
                                          C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
     "vaura_audio_preprocess_lds_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int, C.c_int]),

@@ -26,6 +26,11 @@
 // LDS (the host's integer formula: 2^14-scaled coefficients, chroma replicated over its 2 x 2 block, no interpolation) and filters
 // each of the three as the NCHW instance filters a row.  yuv -> RGB uint8 -> the resize above: the same function as converting on the
 // host first (vaura_amd/preprocess.py: yuv420_to_rgb_u8) and calling the RGB kernel.
+//
+// video_preprocess_frames_kernel / video_preprocess_yuv_frames_kernel are the same launches for video that is not at the model's 25
+// frames per second (the reference re-encoded offline: scripts/reencode_videos.py:71, ffmpeg -vf fps=25): the source frame of every
+// output frame comes from a device table the host builds (vaura_amd/preprocess.py: fps_plan, frames dropped and repeated as ffmpeg's
+// fps filter does), so selecting frames costs no pass over the video.  See the comment in front of them.
 #include "common.h"
 
 #define PREPROC_MAX_TAPS VAURA_PREPROC_MAX_TAPS
@@ -311,6 +316,218 @@ __global__ __launch_bounds__(64 * PREPROC_WAVES) void video_preprocess_yuv_kerne
   }
 }
 
+// ---- The same launches with every output frame's source frame read from a device table (video at its own frame rate: the host's
+// fps plan names, per 25 fps tick, the source frame shown; vaura_amd/preprocess.py: fps_plan).  In the kernels above the source frame
+// is `b * T + seg_start + s * seg_stride + f`; here it is frame_map[(b * S + s) * F + f], one wave-uniform read:
+//   e >= 0  source frame e of the clip, clamped into [0, T)        -1  the output frame is left as it is (the workgroup returns)
+//   -2      the clip's frame in `carry` (one frame per clip in the source layout: the last frame of an earlier block of a stream)
+// They are kernels of their own so that the four functions above stay the source and the device code they were; the argument
+// structs embed theirs, and the staging, filtering and store are restated once for these kernels (frames_prologue, frames_phase2).
+struct PreprocFramesArgs {
+  PreprocArgs p;
+  const int32_t* frame_map;   // (n_clips, S * F)
+  const uint8_t* carry;       // n_clips frames, or NULL
+};
+
+struct PreprocYuvFramesArgs {
+  PreprocYuvArgs p;
+  const int32_t* frame_map;
+  const uint8_t* carry;       // clip b's surface at byte b * frame_stride, or NULL
+};
+
+// first byte of the source frame of output frame `of` (clip b), NULL where the output frame is left as it is; a -2 without a carry
+// buffer is refused by the host and leaves the frame as it is here
+template <class A>
+__device__ __forceinline__ const uint8_t* mapped_frame(const A& a, int of, int b, size_t frame_bytes) {
+  const int e = a.frame_map[of];
+  if (e == -2 && a.carry) return a.carry + (size_t)b * frame_bytes;
+  if (e == -1 || e == -2) return nullptr;
+  return a.p.src + ((size_t)b * a.p.T + min(max(e, 0), a.p.T - 1)) * frame_bytes;
+}
+
+struct PreprocLds {
+  float* lut;        // 768 floats
+  int32_t* hrel;     // crop_w
+  int16_t* hw;       // crop_w * h_taps
+  uint32_t* slabs;   // PREPROC_WAVES slabs of slab_dwords
+  uint32_t* tile;    // [3][tile_src_rows][crop_w / 4] words of 4 uint8
+};
+
+// the workgroup's LDS layout (that of the kernels above) with the three tables copied in; ends with a barrier
+template <class P>
+__device__ __forceinline__ PreprocLds frames_prologue(const P& a, uint32_t* smem, int tid) {
+  PreprocLds l;
+  l.lut = reinterpret_cast<float*>(smem);
+  l.hrel = reinterpret_cast<int32_t*>(smem + 768);
+  l.hw = reinterpret_cast<int16_t*>(smem + 768 + a.crop_w);
+  l.slabs = smem + 768 + a.crop_w + ((a.crop_w * a.h_taps) >> 1);
+  l.tile = l.slabs + PREPROC_WAVES * a.slab_dwords;
+  for (int i = tid; i < 768; i += 64 * PREPROC_WAVES) l.lut[i] = a.lut[i];
+  for (int i = tid; i < a.crop_w; i += 64 * PREPROC_WAVES) l.hrel[i] = min(max(a.h_rel[i], 0), a.span - a.h_taps);
+  for (int i = tid; i < a.crop_w * a.h_taps; i += 64 * PREPROC_WAVES) l.hw[i] = a.h_w[i];
+  __syncthreads();
+  return l;
+}
+
+// horizontal pass of one planar uint8 row `sb` (pixel step PIX bytes) into row yy of channel c of the tile
+template <int PIX, class P>
+__device__ __forceinline__ void frames_filter_row(const P& a, const PreprocLds& l, const uint8_t* sb, int c, int yy, int lane) {
+  const int nq = a.crop_w >> 2;
+  const int hhalf = 1 << (a.h_prec - 1);
+  for (int q = lane; q < nq; q += 64) {
+    uint32_t word = 0;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      const int x = 4 * q + e;
+      const uint8_t* t = sb + PIX * l.hrel[x];
+      const int16_t* w = l.hw + x * a.h_taps;
+      int acc = hhalf;
+      for (int k = 0; k < a.h_taps; ++k) acc += (int)t[PIX * k] * (int)w[k];
+      word |= level_u8(acc, a.h_prec) << (8 * e);
+    }
+    l.tile[((size_t)c * a.tile_src_rows + yy) * nq + q] = word;
+  }
+}
+
+// vertical pass, level -> fp32 table, 16-byte stores: phase 2 of the kernels above
+template <class P>
+__device__ __forceinline__ void frames_phase2(const P& a, const PreprocLds& l, int bs, int f, int r0, int nr, int ylo, int nrows, int tid) {
+  const int nq = a.crop_w >> 2;
+  const int vhalf = 1 << (a.v_prec - 1);
+  const int items = 3 * nr * nq;
+  for (int it = tid; it < items; it += 64 * PREPROC_WAVES) {
+    const int q = it % nq, rc = it / nq, rr = rc % nr, c = rc / nr;
+    const int r = r0 + rr;
+    const int ys = min(max(a.v_start[r] - ylo, 0), nrows - a.v_taps);
+    const int16_t* w = a.v_w + (size_t)r * a.v_taps;
+    const uint32_t* t = l.tile + ((size_t)c * a.tile_src_rows + ys) * nq + q;
+    int a0 = vhalf, a1 = vhalf, a2 = vhalf, a3 = vhalf;
+    for (int k = 0; k < a.v_taps; ++k) {
+      const uint32_t d = t[(size_t)k * nq];
+      const int wk = w[k];
+      a0 += (int)(d & 255u) * wk;
+      a1 += (int)((d >> 8) & 255u) * wk;
+      a2 += (int)((d >> 16) & 255u) * wk;
+      a3 += (int)(d >> 24) * wk;
+    }
+    const float* lc = l.lut + 256 * c;
+    const f32x4 o = {lc[level_u8(a0, a.v_prec)], lc[level_u8(a1, a.v_prec)], lc[level_u8(a2, a.v_prec)], lc[level_u8(a3, a.v_prec)]};
+    float* dst = a.out + ((((size_t)bs * 3 + c) * a.F + f) * a.crop_h + r) * a.crop_w + 4 * q;
+    *reinterpret_cast<f32x4*>(dst) = o;
+  }
+}
+
+template <bool NHWC>
+__global__ __launch_bounds__(64 * PREPROC_WAVES) void video_preprocess_frames_kernel(const PreprocFramesArgs fa) {
+  extern __shared__ uint32_t smem[];
+  const PreprocArgs& a = fa.p;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int of = blockIdx.y;                                           // output frame (b, s, f)
+  const int f = of % a.F, bs = of / a.F, b = bs / a.S;
+  const uint8_t* frame = mapped_frame(fa, of, b, (size_t)3 * a.H * a.W);   // the same for the whole workgroup
+  if (!frame) return;
+  const int r0 = blockIdx.x * a.tile_rows;
+  const int nr = min(a.tile_rows, a.crop_h - r0);
+  const int ylo = min(max(a.v_start[r0], 0), a.H - a.v_taps);
+  const int nrows = min(a.tile_src_rows, a.H - ylo);
+  const PreprocLds l = frames_prologue(a, smem, tid);
+
+  // ---- phase 1: horizontal pass into the tile, one source row of one channel [NCHW] or of all three [NHWC] per wave
+  uint32_t* slab = l.slabs + wave * a.slab_dwords;
+  const int jobs = NHWC ? nrows : 3 * nrows;
+  for (int j0 = 0; j0 < jobs; j0 += PREPROC_WAVES) {
+    const int j = j0 + wave;                                           // wave-uniform
+    const int yy = NHWC ? j : j / 3, cj = NHWC ? 0 : j - 3 * yy;
+    int shift = 0;
+    if (j < jobs) {
+      const size_t row = NHWC ? ((size_t)(ylo + yy) * a.W + a.x0) * 3 : ((size_t)cj * a.H + (ylo + yy)) * a.W + a.x0;
+      shift = stage_bytes(slab, frame + row, (NHWC ? 3 : 1) * a.span, lane);
+    }
+    __syncthreads();
+    if (j < jobs) {
+      const uint8_t* sb = reinterpret_cast<const uint8_t*>(slab) + shift;
+      if (NHWC) {
+#pragma unroll 1
+        for (int c = 0; c < 3; ++c) frames_filter_row<3>(a, l, sb + c, c, yy, lane);
+      } else {
+        frames_filter_row<1>(a, l, sb, cj, yy, lane);
+      }
+    }
+    __syncthreads();
+  }
+  frames_phase2(a, l, bs, f, r0, nr, ylo, nrows, tid);
+}
+
+template <int LAYOUT>   // VAURA_YUV_NV12 / VAURA_YUV_I420
+__global__ __launch_bounds__(64 * PREPROC_WAVES) void video_preprocess_yuv_frames_kernel(const PreprocYuvFramesArgs fa) {
+  extern __shared__ uint32_t smem[];
+  const PreprocYuvArgs& a = fa.p;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int of = blockIdx.y;                                           // output frame (b, s, f)
+  const int f = of % a.F, bs = of / a.F, b = bs / a.S;
+  const uint8_t* frame = mapped_frame(fa, of, b, (size_t)a.frame_stride);
+  if (!frame) return;
+  const int r0 = blockIdx.x * a.tile_rows;
+  const int nr = min(a.tile_rows, a.crop_h - r0);
+  const int ylo = min(max(a.v_start[r0], 0), a.H - a.v_taps);
+  const int nrows = min(a.tile_src_rows, a.H - ylo);
+  const PreprocLds l = frames_prologue(a, smem, tid);
+
+  // ---- phase 1: one source row per wave: stage luma + chroma, convert once, horizontal pass of the three channels into the tile
+  uint32_t* luma = l.slabs + wave * a.slab_dwords;
+  uint32_t* chroma = luma + yuv_luma_dwords(a.span);
+  uint32_t* rgb = chroma + yuv_chroma_dwords(a.span);
+  const int rgbw = yuv_rgb_dwords(a.span);
+  const int c0 = a.x0 >> 1;                                            // first chroma sample of the span
+  const int nc = ((a.x0 + a.span - 1) >> 1) - c0 + 1;                  // chroma samples the span touches (<= span / 2 + 1)
+  for (int j0 = 0; j0 < nrows; j0 += PREPROC_WAVES) {
+    const int yy = j0 + wave;                                          // wave-uniform
+    int ysh = 0, ush = 0, vsh = 0;
+    if (yy < nrows) {
+      const int y = ylo + yy;
+      ysh = stage_bytes(luma, frame + (size_t)y * a.pitch + a.x0, a.span, lane);
+      const uint8_t* cplane = frame + a.chroma_offset;
+      if (LAYOUT == VAURA_YUV_NV12) {
+        ush = stage_bytes(chroma, cplane + (size_t)(y >> 1) * a.pitch + 2 * c0, 2 * nc, lane);
+      } else {
+        const size_t cp = (size_t)(a.pitch >> 1);
+        ush = stage_bytes(chroma, cplane + (size_t)(y >> 1) * cp + c0, nc, lane);
+        vsh = stage_bytes(chroma + yuv_plane_dwords(a.span), cplane + ((size_t)(a.H >> 1) + (y >> 1)) * cp + c0, nc, lane);
+      }
+    }
+    __syncthreads();
+    if (yy < nrows) {
+      const uint8_t* yb = reinterpret_cast<const uint8_t*>(luma) + ysh;
+      const uint8_t* ub = reinterpret_cast<const uint8_t*>(chroma) + ush;
+      const uint8_t* vb = reinterpret_cast<const uint8_t*>(chroma + yuv_plane_dwords(a.span)) + vsh;
+      for (int m = lane; m < rgbw; m += 64) {                          // 4 pixels per lane, one word per channel
+        uint32_t wr = 0, wg = 0, wb = 0;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          const int i = min(4 * m + e, a.span - 1);                    // the last word may pass the span: its spare bytes are never read
+          const int ci = ((a.x0 + i) >> 1) - c0;
+          const int u = (LAYOUT == VAURA_YUV_NV12 ? (int)ub[2 * ci] : (int)ub[ci]) - 128;
+          const int v = (LAYOUT == VAURA_YUV_NV12 ? (int)ub[2 * ci + 1] : (int)vb[ci]) - 128;
+          const int yv = a.cy * ((int)yb[i] - a.y_off) + (1 << (PREPROC_YUV_PREC - 1));
+          wr |= color_u8(yv + a.crv * v) << (8 * e);
+          wg |= color_u8(yv + a.cgu * u + a.cgv * v) << (8 * e);
+          wb |= color_u8(yv + a.cbu * u) << (8 * e);
+        }
+        rgb[m] = wr;
+        rgb[rgbw + m] = wg;
+        rgb[2 * rgbw + m] = wb;
+      }
+    }
+    __syncthreads();
+    if (yy < nrows) {
+#pragma unroll 1
+      for (int c = 0; c < 3; ++c) frames_filter_row<1>(a, l, reinterpret_cast<const uint8_t*>(rgb + c * rgbw), c, yy, lane);
+    }
+    __syncthreads();
+  }
+  frames_phase2(a, l, bs, f, r0, nr, ylo, nrows, tid);
+}
+
 extern "C" {
 
 // what both entry points refuse about the resize / crop / segments / tables, in vaura_video_preprocess's order
@@ -367,17 +584,9 @@ size_t vaura_video_preprocess_lds_bytes(int channels_last, int crop_w, int h_tap
   return preproc_lds_bytes(channels_last, crop_w, h_taps, span, tile_src_rows);
 }
 
-int vaura_video_preprocess_yuv420(const uint8_t* video, int64_t video_bytes, int layout, int64_t pitch, int64_t chroma_offset,
-                                  int64_t frame_stride, int n_clips, int T, int H, int W, int y_off, int cy, int crv, int cgu, int cgv,
-                                  int cbu, int resize, int crop_h, int crop_w, int F, int S, int seg_start, int seg_stride,
-                                  const int32_t* h_rel, const int16_t* h_w, int h_taps, int h_prec, const int32_t* v_start,
-                                  const int16_t* v_w, int v_taps, int v_prec, int x0, int span, int tile_rows, int tile_src_rows,
-                                  const float* lut, float* out, vaura_stream_t s) {
-  if (!video || !h_rel || !h_w || !v_start || !v_w || !lut || !out) return VAURA_ERR_ARG;
-  if (layout != VAURA_YUV_NV12 && layout != VAURA_YUV_I420) return VAURA_ERR_ARG;
-  if (const int st = preproc_check(n_clips, T, 3, H, W, resize, crop_h, crop_w, F, S, seg_start, seg_stride, h_rel, h_w, h_taps, h_prec,
-                                   v_start, v_w, v_taps, v_prec, x0, span, tile_rows, tile_src_rows, lut, out))
-    return st;
+// what both 4:2:0 entry points refuse about the surfaces and the colour formula, after preproc_check
+static int preproc_yuv_check(int64_t video_bytes, int layout, int64_t pitch, int64_t chroma_offset, int64_t frame_stride, int n_clips, int T,
+                             int H, int W, int y_off, int cy, int crv, int cgu, int cgv, int cbu) {
   if ((H & 1) || (W & 1)) return VAURA_ERR_SHAPE;                      // 4:2:0: one chroma sample per 2 x 2 luma block
   // |acc| <= 3 * 2^20 * 256 < 2^31 for any such coefficients (the host's are below 2^16)
   const int lim = 1 << 20;
@@ -394,6 +603,22 @@ int vaura_video_preprocess_yuv420(const uint8_t* video, int64_t video_bytes, int
   if (frame_stride < frame_end || frame_stride > (int64_t)1 << 40) return VAURA_ERR_ARG;       // frames overlap
   const int64_t n_frames = (int64_t)n_clips * T;
   if (video_bytes < 0 || n_frames - 1 > (video_bytes - frame_end) / frame_stride || video_bytes < frame_end) return VAURA_ERR_ARG;
+  return 0;
+}
+
+int vaura_video_preprocess_yuv420(const uint8_t* video, int64_t video_bytes, int layout, int64_t pitch, int64_t chroma_offset,
+                                  int64_t frame_stride, int n_clips, int T, int H, int W, int y_off, int cy, int crv, int cgu, int cgv,
+                                  int cbu, int resize, int crop_h, int crop_w, int F, int S, int seg_start, int seg_stride,
+                                  const int32_t* h_rel, const int16_t* h_w, int h_taps, int h_prec, const int32_t* v_start,
+                                  const int16_t* v_w, int v_taps, int v_prec, int x0, int span, int tile_rows, int tile_src_rows,
+                                  const float* lut, float* out, vaura_stream_t s) {
+  if (!video || !h_rel || !h_w || !v_start || !v_w || !lut || !out) return VAURA_ERR_ARG;
+  if (layout != VAURA_YUV_NV12 && layout != VAURA_YUV_I420) return VAURA_ERR_ARG;
+  if (const int st = preproc_check(n_clips, T, 3, H, W, resize, crop_h, crop_w, F, S, seg_start, seg_stride, h_rel, h_w, h_taps, h_prec,
+                                   v_start, v_w, v_taps, v_prec, x0, span, tile_rows, tile_src_rows, lut, out))
+    return st;
+  if (const int st = preproc_yuv_check(video_bytes, layout, pitch, chroma_offset, frame_stride, n_clips, T, H, W, y_off, cy, crv, cgu, cgv, cbu))
+    return st;
   PreprocYuvArgs a;
   a.src = video; a.h_rel = h_rel; a.h_w = h_w; a.v_start = v_start; a.v_w = v_w; a.lut = lut; a.out = out;
   a.pitch = pitch; a.chroma_offset = chroma_offset; a.frame_stride = frame_stride;
@@ -415,6 +640,76 @@ size_t vaura_video_preprocess_yuv420_lds_bytes(int layout, int crop_w, int h_tap
   if ((layout != VAURA_YUV_NV12 && layout != VAURA_YUV_I420) || crop_w <= 0 || (crop_w & 3) || h_taps <= 0 || span <= 0 || tile_src_rows <= 0)
     return 0;
   return preproc_yuv_lds_bytes(crop_w, h_taps, span, tile_src_rows);
+}
+
+// ---- the launches with a frame table.  The segment arguments of the siblings have no meaning here (the table names the source
+// frame of every output frame), so they are not taken; what preproc_check says about segments is asked of the output sequence.
+static int preproc_frames_check(const int32_t* frame_map, const uint8_t* carry, int carry_used, int T, int F, int S) {
+  if (!frame_map || (reinterpret_cast<uintptr_t>(frame_map) & 3)) return VAURA_ERR_ARG;
+  if (carry_used && !carry) return VAURA_ERR_ARG;
+  if (T <= 0 || F <= 0) return VAURA_ERR_ARG;
+  if (S <= 0 || S > 65535 || F > 65535) return VAURA_ERR_SHAPE;
+  return 0;
+}
+
+int vaura_video_preprocess_frames(const uint8_t* video, int channels_last, int n_clips, int T, int C, int H, int W, int resize,
+                                  int crop_h, int crop_w, int F, int S, const int32_t* h_rel, const int16_t* h_w, int h_taps, int h_prec,
+                                  const int32_t* v_start, const int16_t* v_w, int v_taps, int v_prec, int x0, int span, int tile_rows,
+                                  int tile_src_rows, const float* lut, float* out, const int32_t* frame_map, const uint8_t* carry,
+                                  int carry_used, vaura_stream_t s) {
+  if (!video || !h_rel || !h_w || !v_start || !v_w || !lut || !out) return VAURA_ERR_ARG;
+  if (const int st = preproc_frames_check(frame_map, carry, carry_used, T, F, S)) return st;
+  if (const int st = preproc_check(n_clips, S * F, C, H, W, resize, crop_h, crop_w, F, S, 0, F, h_rel, h_w, h_taps, h_prec, v_start, v_w,
+                                   v_taps, v_prec, x0, span, tile_rows, tile_src_rows, lut, out))
+    return st;
+  PreprocFramesArgs fa;
+  PreprocArgs& a = fa.p;
+  a.src = video; a.h_rel = h_rel; a.h_w = h_w; a.v_start = v_start; a.v_w = v_w; a.lut = lut; a.out = out;
+  a.T = T; a.H = H; a.W = W; a.S = S; a.F = F; a.seg_start = 0; a.seg_stride = F;
+  a.crop_h = crop_h; a.crop_w = crop_w; a.h_taps = h_taps; a.h_prec = h_prec; a.v_taps = v_taps; a.v_prec = v_prec;
+  a.x0 = x0; a.span = span; a.tile_rows = tile_rows; a.tile_src_rows = tile_src_rows;
+  a.slab_dwords = ((channels_last ? 3 : 1) * span + 3 + 3) >> 2;
+  fa.frame_map = frame_map; fa.carry = carry;
+  const size_t lds = preproc_lds_bytes(channels_last, crop_w, h_taps, span, tile_src_rows);
+  if (lds > PREPROC_LDS_LIMIT) return VAURA_ERR_SHAPE;
+  const dim3 grid((unsigned)((crop_h + tile_rows - 1) / tile_rows), (unsigned)((int64_t)n_clips * S * F));
+  hipStream_t st = as_stream(s);
+  if (channels_last) VA_LAUNCH(video_preprocess_frames_kernel<true>, grid, dim3(64 * PREPROC_WAVES), lds, st, fa);
+  else VA_LAUNCH(video_preprocess_frames_kernel<false>, grid, dim3(64 * PREPROC_WAVES), lds, st, fa);
+  return 0;
+}
+
+int vaura_video_preprocess_yuv420_frames(const uint8_t* video, int64_t video_bytes, int layout, int64_t pitch, int64_t chroma_offset,
+                                         int64_t frame_stride, int n_clips, int T, int H, int W, int y_off, int cy, int crv, int cgu,
+                                         int cgv, int cbu, int resize, int crop_h, int crop_w, int F, int S, const int32_t* h_rel,
+                                         const int16_t* h_w, int h_taps, int h_prec, const int32_t* v_start, const int16_t* v_w,
+                                         int v_taps, int v_prec, int x0, int span, int tile_rows, int tile_src_rows, const float* lut,
+                                         float* out, const int32_t* frame_map, const uint8_t* carry, int carry_used, vaura_stream_t s) {
+  if (!video || !h_rel || !h_w || !v_start || !v_w || !lut || !out) return VAURA_ERR_ARG;
+  if (layout != VAURA_YUV_NV12 && layout != VAURA_YUV_I420) return VAURA_ERR_ARG;
+  if (const int st = preproc_frames_check(frame_map, carry, carry_used, T, F, S)) return st;
+  if (const int st = preproc_check(n_clips, S * F, 3, H, W, resize, crop_h, crop_w, F, S, 0, F, h_rel, h_w, h_taps, h_prec, v_start, v_w,
+                                   v_taps, v_prec, x0, span, tile_rows, tile_src_rows, lut, out))
+    return st;
+  if (const int st = preproc_yuv_check(video_bytes, layout, pitch, chroma_offset, frame_stride, n_clips, T, H, W, y_off, cy, crv, cgu, cgv, cbu))
+    return st;
+  PreprocYuvFramesArgs fa;
+  PreprocYuvArgs& a = fa.p;
+  a.src = video; a.h_rel = h_rel; a.h_w = h_w; a.v_start = v_start; a.v_w = v_w; a.lut = lut; a.out = out;
+  a.pitch = pitch; a.chroma_offset = chroma_offset; a.frame_stride = frame_stride;
+  a.y_off = y_off; a.cy = cy; a.crv = crv; a.cgu = cgu; a.cgv = cgv; a.cbu = cbu;
+  a.T = T; a.H = H; a.W = W; a.S = S; a.F = F; a.seg_start = 0; a.seg_stride = F;
+  a.crop_h = crop_h; a.crop_w = crop_w; a.h_taps = h_taps; a.h_prec = h_prec; a.v_taps = v_taps; a.v_prec = v_prec;
+  a.x0 = x0; a.span = span; a.tile_rows = tile_rows; a.tile_src_rows = tile_src_rows;
+  a.slab_dwords = yuv_slab_dwords(span);
+  fa.frame_map = frame_map; fa.carry = carry;
+  const size_t lds = preproc_yuv_lds_bytes(crop_w, h_taps, span, tile_src_rows);
+  if (lds > PREPROC_LDS_LIMIT) return VAURA_ERR_SHAPE;
+  const dim3 grid((unsigned)((crop_h + tile_rows - 1) / tile_rows), (unsigned)((int64_t)n_clips * S * F));
+  hipStream_t st = as_stream(s);
+  if (layout == VAURA_YUV_NV12) VA_LAUNCH(video_preprocess_yuv_frames_kernel<VAURA_YUV_NV12>, grid, dim3(64 * PREPROC_WAVES), lds, st, fa);
+  else VA_LAUNCH(video_preprocess_yuv_frames_kernel<VAURA_YUV_I420>, grid, dim3(64 * PREPROC_WAVES), lds, st, fa);
+  return 0;
 }
 
 }  // extern "C"

@@ -9,6 +9,9 @@ extractor works segment by segment (16 frames -> 8 tokens), and chunk c >= 1 of 
     blocks = s.push(frames=seg)        # (B, 1, C, 16, H, W): one segment of extractor input (model.frames_from_video of 16 frames)
     blocks = s.close()                 # the last blocks; "final" True on the last one
 
+Frames that arrive one at a time, or at another rate than 25 fps, become such segments in ``model.open_video_stream(...)``
+(``preprocess.VideoFrameStream``): ``for seg in vs.push(frames, pts): blocks += s.push(frames=seg)``.
+
 A session runs the UNBOUNDED chunk schedule (``live_plan``): chunk 0 is a full window without a prompt over the segments 0 .. W - 1,
 chunk c >= 1 starts ``stride_tokens`` frames later, is prompted with the tail of chunk c - 1 and reads the segments c .. c + W - 1 —
 what ``longform.chunk_schedule`` gives for every duration of W + 1 segments or more, whose last chunk is again a full window.

@@ -230,8 +230,8 @@ class VAURAModel(nn.Module):
         return self.visual_bridge(vis_feats.detach())
 
     def frames_from_video(self, video, video_transforms=None, channels_last: bool = False, input_format: str = "rgb",
-                          color_matrix: str = "bt601", color_range: str = "limited", size=None, chroma_row=None,
-                          **segment_kw) -> torch.Tensor:
+                          color_matrix: str = "bt601", color_range: str = "limited", size=None, chroma_row=None, src_fps=None,
+                          pts=None, time_base=None, end=None, dst_fps=25, **segment_kw) -> torch.Tensor:
         """Decoded uint8 video -> what ``generate(frames=...)`` takes: (B, S, 3, 16, 224, 224) fp32 on the sampler's device.
         ``video``: uint8 (B, T, C, H, W), (T, C, H, W) or a list of per-clip tensors (``channels_last``: (.., H, W, C)).
         ``input_format`` "nv12" / "i420": decoder surfaces instead, uint8 (B, T, R, P), (T, R, P) or a list of them, converted with
@@ -239,19 +239,46 @@ class VAURAModel(nn.Module):
         ``chroma_row`` describe a padded surface (VideoPreprocessor.__call__).
         ``video_transforms``: the ``video_transforms_test`` list of configs/generate_*.yaml (Resize -> CenterCrop -> ToFloat32DType ->
         Normalize); None = its values in generate_vgg.yaml:53-65.  ``segment_kw``: segment_size_vframes / n_segments / step_size_seg
-        of GenerateMultipleSegments.  The preprocessor (tap tables, device copies) is built once per distinct configuration."""
-        from .preprocess import VideoPreprocessor
+        of GenerateMultipleSegments.  The preprocessor (tap tables, device copies) is built once per distinct configuration.
+        Video that is not at ``dst_fps`` = 25: ``src_fps`` (an int, a Fraction, (num, den), a float; a list: one per clip) or ``pts``
+        with ``time_base`` (and ``end``), see ``VideoPreprocessor.__call__`` — the frames are selected as ffmpeg's ``fps`` filter
+        selects them, in the same launch."""
+        pre = self._video_preprocessor(video_transforms, channels_last, input_format, color_matrix, color_range, src_fps, dst_fps,
+                                       segment_kw)
+        kw = {} if input_format == "rgb" else dict(size=size, chroma_row=chroma_row)
+        if pts is not None or time_base is not None or end is not None:
+            kw.update(pts=pts, time_base=time_base, end=end)
+        return pre(video, **kw)
+
+    def _video_preprocessor(self, video_transforms, channels_last, input_format, color_matrix, color_range, src_fps, dst_fps, segment_kw):
+        """The cached ``VideoPreprocessor`` of one configuration, on the sampler's device."""
+        from .preprocess import VideoPreprocessor, as_rate
+        rate = None if src_fps is None else ([as_rate(r) for r in src_fps] if isinstance(src_fps, list) else as_rate(src_fps))
         key = (repr(_plain(video_transforms)) if video_transforms is not None else None, bool(channels_last),
                tuple(sorted(segment_kw.items())), input_format, color_matrix, color_range)
+        if rate is not None or as_rate(dst_fps) != 25:
+            key += (repr(rate), as_rate(dst_fps))
         cache = self.__dict__.setdefault("_video_preprocessors", {})
         if key not in cache:
             kw = dict(segment_kw, channels_last=channels_last, input_format=input_format, color_matrix=color_matrix,
-                      color_range=color_range)
+                      color_range=color_range, src_fps=src_fps, dst_fps=dst_fps)
             cache[key] = (VideoPreprocessor(**kw) if video_transforms is None
                           else VideoPreprocessor.from_transforms_config(_plain(video_transforms), **kw))
         pre = cache[key]
         pre.device = self.device
-        return pre(video) if input_format == "rgb" else pre(video, size=size, chroma_row=chroma_row)
+        return pre
+
+    def open_video_stream(self, batch: int, *, src_fps=None, time_base=None, dst_fps=25, video_transforms=None,
+                          channels_last: bool = False, input_format: str = "rgb", color_matrix: str = "bt601",
+                          color_range: str = "limited", size=None, chroma_row=None, **segment_kw):
+        """Decoded frames at their own rate in, 25 fps segments out (``preprocess.VideoFrameStream``): ``vs.push(frames, pts)`` takes
+        any number of frames (a camera's one, a decoder's block) and returns the complete (B, 1, 3, 16, 224, 224) segments, which
+        are what ``LiveSession.push(frames=)`` takes; ``vs.close()`` returns what the end of the video completes.  ``src_fps`` for a
+        constant rate, ``time_base`` for frames pushed with their pts; the other keywords are ``frames_from_video``'s."""
+        if (src_fps is None) == (time_base is None):
+            raise L.VauraHipError("open_video_stream takes src_fps (constant rate) or time_base (frames pushed with pts)")
+        pre = self._video_preprocessor(video_transforms, channels_last, input_format, color_matrix, color_range, None, dst_fps, segment_kw)
+        return pre.open_stream(batch, src_fps=src_fps, time_base=time_base, size=size, chroma_row=chroma_row)
 
     def audio_from_pcm(self, pcm, sample_rate: int, *, lengths=None, audio_transforms=None, duration: Optional[float] = None,
                        interleaved: bool = False):

@@ -24,10 +24,21 @@ yuv420p.  With ``input_format="nv12"`` / ``"i420"`` the input is 8-bit 4:2:0 (1.
 defines (``yuv_coefficients``: 2^14-scaled BT.601 / BT.709 coefficients, limited or full range, chroma replicated over its 2 x 2 luma
 block) and the kernel only applies; ``yuv420_to_rgb_u8`` restates it on the CPU.  The reference does not pin it: its loader gets RGB
 from torchvision / PyAV (swscale); what pins it is a float64 evaluation of the same real coefficients (tests/test_preprocess_yuv_host.py).
+
+Frame rate.  Everything behind this stage counts in 25 fps frames (a 16-frame segment is 0.64 s), and the reference got its videos
+there offline (scripts/reencode_videos.py:71: ``ffmpeg -vf fps=25``).  With ``src_fps=`` or ``pts=`` / ``time_base=`` the frames are
+selected here: ``fps_plan`` / ``FpsClock`` restate ffmpeg's ``fps`` filter at its defaults in exact rationals (frames dropped and
+repeated, nothing blended; parity unpinned by the reference — ffmpeg is not run, tests/preprocess_fps_reference.py walks the filter's
+queue literally), the segments are cut from the selected sequence, and ``vaura_video_preprocess_frames`` /
+``vaura_video_preprocess_yuv420_frames`` read every output frame's source frame from a device table: bit for bit the existing
+launch on ``video[:, table]``.  ``VideoFrameStream`` does the same for frames that arrive a few at a time and hands out complete
+segments, which ``LiveSession.push(frames=)`` takes.
 """
 from __future__ import annotations
 
+import functools
 import math
+from fractions import Fraction
 from typing import Dict, List, Optional, Sequence, Tuple, Union
 
 import numpy as np
@@ -127,6 +138,174 @@ def segment_starts(T: int, F: int, step_size_seg: float = 1.0, n_segments: Optio
         raise L.VauraHipError(f"cannot make {S} segments of {F} frames (stride {stride}) from {T} frames: at most {s_max}")
     seq = int((S * step_size_seg + (1 - step_size_seg)) * F)
     return S, (T - seq) // 2, stride
+
+
+# ---- video at its own frame rate: which source frame every 25 fps tick shows (exact rationals, host only)
+MODEL_FPS = 25
+MAP_KEEP, MAP_CARRY = -1, -2                                          # frame_map values of the table launches (include/vaura_hip.h)
+
+
+def as_rate(x) -> Fraction:
+    """A frame rate or a time base as an exact rational: int, Fraction, ``(num, den)`` or float (through ``Fraction(str(x))``, so
+    29.97 is 2997/100 and not its binary neighbour; NTSC rates are ``(30000, 1001)``)."""
+    if isinstance(x, bool):
+        raise L.VauraHipError(f"a rate is an int, a Fraction, (num, den) or a float; got {x!r}")
+    if isinstance(x, Fraction):
+        r = x
+    elif isinstance(x, (int, np.integer)):
+        r = Fraction(int(x))
+    elif isinstance(x, tuple) and len(x) == 2 and all(isinstance(v, (int, np.integer)) for v in x) and x[1] != 0:
+        r = Fraction(int(x[0]), int(x[1]))
+    elif isinstance(x, float) and math.isfinite(x):
+        r = Fraction(str(x))
+    else:
+        raise L.VauraHipError(f"a rate is an int, a Fraction, (num, den) or a float; got {x!r}")
+    if r <= 0:
+        raise L.VauraHipError(f"a rate must be positive; got {x!r}")
+    return r
+
+
+def _rnd(x: Fraction) -> int:
+    """Nearest integer, halves away from zero."""
+    n, d = x.numerator, x.denominator
+    q = (2 * abs(n) + d) // (2 * d)
+    return q if n >= 0 else -q
+
+
+def _pts_list(pts) -> List[int]:
+    vals = pts.tolist() if hasattr(pts, "tolist") else list(pts)
+    if any(isinstance(p, bool) or not isinstance(p, (int, np.integer)) for p in vals):
+        raise L.VauraHipError("pts are integers in units of time_base")
+    return [int(p) for p in vals]
+
+
+class FpsPlan:
+    """``table`` (n_out,) int32: the source frame tick ``first_tick + m`` shows; ``n_out``; ``first_tick`` (r_0)."""
+
+    def __init__(self, table: np.ndarray, first_tick: int):
+        self.table, self.n_out, self.first_tick = table, int(len(table)), int(first_tick)
+
+
+class FpsClock:
+    """ffmpeg's ``fps`` filter at its defaults (``round=near``, ``eof_action=round``) as a rule on integers, applied frame by frame.
+    Parity unpinned by the reference: it is restated from the filter's algorithm, ffmpeg itself is not run.
+
+    Source frame i has time t_i (``i / src_fps``, or ``pts_i * time_base``) and reaches the output at tick
+    ``r_i = rnd(t_i * dst_fps)`` (nearest, halves away from zero).  Tick m shows ``max{i : r_i <= m}``: a frame whose successor has
+    also reached the tick is dropped, a frame whose successor lies beyond it is shown again.  A tick is decided once a frame with
+    ``r_i > m`` has arrived; the end of the video (``close``) decides the ticks up to ``r_end = rnd(t_end * dst_fps)``."""
+
+    def __init__(self, src_fps=None, *, time_base=None, dst_fps=MODEL_FPS):
+        if (src_fps is None) == (time_base is None):
+            raise L.VauraHipError("FpsClock takes src_fps (constant rate) or time_base (timestamped frames), not both and not neither")
+        self.src_fps = None if src_fps is None else as_rate(src_fps)
+        self.time_base = None if time_base is None else as_rate(time_base)
+        self.dst_fps = as_rate(dst_fps)
+        self.n = 0                                                      # frames received
+        self.first_tick: Optional[int] = None                           # r_0
+        self.next_tick: Optional[int] = None                            # the first tick not decided yet (r of the last frame)
+        self._t: List[Fraction] = []                                     # the times of the last two frames
+        self.closed = False
+
+    def _times(self, frames) -> List[Fraction]:
+        if self.src_fps is not None:
+            if isinstance(frames, bool) or not isinstance(frames, (int, np.integer)) or frames < 0:
+                raise L.VauraHipError(f"a constant-rate clock is pushed a number of frames; got {frames!r}")
+            return [Fraction(self.n + i) / self.src_fps for i in range(int(frames))]
+        if isinstance(frames, (int, np.integer)):
+            raise L.VauraHipError("a timestamped clock is pushed the pts of its frames, not a count")
+        ts = [p * self.time_base for p in _pts_list(frames)]
+        prev = self._t[-1] if self._t else None
+        for t in ts:
+            if prev is not None and t <= prev:
+                raise L.VauraHipError("pts must be strictly increasing")
+            prev = t
+        return ts
+
+    def push(self, frames) -> List[Tuple[int, int]]:
+        """``frames``: a count (constant rate) or the pts of the new frames -> [(tick, source frame), ...] that became decided."""
+        if self.closed:
+            raise L.VauraHipError("FpsClock.push after close")
+        out = []
+        for t in self._times(frames):
+            r = _rnd(t * self.dst_fps)
+            if self.n == 0:
+                self.first_tick = self.next_tick = r
+            else:
+                out += [(m, self.n - 1) for m in range(self.next_tick, r)]
+                self.next_tick = r
+            self._t = (self._t + [t])[-2:]
+            self.n += 1
+        return out
+
+    def close(self, end=None) -> List[Tuple[int, int]]:
+        """The ticks the end of the video decides.  Constant rate: t_end = n / src_fps.  With pts: ``end`` (in time_base units, behind
+        the last frame) or, without it, the last frame lasts as long as the one before it (a single frame: one output tick)."""
+        if self.closed:
+            raise L.VauraHipError("FpsClock.close called twice")
+        if self.n == 0:
+            self.closed = True
+            return []
+        if self.src_fps is not None:
+            if end is not None:
+                raise L.VauraHipError("end is a pts; a constant-rate video ends at n / src_fps")
+            t_end = Fraction(self.n) / self.src_fps
+        elif end is not None:
+            t_end = _pts_list([end])[0] * self.time_base
+            if t_end <= self._t[-1]:
+                raise L.VauraHipError("end must lie behind the pts of the last frame")
+        else:
+            t_end = 2 * self._t[-1] - self._t[-2] if self.n >= 2 else self._t[-1] + 1 / self.dst_fps
+        r_end = _rnd(t_end * self.dst_fps)
+        out = [(m, self.n - 1) for m in range(self.next_tick, r_end)]
+        self.next_tick = max(self.next_tick, r_end)
+        self.closed = True
+        return out
+
+
+def fps_plan(n_frames: Optional[int] = None, src_fps=None, *, pts=None, time_base=None, end=None, dst_fps=MODEL_FPS) -> FpsPlan:
+    """The whole selection at once, in closed form (``FpsClock`` is the same rule frame by frame): exactly one of
+    ``(n_frames, src_fps)`` and ``(pts, time_base)``.  N_out = max(r_end - r_0, 0)."""
+    const, stamped = n_frames is not None or src_fps is not None, pts is not None or time_base is not None
+    if const == stamped or (const and (n_frames is None or src_fps is None)) or (stamped and (pts is None or time_base is None)):
+        raise L.VauraHipError("fps_plan takes (n_frames, src_fps) or (pts, time_base), not both and not neither")
+    dst = as_rate(dst_fps)
+    if const:
+        if end is not None:
+            raise L.VauraHipError("end is a pts; a constant-rate video ends at n / src_fps")
+        if isinstance(n_frames, bool) or not isinstance(n_frames, (int, np.integer)) or n_frames < 0:
+            raise L.VauraHipError(f"n_frames must be a non-negative int; got {n_frames!r}")
+        return _constant_plan(int(n_frames), as_rate(src_fps), dst)
+    tb = as_rate(time_base)
+    ts = [p * tb for p in _pts_list(pts)]
+    if any(b <= a for a, b in zip(ts, ts[1:])):
+        raise L.VauraHipError("pts must be strictly increasing")
+    if not ts:
+        return FpsPlan(np.zeros(0, np.int32), 0)
+    if end is not None:
+        t_end = _pts_list([end])[0] * tb
+        if t_end <= ts[-1]:
+            raise L.VauraHipError("end must lie behind the pts of the last frame")
+    else:
+        t_end = 2 * ts[-1] - ts[-2] if len(ts) >= 2 else ts[0] + 1 / dst
+    return _plan_of_times(ts, t_end, dst)
+
+
+def _plan_of_times(ts: List[Fraction], t_end: Fraction, dst: Fraction) -> FpsPlan:
+    r = np.array([_rnd(t * dst) for t in ts], dtype=np.int64)
+    r_end = _rnd(t_end * dst)
+    ticks = np.arange(int(r[0]), max(r_end, int(r[0])), dtype=np.int64)
+    table = (np.searchsorted(r, ticks, side="right") - 1).astype(np.int32)
+    table.setflags(write=False)
+    return FpsPlan(table, int(r[0]))
+
+
+@functools.lru_cache(maxsize=256)
+def _constant_plan(n: int, src: Fraction, dst: Fraction) -> FpsPlan:
+    """Kept per (n, rates): the rationals of a few hundred frames cost more host time than the launch they plan."""
+    if n == 0:
+        return FpsPlan(np.zeros(0, np.int32), 0)
+    return _plan_of_times([Fraction(i) / src for i in range(n)], Fraction(n) / src, dst)
 
 
 INPUT_FORMATS = ("rgb", "nv12", "i420")
@@ -290,7 +469,13 @@ class VideoPreprocessor:
     def __init__(self, resize: int = 256, crop: Sequence[int] = (224, 224), mean: Sequence[float] = (0.5, 0.5, 0.5),
                  std: Sequence[float] = (0.5, 0.5, 0.5), segment_size_vframes: int = 16, n_segments: Optional[int] = None,
                  step_size_seg: float = 1.0, channels_last: bool = False, device: Union[str, torch.device, None] = None,
-                 input_format: str = "rgb", color_matrix: str = "bt601", color_range: str = "limited"):
+                 input_format: str = "rgb", color_matrix: str = "bt601", color_range: str = "limited", src_fps=None,
+                 dst_fps=MODEL_FPS):
+        """``src_fps``: the frame rate of the input (``as_rate``; a list: one rate per clip of a call), None = it is ``dst_fps``
+        already.  Any other rate is converted to ``dst_fps`` by dropping and repeating frames (``fps_plan``) in the same launch;
+        timestamped input passes ``pts`` / ``time_base`` to the call instead."""
+        self.dst_fps = as_rate(dst_fps)
+        self.src_fps = self._rates(src_fps)
         if input_format not in INPUT_FORMATS:
             raise L.VauraHipError(f"input_format {input_format!r} is not built; one of {list(INPUT_FORMATS)}")
         self.input_format, self.color_matrix, self.color_range = input_format, color_matrix, color_range
@@ -314,6 +499,7 @@ class VideoPreprocessor:
         self.device = None if device is None else torch.device(device)
         self._geo: Dict[Tuple[int, int], _Geometry] = {}
         self._lut_dev: Dict[str, torch.Tensor] = {}
+        self._map_dev: Dict[tuple, torch.Tensor] = {}
         # lut[c, level] = ((level / 255) - mean[c]) / std[c], in fp32, in that order
         lv = torch.arange(256, dtype=torch.float32) / 255
         self.lut = torch.stack([(lv - torch.tensor(m, dtype=torch.float32)) / torch.tensor(s, dtype=torch.float32)
@@ -399,12 +585,73 @@ class VideoPreprocessor:
             raise L.VauraHipError(f"video has {C} channels ({'last' if self.channels_last else 'first'} layout expected); 3 are needed")
         return b, T, C, H, W
 
+    # ---- the frame rate
+    @staticmethod
+    def _rates(src_fps):
+        """None, one rate, or a list of per-clip rates (a tuple is ``(num, den)``)."""
+        if src_fps is None:
+            return None
+        return [as_rate(r) for r in src_fps] if isinstance(src_fps, list) else as_rate(src_fps)
+
+    def _plans(self, clips: List[torch.Tensor], src_fps, pts, time_base, end) -> Optional[List[FpsPlan]]:
+        """One ``fps_plan`` per clip of the call (the rows of ``clips`` in order), or None where the frames are at ``dst_fps``
+        already and the launch is the one without a table."""
+        rows = [int(v.shape[1]) for v in clips for _ in range(v.shape[0])]
+        rates = self.src_fps if src_fps is None else self._rates(src_fps)
+        if pts is None:
+            if time_base is not None or end is not None:
+                raise L.VauraHipError("time_base / end describe pts; pass pts")
+            if isinstance(rates, list):
+                if len(rates) != len(rows):
+                    raise L.VauraHipError(f"{len(rates)} rates for {len(rows)} clips")
+            else:
+                rates = [rates] * len(rows)
+            if all(r is None or r == self.dst_fps for r in rates):
+                return None
+            return [fps_plan(T, self.dst_fps if r is None else r, dst_fps=self.dst_fps) for T, r in zip(rows, rates)]
+        if rates is not None:
+            raise L.VauraHipError("pts and src_fps both describe the frames' times; pass one of them")
+        if time_base is None:
+            raise L.VauraHipError("pts are in units of time_base; pass time_base")
+        per_clip = len(pts) > 0 and not isinstance(pts[0], (int, np.integer)) and not (torch.is_tensor(pts[0]) and pts[0].dim() == 0)
+        pts = list(pts) if per_clip else [pts] * len(rows)
+        ends = list(end) if isinstance(end, (list, tuple)) else [end] * len(rows)
+        if len(pts) != len(rows) or len(ends) != len(rows):
+            raise L.VauraHipError(f"{len(pts)} pts lists and {len(ends)} ends for {len(rows)} clips")
+        for T, p in zip(rows, pts):
+            if len(p) != T:
+                raise L.VauraHipError(f"{len(p)} pts for a clip of {T} frames")
+        return [fps_plan(pts=p, time_base=time_base, end=e, dst_fps=self.dst_fps) for p, e in zip(pts, ends)]
+
+    def _frame_maps(self, plans: List[FpsPlan]) -> Tuple[int, List[np.ndarray]]:
+        """(S, per clip the (S * F,) source frames of its output frames): the segments are cut from the CONVERTED sequence of
+        ``n_out`` frames, output (s, f) takes ``table[first + s * stride + f]``."""
+        F = self.segment_size_vframes
+        maps, Ss, done = [], [], {}
+        for p in plans:
+            if id(p) not in done:                                           # the clips of a batch mostly share one plan
+                S, first, stride = segment_starts(p.n_out, F, self.step_size_seg, self.n_segments)
+                idx = first + stride * np.arange(S)[:, None] + np.arange(F)[None, :]
+                done[id(p)] = (S, p.table[idx.reshape(-1)].astype(np.int32))
+            Ss.append(done[id(p)][0])
+            maps.append(done[id(p)][1])
+        if len(set(Ss)) != 1:
+            raise L.VauraHipError(f"clips of one call must give the same number of segments; at {float(self.dst_fps):g} fps they give {Ss}")
+        return Ss[0], maps
+
     # ---- CPU restatement
-    def reference_u8(self, video, size: Optional[Tuple[int, int]] = None, chroma_row: Optional[int] = None) -> torch.Tensor:
+    def reference_u8(self, video, size: Optional[Tuple[int, int]] = None, chroma_row: Optional[int] = None, src_fps=None, pts=None,
+                     time_base=None, end=None) -> torch.Tensor:
         """The kernel's integer arithmetic on the CPU with the same tap tables: uint8 levels (B, S, C, F, h, w) before the scaling.
-        A 4:2:0 input goes through ``yuv420_to_rgb_u8`` first (``size`` / ``chroma_row`` as in ``__call__``)."""
+        A 4:2:0 input goes through ``yuv420_to_rgb_u8`` first (``size`` / ``chroma_row`` as in ``__call__``).  With a frame rate
+        (``src_fps`` / ``pts``, as in ``__call__``) every clip is ``video[table]`` first."""
         outs = []
-        for v in self._clips(video):
+        clips = self._clips(video)
+        plans = self._plans(clips, src_fps, pts, time_base, end)
+        if plans is not None:
+            rows = [v[i:i + 1] for v in clips for i in range(v.shape[0])]
+            clips = [r.cpu().index_select(1, torch.from_numpy(p.table.astype(np.int64))) for r, p in zip(rows, plans)]
+        for v in clips:
             if self.input_format != "rgb":
                 v = yuv420_to_rgb_u8(*yuv420_planes(v.cpu(), self.input_format, size, chroma_row), self.color_matrix, self.color_range)
             b, T, C, H, W = self._dims(v)
@@ -438,9 +685,51 @@ class VideoPreprocessor:
         return outs[0] if len(outs) == 1 else torch.cat(outs, dim=0)
 
     # ---- device path
-    def _launch(self, v: torch.Tensor, out: torch.Tensor, dev: torch.device) -> None:
+    def _check_map(self, fmap: np.ndarray, b: int, T: int, S: int, carry) -> bool:
+        """Every refusal about a (b, S * F) frame map, on the host; -> whether it names the carried frame."""
+        if fmap.dtype != np.int32 or fmap.shape != (b, S * self.segment_size_vframes):
+            raise L.VauraHipError(f"a frame map is int32 (clips, S * F) = {(b, S * self.segment_size_vframes)}; got {fmap.dtype} {fmap.shape}")
+        if fmap.size and (int(fmap.min()) < MAP_CARRY or int(fmap.max()) >= T):
+            raise L.VauraHipError(f"a frame map names source frames 0 .. {T - 1}, -1 (keep) or -2 (the carried frame); got "
+                                  f"{int(fmap.min())} .. {int(fmap.max())}")
+        uses = bool((fmap == MAP_CARRY).any())
+        if uses and carry is None:
+            raise L.VauraHipError("the frame map names the carried frame (-2) and there is none")
+        return uses
+
+    def _device_map(self, fmap: np.ndarray, dev: torch.device) -> torch.Tensor:
+        """The map on the device.  Kept per content: a constant rate gives the same few maps call after call and push after push,
+        and the upload (a synchronous copy of a few hundred bytes) costs as much host time as the launch."""
+        key = (str(dev), fmap.shape, fmap.tobytes())
+        if key not in self._map_dev:
+            if len(self._map_dev) >= 256:
+                self._map_dev.clear()
+            self._map_dev[key] = torch.from_numpy(np.ascontiguousarray(fmap)).to(dev)
+        return self._map_dev[key]
+
+    def _launch(self, v: torch.Tensor, out: torch.Tensor, dev: torch.device, fmap: Optional[np.ndarray] = None,
+                carry: Optional[torch.Tensor] = None) -> None:
         b, T, C, H, W = self._dims(v)
         g = self.geometry(H, W)
+        if fmap is not None:                                               # the table launch: the map has the segments applied
+            S = out.shape[1]
+            uses = self._check_map(fmap, b, T, S, carry)
+            if tuple(out.shape) != (b, S, 3, self.segment_size_vframes, *self.crop) or not out.is_contiguous():
+                raise L.VauraHipError(f"the output of {b} clips is (b, S, 3, F, h, w) and contiguous; got {tuple(out.shape)}")
+            if carry is not None and (tuple(carry.shape) != (b, *v.shape[2:]) or not carry.is_contiguous() or carry.dtype != torch.uint8):
+                raise L.VauraHipError(f"the carried frames are uint8 {(b, *v.shape[2:])}; got {carry.dtype} {tuple(carry.shape)}")
+            tile_rows, tile_src = g.tiles(self.channels_last)
+            h_rel, h_w, v_start, v_w = g.device_tables(dev)
+            key = str(dev)
+            if key not in self._lut_dev:
+                self._lut_dev[key] = self.lut.to(dev)
+            dmap = self._device_map(fmap, dev)
+            L.check(L.lib().vaura_video_preprocess_frames(
+                L.ptr(v), int(self.channels_last), b, T, C, H, W, self.resize, self.crop[0], self.crop[1], self.segment_size_vframes, S,
+                L.ptr(h_rel), L.ptr(h_w), g.h["taps"], g.h["prec"], L.ptr(v_start), L.ptr(v_w), g.v["taps"], g.v["prec"], g.x0, g.span,
+                tile_rows, tile_src, L.ptr(self._lut_dev[key]), L.ptr(out), L.ptr(dmap), L.ptr(carry), int(uses),
+                L.current_stream(dev)), "vaura_video_preprocess_frames")
+            return
         S, first, stride = segment_starts(T, self.segment_size_vframes, self.step_size_seg, self.n_segments)
         if tuple(out.shape) != (b, S, 3, self.segment_size_vframes, *self.crop):
             raise L.VauraHipError(f"clips of one call must give the same number of segments; this group gives {S}, the first {out.shape[1]}")
@@ -454,15 +743,35 @@ class VideoPreprocessor:
             first, stride, L.ptr(h_rel), L.ptr(h_w), g.h["taps"], g.h["prec"], L.ptr(v_start), L.ptr(v_w), g.v["taps"], g.v["prec"],
             g.x0, g.span, tile_rows, tile_src, L.ptr(self._lut_dev[key]), L.ptr(out), L.current_stream(dev)), "vaura_video_preprocess")
 
-    def _launch_yuv(self, v: torch.Tensor, out: torch.Tensor, dev: torch.device, size, chroma_row) -> None:
+    def _launch_yuv(self, v: torch.Tensor, out: torch.Tensor, dev: torch.device, size, chroma_row, fmap: Optional[np.ndarray] = None,
+                    carry: Optional[torch.Tensor] = None) -> None:
         b, T = v.shape[:2]
         H, W, R, P, crow = yuv_surface(v, self.input_format, size, chroma_row)
         # frame n = clip * T + t sits at byte n * frame_stride: true of a contiguous batch and of the usual views of one
         fs = v.stride(1) if T > 1 else (v.stride(0) if b > 1 else R * P)
-        if fs < R * P or (b > 1 and T > 1 and v.stride(0) != T * fs):
+        if fs < R * P or (b > 1 and T > 1 and v.stride(0) != T * fs) or (carry is not None and fs != R * P):
             v = v.contiguous()
             fs = R * P
         g = self.geometry(H, W)
+        if fmap is not None:                                               # the table launch: the map has the segments applied
+            S = out.shape[1]
+            uses = self._check_map(fmap, b, T, S, carry)
+            if tuple(out.shape) != (b, S, 3, self.segment_size_vframes, *self.crop) or not out.is_contiguous():
+                raise L.VauraHipError(f"the output of {b} clips is (b, S, 3, F, h, w) and contiguous; got {tuple(out.shape)}")
+            if carry is not None and (tuple(carry.shape) != (b, R, P) or not carry.is_contiguous() or carry.dtype != torch.uint8):
+                raise L.VauraHipError(f"the carried surfaces are uint8 {(b, R, P)}; got {carry.dtype} {tuple(carry.shape)}")
+            tile_rows, tile_src = g.tiles(False, self.input_format)
+            h_rel, h_w, v_start, v_w = g.device_tables(dev)
+            key = str(dev)
+            if key not in self._lut_dev:
+                self._lut_dev[key] = self.lut.to(dev)
+            dmap = self._device_map(fmap, dev)
+            L.check(L.lib().vaura_video_preprocess_yuv420_frames(
+                L.ptr(v), (b * T - 1) * fs + R * P, _YUV_LAYOUT[self.input_format], P, crow * P, fs, b, T, H, W, *self.yuv, self.resize,
+                self.crop[0], self.crop[1], self.segment_size_vframes, S, L.ptr(h_rel), L.ptr(h_w), g.h["taps"], g.h["prec"],
+                L.ptr(v_start), L.ptr(v_w), g.v["taps"], g.v["prec"], g.x0, g.span, tile_rows, tile_src, L.ptr(self._lut_dev[key]),
+                L.ptr(out), L.ptr(dmap), L.ptr(carry), int(uses), L.current_stream(dev)), "vaura_video_preprocess_yuv420_frames")
+            return
         S, first, stride = segment_starts(T, self.segment_size_vframes, self.step_size_seg, self.n_segments)
         if tuple(out.shape) != (b, S, 3, self.segment_size_vframes, *self.crop):
             raise L.VauraHipError(f"clips of one call must give the same number of segments; this group gives {S}, the first {out.shape[1]}")
@@ -478,18 +787,27 @@ class VideoPreprocessor:
             L.ptr(out), L.current_stream(dev)), "vaura_video_preprocess_yuv420")
 
     @torch.no_grad()
-    def __call__(self, video, size: Optional[Tuple[int, int]] = None, chroma_row: Optional[int] = None) -> torch.Tensor:
+    def __call__(self, video, size: Optional[Tuple[int, int]] = None, chroma_row: Optional[int] = None, *, src_fps=None, pts=None,
+                 time_base=None, end=None) -> torch.Tensor:
         """uint8 (B, T, C, H, W), (T, C, H, W) or a list of per-clip (T, C, H, W) tensors whose H, W may differ (channels last:
         (.., H, W, C)) -> fp32 (B, S, C, F, crop_h, crop_w) on the device.  Host tensors are copied once, as uint8.
 
         ``input_format`` "nv12" / "i420": uint8 (B, T, R, P), (T, R, P) or a list of per-clip (T, R, P) surfaces.  Tight frames have
         R = 3H/2 rows of P = W bytes (H rows of luma, then the chroma plane).  A padded decoder surface passes ``size=(H, W)``: P >= W
         is the pitch, luma sits in rows [0, H), the chroma plane starts at row ``chroma_row`` (default H) and R >= chroma_row + H/2;
-        bytes outside the planes never reach the result.  Host surfaces are copied once, as they are (1.5 bytes per pixel)."""
+        bytes outside the planes never reach the result.  Host surfaces are copied once, as they are (1.5 bytes per pixel).
+
+        Video that is not at ``dst_fps``: the preprocessor's ``src_fps`` (or ``src_fps=`` here; a list: one rate per clip), or
+        ``pts`` (integers in units of ``time_base``, strictly increasing; one list for all clips or one per clip) with an optional
+        ``end``.  The frames are selected by ``fps_plan`` and the segments are cut from the selected sequence, in the same single
+        launch per geometry (``vaura_video_preprocess_frames``); of a host input only the selected frames are copied."""
         yuv = self.input_format != "rgb"
         if not yuv and (size is not None or chroma_row is not None):
             raise L.VauraHipError("size / chroma_row describe a 4:2:0 surface; input_format is 'rgb'")
         clips = self._clips(video)
+        plans = self._plans(clips, src_fps, pts, time_base, end)
+        if plans is not None:
+            return self._call_fps(clips, plans, size, chroma_row)
         # one launch per run of consecutive clips of one geometry (the output keeps the clips' order)
         groups: List[List[torch.Tensor]] = []
         for v in clips:
@@ -506,13 +824,7 @@ class VideoPreprocessor:
                 _, T, _, H, W = self._dims(grp[0])
             self.geometry(H, W)
             segment_starts(T, self.segment_size_vframes, self.step_size_seg, self.n_segments)
-        dev = self.device
-        if dev is None:
-            dev = next((v.device for v in clips if v.device.type == "cuda"), None)
-            if dev is None:
-                if not torch.cuda.is_available():
-                    raise L.VauraHipError("VideoPreprocessor runs on a HIP device only (reference_u8 is the CPU restatement)")
-                dev = torch.device("cuda", torch.cuda.current_device())
+        dev = self._device_for(clips)
         S = segment_starts(clips[0].shape[1], self.segment_size_vframes, self.step_size_seg, self.n_segments)[0]
         B = sum(v.shape[0] for v in clips)
         with torch.cuda.device(dev):
@@ -527,4 +839,201 @@ class VideoPreprocessor:
                     v = (grp[0] if len(grp) == 1 else torch.cat(grp, dim=0)).contiguous()
                     self._launch(v, out[b0:b0 + v.shape[0]], dev)              # same stream as the copy: v may be freed after it
                 b0 += v.shape[0]
+        return out
+
+    def _device_for(self, clips: Sequence[torch.Tensor]) -> torch.device:
+        dev = self.device
+        if dev is None:
+            dev = next((v.device for v in clips if v.device.type == "cuda"), None)
+            if dev is None:
+                if not torch.cuda.is_available():
+                    raise L.VauraHipError("VideoPreprocessor runs on a HIP device only (reference_u8 is the CPU restatement)")
+                dev = torch.device("cuda", torch.cuda.current_device())
+        return dev
+
+    @staticmethod
+    def _upload_named(v: torch.Tensor, used: np.ndarray, dev: torch.device) -> torch.Tensor:
+        """The frames ``used`` (sorted) of the host clips ``v`` (b, T, ..) on the device, (b, len(used), ..): one copy per clip and run
+        of consecutive frames, straight from where they lie (a gather on the host first would cost more than the link saves)."""
+        dst = torch.empty(v.shape[0], len(used), *v.shape[2:], dtype=v.dtype, device=dev)
+        cuts = np.flatnonzero(np.diff(used) != 1) + 1
+        at = 0
+        for run in np.split(used, cuts):
+            for i in range(v.shape[0]):
+                dst[i, at:at + len(run)].copy_(v[i, int(run[0]):int(run[-1]) + 1], non_blocking=True)
+            at += len(run)
+        return dst
+
+    def _call_fps(self, clips: List[torch.Tensor], plans: List[FpsPlan], size, chroma_row) -> torch.Tensor:
+        """``__call__`` for video at its own frame rate: one table launch per run of consecutive clips of one geometry."""
+        yuv = self.input_format != "rgb"
+        F = self.segment_size_vframes
+        S, maps = self._frame_maps(plans)                                    # refuses clips too short for a segment at dst_fps
+        items, r0 = [], 0                                                     # (frames, (b, S * F) map) per input tensor
+        for v in clips:
+            b = v.shape[0]
+            fmap = np.stack(maps[r0:r0 + b])
+            r0 += b
+            if yuv:
+                H, W = yuv_surface(v, self.input_format, size, chroma_row)[:2]
+            else:
+                H, W = self._dims(v)[3:]
+            self.geometry(H, W)
+            if v.device.type != "cuda":                                      # only the frames the table names cross the link
+                used = np.unique(fmap)
+                fmap = np.searchsorted(used, fmap).astype(np.int32)
+            else:
+                used = None
+            items.append((v, fmap, used))
+        shape_of = lambda it: (it[0].shape[1] if it[2] is None else len(it[2]), *it[0].shape[2:])  # noqa: E731  (frames on the device, ..)
+        groups: List[list] = []
+        for it in items:
+            if groups and shape_of(groups[-1][0]) == shape_of(it):
+                groups[-1].append(it)
+            else:
+                groups.append([it])
+        dev = self._device_for(clips)
+        B = sum(v.shape[0] for v in clips)
+        with torch.cuda.device(dev):
+            out = torch.empty(B, S, 3, F, *self.crop, dtype=torch.float32, device=dev)
+            b0 = 0
+            for grp in groups:
+                vs = [v.to(dev, non_blocking=True) if used is None else self._upload_named(v, used, dev) for v, _, used in grp]
+                fmap = np.concatenate([m for _, m, _ in grp])
+                if yuv:
+                    v = vs[0] if len(vs) == 1 else torch.cat(vs, dim=0)
+                    self._launch_yuv(v, out[b0:b0 + v.shape[0]], dev, size, chroma_row, fmap=fmap)
+                else:
+                    v = (vs[0] if len(vs) == 1 else torch.cat(vs, dim=0)).contiguous()
+                    self._launch(v, out[b0:b0 + v.shape[0]], dev, fmap=fmap)
+                b0 += v.shape[0]
+        return out
+
+    def open_stream(self, batch: int, *, src_fps=None, time_base=None, size=None, chroma_row=None) -> "VideoFrameStream":
+        """A ``VideoFrameStream`` of ``batch`` clips on this preprocessor: ``src_fps`` (default: the preprocessor's) or ``time_base``."""
+        if src_fps is None and time_base is None:
+            src_fps = self.src_fps if self.src_fps is not None else self.dst_fps
+        return VideoFrameStream(self, batch, src_fps=src_fps, time_base=time_base, size=size, chroma_row=chroma_row)
+
+
+class VideoFrameStream:
+    """Decoded frames at their own rate in, complete 25 fps segments out: what ``LiveSession.push(frames=)`` takes.
+
+        vs = pre.open_stream(batch, src_fps=30)            # or time_base=(1, 90000) and pts with every push
+        for seg in vs.push(frames, pts): ...                # frames (B, n, ..) uint8, any n >= 0; seg (B, 1, 3, F, h, w) fp32
+        for seg in vs.close(): ...                          # what the end of the video completes; vs.dropped_ticks = the cut tail
+
+    The selection is ``FpsClock`` (all clips of a stream share their frame times); segment s holds the ticks
+    ``[r_0 + s F, r_0 + (s + 1) F)``, so the segments are those of the one-pass call on the whole video with ``step_size_seg == 1``
+    (anything else is refused).  Device state: the pending segment and, per clip, the last frame received — it may still be shown
+    at later ticks.  A push launches once per segment it touches, into the pending segment itself: map value -1 keeps the ticks
+    filled earlier, -2 names the carried frame, so old and new frames are never concatenated."""
+
+    def __init__(self, pre: VideoPreprocessor, batch: int, *, src_fps=None, time_base=None, size=None, chroma_row=None):
+        if pre.step_size_seg != 1.0 or pre.n_segments is not None:
+            raise L.VauraHipError("a frame stream makes back-to-back segments: step_size_seg == 1.0 and n_segments None; got "
+                                  f"{pre.step_size_seg} and {pre.n_segments}")
+        if isinstance(src_fps, list):
+            raise L.VauraHipError("the clips of a stream share one clock: one src_fps, not a list")
+        if batch < 1:
+            raise L.VauraHipError(f"a stream of {batch} clips")
+        if pre.input_format == "rgb" and (size is not None or chroma_row is not None):
+            raise L.VauraHipError("size / chroma_row describe a 4:2:0 surface; input_format is 'rgb'")
+        self.pre, self.batch, self.size, self.chroma_row = pre, int(batch), size, chroma_row
+        self.clock = FpsClock(src_fps, time_base=time_base, dst_fps=pre.dst_fps)
+        self.segments, self.dropped_ticks, self.closed = 0, 0, False
+        self._filled = 0                                                 # ticks of the pending segment that are written
+        self._frame_shape: Optional[Tuple[int, ...]] = None
+        self._pending: Optional[torch.Tensor] = None
+        self._carry: Optional[torch.Tensor] = None
+        self._dev: Optional[torch.device] = None
+
+    def _check(self, frames, pts) -> torch.Tensor:
+        pre = self.pre
+        nd = 2 if pre.input_format != "rgb" else 3                        # dims of one frame
+        if not torch.is_tensor(frames) or frames.dtype != torch.uint8:
+            raise L.VauraHipError("a frame stream takes decoded uint8 frames")
+        if frames.dim() == nd + 1 and self.batch == 1:
+            frames = frames[None]
+        if frames.dim() != nd + 2 or frames.shape[0] != self.batch:
+            raise L.VauraHipError(f"a push is (B = {self.batch}, n, ..) frames in the preprocessor's input layout; got {tuple(frames.shape)}")
+        if self._frame_shape is not None and tuple(frames.shape[2:]) != self._frame_shape:
+            raise L.VauraHipError(f"a stream has one geometry: frames of {self._frame_shape}, then {tuple(frames.shape[2:])}")
+        if self.clock.src_fps is not None:
+            if pts is not None:
+                raise L.VauraHipError("a constant-rate stream takes no pts (open it with time_base= for timestamped frames)")
+        elif pts is None or len(pts) != frames.shape[1]:
+            raise L.VauraHipError(f"a timestamped stream takes one pts per frame; {frames.shape[1]} frames, "
+                                  f"{'no' if pts is None else len(pts)} pts")
+        return frames
+
+    def _emit(self, decided: List[Tuple[int, int]], base: int, v: torch.Tensor) -> List[torch.Tensor]:
+        """Write the decided ticks: source frame ``i`` is ``v[:, i - base]``, or the carried frame for ``i == base - 1``."""
+        pre, F, out = self.pre, self.pre.segment_size_vframes, []
+        at = 0
+        while at < len(decided):
+            n = min(F - self._filled, len(decided) - at)                  # the ticks of this launch: up to the segment's end
+            row = np.full(F, MAP_KEEP, np.int32)
+            for j, (tick, i) in enumerate(decided[at:at + n]):
+                assert (tick - self.clock.first_tick) % F == self._filled + j and i >= base - 1
+                row[self._filled + j] = i - base if i >= base else MAP_CARRY
+            fmap = np.tile(row, (self.batch, 1))
+            if pre.input_format != "rgb":
+                pre._launch_yuv(v, self._pending, self._dev, self.size, self.chroma_row, fmap=fmap, carry=self._carry)
+            else:
+                pre._launch(v, self._pending, self._dev, fmap=fmap, carry=self._carry)
+            self._filled += n
+            at += n
+            if self._filled == F:                                         # complete: handed over, a new buffer takes its place
+                out.append(self._pending)
+                self._pending = torch.empty_like(self._pending)
+                self._filled = 0
+                self.segments += 1
+        return out
+
+    @torch.no_grad()
+    def push(self, frames: torch.Tensor, pts=None) -> List[torch.Tensor]:
+        """``frames``: uint8 (B, n, C, H, W) / (B, n, H, W, C) / (B, n, R, P) surfaces, n >= 0 ((n, ..) with B == 1); ``pts``: their n
+        timestamps on a ``time_base`` stream.  -> the segments (B, 1, 3, F, h, w) fp32 this push completed, oldest first."""
+        if self.closed:
+            raise L.VauraHipError("VideoFrameStream.push after close")
+        frames = self._check(frames, pts)
+        pre = self.pre
+        if self._frame_shape is None:                                     # every refusal about the geometry, before any state
+            if pre.input_format != "rgb":
+                H, W = yuv_surface(frames, pre.input_format, self.size, self.chroma_row)[:2]
+            else:
+                H, W = pre._dims(frames)[3:]
+            pre.geometry(H, W)
+        n = int(frames.shape[1])
+        base = self.clock.n
+        decided = self.clock.push(n if self.clock.src_fps is not None else pts)
+        if n == 0:
+            return []
+        if self._frame_shape is None:
+            self._frame_shape = tuple(frames.shape[2:])
+            self._dev = pre._device_for([frames])
+            with torch.cuda.device(self._dev):
+                self._pending = torch.empty(self.batch, 1, 3, pre.segment_size_vframes, *pre.crop, dtype=torch.float32, device=self._dev)
+                self._carry = torch.empty(self.batch, *self._frame_shape, dtype=torch.uint8, device=self._dev)
+        with torch.cuda.device(self._dev):
+            v = frames.to(self._dev, non_blocking=True).contiguous()
+            out = self._emit(decided, base, v)
+            self._carry.copy_(v[:, -1])                                   # behind the launches that read the frame carried so far
+        return out
+
+    @torch.no_grad()
+    def close(self, end=None) -> List[torch.Tensor]:
+        """The segments the end of the video completes (``end``: its pts on a ``time_base`` stream, see ``FpsClock.close``).  A
+        trailing incomplete segment is dropped; ``dropped_ticks`` says how many ticks it held."""
+        if self.closed:
+            raise L.VauraHipError("VideoFrameStream.close called twice")
+        decided = self.clock.close(end)
+        self.closed = True
+        out = []
+        if self._carry is not None:
+            with torch.cuda.device(self._dev):
+                out = self._emit(decided, self.clock.n, self._carry[:, None])   # every remaining tick shows the last frame
+        self.dropped_ticks = self._filled
+        self._pending = self._carry = None
         return out
