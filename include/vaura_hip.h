@@ -1152,6 +1152,47 @@ int vaura_spectrogram(const float* x, int B, int64_t in_stride, const int64_t* r
 /* dynamic LDS bytes of one workgroup of that launch: the two images of the transform (0 for sizes the kernel does not take) */
 size_t vaura_spectrogram_lds_bytes(int n_fft, int F);
 
+/* -------------------------------------------------------------------------------------------
+ * Streaming loudness (csrc/loudness.hip): an ITU-R BS.1770 meter and a causal loudness normaliser over the codec's mono fp32 rows, one
+ * pass or block by block, the blocks concatenated being the one-pass result bit for bit.  step = nearbyint(0.1 rate), gate = 4 step.
+ * The K-weighting runs in fp64 (coefficients of vaura_audio_loudness's launcher, kept in double), parallel over 256 lane chunks per
+ * step that are anchored at absolute sample indices; step energies S_j are fp32 in a ring of max(history_steps, 32) entries; the
+ * momentary (4 steps), short-term (30 steps) and integrated (two gates, the blocks of the last history_steps steps) loudness use
+ * post.hip's fp32 expressions.  At boundary m (m whole steps received) d_m = clamp(target_lkfs - I_m, +-max_gain_db), held where I_m
+ * is undefined, slew-limited by slew_db_per_step where that is > 0; a_m = powf(10, d_m / 20); sample i of step m, offset k, leaves
+ * as limiter(x (a_{m-1} + (a_m - a_{m-1}) (k + 1) / step)): every pushed sample leaves in the same push.
+ *   x         device fp32 (B, in_stride): the next samples of every clip;  records  device int64 (B, VAURA_LOUDNESS_RECORD): r0 =
+ *             samples the clip has brought before, n = samples it brings now (0 .. in_stride; nothing behind n is read).  The host
+ *             keeps r0 (vaura_amd/loudness.py push_records); a clip's first push (r0 == 0) reads no state.
+ *   out       device fp32 (B, in_stride), not x: the n normalised samples of every row, zeros behind them; NULL: the meter alone
+ *   state     device, vaura_audio_loudness_state_elems(B, rate, history_steps) fp32 words, 8-byte aligned: per clip the filter
+ *             state (8 doubles), d, a_{m-1}, a_m, I, the ring and the raw tail shorter than one step.  Owned by the stream.
+ *   table     device fp64, vaura_audio_loudness_table_elems(rate) values (vaura_amd/loudness.py: table())
+ *   gains     device fp32 (B, meter_stride + 2), written: a_{M0-1}, a_{M0}, .. a_{M1} with M0 = r0 / step, M1 = (r0 + n) / step
+ *   meter     device fp32 (3, B, meter_stride), written: plane 0 I_m at the boundaries m = M0 + 1 .. M1; plane 1 the momentary
+ *             loudness of the blocks those boundaries complete (block m - 4), left-aligned; plane 2 the short-term values (window
+ *             m - 30) likewise; NaN where undefined and behind them.  meter_stride >= the largest M1 - M0 of the push, >= 1.
+ *   info      device fp32 (B, 2), written: d and I at the clip's last boundary;  clipped  device int32 (B), ADDED to: |x g| > 1
+ * One launch where in_stride <= 16384, two otherwise.  VAURA_ERR_ARG: a NULL or misaligned pointer, out == x, B < 1, in_stride < 1,
+ * meter_stride < 1, a table of another size, a non-finite target / initial gain, max_gain_db negative or not finite, a negative or
+ * NaN slew.  VAURA_ERR_DTYPE: an unknown limiter.  VAURA_ERR_SHAPE: a rate outside 8 .. 48 kHz or one whose gating block is not
+ * four whole steps (11 025 Hz), history_steps outside 8 .. 4096, a row of more than 2^31 - 1 samples, more than 65535 clips.  All
+ * before any launch.                                                                                                            */
+#define VAURA_LOUDNESS_RECORD 2
+#define VAURA_LOUDNESS_MIN_HISTORY 8
+#define VAURA_LOUDNESS_MAX_HISTORY 4096
+enum { VAURA_LOUDNESS_CLIP = 0, VAURA_LOUDNESS_TANH = 1 };
+int vaura_audio_loudness_push(const float* x, float* out, int B, int64_t in_stride, const int64_t* records, float* state,
+                              int sample_rate, int history_steps, const double* table, int64_t table_elems, float target_lkfs,
+                              float max_gain_db, float slew_db_per_step, float initial_gain_db, int limiter, float* gains, float* meter,
+                              int meter_stride, float* info, int32_t* clipped, vaura_stream_t s);
+/* fp32 words of the state of n_clips clips (0 for a rate or a history the launcher refuses) */
+size_t vaura_audio_loudness_state_elems(int n_clips, int sample_rate, int history_steps);
+/* fp64 values of the chunk table of a rate (0 for a refused rate) */
+size_t vaura_audio_loudness_table_elems(int sample_rate);
+/* LDS bytes of one workgroup of the push kernel, dynamic and static (0 for a refused rate) */
+size_t vaura_audio_loudness_lds_bytes(int sample_rate);
+
 /* Measurement aid (tools/pmc_driver, A/B timing): selects kernel variants for launches enqueued (or graphs captured) afterwards.
  * vaura_amd/csrc/variants.h is the table of every bit of both words, by name (e.g. bit 0, ROWSPLIT_OFF: wo / w2 GEMVs as one workgroup
  * per column tile instead of the row-split pair); an entry never changes its value.  0 = the product configuration.   */

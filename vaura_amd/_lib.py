@@ -196,6 +196,12 @@ SIGNATURES = {
                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_void_p,
                                     C.c_int64, C.c_void_p]),
     "vaura_spectrogram_lds_bytes": (C.c_size_t, [C.c_int, C.c_int]),
+    "vaura_audio_loudness_push": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
+                                            C.c_void_p, C.c_int64, C.c_float, C.c_float, C.c_float, C.c_float, C.c_int, C.c_void_p,
+                                            C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "vaura_audio_loudness_state_elems": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
+    "vaura_audio_loudness_table_elems": (C.c_size_t, [C.c_int]),
+    "vaura_audio_loudness_lds_bytes": (C.c_size_t, [C.c_int]),
     "vaura_version": (C.c_char_p, []),
     "vaura_set_debug_flags": (None, [C.c_uint]),
     "vaura_set_debug_flags2": (None, [C.c_uint]),

@@ -801,6 +801,13 @@ class VAURAModel(nn.Module):
         from . import post
         return post.audio_to_spectrogram(audio, post.SpectrogramFormat() if fmt is None else fmt, lengths=lengths)
 
+    @staticmethod
+    def loudness_stream(blocks, target=None):
+        """``post.stream_loudness``: the blocks of ``generate_stream`` / ``generate_long_stream`` / a live session with their audio
+        normalised causally towards ``target`` (None: -12 LKFS at 44.1 kHz, ``post.LoudnessTarget()``); ``post.stream_pcm`` composes on top."""
+        from . import post
+        return post.stream_loudness(blocks, post.LoudnessTarget() if target is None else target)
+
     # ------------------------------------------------------------------ one step, reference signature
     @torch.no_grad()
     def _sample_next_token(self, sequence: torch.Tensor, condition: torch.Tensor, use_sampling: bool = False,

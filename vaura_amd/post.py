@@ -15,6 +15,12 @@ result bit for bit (the filter history travels in a carry row on the device).
 The picture of the audio — ``SpectrogramFormat`` / ``audio_to_spectrogram`` / ``SpectrogramStream`` / ``stream_spectrogram`` — is one
 launch of ``vaura_spectrogram`` (csrc/spectrogram.hip) in the same way: log-mel or linear columns, one per codec frame at hop 512, the
 streamed columns concatenated being the one-pass result bit for bit.
+
+Loudness for a stream — ``LoudnessTarget`` / ``measure_loudness`` / ``normalize_loudness_causal`` / ``LoudnessStream`` /
+``stream_loudness`` — is ``vaura_audio_loudness_push`` (csrc/loudness.hip): an ITU-R BS.1770 meter (momentary, short-term, integrated)
+and a causal normaliser whose gain at a sample depends only on the 100 ms steps completed before it, so every pushed sample leaves in
+the same push and the pushes concatenated are the one-pass result bit for bit.  ``normalize_audio(strategy="loudness")`` keeps its own
+kernel and its bits.
 """
 from __future__ import annotations
 
@@ -25,6 +31,7 @@ import torch
 from . import _lib as L
 from . import audio_out as AO
 from . import clip_params
+from . import loudness as LD
 from . import spectrogram as SG
 
 _STRATEGIES = {"clip": 0, "peak": 1, "rms": 2, "": 3, "none": 3}
@@ -175,8 +182,8 @@ _PCM_FORMATS = {torch.int16: 0, torch.int32: 1, torch.float32: 2}      # VAURA_P
 class PcmFormat:
     """What the consumer of the audio takes: ``rate`` Hz, ``dtype`` int16 / int32 / float32, ``channels`` copies of the mono signal
     (1 .. 8), interleaved (B, N, C) or planar (B, C, N), and a ``gain`` — one factor, or one per clip — applied before the
-    conversion (the only scaling a stream can have: ``normalize_audio`` needs whole-clip statistics).  Refused here: a rate the
-    resampler's table refuses (8 kHz and below need more than 64 taps per phase from 44.1 kHz), another dtype, ``channels`` outside 1 .. 8."""
+    conversion (``normalize_audio`` needs whole-clip statistics; ``stream_loudness`` underneath levels a stream causally).
+    Refused here: a rate the resampler's table refuses (8 kHz and below need more than 64 taps per phase from 44.1 kHz), another dtype, ``channels`` outside 1 .. 8."""
 
     def __init__(self, rate: int = 48000, dtype: torch.dtype = torch.int16, channels: int = 2, interleaved: bool = True,
                  gain: Union[float, Sequence[float]] = 1.0):
@@ -215,18 +222,18 @@ def _pcm_table(pl: AO.OutputPlan, dev: torch.device):
 
 
 class _RecordRing:
-    """Pinned (B, 5) int64 buffers for the per-clip records, allocated once and reused in turn.  A slot is taken again only when the
+    """Pinned (B, width) int64 buffers for the per-clip records, allocated once and reused in turn.  A slot is taken again only when the
     copy that last read it has finished (its event is queried, never waited for); while it has not, a fresh pinned tensor serves
     that one push, so the host never waits for the device."""
     SLOTS = 4
 
-    def __init__(self, clips: int):
-        self.clips, self.slots, self.events, self.at = clips, [], [], 0
+    def __init__(self, clips: int, width: int = AO.RECORD):
+        self.clips, self.width, self.slots, self.events, self.at = clips, width, [], [], 0
 
     def send(self, records: List[List[int]], dev: torch.device) -> torch.Tensor:
         host = torch.tensor(records, dtype=torch.int64)
         if len(self.slots) < self.SLOTS:
-            self.slots.append(torch.empty(self.clips, AO.RECORD, dtype=torch.int64).pin_memory())
+            self.slots.append(torch.empty(self.clips, self.width, dtype=torch.int64).pin_memory())
             self.events.append(torch.cuda.Event())
             i = len(self.slots) - 1
         else:
@@ -598,4 +605,201 @@ def stream_spectrogram(blocks: Iterable[dict], fmt: SpectrogramFormat) -> Iterat
         spec, counts = stream.push(audio, [f * hop for f in frames], final=bool(blk["final"]))
         out = dict(blk)
         out.update(spectrogram=spec, spec_start=start, spec_columns=counts)
+        yield out
+
+
+# ------------------------------------------------------------------------------------------------ loudness: a meter and a causal normaliser
+def _number(name, v, lo=None, hi=None) -> float:
+    if isinstance(v, bool) or not isinstance(v, (int, float)) or v != v or v in (float("inf"), float("-inf")):
+        raise L.VauraHipError(f"{name} must be a finite number, got {v!r}")
+    if (lo is not None and v < lo) or (hi is not None and v > hi):
+        raise L.VauraHipError(f"{name} must lie in {lo} .. {hi}, got {v!r}")
+    return float(v)
+
+
+class LoudnessTarget:
+    """Where a causal normaliser steers: ``target_lkfs`` (the integrated loudness aimed at; -12 is ``normalize_audio``'s
+    ``loudness_headroom_db``), ``max_gain_db`` (the clamp on the correction, either way), ``slew_db_per_s`` (None: unlimited; else the most
+    the correction moves per second), ``initial_gain_db`` (the gain before the first integrated value exists), ``limiter`` "clip"
+    (``_clip_wav``) or "tanh" (``tanhf`` then the clip: the reference's ``loudness_compressor``), ``sample_rate`` and ``history_steps``
+    (8 .. 4096: the 100 ms steps the integrated loudness looks back over; the state of a stream does not grow with the audio).  Refused
+    here: a rate the meter refuses (outside 8 .. 48 kHz, or 11 025 Hz, whose gating block is not four whole steps), a history outside
+    its range, a non-finite or out-of-range number, another limiter."""
+
+    def __init__(self, target_lkfs: float = -12.0, max_gain_db: float = 20.0, slew_db_per_s: Optional[float] = None,
+                 initial_gain_db: float = 0.0, limiter: str = "clip", sample_rate: int = 44100, history_steps: int = LD.MAX_HISTORY):
+        self.plan = LD.LoudnessPlan(sample_rate)                          # raises for rates the meter refuses
+        self.history_steps = LD.check_history(history_steps)
+        self.target_lkfs = _number("target_lkfs", target_lkfs, -70.0, 0.0)
+        self.max_gain_db = _number("max_gain_db", max_gain_db, 0.0, 80.0)
+        self.initial_gain_db = _number("initial_gain_db", initial_gain_db, -80.0, 80.0)
+        self.slew_db_per_s = None if slew_db_per_s is None else _number("slew_db_per_s", slew_db_per_s, 1e-3, 1e6)
+        if limiter not in LD.LIMITERS:
+            raise L.VauraHipError(f"VAURA_ERR_DTYPE: limiter must be one of {sorted(LD.LIMITERS)}, got {limiter!r}")
+        self.limiter, self.sample_rate = limiter, sample_rate
+
+    def __repr__(self):
+        return (f"LoudnessTarget(target_lkfs={self.target_lkfs}, max_gain_db={self.max_gain_db}, slew_db_per_s={self.slew_db_per_s}, "
+                f"initial_gain_db={self.initial_gain_db}, limiter={self.limiter!r}, sample_rate={self.sample_rate}, "
+                f"history_steps={self.history_steps})")
+
+
+_loud_tables: Dict[Tuple[int, str], torch.Tensor] = {}
+
+
+def _loud_table(pl: LD.LoudnessPlan, dev: torch.device) -> torch.Tensor:
+    """the fp64 chunk table of a rate on a device, built once"""
+    key = (pl.rate, str(dev))
+    if key not in _loud_tables:
+        _loud_tables[key] = torch.from_numpy(pl.table()).to(dev)
+    return _loud_tables[key]
+
+
+class LoudnessStream:
+    """The causal normaliser block by block: ``push`` takes the next samples of every clip and returns them normalised — all of them:
+    the gain at a sample depends only on the 100 ms steps completed before it, so nothing is held back and ``final`` has no tail to
+    flush.  The pushes concatenated per clip are bit for bit ``normalize_loudness_causal`` of the whole clips.  State: one integer per
+    clip on the host (samples received) and one buffer on the device (per clip the filter state in fp64, the current gains, a ring of
+    ``max(history_steps, 32)`` step energies and the raw tail shorter than one step): it does not grow with the audio.  One push is
+    one launch (two above 16384 samples a row), one asynchronous copy of a (B, 2) record from a pinned buffer the stream keeps and two
+    allocations (the samples; everything else the launch writes); nothing waits for the device."""
+
+    def __init__(self, target: LoudnessTarget, batch: int, device):
+        if not isinstance(target, LoudnessTarget):
+            raise L.VauraHipError(f"LoudnessStream takes a LoudnessTarget, got {type(target).__name__}")
+        if isinstance(batch, bool) or not isinstance(batch, int) or batch < 1:
+            raise L.VauraHipError(f"LoudnessStream takes a batch of at least one clip, got {batch!r}")
+        self.target, self.batch, self.device = target, batch, torch.device(device)
+        if self.device.type != "cuda":
+            raise L.VauraHipError("the loudness meter runs on the HIP device that holds the decoded waveform; there is no CPU path")
+        if self.device.index is None:
+            self.device = torch.device("cuda", torch.cuda.current_device())
+        self.received, self.finished = [0] * batch, [False] * batch
+        words = L.lib().vaura_audio_loudness_state_elems(batch, target.sample_rate, target.history_steps)
+        self._state = torch.empty(words, dtype=torch.float32, device=self.device)      # a clip's first push reads none of it
+        self._clipped = torch.zeros(batch, dtype=torch.int32, device=self.device)
+        self._ring = _RecordRing(batch, LD.RECORD)
+        self._empty = torch.zeros(batch, 1, 1, dtype=torch.float32, device=self.device)
+
+    _per_clip = PcmStream._per_clip
+
+    def push(self, audio: Optional[torch.Tensor], samples=None, final=False, _meter_only: bool = False) -> Tuple[torch.Tensor, dict]:
+        """audio (B, 1, n) fp32 on the stream's device: the next ``samples[b]`` samples of clip b (default: all n; 0 is allowed, and
+        ``audio`` may be None when every clip gives 0) -> (out (B, 1, n): clip b's ``samples[b]`` normalised samples, zeros behind them,
+        info).  ``info``: "gain_db" and "integrated" ((B,) fp32 on the device: the correction and the integrated loudness at the clip's
+        last 100 ms boundary, NaN while undefined), "momentary" ((B, max blocks) fp32: the momentary loudness of the 400 ms blocks this
+        push completed, NaN behind them) with "blocks" (how many per clip), "short_term" / "windows" likewise for the 3 s windows,
+        "integrated_steps" ((B, max boundaries): the integrated loudness at every boundary the push reached) with "boundaries", and
+        "clipped" ((B,) int32: the samples so far with |x g| > 1 — the stream's own running counter, the same tensor in every push's
+        info: clone it to keep a block's figure).  ``final`` (a bool, or one per clip) only closes the clip: a
+        finished clip takes no more samples."""
+        if audio is None:
+            x, n = self._empty, 0
+        else:
+            x = _mono_rows(audio, "LoudnessStream.push")
+            n = x.shape[-1]
+            if x.shape[0] != self.batch or x.device != self.device:
+                raise L.VauraHipError(f"LoudnessStream of {self.batch} clips on {self.device}: got a block of shape {tuple(audio.shape)} "
+                                      f"on {x.device}")
+            if n == 0:
+                x = self._empty
+        counts = [n] * self.batch if samples is None else self._per_clip("samples", samples, int)
+        fin = self._per_clip("final", final, bool)
+        if min(counts) < 0 or max(counts) > n:
+            raise L.VauraHipError(f"samples must lie in 0 .. {n} (the samples of a block's row), got {counts}")
+        for b in range(self.batch):
+            if self.finished[b] and counts[b]:
+                raise L.VauraHipError(f"clip {b} of the stream was closed (final) and takes no more samples; got {counts[b]}")
+        t, dev, B = self.target, self.device, self.batch
+        rec = LD.push_records(t.plan, self.received, counts)
+        stride = rec["stride"]
+        with torch.cuda.device(dev):
+            records = self._ring.send(rec["records"], dev)
+            out = None if _meter_only else torch.empty_like(x)
+            # one buffer per push for everything the launch writes beside the samples: gains (B, stride + 2), meter (3, B, stride), info (B, 2)
+            work = torch.empty(B * (stride + 2) + 3 * B * stride + 2 * B, dtype=torch.float32, device=dev)
+            gains = work[:B * (stride + 2)]
+            meter = work[B * (stride + 2):B * (stride + 2) + 3 * B * stride].view(3, B, stride)
+            info = work[B * (stride + 2) + 3 * B * stride:].view(B, 2)
+            table = _loud_table(t.plan, dev)
+            slew = 0.0 if t.slew_db_per_s is None else 0.1 * t.slew_db_per_s
+            L.check(L.lib().vaura_audio_loudness_push(L.ptr(x), L.ptr(out), B, x.shape[-1], L.ptr(records), L.ptr(self._state),
+                                                      t.sample_rate, t.history_steps, L.ptr(table), table.numel(), t.target_lkfs,
+                                                      t.max_gain_db, slew, t.initial_gain_db, LD.LIMITERS[t.limiter], L.ptr(gains),
+                                                      L.ptr(meter), stride, L.ptr(info), L.ptr(self._clipped), L.current_stream(dev)),
+                    "vaura_audio_loudness_push")                  # (the launch adds to the stream's own clipped counter)
+        self.received = rec["received"]
+        self.finished = [a or b for a, b in zip(self.finished, fin)]
+        if out is not None and n == 0:
+            out = out[:, :, :0]
+        return out, {"gain_db": info[:, 0], "integrated": info[:, 1], "momentary": meter[1, :, :max(rec["blocks"])],
+                     "blocks": rec["blocks"], "short_term": meter[2, :, :max(rec["windows"])], "windows": rec["windows"],
+                     "integrated_steps": meter[0, :, :max(rec["boundaries"])], "boundaries": rec["boundaries"],
+                     "clipped": self._clipped}
+
+
+def _loud_lengths(x: torch.Tensor, lengths) -> List[int]:
+    B, N = x.shape[0], x.shape[-1]
+    if N < 1:
+        raise L.VauraHipError(f"a waveform of shape {tuple(x.shape)} holds no samples")
+    if lengths is None:
+        return [N] * B
+    if not clip_params.is_per_clip(lengths):
+        raise L.VauraHipError(f"lengths must be one integer per clip (a list, tuple or 1-D tensor), got {lengths!r}")
+    n_in = clip_params._int_list("lengths", lengths)
+    if len(n_in) != B:
+        raise L.VauraHipError(f"per-clip lengths has {len(n_in)} values for a batch of {B} clips")
+    if min(n_in) < 1 or max(n_in) > N:
+        raise L.VauraHipError(f"lengths must lie in 1 .. {N} (the samples of a row), got {n_in}")
+    return n_in
+
+
+def normalize_loudness_causal(wav: torch.Tensor, target: LoudnessTarget, lengths=None) -> Tuple[torch.Tensor, dict]:
+    """wav (B, 1, N) fp32 on a HIP device -> (out, info): what a ``LoudnessStream`` of ``target`` returns for the clips, whole: sample i
+    of a clip is scaled by a gain that follows the integrated loudness of the 100 ms steps completed before i towards ``target_lkfs``
+    (``LoudnessStream.push`` names the entries of ``info``).  ``lengths`` (the "audio_lengths" of a ragged ``generate()``): clip b is
+    exactly the clip normalised alone at its own length, zeros follow it, and nothing behind ``lengths[b]`` is read."""
+    x = _mono_rows(wav, "normalize_loudness_causal")
+    n_in = _loud_lengths(x, lengths)
+    if not x.is_cuda:
+        raise L.VauraHipError("the loudness meter runs on the HIP device that holds the decoded waveform; there is no CPU path")
+    return LoudnessStream(target, x.shape[0], x.device).push(x, samples=n_in, final=True)
+
+
+def measure_loudness(wav: torch.Tensor, lengths=None, sample_rate: int = 44100, history_steps: int = LD.MAX_HISTORY) -> dict:
+    """wav (B, 1, N) fp32 on a HIP device -> {"integrated" (B,): the integrated loudness in LKFS at each clip's last 100 ms boundary,
+    over the blocks of its last ``history_steps`` steps; "momentary" (B, max blocks): one value per 400 ms block, every 100 ms;
+    "short_term" (B, max windows): the same over 3 s; "blocks" (per clip, on the host); "windows"; "step" (samples per 100 ms)}, fp32 on
+    the device, NaN where undefined (a clip shorter than one block, no block above the gates) and behind a clip's values."""
+    x = _mono_rows(wav, "measure_loudness")
+    n_in = _loud_lengths(x, lengths)
+    target = LoudnessTarget(sample_rate=sample_rate, history_steps=history_steps)
+    if not x.is_cuda:
+        raise L.VauraHipError("the loudness meter runs on the HIP device that holds the decoded waveform; there is no CPU path")
+    _, info = LoudnessStream(target, x.shape[0], x.device).push(x, samples=n_in, final=True, _meter_only=True)
+    return {"integrated": info["integrated"], "momentary": info["momentary"], "short_term": info["short_term"],
+            "blocks": info["blocks"], "windows": info["windows"], "step": target.plan.step}
+
+
+def stream_loudness(blocks: Iterable[dict], target: LoudnessTarget) -> Iterator[dict]:
+    """Wrap a streaming generator (``generate_stream``, ``generate_long_stream`` with or without ``block_frames``,
+    ``generate_long_clips_stream``) or the blocks of a live session: every dict comes back with "audio" replaced by the normalised
+    block and "loudness_gain_db", "loudness_integrated", "loudness_momentary", "loudness_blocks", "loudness_short_term",
+    "loudness_windows" and "loudness_clipped" (the stream's running counter: one tensor for all blocks) added (the
+    entries of ``LoudnessStream.push``'s info); every other key passes through, so ``stream_pcm`` and ``stream_spectrogram`` compose on
+    top.  No sample is held back: a block's audio is the block's audio."""
+    stream = None
+    for blk in blocks:
+        audio = blk["audio"]
+        B = audio.shape[0]
+        frames = blk["frames"]
+        frames = [int(f) for f in frames] if isinstance(frames, (list, tuple)) else [int(frames)] * B
+        hop = audio.shape[-1] // max(frames) if max(frames) > 0 else 0
+        if stream is None:
+            stream = LoudnessStream(target, B, audio.device)
+        norm, info = stream.push(audio, [f * hop for f in frames], final=bool(blk["final"]))
+        out = dict(blk)
+        out.update(audio=norm.reshape(audio.shape), loudness_gain_db=info["gain_db"], loudness_integrated=info["integrated"],
+                   loudness_momentary=info["momentary"], loudness_blocks=info["blocks"], loudness_short_term=info["short_term"],
+                   loudness_windows=info["windows"], loudness_clipped=info["clipped"])
         yield out
